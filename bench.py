@@ -2,7 +2,11 @@
 """Headline benchmark: atom-steps/sec (energy + forces) of HVNet, fp32, synthetic data, random-init (seeded)
 weights; model of BASELINE.json configs[1]: rc=5 A, hidden=128, num_rbf=128, 5 layers, 3 elements.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config auto|c2|c4|weak] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config auto|c2|c4|weak] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-secondary]]
+
+A plain run measures the headline only: set-up, W warm-up steps, K timed steps, the result line.  `--full` adds the
+per-kernel / roofline figures, the secondaries and the CPU baseline.
 
 A "step" = HVNet.forward(data) + autograd.grad(E, pos) on a prebuilt `Data` (neighbour list excluded, as in
 SURVEY.md section 8(d)); the relation-ordered graph build (the replacement of the reference's per-layer
@@ -301,8 +305,9 @@ def self_peer_secondary(timeout=240.0):
     line is condensed here.  What a one-GPU box can say about the 8-GPU curve: `projected_speedup_at_8` = the unsharded 100k
     cell's step / this step -- compute, launches and stream hand-offs are real, the links are not (a local copy)."""
     import subprocess
+    # (--full: the child's comm block and secondaries are what is condensed below)
     cmd = [sys.executable, os.path.abspath(__file__), "--self-peer", "1", "--config", "c2", "--reps", "10,10,31", "--steps", "30",
-           "--warmup", "5", "--no-cpu-baseline"]
+           "--warmup", "5", "--full", "--no-cpu-baseline"]
     env = dict(os.environ, HERMNET_BENCH_CHILD="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
@@ -617,6 +622,27 @@ def rank_fence(sharded, backend, dev):
     return fence
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """`--dump-outputs`: one float32 DIR/<name>.npy per array, for comparing two builds output for output.  Every array gets
+    an equal share of DUMP_LIMIT_BYTES for all the files it writes; one over its share is cut to a fixed (seeded) sample of
+    its rows, in row order, and the row indices (float64) go to <name>_rows.npy, counted in the same share."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    header = 4096                                   # an upper bound on an .npy header
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() * 4 + header > share:
+            keep = (share - 2 * header) // (4 * max(1, t[0].numel()) + 8)
+            rows = torch.randperm(t.size(0), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            np.save(os.path.join(path, name + "_rows.npy"), rows.numpy().astype(np.float64))
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+
+
 def launch_rehearsal(args, world, rank):
     """`--launch-rehearsal`: the launcher, rendezvous, fences and the max-over-ranks timing around an EMPTY step --
     no model, no GPU, nothing measured (value null).  What the CPU suite can check of the N > 1 command line."""
@@ -742,8 +768,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="auto", choices=["auto", "c2", "c4", "weak"],
                     help="workload (see the module docstring); auto = c2 on one GPU, c4 (strong scaling) on several")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="headline step only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-kernel, roofline and node-GEMM figures (HIP events inside the "
+                         "timed steps), the secondaries and the CPU baseline (single GPU), the halo-exchange costs and the "
+                         "unsharded comparison (sharded).  A plain run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0): DIR/energy.npy and "
+                         "DIR/forces.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: no secondaries (profiling runs)")
     ap.add_argument("--shard-anyway", action="store_true",
                     help="take the sharded (process-group) code path even with one rank: rehearsal of the RCCL calls "
                          "on a single GPU (launch through torch.distributed.run --nproc-per-node 1)")
@@ -902,7 +935,8 @@ def main():
         step()
     if online_tuning:
         freeze_gemm_tuning()
-    timer = ops.KernelTimer()
+    # --full: the message kernels bracketed with HIP events inside the timed steps (the roofline figure)
+    timer = ops.KernelTimer() if args.full else None
     ops.set_kernel_timer(timer)
     fence()
     t0 = time.perf_counter()
@@ -914,19 +948,22 @@ def main():
     ops.set_kernel_timer(None)
     dt_local = dt
     dt = max_over_ranks(dt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"energy": e, "forces": f})
 
     # ---- after the timed region: the dense linears, timed with HIP events in a short pass of their own (an event
     # pair costs ~15 us of host time; ~50 of them per step inside the timed region would distort a ~3 ms step)
-    gtimer = ops.KernelTimer(prefix=("gemm", "node_"))
-    ops.set_kernel_timer(gtimer)
-    for _ in range(3):
-        step()
-    torch.cuda.synchronize()
-    ops.set_kernel_timer(None)
+    if args.full:
+        gtimer = ops.KernelTimer(prefix=("gemm", "node_"))
+        ops.set_kernel_timer(gtimer)
+        for _ in range(3):
+            step()
+        torch.cuda.synchronize()
+        ops.set_kernel_timer(None)
 
     # ---- sharded runs: what the halo exchanges cost (every rank takes part; rank 0 prints)
     comm = None
-    if sharded:
+    if sharded and args.full:
         try:
             # this rank's own kernels per step: message kernels (timed region) + node chain kernels (the pass above)
             own_ms = (sum(c * ms for _, (c, ms) in timer.summary().items()) / args.steps
@@ -939,7 +976,7 @@ def main():
     # ---- secondary, all ranks: the step INCLUDING planning (sharded: slab plan + slab-local neighbour search;
     # single GPU: the device neighbour search), i.e. what one MD step costs end to end
     md = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         from hermnet_amd.neighbor import neighbor_search
         if sharded:
             md_valid = []
@@ -1008,7 +1045,7 @@ def main():
             fence()
             replan_ms = max_over_ranks(time.perf_counter() - t1) / 3 * 1e3
 
-    if rank == 0:
+    if rank == 0 and args.full:
         ksum = timer.summary()            # name -> (launches, mean ms), HIP events on the launch stream
         ab = algorithmic_bytes(E, N, H, T)
         kernels = {}
@@ -1071,6 +1108,7 @@ def main():
                                           "of the layer above (hn_pending_grads: what message_bwd_finish + layernorm_bwd_parts did "
                                           "in two launches outside this section): +12-15 us per launch of memory-bound work counted "
                                           "here, 1 % off the step; HERMNET_DEFER_SUMS=0 gives the separate launches")
+    if rank == 0:
         names = {"c2": "configs[1]: %d-atom 3-element fcc alloy (Al/Ni/Cu)",
                  "c4": "configs[3]: FIXED %d-atom 3-element fcc alloy cell (10x10x250, 36x36x900 A)",
                  "weak": "weak-scaling variant: %d-atom 3-element fcc alloy cell (10x10x25N)"}
@@ -1094,15 +1132,16 @@ def main():
                        "1 GPU" if world == 1 else
                        "atom-sharded x%d slabs (slab-local planning), one-hop halo all-to-all per layer over %s"
                        % (world, args.backend)},
-            "roofline": {"bound": limiter[dom], "kernel": dom, "achieved": kernels[dom]["GBps"], "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": kernels[dom]["GBps"] / HBM_PEAK_GBS, "traffic": traffic,
-                         "note": "achieved/peak/frac are ALGORITHMIC HBM bytes per launch / HIP-event time vs the 8 TB/s "
-                                 "HBM peak; `bound` names what limits the kernel in practice"},
-            "mfma": mfma,
-            "kernels": kernels,
             "energy": float(e.detach()[0]),
             "library": _lib.build_info(),
         }
+        if args.full:
+            out["roofline"] = {"bound": limiter[dom], "kernel": dom, "achieved": kernels[dom]["GBps"], "peak": HBM_PEAK_GBS,
+                               "unit": "GB/s", "frac": kernels[dom]["GBps"] / HBM_PEAK_GBS, "traffic": traffic,
+                               "note": "achieved/peak/frac are ALGORITHMIC HBM bytes per launch / HIP-event time vs the 8 TB/s "
+                                       "HBM peak; `bound` names what limits the kernel in practice"}
+            out["mfma"] = mfma
+            out["kernels"] = kernels
         if comm is not None:
             out["comm"] = comm
         if md is not None:
@@ -1119,7 +1158,7 @@ def main():
                                          "steps_repeated": stepper.repeats,
                                          "planning_note": "plan reused under the Verlet skin (static coordinates here); a "
                                                           "re-plan costs replan_ms more on the step that needs it"})
-        if sharded and not args.no_secondary and cfg != "weak":
+        if sharded and args.full and not args.no_secondary and cfg != "weak":
             # the strong-scaling baseline inside the same run: the same cell, unsharded, on rank 0's GPU
             try:
                 d1 = synth.fcc_alloy(reps=reps, seed=0, device=dev)
@@ -1141,7 +1180,7 @@ def main():
                 del d1
             except Exception as ex:
                 out["secondary"]["single_gpu_same_cell"] = {"error": repr(ex)}
-        if world == 1 and not sharded and not args.no_secondary:
+        if world == 1 and not sharded and args.full and not args.no_secondary:
             try:      # kernel launches of ONE step, counted by the profiler (every device kernel, torch's included)
                 out["secondary"]["launches_per_step"], out["secondary"]["launches_per_step_own_kernels"] = count_launches(step)
             except Exception as ex:
@@ -1186,7 +1225,7 @@ def main():
                 out["secondary"]["training"] = training_secondary(hn, synth, dev, model_kw)
             except Exception as ex:      # never lose the headline line over the secondary figure
                 out["secondary"]["training"] = {"error": repr(ex)}
-        if world == 1 and not sharded and not args.no_cpu_baseline:
+        if world == 1 and not sharded and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model_kw, elems, seed)
         print(json.dumps(out), flush=True)
     if sharded:

@@ -24,5 +24,5 @@ cp $O/traffic.json profiles/traffic.json      # bench.py reads roofline.traffic 
 cp $(ls $O/stats/*/*_kernel_stats.csv | head -1) $O/kernel_stats.csv
 cp $(ls $O/pmc/FETCH_SIZE/*/*_counter_collection.csv | head -1) $O/pmc_FETCH_SIZE.csv
 cp $(ls $O/pmc/WRITE_SIZE/*/*_counter_collection.csv | head -1) $O/pmc_WRITE_SIZE.csv
-python bench.py > $O/bench.json 2> $O/bench.err
+python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 400 $O/bench.json
