@@ -1,0 +1,282 @@
+"""Training step on every route of the differentiable path against the oracle in float64.
+
+`test_training.py` checks the step on the reference's own goldens, which all take the same few routes (Gaussian basis,
+polynomial envelope, H of 64 or 128, two layers, one small cell each).  The step chooses between kernels and torch
+fallbacks by shape: bucketed or materialised basis (hermnet.py), the basis-window kernel (rmnet.RadialBasis.bucketed),
+the band-product kernels (3H <= 480, 3H % 32 == 0), the column-sum kernel (O % 4, O <= 1024, K >= 256), chunked Gram
+products (more than trainops._SPLIT_K_ROWS rows per relation), the fused node stages and message kernels (H % 4 == 0), the
+read-back edge total (atoms of an unknown element), empty relations and the tight row layout.  Each case below runs one
+full step (`autograd.grad(E, pos, create_graph=True)`, `loss.backward()`) with the pure force loss and with the pure
+energy loss, compares the loss terms and every parameter gradient with `oracle.training_loss_and_grads` evaluated in
+float64, and asserts which routes it took, so that a retuned threshold cannot empty the matrix silently.
+
+Gradient tolerance: max(GRAD_TOL, 2 d32), d32 = the same metric for the fp32 oracle against the fp64 oracle on the same
+case.  Where fp32 arithmetic itself stays within GRAD_TOL / 2 this is GRAD_TOL; deeper or wider cases may use no more
+than twice what an fp32 evaluation of the reference arithmetic makes."""
+import copy
+import functools
+import math
+
+import pytest
+import torch
+
+import hermnet_amd as hn
+from hermnet_amd import synth, trainops
+from hermnet_amd.synth import synth_state_dict
+from oracle import hermnet_oracle as orc
+from test_training import GRAD_TOL, assert_grads_close, training_step
+
+pytestmark = pytest.mark.gpu
+
+
+def _alloy(reps, species=(13, 28, 29), rc=5.0):
+    return synth.fcc_alloy(reps=reps, species=species, rc=rc)
+
+
+def _with_gold(d, rows=(3, 40, 77)):
+    z = d.atomic_number.clone()
+    z[list(rows)] = 79                       # gold: not an element of the model
+    d.atomic_number = z
+    return d
+
+
+ALNICU = ["Al", "Ni", "Cu"]
+HCO = ["H", "C", "O"]
+EXPENV = {"name": "exponential"}
+
+# name: (system, elements, model keywords, weight seed)
+CASES = {
+    "scale_T1": (lambda: _alloy((8, 8, 9), species=(13,)), ["Al"],
+                 dict(hidden_channels=64, num_rbf=32, num_layers=2), 31),
+    "bench_shape": (lambda: synth.molecule_batch(num_graphs=128), HCO,
+                    dict(hidden_channels=128, num_rbf=128, num_layers=5), 32),
+    "bench_shape_intensive": (lambda: synth.molecule_batch(num_graphs=64, seed=1), HCO,
+                              dict(hidden_channels=128, num_rbf=128, num_layers=5, intensive=True), 33),
+    "wide_256": (lambda: _alloy((4, 4, 4)), ALNICU, dict(hidden_channels=256, num_rbf=64, num_layers=2), 34),
+    "default_512": (lambda: _alloy((4, 4, 4)), ALNICU, dict(hidden_channels=512, num_rbf=128, num_layers=2), 35),
+    "width_100": (lambda: synth.molecule_batch(num_graphs=8, seed=2), HCO,
+                  dict(hidden_channels=100, num_rbf=32, num_layers=2), 36),
+    "width_50": (lambda: synth.molecule_batch(num_graphs=8, seed=3), HCO,
+                 dict(hidden_channels=50, num_rbf=32, num_layers=2), 37),
+    "bessel_exp": (lambda: _alloy((2, 2, 3), rc=4.0), ALNICU,
+                   dict(rc=4.0, hidden_channels=64, num_rbf=16, num_layers=2, rbf={"name": "spherical_bessel"},
+                        envelope=EXPENV), 38),
+    "bernstein": (lambda: _alloy((2, 2, 3), rc=4.0), ALNICU,
+                  dict(rc=4.0, hidden_channels=64, num_rbf=16, num_layers=2, rbf={"name": "bernstein"}), 39),
+    "gauss_expenv": (lambda: _alloy((2, 2, 3), rc=4.0), ALNICU,
+                     dict(rc=4.0, hidden_channels=64, num_rbf=32, num_layers=2, envelope=EXPENV), 40),
+    "small_R": (lambda: _alloy((2, 2, 3), rc=4.0), ALNICU, dict(rc=4.0, hidden_channels=64, num_rbf=8, num_layers=2), 41),
+    "large_R": (lambda: _alloy((2, 2, 3), rc=4.0), ALNICU, dict(rc=4.0, hidden_channels=64, num_rbf=300, num_layers=2), 42),
+    "unknown_element": (lambda: _with_gold(_alloy((3, 3, 3))), ALNICU,
+                        dict(hidden_channels=64, num_rbf=32, num_layers=2), 43),
+    "absent_element": (lambda: _alloy((3, 3, 3), species=(13, 28)), ALNICU,
+                       dict(hidden_channels=64, num_rbf=32, num_layers=2), 44),
+    "skewed": (lambda: _alloy((3, 3, 3), species=(13, 13, 13, 13, 28, 29)), ALNICU,
+               dict(hidden_channels=64, num_rbf=32, num_layers=2), 45),
+    # (polynomial envelope only: the exponential one overflows past the cutoff in the oracle and the reference alike)
+    "list_past_cutoff": (lambda: _alloy((3, 3, 3), rc=5.0), ALNICU, dict(rc=4.0, hidden_channels=64, num_rbf=32, num_layers=2), 46),
+}
+LOSSES = {"force": 1.0, "energy": 0.0}
+
+
+def _oracle_kwargs(kw):
+    out = dict(rc=kw.get("rc", 5.0), intensive=kw.get("intensive", False), num_layers=kw["num_layers"],
+               hidden_channels=kw["hidden_channels"], num_rbf=kw["num_rbf"])
+    if "rbf" in kw:
+        out["rbf"] = kw["rbf"]
+    if "envelope" in kw:
+        out["envelope_spec"] = kw["envelope"]
+    return out
+
+
+def _double(d):
+    """The data with its floating tensors in float64 (an exact cast)."""
+    kw = {k: d.get(k) for k in ("pos", "atomic_number", "edge_index", "batch", "edge_shift", "cell") if d.get(k) is not None}
+    return hn.Data(**{k: (v.double() if v.is_floating_point() else v) for k, v in kw.items()})
+
+
+@functools.lru_cache(maxsize=2)
+def _inputs(name):
+    """(data [host, fp32], elements, model keywords, weights [fp32], per-graph energy target y, force target, fp64 energies)."""
+    system, elems, kw, seed = CASES[name]
+    d = system()
+    sd = synth_state_dict(hn.HVNet(elems, **kw).state_dict(), seed)
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    d64 = _double(d)
+    with torch.no_grad():
+        e64 = orc.hvnet_energy(sd64, elems, d64.pos, d64.atomic_number, d64.edge_index, d64.batch, d64.get("edge_shift"),
+                               d64.get("cell"), **_oracle_kwargs(kw))
+    # targets as test_training.py's: |E - y| ~ 0.5, so that the (extensive) energy term does not swamp the force term
+    gen = torch.Generator().manual_seed(seed)
+    y = (e64 + 0.5 * torch.randn(e64.shape, generator=gen, dtype=torch.float64)).float()
+    ftgt = 0.5 * torch.randn(d.pos.shape, generator=gen)
+    return d, elems, kw, sd, y, ftgt, e64
+
+
+@functools.lru_cache(maxsize=4)
+def _oracle(name, gamma):
+    """fp64 oracle (loss, e_loss, f_loss, grads) and d32, the gradient metric of the fp32 oracle against it."""
+    d, elems, kw, sd, y, ftgt, _ = _inputs(name)
+    okw = _oracle_kwargs(kw)
+    sd64 = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items()}
+    r64 = orc.training_loss_and_grads(sd64, elems, _double(d), y.double(), ftgt.double(), gamma, **okw)
+    r32 = orc.training_loss_and_grads(sd, elems, d, y, ftgt, gamma, **okw)
+    ref = {k: v for k, v in r64[3].items() if v is not None}
+    d32 = assert_grads_close({k: v for k, v in r32[3].items() if v is not None}, ref, tol=math.inf)
+    return r64, d32
+
+
+@pytest.fixture
+def routes(monkeypatch):
+    """Pass-through wrappers that record which route each shape-dependent decision of the step took."""
+    rec = {"band": [], "col_sum": [], "col_sum_kernel": [], "split_k": [], "window": 0, "torch_message": 0,
+           "message_algebra": 0, "layer_norm_kernel": 0, "tall_linear": 0}
+
+    def wrap(owner, attr, note):
+        orig = getattr(owner, attr)
+
+        def f(*args):
+            out = orig(*args)
+            note(args, out)
+            return out
+        monkeypatch.setattr(owner, attr, f)
+
+    def count(key):
+        def note(args, out):
+            rec[key] += 1
+        return note
+
+    wrap(trainops, "_band_kernels", lambda a, ok: rec["band"].append((int(a[1]), bool(ok))))
+    wrap(trainops, "_col_sum_over_rows", lambda a, out: rec["col_sum"].append(tuple(a[0].shape)))
+    wrap(trainops._ColSum, "apply", lambda a, out: rec["col_sum_kernel"].append(tuple(a[0].shape)))
+    wrap(trainops, "_split_k_chunk", lambda a, c: rec["split_k"].append((int(a[0]), int(c))))
+    wrap(trainops.BasisWindow, "apply", count("window"))
+    wrap(trainops, "_edge_message_torch", count("torch_message"))
+    wrap(trainops.MessageAlgebra, "apply", count("message_algebra"))
+    wrap(trainops.LayerNorm2, "apply", count("layer_norm_kernel"))
+    wrap(trainops.TallLinear, "apply", count("tall_linear"))
+    return rec
+
+
+def _bucketed(d):
+    b = d._hn_edge_embed
+    assert isinstance(b, trainops.BucketedBasis), "expected the bucketed basis, got %s" % type(b).__name__
+    return b
+
+
+def _materialised(d):
+    assert torch.is_tensor(d._hn_edge_embed) and d._hn_edge_embed.dim() == 2, "expected a materialised [E,R] basis"
+
+
+def _edges_per_group(b):
+    """Edges (not padding rows) of every (relation, bucket) group of the bucketed basis."""
+    C = b.phi.size(1)
+    return torch.bincount(b.group[b.slot // C])
+
+
+def _band(rec, on):
+    assert rec["band"], "no band-product decision was made"
+    assert all(ok == on for _, ok in rec["band"]), rec["band"]
+
+
+def _col_sum_kernel_used(rec):
+    assert rec["col_sum_kernel"], "the column-sum kernel never ran"
+
+
+def _check_routes(name, rec, d, model):
+    g = d._hn_graph
+    H = model.hidden_channels
+    msg_kernels = lambda: rec["message_algebra"] > 0 and rec["torch_message"] == 0 and rec["layer_norm_kernel"] > 0
+    if name == "scale_T1":
+        b = _bucketed(d)
+        assert rec["window"] > 0
+        assert int(_edges_per_group(b).max()) > b.phi.size(1), "no (relation, bucket) group spans two chunks"
+        assert any(0 < c < k for k, c in rec["split_k"]), rec["split_k"]
+        assert any(k > trainops._SPLIT_K_ROWS for k, c in rec["split_k"]), rec["split_k"]
+        _col_sum_kernel_used(rec)
+        _band(rec, True)
+    elif name.startswith("bench_shape"):
+        b = _bucketed(d)
+        assert b.nb == 7
+        _band(rec, True)
+        assert g.num_graphs == int(d.batch.max()) + 1 > 1
+        assert msg_kernels()
+    elif name == "wide_256":
+        _bucketed(d)
+        _band(rec, False)
+        assert {n for n, _ in rec["band"]} == {3 * H}
+        _col_sum_kernel_used(rec)
+    elif name == "default_512":
+        _bucketed(d)
+        _band(rec, False)
+        # the [T, K, 3H] bias gradients of x_proj take the torch sums because of their width alone
+        assert any(o == 3 * H and k >= 256 for _, k, o in rec["col_sum"]), rec["col_sum"]
+        assert not any(o == 3 * H for _, _, o in rec["col_sum_kernel"]), rec["col_sum_kernel"]
+    elif name == "width_100":
+        _bucketed(d)
+        _band(rec, False)
+        assert msg_kernels()
+    elif name == "width_50":
+        _materialised(d)
+        assert rec["torch_message"] > 0 and rec["message_algebra"] == 0 and rec["layer_norm_kernel"] == 0
+    elif name in ("bessel_exp", "bernstein"):
+        _materialised(d)
+        assert rec["tall_linear"] > 0 and rec["window"] == 0
+    elif name == "gauss_expenv":
+        _bucketed(d)
+        assert rec["window"] == 0
+    elif name == "small_R":
+        b = _bucketed(d)
+        assert b.nb == 1 and b.num_radial < trainops.BucketedBasis.WIDTH
+    elif name == "large_R":
+        b = _bucketed(d)
+        assert b.nb == 16 and b.num_radial > model.radial_basis.FUSED_MAX_RBF
+    elif name == "unknown_element":
+        _bucketed(d)
+        assert not g._all_known and g.N > g.type_rowptr_host[-1]
+    elif name == "absent_element":
+        _bucketed(d)
+        bounds = g.rel_edge_bounds()
+        assert bounds[3] == bounds[2] and bounds[1] > 0 and bounds[2] > bounds[1], bounds
+    elif name == "skewed":
+        _bucketed(d)
+        assert not g.uniform
+    elif name == "list_past_cutoff":
+        b = _bucketed(d)
+        dist = d._hn_edge[:, 3].detach()
+        assert bool((dist > model.rc).any()) and bool((dist < model.rc).any())
+        assert b.slot.numel() == g.E
+    else:
+        raise AssertionError("no route assertions for case %s" % name)
+
+
+@pytest.mark.parametrize("loss", list(LOSSES))
+@pytest.mark.parametrize("name", list(CASES))
+def test_training_step_matches_fp64_oracle(name, loss, routes):
+    dev = torch.device("cuda:0")
+    gamma = LOSSES[loss]
+    d, elems, kw, sd, y, ftgt, e64 = _inputs(name)
+    (lo, leo, lfo, og), d32 = _oracle(name, gamma)
+
+    model = hn.HVNet(elems, **kw)
+    model.load_state_dict(sd)
+    model = model.to(dev).train()
+    dd = copy.copy(d).to(dev)              # (Data.to moves in place: the host copy stays for the next case)
+    l, le, lf = training_step(model, dd, y.to(dev), ftgt.to(dev), gamma)
+    _check_routes(name, routes, dd, model)
+
+    emax = max(1.0, float(e64.abs().max()))
+    assert abs(float(le) - float(leo)) < 2e-5 * emax * max(1.0, float(leo)), (float(le), float(leo))
+    assert abs(float(lf) - float(lfo)) < 2e-5 * max(1.0, float(lfo)), (float(lf), float(lfo))
+    assert abs(float(l) - float(lo)) < 2e-5 * emax * max(1.0, float(lo)), (float(l), float(lo))
+
+    grads = {k: p.grad for k, p in model.named_parameters()}
+    absent = [k for k, v in og.items() if v is None]
+    for k in absent:             # parameters of an element without atoms: no gradient, or an exact zero
+        assert grads.get(k) is None or not bool(grads[k].any()), k
+    # (only the absent element's parameters may go without a gradient: every other case compares every parameter)
+    assert bool(absent) == (name == "absent_element") and all(".Cu." in k for k in absent), absent
+    ref = {k: v for k, v in og.items() if v is not None}
+    tol = max(GRAD_TOL, 2 * d32)
+    worst = assert_grads_close({k: v for k, v in grads.items() if k not in absent}, ref, tol=tol)
+    print("%-22s %-6s worst %.2e  d32 %.2e  tol %.2e  worst/tol %.2f" % (name, loss, worst, d32, tol, worst / tol))
