@@ -3,6 +3,8 @@
 //   hermnet_edge_geometry_fwd  <- HVNet.with_edge              /root/reference/HermNet/hermnet.py:133-152
 //   hermnet_edge_geometry_bwd  <- autograd of the same w.r.t. pos (callers: plugin/ase_interface/calculator.py:77-83,
 //                                 plugin/lmp_interface/lmp_calc.py:50-56)
+//   hermnet_edge_geometry_bwd_virial <- the same position gradient plus the per-atom virial
+//                                 W_i = -1/2 sum_{e touching i} D_e (x) gD_e (no reference counterpart: DESIGN section 1)
 // Both are tiny, HBM-streaming kernels (E * ~50 B); one thread per edge / one wave per atom.
 #include <hip/hip_runtime.h>
 #include "../../include/hermnet_hip.h"
@@ -96,6 +98,90 @@ __global__ __launch_bounds__(256) void edge_geometry_bwd_csc_kernel(
   }
 }
 
+// The position gradient of the two kernels above plus the per-atom virial W_a = -1/2 sum_{e touching a} D_e (x) gD_e
+// (row-major [a][alpha*3+beta] = D_alpha gD_beta, unsymmetrised): each edge is split equally between its two atoms, an edge
+// between an atom and its own periodic image (in both walks of the row) counts fully.  D_e is recomputed with the
+// forward kernel's arithmetic (not rhat * d: d is clamped near 0).  Same wave per row, lane-to-edge assignment, walk order
+// and xor tree as the gradient-only kernels, so gpos is bit for bit theirs; nine more accumulators alongside.
+// CSC: the out-edges from the T CSC segments (edge_geometry_bwd_csc_kernel), else from out_rowptr / out_edges
+// (edge_geometry_bwd_kernel with in_edges = NULL).
+__device__ __forceinline__ float3 edge_vector(const float* __restrict__ pos, const int* __restrict__ src_id,
+                                              const int* __restrict__ tgt_id, const float* __restrict__ shift,
+                                              const float* __restrict__ cell, const int* __restrict__ batch, int e) {
+  const int j = src_id[e], i = tgt_id[e];
+  float dx = pos[3 * j + 0] - pos[3 * i + 0];
+  float dy = pos[3 * j + 1] - pos[3 * i + 1];
+  float dz = pos[3 * j + 2] - pos[3 * i + 2];
+  if (shift != nullptr) {
+    const float* c = cell + 9 * (batch ? batch[j] : 0);
+    const float s0 = shift[3 * e + 0], s1 = shift[3 * e + 1], s2 = shift[3 * e + 2];
+    dx += s0 * c[0] + s1 * c[3] + s2 * c[6];
+    dy += s0 * c[1] + s1 * c[4] + s2 * c[7];
+    dz += s0 * c[2] + s1 * c[5] + s2 * c[8];
+  }
+  return make_float3(dx, dy, dz);
+}
+
+template <bool CSC>
+__global__ __launch_bounds__(256) void edge_geometry_bwd_virial_kernel(
+    const float4* __restrict__ gD, const int* __restrict__ in_rowptr, const int* __restrict__ csc_rowptr,
+    const int* __restrict__ csc_pos, int T, const int* __restrict__ out_rowptr, const int* __restrict__ out_edges,
+    const float* __restrict__ pos, const int* __restrict__ src_id, const int* __restrict__ tgt_id,
+    const float* __restrict__ shift, const float* __restrict__ cell, const int* __restrict__ batch, int N,
+    float* __restrict__ gpos, float* __restrict__ atom_virial) {
+  const int a = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (a >= N) return;
+  const int lane = threadIdx.x & 63;
+  float sx = 0.f, sy = 0.f, sz = 0.f;
+  float w[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) w[q] = 0.f;
+  auto virial = [&](int e, const float4 g) {
+    const float3 D = edge_vector(pos, src_id, tgt_id, shift, cell, batch, e);
+    w[0] += D.x * g.x; w[1] += D.x * g.y; w[2] += D.x * g.z;
+    w[3] += D.y * g.x; w[4] += D.y * g.y; w[5] += D.y * g.z;
+    w[6] += D.z * g.x; w[7] += D.z * g.y; w[8] += D.z * g.z;
+  };
+  if (CSC) {
+    for (int t = 0; t < T; ++t) {
+      const int beg = csc_rowptr[(size_t)t * N + a], end = csc_rowptr[(size_t)t * N + a + 1];
+      for (int k = beg + lane; k < end; k += 64) {
+        const int e = csc_pos[k];
+        const float4 g = gD[e];
+        sx += g.x; sy += g.y; sz += g.z;
+        virial(e, g);
+      }
+    }
+  } else {
+    for (int k = out_rowptr[a] + lane; k < out_rowptr[a + 1]; k += 64) {
+      const int e = out_edges ? out_edges[k] : k;
+      const float4 g = gD[e];
+      sx += g.x; sy += g.y; sz += g.z;
+      virial(e, g);
+    }
+  }
+  for (int k = in_rowptr[a] + lane; k < in_rowptr[a + 1]; k += 64) {
+    const float4 g = gD[k];
+    sx -= g.x; sy -= g.y; sz -= g.z;
+    virial(k, g);
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    sx += __shfl_xor(sx, m, 64);
+    sy += __shfl_xor(sy, m, 64);
+    sz += __shfl_xor(sz, m, 64);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) w[q] += __shfl_xor(w[q], m, 64);
+  }
+  if (lane == 0) {
+    gpos[3 * a + 0] = sx;
+    gpos[3 * a + 1] = sy;
+    gpos[3 * a + 2] = sz;
+#pragma unroll
+    for (int q = 0; q < 9; ++q) atom_virial[9 * (size_t)a + q] = -0.5f * w[q];
+  }
+}
+
 }  // namespace
 
 extern "C" int hermnet_edge_geometry_fwd(const float* pos, const int* src_id, const int* tgt_id,
@@ -135,5 +221,32 @@ extern "C" int hermnet_edge_geometry_bwd_csc(const float* gD, const int* csr_row
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(edge_geometry_bwd_csc_kernel, dim3((num_nodes + 3) / 4), dim3(256), 0, s,
                      reinterpret_cast<const float4*>(gD), csr_rowptr, csc_rowptr, csc_pos, num_rel, num_nodes, gpos);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_edge_geometry_bwd_virial(const float* gD, const int* csr_rowptr, const int* csc_rowptr,
+                                                const int* csc_pos, int num_rel, const int* out_rowptr,
+                                                const int* out_edges, const float* pos, const int* src_id,
+                                                const int* tgt_id, const float* shift, const float* cell,
+                                                const int* batch, int num_nodes, float* gpos, float* atom_virial,
+                                                void* stream) {
+  if (num_nodes < 0 || num_rel < 0) return HN_ERR_BAD_ARG;
+  const bool csc = csc_rowptr != nullptr, out = out_rowptr != nullptr;
+  if (csc == out) return HN_ERR_BAD_ARG;                  // exactly one out-adjacency
+  if (csc && num_rel == 0) return HN_ERR_BAD_ARG;
+  if (shift && !cell) return HN_ERR_BAD_ARG;
+  if (num_nodes == 0) return HN_OK;
+  // gD / csc_pos / out_edges / src_id / tgt_id may be NULL for an edge-less graph (never read)
+  if (!csr_rowptr || !pos || !gpos || !atom_virial) return HN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((num_nodes + 3) / 4), block(256);     // 4 atoms per block, one wave each
+  if (csc)
+    hipLaunchKernelGGL(edge_geometry_bwd_virial_kernel<true>, grid, block, 0, s, reinterpret_cast<const float4*>(gD),
+                       csr_rowptr, csc_rowptr, csc_pos, num_rel, nullptr, nullptr, pos, src_id, tgt_id, shift, cell,
+                       batch, num_nodes, gpos, atom_virial);
+  else
+    hipLaunchKernelGGL(edge_geometry_bwd_virial_kernel<false>, grid, block, 0, s, reinterpret_cast<const float4*>(gD),
+                       csr_rowptr, nullptr, nullptr, 0, out_rowptr, out_edges, pos, src_id, tgt_id, shift, cell,
+                       batch, num_nodes, gpos, atom_virial);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }

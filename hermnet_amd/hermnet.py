@@ -278,6 +278,29 @@ class HVNet(nn.Module):
         d = torch.where(d.abs() <= 1.0e-6, torch.full_like(d, 1.0e-6), d)           # hermnet.py:146-147
         return torch.cat([D / d[:, None], d[:, None]], dim=1), None
 
+    @staticmethod
+    def _check_atom_props(train, shard):
+        """Per-atom outputs are first-order eval() results of whole, unsharded graphs, computed eagerly: refuse the rest."""
+        if train:
+            raise NotImplementedError("per-atom outputs are eval() results: not in train() or with eval_param_grads")
+        if shard is not None:
+            raise NotImplementedError("per-atom outputs of atom-sharded data: the ghost atoms' shares would have to be sent "
+                                      "back to their owners, which is not implemented")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise NotImplementedError("per-atom outputs are not available inside a captured hipGraph")
+
+    def _atom_energies(self, e_rows, graph, batch):
+        """The read-out term of every atom (hermnet.py:129) in atom order; intensive models: divided by its graph's atom
+        count, so that the terms of a graph sum to its energy."""
+        e = e_rows.detach().index_select(0, graph.row_of_node)
+        if self.intensive:
+            if graph.num_graphs == 1:
+                e = e / max(graph.num_atoms, 1)
+            else:
+                cnt = torch.bincount(batch.long(), minlength=graph.num_graphs).clamp(min=1).to(e.dtype)
+                e = e / cnt.index_select(0, batch.long())
+        return e
+
     def forward(self, data):
         """Two execution modes behind the same signature, chosen like any PyTorch module chooses:
         `eval()` (calculators, MD, validation -- `calculator.py:73`, `lmp_calc.py:46`, `dist_train.py:109`):
@@ -306,7 +329,13 @@ class HVNet(nn.Module):
         # basis takes the materialised route instead of failing in the backward: ADVICE r5)
         if fused and self.radial_basis.num_radial > 176 and pos.size(0) * 1.2 * 3 * ((self.hidden_channels + 63) // 64 * 64) * 4 >= 2 ** 32:
             fused = False
+        # per-atom outputs (atomic.atom_properties, the ASE calculator's `energies` / `stresses`): an ops.AtomSink of this call
+        props = data.get("_hn_atom_props")
+        if props is not None:
+            self._check_atom_props(train, shard)
         graph = self._build_graph(data, zl, shard)
+        if props is not None and graph.num_src:
+            raise NotImplementedError("per-atom outputs: HTNet's triadic graphs are not supported")
         rbf = self.radial_basis.descriptor() if fused else None
         row_plan = None
         if shard is not None:
@@ -347,7 +376,10 @@ class HVNet(nn.Module):
         if train:
             edge, edge_parts = self._edge_geometry_autograd(pos, data.get("cell"), graph)
         else:
-            edge = EdgeGeometry.apply(pos, data.get("cell"), graph)      # with_edge, hermnet.py:133-152
+            if props is not None and props.want_virials:
+                edge = EdgeGeometry.apply(pos, data.get("cell"), graph, props)    # (its backward fills props.virials)
+            else:
+                edge = EdgeGeometry.apply(pos, data.get("cell"), graph)      # with_edge, hermnet.py:133-152
 
         vec = None                                                          # zeros, hermnet.py:124
         if not fused and not train:
@@ -416,6 +448,8 @@ class HVNet(nn.Module):
         else:
             e_rows = EnergyHead.apply(x.contiguous(), *[p.detach() for p in head_params],
                                       graph.row_real if single else shard_rows)
+        if props is not None:
+            props.energies = self._atom_energies(e_rows, graph, data.batch)
         if shard_rows is not None:
             energy = e_rows.sum().reshape(1)
             if shard.world > 1:
@@ -557,4 +591,6 @@ class HTNet(HVNet):
         every parameter of the 18 (T * P) PaiNNModules per layer gets its gradient, forces included in the loss."""
         if not self.radial_basis.fused:
             raise NotImplementedError("HTNet runs on the fused kernels: Gaussian radial basis")
+        if data.get("_hn_atom_props") is not None:
+            raise NotImplementedError("per-atom outputs are not implemented for HTNet")
         return super().forward(data)

@@ -79,11 +79,28 @@ class RbfDescriptor(object):
                             self.env_kind, self.env_p)
 
 
+class AtomSink(object):
+    """Per-evaluation request for per-atom outputs (`HVNet.forward` reads it from `data._hn_atom_props`; never stored on a
+    cached graph).  `HVNet.forward` fills `energies` [N] (atom order, intensive models already divided by their graph's atom
+    count); with `virials=True` the first position backward through `EdgeGeometry` fills `virials` [N,3,3] (atom order,
+    W_i = -1/2 sum_{e touching i} D_e (x) dE/dD_e, include/hermnet_hip.h: hermnet_edge_geometry_bwd_virial).  Later backward
+    passes through the same forward (the stress path's cell gradient) leave it as it is."""
+
+    def __init__(self, virials=True):
+        self.want_virials = bool(virials)
+        self.energies = self.virials = None
+
+    def reset(self):
+        self.energies = self.virials = None
+        return self
+
+
 class EdgeGeometry(torch.autograd.Function):
-    """`HVNet.with_edge` (hermnet.py:133-152) -> edge[E,4] = (rhat, d) in CSR order."""
+    """`HVNet.with_edge` (hermnet.py:133-152) -> edge[E,4] = (rhat, d) in CSR order.  `sink` (optional `AtomSink`): the
+    first backward also writes the per-atom virials into it."""
 
     @staticmethod
-    def forward(ctx, pos, cell, graph):
+    def forward(ctx, pos, cell, graph, sink=None):
         _require_gpu(pos, "EdgeGeometry")
         lib = _lib.load()
         pos_c = pos.detach().float().contiguous()
@@ -96,7 +113,7 @@ class EdgeGeometry(torch.autograd.Function):
             _lib.ptr(pos_c), _lib.ptr(graph.src_id), _lib.ptr(graph.tgt_id),
             _lib.ptr(graph.shift if cell_c is not None else None), _lib.ptr(cell_c), _lib.ptr(batch32),
             graph.E, _lib.ptr(edge), _stream()), "hermnet_edge_geometry_fwd")
-        ctx.graph = graph
+        ctx.graph, ctx.sink = graph, sink
         ctx.keep = (pos_c, cell_c)
         ctx.cell_shape = None if cell is None else tuple(cell.shape)
         return edge
@@ -118,6 +135,19 @@ class EdgeGeometry(torch.autograd.Function):
                                          lengths=rp_s[1:] - rp_s[:-1], unsafe=True)                      # [TR*Ns,3]
             gpos_rows = outof.view(TR, graph.num_src, 3).sum(0)
             gpos_rows[:Te * B_] -= into.view(Te, P_, B_, 3).sum(1).reshape(Te * B_, 3)
+        elif ctx.sink is not None and ctx.sink.virials is None:
+            # per-atom virials wanted and not yet taken: the same position gradient (bit for bit) with W_i alongside
+            pos_c, cell_c = ctx.keep
+            csc = graph.out_rowptr is None
+            vrows = torch.empty(graph.N, 9, dtype=torch.float32, device=gD.device)
+            _lib.check(lib.hermnet_edge_geometry_bwd_virial(
+                _lib.ptr(gD), _lib.ptr(graph.csr_rowptr), _lib.ptr(graph.csc_rowptr if csc else None),
+                _lib.ptr(graph.csc_pos if csc else None), graph.T if csc else 0,
+                _lib.ptr(None if csc else graph.out_rowptr), _lib.ptr(None if csc else graph.out_edges), _lib.ptr(pos_c),
+                _lib.ptr(graph.src_id), _lib.ptr(graph.tgt_id), _lib.ptr(graph.shift if cell_c is not None else None),
+                _lib.ptr(cell_c), _lib.ptr(graph.batch32), graph.N, _lib.ptr(gpos_rows), _lib.ptr(vrows), _stream()),
+                "hermnet_edge_geometry_bwd_virial")
+            ctx.sink.virials = vrows.index_select(0, graph.row_of_node).view(-1, 3, 3)
         elif graph.out_rowptr is None:      # device-built graphs: out-edges from the CSC order (one sort fewer)
             _lib.check(lib.hermnet_edge_geometry_bwd_csc(
                 _lib.ptr(gD), _lib.ptr(graph.csr_rowptr), _lib.ptr(graph.csc_rowptr), _lib.ptr(graph.csc_pos),
@@ -138,7 +168,7 @@ class EdgeGeometry(torch.autograd.Function):
                 b = graph.batch32.long()[graph.src_id.long()]
                 gcell = torch.zeros(nb, 3, 3, dtype=gD.dtype, device=gD.device).index_add_(0, b, outer)
             gcell = gcell.reshape(ctx.cell_shape)
-        return gpos_rows.index_select(0, graph.row_of_node), gcell, None
+        return gpos_rows.index_select(0, graph.row_of_node), gcell, None, None
 
 
 class TrueEdgeGradient(torch.autograd.Function):

@@ -89,12 +89,16 @@ def build_graph(cell, elements, pos, rc, device=None, reference_compat=False, ca
     return data
 
 
-def _evaluate(model, data, device, pbc, want_virial, trn_mean=0.0):
+def _evaluate(model, data, device, pbc, want_virial, trn_mean=0.0, atom_props=None):
     """One energy + force evaluation -> (energy [graphs] tensor, forces [N,3] tensor, W [3,3] tensor in energy units
     or None).  W = -dE/d(strain) = sum_i pos_i (x) F_i - cell^T dE/dcell, symmetrised (`utils.virial_calc` with unit
-    factor 1); the cell gradient comes from the edge geometry kernel's backward."""
+    factor 1); the cell gradient comes from the edge geometry kernel's backward.  `atom_props` (optional `ops.AtomSink`):
+    emptied, then filled with the per-atom energies (without `trn_mean`) and virials of this evaluation; the three
+    results are the same either way."""
     device = torch.device(device)
     data = data.to(device)
+    if atom_props is not None:
+        data._hn_atom_props = atom_props.reset()
     data.pos.requires_grad = True
     periodic = bool(pbc) and data.get('cell') is not None
     if want_virial and periodic:
@@ -110,13 +114,13 @@ def _evaluate(model, data, device, pbc, want_virial, trn_mean=0.0):
     return energy.detach(), forces.detach(), w
 
 
-def _evaluate_finite(model, data, device, pbc, want_virial, trn_mean=0.0):
+def _evaluate_finite(model, data, device, pbc, want_virial, trn_mean=0.0, atom_props=None):
     """`_evaluate` + the energy on the host (every caller copies it there anyway), never NaN: the stale-cache guard
     (`guard.ParamGuard`) answers a write through `.data` behind the cached kernel-ready weights with a NaN step, and ONE NaN
     force step handed to an integrator corrupts a trajectory for good.  A non-finite energy therefore drops the caches,
     evaluates again with the current weights (warning once per model), and raises if the result is still not finite."""
     for attempt in (0, 1):
-        energy, forces, w = _evaluate(model, data, device, pbc, want_virial, trn_mean)
+        energy, forces, w = _evaluate(model, data, device, pbc, want_virial, trn_mean, atom_props)
         e_host = energy.cpu()
         if bool(torch.isfinite(e_host).all()):
             return e_host, forces, w
@@ -165,9 +169,18 @@ def stress_from_virial(w, volume):
     return np.array([s[0, 0], s[1, 1], s[2, 2], s[1, 2], s[0, 2], s[0, 1]])
 
 
+def stresses_from_virials(w, volume):
+    """Per-atom `stresses` [N,6] from per-atom virials W_i [N,3,3] (energy units, unsymmetrised): sigma_i = -sym(W_i) / V
+    under the contract of `stress_from_virial` (Voigt [xx, yy, zz, yz, xz, xy]), so that they sum to `results['stress']`.
+    V is the cell's volume: the convention of ASE's pair calculators and of LAMMPS `compute stress/atom` divided by V."""
+    w = np.asarray(w, dtype=np.float64)
+    s = -0.5 * (w + w.transpose(0, 2, 1)) / float(volume)
+    return np.stack([s[:, 0, 0], s[:, 1, 1], s[:, 2, 2], s[:, 1, 2], s[:, 0, 2], s[:, 0, 1]], axis=1)
+
+
 class NNCalculator(_Base):
     """`calculator.py:30-57`.  `model_path=None` keeps the weights already in `model`."""
-    implemented_properties = ['energy', 'free_energy', 'forces', 'stress']
+    implemented_properties = ['energy', 'free_energy', 'forces', 'stress', 'energies', 'stresses']
 
     def __init__(self, model, model_path, trn_mean, device_='cuda', ensemble='NVT', reference_compat=False,
                  graph_replay=False):
@@ -176,8 +189,8 @@ class NNCalculator(_Base):
         per-launch host work: 2-3x on cells of a few hundred atoms, where the eager step is bound by launch overhead).
         The capture is renewed by itself when the species, the cell, the atom count or the model's weights
         (`load_state_dict`, `.to()`, `invalidate_caches()`) change or the list outgrows its capacity; weights written
-        through `.data` need `model.invalidate_caches()` as everywhere else.  Calls that need the stress, open systems and
-        CPU runs take the eager path."""
+        through `.data` need `model.invalidate_caches()` as everywhere else.  Calls that need the stress or a per-atom
+        property (`energies`, `stresses`: `atomic.atom_properties`), open systems and CPU runs take the eager path."""
         super(NNCalculator, self).__init__()
         self.reference_compat = reference_compat     # see `build_graph`
         self.graph_replay = bool(graph_replay)
@@ -238,14 +251,17 @@ class NNCalculator(_Base):
         elems = (np.asarray(numbers) if numbers is not None
                  else np.array([atomic_numbers[s] for s in atoms.get_chemical_symbols()]))
         dev = self.device_ if torch.device(self.device_).type == 'cuda' else None
+        # per-atom properties: computed in the eager evaluation (never in a replayed graph), energy / forces / stress as always
+        per_atom = [k for k in ('energies', 'stresses') if k in tuple(properties)]
         if (self.graph_replay and dev is not None and pbc and cell is not None and np.any(cell)
-                and self.ensemble.lower() != 'npt' and 'stress' not in tuple(properties)):
+                and self.ensemble.lower() != 'npt' and 'stress' not in tuple(properties) and not per_atom):
             out = self._replayed(cell, elems, atoms.positions)
             if out is not None:
                 self.results['energy'] = out[0]
                 self.results['free_energy'] = out[0]
                 self.results['forces'] = out[1]
-                self.results.pop('stress', None)      # (not computed: see the end of this method)
+                for k in ('stress', 'energies', 'stresses'):
+                    self.results.pop(k, None)      # (not computed: see the end of this method)
                 return
         # periodic cells on the GPU: from the second call on the neighbour list is built without its host read, padded to a
         # capacity taken from the last edge count; count and flags are checked behind the step, where the results are
@@ -255,7 +271,11 @@ class NNCalculator(_Base):
                            reference_compat=self.reference_compat, capacity=cap)
         # stress whenever ASE asks for it (or the ensemble is NPT) on a periodic cell; an open system has none
         want = pbc and cell is not None and (self.ensemble.lower() == 'npt' or 'stress' in tuple(properties))
-        energy, forces, w = _evaluate_finite(self.model, data, self.device_, pbc, want, self.trn_mean)
+        sink = None
+        if per_atom:
+            from ..ops import AtomSink
+            sink = AtomSink(virials='stresses' in per_atom)
+        energy, forces, w = _evaluate_finite(self.model, data, self.device_, pbc, want, self.trn_mean, sink)
         energy = energy.item()
         if dev is not None and cell is not None:
             from ..neighbor import padded_capacity, padded_list_ok
@@ -283,6 +303,21 @@ class NNCalculator(_Base):
             # a property's name is in `results`, so a cached zero vector would be handed to a later `atoms.get_stress()`
             # (cell filters, NPT dynamics) without a recomputation; absent, ASE calls `calculate(['stress'])` again.
             self.results.pop('stress', None)
+        # per-atom properties: stored when computed in this call, dropped otherwise (the same reasoning as for `stress`)
+        n = len(elems)
+        if 'energies' in per_atom:
+            self.results['energies'] = sink.energies.double().cpu().numpy() + float(self.trn_mean) / max(n, 1)
+        else:
+            self.results.pop('energies', None)
+        if 'stresses' in per_atom:
+            volume = abs(float(np.linalg.det(np.asarray(cell, dtype=np.float64).reshape(3, 3)))) if pbc and cell is not None else 0.0
+            if volume > 0:
+                vir = sink.virials if sink.virials is not None else torch.zeros(n, 3, 3)
+                self.results['stresses'] = stresses_from_virials(vir.cpu().numpy(), volume)
+            else:
+                self.results['stresses'] = np.zeros((n, 6))     # an open system: zeros, as for `stress`
+        else:
+            self.results.pop('stresses', None)
 
     def model_calc(self, data, device, pbc, ensemble='NVT'):
         """`calculator.py:59-98`: (energy, forces [N,3], LAMMPS-packed virial [6]) -- see the module-level function."""

@@ -16,7 +16,8 @@
  *   - float = IEEE fp32 (the reference is fp32-only), indices = int32 (int64 where a parameter says so:
  *     the caller's edge_index / atomic_number / halo index lists arrive as torch LongTensors).
  *
- * ABI version 13 (`hermnet_abi_version`): v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
+ * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial was added within v13 (a new entry point only, nothing
+ * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
  * variables, hermnet_weight_fragments; no signature, struct or fragment format of v11 changed).  STABLE from v11 on: hn_graph,
@@ -234,6 +235,23 @@ int hermnet_edge_geometry_bwd(const float* gD, const int* in_rowptr, const int* 
  * point `hermnet_build_relations` may be called with out_rowptr = out_edges = NULL (one edge order fewer). */
 int hermnet_edge_geometry_bwd_csc(const float* gD, const int* csr_rowptr, const int* csc_rowptr, const int* csc_pos,
                                   int num_rel, int num_nodes, float* gpos, void* stream);
+/* The position gradient of either form above plus the per-atom virial (ABI 13, additive: no reference counterpart;
+ * DESIGN section 1).  With D_e the edge vector exactly as hermnet_edge_geometry_fwd computes it (pos[src] - pos[tgt]
+ * + shift_e @ cell[batch[src]], before the d ~ 0 clamp) and gD_e = dE/dD_e:
+ *   atom_virial[a] = W_a = -1/2 sum_{e touching row a} D_e (x) gD_e   [N,9] rows, row-major [alpha][beta] = D_alpha gD_beta,
+ *   unsymmetrised, energy units.  Each edge is split equally between its two atoms (the pair convention of LAMMPS and
+ *   of ASE's pair calculators; the split is a convention); an edge between an atom and its own periodic image counts
+ *   fully.  Summed over a graph: -sum_e D_e (x) gD_e, whose symmetric part is the virial of `virial_calc`.
+ * gpos [N,3] rows is bit for bit what hermnet_edge_geometry_bwd_csc (csc_rowptr / csc_pos / num_rel given, out_rowptr =
+ * out_edges = NULL) or hermnet_edge_geometry_bwd with in_edges = NULL (out_rowptr / out_edges given, csc_rowptr = csc_pos
+ * = NULL, num_rel ignored) writes; every row of both outputs is written.  pos [N,3], src_id / tgt_id, shift, cell,
+ * batch as for hermnet_edge_geometry_fwd (shift NULL: open system).  No atomics: bit-reproducible run to run.
+ * HN_ERR_BAD_ARG: negative counts, both out-adjacencies or neither, num_rel = 0 with the CSC form, shift without
+ * cell, a missing output; num_nodes = 0 is HN_OK. */
+int hermnet_edge_geometry_bwd_virial(const float* gD, const int* csr_rowptr, const int* csc_rowptr, const int* csc_pos,
+                                     int num_rel, const int* out_rowptr, const int* out_edges, const float* pos,
+                                     const int* src_id, const int* tgt_id, const float* shift, const float* cell,
+                                     const int* batch, int num_nodes, float* gpos, float* atom_virial, void* stream);
 
 /* ---- A3+A7(rbf_proj)+A8+A9+A10 and the residual of A6 ---------------------------------------
  * Replaces, for ALL relations of one HeteroVertexConv layer at once,
