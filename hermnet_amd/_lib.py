@@ -52,6 +52,8 @@ SIGNATURES = {
     "hermnet_edge_geometry_bwd_csc": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
     "hermnet_edge_geometry_bwd_virial": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
                                                         c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
+    "hermnet_graph_virial_workspace": (ctypes.c_size_t, [ctypes.c_int]),
+    "hermnet_graph_virial": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_size_t, c_fp, c_fp]),
     "hermnet_message_scatter_fwd": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int,
                                                    c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp]),
     "hermnet_message_scatter_bwd": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int,
@@ -63,6 +65,8 @@ SIGNATURES = {
     "hermnet_neighbor_workspace_for": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
     "hermnet_neighbor_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_double, c_fp,
                                               ctypes.c_size_t, c_fp, c_fp, c_fp]),
+    "hermnet_neighbor_count_devcell": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_double, c_fp, ctypes.c_size_t,
+                                                      c_fp, c_fp, c_fp]),
     "hermnet_neighbor_fill": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_double, c_fp, ctypes.c_size_t,
                                              ctypes.c_long, ctypes.c_float, ctypes.c_int, ctypes.c_int,
                                              c_fp, c_fp, c_fp, c_fp, c_fp]),

@@ -9,7 +9,8 @@
                                `compute stress/atom` and of ASE's pair calculators).  Summed over a graph, the symmetric
                                part is the virial of `utils.virial_calc(..., units='lj')`.
 
-Refused (NotImplementedError): atom-sharded data, HTNet, train() / create_graph, a captured hipGraph.
+Refused (NotImplementedError): atom-sharded data, HTNet, train() / create_graph.  (With `trn_mean` on a batch of several
+graphs the call reads the host -- a bincount -- and cannot be captured into a hipGraph; without it nothing does.)
 """
 import copy
 

@@ -5,6 +5,8 @@
 //                                 plugin/lmp_interface/lmp_calc.py:50-56)
 //   hermnet_edge_geometry_bwd_virial <- the same position gradient plus the per-atom virial
 //                                 W_i = -1/2 sum_{e touching i} D_e (x) gD_e (no reference counterpart: DESIGN section 1)
+//   hermnet_graph_virial      <- the per-graph sums of those rows, W_b = sum_{i in b} W_i (the stress of a graph), as an
+//                                 ordered two-stage reduction
 // Both are tiny, HBM-streaming kernels (E * ~50 B); one thread per edge / one wave per atom.
 #include <hip/hip_runtime.h>
 #include "../../include/hermnet_hip.h"
@@ -182,6 +184,96 @@ __global__ __launch_bounds__(256) void edge_geometry_bwd_virial_kernel(
   }
 }
 
+// Per-graph virial W_b = sum_{atoms i of graph b} W_i from the rows the kernel above wrote -- two stages, fixed order, no
+// atomics.  The atoms are taken in "graph order": position k holds atom perm[k] (perm = stable argsort of batch, NULL =
+// identity), so a graph's atoms are one contiguous range of positions and padding rows are never touched.
+// Stage 1: one workgroup per fixed chunk of kVirChunk positions -> the chunk's sum (xor tree per wave, waves in order).
+// Stage 2: one workgroup per graph: its range [lo, hi) by binary search on batch[perm[.]], then the chunk sums of the
+// chunks that lie wholly inside it plus the atoms of the ragged head and tail, strided over the threads in a fixed order.
+constexpr int kVirChunk = 256;
+
+__device__ __forceinline__ void virial_block_sum(float (&w)[9], float (*lds)[9]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) w[q] += __shfl_xor(w[q], m, 64);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) lds[wave][q] = w[q];
+  }
+  __syncthreads();
+}
+
+__device__ __forceinline__ void virial_add_atom(float (&w)[9], const float* __restrict__ atom_virial,
+                                                const long* __restrict__ row_of_node, const long* __restrict__ perm, long k) {
+  const long a = perm ? perm[k] : k;
+  const float* r = atom_virial + 9 * (size_t)row_of_node[a];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) w[q] += r[q];
+}
+
+__global__ __launch_bounds__(kVirChunk) void graph_virial_chunk_kernel(
+    const float* __restrict__ atom_virial, const long* __restrict__ row_of_node, const long* __restrict__ perm, int N,
+    float* __restrict__ chunk_sums) {
+  __shared__ float lds[kVirChunk / 64][9];
+  float w[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) w[q] = 0.f;
+  const long k = (long)blockIdx.x * kVirChunk + threadIdx.x;
+  if (k < N) virial_add_atom(w, atom_virial, row_of_node, perm, k);
+  virial_block_sum(w, lds);
+  if (threadIdx.x < 9) {
+    float s = lds[0][threadIdx.x];
+    for (int v = 1; v < kVirChunk / 64; ++v) s += lds[v][threadIdx.x];
+    chunk_sums[9 * (size_t)blockIdx.x + threadIdx.x] = s;
+  }
+}
+
+__global__ __launch_bounds__(kVirChunk) void graph_virial_finish_kernel(
+    const float* __restrict__ atom_virial, const long* __restrict__ row_of_node, const long* __restrict__ perm,
+    const int* __restrict__ batch, int N, int B, const float* __restrict__ chunk_sums, float* __restrict__ graph_virial) {
+  __shared__ float lds[kVirChunk / 64][9];
+  __shared__ int range[2];
+  const int b = blockIdx.x;
+  if (threadIdx.x < 2) {
+    // first position whose graph index is >= b (thread 0) / >= b + 1 (thread 1); one graph: everything
+    int lo = 0, hi = N;
+    if (B > 1) {
+      const int want = b + (int)threadIdx.x;
+      while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (batch[perm ? perm[mid] : mid] < want) lo = mid + 1; else hi = mid;
+      }
+    } else if (threadIdx.x == 1) {
+      lo = N;
+    }
+    range[threadIdx.x] = lo;
+  }
+  __syncthreads();
+  const int lo = range[0], hi = range[1];
+  float w[9];
+#pragma unroll
+  for (int q = 0; q < 9; ++q) w[q] = 0.f;
+  int c0 = (lo + kVirChunk - 1) / kVirChunk, c1 = hi / kVirChunk;      // whole chunks inside the range: [c0, c1)
+  if (c0 >= c1) { c0 = c1 = 0; }
+  const int head_end = c0 < c1 ? c0 * kVirChunk : hi;                  // atoms [lo, head_end) and [tail_beg, hi) singly
+  const int tail_beg = c0 < c1 ? c1 * kVirChunk : hi;
+  for (int k = lo + (int)threadIdx.x; k < head_end; k += kVirChunk) virial_add_atom(w, atom_virial, row_of_node, perm, k);
+  for (int c = c0 + (int)threadIdx.x; c < c1; c += kVirChunk) {
+#pragma unroll
+    for (int q = 0; q < 9; ++q) w[q] += chunk_sums[9 * (size_t)c + q];
+  }
+  for (int k = tail_beg + (int)threadIdx.x; k < hi; k += kVirChunk) virial_add_atom(w, atom_virial, row_of_node, perm, k);
+  virial_block_sum(w, lds);
+  if (threadIdx.x < 9) {
+    float s = lds[0][threadIdx.x];
+    for (int v = 1; v < kVirChunk / 64; ++v) s += lds[v][threadIdx.x];
+    graph_virial[9 * (size_t)b + threadIdx.x] = s;
+  }
+}
+
 }  // namespace
 
 extern "C" int hermnet_edge_geometry_fwd(const float* pos, const int* src_id, const int* tgt_id,
@@ -248,5 +340,29 @@ extern "C" int hermnet_edge_geometry_bwd_virial(const float* gD, const int* csr_
     hipLaunchKernelGGL(edge_geometry_bwd_virial_kernel<false>, grid, block, 0, s, reinterpret_cast<const float4*>(gD),
                        csr_rowptr, nullptr, nullptr, 0, out_rowptr, out_edges, pos, src_id, tgt_id, shift, cell,
                        batch, num_nodes, gpos, atom_virial);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" size_t hermnet_graph_virial_workspace(int num_nodes) {
+  const size_t chunks = num_nodes > 0 ? ((size_t)num_nodes + kVirChunk - 1) / kVirChunk : 0;
+  return (chunks > 0 ? chunks : 1) * 9 * sizeof(float);
+}
+
+extern "C" int hermnet_graph_virial(const float* atom_virial, const long* row_of_node, const long* graph_perm,
+                                    const int* batch, int num_nodes, int num_graphs, void* workspace,
+                                    size_t workspace_bytes, float* graph_virial, void* stream) {
+  if (num_nodes < 0 || num_graphs < 0) return HN_ERR_BAD_ARG;
+  if (!graph_virial && num_graphs > 0) return HN_ERR_BAD_ARG;
+  if (num_nodes > 0 && (!atom_virial || !row_of_node || !workspace)) return HN_ERR_BAD_ARG;
+  if (num_nodes > 0 && num_graphs > 1 && !batch) return HN_ERR_BAD_ARG;
+  if (num_nodes > 0 && workspace_bytes < hermnet_graph_virial_workspace(num_nodes)) return HN_ERR_BAD_ARG;
+  if (num_graphs == 0 || num_nodes == 0) return HN_OK;     // (no atoms: there are no rows to sum, graph_virial is left alone)
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int chunks = (num_nodes + kVirChunk - 1) / kVirChunk;
+  float* sums = reinterpret_cast<float*>(workspace);
+  hipLaunchKernelGGL(graph_virial_chunk_kernel, dim3(chunks), dim3(kVirChunk), 0, s, atom_virial, row_of_node, graph_perm,
+                     num_nodes, sums);
+  hipLaunchKernelGGL(graph_virial_finish_kernel, dim3(num_graphs), dim3(kVirChunk), 0, s, atom_virial, row_of_node,
+                     graph_perm, batch, num_nodes, num_graphs, sums, graph_virial);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }

@@ -51,10 +51,18 @@ __device__ __forceinline__ void cart_of(const NbrGeom& g, const double* f, doubl
   p[2] = f[0] * g.cell[2] + f[1] * g.cell[5] + f[2] * g.cell[8];
 }
 
+// The geometry reaches a kernel by value (G = NbrGeom: made on the host from a host copy of the cell) or through a pointer
+// (G = const NbrGeom*: made on the device by nbr_geom_kernel from the cell in device memory, so that a captured search
+// follows a cell that changes between replays).
+__device__ __forceinline__ const NbrGeom& geom_of(const NbrGeom& g) { return g; }
+__device__ __forceinline__ const NbrGeom& geom_of(const NbrGeom* g) { return *g; }
+
 // wrapped fractional coordinate, integer wrap, bin id
-__global__ __launch_bounds__(kBlock) void nbr_bin_kernel(const float* __restrict__ pos, int N, NbrGeom g,
+template <class G>
+__global__ __launch_bounds__(kBlock) void nbr_bin_kernel(const float* __restrict__ pos, int N, G geom,
                                                         double* __restrict__ fw, int* __restrict__ wrap,
                                                         unsigned* __restrict__ bin) {
+  const NbrGeom& g = geom_of(geom);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   const double p[3] = {(double)pos[3 * i], (double)pos[3 * i + 1], (double)pos[3 * i + 2]};
@@ -104,10 +112,10 @@ __global__ __launch_bounds__(kBlock) void nbr_bin_scatter_kernel(const unsigned*
 // Visit every candidate (j, image) of atom i.  MODE 0 counts and stashes the keys at keys[i * kStash ...] (flags: bit 0
 // |S| overflow, bit 1 an atom with more than kStash pairs), MODE 1 writes the keys at keys[offset[i] ...] (two-pass form).
 // key = ((i * N + j) * 17^3 + code(S)),  S = image - wrap_j + wrap_i (shift for the caller's coordinates).
-template <int MODE>
+template <int MODE, class G>
 __global__ __launch_bounds__(kBlock) void nbr_pairs_kernel(const double* __restrict__ fw, const int* __restrict__ wrap,
                                                           const int* __restrict__ sorted_ids,
-                                                          const int* __restrict__ bin_start, int N, NbrGeom g,
+                                                          const int* __restrict__ bin_start, int N, G geom,
                                                           const long* __restrict__ offset, int* __restrict__ count,
                                                           unsigned long long* __restrict__ keys,
                                                           int* __restrict__ overflow,
@@ -115,6 +123,7 @@ __global__ __launch_bounds__(kBlock) void nbr_pairs_kernel(const double* __restr
                                                           int stash) {
   // one WAVE per atom: the lanes share the candidates of a bin (one atom per thread left the chip at 40 workgroups
   // for 10k atoms, each thread walking ~200 candidates serially: 0.2 ms per pass)
+  const NbrGeom& g = geom_of(geom);
   const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (i >= N) return;
   const int lane = threadIdx.x & 63;
@@ -295,6 +304,61 @@ __global__ void nbr_total_kernel(const long* __restrict__ offset_end, const int*
   if (threadIdx.x == 0) { total[0] = offset_end[0]; total[1] = (long)overflow[0]; }
 }
 
+// `make_geom` (periodic branch) + the coarsening loop of hermnet_neighbor_count, restated for ONE device thread: the cell
+// is read from device memory (float32 values, widened: the numbers a host copy of the same tensor gives), every step in
+// float64 without fused multiply-adds, so that the geometry -- and with it the list -- is bit for bit the host's.
+// A cell the host refuses (singular, or so small that a cutoff sphere reaches beyond kMaxImg bins) cannot be a return code
+// here: flag bit 3 is raised and the geometry is replaced by an inert one (zero matrices, one bin, reach 1, a negative
+// cutoff), on which the following kernels stay inside their arrays and list no pair; the caller discards such a step.
+__global__ void nbr_geom_kernel(const float* __restrict__ cell, double rc, int N, NbrGeom* __restrict__ out,
+                                int* __restrict__ overflow) {
+#pragma clang fp contract(off)
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  NbrGeom g;
+  g.rc2 = rc * rc;
+  g.periodic = 1;
+  double c[9];
+  bool bad = false;
+  for (int k = 0; k < 9; ++k) { c[k] = (double)cell[k]; g.cell[k] = c[k]; }
+  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+  if (!(fabs(det) >= 1e-12) || !(fabs(det) <= 1.0e300)) bad = true;      // (also NaN / Inf, which the host never sees)
+  if (!bad) {
+    g.inv[0] = (c[4] * c[8] - c[5] * c[7]) / det; g.inv[1] = (c[2] * c[7] - c[1] * c[8]) / det; g.inv[2] = (c[1] * c[5] - c[2] * c[4]) / det;
+    g.inv[3] = (c[5] * c[6] - c[3] * c[8]) / det; g.inv[4] = (c[0] * c[8] - c[2] * c[6]) / det; g.inv[5] = (c[2] * c[3] - c[0] * c[5]) / det;
+    g.inv[6] = (c[3] * c[7] - c[4] * c[6]) / det; g.inv[7] = (c[1] * c[6] - c[0] * c[7]) / det; g.inv[8] = (c[0] * c[4] - c[1] * c[3]) / det;
+    for (int k = 0; k < 3; ++k) {
+      const double h = 1.0 / sqrt(g.inv[k] * g.inv[k] + g.inv[3 + k] * g.inv[3 + k] + g.inv[6 + k] * g.inv[6 + k]);
+      if (!(h > 0.0) || !(h <= 1.0e300)) { bad = true; break; }
+      const double q = floor(h / rc);
+      int nb = q > 1024.0 ? 1024 : (int)q;
+      if (nb < 1) nb = 1;
+      g.nbins[k] = nb;
+      const double r = ceil(rc / (h / nb) - 1e-12);
+      int reach = r > (double)(kMaxImg + 1) ? kMaxImg + 1 : (int)r;
+      if (reach < 1) reach = 1;
+      if (reach > kMaxImg) { bad = true; break; }
+      g.reach[k] = reach;
+      g.lo[k] = 0.0;
+    }
+  }
+  if (bad) {
+    for (int k = 0; k < 9; ++k) { g.cell[k] = 0.0; g.inv[k] = 0.0; }
+    for (int k = 0; k < 3; ++k) { g.nbins[k] = 1; g.reach[k] = 1; g.lo[k] = 0.0; }
+    g.rc2 = -1.0;                   // (no distance is below it: no pair is listed)
+    overflow[0] = 8;
+  } else {
+    long nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
+    while (nbins > 8l * N + 64) {   // must mirror hermnet_neighbor_count
+      int kmax = 0;
+      for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
+      if (g.nbins[kmax] <= 1) break;
+      g.nbins[kmax] = (g.nbins[kmax] + 1) / 2;
+      nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
+    }
+  }
+  *out = g;
+}
+
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 int key_bits(int N) {
@@ -438,17 +502,50 @@ extern "C" int hermnet_neighbor_count(const float* pos, int num_atoms, const dou
   NbrWork w;
   carve(workspace, N, 8l * N + 64, stash, w);
   w.temp_bytes = workspace_bytes - (size_t)((char*)w.temp - (char*)workspace);
-  hipLaunchKernelGGL(nbr_bin_kernel, grid_for(N), dim3(kBlock), 0, s, pos, N, g, w.fw, w.wrap, w.bin);
+  hipLaunchKernelGGL(nbr_bin_kernel<NbrGeom>, grid_for(N), dim3(kBlock), 0, s, pos, N, g, w.fw, w.wrap, w.bin);
   hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
   hipLaunchKernelGGL(nbr_bin_hist_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_fill);
   if (exclusive_scan_i32(w.bin_fill, w.bin_start, (int)nbins + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
   hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
   hipLaunchKernelGGL(nbr_bin_scatter_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_start, w.bin_fill, w.ids_sorted);
   hipLaunchKernelGGL(nbr_clear_kernel, dim3(1), dim3(64), 0, s, w.count + N, w.overflow);
-  hipLaunchKernelGGL(nbr_pairs_kernel<0>, grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
+  hipLaunchKernelGGL((nbr_pairs_kernel<0, NbrGeom>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
                      g, (const long*)nullptr, w.count, w.stash, w.overflow, target_ok, g.periodic, stash);
   if (exclusive_scan_i32_to_long(w.count, w.offset, N + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
   // total_device = (pairs found, flags of the pass)
+  hipLaunchKernelGGL(nbr_total_kernel, dim3(1), dim3(64), 0, s, w.offset + N, w.overflow, total_device);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+// The counting pass with the cell in DEVICE memory (periodic cells; `cell` [9] float32, rows = lattice vectors): nothing
+// about the cell is known on the host, so the launch sizes that follow the bin count take the bound the workspace is
+// carved for (8 N + 64 bins; counters beyond the grid's bins stay zero) and the geometry lives in the workspace.
+extern "C" int hermnet_neighbor_count_devcell(const float* pos, int num_atoms, const float* cell, double rc,
+                                              void* workspace, size_t workspace_bytes, const unsigned char* target_ok,
+                                              long* total_device, void* stream) {
+  const int N = num_atoms;
+  if (N <= 0 || !(rc > 0.0) || !pos || !cell || !workspace || !total_device) return HN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int stash = stash_checked(N, workspace_bytes);
+  if (stash == 0) return HN_ERR_BAD_ARG;
+  const long nbins = 8l * N + 64;
+  NbrWork w;
+  carve(workspace, N, nbins, stash, w);
+  w.temp_bytes = workspace_bytes - (size_t)((char*)w.temp - (char*)workspace);
+  // (the flags' 256-byte block: two ints of flags in front, the geometry behind them)
+  static_assert(sizeof(NbrGeom) + 32 <= 256, "NbrGeom must fit behind the flags");
+  NbrGeom* g = reinterpret_cast<NbrGeom*>(reinterpret_cast<char*>(w.overflow) + 32);
+  hipLaunchKernelGGL(nbr_clear_kernel, dim3(1), dim3(64), 0, s, w.count + N, w.overflow);
+  hipLaunchKernelGGL(nbr_geom_kernel, dim3(1), dim3(64), 0, s, cell, rc, N, g, w.overflow);
+  hipLaunchKernelGGL(nbr_bin_kernel<const NbrGeom*>, grid_for(N), dim3(kBlock), 0, s, pos, N, (const NbrGeom*)g, w.fw, w.wrap, w.bin);
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
+  hipLaunchKernelGGL(nbr_bin_hist_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_fill);
+  if (exclusive_scan_i32(w.bin_fill, w.bin_start, (int)nbins + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
+  hipLaunchKernelGGL(nbr_bin_scatter_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_start, w.bin_fill, w.ids_sorted);
+  hipLaunchKernelGGL((nbr_pairs_kernel<0, const NbrGeom*>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted,
+                     w.bin_start, N, (const NbrGeom*)g, (const long*)nullptr, w.count, w.stash, w.overflow, target_ok, 1, stash);
+  if (exclusive_scan_i32_to_long(w.count, w.offset, N + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
   hipLaunchKernelGGL(nbr_total_kernel, dim3(1), dim3(64), 0, s, w.offset + N, w.overflow, total_device);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }
@@ -503,7 +600,7 @@ extern "C" int hermnet_neighbor_fill(const float* pos, int num_atoms, const doub
   carve(workspace, N, 8l * N + 64, stash, w);
   w.temp_bytes = workspace_bytes - (size_t)((char*)w.temp - (char*)workspace);
   if (!stash_ok)    // an atom had more pairs than its stash slot: second pass over the candidates into `keys`
-    hipLaunchKernelGGL(nbr_pairs_kernel<1>, grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
+    hipLaunchKernelGGL((nbr_pairs_kernel<1, NbrGeom>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
                        g, w.offset, (int*)nullptr, keys, w.overflow, target_ok, g.periodic, 0);
   hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s,
                      stash_ok ? w.stash : keys, stash_ok ? stash : 0, w.count, w.offset, N, num_edges, shift_sign,

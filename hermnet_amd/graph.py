@@ -23,14 +23,17 @@ class GraphedStep(object):
     model: HVNet / HTNet in eval() with parameters that do not require grad; data: `Data` on the GPU with
     `edge_index` (and `cell` / `edge_shift`) already built.  Construction runs `warmup` eager steps on a side stream,
     then captures one step.  `__call__(pos=None)` copies `pos` into the static input (if given), replays, and returns
-    the static output tensors (valid until the next call; clone them to keep them)."""
+    the static output tensors (valid until the next call; clone them to keep them).
+    `stress=True`: the capture contains the virial kernels (stress.energy_forces_virial: the same forward and the same ONE
+    backward) and a call returns (energy, forces, virial [B,3,3]); energy and forces are bit for bit the plain step's."""
 
-    def __init__(self, model, data, warmup=3):
+    def __init__(self, model, data, warmup=3, stress=False):
         if not data.pos.is_cuda:
             raise RuntimeError("GraphedStep needs GPU tensors")
         if model.training:
             raise RuntimeError("GraphedStep captures the eval() path")
-        self.model, self.data = model, data
+        self.model, self.data, self.stress = model, data, bool(stress)
+        self.virial = None
         self.pos = data.pos.detach().clone().requires_grad_(True)      # static input
         data.pos = self.pos
         side = torch.cuda.Stream()
@@ -42,7 +45,10 @@ class GraphedStep(object):
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.energy, self.forces = self._eager()
+            out = self._eager()
+        self.energy, self.forces = out[:2]
+        if self.stress:
+            self.virial = out[2]
         torch.cuda.synchronize()
         # the captured topology: the tensor OBJECTS (kept alive here, so their addresses cannot be handed to a rebuilt
         # list of the same size) and their versions (in-place edits); taken after the first forward, which fills in a
@@ -50,6 +56,9 @@ class GraphedStep(object):
         self._topo = self._topology(data)
 
     def _eager(self):
+        if self.stress:
+            from .stress import energy_forces_virial
+            return energy_forces_virial(self.model, self.data, self.pos)
         e = self.model(self.data)
         f = -torch.autograd.grad(e.sum(), self.pos)[0]
         return e.detach(), f
@@ -70,6 +79,8 @@ class GraphedStep(object):
             with torch.no_grad():
                 self.pos.copy_(pos)
         self.graph.replay()
+        if self.stress:
+            return self.energy, self.forces, self.virial
         return self.energy, self.forces
 
 
@@ -81,15 +92,25 @@ class GraphedMDStep(object):
     What makes the launch geometry independent of the edge count: the list is padded to `capacity` columns with NULL
     edges that the relation build files behind every row (`neighbor.neighbor_search_padded`), and the search itself runs
     without a host read, library sort or memset.  model: HVNet in eval(), parameters not requiring grad; one periodic
-    structure (atomic_number [N], cell [3,3], both on the GPU and unchanged for the life of the object; `pos` [N,3] gives
-    the first coordinates).  `capacity` defaults to the first list's edge count + 4 %.
+    structure (atomic_number [N], cell [3,3], both on the GPU and unchanged for the life of the object -- unless
+    `variable_cell`, below --; `pos` [N,3] gives the first coordinates).  `capacity` defaults to the first list's edge count + 4 %.
 
         step = GraphedMDStep(model, z, cell, pos0)
         e, f = step(pos)            # static outputs: valid until the next call
         ok, n_edges = step.check()  # a host read -- do it when e / f are copied to the host anyway; not ok: the list
-                                    # outgrew the capacity (or left the cell by > 8 images): `step.recapture(pos)`"""
+                                    # outgrew the capacity (or left the cell by > 8 images): `step.recapture(pos)`
 
-    def __init__(self, model, atomic_number, cell, pos, capacity=None, warmup=3, reference_compat=False):
+    `stress=True`: the capture contains the virial kernels; a call returns (energy, forces, virial [1,3,3]) and `fetch()`
+    carries the nine virial values in its one packed copy (a fifth result).
+    `variable_cell=True`: the cell is a static INPUT like the coordinates -- `step(pos, cell)` copies a new [3,3] cell into
+    the device tensor that search, edge geometry and virial kernels read (`neighbor_search_padded(..., device_cell=True)`:
+    the bin geometry is made on the device, no host copy of the cell is consulted), so one capture serves NPT dynamics and
+    cell relaxation.  A degenerate cell (singular, or far smaller than the cutoff) cannot raise inside a replay: flag bit 3
+    makes `check()` / `fetch()` report "not ok" (`last_flags & 8`), the step's numbers are to be discarded and the capture
+    stays valid for the next sane cell."""
+
+    def __init__(self, model, atomic_number, cell, pos, capacity=None, warmup=3, reference_compat=False, stress=False,
+                 variable_cell=False):
         from .neighbor import neighbor_search, padded_capacity
         self.reference_compat = bool(reference_compat)      # edge conventions of the reference's own pipeline (neighbor.py)
         if not pos.is_cuda or cell is None:
@@ -97,6 +118,10 @@ class GraphedMDStep(object):
         if model.training:
             raise RuntimeError("GraphedMDStep captures the eval() path")
         self.model, self.z, self.cell = model, atomic_number, cell
+        self.stress, self.variable_cell = bool(stress), bool(variable_cell)
+        self.virial, self.last_flags = None, 0
+        if self.variable_cell:
+            self.cell = cell.detach().float().reshape(3, 3).contiguous().clone()      # static input
         self.batch = torch.zeros(atomic_number.numel(), dtype=torch.long, device=pos.device)
         self.pos = pos.detach().clone().float().requires_grad_(True)      # static input
         self._warmup = warmup
@@ -109,10 +134,14 @@ class GraphedMDStep(object):
         from .data import Data
         from .neighbor import neighbor_search_padded
         ei, sh, total = neighbor_search_padded(self.pos.detach(), self.model.rc, self.cell, self.capacity,
-                                               reference_compat=self.reference_compat)
+                                               reference_compat=self.reference_compat, device_cell=self.variable_cell)
         d = Data(pos=self.pos, atomic_number=self.z, batch=self.batch, cell=self.cell.reshape(1, 3, 3), edge_index=ei,
                  edge_shift=sh)
         d._hn_edge_count = total
+        if self.stress:
+            from .stress import energy_forces_virial
+            e, f, w = energy_forces_virial(self.model, d, self.pos)
+            return e, f, total, w
         e = self.model(d)
         f = -torch.autograd.grad(e.sum(), self.pos)[0]
         return e.detach(), f, total
@@ -134,24 +163,38 @@ class GraphedMDStep(object):
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.energy, self.forces, self.total = self._eager()
+            out = self._eager()
+            self.energy, self.forces, self.total = out[:3]
             # everything a caller copies to the host per step, as ONE array (`fetch`): energies | (edges, flags) | forces
-            self.packed = torch.cat([self.energy.double().reshape(-1), self.total.double(), self.forces.double().reshape(-1)])
+            # (| virial with `stress`)
+            parts = [self.energy.double().reshape(-1), self.total.double(), self.forces.double().reshape(-1)]
+            if self.stress:
+                self.virial = out[3]
+                parts.append(self.virial.double().reshape(-1))
+            self.packed = torch.cat(parts)
         self._host = None
         torch.cuda.synchronize()
 
-    def __call__(self, pos=None):
-        """`pos` [N,3]: a device tensor, or a float32 host tensor (uploaded straight into the captured input)."""
-        if pos is not None:
-            with torch.no_grad():
+    def __call__(self, pos=None, cell=None):
+        """`pos` [N,3]: a device tensor, or a float32 host tensor (uploaded straight into the captured input); `cell` [3,3]
+        likewise (`variable_cell=True` only)."""
+        if cell is not None and not self.variable_cell:
+            raise RuntimeError("GraphedMDStep: the cell is baked into this capture (construct it with variable_cell=True)")
+        with torch.no_grad():
+            if pos is not None:
                 self.pos.copy_(pos)
+            if cell is not None:
+                self.cell.copy_(cell.reshape(3, 3))
         self.graph.replay()
+        if self.stress:
+            return self.energy, self.forces, self.virial
         return self.energy, self.forces
 
     def fetch(self):
         """The last call's results on the host through ONE device-to-host copy and one synchronisation (separate reads of
         the energy, the forces and the list's counters cost a round trip each -- as much as the whole replay of a small
-        cell): (energy [graphs] float32 array, forces [N,3] float32 array, list complete?, edges found)."""
+        cell): (energy [graphs] float32 array, forces [N,3] float32 array, list complete?, edges found), with `stress` also
+        the virial [graphs,3,3] float32 array as a fifth result.  `last_flags` keeps the list's flags."""
         import numpy as np
         from .neighbor import _stash_overflowed
         if self._host is None:
@@ -161,21 +204,30 @@ class GraphedMDStep(object):
         h = self._host.numpy()
         ng = self.energy.numel()
         n_edges, flags = int(h[ng]), int(h[ng + 1])
+        self.last_flags = flags
         if flags & 2:
             _stash_overflowed(self.packed.device)        # (the repeat gets a larger stash slot per atom)
+        if self.stress:
+            nf = self.forces.numel()
+            return (h[:ng].astype(np.float32), h[ng + 2:ng + 2 + nf].astype(np.float32).reshape(-1, 3), flags == 0, n_edges,
+                    h[ng + 2 + nf:].astype(np.float32).reshape(-1, 3, 3))
         return h[:ng].astype(np.float32), h[ng + 2:].astype(np.float32).reshape(-1, 3), flags == 0, n_edges
 
     def check(self):
         """(list complete?, edges found) of the last call: one host read."""
         from .neighbor import padded_list_ok
-        return padded_list_ok(self.total)
+        ok, n_edges = padded_list_ok(self.total)
+        self.last_flags = 0 if ok else int(self.total[1])
+        return ok, n_edges
 
-    def recapture(self, pos=None, capacity=None):
+    def recapture(self, pos=None, capacity=None, cell=None):
         """A new graph for a larger capacity (default: from the last edge count); returns the step's results."""
         from .neighbor import padded_capacity
-        if pos is not None:
-            with torch.no_grad():
+        with torch.no_grad():
+            if pos is not None:
                 self.pos.copy_(pos)
+            if cell is not None and self.variable_cell:
+                self.cell.copy_(cell.reshape(3, 3))
         if capacity is None:
             capacity = padded_capacity(max(int(self.total[0]), self.capacity))
         self._capture(int(capacity))

@@ -280,14 +280,13 @@ class HVNet(nn.Module):
 
     @staticmethod
     def _check_atom_props(train, shard):
-        """Per-atom outputs are first-order eval() results of whole, unsharded graphs, computed eagerly: refuse the rest."""
+        """Per-atom outputs and the per-graph virial are first-order eval() results of whole, unsharded graphs: refuse the
+        rest.  (Nothing on their path reads the host, so they may run inside a captured hipGraph.)"""
         if train:
-            raise NotImplementedError("per-atom outputs are eval() results: not in train() or with eval_param_grads")
+            raise NotImplementedError("per-atom outputs / virials are eval() results: not in train() or with eval_param_grads")
         if shard is not None:
-            raise NotImplementedError("per-atom outputs of atom-sharded data: the ghost atoms' shares would have to be sent "
-                                      "back to their owners, which is not implemented")
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            raise NotImplementedError("per-atom outputs are not available inside a captured hipGraph")
+            raise NotImplementedError("per-atom outputs / virials of atom-sharded data: the ghost atoms' shares would have to "
+                                      "be sent back to their owners, which is not implemented")
 
     def _atom_energies(self, e_rows, graph, batch):
         """The read-out term of every atom (hermnet.py:129) in atom order; intensive models: divided by its graph's atom
@@ -297,7 +296,8 @@ class HVNet(nn.Module):
             if graph.num_graphs == 1:
                 e = e / max(graph.num_atoms, 1)
             else:
-                cnt = torch.bincount(batch.long(), minlength=graph.num_graphs).clamp(min=1).to(e.dtype)
+                # (the atom counts of the read-out's per-graph sums: the same integers as a bincount, without its host read)
+                cnt = graph.graph_lengths.clamp(min=1).to(e.dtype)
                 e = e / cnt.index_select(0, batch.long())
         return e
 
@@ -376,7 +376,7 @@ class HVNet(nn.Module):
         if train:
             edge, edge_parts = self._edge_geometry_autograd(pos, data.get("cell"), graph)
         else:
-            if props is not None and props.want_virials:
+            if props is not None and (props.want_virials or props.want_graph_virial):
                 edge = EdgeGeometry.apply(pos, data.get("cell"), graph, props)    # (its backward fills props.virials)
             else:
                 edge = EdgeGeometry.apply(pos, data.get("cell"), graph)      # with_edge, hermnet.py:133-152
@@ -448,7 +448,7 @@ class HVNet(nn.Module):
         else:
             e_rows = EnergyHead.apply(x.contiguous(), *[p.detach() for p in head_params],
                                       graph.row_real if single else shard_rows)
-        if props is not None:
+        if props is not None and props.want_energies:
             props.energies = self._atom_energies(e_rows, graph, data.batch)
         if shard_rows is not None:
             energy = e_rows.sum().reshape(1)

@@ -216,17 +216,22 @@ def _neighbor_search_device(pos, rc, cell, reference_compat, target_mask=None):
     return (edge_index, shift) if periodic else edge_index
 
 
-def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, target_mask=None):
+def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, target_mask=None, device_cell=False):
     """The device cell list WITHOUT its host read: `capacity` columns are provided up front, the pairs
     found fill the first E of them and the rest become NULL edges (-1, -1; shift 0), which the relation build files behind
     every row -- the model runs on the padded list unchanged, with a launch geometry that does not depend on E.
 
     Returns (edge_index [2, capacity] int64, edge_shift [capacity, 3] float32 or None, total [2] int64 ON THE DEVICE):
-    total[0] = E, total[1] = flags; read them when the step's results are copied to the host anyway.  The list is
+    total[0] = E, total[1] = flags (include/hermnet_hip.h); read them when the step's results are copied to the host anyway.  The list is
     complete iff `padded_list_ok(total)`; otherwise (more pairs than columns, an atom with more pairs than its stash slot,
     coordinates many cells away from the cell) repeat with `neighbor_search` and a larger capacity.  GPU tensors only;
     open systems need `reference_compat=False` (the 32-neighbour cap is a host-side filter).
-    `target_mask` [N] bool / uint8 (atom shards): list only the pairs whose target atom (row 1) is flagged."""
+    `target_mask` [N] bool / uint8 (atom shards): list only the pairs whose target atom (row 1) is flagged.
+    `device_cell=True` (periodic cells): the cell is read from DEVICE memory by the search itself -- no host copy of it is
+    consulted (`_cell_on_host`), so a captured search follows a `cell` tensor that is rewritten between replays
+    (graph.GraphedMDStep, `variable_cell`).  `cell` must then be a contiguous float32 [3,3] (or [1,3,3]) GPU tensor; for the
+    same values the list is bit for bit the host-cell form's.  A degenerate cell (singular, or far smaller than the
+    cutoff), which the host-cell form refuses with an error, raises flag bit 3 of total[1] instead."""
     import ctypes
     from . import _lib
     if not pos.is_cuda:
@@ -241,7 +246,12 @@ def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, targ
     N, cap = int(p32.size(0)), int(capacity)
     dbl3 = ctypes.c_double * 3
     cell_h = lo_h = hi_h = None
-    if cell is not None:
+    if device_cell:
+        if cell is None or not cell.is_cuda or cell.dtype != torch.float32 or cell.numel() != 9 or not cell.is_contiguous():
+            raise ValueError("device_cell=True needs a contiguous float32 [3,3] cell on the GPU")
+        if N == 0:
+            raise ValueError("device_cell=True needs at least one atom")
+    elif cell is not None:
         cell_h = (ctypes.c_double * 9)(*_cell_on_host(cell))
     else:       # (an open system's bounding box is a host read of its own: periodic cells are the MD case)
         mm = torch.stack([p32.min(0).values, p32.max(0).values]).double().cpu().tolist()
@@ -262,8 +272,12 @@ def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, targ
         edge_index.fill_(0x3f3f3f3f3f3f3f3f)
         if shift is not None:
             shift.fill_(float("nan"))
-    _lib.check(lib.hermnet_neighbor_count(P(p32), N, cell_h, lo_h, hi_h, float(rc), P(work), ws_bytes, P(mask), P(total), stream),
-               "hermnet_neighbor_count")
+    if device_cell:
+        _lib.check(lib.hermnet_neighbor_count_devcell(P(p32), N, P(cell), float(rc), P(work), ws_bytes, P(mask), P(total), stream),
+                   "hermnet_neighbor_count_devcell")
+    else:
+        _lib.check(lib.hermnet_neighbor_count(P(p32), N, cell_h, lo_h, hi_h, float(rc), P(work), ws_bytes, P(mask), P(total),
+                                              stream), "hermnet_neighbor_count")
     sign = 1.0 if reference_compat else -1.0
     _lib.check(lib.hermnet_neighbor_fill_padded(N, P(work), ws_bytes, cap, sign, 0 if periodic else 1, P(edge_index), P(shift),
                                                 P(total), stream), "hermnet_neighbor_fill_padded")

@@ -84,15 +84,34 @@ class AtomSink(object):
     cached graph).  `HVNet.forward` fills `energies` [N] (atom order, intensive models already divided by their graph's atom
     count); with `virials=True` the first position backward through `EdgeGeometry` fills `virials` [N,3,3] (atom order,
     W_i = -1/2 sum_{e touching i} D_e (x) dE/dD_e, include/hermnet_hip.h: hermnet_edge_geometry_bwd_virial).  Later backward
-    passes through the same forward (the stress path's cell gradient) leave it as it is."""
+    passes through the same forward (the stress path's cell gradient) leave it as it is.
+    `graph_virial=True` (stress.energy_forces_stress, the captured steps): the same backward also fills `graph_virial`
+    [B,3,3] = the ordered per-graph sums of the W_i (hermnet_graph_virial); `energies=False` skips the per-atom energies."""
 
-    def __init__(self, virials=True):
+    def __init__(self, virials=True, graph_virial=False, energies=True):
         self.want_virials = bool(virials)
-        self.energies = self.virials = None
+        self.want_graph_virial = bool(graph_virial)
+        self.want_energies = bool(energies)
+        self.energies = self.virials = self.graph_virial = None
 
     def reset(self):
-        self.energies = self.virials = None
+        self.energies = self.virials = self.graph_virial = None
         return self
+
+
+def graph_virial(vrows, graph):
+    """[B,3,3] ordered per-graph sums of the per-atom virial rows `vrows` [rows,9] of `graph` (hermnet_graph_virial: two
+    launches, no atomics, no host read)."""
+    lib = _lib.load()
+    B, n = int(graph.num_graphs), int(graph.num_atoms)
+    if n == 0 or B == 0:
+        return torch.zeros(B, 3, 3, dtype=torch.float32, device=vrows.device)
+    out = torch.empty(B, 9, dtype=torch.float32, device=vrows.device)
+    wbytes = lib.hermnet_graph_virial_workspace(n)
+    work = torch.empty(wbytes, dtype=torch.uint8, device=vrows.device)
+    _lib.check(lib.hermnet_graph_virial(P(vrows), P(graph.row_of_node), P(graph.graph_perm), P(graph.batch32), n, B, P(work), wbytes,
+                                        P(out), _stream()), "hermnet_graph_virial")
+    return out.view(B, 3, 3)
 
 
 class EdgeGeometry(torch.autograd.Function):
@@ -135,8 +154,8 @@ class EdgeGeometry(torch.autograd.Function):
                                          lengths=rp_s[1:] - rp_s[:-1], unsafe=True)                      # [TR*Ns,3]
             gpos_rows = outof.view(TR, graph.num_src, 3).sum(0)
             gpos_rows[:Te * B_] -= into.view(Te, P_, B_, 3).sum(1).reshape(Te * B_, 3)
-        elif ctx.sink is not None and ctx.sink.virials is None:
-            # per-atom virials wanted and not yet taken: the same position gradient (bit for bit) with W_i alongside
+        elif ctx.sink is not None and ctx.sink.virials is None and ctx.sink.graph_virial is None:
+            # virials wanted and not yet taken: the same position gradient (bit for bit) with W_i alongside
             pos_c, cell_c = ctx.keep
             csc = graph.out_rowptr is None
             vrows = torch.empty(graph.N, 9, dtype=torch.float32, device=gD.device)
@@ -147,7 +166,10 @@ class EdgeGeometry(torch.autograd.Function):
                 _lib.ptr(graph.src_id), _lib.ptr(graph.tgt_id), _lib.ptr(graph.shift if cell_c is not None else None),
                 _lib.ptr(cell_c), _lib.ptr(graph.batch32), graph.N, _lib.ptr(gpos_rows), _lib.ptr(vrows), _stream()),
                 "hermnet_edge_geometry_bwd_virial")
-            ctx.sink.virials = vrows.index_select(0, graph.row_of_node).view(-1, 3, 3)
+            if ctx.sink.want_virials:
+                ctx.sink.virials = vrows.index_select(0, graph.row_of_node).view(-1, 3, 3)
+            if ctx.sink.want_graph_virial:
+                ctx.sink.graph_virial = graph_virial(vrows, graph)
         elif graph.out_rowptr is None:      # device-built graphs: out-edges from the CSC order (one sort fewer)
             _lib.check(lib.hermnet_edge_geometry_bwd_csc(
                 _lib.ptr(gD), _lib.ptr(graph.csr_rowptr), _lib.ptr(graph.csc_rowptr), _lib.ptr(graph.csc_pos),

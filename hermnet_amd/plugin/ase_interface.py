@@ -183,17 +183,23 @@ class NNCalculator(_Base):
     implemented_properties = ['energy', 'free_energy', 'forces', 'stress', 'energies', 'stresses']
 
     def __init__(self, model, model_path, trn_mean, device_='cuda', ensemble='NVT', reference_compat=False,
-                 graph_replay=False):
+                 graph_replay=False, replay_stress=False):
         """`graph_replay=True` (GPU, periodic cell, forces without stress): neighbour search + relation build + forward +
         force backward are captured ONCE as a hipGraph and replayed every call (`graph.GraphedMDStep`; the same kernels, no
         per-launch host work: 2-3x on cells of a few hundred atoms, where the eager step is bound by launch overhead).
         The capture is renewed by itself when the species, the cell, the atom count or the model's weights
         (`load_state_dict`, `.to()`, `invalidate_caches()`) change or the list outgrows its capacity; weights written
         through `.data` need `model.invalidate_caches()` as everywhere else.  Calls that need the stress or a per-atom
-        property (`energies`, `stresses`: `atomic.atom_properties`), open systems and CPU runs take the eager path."""
+        property (`energies`, `stresses`: `atomic.atom_properties`), open systems and CPU runs take the eager path.
+        `replay_stress=True` (with `graph_replay`): the ONE capture is a `GraphedMDStep(stress=True, variable_cell=True)` --
+        the virial comes out of the same force backward (`stress.energy_forces_virial`) and the cell is an input that is
+        uploaded with the coordinates every call, so calls that need the stress (or an NPT ensemble) and calls with a new
+        cell replay too: a cell change alone never recaptures.  A degenerate cell (flag bit 3 of the captured search) drops
+        the capture and lets the eager path answer."""
         super(NNCalculator, self).__init__()
         self.reference_compat = reference_compat     # see `build_graph`
         self.graph_replay = bool(graph_replay)
+        self.replay_stress = bool(replay_stress)
         self._graphed = None              # ((z tensor, cell tensor, N), GraphedMDStep)
         self.graph_captures = 0           # how often a step was captured (diagnostics / tests)
         self.device_ = device_
@@ -208,29 +214,38 @@ class NNCalculator(_Base):
         self._edge_capacity = None        # columns of the padded neighbour list of the next call (None: exact search)
 
     def _replayed(self, cell, elems, positions):
-        """(energy tensor, forces tensor) from the captured step, or None when this call has to run eagerly."""
+        """(energy, forces array, virial [3,3] array or None) from the captured step, or None when this call has to run
+        eagerly.  With `replay_stress` the cell is an input of the capture (uploaded per call, never part of its key)."""
         from ..graph import GraphedMDStep
         dev = torch.device(self.device_)
         z, _batch = _species_tensors(elems, dev)
-        cell_t = _cell_tensor(cell, dev)
+        var = self.replay_stress
         pos_t = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32))     # host: copied into the captured input
+        if var:
+            # (float32 values of the float64 cell: the numbers `_cell_tensor` hands the eager path)
+            cell_t, cell_in = None, torch.from_numpy(np.asarray(cell, dtype=np.float64).reshape(3, 3)).float()
+        else:
+            cell_t, cell_in = _cell_tensor(cell, dev), None
         g = self._graphed
         if (g is None or g[0][0] is not z or g[0][1] is not cell_t or g[0][2] != pos_t.size(0) or g[1].stale()
-                or g[1].model is not self.model):
+                or g[1].model is not self.model or g[1].variable_cell != var):
             if self.model.training:
                 self.model.eval()
-            step = GraphedMDStep(self.model, z, cell_t, pos_t.to(dev), reference_compat=self.reference_compat)
+            step = GraphedMDStep(self.model, z, cell_in.to(dev) if var else cell_t, pos_t.to(dev),
+                                 reference_compat=self.reference_compat, stress=var, variable_cell=var)
             self._graphed = g = ((z, cell_t, pos_t.size(0)), step)
             self.graph_captures += 1
-        g[1](pos_t)
-        e, f, ok, _n = g[1].fetch()            # ONE device-to-host copy: energy, forces and the list's counters
-        if not ok:                             # the list outgrew its columns: a larger capture, this step again
-            g[1].recapture(pos_t)
+        g[1](pos_t, cell_in)
+        out = g[1].fetch()                     # ONE device-to-host copy: energy, forces (, virial) and the list's counters
+        if not out[2] and not (g[1].last_flags & 8):       # the list outgrew its columns: a larger capture, this step again
+            g[1].recapture(pos_t, cell=cell_in)
             self.graph_captures += 1
-            e, f, ok, _n = g[1].fetch()
-            if not ok:                         # (coordinates many images outside the cell ...): the eager path decides
-                self._graphed = None
-                return None
+            out = g[1].fetch()
+        if not out[2]:                         # (a degenerate cell, coordinates many images outside the cell ...): the
+            self._graphed = None               # capture is dropped and the eager path decides
+            return None
+        e, f = out[0], out[1]
+        w = out[4][0] if var else None
         if not np.isfinite(e[0]):
             # The captured step contains the stale-cache guard's check-and-poison kernel, and a replay cannot read its flag:
             # after a write through `.data` (an EMA swap) EVERY replay would return NaN.  The results are on the host here:
@@ -240,7 +255,7 @@ class NNCalculator(_Base):
             self.model.invalidate_caches()
             self._graphed = None
             return None
-        return float(np.float32(e[0]) + np.float32(self.trn_mean)), f
+        return float(np.float32(e[0]) + np.float32(self.trn_mean)), f, w
 
     def calculate(self, atoms, properties=('energy',), system_changes=all_changes):
         super(NNCalculator, self).calculate(atoms, properties, system_changes)
@@ -253,8 +268,9 @@ class NNCalculator(_Base):
         dev = self.device_ if torch.device(self.device_).type == 'cuda' else None
         # per-atom properties: computed in the eager evaluation (never in a replayed graph), energy / forces / stress as always
         per_atom = [k for k in ('energies', 'stresses') if k in tuple(properties)]
+        want_stress = self.ensemble.lower() == 'npt' or 'stress' in tuple(properties)
         if (self.graph_replay and dev is not None and pbc and cell is not None and np.any(cell)
-                and self.ensemble.lower() != 'npt' and 'stress' not in tuple(properties) and not per_atom):
+                and (self.replay_stress or not want_stress) and not per_atom):
             out = self._replayed(cell, elems, atoms.positions)
             if out is not None:
                 self.results['energy'] = out[0]
@@ -262,6 +278,10 @@ class NNCalculator(_Base):
                 self.results['forces'] = out[1]
                 for k in ('stress', 'energies', 'stresses'):
                     self.results.pop(k, None)      # (not computed: see the end of this method)
+                if want_stress:                    # (`replay_stress`: the virial of the replayed backward)
+                    w = np.asarray(out[2], dtype=np.float64)
+                    volume = abs(float(np.linalg.det(np.asarray(cell, dtype=np.float64).reshape(3, 3))))
+                    self.results['stress'] = stress_from_virial(0.5 * (w + w.T), volume)
                 return
         # periodic cells on the GPU: from the second call on the neighbour list is built without its host read, padded to a
         # capacity taken from the last edge count; count and flags are checked behind the step, where the results are

@@ -16,7 +16,8 @@
  *   - float = IEEE fp32 (the reference is fp32-only), indices = int32 (int64 where a parameter says so:
  *     the caller's edge_index / atomic_number / halo index lists arrive as torch LongTensors).
  *
- * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial was added within v13 (a new entry point only, nothing
+ * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
+ * hermnet_neighbor_count_devcell were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -120,7 +121,8 @@ typedef struct hn_graph {
  * output sorted by (i, j, Sx, Sy, Sz).  Two calls around one host read:
  *   hermnet_neighbor_count  -> total_device[0] = E, total_device[1] = flags (bit 0: an |S| component exceeded 8 --
  *                              coordinates many cells away from the cell: wrap them or use the host path; bit 1: an
- *                              atom has more pairs than the per-atom key stash holds); keeps its state in `workspace`
+ *                              atom has more pairs than the per-atom key stash holds; bit 3: the device-cell form met
+ *                              a degenerate cell, see below); keeps its state in `workspace`
  *   hermnet_neighbor_fill   -> edge_index [2,E] int64, edge_shift [E,3] = shift_sign * S.  stash_ok = 1 (flag bit 1
  *                              clear): the keys stashed by the counting pass are rank-sorted per atom and decoded --
  *                              no second pass over the candidates, no global sort; stash_ok = 0: two-pass form through
@@ -150,6 +152,18 @@ size_t hermnet_neighbor_workspace_for(int num_atoms, int stash_per_atom);
 int hermnet_neighbor_count(const float* pos, int num_atoms, const double* cell_host, const double* lo_host,
                            const double* hi_host, double rc, void* workspace, size_t workspace_bytes,
                            const unsigned char* target_ok, long* total_device /* [2] */, void* stream);
+/* The counting pass of a periodic cell that lives in DEVICE memory (ABI 13, additive): `cell` [9] float32, rows = lattice
+ * vectors.  A single-thread kernel builds the search geometry (inverse, plane spacings, bin grid, reach, coarsening) from it
+ * in float64 exactly as the host does for hermnet_neighbor_count, so for the same float32 cell values the list is bit for
+ * bit the same; nothing about the cell is baked into the launches (those that follow the bin count are sized by the bound
+ * the workspace is carved for), so search + step captured into one hipGraph follow a cell that changes between replays.
+ * Follow it with hermnet_neighbor_fill_padded on the same workspace.  A cell the host form refuses with HN_ERR_BAD_ARG
+ * (singular, or so small that the cutoff reaches beyond 8 bins) raises flag bit 3 (value 8) in total_device[1] instead:
+ * the kernels then run on an inert geometry (no pair is listed, nothing is read or written out of bounds) and the caller
+ * must discard the step.  HN_ERR_BAD_ARG: num_atoms <= 0, rc <= 0, a missing pointer, a workspace too small. */
+int hermnet_neighbor_count_devcell(const float* pos, int num_atoms, const float* cell, double rc, void* workspace,
+                                   size_t workspace_bytes, const unsigned char* target_ok, long* total_device /* [2] */,
+                                   void* stream);
 int hermnet_neighbor_fill(const float* pos, int num_atoms, const double* cell_host, const double* lo_host,
                           const double* hi_host, double rc, void* workspace, size_t workspace_bytes,
                           long num_edges, float shift_sign, int source_first, int stash_ok,
@@ -252,6 +266,22 @@ int hermnet_edge_geometry_bwd_virial(const float* gD, const int* csr_rowptr, con
                                      int num_rel, const int* out_rowptr, const int* out_edges, const float* pos,
                                      const int* src_id, const int* tgt_id, const float* shift, const float* cell,
                                      const int* batch, int num_nodes, float* gpos, float* atom_virial, void* stream);
+/* Per-graph virial (ABI 13, additive): graph_virial[b] = sum_{atoms i of graph b} W_i  [B,9], W_i = atom_virial[row_of_node[i]]
+ * as written by the entry point above -- so graph_virial[b] = -sum_{e in b} D_e (x) gD_e, unsymmetrised, energy units; the
+ * stress of graph b is -sym(graph_virial[b]) / V_b.  Rows are gathered in atom order through row_of_node [N] int64, so
+ * padding rows never enter a sum.  `batch` [N] int32 (original atom order, values in [0, B)) and `graph_perm` [N] int64 =
+ * the atoms sorted by graph (stable) are the pair the read-out's ordered per-graph energy sum uses: batch need not be sorted,
+ * batch[graph_perm[.]] is.  graph_perm NULL: batch is already sorted; num_graphs = 1: both are ignored (every atom counts).
+ * Two launches: sums of fixed chunks of 256 atoms (in graph order), then one workgroup per graph adds the chunks inside its
+ * range and the atoms of its ragged ends in a fixed order -- no atomics, no memset / memcpy, no host read: bit-reproducible
+ * and graph-capturable; every element of graph_virial is written (a graph without atoms gets zeros).  `workspace`: at least
+ * hermnet_graph_virial_workspace bytes for num_nodes.  num_graphs = 0 or num_nodes = 0: HN_OK, nothing is launched (without
+ * atoms there is no row to sum: the caller's zeros stand).  HN_ERR_BAD_ARG before any launch: a negative count, a missing
+ * pointer (batch with num_graphs > 1), a workspace too small. */
+size_t hermnet_graph_virial_workspace(int num_nodes);
+int hermnet_graph_virial(const float* atom_virial, const long* row_of_node, const long* graph_perm, const int* batch,
+                         int num_nodes, int num_graphs, void* workspace, size_t workspace_bytes, float* graph_virial,
+                         void* stream);
 
 /* ---- A3+A7(rbf_proj)+A8+A9+A10 and the residual of A6 ---------------------------------------
  * Replaces, for ALL relations of one HeteroVertexConv layer at once,
