@@ -11,8 +11,8 @@ from .elements import atomic_numbers
 from .ops import EdgeGeometry, TrueEdgeGradient, edge_radial_table
 from .relations import RelationalGraph
 from .sharding import HaloExchange, HaloExchangeFeatures, HaloGradReturn, SumAcrossRanks
-from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, LayerWeights, _node_chain_enabled, _PENDING,
-                    _PRE_NEXT)
+from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, GemmRelationalLayer, LayerWeights, Route,
+                    StepState)
 from .rmnet import PaiNNModule, RadialBasis, ScaledSiLU, relational_layer
 
 
@@ -34,17 +34,17 @@ class HeteroVertexConv(nn.Module):
         # layer that consumes them).  The fused chain path overlaps it with its node projection; every other path runs
         # it first.
         halo, data._hn_halo = data.get("_hn_halo"), None
-        w = None
+        step = data._hn_step                     # (layer.StepState of this evaluation)
+        li = step.layer
         ready = data.get("_hn_weights")          # (HVNet.forward refreshed every layer's copies up front: guard.ParamGuard)
-        if ready is not None and ready[data.get("_hn_layer", 0)].mods[0] is next(iter(self.mods.values())):
-            w = ready[data.get("_hn_layer", 0)]
-        if w is None and halo is not None and data.get("_hn_edge_embed") is None and switches.fused_layer:
+        w = ready[li] if (ready is not None and ready[li].mods[0] is next(iter(self.mods.values()))) else None
+        if w is None and data.get("_hn_edge_embed") is None and switches.fused_layer:
             if self._weights is None:
                 self._weights = LayerWeights(self.mods.values())
             w = self._weights.refresh()
         # (the exchange inside the layer needs the chain kernels and the channel-per-lane backward, which takes row ranges;
         # switches.halo_overlap() == "0" runs the blocking exchange in front of the layer instead)
-        if halo is not None and not (w is not None and w.chain and _node_chain_enabled()
+        if halo is not None and not (w is not None and w.chain and switches.node_chain
                                      and halo.fwd_early is not None and g.N * 3 * data.x.size(1) * 4 < 2 ** 32
                                      # (a rank that neither sends nor receives joins the collective in its plain form:
                                      # nothing to hide, and the asynchronous form costs ~15 us of stream hand-offs)
@@ -61,39 +61,37 @@ class HeteroVertexConv(nn.Module):
             # debugging path: same kernels for the edge part, node algebra through PyTorch autograd
             data.x, data.vec = relational_layer(self.mods.values(), data.x, data.vec, data._hn_edge, g, data._hn_rbf)
             return data
-        if self._weights is None:
-            self._weights = LayerWeights(self.mods.values())
-        handles, li = data.get("_hn_edge_handles"), data.get("_hn_layer", 0)
+        handles = data.get("_hn_edge_handles")
         edge = data._hn_edge if handles is None else handles[li]
-        w = w if w is not None else self._weights.refresh()
+        node, data._hn_chain_node = data.get("_hn_chain_node"), None
+        if not (w.chain and switches.node_chain):
+            # library GEMMs joined by the stage kernels (the only path for widths the chain kernels are not instantiated for)
+            if halo is not None:
+                raise RuntimeError("the in-layer halo exchange belongs to the chain path")
+            data.x, data.vec = GemmRelationalLayer.apply(data.x, data.vec, edge, g, data._hn_rbf, w, step)
+            return data
         # (x, vec) straight from the chain layer below -- both still carry THAT autograd node (an in-place exchange of halo
         # rows or any other op in between replaces it) -- and this layer is their only reader: its backward may hand its
-        # input gradients down as partial sums (layer.FusedRelationalLayer, `defer`)
-        node = data.get("_hn_chain_node")
+        # input gradients down as partial sums (layer.Route, `defer`)
         # (not under anomaly detection -- its NaN check would read the not-yet-filled buffers -- and not when a tensor hook
         # would: both are debugging situations, which get the finishing launches; switches.defer_sums() forces them)
         straight = (node is not None and data.vec is not None and data.x.grad_fn is node and data.vec.grad_fn is node
                     and not g.num_src and not torch.is_anomaly_enabled()
                     and not getattr(data.x, "_backward_hooks", None) and not getattr(data.vec, "_backward_hooks", None))
-        defer = straight and halo is None and (data.get("_hn_shard") is None or data.get("_hn_lone"))
-        # atom shards: the exchange in its "proj" form (layer.FusedRelationalLayer; switches.halo_overlap() "1": the round-4
-        # form, x | vec rows with windowed node launches around the exchange; "0": the blocking exchange in front of the layer)
-        proj = straight and halo is not None and switches.halo_overlap() not in ("0", "1")
-        # the node projection of THIS x, already computed: the first layer's by HVNet.forward (side stream), every later layer's
-        # by the fused update launch of the layer below (round 5)
-        pre, data._hn_pre0 = data.get("_hn_pre0"), None
-        if pre is not None and not (w.chain and _node_chain_enabled() and halo is None
-                                    and pre[0].data_ptr() == data.x.data_ptr() and pre[0].shape == data.x.shape):
-            pre = None
-        # the next layer's weights: its projection of the rows this layer produces can run inside this layer's update launch
-        w_next = None
-        if ready is not None and li + 1 < len(ready) and halo is None and (data.get("_hn_shard") is None or data.get("_hn_lone")):
-            w_next = ready[li + 1]
-        data.x, data.vec = FusedRelationalLayer.apply(data.x, data.vec, edge, g, data._hn_rbf, w,
-                                                      data.get("_hn_edge_sink"), li, halo, defer,
-                                                      None if pre is None else pre[1], w_next, proj)
-        data._hn_pre0 = _PRE_NEXT.pop((id(g), li + 1), None)
-        data._hn_chain_node = data.x.grad_fn if (w.chain and _node_chain_enabled() and not g.num_src) else None
+        if halo is not None:
+            # atom shards: the exchange in its "proj" form; switches.halo_overlap() "1": the round-4 form, x | vec rows
+            route = Route("proj" if straight and switches.halo_overlap() not in ("0", "1") else "rows", halo)
+        else:
+            whole = data.get("_hn_shard") is None or data.get("_hn_lone")     # (no peers: the unsharded forms)
+            # the node projection of THIS x, already computed by the fused update launch of the layer below
+            pre = step.pre_next.pop(li, None)
+            if pre is not None and not (pre[0].data_ptr() == data.x.data_ptr() and pre[0].shape == data.x.shape):
+                pre = None
+            # the next layer's weights: its projection of the rows this layer produces can run inside this layer's update launch
+            w_next = ready[li + 1] if (ready is not None and li + 1 < len(ready) and whole) else None
+            route = Route(defer=straight and whole, pre=None if pre is None else pre[1], w_next=w_next)
+        data.x, data.vec = FusedRelationalLayer.apply(data.x, data.vec, edge, g, data._hn_rbf, w, step, route)
+        data._hn_chain_node = None if g.num_src else data.x.grad_fn
         return data
 
 
@@ -369,7 +367,6 @@ class HVNet(nn.Module):
         if Hp != H:
             # widths that are not a multiple of 64 run on the same kernels with zero-padded channels (layer.LayerWeights)
             x = torch.nn.functional.pad(x, (0, Hp - H))
-        data._hn_pre0 = None
         data._hn_weights = None
         if fused and switches.fused_layer:
             data._hn_weights = self._refresh_weights(pos.device)
@@ -402,19 +399,18 @@ class HVNet(nn.Module):
         else:
             data._hn_edge_embed = self.radial_basis(edge[:, 3])
         data.x, data.vec = x, vec
-        data._hn_edge_handles = data._hn_edge_sink = data._hn_halo = data._hn_chain_node = None
+        data._hn_edge_handles = data._hn_halo = data._hn_chain_node = None
+        step = data._hn_step = StepState()       # (what the layers of this evaluation hand to each other)
         if fused and edge.requires_grad and switches.fused_layer:
             # one reduction of the edge gradients per step instead of one per layer (layer.EdgeFanout)
             # (atoms of an unknown element own the rows past type_rowptr[T]; only edges INTO them go unwritten)
             # (the slots of a padded list's NULL edges stay unwritten too, but nothing reads them: the position gradient
             # walks the CSC segments, and NULL edges are in none)
             all_known = graph.num_src == 0 and graph.N == graph.type_rowptr_host[-1]
-            data._hn_edge_sink = EdgeGradSink(len(self.hermconvs), Hp // 64, graph.E, pos.device, zero=not all_known)
-            data._hn_edge_handles = EdgeFanout.apply(edge, data._hn_edge_sink)
-        _PENDING.clear()                      # (leftovers of a backward pass that did not complete)
-        _PRE_NEXT.clear()
+            step.edge_sink = EdgeGradSink(len(self.hermconvs), Hp // 64, graph.E, pos.device, zero=not all_known)
+            data._hn_edge_handles = EdgeFanout.apply(edge, step.edge_sink)
         for li, conv in enumerate(self.hermconvs):
-            data._hn_layer = li
+            step.layer = li
             data = conv(data)
             if row_plan is not None and li + 1 < len(self.hermconvs):
                 # one exchange per layer: (x | vec) rows of halo atoms, 4H floats each -- due before the next layer reads

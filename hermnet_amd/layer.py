@@ -1,24 +1,21 @@
-"""One HeteroVertexConv layer (`HermNet/hermnet.py:37-65` + `rmnet.py:21-32`) as a single
-autograd node with a hand-written first-order backward.
-
-The launch sequence is fixed and short: LayerNorm, 2 GEMMs, the fused message kernel, and per
-relation three GEMMs joined by fused elementwise kernels (`csrc/node_kernels.hip`).  Parameters
-are treated as constants (energy/force evaluation; parameter gradients are not produced --
-the training step runs through the differentiable device-op path, `HVNet.forward` in train() mode).
+"""One HeteroVertexConv layer (`HermNet/hermnet.py:37-65` + `rmnet.py:21-32`) as ONE autograd node with a hand-written
+first-order backward.  `HeteroVertexConv.forward` picks between two Functions and decides the first one's `Route`:
+  FusedRelationalLayer  the chain kernels (csrc/node_chain*.hip, widths up to 512), three launches each way: the node projection
+                        of every relation (LayerNorm + x_proj), the message kernel, the update.  Projection and messages run
+                        locally (`_local_*`) or, on an atom shard, around the exchange of the halo rows: "rows" (x | vec rows
+                        travel, windowed node launches redo the halo tiles: `_halo_rows_*`) or "proj" (projected rows travel
+                        forward, partial sums of gradients backward: `_halo_proj_*`).  `_update_fwd`: the fused layer boundaries.
+  GemmRelationalLayer   switches.node_chain = False, and the only path for widths the chain kernels are not instantiated for:
+                        the node-level linears through library GEMMs joined by the stage kernels (csrc/node_kernels.hip).
+What the layers of one step hand to each other lives on that step's `StepState`.  Parameters are treated as constants
+(energy/force evaluation; parameter gradients are not produced -- the training step runs through the differentiable
+device-op path, `HVNet.forward` in train() mode).
 """
-import os as _os
-
 import torch
 
 from . import _lib, nodeops, switches
-from .ops import _launch, _msg_bwd, _msg_fwd, _stream
-
-P = _lib.ptr
-
-# switches.node_chain = False: node-level linears through library GEMMs joined by the stage kernels (the only path for widths
-# the chain kernels are not instantiated for) instead of the four chain kernels of csrc/node_chain.hip.
-def _node_chain_enabled():
-    return switches.node_chain
+from .ops import _launch, _msg_bwd, _msg_fwd
+from .sharding import _all_to_all_rows_start, comm_wait
 
 
 class LayerWeights(object):
@@ -202,16 +199,88 @@ class EdgeFanout(torch.autograd.Function):
         return (torch.stack(live, 0).sum(0) if live else None), None
 
 
-# gradients handed down as partial sums, keyed by (graph, index of the consuming layer) (nodeops.PendingGrads);
-# an entry lives from one layer's backward to the next one's (HVNet.forward clears leftovers of an interrupted pass)
-_PENDING = {}
-# the NEXT layer's node projection, computed by a layer's fused update launch: (graph, index of the next layer) ->
-# (x_out, (hb, xh, mean, rstd)); HeteroVertexConv.forward hands it to that layer (`pre`)
-_PRE_NEXT = {}
+class StepState(object):
+    """What the layers of ONE evaluation hand to each other, indexed by layer.  `HVNet.forward` creates it and every layer
+    receives it, so a new step starts empty and no other model or step in the process sees it."""
+
+    def __init__(self):
+        self.edge_sink = None           # EdgeGradSink of this step, where the edge gradients are wanted
+        self.layer = 0                  # index of the layer that is running its forward (HVNet.forward's loop)
+        self.pending = {}               # consuming layer -> nodeops.PendingGrads, from one layer's backward to the next one's
+        self.pre_next = {}              # layer -> (x, its node projection), left by the fused update launch of the layer below
 
 
-def _boundary_mode():
-    """`switches.boundary_mode` -- how the node launches of a layer boundary are cut, where `nodeops.fused_boundary_supported`
+class Route(object):
+    """How one layer runs on the chain kernels, decided once by `HeteroVertexConv.forward`.
+    `exchange`, `halo` (atom shards; `sharding.HaloOverlap`): the exchange of the halo rows of (x, vec) is still due and runs
+    inside the layer, in its "rows" or its "proj" form; None: nothing to exchange.
+    `defer`: x and vec are the outputs of the chain layer below and of nothing else, so the backward may hand its input
+    gradients down as partial sums (`_hand_down`) -- two small launches per layer boundary less, same bits.
+    `pre`: the node projection of THIS x, already computed by the fused update launch of the layer below.
+    `w_next`: the NEXT layer's weights, where its projection of the rows this layer produces may run inside this layer's
+    update launch; `boundary`: switches.boundary_mode, read once (`_update_fwd`)."""
+
+    def __init__(self, exchange=None, halo=None, defer=False, pre=None, w_next=None):
+        self.exchange, self.halo, self.defer, self.pre, self.w_next = exchange, halo, defer, pre, w_next
+        self.boundary = int(switches.boundary_mode)
+
+
+def _local_fwd(x, vec, edge, graph, rbf, w, route):
+    pre = route.pre if route.pre is not None else nodeops.node_pre_fwd(x, w, graph.T, src_ranges=graph.src_ranges)
+    x1, vec1 = _msg_fwd(graph, rbf, x.size(1), pre[1], vec, x, w, edge, xh_bias=False)
+    return pre, x1, vec1
+
+
+def _halo_rows_fwd(x, vec, edge, graph, rbf, w, route):
+    """The exchange runs behind the node projection AND the message kernel of every target that reads no halo row (SURVEY
+    8(e): "run interior edges while the halo is in flight"):
+      pack -> start the all-to-all -> project every row (halo rows from stale inputs: redone below) -> messages into the
+      early targets -> the STREAM waits -> unpack IN PLACE -> project the tiles that hold a halo row -> messages into the
+      remaining targets."""
+    halo, plan, H = route.halo, route.halo.plan, x.size(1)
+    send = nodeops.halo_rows(0, x, vec, plan.send_idx)
+    recv, work = _all_to_all_rows_start(send, plan.send_counts, plan.recv_counts, plan.group)
+    if switches.debug_poison():     # (tests: nothing that runs before the unpack may depend on a halo row)
+        nodeops.halo_rows(2, x, vec, plan.recv_idx, torch.full_like(recv, float("nan")))
+    pre = nodeops.node_pre_fwd(x, w, graph.T, src_ranges=graph.src_ranges)
+    out = _msg_fwd(graph, rbf, H, pre[1], vec, x, w, edge, xh_bias=False, ranges=halo.fwd_early, zero_unknown=True,
+                   range_rows=halo.early_rows)
+    comm_wait(work, "fwd", sum(plan.send_counts), sum(plan.recv_counts))
+    if plan.recv_idx.numel() > 0:   # (a rank without halo atoms has nothing to redo)
+        nodeops.halo_rows(2, x, vec, plan.recv_idx, recv)
+        nodeops.node_pre_fwd(x, w, graph.T, src_ranges=graph.src_ranges, windows=halo.windows, mode=1, out=pre)
+    if halo.late_rows > 0:
+        _msg_fwd(graph, rbf, H, pre[1], vec, x, w, edge, xh_bias=False, ranges=halo.fwd_late, zero_unknown=False, out=out,
+                 range_rows=halo.late_rows)
+    return pre, out[0], out[1]
+
+
+def _halo_proj_fwd(x, vec, edge, graph, rbf, w, route):
+    """The halo rows travel as what the message kernel gathers -- xh[t] of every relation and vec, 12H floats per atom -- so
+    no node kernel runs a second time on the halo tiles:
+      project every row (halo rows from stale inputs: replaced below) -> pack (xh | vec) of the rows the peers need -> start
+      the all-to-all -> messages into the targets that read no halo row -> the STREAM waits -> unpack IN PLACE -> messages
+      into the remaining targets."""
+    halo, plan, H = route.halo, route.halo.plan, x.size(1)
+    pre = nodeops.node_pre_fwd(x, w, graph.T, src_ranges=graph.src_ranges)
+    xh = pre[1]
+    send = nodeops.halo_proj_rows(0, xh, vec, plan.send_idx)
+    recv, work = _all_to_all_rows_start(send, plan.send_counts, plan.recv_counts, plan.group)
+    if switches.debug_poison():     # (tests: nothing that runs before the unpack may depend on a halo row)
+        nodeops.halo_proj_rows(2, xh, vec, plan.recv_idx, torch.full_like(recv, float("nan")))
+    out = _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=False, ranges=halo.fwd_early, zero_unknown=True,
+                   range_rows=halo.early_rows)
+    comm_wait(work, "fwd", sum(plan.send_counts), sum(plan.recv_counts))
+    nodeops.halo_proj_rows(2, xh, vec, plan.recv_idx, recv)
+    if halo.late_rows > 0:
+        _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=False, ranges=halo.fwd_late, zero_unknown=False, out=out,
+                 range_rows=halo.late_rows)
+    return pre, out[0], out[1]
+
+
+def _update_fwd(x1, vec1, graph, w, step, li, route):
+    """The update launch -> (x_out, vec_out, vp, h2b, q23, nrm).
+    `switches.boundary_mode` -- how the node launches of a layer boundary are cut, where `nodeops.fused_boundary_supported`
     (width 128, 16-row update tiles, HVNet rows: csrc/node_chain16.hip):
       0 (default)  every phase a launch of its own: 64-row projection kernels + 16-row update kernels, the input gradients handed
                    down as partial sums (the round-4 form);
@@ -224,117 +293,201 @@ def _boundary_mode():
     Measured in the model (configs[1], one box, three interleaved rounds).  With fp32 MFMAs (profiles/r05_boundary_ab.log):
     0: 2.944, 4: 2.945, 3: 2.971, 1: 2.988 ms per step.  Since the products run as bf16 splits (profiles/r05_boundary_ab_split.log):
     0: 2.80, 4: 2.82, 3: 2.87, 1: 2.89 -- with the matrix pipe 2.7 x cheaper a tile's time is its weight stream, and a 64-row
-    projection tile streams a quarter of the bytes per row of a 16-row one: the fused forms lose what that gains."""
-    return int(switches.boundary_mode)
+    projection tile streams a quarter of the bytes per row of a 16-row one: the fused forms lose what that gains.
+    The forward boundary (1, 2, 3) leaves the next layer's projection in `step.pre_next`; the backward one: `_pre_bwd_parts`."""
+    w_next = route.w_next
+    if w_next is None or route.boundary not in (1, 2, 3) or not nodeops.fused_boundary_supported(graph, x1.size(1), w, w_next):
+        return nodeops.node_update_fwd(x1, vec1, w, graph)
+    if route.boundary != 2:
+        x_out, vec_out, vp, h2b, q23, nrm, pre_next = nodeops.node_update_pre_fwd(x1, vec1, w, graph, w_next)
+    else:
+        x_out, vec_out, vp, h2b, q23, nrm = nodeops.node_update_fwd(x1, vec1, w, graph)
+        pre_next = nodeops.node_pre_fwd16(x_out, w_next, graph.T)
+    step.pre_next[li + 1] = (x_out, pre_next)
+    return x_out, vec_out, vp, h2b, q23, nrm
+
+
+def _edge_grad_slot(edge, graph, step, li, H, device):
+    """Where the message backward writes the edge gradients [H/64, E, 4]: with a handle from `EdgeFanout`, the sink's slice."""
+    if edge.dim() == 3 and step.edge_sink is not None:
+        return step.edge_sink.slice(li)
+    return torch.zeros(H // 64, graph.E, 4, dtype=torch.float32, device=device)
+
+
+def _edge_grad(edge, gedge):
+    """The gradient returned for `edge`: a handle from `EdgeFanout` gets the slices unreduced."""
+    return gedge if edge.dim() == 3 else (gedge[0] if gedge.size(0) == 1 else gedge.sum(0))
+
+
+def _hand_down(step, li, x, vec, gn_parts, gv_parts, mean, rstd, gx1, gvec1, w, chain=None):
+    """The input gradients of layer `li` go down as partial sums: registered as `nodeops.PendingGrads` for the update backward
+    of the layer below, which forms them in its own launch -> the (gx, gvec) buffers it will fill."""
+    gx_total, gvec_in = torch.empty_like(x), torch.empty_like(vec)
+    if switches.debug_poison():                # (tests: nothing reads them before that)
+        gx_total.fill_(float("nan"))
+        gvec_in.fill_(float("nan"))
+    pend = step.pending[li - 1] = nodeops.PendingGrads(
+        gx_total, gvec_in, gn_parts, gv_parts, x, mean, rstd, gx1, gvec1, w.h_real, chain=chain)
+    pend.w_above = w            # (keeps the fragment copies alive; the CPU restatement of the tests reads it)
+    return gx_total, gvec_in
+
+
+def _pre_bwd_parts(ctx, gxh, hb, x, mean, rstd):
+    """The projection's backward up to its per-relation partial sums -> (gn_parts, chain).  Boundary modes 1, 4: it runs inside
+    the update backward of the layer below (`chain`, no launch here); 2: the same 16-row phase as a launch of its own."""
+    graph, w = ctx.graph, ctx.w
+    if ctx.route.boundary in (1, 2, 4) and nodeops.fused_boundary_supported(graph, x.size(1), w):
+        if ctx.route.boundary != 2:
+            return None, (gxh, hb, w.w2tf16, w.w1tf16)
+        return nodeops.node_pre_bwd16(gxh, hb, w), None
+    return nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, src_ranges=graph.src_ranges, parts_only=True), None
+
+
+def _local_bwd(ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge):
+    graph, rbf, w, H = ctx.graph, ctx.rbf, ctx.w, x.size(1)
+    if _bwd_sums_deferrable(graph, H):
+        if ctx.route.defer and ctx.needs_input_grad[0]:
+            gxh, gv_parts = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, finish=False)
+            gn_parts, chain = _pre_bwd_parts(ctx, gxh, hb, x, mean, rstd)
+            return _hand_down(ctx.step, ctx.li, x, vec, gn_parts, gv_parts, mean, rstd, gx1, gvec1, w, chain)
+        if vec is None and not ctx.needs_input_grad[0]:     # the first layer: nothing below wants gx / gvec
+            _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, finish=False)
+            return None, None
+    gxh, gvec_in, gx_in = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False)
+    _virtual_residual(graph, gx1, gvec1, gx_in, gvec_in, H)
+    want_gx = ctx.needs_input_grad[0]
+    return (nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, add=gx_in, src_ranges=graph.src_ranges) if want_gx else None), gvec_in
+
+
+def _halo_rows_bwd(ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge):
+    """The gradients of the halo rows first: they travel to their owners while the other rows are computed."""
+    graph, rbf, w, halo, plan, H = ctx.graph, ctx.rbf, ctx.w, ctx.route.halo, ctx.route.halo.plan, x.size(1)
+    bufs = None
+    if halo.bwd_first[1]:
+        bufs = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_first)
+        gxh, gvec_in, gx_in, _ = bufs
+        _virtual_residual(graph, gx1, gvec1, gx_in, gvec_in, H, halo.bwd_first)
+        out = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, add=gx_in, src_ranges=graph.src_ranges,
+                                   windows=halo.windows, mode=1)
+        gsend = nodeops.halo_rows(1, out[0], gvec_in, plan.recv_idx)           # pack and clear: none stays here
+    else:                                                                   # (a rank without halo atoms)
+        out, gsend = None, x.new_empty(0, 4 * H)
+    back, work = _all_to_all_rows_start(gsend, plan.recv_counts, plan.send_counts, plan.group)
+    if halo.bwd_rest[1]:
+        bufs = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_rest, out=bufs)
+        _virtual_residual(graph, gx1, gvec1, bufs[2], bufs[1], H, halo.bwd_rest)
+    gxh, gvec_in, gx_in, _ = bufs
+    gx_total = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, add=gx_in, src_ranges=graph.src_ranges,
+                                    windows=halo.windows, mode=2, out=out)[0]
+    comm_wait(work, "bwd", sum(plan.recv_counts), sum(plan.send_counts))
+    nodeops.halo_accumulate(gx_total, gvec_in, plan, back)                  # gradients of my atoms used elsewhere
+    return gx_total, gvec_in
+
+
+def _halo_proj_bwd(ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge):
+    """The gradients of the halo SOURCE rows first, as they stand behind the message backward -- gxh[t] of every relation and
+    the per-relation partial sums of gvec, summed while they are packed; cleared here: the local halo rows were overwritten
+    in the forward --; they travel to their owners while the other source rows are computed; the owners add them to their own
+    gxh / partial sums in list order, and ONE node_pre_bwd over every row follows.  The input gradients go down as partial
+    sums (`_hand_down`): no finishing launch, no windowed node launch, no LayerNorm backward."""
+    graph, rbf, w, halo, plan, H = ctx.graph, ctx.rbf, ctx.w, ctx.route.halo, ctx.route.halo.plan, x.size(1)
+    gxh = torch.empty_like(xh)
+    gv_parts = torch.empty((graph.T,) + tuple(vec.shape), dtype=vec.dtype, device=vec.device)
+    bufs = (gxh, gv_parts)
+    if halo.bwd_first_rows[1]:
+        _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_first_rows, out=bufs,
+                 finish=False)
+    gsend = nodeops.halo_proj_rows(1, gxh, gv_parts, plan.recv_idx)           # pack and clear: none stays here
+    back, work = _all_to_all_rows_start(gsend, plan.recv_counts, plan.send_counts, plan.group)
+    if halo.bwd_rest_rows[1]:
+        _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_rest_rows, out=bufs,
+                 finish=False)
+    comm_wait(work, "bwd", sum(plan.recv_counts), sum(plan.send_counts))
+    nodeops.halo_proj_accumulate(gxh, gv_parts, plan, back)                 # gradients of my atoms used elsewhere
+    gn_parts = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, src_ranges=graph.src_ranges, parts_only=True)
+    return _hand_down(ctx.step, ctx.li, x, vec, gn_parts, gv_parts, mean, rstd, gx1, gvec1, w)
+
+
+_ROUTES = {None: (_local_fwd, _local_bwd), "rows": (_halo_rows_fwd, _halo_rows_bwd), "proj": (_halo_proj_fwd, _halo_proj_bwd)}
 
 
 class FusedRelationalLayer(torch.autograd.Function):
-    """(x, vec, edge) -> (x_out, vec_out) for one layer, relation (row) order."""
+    """(x, vec, edge) -> (x_out, vec_out) for one layer on the chain kernels, relation (row) order."""
 
     @staticmethod
-    def forward(ctx, x, vec, edge, graph, rbf, w, sink=None, li=0, halo=None, defer=False, pre=None, w_next=None, proj=False):
+    def forward(ctx, x, vec, edge, graph, rbf, w, step, route):
         """`edge`: [E,4], or this layer's handle from `EdgeFanout` ([H/64,E,4] stride-0 view; same memory).
         x / vec live in SOURCE rows, the outputs in TARGET rows; the two coincide for HVNet and differ for HTNet
-        (`graph.num_src`: one target row per atom and pair relation, relations.build_triadic).
-        `halo` (atom shards, chain path only; `sharding.HaloOverlap`): the exchange of the halo rows of (x, vec) is
-        still due -- it runs here, around the node projection: pack, start the all-to-all, project the row tiles
-        that hold no halo row, wait, unpack IN PLACE, project the rest.  The backward mirrors it.
-        `defer` (HeteroVertexConv.forward: x and vec are the outputs of the chain layer below and of nothing else): the
-        backward hands its input gradients down as partial sums (`nodeops.PendingGrads`) and the update backward of the
-        layer below forms them in its own launch -- two small launches per layer boundary less, same bits.
-        `pre` (chain path without halo): the node projection of THIS x, already launched by the caller (HVNet.forward runs the
-        first layer's beside the relation build; round 5: every later layer's comes out of the fused update launch of the
-        layer below).
-        `w_next` (round 5): the NEXT layer's weights -- its node projection of the rows this layer produces runs inside this
-        layer's update launch where `nodeops.fused_boundary_supported` (result left in `_PRE_NEXT`).
-        `proj` (round 6, with `halo`): x and vec come straight from the chain layer below (as for `defer`), so the exchange may
-        take the "proj" form: projected rows travel forward, partial sums of gradients backward."""
+        (`graph.num_src`: one target row per atom and pair relation, relations.build_triadic)."""
+        x = x.contiguous()
+        vec = None if vec is None else vec.contiguous()
+        # (the proj form hands its input gradients down as partial sums: where the layer below cannot take them and somebody
+        # wants them -- known only here --, the exchange takes the rows form)
+        ctx.exchange = "rows" if (route.exchange == "proj" and not _bwd_sums_deferrable(graph, x.size(1))
+                                  and (ctx.needs_input_grad[0] or ctx.needs_input_grad[2])) else route.exchange
+        (hb, xh, mean, rstd), x1, vec1 = _ROUTES[ctx.exchange][0](x, vec, edge, graph, rbf, w, route)
+        x_out, vec_out, vp, h2b, q23, nrm = _update_fwd(x1, vec1, graph, w, step, step.layer, route)
+        ctx.save_for_backward(x, mean, rstd, hb, xh, vec, edge, vp, h2b, q23, nrm)
+        ctx.graph, ctx.rbf, ctx.w, ctx.step, ctx.li, ctx.route = graph, rbf, w, step, step.layer, route
+        return x_out, vec_out
+
+    @staticmethod
+    def backward(ctx, gxo, gvo):
+        x, mean, rstd, hb, xh, vec, edge, vp, h2b, q23, nrm = ctx.saved_tensors
+        gxo, gvo = gxo.contiguous(), gvo.contiguous()
+        # (the layer above may have left its finishing launches to this one: the buffers arrive unfilled -- and they must be
+        # the very buffers it registered: a copy made on the way would hold garbage, so that is refused loudly)
+        pend = ctx.step.pending.pop(ctx.li, None)
+        if pend is not None and (pend.gx.data_ptr() != gxo.data_ptr() or pend.gvec.data_ptr() != gvo.data_ptr()):
+            raise RuntimeError("hermnet_amd: the gradients handed down as partial sums (layer %d) did not arrive in the "
+                               "buffers they were registered with; set the environment variable named in "
+                               "hermnet_amd/switches.py: defer_sums to 0" % (ctx.li + 1))
+        gx1, gvec1 = nodeops.node_update_bwd(gxo, gvo, vp, h2b, q23, nrm, ctx.w, ctx.graph, pending=pend)
+        gedge = _edge_grad_slot(edge, ctx.graph, ctx.step, ctx.li, x.size(1), gx1.device)
+        gx, gvec = _ROUTES[ctx.exchange][1](ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge)
+        return (gx, gvec, _edge_grad(edge, gedge)) + (None,) * 5
+
+
+def _relation_gemms(graph, a, w_s, w_t, out, bias=None, acc=False):
+    """out[rows of t] = a[rows of t] @ W_t for every relation t, under `_launch("gemm", ...)`: ONE batched product over the
+    stacked weights `w_s` where every relation owns `graph.block` rows (graph.uniform), else one product per non-empty
+    relation with `w_t[t]`.  Operands [rows, 3, K] count as three rows each.  `bias`: added by the per-relation products
+    only -- a bias that would be broadcast over a batched GEMM's rows is added by the consuming kernel on load instead
+    (baddbmm with a broadcast bias first copies it over the whole output).  `acc`: the products are added to `out`."""
+    rp = graph.type_rowptr_host
+    nk, T, K, M = rp[-1], graph.T, a.size(-1), out.size(-1)
+    if graph.uniform and nk > 0:
+        av, ov = a[:nk].view(T, -1, K), out[:nk].view(T, -1, M)
+        _launch("gemm", (lambda: torch.baddbmm(ov, av, w_s, out=ov)) if acc else (lambda: torch.bmm(av, w_s, out=ov)))
+        return
+    for t in range(T):
+        lo, hi = rp[t], rp[t + 1]
+        if hi > lo:
+            av, ov = a[lo:hi].view(-1, K), out[lo:hi].view(-1, M)
+            if acc:
+                _launch("gemm", lambda: torch.addmm(ov, av, w_t[t], out=ov))
+            elif bias is not None:
+                _launch("gemm", lambda: torch.addmm(bias[t], av, w_t[t], out=ov))
+            else:
+                _launch("gemm", lambda: torch.mm(av, w_t[t], out=ov))
+
+
+class GemmRelationalLayer(torch.autograd.Function):
+    """The same layer with its node-level linears as library GEMMs joined by the stage kernels (csrc/node_kernels.hip):
+    switches.node_chain = False, and every width the chain kernels are not instantiated for.  No exchange runs in here."""
+
+    @staticmethod
+    def forward(ctx, x, vec, edge, graph, rbf, w, step):
         Ns, H = x.shape
-        N = graph.N
-        T = graph.T
-        rp = graph.type_rowptr_host
-        nk = rp[-1]
+        N, T, B = graph.N, graph.T, graph.block
+        nk = graph.type_rowptr_host[-1]
+        uni = graph.uniform and nk > 0
         x = x.contiguous()
         vec = None if vec is None else vec.contiguous()
         # --- node projection of every relation: xh[t] = x_proj_t(LayerNorm_t(x))  (rmnet.py:52)
-        uni, B = graph.uniform and nk > 0, graph.block
-        ctx.chain = w.chain and _node_chain_enabled()
-        if ctx.chain:
-            # three launches: node_pre_fwd (LayerNorm + x_proj of every relation), the message kernel, node_update_fwd
-            # atom shards, the "proj" form of the exchange (round 6): the halo rows travel as what the message kernel gathers --
-            # xh[t] of every relation and vec, 12H floats per atom -- so no node kernel runs a second time on the halo tiles
-            # and the backward hands its gradients down as partial sums like the unsharded layer (`defer`)
-            ctx.proj = bool(proj) and halo is not None and vec is not None and (
-                _bwd_sums_deferrable(graph, H) or not (ctx.needs_input_grad[0] or ctx.needs_input_grad[2]))
-            if halo is None:
-                hb, xh, mean, rstd = pre if pre is not None else nodeops.node_pre_fwd(x, w, T, src_ranges=graph.src_ranges)
-                x1, vec1 = _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=False)
-            elif ctx.proj:
-                #   project every row (halo rows from stale inputs: replaced below) -> pack (xh | vec) of the rows the peers
-                #   need -> start the all-to-all -> messages into the targets that read no halo row -> the STREAM waits ->
-                #   unpack IN PLACE -> messages into the remaining targets
-                from .sharding import _all_to_all_rows_start, comm_wait
-                plan = halo.plan
-                hb, xh, mean, rstd = nodeops.node_pre_fwd(x, w, T, src_ranges=graph.src_ranges)
-                send = nodeops.halo_proj_rows(0, xh, vec, plan.send_idx)
-                recv, work = _all_to_all_rows_start(send, plan.send_counts, plan.recv_counts, plan.group)
-                if switches.debug_poison():
-                    # (tests: nothing that runs before the unpack may depend on a halo row)
-                    nodeops.halo_proj_rows(2, xh, vec, plan.recv_idx, torch.full_like(recv, float("nan")))
-                x1, vec1 = out = _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=False, ranges=halo.fwd_early,
-                                          zero_unknown=True, range_rows=halo.early_rows)
-                comm_wait(work, "fwd", sum(plan.send_counts), sum(plan.recv_counts))
-                nodeops.halo_proj_rows(2, xh, vec, plan.recv_idx, recv)
-                if halo.late_rows > 0:
-                    _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=False, ranges=halo.fwd_late, zero_unknown=False,
-                             out=out, range_rows=halo.late_rows)
-            else:
-                # The exchange runs behind the node projection AND the message kernel of every target that reads no
-                # halo row (SURVEY 8(e): "run interior edges while the halo is in flight"):
-                #   pack -> start the all-to-all -> project every row (halo rows from stale inputs: redone below) ->
-                #   messages into the early targets -> the STREAM waits -> unpack IN PLACE -> project the tiles that hold
-                #   a halo row -> messages into the remaining targets.
-                from .sharding import _all_to_all_rows_start
-                plan = halo.plan
-                send = nodeops.halo_rows(0, x, vec, plan.send_idx)
-                recv, work = _all_to_all_rows_start(send, plan.send_counts, plan.recv_counts, plan.group)
-                if switches.debug_poison():
-                    # (tests: nothing that runs before the unpack may depend on a halo row)
-                    nodeops.halo_rows(2, x, vec, plan.recv_idx, torch.full_like(recv, float("nan")))
-                hb, xh, mean, rstd = pre = nodeops.node_pre_fwd(x, w, T, src_ranges=graph.src_ranges)
-                x1, vec1 = out = _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=False, ranges=halo.fwd_early,
-                                          zero_unknown=True, range_rows=halo.early_rows)
-                from .sharding import comm_wait
-                comm_wait(work, "fwd", sum(plan.send_counts), sum(plan.recv_counts))
-                if plan.recv_idx.numel() > 0:  # (a rank without halo atoms has nothing to redo)
-                    nodeops.halo_rows(2, x, vec, plan.recv_idx, recv)
-                    nodeops.node_pre_fwd(x, w, T, src_ranges=graph.src_ranges, windows=halo.windows, mode=1, out=pre)
-                if halo.late_rows > 0:
-                    _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=False, ranges=halo.fwd_late, zero_unknown=False,
-                             out=out, range_rows=halo.late_rows)
-            ctx.halo = halo
-            ctx.defer = (bool(defer) and halo is None and vec is not None) or ctx.proj
-            mode = _boundary_mode()
-            if (w_next is not None and halo is None and mode in (1, 2, 3)
-                    and nodeops.fused_boundary_supported(graph, H, w, w_next)):
-                if mode != 2:
-                    x_out, vec_out, vp, h2b, q23, nrm, pre_next = nodeops.node_update_pre_fwd(x1, vec1, w, graph, w_next)
-                else:
-                    x_out, vec_out, vp, h2b, q23, nrm = nodeops.node_update_fwd(x1, vec1, w, graph)
-                    pre_next = nodeops.node_pre_fwd16(x_out, w_next, T)
-                _PRE_NEXT[(id(graph), li + 1)] = (x_out, pre_next)
-            else:
-                x_out, vec_out, vp, h2b, q23, nrm = nodeops.node_update_fwd(x1, vec1, w, graph)
-            ctx.save_for_backward(x, mean, rstd, hb, xh, vec, edge, vp, h2b, q23, nrm)
-            ctx.graph, ctx.rbf, ctx.w, ctx.sink, ctx.li = graph, rbf, w, sink, li
-            return x_out, vec_out
-        if halo is not None:
-            raise RuntimeError("the in-layer halo exchange belongs to the chain path (HeteroVertexConv.forward decides)")
         n, mean, rstd = nodeops.layernorm_fwd(x, 1e-5, h_real=w.h_real)
         h = _launch("gemm", lambda: torch.addmm(w.b1cat, n, w.w1cat.t()))                                     # [Ns, T*H]
         a = nodeops.ssilu_fwd(h)
-        # (biases that would be broadcast over a batched GEMM's rows are added by the consuming kernel
-        # instead: baddbmm with a broadcast bias first copies it over the whole output)
         xh = _launch("gemm", lambda: torch.bmm(a.view(Ns, T, H).transpose(0, 1), w.w2t))                      # [T, Ns, 3H], + b2 on load
         # --- fused edge part + residual (rmnet.py:55-73, 24-26)
         x1, vec1 = _msg_fwd(graph, rbf, H, xh, vec, x, w, edge)
@@ -342,193 +495,43 @@ class FusedRelationalLayer(torch.autograd.Function):
         vp = torch.empty(N, 3, 2 * H, dtype=x.dtype, device=x.device)
         h2 = torch.empty(N, H, dtype=x.dtype, device=x.device)
         q = torch.empty(N, 3 * H, dtype=x.dtype, device=x.device)
-        if uni:   # every relation owns `B` rows: one batched GEMM per stage
-            _launch("gemm", lambda: torch.bmm(vec1[:nk].view(T, 3 * B, H), w.wvt_s, out=vp[:nk].view(T, 3 * B, 2 * H)))
-        else:
-            for t in range(T):
-                lo, hi = rp[t], rp[t + 1]
-                if hi > lo:
-                    _launch("gemm", lambda: torch.mm(vec1[lo:hi].view(-1, H), w.wvt[t], out=vp[lo:hi].view(-1, 2 * H)))
+        _relation_gemms(graph, vec1, w.wvt_s, w.wvt, vp)
         vdot, xin = nodeops.update_mid(vp, x1, nk, H)
-        if uni:
-            _launch("gemm", lambda: torch.bmm(xin[:nk].view(T, B, 2 * H), w.wx0t_s, out=h2[:nk].view(T, B, H)))
-        else:
-            for t in range(T):
-                lo, hi = rp[t], rp[t + 1]
-                if hi > lo:
-                    _launch("gemm", lambda: torch.addmm(w.bx0[t], xin[lo:hi], w.wx0t[t], out=h2[lo:hi]))
+        _relation_gemms(graph, xin, w.wx0t_s, w.wx0t, h2, bias=w.bx0)
         kb = dict(bias=w.bx0_s, rows_per_bias=B) if uni else {}
         a2 = nodeops.ssilu_fwd(h2[:nk], **kb) if nk > 0 else h2[:0]
-        if uni:
-            _launch("gemm", lambda: torch.bmm(a2.view(T, B, H), w.wx2t_s, out=q[:nk].view(T, B, 3 * H)))
-        else:
-            for t in range(T):
-                lo, hi = rp[t], rp[t + 1]
-                if hi > lo:
-                    _launch("gemm", lambda: torch.addmm(w.bx2[t], a2[lo:hi], w.wx2t[t], out=q[lo:hi]))
+        _relation_gemms(graph, a2, w.wx2t_s, w.wx2t, q, bias=w.bx2)
         qb = dict(qbias=w.bx2_s, rows_per_bias=B) if uni else {}
         x_out, vec_out = nodeops.update_out(q, vdot, vp, x1, vec1, graph.row_active, N, nk, H, **qb)
         ctx.save_for_backward(x, mean, rstd, h, xh, vec, edge, vp, vdot, xin, h2, q)
-        ctx.graph, ctx.rbf, ctx.w, ctx.sink, ctx.li = graph, rbf, w, sink, li
+        ctx.graph, ctx.rbf, ctx.w, ctx.step, ctx.li, ctx.kb, ctx.qb = graph, rbf, w, step, step.layer, kb, qb
         return x_out, vec_out
 
     @staticmethod
     def backward(ctx, gxo, gvo):
-        graph, rbf, w = ctx.graph, ctx.rbf, ctx.w
-        N = graph.N
-        T = graph.T
-        rp = graph.type_rowptr_host
-        nk = rp[-1]
-        gxo = gxo.contiguous()
-        gvo = gvo.contiguous()
-        uni, B = graph.uniform and nk > 0, graph.block
-        if ctx.chain:
-            x, mean, rstd, hb, xh, vec, edge, vp, h2b, q23, nrm = ctx.saved_tensors
-            Ns, H = x.shape
-            # (the layer above may have left its finishing launches to this one: the buffers arrive unfilled -- and they must be
-            # the very buffers it registered: a copy made on the way would hold garbage, so that is refused loudly)
-            pend = _PENDING.pop((id(graph), ctx.li), None)
-            if pend is not None and (pend.gx.data_ptr() != gxo.data_ptr() or pend.gvec.data_ptr() != gvo.data_ptr()):
-                raise RuntimeError("hermnet_amd: the gradients handed down as partial sums (layer %d) did not arrive in the "
-                                   "buffers they were registered with; set the environment variable named in "
-                                   "hermnet_amd/switches.py: defer_sums to 0" % (ctx.li + 1))
-            gx1, gvec1 = nodeops.node_update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending=pend)
-        else:
-            x, mean, rstd, h, xh, vec, edge, vp, vdot, xin, h2, q = ctx.saved_tensors
-            Ns, H = x.shape
-            qb = dict(qbias=w.bx2_s, rows_per_bias=B) if uni else {}
-            kb = dict(bias=w.bx0_s, rows_per_bias=B) if uni else {}
-            gq, gvdot, gvp, gx1, gvec1 = nodeops.update_out_bwd(gxo, gvo, q, vdot, vp, graph.row_active, N, nk, H, **qb)
-            gxin = torch.empty(N, 2 * H, dtype=x.dtype, device=x.device)
-            ga2 = torch.empty(N, H, dtype=x.dtype, device=x.device)
-            if uni:
-                _launch("gemm", lambda: torch.bmm(gq[:nk].view(T, B, 3 * H), w.wx2_s, out=ga2[:nk].view(T, B, H)))
-            else:
-                for t in range(T):
-                    lo, hi = rp[t], rp[t + 1]
-                    if hi > lo:
-                        _launch("gemm", lambda: torch.mm(gq[lo:hi], w.wx2[t], out=ga2[lo:hi]))
-            gh2 = nodeops.ssilu_bwd(ga2, h2, nk, 1, H, H, H, **kb) if nk > 0 else ga2[:0]
-            if uni:
-                _launch("gemm", lambda: torch.bmm(gh2.view(T, B, H), w.wx0_s, out=gxin[:nk].view(T, B, 2 * H)))
-            else:
-                for t in range(T):
-                    lo, hi = rp[t], rp[t + 1]
-                    if hi > lo:
-                        _launch("gemm", lambda: torch.mm(gh2[lo:hi], w.wx0[t], out=gxin[lo:hi]))
-            nodeops.update_mid_bwd(gvdot, gxin, vp, xin, gvp, gx1, nk, H)
-            if uni:
-                gv = gvec1[:nk].view(T, 3 * B, H)
-                _launch("gemm", lambda: torch.baddbmm(gv, gvp[:nk].view(T, 3 * B, 2 * H), w.wv_s, out=gv))
-            else:
-                for t in range(T):
-                    lo, hi = rp[t], rp[t + 1]
-                    if hi > lo:
-                        g = gvec1[lo:hi].view(-1, H)
-                        _launch("gemm", lambda: torch.addmm(g, gvp[lo:hi].view(-1, 2 * H), w.wv[t], out=g))
-        fan = edge.dim() == 3          # handle from EdgeFanout: return the slices unreduced
-        if fan and ctx.sink is not None:
-            gedge = ctx.sink.slice(ctx.li)
-        else:
-            gedge = torch.zeros(H // 64, graph.E, 4, dtype=torch.float32, device=gx1.device)
-        halo = ctx.halo if ctx.chain else None
-        if halo is not None and ctx.proj:
-            # The gradients of the halo SOURCE rows first, as they stand behind the message backward -- gxh[t] of every relation
-            # and the per-relation partial sums of gvec, summed while they are packed; cleared here: the local halo rows were
-            # overwritten in the forward --; they travel to their owners while the other source rows are computed; the owners add
-            # them to their own gxh / partial sums in list order, and ONE node_pre_bwd over every row follows.  The input
-            # gradients go down as partial sums (`defer`): no finishing launch, no windowed node launch, no LayerNorm backward.
-            from .sharding import _all_to_all_rows_start, comm_wait
-            plan = halo.plan
-            gxh = torch.empty_like(xh)
-            gv_parts = torch.empty((T,) + tuple(vec.shape), dtype=vec.dtype, device=vec.device)
-            bufs = (gxh, gv_parts)
-            if halo.bwd_first_rows[1]:
-                _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_first_rows,
-                         out=bufs, finish=False)
-            gsend = nodeops.halo_proj_rows(1, gxh, gv_parts, plan.recv_idx)           # pack and clear: none stays here
-            back, work = _all_to_all_rows_start(gsend, plan.recv_counts, plan.send_counts, plan.group)
-            if halo.bwd_rest_rows[1]:
-                _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_rest_rows,
-                         out=bufs, finish=False)
-            comm_wait(work, "bwd", sum(plan.recv_counts), sum(plan.send_counts))
-            nodeops.halo_proj_accumulate(gxh, gv_parts, plan, back)                 # gradients of my atoms used elsewhere
-            gn_parts = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, src_ranges=graph.src_ranges, parts_only=True)
-            gx_total, gvec_in = torch.empty_like(x), torch.empty_like(vec)          # filled by the layer below
-            if switches.debug_poison():                # (tests: nothing reads them before that)
-                gx_total.fill_(float("nan"))
-                gvec_in.fill_(float("nan"))
-            pend = _PENDING[(id(graph), ctx.li - 1)] = nodeops.PendingGrads(
-                gx_total, gvec_in, gn_parts, gv_parts, x, mean, rstd, gx1, gvec1, w.h_real)
-            pend.w_above = w
-            ge = gedge if fan else (gedge[0] if gedge.size(0) == 1 else gedge.sum(0))
-            return (gx_total, gvec_in, ge) + (None,) * 10
-        if halo is not None:
-            # the gradients of the halo rows first: they travel to their owners while the other rows are computed
-            from .sharding import _all_to_all_rows_start
-            plan = halo.plan
-            bufs = None
-            if halo.bwd_first[1]:
-                bufs = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_first)
-                gxh, gvec_in, gx_in, _ = bufs
-                _virtual_residual(graph, gx1, gvec1, gx_in, gvec_in, H, halo.bwd_first)
-                out = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, add=gx_in, src_ranges=graph.src_ranges,
-                                           windows=halo.windows, mode=1)
-                gsend = nodeops.halo_rows(1, out[0], gvec_in, plan.recv_idx)           # pack and clear: none stays here
-            else:                                                                   # (a rank without halo atoms)
-                out = None
-                gsend = x.new_empty(0, 4 * H)
-            back, work = _all_to_all_rows_start(gsend, plan.recv_counts, plan.send_counts, plan.group)
-            if halo.bwd_rest[1]:
-                bufs = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, ranges=halo.bwd_rest,
-                                out=bufs)
-                _virtual_residual(graph, gx1, gvec1, bufs[2], bufs[1], H, halo.bwd_rest)
-            gxh, gvec_in, gx_in, _ = bufs
-            res = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, add=gx_in, src_ranges=graph.src_ranges,
-                                       windows=halo.windows, mode=2, out=out)
-            gx_total = res[0]
-            from .sharding import comm_wait
-            comm_wait(work, "bwd", sum(plan.recv_counts), sum(plan.send_counts))
-            nodeops.halo_accumulate(gx_total, gvec_in, plan, back)                  # gradients of my atoms used elsewhere
-            ge = gedge if fan else (gedge[0] if gedge.size(0) == 1 else gedge.sum(0))
-            return (gx_total, gvec_in, ge) + (None,) * 10
-        ge = gedge if fan else (gedge[0] if gedge.size(0) == 1 else gedge.sum(0))
-        if ctx.chain and _bwd_sums_deferrable(graph, H):
-            if ctx.defer and ctx.needs_input_grad[0]:
-                gxh, gv_parts = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, finish=False)
-                mode, chain = _boundary_mode(), None
-                if mode in (1, 2, 4) and nodeops.fused_boundary_supported(graph, H, w):
-                    # round 5: this layer's projection backward runs inside the update backward of the layer below (1), or as
-                    # the same 16-row phase in a launch of its own (2)
-                    if mode != 2:
-                        gn_parts, chain = None, (gxh, hb, w.w2tf16, w.w1tf16)
-                    else:
-                        gn_parts = nodeops.node_pre_bwd16(gxh, hb, w)
-                else:
-                    gn_parts = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, src_ranges=graph.src_ranges, parts_only=True)
-                gx_total, gvec_in = torch.empty_like(x), torch.empty_like(vec)      # filled by the layer below
-                if switches.debug_poison():            # (tests: nothing reads them before that)
-                    gx_total.fill_(float("nan"))
-                    gvec_in.fill_(float("nan"))
-                pend = _PENDING[(id(graph), ctx.li - 1)] = nodeops.PendingGrads(
-                    gx_total, gvec_in, gn_parts, gv_parts, x, mean, rstd, gx1, gvec1, w.h_real, chain=chain)
-                pend.w_above = w            # (keeps the fragment copies alive; the CPU restatement of the tests reads it)
-                return (gx_total, gvec_in, ge) + (None,) * 10
-            if vec is None and not ctx.needs_input_grad[0]:     # the first layer: nothing below wants gx / gvec
-                _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, finish=False)
-                return (None, None, ge) + (None,) * 10
-        gxh, gvec_in, gx_in = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=not ctx.chain)
+        x, mean, rstd, h, xh, vec, edge, vp, vdot, xin, h2, q = ctx.saved_tensors
+        graph, rbf, w, kb, qb = ctx.graph, ctx.rbf, ctx.w, ctx.kb, ctx.qb
+        Ns, H = x.shape
+        N, T, nk = graph.N, graph.T, graph.type_rowptr_host[-1]
+        gq, gvdot, gvp, gx1, gvec1 = nodeops.update_out_bwd(gxo.contiguous(), gvo.contiguous(), q, vdot, vp, graph.row_active,
+                                                            N, nk, H, **qb)
+        gxin = torch.empty(N, 2 * H, dtype=x.dtype, device=x.device)
+        ga2 = torch.empty(N, H, dtype=x.dtype, device=x.device)
+        _relation_gemms(graph, gq, w.wx2_s, w.wx2, ga2)
+        gh2 = nodeops.ssilu_bwd(ga2, h2, nk, 1, H, H, H, **kb) if nk > 0 else ga2[:0]
+        _relation_gemms(graph, gh2, w.wx0_s, w.wx0, gxin)
+        nodeops.update_mid_bwd(gvdot, gxin, vp, xin, gvp, gx1, nk, H)
+        _relation_gemms(graph, gvp, w.wv_s, w.wv, gvec1, acc=True)
+        gedge = _edge_grad_slot(edge, graph, ctx.step, ctx.li, H, gx1.device)
+        gxh, gvec_in, gx_in = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=True)
         _virtual_residual(graph, gx1, gvec1, gx_in, gvec_in, H)
         gx_total = None
         if ctx.needs_input_grad[0]:
-            if ctx.chain:
-                gx_total = nodeops.node_pre_bwd(gxh, hb, x, mean, rstd, w, add=gx_in, src_ranges=graph.src_ranges)
-            else:
-                ga = _launch("gemm", lambda: torch.bmm(gxh, w.w2))                                            # [T, Ns, H]
-                gh = nodeops.ssilu_bwd(ga, h, Ns, T, H, H, Ns * H)                   # [Ns, T*H]
-                gn = _launch("gemm", lambda: torch.mm(gh, w.w1cat))                                           # [N, H]
-                gx_total = nodeops.layernorm_bwd(gn, x, mean, rstd, add=gx_in, h_real=w.h_real)
-        return (gx_total, gvec_in, ge) + (None,) * 10
+            ga = _launch("gemm", lambda: torch.bmm(gxh, w.w2))                                                # [T, Ns, H]
+            gh = nodeops.ssilu_bwd(ga, h, Ns, T, H, H, Ns * H)                   # [Ns, T*H]
+            gn = _launch("gemm", lambda: torch.mm(gh, w.w1cat))                                               # [N, H]
+            gx_total = nodeops.layernorm_bwd(gn, x, mean, rstd, add=gx_in, h_real=w.h_real)
+        return (gx_total, gvec_in, _edge_grad(edge, gedge)) + (None,) * 4
 
 
 class EnergyHead(torch.autograd.Function):

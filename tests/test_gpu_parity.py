@@ -1317,7 +1317,6 @@ def test_deferred_gradient_sums_equal_the_finishing_launches_bit_for_bit(name, w
     the layer below forms them in its own launch (hn_pending_grads) -- no message_bwd_finish / layernorm_bwd_parts
     launches, the same bits in energy and forces."""
     from hermnet_amd import ops
-    from hermnet_amd.layer import _PENDING
     dev = _dev()
     g = Golden(name)
     # (the round-4 forms of both sides: with the layer boundary fused -- round 5's default at width 128 -- the deferred side runs
@@ -1346,7 +1345,7 @@ def test_deferred_gradient_sums_equal_the_finishing_launches_bit_for_bit(name, w
             ops.set_kernel_timer(None)
         torch.cuda.synchronize()
         res.append((e.detach().clone(), f.clone(), cnt.names))
-        assert not _PENDING                     # every handed-down gradient was picked up
+        assert not d._hn_step.pending           # every handed-down gradient was picked up
     assert torch.isfinite(res[1][1]).all()
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
     assert len(res[1][2]) == len(res[0][2])     # (the same library calls: the launches they no longer make are inside them)

@@ -233,7 +233,7 @@ def test_fused_layer_orchestration_matches_golden(name, monkeypatch):
             d.pos.requires_grad_(True)
             e = model(d)
             f = -torch.autograd.grad(e.sum(), d.pos)[0]
-            assert not lmod._PENDING and not lmod._PRE_NEXT
+            assert not d._hn_step.pending and not d._hn_step.pre_next
             assert rel_err(e.detach(), g.energy) < 2e-6
             assert rel_err(f, g.forces) < 1e-5
             if g.model_kw["hidden_channels"] == 128 and name != "alloy108_unknown_type_":
