@@ -4,6 +4,9 @@
 #include <stddef.h>
 
 #define HN_EDGE_TABLE_FLOATS 32   // floats per edge record of hermnet_edge_radial_table (include/hermnet_hip.h)
+// floats per edge of the forward's tap records (hermnet_edge_radial_tables, CSR order): [0..11] the raw taps g_m |
+// [12] env(u) | [13] padded tile row of tap 0 (int bits) | [14,15] 0 -- one aligned 64-byte line quarter per edge
+#define HN_FWD_TAPS_FLOATS 16
 
 struct HnBwdClArgs {
   int N, Nsrc, E, T;         // target rows, source rows, edges, relations

@@ -54,13 +54,65 @@ constexpr int kRec = HN_EDGE_TABLE_FLOATS;   // floats per edge record
 #ifndef HN_NT_TABLE
 #define HN_NT_TABLE 1
 #endif
+// env(u) rounded as the forward kernels' own evaluation of hn_envelope rounds it (message_kernels.hip, every instance):
+// hipcc packs w * (...) and u^(p-1) * u into one v_pk_mul_f32 there, which keeps the "1 +" behind it out of an FMA --
+// FMA, multiply, add, FMA -- whereas this file's build contracts all three.  The forward's tap records must hold the
+// forward's bits (tests/test_fwd_tap_table.py compares the two forms bit for bit), so their envelope is spelled out.
+__device__ __forceinline__ float fwd_envelope_val(float u, int kind, int p) {
+#pragma clang fp contract(off)
+  if (kind != 0 || !(u < 1.0f)) return hn_envelope(u, kind, p).val;
+  const float up = hn_powi(u, p - 1) * u;
+  const float w = 1.0f - u;
+  const float fp = (float)p;
+  const float inner = __builtin_fmaf(0.5f * fp * (fp + 1.0f), w, fp);
+  const float q = 1.0f + w * inner;
+  return __builtin_fmaf(-q, up, 1.0f);
+}
 __global__ __launch_bounds__(256) void edge_table_kernel(const float4* __restrict__ edge, const int* __restrict__ csc_pos,
                                                          int E, const float* __restrict__ offset, int R, float inv_rc,
                                                          float coeff, int env_kind, int env_p,
-                                                         float* __restrict__ table, const int* __restrict__ csc_end) {
+                                                         float* __restrict__ table, const int* __restrict__ csc_end,
+                                                         float* __restrict__ fwd_taps, int csc_blocks) {
   constexpr int kLd = kRec + 4;                          // 36 floats: 16-byte aligned rows, 8 lanes per 128 B then a 144-B step
   __shared__ __align__(16) float stage[4][64 * kLd];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if ((int)blockIdx.x >= csc_blocks) {
+    // The forward's tap records (message_kernels.hip), in the CSR order it walks: the workgroups behind the CSC ones
+    // restate, per edge, exactly what the forward evaluates in its loop when it has no records -- hn_envelope,
+    // hn_window_lo and coop_taps' g = exp(coeff (u - mu)^2) with mu = offset[clamp(lo + m)] -- so that the kernel fed
+    // from them returns the same bits.  (Same launch, own workgroups: written from the CSC workgroups the records would
+    // be 64-byte stores scattered by csc_pos, and the CSC positions past the last segment have no CSR edge to write.)
+    constexpr int kF = HN_FWD_TAPS_FLOATS, kLdF = kF + 4;
+    const int e0 = (((int)blockIdx.x - csc_blocks) * 4 + wave) * 64;
+    if (e0 >= E) return;
+    const float u = edge[min(e0 + lane, E - 1)].w * inv_rc;
+    const float env_val = fwd_envelope_val(u, env_kind, env_p);
+    const int lo = hn_window_lo(u, R);
+    float t[kF];
+#pragma unroll
+    for (int m = 0; m < HN_TAPS; ++m) {
+      int k = lo + m;
+      k = k < 0 ? 0 : (k >= R ? R - 1 : k);
+      const float diff = u - offset[k];
+      t[m] = __expf(coeff * (diff * diff));
+    }
+    t[12] = env_val;
+    t[13] = __int_as_float(lo + HN_PAD);
+    t[14] = t[15] = 0.f;
+    float* st = stage[wave];
+#pragma unroll
+    for (int w = 0; w < kF / 4; ++w)
+      *reinterpret_cast<float4*>(st + lane * kLdF + 4 * w) = make_float4(t[4 * w], t[4 * w + 1], t[4 * w + 2], t[4 * w + 3]);
+    // (one wave's LDS operations execute in order) 64 records leave as four coalesced 1-KiB stores
+    const int nrec = min(64, E - e0);
+    float4* out = reinterpret_cast<float4*>(fwd_taps + (size_t)e0 * kF);
+#pragma unroll
+    for (int j = 0; j < kF / 4; ++j) {
+      const int idx = j * 64 + lane, r = idx / (kF / 4), w = idx % (kF / 4);
+      if (r < nrec) out[idx] = *reinterpret_cast<const float4*>(st + r * kLdF + 4 * w);
+    }
+    return;
+  }
   const int q0 = (blockIdx.x * 4 + wave) * 64;           // first record of this wave
   if (q0 >= E) return;
   const int q = q0 + lane;
@@ -732,15 +784,23 @@ int hn_bwd_cl_launch(HnBwdClArgs a, bool has_vec, int rows_override, const int* 
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }
 
-extern "C" int hermnet_edge_radial_table(const hn_graph* g, const hn_rbf_desc* rbf, const float* edge, float* table,
-                                         void* stream) {
+extern "C" int hermnet_edge_radial_tables(const hn_graph* g, const hn_rbf_desc* rbf, const float* edge, float* table,
+                                          float* fwd_taps, void* stream) {
   if (!g || !rbf || rbf->num_rbf < 2 || g->num_edges < 0) return HN_ERR_BAD_ARG;
   const int num_edges = g->num_edges;
   if (num_edges == 0) return HN_OK;
   if (!edge || !table || !rbf->offset || !g->csc_pos || !g->csc_rowptr) return HN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(edge_table_kernel, dim3((num_edges + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+  // one launch: the workgroups of the CSC table, then (fwd_taps given) as many again for the forward's CSR records
+  const int csc_blocks = (num_edges + 255) / 256;
+  hipLaunchKernelGGL(edge_table_kernel, dim3(fwd_taps ? 2 * csc_blocks : csc_blocks), dim3(256), 0, (hipStream_t)stream,
                      reinterpret_cast<const float4*>(edge), g->csc_pos, num_edges, rbf->offset, rbf->num_rbf, rbf->inv_rc,
                      rbf->coeff, rbf->env_kind, rbf->env_p, table,
-                     g->csc_rowptr + (size_t)g->num_rel * (size_t)(g->num_src > 0 ? g->num_src : g->num_nodes));
+                     g->csc_rowptr + (size_t)g->num_rel * (size_t)(g->num_src > 0 ? g->num_src : g->num_nodes), fwd_taps,
+                     csc_blocks);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_edge_radial_table(const hn_graph* g, const hn_rbf_desc* rbf, const float* edge, float* table,
+                                         void* stream) {
+  return hermnet_edge_radial_tables(g, rbf, edge, table, nullptr, stream);
 }

@@ -58,6 +58,7 @@ struct MsgArgs {
   const float* wt;     // [T,R,3H]
   const float* brbf;   // [T,3H]
   const float4* edge;  // [E] (rx,ry,rz,d)
+  const float* fwd_taps;   // fwd: [E][HN_FWD_TAPS_FLOATS] tap records in CSR order (hermnet_edge_radial_tables), or null
   float* x1;           // fwd out
   float* vec1;         // fwd out
   const float* xh_bias;  // [T,3H] or null: bias of the x_proj output, added on load (xh holds the GEMM without it)
@@ -282,8 +283,13 @@ __device__ __forceinline__ int decode_block(const MsgArgs& a, int bx, int& t, in
 // ------------------------------------------------------------------------------------------
 // Forward: one workgroup = (relation, column block, chunk of target rows).
 // ------------------------------------------------------------------------------------------
+// With the step's tap records (REC) a wave fetches the four records of its edge slots with ONE coalesced 256-byte load
+// (lane l: word l % 16 of the record of slot l / 16) an iteration ahead, parks them in its LDS scratch and every lane group
+// reads its own back as broadcasts (3 x ds_read_b128 + ds_read_b64): one VGPR of look-ahead.  (Whole records loaded into
+// registers, 4 x dwordx4 per lane: 203 VGPRs, layer 0 spills at its 128; measured slower than no records)
 struct FwdIn {
   float4 g;        // (rx, ry, rz, d)
+  float rec;       // REC: word `gl` of the edge's tap record
   Vec xs, xa, xb;
   Vec vj[3];
   bool live;
@@ -292,7 +298,10 @@ struct FwdIn {
 // NW waves per workgroup: 8 with vec rows, 16 for layer 0 (no vec rows, <= 128 VGPRs).
 // WIN: the launch works on a window of the tap rows (MsgArgs::win_*): an edge it does not own is a padding slot (lv = 0)
 // reading a clamped tile row; with win_accumulate the epilogue adds to the other launch's rows.
-template <bool HAS_VEC, int NW, bool WIN>
+// REC: everything that depends on the edge alone -- the twelve taps, the envelope, the tile row -- comes from the per-edge
+// records written once per step (MsgArgs::fwd_taps) instead of being evaluated here, in every layer and column block; the
+// records hold the values this kernel computes without them, so both forms return the same bits.
+template <bool HAS_VEC, int NW, bool WIN, bool REC>
 __global__ __launch_bounds__(NW * 64, NW / 4) void message_scatter_fwd_kernel(MsgArgs a) {
   extern __shared__ __align__(16) float lds[];
   const int tile_rows = WIN ? a.win_rows : a.R + 2 * HN_PAD + 1;
@@ -358,6 +367,9 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void message_scatter_fwd_kernel(Ms
         const int idx = VW * it + grp;
         in.live = idx < cnt;
         in.g = a.edge[base + (in.live ? idx : 0)];
+        if (REC) {   // (always the record of an edge of this row: no look-ahead past the table's end)
+          in.rec = a.fwd_taps[(size_t)(base + (in.live ? idx : 0)) * HN_FWD_TAPS_FLOATS + gl];
+        }
       };
       auto load_rows = [&](int it, FwdIn& in) {
         const int j = __shfl(my_src, VW * it + grp, 64);
@@ -383,21 +395,37 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void message_scatter_fwd_kernel(Ms
         FwdIn nxt;
         load_geom(min(it + 1, nit - 1), nxt);
         __builtin_amdgcn_sched_barrier(0);
-        const float u = cur.g.w * a.inv_rc;
-        const HnEnv env = hn_envelope(u, a.env_kind, a.env_p);
-        const int lo = hn_window_lo(u, a.R);
-        int trow = lo + HN_PAD;                               // padded tile row of tap 0
+        float g[HN_TAPS], gd[HN_TAPS];
+        float env_val;
+        int trow;                                             // padded tile row of tap 0
+        if (REC) {
+          float t[HN_FWD_TAPS_FLOATS];
+          float* tf = reinterpret_cast<float*>(tb);
+          tf[gl] = cur.rec;       // (one wave's LDS operations execute in order: no barrier before the reads)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) *reinterpret_cast<float4*>(t + 4 * q) = *reinterpret_cast<const float4*>(tf + 4 * q);
+          *reinterpret_cast<float2*>(t + 12) = *reinterpret_cast<const float2*>(tf + 12);
+#pragma unroll
+          for (int m = 0; m < HN_TAPS; ++m) g[m] = t[m];
+          env_val = t[12];
+          trow = __float_as_int(t[13]);
+        } else {
+          const float u = cur.g.w * a.inv_rc;
+          const HnEnv env = hn_envelope(u, a.env_kind, a.env_p);
+          const int lo = hn_window_lo(u, a.R);
+          env_val = env.val;
+          trow = lo + HN_PAD;
+          coop_taps(mu, tb, lo, u, a.coeff, gl);
+          rbf_taps<false>(tb, g, gd);
+        }
         bool own = true;
         if (WIN) { own = trow >= a.win_lo && trow < a.win_hi; trow = min(max(trow - a.win_base, 0), a.win_rows - HN_TAPS); }
         const float* wcol = wl + trow * HN_LDS_ROW + VW * gl;
-        float g[HN_TAPS], gd[HN_TAPS];
-        coop_taps(mu, tb, lo, u, a.coeff, gl);
-        rbf_taps<false>(tb, g, gd);
         HN_SB;
         // padding slots (segment length not a multiple of VW) contribute nothing: every term is
         // linear in rbfh = bias + env * S0 (rmnet.py:55), so scale it by 0 for them
         const float lv = (cur.live && own) ? 1.0f : 0.0f;
-        const float ev = env.val * lv;
+        const float ev = env_val * lv;
         Vec S0, S1;
         // message (rmnet.py:61-67), one part at a time to keep the register footprint small
         rbf_part<false>(wcol, g, gd, S0, S1);   // part s -> dx
@@ -419,6 +447,7 @@ __global__ __launch_bounds__(NW * 64, NW / 4) void message_scatter_fwd_kernel(Ms
         load_rows(min(it + 1, nit - 1), cur);
         cur.g = nxt.g;
         cur.live = nxt.live;
+        if (REC) cur.rec = nxt.rec;
       }
     }
     // combine the lane groups, then the residual epilogue (rmnet.py:24-26).  rows_reduce4 leaves ONE channel (col + grp)
@@ -715,11 +744,11 @@ int ensure_lds(kern_t k, size_t lds) {
 
 }  // namespace
 
-extern "C" int hermnet_message_scatter_fwd(const hn_graph* g, const hn_rbf_desc* rbf, int hidden,
-                                           const float* xh, const float* xh_bias, const float* vec, const float* x,
-                                           const float* wt, const float* brbf, const float* edge,
-                                           float* x1, float* vec1, const int* target_ranges, int zero_unknown_rows,
-                                           int range_rows, void* stream) {
+extern "C" int hermnet_message_scatter_fwd_taps(const hn_graph* g, const hn_rbf_desc* rbf, int hidden,
+                                                const float* xh, const float* xh_bias, const float* vec, const float* x,
+                                                const float* wt, const float* brbf, const float* edge,
+                                                const float* fwd_taps, float* x1, float* vec1, const int* target_ranges,
+                                                int zero_unknown_rows, int range_rows, void* stream) {
   MsgArgs a = {};
   int rc = fill_args(g, rbf, hidden, a);
   if (rc) return rc;
@@ -727,6 +756,7 @@ extern "C" int hermnet_message_scatter_fwd(const hn_graph* g, const hn_rbf_desc*
   if (a.N == 0) return HN_OK;
   a.xh = xh; a.xh_bias = xh_bias; a.vec = vec; a.x = x; a.wt = wt; a.brbf = brbf;
   a.edge = reinterpret_cast<const float4*>(edge);
+  a.fwd_taps = fwd_taps;
   a.x1 = x1; a.vec1 = vec1;
   a.row_ranges = target_ranges; a.zero_unknown = (target_ranges == nullptr) || zero_unknown_rows;
   const int rpb_fwd = hn_option(HN_OPT_FWD_ROWS);
@@ -749,7 +779,8 @@ extern "C" int hermnet_message_scatter_fwd(const hn_graph* g, const hn_rbf_desc*
     const int held = split + HN_PAD > rows_all - split ? split + HN_PAD : rows_all - split;
     lds = lds_bytes(a.R, held);
     if (lds > 160 * 1024) return HN_ERR_LDS;
-    kern_t k = vec ? message_scatter_fwd_kernel<true, 8, true> : message_scatter_fwd_kernel<false, 16, true>;
+    kern_t k = fwd_taps ? (vec ? message_scatter_fwd_kernel<true, 8, true, true> : message_scatter_fwd_kernel<false, 16, true, true>)
+                        : (vec ? message_scatter_fwd_kernel<true, 8, true, false> : message_scatter_fwd_kernel<false, 16, true, false>);
     if (ensure_lds(k, lds) != HN_OK) return HN_ERR_LDS;
     a.win_base = 0; a.win_rows = split + HN_PAD; a.win_lo = 0; a.win_hi = split; a.win_accumulate = 0;
     hipLaunchKernelGGL(k, grid, dim3(nw * 64), lds, s, a);
@@ -758,10 +789,20 @@ extern "C" int hermnet_message_scatter_fwd(const hn_graph* g, const hn_rbf_desc*
     hipLaunchKernelGGL(k, grid, dim3(nw * 64), lds, s, a);
     return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
   }
-  kern_t k = vec ? message_scatter_fwd_kernel<true, 8, false> : message_scatter_fwd_kernel<false, 16, false>;
+  kern_t k = fwd_taps ? (vec ? message_scatter_fwd_kernel<true, 8, false, true> : message_scatter_fwd_kernel<false, 16, false, true>)
+                      : (vec ? message_scatter_fwd_kernel<true, 8, false, false> : message_scatter_fwd_kernel<false, 16, false, false>);
   if (ensure_lds(k, lds) != HN_OK) return HN_ERR_LDS;
   hipLaunchKernelGGL(k, grid, dim3(nw * 64), lds, s, a);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_message_scatter_fwd(const hn_graph* g, const hn_rbf_desc* rbf, int hidden,
+                                           const float* xh, const float* xh_bias, const float* vec, const float* x,
+                                           const float* wt, const float* brbf, const float* edge,
+                                           float* x1, float* vec1, const int* target_ranges, int zero_unknown_rows,
+                                           int range_rows, void* stream) {
+  return hermnet_message_scatter_fwd_taps(g, rbf, hidden, xh, xh_bias, vec, x, wt, brbf, edge, nullptr, x1, vec1,
+                                          target_ranges, zero_unknown_rows, range_rows, stream);
 }
 
 extern "C" int hermnet_message_scatter_bwd(const hn_graph* g, const hn_rbf_desc* rbf, int hidden,

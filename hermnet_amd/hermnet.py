@@ -8,7 +8,7 @@ from torch import nn
 
 from . import switches
 from .elements import atomic_numbers
-from .ops import EdgeGeometry, TrueEdgeGradient, edge_radial_table
+from .ops import EdgeGeometry, TrueEdgeGradient, edge_radial_tables
 from .relations import RelationalGraph
 from .sharding import HaloExchange, HaloExchangeFeatures, HaloGradReturn, SumAcrossRanks
 from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, GemmRelationalLayer, LayerWeights, Route,
@@ -382,9 +382,11 @@ class HVNet(nn.Module):
         if not fused and not train:
             edge = TrueEdgeGradient.apply(edge)      # autograd's (rhat, d) gradients -> Cartesian for the kernel
         data._hn_graph, data._hn_edge, data._hn_rbf = graph, edge, rbf
+        graph.fwd_taps = None      # (records of an earlier step's coordinates must not feed this step's forward)
         if fused and edge.requires_grad and edge.is_cuda:
-            # forces wanted: the backward message kernels read the radial quantities of an edge from this table
-            graph.edge_table = edge_radial_table(graph, rbf, edge.detach())
+            # forces wanted: the backward message kernels read the radial quantities of an edge from this table, the
+            # forward ones of every layer from the tap records the same launch writes
+            graph.edge_table, graph.fwd_taps = edge_radial_tables(graph, rbf, edge.detach())
         # rmnet.py:168-172 for the optional bases only: [E,R] basis from the kernel's distances
         if fused:
             data._hn_edge_embed = None

@@ -224,11 +224,12 @@ def _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=True, ranges=None, zero
     else:
         x1, vec1 = out
     gs, rs = graph.as_struct(), rbf.struct()
+    # (graph.fwd_taps: the step's per-edge tap records, or None -- the kernel then evaluates them itself; same bits)
     _lib.check(_launch("message_scatter_fwd" + ("" if vec is not None else "_l0"),
-                       lambda: lib.hermnet_message_scatter_fwd(
+                       lambda: lib.hermnet_message_scatter_fwd_taps(
                            ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(b2), P(vec), P(x), P(w.wt), P(w.brbf), P(edge),
-                           P(x1), P(vec1), P(ranges), 1 if zero_unknown else 0, int(range_rows), _stream())),
-               "hermnet_message_scatter_fwd")
+                           P(graph.fwd_taps), P(x1), P(vec1), P(ranges), 1 if zero_unknown else 0, int(range_rows), _stream())),
+               "hermnet_message_scatter_fwd_taps")
     return x1, vec1
 
 
@@ -326,3 +327,17 @@ def edge_radial_table(graph, rbf, edge):
     _lib.check(_launch("edge_radial_table", lambda: _lib.load().hermnet_edge_radial_table(
         ctypes.byref(gs), ctypes.byref(rs), _lib.ptr(edge), _lib.ptr(table), _stream())), "hermnet_edge_radial_table")
     return table
+
+
+def edge_radial_tables(graph, rbf, edge):
+    """`edge_radial_table` and, from the same launch, the forward's tap records [E,16] in CSR order (twelve raw taps, the
+    envelope, the tile row of every edge: `include/hermnet_hip.h`: hermnet_edge_radial_tables), which the forward message
+    kernel of every layer reads instead of evaluating them.  Returns (table, fwd_taps)."""
+    E = edge.size(0)
+    table = torch.empty(E + 1, 32, dtype=torch.float32, device=edge.device)
+    taps = torch.empty(E, 16, dtype=torch.float32, device=edge.device)
+    gs, rs = graph.as_struct(), rbf.struct()
+    _lib.check(_launch("edge_radial_table", lambda: _lib.load().hermnet_edge_radial_tables(
+        ctypes.byref(gs), ctypes.byref(rs), _lib.ptr(edge), _lib.ptr(table), _lib.ptr(taps), _stream())),
+        "hermnet_edge_radial_tables")
+    return table, taps

@@ -350,6 +350,23 @@ int hermnet_message_scatter_bwd(const hn_graph* g, const hn_rbf_desc* rbf, int h
  * workspace [T, N, 3, H] (per-relation partial sums of gvec, added up in a fixed order by a second small launch;
  * not needed when T = 1 or vec is NULL); without it the 16-lanes-per-edge form runs. */
 int hermnet_edge_radial_table(const hn_graph* g, const hn_rbf_desc* rbf, const float* edge, float* table, void* stream);
+/* The same launch, which also writes the forward's tap records (fwd_taps NULL: exactly hermnet_edge_radial_table):
+ * fwd_taps [E, 16] floats in CSR order -- record e belongs to edge[e] --
+ *   [0..11] g_m = exp(coeff (u - mu_{lo+m})^2), the raw taps (no envelope folded in) | [12] env(u) |
+ *   [13] padded tile row of tap 0 (int bits) | [14,15] 0
+ * evaluated exactly as hermnet_message_scatter_fwd evaluates them in its edge loop (same expressions, clamping and
+ * operation order), once per step instead of once per layer and column block.  Every one of the E records is written;
+ * the reader requests only records of edges of the row it works on, so there is no spare record behind the last. */
+int hermnet_edge_radial_tables(const hn_graph* g, const hn_rbf_desc* rbf, const float* edge, float* table, float* fwd_taps,
+                               void* stream);
+/* hermnet_message_scatter_fwd with the taps, envelope and tile row of every edge read from `fwd_taps` (above; built from
+ * the same graph, radial basis and `edge`).  Bit for bit the result of hermnet_message_scatter_fwd; fwd_taps NULL: that
+ * entry point itself. */
+int hermnet_message_scatter_fwd_taps(const hn_graph* g, const hn_rbf_desc* rbf, int hidden,
+                                     const float* xh, const float* xh_bias, const float* vec, const float* x,
+                                     const float* wt, const float* brbf, const float* edge, const float* fwd_taps,
+                                     float* x1, float* vec1, const int* target_ranges, int zero_unknown_rows,
+                                     int range_rows, void* stream);
 
 /* ---- node-level fused elementwise stages (A11/A12; the GEMMs between them are library calls) ----
  * Bias convention of these stages: the GEMM in front of a stage may run WITHOUT its bias (a GEMM with a

@@ -57,13 +57,20 @@ def main():
     gs, rs = g.as_struct(), rbf.struct()
     P = _lib.ptr
 
-    def fwd(v):
-        return lib.hermnet_message_scatter_fwd(ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(xb), P(v), P(x), P(wt), P(brbf),
-                                               P(edge), P(x1), P(vec1), None, 1, 0, _stream())
-
     # KBENCH_TABLE=0: without the per-edge radial table the backward takes its 16-lanes-per-edge form
-    from hermnet_amd.ops import edge_radial_table
-    table = edge_radial_table(g, rbf, edge) if os.environ.get("KBENCH_TABLE", "1") != "0" else None
+    from hermnet_amd.ops import edge_radial_tables
+    table, taps = edge_radial_tables(g, rbf, edge) if os.environ.get("KBENCH_TABLE", "1") != "0" else (None, None)
+
+    # the forward is timed both ways in one job: fed from the step's tap records ("+taps") and evaluating them itself
+    def fwd(v, t=None):
+        return lib.hermnet_message_scatter_fwd_taps(ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(xb), P(v), P(x), P(wt),
+                                                    P(brbf), P(edge), P(t), P(x1), P(vec1), None, 1, 0, _stream())
+
+    def fwd_taps(v):
+        return fwd(v, taps)
+
+    def tables(_):
+        return lib.hermnet_edge_radial_tables(ctypes.byref(gs), ctypes.byref(rs), P(edge), P(table), P(taps), _stream())
 
     part = torch.empty(T, N, 3, H, device=dev) if table is not None else None
 
@@ -74,8 +81,14 @@ def main():
 
     ab = algorithmic_bytes(E, N, H, T)
     res = {}
-    for name, fn, arg in [("message_scatter_fwd", fwd, vec), ("message_scatter_fwd_l0", fwd, None),
-                          ("message_scatter_bwd", bwd, vec), ("message_scatter_bwd_l0", bwd, None)]:
+    runs = [("message_scatter_fwd", fwd, vec), ("message_scatter_fwd_l0", fwd, None),
+            ("message_scatter_bwd", bwd, vec), ("message_scatter_bwd_l0", bwd, None)]
+    if taps is not None:
+        runs += [("message_scatter_fwd+taps", fwd_taps, vec), ("message_scatter_fwd_l0+taps", fwd_taps, None),
+                 ("message_scatter_fwd", fwd, vec), ("message_scatter_fwd+taps", fwd_taps, vec),     # (again: the spread)
+                 ("edge_radial_tables", tables, None)]
+    sums = {}
+    for name, fn, arg in runs:
         for _ in range(3):
             assert fn(arg) == 0
         torch.cuda.synchronize()
@@ -87,7 +100,9 @@ def main():
         torch.cuda.synchronize()
         ms = a.elapsed_time(b) / iters
         res[name] = ms
-        print("%-24s %8.3f ms  %7.1f GB/s (algorithmic)" % (name, ms, ab[name] / 1e6 / ms))
+        print("%-28s %8.3f ms  %7.1f GB/s (algorithmic)" % (name, ms, ab.get(name.replace("+taps", ""), 0) / 1e6 / ms))
+        if "fwd" in name:
+            sums[name] = float(x1.double().sum() + vec1.double().sum())
         if hasattr(lib, "hermnet_debug_stamps_cl") and "bwd" in name and table is not None:
             buf = (ctypes.c_ulonglong * 12)()
             lib.hermnet_debug_stamps_cl(buf)
@@ -100,6 +115,8 @@ def main():
                          100 * red / tot, 100 * epi / tot, rec / edges, con / edges, alg / edges, red / edges, pro / segs,
                          epi / segs, edges / segs))
     knobs = {k: v for k, v in os.environ.items() if k.startswith("HERMNET_") or k.startswith("KBENCH_") or k == "HN_OPTIONS"}
+    for name in sums:          # the two forms of the forward return the same bits
+        assert sums[name] == sums[name.replace("+taps", "")], (name, sums)
     print("knobs", knobs, "checksum", float(x1.sum() + vec1.sum()), float(gxh.sum() + gvec.sum() + gedge.sum()))
 
 
