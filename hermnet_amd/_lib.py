@@ -60,6 +60,8 @@ SIGNATURES = {
                                                    c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                                    c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp,
                                                    c_fp, c_fp, ctypes.c_int, c_fp]),
+    "hermnet_message_scatter_bwd_gedge": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int] +
+                                          [c_fp] * 9),
     "hermnet_edge_radial_table": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), c_fp, c_fp, c_fp]),
     "hermnet_edge_radial_tables": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), c_fp, c_fp, c_fp, c_fp]),
     "hermnet_message_scatter_fwd_taps": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int,
@@ -126,6 +128,8 @@ SIGNATURES = {
     "hermnet_node_update_fwd": (ctypes.c_int, [c_fp] * 16 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
     "hermnet_node_update_bwd": (ctypes.c_int, [c_fp] * 14 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp,
                                                            c_fp]),
+    "hermnet_node_update_fwd_last": (ctypes.c_int, [c_fp] * 15 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
+    "hermnet_node_update_bwd_last": (ctypes.c_int, [c_fp] * 13 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
     "hermnet_node_fused_supported": (ctypes.c_int, [ctypes.c_int]),
     "hermnet_node_update_pre_fwd": (ctypes.c_int, [c_fp] * 16 + [ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_fp] * 8 +
                                     [ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp]),

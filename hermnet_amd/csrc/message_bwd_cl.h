@@ -25,7 +25,7 @@ struct HnBwdClArgs {
   const float* brbf;         // [T, 3H]
   const float* gx1;          // [N, H]
   const float* gvec1;        // [N, 3, H]
-  float* gxh;                // [T, Nsrc, 3H]
+  float* gxh;                // [T, Nsrc, 3H] (null in the form without source-row gradients)
   float* gvec;               // workspace [T, Nsrc, 3, H] partial sums per relation (null when vec is null)
   float* gvec_out;           // [Nsrc, 3, H] or null
   float* gx;                 // [Nsrc, H]
@@ -45,4 +45,5 @@ struct HnBwdClArgs {
 
 size_t hn_bwd_cl_lds_bytes(int R);
 // `ranges_host`: the same [num_ranges][2] values on the host (grid size)
-int hn_bwd_cl_launch(HnBwdClArgs a, bool has_vec, int rows_override, const int* ranges_host, hipStream_t s);
+// `need_gxh` = false: layer 0 of a force evaluation (no vec rows, no finishing launch) -- only gedge is written
+int hn_bwd_cl_launch(HnBwdClArgs a, bool has_vec, bool need_gxh, int rows_override, const int* ranges_host, hipStream_t s);

@@ -275,8 +275,14 @@ struct EdgeIn {          // what one edge needs from memory (vector part)
 #ifndef HN_KO_BWD
 #define HN_KO_BWD 0      // 1: no contraction, 2: no channel algebra (diagnostic builds: tools/build_variant.sh)
 #endif
-template <bool HAS_VEC, bool WIN>
-__global__ __launch_bounds__(1024, 4) void message_scatter_bwd_cl_kernel(HnBwdClArgs a) {
+//
+// NEED_GXH = false (layer 0 of an energy / force evaluation, HAS_VEC = false only): x of the first layer is the species
+// embedding, which does not depend on the positions, so nothing below wants the source rows' gradients -- no gs / gb sums,
+// an empty row epilogue, no gxh array (a.gxh may be null).  What gedge depends on is instruction for instruction the
+// general form's: the same bits.
+template <bool HAS_VEC, bool WIN, bool NEED_GXH>
+__device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a) {
+  static_assert(NEED_GXH || !HAS_VEC, "rows with a vec part always hand gradients down");
   extern __shared__ __align__(16) float4 tile[];     // [tap row][64] of (s, a, b, 0)
   const int tile_rows = WIN ? a.win_rows : a.R + 2 * HN_PAD + 1;
   const int tile_base = WIN ? a.win_base : 0;        // padded tile row held by tile[0..63]
@@ -344,7 +350,7 @@ __global__ __launch_bounds__(1024, 4) void message_scatter_bwd_cl_kernel(HnBwdCl
   }
 
   const unsigned long long xh_t = uniform_addr(a.xh + (size_t)t * a.Nsrc * 3 * H);
-  const unsigned long long gxh_t = uniform_addr(a.gxh + (size_t)t * a.Nsrc * 3 * H);
+  const unsigned long long gxh_t = NEED_GXH ? uniform_addr(a.gxh + (size_t)t * a.Nsrc * 3 * H) : 0ull;
   const unsigned long long gvec_t = HAS_VEC ? uniform_addr(a.gvec + (size_t)t * a.Nsrc * 3 * H) : 0ull;
   const unsigned long long vec_a = HAS_VEC ? uniform_addr(a.vec) : 0ull;
   const int* rowptr_t = a.csc_rowptr + (size_t)t * a.Nsrc;
@@ -408,6 +414,7 @@ __global__ __launch_bounds__(1024, 4) void message_scatter_bwd_cl_kernel(HnBwdCl
       fresh = false;
     };
     auto row_epilogue = [&](int r) {                 // every lane owns its channel: plain coalesced stores
+      if constexpr (!NEED_GXH) return;
       const unsigned ro = (unsigned)__builtin_amdgcn_readfirstlane(r * (3 * H));
       const hn_rsrc go = row_rsrc(gxh_t, ro, H);
       if constexpr (WIN) {
@@ -561,7 +568,7 @@ __global__ __launch_bounds__(1024, 4) void message_scatter_bwd_cl_kernel(HnBwdCl
         // (the .x sums are rbfh - bias, the .y sums d rbfh / d d: see the record layout)
         // ---- part s: dx = sum xs * rs
         const float rs = Ss.x + bs;
-        gs = fmaf(gx1, rs, gs);
+        if (NEED_GXH) gs = fmaf(gx1, rs, gs);
         float pdv = gx1 * xs * Ss.y;
         // ---- part a: dvec += vec_j * (xa * ra) / sqrt(3H)
         if (HAS_VEC) {
@@ -575,7 +582,7 @@ __global__ __launch_bounds__(1024, 4) void message_scatter_bwd_cl_kernel(HnBwdCl
         // ---- part b: dvec += rhat * (xb * rb) / sqrt(H)
         const float rb_ = Sb.x + bb;
         const float B = fmaf(rx, g0, fmaf(ry, g1, rz * g2));
-        gb = fmaf(B, rb_, gb);
+        if (NEED_GXH) gb = fmaf(B, rb_, gb);
         pdv = fmaf(B * xb, Sb.y, pdv);
         // ---- this channel's share of dE/dD, already Cartesian (rhat and 1/d are wave-uniform scalars here):
         // d = |D|, rhat = D/d:  gD = pd rhat + (pr - (pr.rhat) rhat) / d  with  pr = q (g0,g1,g2), pr.rhat = q B
@@ -630,6 +637,16 @@ __global__ __launch_bounds__(1024, 4) void message_scatter_bwd_cl_kernel(HnBwdCl
       gs = 0.f; ga = 0.f; gb = 0.f; gv0 = 0.f; gv1 = 0.f; gv2 = 0.f;
     }
   }
+}
+
+template <bool HAS_VEC, bool WIN>
+__global__ __launch_bounds__(1024, 4) void message_scatter_bwd_cl_kernel(HnBwdClArgs a) {
+  message_scatter_bwd_cl_body<HAS_VEC, WIN, true>(a);
+}
+// the NEED_GXH = false instances (a kernel name of their own: the four general instances keep theirs)
+template <bool WIN>
+__global__ __launch_bounds__(1024, 4) void message_edge_bwd_cl_kernel(HnBwdClArgs a) {
+  message_scatter_bwd_cl_body<false, WIN, false>(a);
 }
 
 // gvec[r] = sum_t part[t][r] (+ gvec1[r] on target rows), gx[r] = gx1[r] / sqrt2 on target rows, 0 elsewhere.
@@ -692,7 +709,10 @@ size_t hn_bwd_cl_lds_bytes(int R) {
   return (size_t)(R + 2 * HN_PAD + 1) * HN_CB * sizeof(float4);
 }
 
-int hn_bwd_cl_launch(HnBwdClArgs a, bool has_vec, int rows_override, const int* ranges_host, hipStream_t s) {
+int hn_bwd_cl_launch(HnBwdClArgs a, bool has_vec, bool need_gxh, int rows_override, const int* ranges_host, hipStream_t s) {
+  // without source-row gradients: the layer-0 form only, and never with a finishing launch (which would read them)
+  // (the general form's gxh is checked by its entry point, hermnet_message_scatter_bwd)
+  if (!need_gxh && (has_vec || a.gx != nullptr)) return HN_ERR_BAD_ARG;
   // The whole tile (num_rbf + 23 rows of 1 KiB) fits the LDS up to num_rbf = 137.  Beyond that: two launches over
   // tap-row windows.  The first owns the edges whose first tap row is below `split` and stages rows [0, split + 11), the
   // second owns the rest and stages [split, rows): 145 rows each at num_rbf = 256, 160 at 286 (the limit).
@@ -706,8 +726,9 @@ int hn_bwd_cl_launch(HnBwdClArgs a, bool has_vec, int rows_override, const int* 
   typedef void (*kern_t)(HnBwdClArgs);
   kern_t k = windowed ? (has_vec ? message_scatter_bwd_cl_kernel<true, true> : message_scatter_bwd_cl_kernel<false, true>)
                       : (has_vec ? message_scatter_bwd_cl_kernel<true, false> : message_scatter_bwd_cl_kernel<false, false>);
-  static bool done[4] = {false, false, false, false};
-  const int which = (windowed ? 2 : 0) + (has_vec ? 1 : 0);
+  if (!need_gxh) k = windowed ? message_edge_bwd_cl_kernel<true> : message_edge_bwd_cl_kernel<false>;
+  static bool done[6] = {false, false, false, false, false, false};
+  const int which = need_gxh ? (windowed ? 2 : 0) + (has_vec ? 1 : 0) : (windowed ? 5 : 4);
   if (!done[which]) {      // (once per kernel, for the largest tile it can be given: a host-side attribute)
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                             kMaxRows * HN_CB * (int)sizeof(float4)) != hipSuccess)

@@ -848,7 +848,7 @@ extern "C" int hermnet_message_scatter_bwd(const hn_graph* g, const hn_rbf_desc*
     const int rpb_cl = hn_option(HN_OPT_BWD_CL_ROWS);
     b.xcd_remap = 1;
     b.src_ranges = source_ranges; b.num_ranges = num_ranges;
-    return hn_bwd_cl_launch(b, vec != nullptr, rpb_cl, source_ranges_host, reinterpret_cast<hipStream_t>(stream));
+    return hn_bwd_cl_launch(b, vec != nullptr, true, rpb_cl, source_ranges_host, reinterpret_cast<hipStream_t>(stream));
   }
   a.xh = xh; a.xh_bias = xh_bias; a.vec = vec; a.wt = wt; a.brbf = brbf;
   a.edge = reinterpret_cast<const float4*>(edge);
@@ -864,4 +864,28 @@ extern "C" int hermnet_message_scatter_bwd(const hn_graph* g, const hn_rbf_desc*
   if (ensure_lds(k, lds) != HN_OK) return HN_ERR_LDS;
   hipLaunchKernelGGL(k, grid, dim3(BWD_NW * 64), lds, s, a);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_message_scatter_bwd_gedge(const hn_graph* g, const hn_rbf_desc* rbf, int hidden,
+                                                 const float* xh, const float* wt, const float* brbf,
+                                                 const float* edge, const float* gx1, const float* gvec1,
+                                                 float* gedge, const float* edge_table, void* stream) {
+  MsgArgs a = {};
+  int rc = fill_args(g, rbf, hidden, a);
+  if (rc) return rc;
+  if (!xh || !wt || !brbf || !gx1 || !gvec1 || !edge_table || (g->num_edges > 0 && (!gedge || !edge))) return HN_ERR_BAD_ARG;
+  if (g->num_src > 0 || g->res_row != nullptr) return HN_ERR_BAD_ARG;
+  if (a.N == 0) return HN_OK;
+  // the channel-per-lane form's limits (32-bit buffer and row offsets), as in hermnet_message_scatter_bwd
+  if ((size_t)a.N * 3 * hidden * sizeof(float) >= 0xffffffffull || hn_option(HN_OPT_BWD_LANES16) != 0) return HN_ERR_BAD_ARG;
+  HnBwdClArgs b = {};
+  b.N = a.N; b.Nsrc = a.N; b.E = a.E; b.T = a.T;
+  b.identity = 1;
+  b.csc_rowptr = a.csc_rowptr; b.csc_tgt = a.csc_tgt; b.csc_pos = a.csc_pos;
+  b.R = a.R; b.H = hidden; b.table = edge_table; b.edge = reinterpret_cast<const float4*>(edge);
+  b.xh = xh; b.wt = wt; b.brbf = brbf; b.gx1 = gx1; b.gvec1 = gvec1;     // (xh includes x_proj's bias; no vec rows)
+  b.gedge = reinterpret_cast<float4*>(gedge);
+  b.type_rowptr = g->type_rowptr;
+  b.xcd_remap = 1;
+  return hn_bwd_cl_launch(b, false, false, hn_option(HN_OPT_BWD_CL_ROWS), nullptr, reinterpret_cast<hipStream_t>(stream));
 }

@@ -975,3 +975,38 @@ extern "C" int hermnet_energy_head16_bwd(const float* ge, const float* h, const 
   if (!ge || !h || !w0t_frag16 || !w2 || !gx) return HN_ERR_BAD_ARG;
   return hn_head16_bwd(ge, h, w0t_frag16, w2, row_mask, gx, rows, stream);
 }
+
+// ---- the LAST layer of an energy / force evaluation (csrc/node_chain16.hip: NOVEC / NOGV) -------------------------------------
+// The read-out takes x only: vec_out feeds nothing, its gradient is identically zero.  16-row tiles, width 128.
+extern "C" int hermnet_node_update_fwd_last(const float* x1, const float* vec1, const float* wv_frag16, const float* wx0_frag16,
+                                            const float* bx0, const float* wx2_frag16, const float* bx2,
+                                            const float* row_active, const int* type_rowptr, const int* type_rowptr_host,
+                                            float* vp, float* h2b, float* q2, float* nrm, float* x_out, int num_nodes,
+                                            int num_rel, int hidden, void* stream) {
+  if (num_nodes < 0 || num_rel <= 0 || !type_rowptr_host) return HN_ERR_BAD_ARG;
+  if (!hn_update16_supported(hidden) || use_wide(hidden)) return HN_ERR_BAD_ARG;
+  if (num_nodes == 0) return HN_OK;
+  if (!x1 || !vec1 || !wv_frag16 || !wx0_frag16 || !bx0 || !wx2_frag16 || !bx2 || !type_rowptr || !vp || !h2b || !q2 || !nrm ||
+      !x_out || type_rowptr_host[num_rel] > num_nodes)
+    return HN_ERR_BAD_ARG;
+  UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q2, nrm, x_out,
+                  nullptr, num_nodes, num_rel};
+  return hn_update16_fwd(hidden, a, HN_TILES(16), stream);
+}
+
+extern "C" int hermnet_node_update_bwd_last(const float* gx_out, const float* vp, const float* h2b, const float* q2,
+                                            const float* nrm, const float* wx2t_frag16, const float* wx0t_frag16,
+                                            const float* wvt_frag16, const float* row_active, const int* type_rowptr,
+                                            const int* type_rowptr_host, float* gx1, float* gvec1, int num_nodes, int num_rel,
+                                            int hidden, const hn_pending_grads* pending, void* stream) {
+  if (num_nodes < 0 || num_rel <= 0 || !type_rowptr_host) return HN_ERR_BAD_ARG;
+  if (!hn_update16_supported(hidden) || use_wide(hidden)) return HN_ERR_BAD_ARG;
+  if (pending) return HN_ERR_BAD_ARG;             // no layer above the last one can have handed anything down
+  if (num_nodes == 0) return HN_OK;
+  if (!gx_out || !vp || !h2b || !q2 || !nrm || !wx2t_frag16 || !wx0t_frag16 || !wvt_frag16 || !type_rowptr || !gx1 || !gvec1 ||
+      type_rowptr_host[num_rel] > num_nodes)
+    return HN_ERR_BAD_ARG;
+  UpdBwdArgs a = {gx_out, nullptr, vp, h2b, q2, nrm, wx2t_frag16, wx0t_frag16, wvt_frag16, row_active, type_rowptr, gx1, gvec1,
+                  num_nodes, num_rel, {}};
+  return hn_update16_bwd(hidden, a, HN_TILES(16), stream);
+}

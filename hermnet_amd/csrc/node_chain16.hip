@@ -361,10 +361,16 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_pre_fwd16_kernel(Pr
 // =====================================================================================================================
 // node_update_fwd on 16-row tiles (H = 128: four waves x 32 channels); FUSE: + the next layer's node projection of the tile
 // =====================================================================================================================
-template <int H, bool FUSE>
+// NOVEC (the LAST layer of an energy / force evaluation: the read-out takes x only, so vec_out feeds nothing): the r third of
+// the last product -- its weight fragments and MFMAs --, dvec = r v1 and the vec_out store are left out; q23 receives q only
+// (its r half stays unwritten: the matching backward, NOGV below, does not read it).  Every accumulator block of p and q sees
+// the MFMAs it sees in the general form, in the same order: x_out, vp, h2b, nrm and q are the same bits.
+template <int H, bool FUSE, bool NOVEC = false>
 __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel(UpdFwdArgs a, PreFwdArgs p) {
   static_assert(H == 128, "four waves x 32 channels");
+  static_assert(!(FUSE && NOVEC), "the last layer has no layer above");
   constexpr int TR = kTR16, LD = H + 8, NB16 = H / 16;       // NB16: 16-channel blocks per part
+  constexpr int NQ = NOVEC ? 2 : 3;                          // parts of the last product: (p | q) or (p | q | r)
   extern __shared__ __align__(16) float lds[];               // 3 x [TR][LD], then 4 x [16][36] scratch
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   float* scr = lds + 3 * TR * LD + wave * kScr16Floats;
@@ -376,7 +382,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
       const int r = row0 + idx / V, c = (idx % V) * 4;
       *reinterpret_cast<f32x4*>(a.x_out + (size_t)r * H + c) = zero4();
 #pragma unroll
-      for (int d = 0; d < 3; ++d) *reinterpret_cast<f32x4*>(a.vec_out + ((size_t)r * 3 + d) * H + c) = zero4();
+      for (int d = 0; d < (NOVEC ? 0 : 3); ++d) *reinterpret_cast<f32x4*>(a.vec_out + ((size_t)r * 3 + d) * H + c) = zero4();
     }
     if constexpr (FUSE) {                         // (they are sources all the same: their projection runs on x = 0)
       for (int idx = tid; idx < TR * (H / 4); idx += 256)
@@ -392,7 +398,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
   // this wave's blocks of part p: b = p * NB16 + 2 wave + s
   const f32x4* bpv[4];
   const f32x4* bpx[2];
-  const f32x4* bpq[6];
+  const f32x4* bpq[2 * NQ];
 #pragma unroll
   for (int p = 0; p < 2; ++p)
 #pragma unroll
@@ -400,7 +406,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
 #pragma unroll
   for (int s = 0; s < 2; ++s) bpx[s] = wx0 + (size_t)(2 * wave + s) * frag16_f4(2 * H);
 #pragma unroll
-  for (int p = 0; p < 3; ++p)
+  for (int p = 0; p < NQ; ++p)
 #pragma unroll
     for (int s = 0; s < 2; ++s) bpq[2 * p + s] = wx2 + (size_t)(p * NB16 + 2 * wave + s) * frag16_f4(H);
 
@@ -413,7 +419,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
   const rsrc_t h2b_r = tile_rsrc(a.h2b + (size_t)row0 * H, nrows * H);
   const rsrc_t q23_r = tile_rsrc(a.q23 + (size_t)row0 * 2 * H, nrows * 2 * H);
   const rsrc_t xo_r = tile_rsrc(a.x_out + (size_t)row0 * H, nrows * H);
-  const rsrc_t vo_r = tile_rsrc(a.vec_out + (size_t)row0 * 3 * H, nrows * 3 * H);
+  const rsrc_t vo_r = tile_rsrc(NOVEC ? a.x_out : a.vec_out + (size_t)row0 * 3 * H, NOVEC ? 0 : nrows * 3 * H);
   const rsrc_t nrm_r = tile_rsrc(a.nrm + (size_t)row0 * H, nrows * H);
   f32x4 dot[2] = {zero4(), zero4()}, sq[2] = {zero4(), zero4()};
 
@@ -435,7 +441,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
   tile16_load<H>(regs, x1_r, H, 0, tid);               // (in flight during the product)
   // (accumulators START at their bias -- a lane's float4 of a block is exactly the bias float4 of its channels --, loaded
   // in front of the preceding epilogue's stores: vmcnt retires in order, a bias load issued behind stores waits for them)
-  f32x4 acch[2], accq[6];
+  f32x4 acch[2], accq[2 * NQ];
   {
     f32x4 accv[3][4];
 #pragma unroll
@@ -487,10 +493,10 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
     mma16_panel<H, 2, false>(acch, bufn + mrow * LD + ch, bpx1, rx);
   }
   STAMP(5);
-  Ring16<6> rq;
+  Ring16<2 * NQ> rq;
   b16_preload(rq, bpq);
 #pragma unroll
-  for (int p = 0; p < 3; ++p)
+  for (int p = 0; p < NQ; ++p)
 #pragma unroll
     for (int s = 0; s < 2; ++s) accq[2 * p + s] = ld4g(a.bx2 + (size_t)t * 3 * H + p * H + cw + 16 * s + ch);
   __syncthreads();                                   // buffer 0 is free (x1 stays in buffer 1)
@@ -509,13 +515,15 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
   // vec1 and v1 of component 0, requested before the product; the components behind it one epilogue step ahead.  (v1 was
   // stored by this wave's own lanes: the wait makes the stores of the three vp epilogues final before it is read back.)
   Load16 lvv, lv1;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  issue16<3 * H>(lvv, lane, vec1_r, cw);
-  issue16<6 * H>(lv1, lane, vp_r, cw);
+  if constexpr (!NOVEC) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    issue16<3 * H>(lvv, lane, vec1_r, cw);
+    issue16<6 * H>(lv1, lane, vp_r, cw);
+  }
   const float on = (all_on | (bld(act_r, mrow) != 0.f)) ? 1.f : 0.f;
   fence_sched();
   STAMP(6);
-  mma16_panel<H, 6, false>(accq, lds + mrow * LD + ch, bpq, rq);
+  mma16_panel<H, 2 * NQ, false>(accq, lds + mrow * LD + ch, bpq, rq);
   fence_sched();
   STAMP(7);
   const float inv_sqrt_h = rsqrtf((float)H);
@@ -525,12 +533,12 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
     const int c0 = cw + 16 * s + ch;
     const f32x4 p = accq[s];                         // (incl. bx2)
     q[s] = accq[2 + s];
-    r[s] = accq[4 + s];
+    if constexpr (!NOVEC) r[s] = accq[4 + s];
     const f32x4 x1v = *reinterpret_cast<const f32x4*>(bufx + mrow * LD + c0);
     xo[s] = (x1v + (p + q[s] * dot[s] * inv_sqrt_h) * kInvSqrt2) * on;
   }
   store16<2 * H, true>(scr, lane, q, q23_r, cw);
-  store16<2 * H, true>(scr, lane, r, q23_r, H + cw);
+  if constexpr (!NOVEC) store16<2 * H, true>(scr, lane, r, q23_r, H + cw);
   store16<H>(scr, lane, xo, xo_r, cw);
   if constexpr (FUSE) {
     // the rows this tile has just produced are the next layer's LayerNorm input: a third tile takes them (buffers 0 / 1 may
@@ -539,7 +547,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
     for (int s = 0; s < 2; ++s) *reinterpret_cast<f32x4*>(lds + 2 * TR * LD + mrow * LD + cw + 16 * s + ch) = xo[s];
   }
 #pragma unroll
-  for (int d = 0; d < 3; ++d) {
+  for (int d = 0; d < (NOVEC ? 0 : 3); ++d) {
     f32x4 vo[2], v1[2];
     finish16(scr, lane, lvv, vo);
     finish16(scr, lane, lv1, v1);
@@ -660,9 +668,21 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_pre_bwd16_kernel(Pr
 // =====================================================================================================================
 // node_update_bwd on 16-row tiles; FUSE: the backward of the layer ABOVE's node projection runs in front, on the same rows
 // =====================================================================================================================
-template <int H, bool FUSE>
+// NOGV (the last layer: gvec_out is identically zero and is not passed, a.gvo is null): the backward of dvec = r v1 is left
+// out -- the gq3 = sum_d gv[d] v1[d] panel of the first product with its weight fragments, and the gv terms of gv1 and gvec1;
+// r (the second half of q23) is not read.  Same bits as the general form fed gvo = +0, for finite saved tensors and as long as
+// no accumulator UNDERFLOWS to -0 (a negative partial result below ~1e-45 rounds to -0: the general form's extra +-0 product
+// then turns it into +0 where this form keeps -0 -- the sign of a zero in gx1 / gvec1, nothing else):
+//   * gq3 is (+0) + (+-0) = +0 there, so the third panel adds products (+-0) w to accumulators that come out of MFMAs that
+//     started at +0: an accumulator that is not zero stays what it is, one that is zero is +0 (short of the underflow above, a
+//     sum that starts at +0 does not become -0 in round-to-nearest: exact cancellation gives +0) and stays +0;
+//   * gvec1's accumulator starts at gv = +0 either way;
+//   * gv q3 + s v2 may differ from s v2 in the SIGN of a zero (-0 + +0 = +0), but only as an MFMA operand whose accumulator
+//     started at +0: a +-0 product changes neither a non-zero sum nor a +0 one.
+template <int H, bool FUSE, bool NOGV = false>
 __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel(UpdBwdArgs a) {
   static_assert(H == 128, "four waves x 32 channels");
+  static_assert(!(FUSE && NOGV), "the last layer has no layer above");
   constexpr int TR = kTR16, LD = H + 8, NB16 = H / 16, V = H / 4, F4 = TR * H / 4 / 256;
   // 2 x [TR][LD], then 4 x [16][36] scratch; FUSE: [TR][3H + 8] (later the two tiles), [TR][LD], then the scratch
   extern __shared__ __align__(16) float lds[];
@@ -719,7 +739,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
   const int mrow = lane & 15, ch = 4 * (lane >> 4), cw = 32 * wave;
   const float inv_sqrt_h = rsqrtf((float)H);
   const rsrc_t gxo_r = tile_rsrc(a.gxo + (size_t)row0 * H, nrows * H);
-  const rsrc_t gvo_r = tile_rsrc(a.gvo + (size_t)row0 * 3 * H, nrows * 3 * H);
+  const rsrc_t gvo_r = tile_rsrc(NOGV ? a.gxo : a.gvo + (size_t)row0 * 3 * H, NOGV ? 0 : nrows * 3 * H);
   const rsrc_t vp_r = tile_rsrc(a.vp + (size_t)row0 * 6 * H, nrows * 6 * H);
   const rsrc_t h2b_r = tile_rsrc(a.h2b + (size_t)row0 * H, nrows * H);
   const rsrc_t q23_r = tile_rsrc(a.q23 + (size_t)row0 * 2 * H, nrows * 2 * H);
@@ -741,9 +761,11 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
     for (int d = 0; d < 3; ++d) {
       const f32x4 v1 = bld4(vp_r, (lr * 3 + d) * 2 * H + c);
       const f32x4 v2 = bld4(vp_r, (lr * 3 + d) * 2 * H + H + c);
-      const f32x4 gv = bld4(gvo_r, (lr * 3 + d) * H + c) * on;
       vd += v1 * v2;
-      gq3 += gv * v1;
+      if constexpr (!NOGV) {
+        const f32x4 gv = bld4(gvo_r, (lr * 3 + d) * H + c) * on;
+        gq3 += gv * v1;
+      }
     }
     *reinterpret_cast<f32x4*>(buf0 + lr * LD + c) = gx * kInvSqrt2;
     *reinterpret_cast<f32x4*>(buf1 + lr * LD + c) = gx * vd * (inv_sqrt_h * kInvSqrt2);
@@ -762,11 +784,16 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
     const f32x4* bp1[2] = {bpa[0] + (size_t)frag16_f4(H), bpa[1] + (size_t)frag16_f4(H)};
     const f32x4* bp2[2] = {bpa[0] + (size_t)frag16_f4(2 * H), bpa[1] + (size_t)frag16_f4(2 * H)};
     mma16_panel<H, 2, true>(acc, buf0 + mrow * LD + ch, bpa, ra);
-    __syncthreads();                                 // buffer 0 is free
-    tile16_store<H, LD>(buf0, g3, tid);
-    mma16_panel<H, 2, true>(acc, buf1 + mrow * LD + ch, bp1, ra);
-    __syncthreads();                                 // third part in place, buffer 1 free
-    mma16_panel<H, 2, false>(acc, buf0 + mrow * LD + ch, bp2, ra);
+    if constexpr (!NOGV) {
+      __syncthreads();                               // buffer 0 is free
+      tile16_store<H, LD>(buf0, g3, tid);
+      mma16_panel<H, 2, true>(acc, buf1 + mrow * LD + ch, bp1, ra);
+      __syncthreads();                               // third part in place, buffer 1 free
+      mma16_panel<H, 2, false>(acc, buf0 + mrow * LD + ch, bp2, ra);
+    } else {
+      mma16_panel<H, 2, false>(acc, buf1 + mrow * LD + ch, bp1, ra);
+      __syncthreads();                               // both buffers free
+    }
   }
   STAMP(8);
   Ring16<4> rx;
@@ -792,8 +819,10 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
   // inputs of the later epilogues, requested one product ahead
   Load16 lnr, lgv, lq3, lw1, lw2;
   issue16<H, true>(lnr, lane, nrm_r, cw);
-  issue16<3 * H>(lgv, lane, gvo_r, cw);
-  issue16<2 * H, true>(lq3, lane, q23_r, H + cw);
+  if constexpr (!NOGV) {
+    issue16<3 * H>(lgv, lane, gvo_r, cw);
+    issue16<2 * H, true>(lq3, lane, q23_r, H + cw);
+  }
   issue16<6 * H>(lw1, lane, vp_r, cw);
   issue16<6 * H>(lw2, lane, vp_r, H + cw);
   fence_sched();
@@ -816,8 +845,10 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
     }
     store16<H>(scr, lane, gx1v, gx1_r, cw);
   }
-  finish16(scr, lane, lgv, pgv);
-  finish16(scr, lane, lq3, pq3);
+  if constexpr (!NOGV) {
+    finish16(scr, lane, lgv, pgv);
+    finish16(scr, lane, lq3, pq3);
+  }
   finish16(scr, lane, lw1, pw1);
   finish16(scr, lane, lw2, pw2);
   // ---- gvec1[d] = gv[d] + (gv1[d] | gv2[d]) Wv,  gv1 = gv q3 + s v2,  gv2 = s v1 + gnn v2  (the accumulator starts at gv[d])
@@ -828,15 +859,20 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       const int c0 = cw + 16 * s + ch;
-      const f32x4 gv = pgv[s] * onr;
-      accg[s] = gv;
-      *reinterpret_cast<f32x4*>(buf0 + mrow * LD + c0) = gv * pq3[s] + s_[s] * pw2[s];
+      if constexpr (NOGV) {
+        accg[s] = zero4();
+        *reinterpret_cast<f32x4*>(buf0 + mrow * LD + c0) = s_[s] * pw2[s];
+      } else {
+        const f32x4 gv = pgv[s] * onr;
+        accg[s] = gv;
+        *reinterpret_cast<f32x4*>(buf0 + mrow * LD + c0) = gv * pq3[s] + s_[s] * pw2[s];
+      }
       *reinterpret_cast<f32x4*>(buf1 + mrow * LD + c0) = s_[s] * pw1[s] + gnn[s] * pw2[s];
     }
     fence_sched();
     Load16 ngv, nw1, nw2;
     if (d < 2) {                                     // in flight during the product below
-      issue16<3 * H>(ngv, lane, gvo_r, (d + 1) * H + cw);
+      if constexpr (!NOGV) issue16<3 * H>(ngv, lane, gvo_r, (d + 1) * H + cw);
       issue16<6 * H>(nw1, lane, vp_r, (d + 1) * 2 * H + cw);
       issue16<6 * H>(nw2, lane, vp_r, (d + 1) * 2 * H + H + cw);
     }
@@ -848,7 +884,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
     if (d < 2) b16_preload(rg, bpg);
     fence_sched();
     if (d < 2) {
-      finish16(scr, lane, ngv, pgv);
+      if constexpr (!NOGV) finish16(scr, lane, ngv, pgv);
       finish16(scr, lane, nw1, pw1);
       finish16(scr, lane, nw2, pw2);
     }
@@ -970,7 +1006,10 @@ constexpr size_t kLdsFwdFused16 = (size_t)(3 * 16 * 136 + 4 * kScr16Floats) * 4;
 constexpr size_t kLdsBwdFused16 = (size_t)(pre_bwd16_tile_floats(128) + 16 * 136 + 4 * kScr16Floats) * 4;
 
 int launch_fwd16(bool fuse, int tiles, size_t lds_bytes, void* stream, const UpdFwdArgs& a, const PreFwdArgs& p) {
-  if (fuse) hipLaunchKernelGGL((node_update_fwd16_kernel<128, true>), dim3((unsigned)tiles), dim3(256), lds_bytes, (hipStream_t)stream, a, p);
+  if (a.vec_out == nullptr) {                     // the last layer's form (see the kernel: NOVEC)
+    if (fuse) return HN_ERR_BAD_ARG;
+    hipLaunchKernelGGL((node_update_fwd16_kernel<128, false, true>), dim3((unsigned)tiles), dim3(256), lds_bytes, (hipStream_t)stream, a, p);
+  } else if (fuse) hipLaunchKernelGGL((node_update_fwd16_kernel<128, true>), dim3((unsigned)tiles), dim3(256), lds_bytes, (hipStream_t)stream, a, p);
   else hipLaunchKernelGGL((node_update_fwd16_kernel<128, false>), dim3((unsigned)tiles), dim3(256), lds_bytes, (hipStream_t)stream, a, p);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }
@@ -989,6 +1028,10 @@ int hn_update16_pre_fwd(int hidden, const UpdFwdArgs& a, const PreFwdArgs& p, in
 
 int hn_update16_bwd(int hidden, const UpdBwdArgs& a, int tiles, void* stream) {
   if (hidden != 128) return HN_ERR_BAD_ARG;
+  if (a.gvo == nullptr) {                         // the last layer's form (see the kernel: NOGV); nothing is ever pending above it
+    if (a.pend.gxh != nullptr || a.pend.gn != nullptr) return HN_ERR_BAD_ARG;
+    return launch_chain(node_update_bwd16_kernel<128, false, true>, dim3((unsigned)tiles), kLdsUpd16, stream, a);
+  }
   if (a.pend.gxh != nullptr)
     return launch_chain(node_update_bwd16_kernel<128, true>, dim3((unsigned)tiles), kLdsBwdFused16, stream, a);
   return launch_chain(node_update_bwd16_kernel<128, false>, dim3((unsigned)tiles), kLdsUpd16, stream, a);

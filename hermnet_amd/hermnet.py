@@ -89,7 +89,9 @@ class HeteroVertexConv(nn.Module):
                 pre = None
             # the next layer's weights: its projection of the rows this layer produces can run inside this layer's update launch
             w_next = ready[li + 1] if (ready is not None and li + 1 < len(ready) and whole) else None
-            route = Route(defer=straight and whole, pre=None if pre is None else pre[1], w_next=w_next)
+            # (HVNet.forward: this is the last layer and the read-out takes its x only)
+            last, data._hn_last = bool(data.get("_hn_last")) and not g.num_src and w_next is None, None
+            route = Route(defer=straight and whole, pre=None if pre is None else pre[1], w_next=w_next, last=last)
         data.x, data.vec = FusedRelationalLayer.apply(data.x, data.vec, edge, g, data._hn_rbf, w, step, route)
         data._hn_chain_node = None if g.num_src else data.x.grad_fn
         return data
@@ -413,6 +415,13 @@ class HVNet(nn.Module):
             data._hn_edge_handles = EdgeFanout.apply(edge, step.edge_sink)
         for li, conv in enumerate(self.hermconvs):
             step.layer = li
+            # The read-out takes x only: in an energy / force evaluation (parameters constant, forces the only gradient) the
+            # LAST layer's vec feeds nothing, and its layer may leave it out (layer.Route: `last`; data.vec is None behind it).
+            # A forward hook on the layer is somebody who reads it: the general form.
+            data._hn_last = (li + 1 == len(self.hermconvs) and fused and switches.fused_layer and switches.dead_ends
+                             and type(conv) is HeteroVertexConv        # (HTNet's layer reads both outputs: PairMean)
+                             and edge.requires_grad and not conv._forward_hooks
+                             and not torch.nn.modules.module._global_forward_hooks)
             data = conv(data)
             if row_plan is not None and li + 1 < len(self.hermconvs):
                 # one exchange per layer: (x | vec) rows of halo atoms, 4H floats each -- due before the next layer reads

@@ -14,7 +14,7 @@ device-op path, `HVNet.forward` in train() mode).
 import torch
 
 from . import _lib, nodeops, switches
-from .ops import _launch, _msg_bwd, _msg_fwd
+from .ops import _launch, _msg_bwd, _msg_bwd_gedge, _msg_fwd
 from .sharding import _all_to_all_rows_start, comm_wait
 
 
@@ -218,11 +218,17 @@ class Route(object):
     gradients down as partial sums (`_hand_down`) -- two small launches per layer boundary less, same bits.
     `pre`: the node projection of THIS x, already computed by the fused update launch of the layer below.
     `w_next`: the NEXT layer's weights, where its projection of the rows this layer produces may run inside this layer's
-    update launch; `boundary`: switches.boundary_mode, read once (`_update_fwd`)."""
+    update launch; `boundary`: switches.boundary_mode, read once (`_update_fwd`).
+    `last`: the caller reads x_out only (HVNet's last layer in front of the read-out, energy / force evaluation): the layer
+    returns (x_out, None) and its update launches leave out everything that only vec_out and its zero gradient need, where
+    `nodeops.last_update_supported`; `first`: the first layer's message backward may skip the source rows' sums
+    (switches.dead_ends, read once)."""
 
-    def __init__(self, exchange=None, halo=None, defer=False, pre=None, w_next=None):
+    def __init__(self, exchange=None, halo=None, defer=False, pre=None, w_next=None, last=False):
         self.exchange, self.halo, self.defer, self.pre, self.w_next = exchange, halo, defer, pre, w_next
         self.boundary = int(switches.boundary_mode)
+        self.first = bool(switches.dead_ends)
+        self.last = bool(last and switches.dead_ends and exchange is None and w_next is None)
 
 
 def _local_fwd(x, vec, edge, graph, rbf, w, route):
@@ -351,7 +357,10 @@ def _local_bwd(ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge):
             gn_parts, chain = _pre_bwd_parts(ctx, gxh, hb, x, mean, rstd)
             return _hand_down(ctx.step, ctx.li, x, vec, gn_parts, gv_parts, mean, rstd, gx1, gvec1, w, chain)
         if vec is None and not ctx.needs_input_grad[0]:     # the first layer: nothing below wants gx / gvec
-            _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, finish=False)
+            if ctx.route.first and x.is_cuda:               # ... nor the sums they would be formed from: gedge only
+                _msg_bwd_gedge(graph, rbf, H, xh, w, edge, gx1, gvec1, gedge)
+            else:
+                _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False, finish=False)
             return None, None
     gxh, gvec_in, gx_in = _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=False)
     _virtual_residual(graph, gx1, gvec1, gx_in, gvec_in, H)
@@ -426,7 +435,14 @@ class FusedRelationalLayer(torch.autograd.Function):
         ctx.exchange = "rows" if (route.exchange == "proj" and not _bwd_sums_deferrable(graph, x.size(1))
                                   and (ctx.needs_input_grad[0] or ctx.needs_input_grad[2])) else route.exchange
         (hb, xh, mean, rstd), x1, vec1 = _ROUTES[ctx.exchange][0](x, vec, edge, graph, rbf, w, route)
-        x_out, vec_out, vp, h2b, q23, nrm = _update_fwd(x1, vec1, graph, w, step, step.layer, route)
+        # (the last layer in front of a read-out of x: no vec output, and no zero gradient for it on the way back)
+        # (the short forms are kernels of the device library only)
+        ctx.short = route.last and x.is_cuda and ctx.exchange is None and nodeops.last_update_supported(graph, x.size(1), w)
+        if ctx.short:
+            x_out, vp, h2b, q23, nrm = nodeops.node_update_fwd_last(x1, vec1, w, graph)
+            vec_out = None
+        else:
+            x_out, vec_out, vp, h2b, q23, nrm = _update_fwd(x1, vec1, graph, w, step, step.layer, route)
         ctx.save_for_backward(x, mean, rstd, hb, xh, vec, edge, vp, h2b, q23, nrm)
         ctx.graph, ctx.rbf, ctx.w, ctx.step, ctx.li, ctx.route = graph, rbf, w, step, step.layer, route
         return x_out, vec_out
@@ -434,6 +450,13 @@ class FusedRelationalLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gxo, gvo):
         x, mean, rstd, hb, xh, vec, edge, vp, h2b, q23, nrm = ctx.saved_tensors
+        if ctx.short:
+            if ctx.step.pending.pop(ctx.li, None) is not None:
+                raise RuntimeError("hermnet_amd: gradients handed down to the last layer")
+            gx1, gvec1 = nodeops.node_update_bwd_last(gxo.contiguous(), vp, h2b, q23, nrm, ctx.w, ctx.graph)
+            gedge = _edge_grad_slot(edge, ctx.graph, ctx.step, ctx.li, x.size(1), gx1.device)
+            gx, gvec = _ROUTES[ctx.exchange][1](ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge)
+            return (gx, gvec, _edge_grad(edge, gedge)) + (None,) * 5
         gxo, gvo = gxo.contiguous(), gvo.contiguous()
         # (the layer above may have left its finishing launches to this one: the buffers arrive unfilled -- and they must be
         # the very buffers it registered: a copy made on the way would hold garbage, so that is refused loudly)

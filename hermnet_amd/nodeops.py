@@ -358,6 +358,41 @@ def node_update_fwd(x1, vec1, w, graph):
     return xo, vo, vp, h2b, q23, nrm
 
 
+def last_update_supported(graph, H, w):
+    """The update launches of the LAST layer without its vec output (csrc/node_chain16.hip: NOVEC / NOGV): width 128 on
+    16-row update tiles."""
+    return H == 128 and getattr(w, "wvf16", None) is not None and update_tile_rows(graph, H) == 16
+
+
+def node_update_fwd_last(x1, vec1, w, graph):
+    """node_update_fwd where nothing reads vec_out (the last layer in front of the read-out) -> (x_out, vp, h2b, q23, nrm);
+    of q23 [N,2H] only the q half is written."""
+    N, H = x1.shape
+    dev, dt = x1.device, x1.dtype
+    vp = torch.empty(N, 3, 2 * H, dtype=dt, device=dev)
+    h2b = torch.empty(N, H, dtype=dt, device=dev)
+    q23 = torch.empty(N, 2 * H, dtype=dt, device=dev)
+    nrm = torch.empty(N, H, dtype=dt, device=dev)
+    xo = torch.empty(N, H, dtype=dt, device=dev)
+    _lib.check(_launch("node_update_fwd", lambda: _lib.load().hermnet_node_update_fwd_last(
+        P(x1), P(vec1), P(w.wvf16), P(w.wx0f16), P(w.bx0_s), P(w.wx2f16), P(w.bx2_s), P(graph.row_active), P(graph.type_rowptr),
+        _rowptr_host(graph), P(vp), P(h2b), P(q23), P(nrm), P(xo), N, graph.T, H, _stream())),
+        "hermnet_node_update_fwd_last")
+    return xo, vp, h2b, q23, nrm
+
+
+def node_update_bwd_last(gxo, vp, h2b, q23, nrm, w, graph):
+    """node_update_bwd for gvec_out = 0 (the saved tensors of node_update_fwd_last) -> (gx1, gvec1)."""
+    N, H = gxo.shape
+    gx1 = torch.empty_like(gxo)
+    gvec1 = torch.empty(N, 3, H, dtype=gxo.dtype, device=gxo.device)
+    _lib.check(_launch("node_update_bwd", lambda: _lib.load().hermnet_node_update_bwd_last(
+        P(gxo), P(vp), P(h2b), P(q23), P(nrm), P(w.wx2tf16), P(w.wx0tf16), P(w.wvtf16), P(graph.row_active),
+        P(graph.type_rowptr), _rowptr_host(graph), P(gx1), P(gvec1), N, graph.T, H, None, _stream())),
+        "hermnet_node_update_bwd_last")
+    return gx1, gvec1
+
+
 class PendingGrads(object):
     """The gradients a layer's backward hands DOWN while they still sit in partial sums (hn_pending_grads): `gx` / `gvec`
     are the buffers the consumer -- the update backward of the layer below -- fills before it reads them.

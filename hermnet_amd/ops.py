@@ -287,6 +287,18 @@ def _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=True, r
     return gxh, gvec, gx
 
 
+def _msg_bwd_gedge(graph, rbf, H, xh, w, edge, gx1, gvec1, gedge):
+    """The message backward of a FIRST layer whose inputs carry no gradient (no vec rows; `_bwd_sums_deferrable`): only
+    `gedge` is written -- no source-row sums, no gxh buffer."""
+    lib = _lib.load()
+    gs, rs = graph.as_struct(), rbf.struct()
+    _lib.check(_launch("message_scatter_bwd_l0",
+                       lambda: lib.hermnet_message_scatter_bwd_gedge(
+                           ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(w.wt), P(w.brbf), P(edge),
+                           P(gx1), P(gvec1), P(gedge), P(graph.edge_table), _stream())),
+               "hermnet_message_scatter_bwd_gedge")
+
+
 class MessageScatter(torch.autograd.Function):
     """rbf_proj + propagate + residual of one HeteroVertexConv layer, all relations
     (rmnet.py:24-26, 55-73; utils.py:11-24).  Returns (x1, vec1).

@@ -20,6 +20,7 @@ fused_layer = True          # False: the layer's node algebra through PyTorch au
 node_chain = True           # False: library GEMMs + stage kernels instead of the node chain kernels (the path of widths > 512)
 boundary_mode = 0           # layer.FusedRelationalLayer: 0 every phase a launch of its own; 4 / 1 / 3 / 2: the fused 16-row forms
 native_relations = True     # False: the relation build as torch ops (its definition: relations.py) instead of the HIP kernels
+dead_ends = True            # False: the general kernel forms at both ends of the layer stack too (layer.Route: `first`, `last`)
 train_row_sums = True       # False: train(): per-edge message kernels + segmented sums instead of row sums inside the kernels
 
 

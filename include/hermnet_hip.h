@@ -17,7 +17,8 @@
  *     the caller's edge_index / atomic_number / halo index lists arrive as torch LongTensors).
  *
  * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
- * hermnet_neighbor_count_devcell were added within v13 (new entry points only, nothing
+ * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
+ * forms without dead work at the two ends of the layer stack) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -335,6 +336,17 @@ int hermnet_message_scatter_bwd(const hn_graph* g, const hn_rbf_desc* rbf, int h
                                 const float* edge_table, float* gvec_partials,
                                 const int* source_ranges, const int* source_ranges_host, int num_ranges, void* stream);
 
+/* hermnet_message_scatter_bwd for the FIRST layer of an energy / force evaluation (ABI 13, additive): its x is the species
+ * embedding, which does not depend on the positions, and it has no vec rows, so gedge is the only result anybody reads.
+ * Channel-per-lane form without the source rows' sums: no gxh, no gx, no finishing launch; gedge is bit for bit what
+ * hermnet_message_scatter_bwd writes for vec = NULL.  HVNet rows only (num_src = 0, res_row = NULL), edge_table required;
+ * xh includes x_proj's bias (the chain kernels' form).  There is no vec argument: rows with a vec part hand gradients
+ * down and take hermnet_message_scatter_bwd, which refuses a NULL gxh. */
+int hermnet_message_scatter_bwd_gedge(const hn_graph* g, const hn_rbf_desc* rbf, int hidden,
+                                      const float* xh, const float* wt, const float* brbf, const float* edge,
+                                      const float* gx1, const float* gvec1, float* gedge,
+                                      const float* edge_table, void* stream);
+
 /* Per-edge radial record, computed ONCE per step (geometry and radial basis are shared by every layer):
  * table [E + 1, 32] floats in CSC order -- record q belongs to CSC edge q, i.e. CSR edge csc_pos[q]; `edge` stays in
  * CSR order; record E repeats record E-1, the kernel requests one record ahead without a bounds check --, so the
@@ -542,6 +554,25 @@ int hermnet_node_update_bwd(const float* gx_out, const float* gvec_out, const fl
                             const float* row_active, const int* type_rowptr, const int* type_rowptr_host, float* gx1,
                             float* gvec1, int num_nodes, int num_rel, int hidden, int tile_rows,
                             const hn_pending_grads* pending, void* stream);
+
+/* The LAST layer of an energy / force evaluation (ABI 13, additive; hidden 128, 16-row tiles, frag16 weights): the read-out
+ * takes x only, so vec_out feeds nothing and its gradient is identically zero.
+ * hermnet_node_update_fwd_last: hermnet_node_update_fwd (16-row form) without vec_out -- the r third of the last product and
+ *   dvec = r v1 are not computed; x_out, vp, h2b, nrm and the q half of q23 [N, 2H] are bit for bit the general form's, the r
+ *   half of q23 is left unwritten.
+ * hermnet_node_update_bwd_last: hermnet_node_update_bwd (16-row form) for gvec_out = 0, which is not passed; reads the q half
+ *   of q23 only.  gx1, gvec1: bit for bit the general form's results for an all-zero gvec_out, given finite saved tensors
+ *   and no partial sum that underflows to -0 (products below ~1e-45): there the two forms may differ in the SIGN of a zero.
+ *   `pending` must be NULL (no layer above the last one hands anything down): HN_ERR_BAD_ARG otherwise. */
+int hermnet_node_update_fwd_last(const float* x1, const float* vec1, const float* wv_frag16, const float* wx0_frag16,
+                                 const float* bx0, const float* wx2_frag16, const float* bx2, const float* row_active,
+                                 const int* type_rowptr, const int* type_rowptr_host, float* vp, float* h2b, float* q23,
+                                 float* nrm, float* x_out, int num_nodes, int num_rel, int hidden, void* stream);
+int hermnet_node_update_bwd_last(const float* gx_out, const float* vp, const float* h2b, const float* q23,
+                                 const float* nrm, const float* wx2t_frag16, const float* wx0t_frag16,
+                                 const float* wvt_frag16, const float* row_active, const int* type_rowptr,
+                                 const int* type_rowptr_host, float* gx1, float* gvec1, int num_nodes, int num_rel,
+                                 int hidden, const hn_pending_grads* pending, void* stream);
 
 /* ---- ABI v9: one node launch per layer boundary, each way (csrc/node_chain16.hip; hidden 128, 16-row tiles).
  * A tile's PaiNNUpdate of layer l (rmnet.py:94-107, 29-31) and the node projection of layer l + 1 on the rows it has just
