@@ -4,6 +4,7 @@ from .data import Data, neighbor_search, transform  # noqa: F401
 from .hermnet import HVNet, HeteroVertexConv, HTNet, HeteroTriadicConv  # noqa: F401
 from .atomic import atom_properties  # noqa: F401
 from .stress import energy_forces_stress  # noqa: F401
+from .graph import GraphedStep, GraphedMDStep, GraphedBatchMDStep  # noqa: F401
 from .rmnet import PaiNNModule, PaiNNMessage, PaiNNUpdate, ScaledSiLU, RadialBasis  # noqa: F401
 
 __version__ = "0.1.0"

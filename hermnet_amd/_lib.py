@@ -78,6 +78,13 @@ SIGNATURES = {
                                              c_fp, c_fp, c_fp, c_fp, c_fp]),
     "hermnet_neighbor_fill_padded": (ctypes.c_int, [ctypes.c_int, c_fp, ctypes.c_size_t, ctypes.c_long, ctypes.c_float,
                                                     ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
+    "hermnet_neighbor_batch_workspace": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "hermnet_neighbor_batch_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_double, c_fp,
+                                                    ctypes.c_size_t, c_fp, c_fp]),
+    "hermnet_neighbor_batch_fill": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_size_t, ctypes.c_long,
+                                                   ctypes.c_float, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
+    "hermnet_neighbor_batch_fill_padded": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_size_t, ctypes.c_long,
+                                                          ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
     "hermnet_relation_counts": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp]),
     "hermnet_build_relations_workspace": (ctypes.c_size_t, [ctypes.c_int] * 4),
     "hermnet_build_relations": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int,

@@ -54,17 +54,29 @@ __device__ __forceinline__ void cart_of(const NbrGeom& g, const double* f, doubl
 // The geometry reaches a kernel by value (G = NbrGeom: made on the host from a host copy of the cell) or through a pointer
 // (G = const NbrGeom*: made on the device by nbr_geom_kernel from the cell in device memory, so that a captured search
 // follows a cell that changes between replays).
-__device__ __forceinline__ const NbrGeom& geom_of(const NbrGeom& g) { return g; }
-__device__ __forceinline__ const NbrGeom& geom_of(const NbrGeom* g) { return *g; }
+// A batch of structures (G = NbrBatch) has one geometry per structure, made on the device by nbr_batch_geom_kernel:
+// atom i reads the geometry of its structure graph[i] and files its bins behind those of the structures in front of it
+// (bin_base: exclusive scan of the per-structure bin counts), so a wave only ever walks its own structure's grid.
+struct NbrBatch {
+  const NbrGeom* geom;     // [B]
+  const int* graph;        // [N] structure of every atom, inside [0, B)
+  const int* bin_base;     // [B+1]
+};
+__device__ __forceinline__ const NbrGeom& geom_of(const NbrGeom& g, int) { return g; }
+__device__ __forceinline__ const NbrGeom& geom_of(const NbrGeom* g, int) { return *g; }
+__device__ __forceinline__ const NbrGeom& geom_of(const NbrBatch& g, int i) { return g.geom[g.graph[i]]; }
+__device__ __forceinline__ int bin_base_of(const NbrGeom&, int) { return 0; }
+__device__ __forceinline__ int bin_base_of(const NbrGeom*, int) { return 0; }
+__device__ __forceinline__ int bin_base_of(const NbrBatch& g, int i) { return g.bin_base[g.graph[i]]; }
 
 // wrapped fractional coordinate, integer wrap, bin id
 template <class G>
 __global__ __launch_bounds__(kBlock) void nbr_bin_kernel(const float* __restrict__ pos, int N, G geom,
                                                         double* __restrict__ fw, int* __restrict__ wrap,
                                                         unsigned* __restrict__ bin) {
-  const NbrGeom& g = geom_of(geom);
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
+  const NbrGeom& g = geom_of(geom, i);
   const double p[3] = {(double)pos[3 * i], (double)pos[3 * i + 1], (double)pos[3 * i + 2]};
   double f[3];
   int b[3];
@@ -86,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void nbr_bin_kernel(const float* __restrict
     }
   }
   fw[3 * i] = f[0]; fw[3 * i + 1] = f[1]; fw[3 * i + 2] = f[2];
-  bin[i] = (unsigned)((b[0] * g.nbins[1] + b[1]) * g.nbins[2] + b[2]);
+  bin[i] = (unsigned)(bin_base_of(geom, i) + (b[0] * g.nbins[1] + b[1]) * g.nbins[2] + b[2]);
 }
 
 // Atoms grouped by bin with a counting sort (histogram -> exclusive scan = bin_start -> scatter through per-bin cursors).
@@ -123,9 +135,10 @@ __global__ __launch_bounds__(kBlock) void nbr_pairs_kernel(const double* __restr
                                                           int stash) {
   // one WAVE per atom: the lanes share the candidates of a bin (one atom per thread left the chip at 40 workgroups
   // for 10k atoms, each thread walking ~200 candidates serially: 0.2 ms per pass)
-  const NbrGeom& g = geom_of(geom);
   const int i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (i >= N) return;
+  const NbrGeom& g = geom_of(geom, i);
+  const int bin0 = bin_base_of(geom, i);
   const int lane = threadIdx.x & 63;
   // `target_ok` (atom-sharded lists, sharding.py): only pairs whose TARGET atom is flagged are listed -- the target is j
   // in the periodic convention ([i; j]), i in the open-system one ([j; i])
@@ -163,7 +176,7 @@ __global__ __launch_bounds__(kBlock) void nbr_pairs_kernel(const double* __restr
           }
         }
         if (!ok) continue;
-        const int b = (tb[0] * g.nbins[1] + tb[1]) * g.nbins[2] + tb[2];
+        const int b = bin0 + (tb[0] * g.nbins[1] + tb[1]) * g.nbins[2] + tb[2];
         const int s_end = bin_start[b + 1];
         for (int s0 = bin_start[b]; s0 < s_end; s0 += 64) {      // (wave-uniform loop: ballots are well defined)
           const int s = s0 + lane;
@@ -357,6 +370,151 @@ __global__ void nbr_geom_kernel(const float* __restrict__ cell, double rc, int N
     }
   }
   *out = g;
+}
+
+// ---- a batch of structures: everything about them is found on the device ----------------------------------------------
+// Atom ranges ptr[B+1] of the structures from the non-decreasing `batch` (thread i looks at the boundary in front of atom
+// i and writes the first atom of every structure that begins there, empty ones included) and the structure of every atom
+// as an int inside [0, B).  A value outside [0, B) or a decrease raises flag bit 4: the ranges then mean nothing (`ptr` was
+// zeroed, so they stay inside [0, N]) and nbr_batch_geom_kernel gives every structure a geometry on which no atom looks at
+// any bin.
+__global__ __launch_bounds__(kBlock) void nbr_batch_ptr_kernel(const long* __restrict__ batch, int N, int B,
+                                                              int* __restrict__ graph, int* __restrict__ ptr,
+                                                              int* __restrict__ overflow) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i > N) return;
+  const long hi = (long)B - 1;
+  const long prev = i == 0 ? -1 : batch[i - 1], cur = i == N ? (long)B : batch[i];
+  const long pc = i == 0 ? -1 : (prev < 0 ? 0 : (prev > hi ? hi : prev));
+  const long cc = i == N ? (long)B : (cur < 0 ? 0 : (cur > hi ? hi : cur));
+  if (i < N) {
+    graph[i] = (int)cc;
+    if (cur < 0 || cur > hi || (i > 0 && cur < prev)) atomicOr(overflow, 16);
+  }
+  for (long b = pc + 1; b <= cc; ++b) ptr[b] = i;
+}
+
+// nbr_geom_kernel's arithmetic for one structure of a batch, statement for statement (the single search's kernel keeps its
+// own text, and with it its instructions): true = a usable geometry in `g`, false = a degenerate cell, `g` half written.
+__device__ __forceinline__ bool nbr_periodic_geom(const float* __restrict__ cell, double rc, int N, NbrGeom& g) {
+#pragma clang fp contract(off)
+  g.rc2 = rc * rc;
+  g.periodic = 1;
+  double c[9];
+  for (int k = 0; k < 9; ++k) { c[k] = (double)cell[k]; g.cell[k] = c[k]; }
+  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+  if (!(fabs(det) >= 1e-12) || !(fabs(det) <= 1.0e300)) return false;    // (also NaN / Inf, which the host never sees)
+  g.inv[0] = (c[4] * c[8] - c[5] * c[7]) / det; g.inv[1] = (c[2] * c[7] - c[1] * c[8]) / det; g.inv[2] = (c[1] * c[5] - c[2] * c[4]) / det;
+  g.inv[3] = (c[5] * c[6] - c[3] * c[8]) / det; g.inv[4] = (c[0] * c[8] - c[2] * c[6]) / det; g.inv[5] = (c[2] * c[3] - c[0] * c[5]) / det;
+  g.inv[6] = (c[3] * c[7] - c[4] * c[6]) / det; g.inv[7] = (c[1] * c[6] - c[0] * c[7]) / det; g.inv[8] = (c[0] * c[4] - c[1] * c[3]) / det;
+  for (int k = 0; k < 3; ++k) {
+    const double h = 1.0 / sqrt(g.inv[k] * g.inv[k] + g.inv[3 + k] * g.inv[3 + k] + g.inv[6 + k] * g.inv[6 + k]);
+    if (!(h > 0.0) || !(h <= 1.0e300)) return false;
+    const double q = floor(h / rc);
+    int nb = q > 1024.0 ? 1024 : (int)q;
+    if (nb < 1) nb = 1;
+    g.nbins[k] = nb;
+    const double r = ceil(rc / (h / nb) - 1e-12);
+    int reach = r > (double)(kMaxImg + 1) ? kMaxImg + 1 : (int)r;
+    if (reach < 1) reach = 1;
+    if (reach > kMaxImg) return false;
+    g.reach[k] = reach;
+    g.lo[k] = 0.0;
+  }
+  long nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
+  while (nbins > 8l * N + 64) {   // must mirror hermnet_neighbor_count and nbr_geom_kernel
+    int kmax = 0;
+    for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
+    if (g.nbins[kmax] <= 1) break;
+    g.nbins[kmax] = (g.nbins[kmax] + 1) / 2;
+    nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
+  }
+  return true;
+}
+
+// `make_geom`'s open branch + the coarsening loop of hermnet_neighbor_count for one device thread, from the float32
+// bounding box of the structure (what the host form is handed): float64, no fused multiply-adds, like the periodic one.
+__device__ __forceinline__ bool nbr_open_geom(const float* __restrict__ lo, const float* __restrict__ hi, double rc, int N,
+                                              NbrGeom& g) {
+#pragma clang fp contract(off)
+  g.rc2 = rc * rc;
+  g.periodic = 0;
+  for (int k = 0; k < 9; ++k) { g.cell[k] = (k % 4 == 0) ? 1.0 : 0.0; g.inv[k] = 0.0; }
+  for (int k = 0; k < 3; ++k) {
+    const double span = (double)hi[k] - (double)lo[k] + 2e-6;
+    if (!(span > 0.0) || !(span <= 1.0e300)) return false;               // (NaN / Inf coordinates)
+    const double q = floor(span / rc);
+    int nb = q > 1024.0 ? 1024 : (int)q;
+    if (nb < 1) nb = 1;
+    g.nbins[k] = nb;
+    g.lo[k] = (double)lo[k] - 1e-6;
+    g.inv[4 * k] = nb / span;                                            // 1 / bin width (>= rc wide)
+    g.reach[k] = 1;
+  }
+  long nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
+  while (nbins > 8l * N + 64) {   // must mirror hermnet_neighbor_count
+    int kmax = 0;
+    for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
+    if (g.nbins[kmax] <= 1) break;
+    const int nb = (g.nbins[kmax] + 1) / 2;
+    g.inv[4 * kmax] *= (double)nb / g.nbins[kmax];
+    g.nbins[kmax] = nb;
+    nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
+  }
+  return true;
+}
+
+// One workgroup per structure: the bounding box of an open structure (min / max are exact in any order), then ONE thread
+// writes its NbrGeom and its bin count (at most 8 N_b + 64, the bound of the single search: the lists are the same bit for
+// bit).  A degenerate cell raises flag bit 3 for that structure alone.  It, an empty structure and every structure of a
+// batch with flag bit 4 get a geometry of reach -1: an atom of such a structure visits no bin and lists no pair.
+__global__ __launch_bounds__(kBlock) void nbr_batch_geom_kernel(const float* __restrict__ pos, const int* __restrict__ ptr,
+                                                               const float* __restrict__ cells, double rc, int B,
+                                                               NbrGeom* __restrict__ geom, int* __restrict__ nbin_count,
+                                                               int* __restrict__ overflow) {
+  __shared__ float red[6][kBlock];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int n0 = ptr[b], n1 = ptr[b + 1];
+  const int nb_atoms = n1 > n0 ? n1 - n0 : 0;
+  if (cells == nullptr) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int a = n0 + t; a < n1; a += kBlock)
+      for (int k = 0; k < 3; ++k) { const float v = pos[3 * a + k]; lo[k] = fminf(lo[k], v); hi[k] = fmaxf(hi[k], v); }
+    for (int k = 0; k < 3; ++k) { red[k][t] = lo[k]; red[3 + k][t] = hi[k]; }
+    __syncthreads();
+    for (int w = kBlock / 2; w > 0; w >>= 1) {
+      if (t < w)
+        for (int k = 0; k < 3; ++k) {
+          red[k][t] = fminf(red[k][t], red[k][t + w]);
+          red[3 + k][t] = fmaxf(red[3 + k][t], red[3 + k][t + w]);
+        }
+      __syncthreads();
+    }
+  }
+  if (t != 0) return;
+  NbrGeom g;
+  bool ok = nb_atoms > 0 && (atomicOr(overflow, 0) & 16) == 0;
+  if (ok) {
+    if (cells != nullptr) {
+      ok = nbr_periodic_geom(cells + 9 * (long)b, rc, nb_atoms, g);
+    } else {
+      const float lo[3] = {red[0][0], red[1][0], red[2][0]}, hi[3] = {red[3][0], red[4][0], red[5][0]};
+      ok = nbr_open_geom(lo, hi, rc, nb_atoms, g);
+    }
+    if (!ok) atomicOr(overflow, 8);
+  }
+  if (!ok) {
+    g.periodic = cells != nullptr;
+    for (int k = 0; k < 9; ++k) { g.cell[k] = 0.0; g.inv[k] = 0.0; }
+    for (int k = 0; k < 3; ++k) { g.nbins[k] = 1; g.reach[k] = -1; g.lo[k] = 0.0; }
+    g.rc2 = -1.0;
+  }
+  geom[b] = g;
+  nbin_count[b] = g.nbins[0] * g.nbins[1] * g.nbins[2];
+  if (b == 0) nbin_count[B] = 0;
+}
+__global__ void nbr_zero_total_kernel(long* __restrict__ total) {
+  if (threadIdx.x < 2) total[threadIdx.x] = 0;
 }
 
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -605,5 +763,144 @@ extern "C" int hermnet_neighbor_fill(const float* pos, int num_atoms, const doub
   hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s,
                      stash_ok ? w.stash : keys, stash_ok ? stash : 0, w.count, w.offset, N, num_edges, shift_sign,
                      source_first, edge_index, edge_shift);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+// ---- the search of a batch of structures (`batch` [N] int64 non-decreasing, `cells` [B,9] float32 in device memory or
+// NULL for open structures): the pipeline above with one geometry per structure, all of them made on the device.  The
+// workspace is the single search's for 8 N + 64 B bins, with the per-structure arrays behind it.
+namespace {
+
+struct NbrBatchWork {
+  NbrWork w;
+  int* graph; int* ptr; int* nbin_count; int* bin_base; NbrGeom* geom;
+};
+
+long batch_bins(int N, int B) { return 8l * N + 64l * B; }
+
+size_t batch_extra_bytes(int N, int B) {
+  return align256(sizeof(int) * (size_t)(N > 0 ? N : 1)) + 3 * align256(sizeof(int) * ((size_t)B + 1)) +
+         align256(sizeof(NbrGeom) * (size_t)B);
+}
+
+size_t batch_workspace_for(int N, int B, int stash) {
+  const long nbins = batch_bins(N, B);
+  return fixed_bytes(N, nbins, stash) + batch_extra_bytes(N, B) + align256(scan_temp_bytes((int)nbins + 2)) + 512;
+}
+
+bool batch_shape_ok(int N, int B) {
+  if (N < 0 || B <= 0 || batch_bins(N, B) + 2 > 0x7fffffffl) return false;
+  return (double)N * N * 4913.0 < 1.8e19;                    // the keys (i N + j) 17^3 + code(S) stay inside 64 bits
+}
+
+int batch_stash_checked(int N, int B, size_t workspace_bytes) {
+  int lo = 0, hi = kStash;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (batch_workspace_for(N, B, mid) <= workspace_bytes) lo = mid; else hi = mid - 1;
+  }
+  return lo >= 8 ? lo : 0;
+}
+
+void carve_batch(void* workspace, size_t workspace_bytes, int N, int B, int stash, NbrBatchWork& bw) {
+  carve(workspace, N, batch_bins(N, B), stash, bw.w);
+  char* p = reinterpret_cast<char*>(bw.w.temp);
+  auto take = [&](size_t bytes) { void* r = p; p += align256(bytes); return r; };
+  bw.graph = (int*)take(sizeof(int) * (size_t)(N > 0 ? N : 1));
+  bw.ptr = (int*)take(sizeof(int) * ((size_t)B + 1));
+  bw.nbin_count = (int*)take(sizeof(int) * ((size_t)B + 1));
+  bw.bin_base = (int*)take(sizeof(int) * ((size_t)B + 1));
+  bw.geom = (NbrGeom*)take(sizeof(NbrGeom) * (size_t)B);
+  bw.w.temp = p;
+  bw.w.temp_bytes = workspace_bytes - (size_t)(p - (char*)workspace);
+}
+
+}  // namespace
+
+extern "C" size_t hermnet_neighbor_batch_workspace(int num_atoms, int num_graphs, int stash_per_atom) {
+  if (!batch_shape_ok(num_atoms, num_graphs)) return 0;
+  const int st = stash_per_atom < 8 ? 8 : (stash_per_atom > kStash ? kStash : stash_per_atom);
+  return batch_workspace_for(num_atoms, num_graphs, st);
+}
+
+extern "C" int hermnet_neighbor_batch_count(const float* pos, int num_atoms, const long* batch, int num_graphs,
+                                            const float* cells, double rc, void* workspace, size_t workspace_bytes,
+                                            long* total_device, void* stream) {
+  const int N = num_atoms, B = num_graphs;
+  if (!batch_shape_ok(N, B) || !(rc > 0.0) || !workspace || !total_device) return HN_ERR_BAD_ARG;
+  if (N > 0 && (!pos || !batch)) return HN_ERR_BAD_ARG;
+  const int stash = batch_stash_checked(N, B, workspace_bytes);
+  if (stash == 0) return HN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (N == 0) {
+    hipLaunchKernelGGL(nbr_zero_total_kernel, dim3(1), dim3(64), 0, s, total_device);
+    return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  }
+  const long nbins = batch_bins(N, B);
+  NbrBatchWork bw;
+  carve_batch(workspace, workspace_bytes, N, B, stash, bw);
+  NbrWork& w = bw.w;
+  const NbrBatch g = {bw.geom, bw.graph, bw.bin_base};
+  hipLaunchKernelGGL(nbr_clear_kernel, dim3(1), dim3(64), 0, s, w.count + N, w.overflow);
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(B + 1l), dim3(kBlock), 0, s, bw.ptr, B + 1l);
+  hipLaunchKernelGGL(nbr_batch_ptr_kernel, grid_for(N + 1l), dim3(kBlock), 0, s, batch, N, B, bw.graph, bw.ptr, w.overflow);
+  hipLaunchKernelGGL(nbr_batch_geom_kernel, dim3(B), dim3(kBlock), 0, s, pos, bw.ptr, cells, rc, B, bw.geom, bw.nbin_count,
+                     w.overflow);
+  if (exclusive_scan_i32(bw.nbin_count, bw.bin_base, B + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(nbr_bin_kernel<NbrBatch>, grid_for(N), dim3(kBlock), 0, s, pos, N, g, w.fw, w.wrap, w.bin);
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
+  hipLaunchKernelGGL(nbr_bin_hist_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_fill);
+  if (exclusive_scan_i32(w.bin_fill, w.bin_start, (int)nbins + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
+  hipLaunchKernelGGL(nbr_bin_scatter_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_start, w.bin_fill, w.ids_sorted);
+  hipLaunchKernelGGL((nbr_pairs_kernel<0, NbrBatch>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted,
+                     w.bin_start, N, g, (const long*)nullptr, w.count, w.stash, w.overflow, (const unsigned char*)nullptr, 0,
+                     stash);
+  if (exclusive_scan_i32_to_long(w.count, w.offset, N + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(nbr_total_kernel, dim3(1), dim3(64), 0, s, w.offset + N, w.overflow, total_device);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_neighbor_batch_fill(int num_atoms, int num_graphs, void* workspace, size_t workspace_bytes,
+                                           long num_edges, float shift_sign, int source_first, int stash_ok,
+                                           unsigned long long* keys, long* edge_index, float* edge_shift, void* stream) {
+  const int N = num_atoms, B = num_graphs;
+  if (!batch_shape_ok(N, B) || N == 0 || num_edges < 0 || num_edges > 0x7fffffffl || !workspace || !edge_index)
+    return HN_ERR_BAD_ARG;
+  if (num_edges > 0 && !stash_ok && !keys) return HN_ERR_BAD_ARG;
+  const int stash = batch_stash_checked(N, B, workspace_bytes);
+  if (stash == 0) return HN_ERR_BAD_ARG;
+  if (num_edges == 0) return HN_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  NbrBatchWork bw;
+  carve_batch(workspace, workspace_bytes, N, B, stash, bw);
+  NbrWork& w = bw.w;
+  if (!stash_ok) {  // an atom had more pairs than its stash slot: second pass over the candidates into `keys`
+    const NbrBatch g = {bw.geom, bw.graph, bw.bin_base};
+    hipLaunchKernelGGL((nbr_pairs_kernel<1, NbrBatch>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted,
+                       w.bin_start, N, g, w.offset, (int*)nullptr, keys, w.overflow, (const unsigned char*)nullptr, 0, 0);
+  }
+  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s, stash_ok ? w.stash : keys,
+                     stash_ok ? stash : 0, w.count, w.offset, N, num_edges, shift_sign, source_first, edge_index, edge_shift);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_neighbor_batch_fill_padded(int num_atoms, int num_graphs, void* workspace, size_t workspace_bytes,
+                                                  long capacity, float shift_sign, int source_first, long* edge_index,
+                                                  float* edge_shift, long* total_device, void* stream) {
+  const int N = num_atoms, B = num_graphs;
+  if (!batch_shape_ok(N, B) || N == 0 || capacity <= 0 || capacity > 0x7fffffffl || !workspace || !edge_index ||
+      !total_device)
+    return HN_ERR_BAD_ARG;
+  const int stash = batch_stash_checked(N, B, workspace_bytes);
+  if (stash == 0) return HN_ERR_BAD_ARG;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  NbrBatchWork bw;
+  carve_batch(workspace, workspace_bytes, N, B, stash, bw);
+  NbrWork& w = bw.w;
+  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s, w.stash, stash, w.count, w.offset, N,
+                     capacity, shift_sign, source_first, edge_index, edge_shift);
+  hipLaunchKernelGGL(nbr_pad_kernel, grid_for(capacity), dim3(kBlock), 0, s, w.offset, w.overflow, N, capacity, edge_index,
+                     edge_shift, total_device);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }

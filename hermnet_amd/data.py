@@ -84,9 +84,20 @@ class Data(object):
         return "Data(%s)" % ", ".join(parts)
 
 
-def transform(data, rc, reference_compat=False):
-    """`HermNet/data.py:27-35`: attach `edge_index` (and `edge_shift`) for cutoff rc."""
+def transform(data, rc, reference_compat=False, per_graph=False):
+    """`HermNet/data.py:27-35`: attach `edge_index` (and `edge_shift`) for cutoff rc.
+    `per_graph=True` (no reference counterpart): every graph of `data.batch` is searched on its own, with its own cell of
+    `data.cell` [B,3,3] -- the default lists pairs across graphs and uses the first cell, as the reference does."""
     assert data.pos is not None
+    if per_graph and data.get("batch") is not None:
+        cell = data.get("cell")
+        out = neighbor_search(data.pos, rc, cell, reference_compat=reference_compat and cell is not None, batch=data.batch,
+                              num_graphs=None if cell is None else cell.reshape(-1, 3, 3).size(0))
+        if cell is None:
+            data.edge_index = out
+        else:
+            data.edge_index, data.edge_shift = out
+        return data
     if data.get("cell") is None:
         data.edge_index = neighbor_search(data.pos, rc)
     else:

@@ -184,7 +184,7 @@ class GraphedMDStep(object):
             if pos is not None:
                 self.pos.copy_(pos)
             if cell is not None:
-                self.cell.copy_(cell.reshape(3, 3))
+                self.cell.copy_(cell.reshape(self.cell.shape))
         self.graph.replay()
         if self.stress:
             return self.energy, self.forces, self.virial
@@ -227,8 +227,65 @@ class GraphedMDStep(object):
             if pos is not None:
                 self.pos.copy_(pos)
             if cell is not None and self.variable_cell:
-                self.cell.copy_(cell.reshape(3, 3))
+                self.cell.copy_(cell.reshape(self.cell.shape))
         if capacity is None:
             capacity = padded_capacity(max(int(self.total[0]), self.capacity))
         self._capture(int(capacity))
         return self.__call__()
+
+
+class GraphedBatchMDStep(GraphedMDStep):
+    """`GraphedMDStep` for a batch of structures (path-integral beads, replicas, displaced supercells): the batched
+    neighbour search (`neighbor.neighbor_search_padded(..., batch=, num_graphs=)`), the relation build, the forward and the
+    force backward of ALL of them as ONE hipGraph launch.  atomic_number [N], batch [N] int64 non-decreasing, `num_graphs`
+    = B and cell [B,3,3], or None for a batch of open structures (molecules), all on the GPU.
+
+        step = GraphedBatchMDStep(model, z, cells, pos0, batch, B)
+        e, f = step(pos)            # energy [B], forces [N,3]: static outputs, valid until the next call
+        e, f = step(pos, cells)     # periodic batches: the cells are static INPUTS like the coordinates
+
+    The search reads cells, atom ranges and bounding boxes on the device, so nothing inside the capture reads the host and
+    one capture serves NVT and NPT replicas; `stress=True` adds virial [B,3,3].  `fetch()` (its packed copy carries the B
+    energies), `check()`, `recapture()` and `stale()` are the single form's.  Flag bit 3 (`last_flags & 8`) marks a
+    degenerate cell of one replica -- that replica listed no pair, discard the step --, bit 4 a `batch` that decreases."""
+
+    def __init__(self, model, atomic_number, cell, pos, batch, num_graphs, capacity=None, warmup=3, reference_compat=False,
+                 stress=False):
+        from .neighbor import neighbor_search, padded_capacity
+        if not pos.is_cuda:
+            raise RuntimeError("GraphedBatchMDStep needs GPU tensors")
+        if model.training:
+            raise RuntimeError("GraphedBatchMDStep captures the eval() path")
+        self.reference_compat = bool(reference_compat)
+        if cell is None and self.reference_compat:
+            raise NotImplementedError("the reference pipeline's 32-neighbour cap needs the exact list (neighbor_search)")
+        self.model, self.z, self.num_graphs = model, atomic_number, int(num_graphs)
+        self.batch = batch.detach().long().contiguous()
+        self.cell = None if cell is None else cell.detach().float().reshape(self.num_graphs, 3, 3).contiguous().clone()
+        self.stress, self.variable_cell = bool(stress), cell is not None
+        self.virial, self.last_flags = None, 0
+        self.pos = pos.detach().clone().float().requires_grad_(True)      # static input
+        self._warmup = warmup
+        if capacity is None:
+            out = neighbor_search(self.pos.detach(), model.rc, self.cell, reference_compat=self.reference_compat,
+                                  batch=self.batch, num_graphs=self.num_graphs)
+            capacity = padded_capacity(int((out if cell is None else out[0]).size(1)))
+        self._capture(int(capacity))
+
+    def _eager(self):
+        from .data import Data
+        from .neighbor import neighbor_search_padded
+        ei, sh, total = neighbor_search_padded(self.pos.detach(), self.model.rc, self.cell, self.capacity,
+                                               reference_compat=self.reference_compat, batch=self.batch,
+                                               num_graphs=self.num_graphs)
+        d = Data(pos=self.pos, atomic_number=self.z, batch=self.batch, edge_index=ei)
+        if self.cell is not None:
+            d.cell, d.edge_shift = self.cell, sh
+        d._hn_edge_count = total
+        if self.stress:
+            from .stress import energy_forces_virial
+            e, f, w = energy_forces_virial(self.model, d, self.pos)
+            return e, f, total, w
+        e = self.model(d)
+        f = -torch.autograd.grad(e.sum(), self.pos)[0]
+        return e.detach(), f, total

@@ -216,7 +216,137 @@ def _neighbor_search_device(pos, rc, cell, reference_compat, target_mask=None):
     return (edge_index, shift) if periodic else edge_index
 
 
-def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, target_mask=None, device_cell=False):
+def _batch_args(pos, cell, batch, num_graphs):
+    """(float32 pos, int64 batch, float32 [B,9] cells or None, B) of a batched search; `num_graphs` defaults to the number
+    of cells or, for open structures, to one host read of `batch[-1]`."""
+    if batch is None:
+        raise ValueError("num_graphs without batch")
+    p32 = pos.detach().float().contiguous()
+    b64 = batch.detach().long().contiguous()
+    if b64.dim() != 1 or b64.numel() != p32.size(0) or b64.device != p32.device:
+        raise ValueError("batch must be [N] on the device of pos")
+    cells = None
+    if cell is not None:
+        cells = cell.detach().float().reshape(-1, 9).contiguous()
+        if cells.device != p32.device:
+            raise ValueError("cell must be on the device of pos")
+    if num_graphs is None:
+        if cells is not None:
+            num_graphs = cells.size(0)
+        else:
+            num_graphs = int(b64[-1]) + 1 if b64.numel() else 1
+    B = int(num_graphs)
+    if B <= 0 or (cells is not None and cells.size(0) != B):
+        raise ValueError("a batched search takes cell = None or one [3,3] cell per graph ([num_graphs,3,3])")
+    return p32, b64, cells, B
+
+
+def _batch_count(lib, p32, b64, cells, B, rc, total):
+    """The counting pass of a batched search (csrc/neighbor_kernels.hip); returns (workspace, its size)."""
+    import ctypes
+    from . import _lib
+    P = _lib.ptr
+    N = int(p32.size(0))
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ws_bytes = lib.hermnet_neighbor_batch_workspace(N, B, _STASH.get(str(p32.device), _STASH_DEFAULT))
+    if ws_bytes == 0:
+        raise RuntimeError("batched neighbour search: %d atoms in %d graphs are beyond the search's index range" % (N, B))
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p32.device)
+    _lib.check(lib.hermnet_neighbor_batch_count(P(p32), N, P(b64), B, P(cells), float(rc), P(work), ws_bytes, P(total), stream),
+               "hermnet_neighbor_batch_count")
+    return work, ws_bytes
+
+
+def _batch_flags_error(flags):
+    if flags & 16:
+        raise ValueError("batched neighbour search: `batch` must be non-decreasing with values in [0, num_graphs)")
+    if flags & 8:
+        raise RuntimeError("batched neighbour search: a cell of the batch is singular or far smaller than the cutoff")
+
+
+def _neighbor_search_device_batched(pos, rc, cell, batch, num_graphs, reference_compat):
+    """`_neighbor_search_device` for a batch of structures: one pass, one host read of (E, flags)."""
+    import ctypes
+    from . import _lib
+    lib = _lib.load()
+    P = _lib.ptr
+    p32, b64, cells, B = _batch_args(pos, cell, batch, num_graphs)
+    dev, N, periodic = p32.device, int(p32.size(0)), cells is not None
+    if N == 0:
+        ei = torch.empty(2, 0, dtype=torch.long, device=dev)
+        return (ei, torch.empty(0, 3, dtype=torch.float32, device=dev)) if periodic else ei
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    total = torch.zeros(2, dtype=torch.long, device=dev)
+    work, ws_bytes = _batch_count(lib, p32, b64, cells, B, rc, total)
+    E, flags = total.tolist()                                # the one host read of the search
+    _batch_flags_error(flags)
+    if flags & 2:
+        _stash_overflowed(dev)                               # (this search finishes in its two-pass form)
+    if flags & 1:                                            # an image shift beyond +-8 cells: the host path handles it
+        return None
+    edge_index = torch.empty(2, E, dtype=torch.long, device=dev)
+    shift = torch.empty(E, 3, dtype=torch.float32, device=dev) if periodic else None
+    if E > 0:
+        stash_ok = 0 if (flags & 2) else 1
+        keys = None if stash_ok else torch.empty(E, dtype=torch.long, device=dev)
+        _lib.check(lib.hermnet_neighbor_batch_fill(N, B, P(work), ws_bytes, E, 1.0 if reference_compat else -1.0,
+                                                   0 if periodic else 1, stash_ok, P(keys), P(edge_index), P(shift), stream),
+                   "hermnet_neighbor_batch_fill")
+    return (edge_index, shift) if periodic else edge_index
+
+
+def _neighbor_search_padded_batched(pos, rc, cell, capacity, reference_compat, batch, num_graphs):
+    """`neighbor_search_padded` for a batch of structures: nothing about them is read on the host (pass `num_graphs`)."""
+    import ctypes
+    from . import _lib
+    lib = _lib.load()
+    P = _lib.ptr
+    p32, b64, cells, B = _batch_args(pos, cell, batch, num_graphs)
+    dev, N, cap, periodic = p32.device, int(p32.size(0)), int(capacity), cells is not None
+    if N == 0:
+        raise ValueError("a padded batched search needs at least one atom")
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    total = torch.empty(2, dtype=torch.long, device=dev)
+    edge_index = torch.empty(2, cap, dtype=torch.long, device=dev)
+    shift = torch.empty(cap, 3, dtype=torch.float32, device=dev) if periodic else None
+    if switches.debug_poison():
+        edge_index.fill_(0x3f3f3f3f3f3f3f3f)
+        if shift is not None:
+            shift.fill_(float("nan"))
+    work, ws_bytes = _batch_count(lib, p32, b64, cells, B, rc, total)
+    _lib.check(lib.hermnet_neighbor_batch_fill_padded(N, B, P(work), ws_bytes, cap, 1.0 if reference_compat else -1.0,
+                                                      0 if periodic else 1, P(edge_index), P(shift), P(total), stream),
+               "hermnet_neighbor_batch_fill_padded")
+    return edge_index, shift, total
+
+
+def _neighbor_search_host_batched(pos, rc, cell, batch, num_graphs, reference_compat):
+    """The batched search on the host: `neighbor_list` per structure, the atom offsets added."""
+    dev = pos.device
+    p = pos.detach().cpu().numpy()
+    b = batch.detach().cpu().numpy().astype(np.int64)
+    cells = None if cell is None else cell.detach().cpu().numpy().reshape(-1, 3, 3)
+    if num_graphs is None:
+        num_graphs = cells.shape[0] if cells is not None else (int(b[-1]) + 1 if b.size else 1)
+    B = int(num_graphs)
+    if b.shape != (p.shape[0],) or B <= 0 or (cells is not None and cells.shape[0] != B):
+        raise ValueError("a batched search takes batch [N] and cell = None or one [3,3] cell per graph ([num_graphs,3,3])")
+    if b.size and (np.any(np.diff(b) < 0) or b[0] < 0 or b[-1] >= B):
+        raise ValueError("batched neighbour search: `batch` must be non-decreasing with values in [0, num_graphs)")
+    ptr = np.searchsorted(b, np.arange(B + 1))
+    ii, jj, ss = [np.zeros(0, np.int64)], [np.zeros(0, np.int64)], [np.zeros((0, 3), np.int64)]
+    for g in range(B):
+        i, j, s = neighbor_list(p[ptr[g]:ptr[g + 1]], rc, None if cells is None else cells[g])
+        ii.append(i + ptr[g]), jj.append(j + ptr[g]), ss.append(s)
+    i, j, s = np.concatenate(ii), np.concatenate(jj), np.concatenate(ss)
+    if cells is None:
+        return torch.from_numpy(np.vstack([j, i])).long().to(dev)
+    sign = 1.0 if reference_compat else -1.0
+    return (torch.from_numpy(np.vstack([i, j])).long().to(dev), torch.from_numpy(sign * s.astype(np.float32)).float().to(dev))
+
+
+def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, target_mask=None, device_cell=False, batch=None,
+                           num_graphs=None):
     """The device cell list WITHOUT its host read: `capacity` columns are provided up front, the pairs
     found fill the first E of them and the rest become NULL edges (-1, -1; shift 0), which the relation build files behind
     every row -- the model runs on the padded list unchanged, with a launch geometry that does not depend on E.
@@ -231,13 +361,22 @@ def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, targ
     consulted (`_cell_on_host`), so a captured search follows a `cell` tensor that is rewritten between replays
     (graph.GraphedMDStep, `variable_cell`).  `cell` must then be a contiguous float32 [3,3] (or [1,3,3]) GPU tensor; for the
     same values the list is bit for bit the host-cell form's.  A degenerate cell (singular, or far smaller than the
-    cutoff), which the host-cell form refuses with an error, raises flag bit 3 of total[1] instead."""
+    cutoff), which the host-cell form refuses with an error, raises flag bit 3 of total[1] instead.
+    `batch` [N] int64, non-decreasing (with `num_graphs`; without it one host read finds it for open structures): a batch
+    of structures searched in one pass, `cell` = None or [num_graphs,3,3].  Cells, atom ranges and bounding boxes are all
+    read on the device (the cells as with `device_cell=True`), so the call is capturable for periodic and open batches
+    alike; the list is the structures' lists concatenated with their atom offsets.  Flag bit 3 then marks a degenerate cell
+    of one structure (which lists no pair; the others are complete), bit 4 a `batch` that decreases (no pair at all)."""
     import ctypes
     from . import _lib
     if not pos.is_cuda:
         raise RuntimeError("neighbor_search_padded runs on the device list only")
     if cell is None and reference_compat:
         raise NotImplementedError("the reference pipeline's 32-neighbour cap needs the exact list (neighbor_search)")
+    if batch is not None or num_graphs is not None:
+        if target_mask is not None:
+            raise NotImplementedError("target_mask is not part of the batched search")
+        return _neighbor_search_padded_batched(pos, rc, cell, capacity, reference_compat, batch, num_graphs)
     lib = _lib.load()
     P = _lib.ptr
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -312,7 +451,7 @@ def _cap_neighbors(edge_index, cap):
     return edge_index[:, (pos - start) < cap]
 
 
-def neighbor_search(pos, rc, cell=None, reference_compat=False, target_mask=None):
+def neighbor_search(pos, rc, cell=None, reference_compat=False, target_mask=None, batch=None, num_graphs=None):
     """Drop-in for `HermNet/data.py:14-24`.
 
     pos: float Tensor [N,3]; cell: Tensor [3,3] or [1,3,3] or None.
@@ -327,9 +466,24 @@ def neighbor_search(pos, rc, cell=None, reference_compat=False, target_mask=None
 
     `target_mask` [N] bool (no reference counterpart; `sharding.py`): keep only the edges whose target atom
     (`edge_index[1]`) is flagged, same order -- the list of an atom shard, without building the rest.
+
+    `batch` [N] int64, non-decreasing (no reference counterpart): the structures of a batch, each searched on its own in
+    one pass -- `cell` is then None (all open) or [num_graphs,3,3], and no pair crosses structures even where their
+    coordinates overlap.  The result is the structures' lists concatenated, atom offsets added.  `num_graphs` defaults to
+    the number of cells or, for open structures, to a host read of `batch[-1]`.
     """
     if cell is None and reference_compat:
-        return _cap_neighbors(neighbor_search(pos, rc, None, False, target_mask), 32)
+        return _cap_neighbors(neighbor_search(pos, rc, None, False, target_mask, batch, num_graphs), 32)
+    if batch is not None or num_graphs is not None:
+        if target_mask is not None:
+            raise NotImplementedError("target_mask is not part of the batched search")
+        if batch is None:
+            raise ValueError("num_graphs without batch")
+        if pos.is_cuda:
+            out = _neighbor_search_device_batched(pos, rc, cell, batch, num_graphs, reference_compat)
+            if out is not None:
+                return out
+        return _neighbor_search_host_batched(pos, rc, cell, batch, num_graphs, reference_compat)
     if pos.is_cuda:
         out = _neighbor_search_device(pos, rc, cell, reference_compat, target_mask)
         if out is not None:

@@ -18,7 +18,8 @@
  *
  * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
- * forms without dead work at the two ends of the layer stack) were added within v13 (new entry points only, nothing
+ * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
+ * _fill_padded (the search of a batch of structures) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -170,6 +171,34 @@ int hermnet_neighbor_fill(const float* pos, int num_atoms, const double* cell_ho
                           long num_edges, float shift_sign, int source_first, int stash_ok,
                           unsigned long long* keys, const unsigned char* target_ok, long* edge_index,
                           float* edge_shift, void* stream);
+
+/* The search of a BATCH of structures in one pass (ABI 13, additive): `batch` [num_atoms] int64 in device memory, values
+ * in [0, num_graphs), non-decreasing (the atoms of a structure are contiguous; a structure may be empty); `cells`
+ * [num_graphs, 9] float32 in device memory (rows = lattice vectors), or NULL when every structure is open -- a batch is
+ * all periodic or all open.  Nothing about the structures is known on the host: their atom ranges, the bounding boxes of
+ * open structures and one search geometry per structure (the float64 arithmetic of the single search, with its bound of
+ * 8 N_b + 64 bins per structure) are made on the device, every launch is sized by num_atoms and num_graphs alone, and no
+ * pair crosses structures.  The list is the per-structure lists of the single search with the atom offsets added, in
+ * the same canonical order, bit for bit.  Three calls on one workspace, as for one structure:
+ *   _batch_count        -> total_device = (E, flags); flags as above (bit 3: a degenerate cell, raised for that structure
+ *                          alone, which then lists no pair), plus bit 4 (value 16): `batch` decreases or leaves
+ *                          [0, num_graphs) -- no pair is listed at all
+ *   _batch_fill         -> the exact list after a host read of E (stash_ok / keys as for one structure)
+ *   _batch_fill_padded  -> `capacity` columns, NULL edges behind the pairs, total_device rewritten with bit 2
+ * target_ok masks are not part of this form.  HN_ERR_BAD_ARG, before anything is launched: a missing pointer,
+ * num_graphs <= 0, rc <= 0, num_atoms * num_atoms * 4913 beyond 64 bits or 8 num_atoms + 64 num_graphs beyond 31 bits, a
+ * workspace smaller than the query's for (num_atoms, num_graphs, 8); the fills also refuse num_atoms = 0.  The query
+ * returns 0 for a shape the search refuses. */
+size_t hermnet_neighbor_batch_workspace(int num_atoms, int num_graphs, int stash_per_atom);
+int hermnet_neighbor_batch_count(const float* pos, int num_atoms, const long* batch, int num_graphs, const float* cells,
+                                 double rc, void* workspace, size_t workspace_bytes, long* total_device /* [2] */,
+                                 void* stream);
+int hermnet_neighbor_batch_fill(int num_atoms, int num_graphs, void* workspace, size_t workspace_bytes, long num_edges,
+                                float shift_sign, int source_first, int stash_ok, unsigned long long* keys,
+                                long* edge_index, float* edge_shift, void* stream);
+int hermnet_neighbor_batch_fill_padded(int num_atoms, int num_graphs, void* workspace, size_t workspace_bytes,
+                                       long capacity, float shift_sign, int source_first, long* edge_index,
+                                       float* edge_shift, long* total_device /* [2] */, void* stream);
 
 /* ---- A13: in_subgraph (utils.py:11-24) replaced by a one-off device-side build of the relation-ordered
  * graph per neighbour list (three stable radix sorts + binary-searched row pointers, no host sync).
