@@ -170,6 +170,7 @@ SIGNATURES = {
                                                 ctypes.c_long, ctypes.c_float, c_fp]),
     "hermnet_host_rbf_row": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
                                             ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float, c_fp, c_fp]),
+    "hermnet_host_neighbor_geometry": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_double, ctypes.c_int, c_fp, c_fp]),
 }
 
 _lib = None

@@ -38,6 +38,75 @@ struct NbrGeom {
   double rc2;
 };
 
+
+// THE geometry of the cell list: inverse cell, plane spacings, bins at least rc wide, reach, the box of an open structure,
+// and the grid coarsened to at most 8 N + 64 bins.  This one text serves the host (hermnet_neighbor_count / _fill and the
+// probe hermnet_host_neighbor_geometry) and one device thread (nbr_geom_kernel, nbr_batch_geom_kernel, which widen their
+// float32 inputs): float64 without fused multiply-adds on both sides, so every form of the search bins alike and lists
+// alike, bit for bit.  `cell` [9] (rows = lattice vectors), or NULL with the corners lo / hi of an open structure's
+// bounding box.  false = degenerate, `g` half written: a singular cell, one so small that a cutoff sphere reaches beyond
+// kMaxImg bins, a determinant, plane spacing or span that is not finite.  The clamps are taken in double BEFORE the int
+// casts.  (The host once cast first -- undefined for a non-finite cell or box, which it now refuses with
+// HN_ERR_BAD_ARG; for every other input the numbers are what they were.)
+__host__ __device__ inline bool nbr_make_geom(const double* cell, const double* lo, const double* hi, double rc, int N,
+                                              NbrGeom& g) {
+#pragma clang fp contract(off)
+  g.rc2 = rc * rc;
+  g.periodic = cell != nullptr;
+  if (cell) {
+    const double* c = cell;
+    for (int k = 0; k < 9; ++k) g.cell[k] = c[k];
+    const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
+    if (!(fabs(det) >= 1e-12) || !(fabs(det) <= 1.0e300)) return false;      // (also NaN / Inf)
+    g.inv[0] = (c[4] * c[8] - c[5] * c[7]) / det; g.inv[1] = (c[2] * c[7] - c[1] * c[8]) / det; g.inv[2] = (c[1] * c[5] - c[2] * c[4]) / det;
+    g.inv[3] = (c[5] * c[6] - c[3] * c[8]) / det; g.inv[4] = (c[0] * c[8] - c[2] * c[6]) / det; g.inv[5] = (c[2] * c[3] - c[0] * c[5]) / det;
+    g.inv[6] = (c[3] * c[7] - c[4] * c[6]) / det; g.inv[7] = (c[1] * c[6] - c[0] * c[7]) / det; g.inv[8] = (c[0] * c[4] - c[1] * c[3]) / det;
+  } else {
+    for (int k = 0; k < 9; ++k) { g.cell[k] = (k % 4 == 0) ? 1.0 : 0.0; g.inv[k] = 0.0; }
+  }
+  for (int k = 0; k < 3; ++k) {
+    // extent along axis k: the plane spacing 1 / |column k of inv|, or the side of the open box
+    const double h = cell ? 1.0 / sqrt(g.inv[k] * g.inv[k] + g.inv[3 + k] * g.inv[3 + k] + g.inv[6 + k] * g.inv[6 + k])
+                          : hi[k] - lo[k] + 2e-6;
+    if (!(h > 0.0) || !(h <= 1.0e300)) return false;
+    const double q = floor(h / rc);
+    int nb = q > 1024.0 ? 1024 : (int)q;
+    if (nb < 1) nb = 1;
+    g.nbins[k] = nb;
+    if (cell) {
+      const double r = ceil(rc / (h / nb) - 1e-12);
+      int reach = r > (double)(kMaxImg + 1) ? kMaxImg + 1 : (int)r;
+      if (reach < 1) reach = 1;
+      if (reach > kMaxImg) return false;                         // cell far smaller than the cutoff
+      g.reach[k] = reach;
+      g.lo[k] = 0.0;
+    } else {
+      g.lo[k] = lo[k] - 1e-6;
+      g.inv[4 * k] = nb / h;                                     // 1 / bin width (>= rc wide)
+      g.reach[k] = 1;
+    }
+  }
+  // sparse box: coarsen the grid (bins only get wider, still >= rc) until the workspace's 8 N + 64 counters hold it
+  while ((long)g.nbins[0] * g.nbins[1] * g.nbins[2] > 8l * N + 64) {
+    int kmax = 0;
+    for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
+    if (g.nbins[kmax] <= 1) break;
+    const int nb = (g.nbins[kmax] + 1) / 2;
+    if (!g.periodic) g.inv[4 * kmax] *= (double)nb / g.nbins[kmax];
+    g.nbins[kmax] = nb;
+  }
+  return true;
+}
+
+// What a kernel puts in place of a degenerate geometry: zero matrices, one bin, a negative cutoff (no distance is below it:
+// no pair is listed).  On it the following kernels stay inside their arrays; reach -1 visits no bin at all.
+__device__ __forceinline__ void nbr_inert_geom(NbrGeom& g, int periodic, int reach) {
+  g.periodic = periodic;
+  for (int k = 0; k < 9; ++k) { g.cell[k] = 0.0; g.inv[k] = 0.0; }
+  for (int k = 0; k < 3; ++k) { g.nbins[k] = 1; g.reach[k] = reach; g.lo[k] = 0.0; }
+  g.rc2 = -1.0;
+}
+
 __device__ __forceinline__ void frac_of(const NbrGeom& g, const double* p, double* f) {
   // p @ inv  (row vector times matrix)
   f[0] = p[0] * g.inv[0] + p[1] * g.inv[3] + p[2] * g.inv[6];
@@ -219,26 +288,6 @@ __global__ __launch_bounds__(kBlock) void nbr_pairs_kernel(const double* __restr
   }
 }
 
-// sorted keys -> edge_index [2,E] int64 ([i; j]) and shifts [E,3] float32 (sign * S)
-__global__ __launch_bounds__(kBlock) void nbr_decode_kernel(const unsigned long long* __restrict__ keys, long E,
-                                                           int N, float sign, int swap_rows,
-                                                           long* __restrict__ edge_index, float* __restrict__ shift) {
-  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  const unsigned long long key = keys[e];
-  const unsigned long long c3 = (unsigned long long)(kCode * kCode * kCode);
-  const unsigned long long pair = key / c3;
-  const int code = (int)(key - pair * c3);
-  const long i = (long)(pair / (unsigned long long)N), j = (long)(pair - (unsigned long long)i * N);
-  edge_index[e] = swap_rows ? j : i;
-  edge_index[E + e] = swap_rows ? i : j;
-  if (shift != nullptr) {
-    shift[3 * e + 0] = sign * (float)(code / (kCode * kCode) - kMaxImg);
-    shift[3 * e + 1] = sign * (float)((code / kCode) % kCode - kMaxImg);
-    shift[3 * e + 2] = sign * (float)(code % kCode - kMaxImg);
-  }
-}
-
 // One wave per atom: rank sort of its keys (unique, so rank = number of smaller keys) and decode into the caller's
 // arrays at offset[i] + rank.  `stride` = kStash (stashed keys at src[i * kStash]) or 0 (keys at src[offset[i]]).
 // (E = columns of edge_index; in capacity mode the list may hold more pairs than that: positions >= E are dropped and
@@ -317,57 +366,19 @@ __global__ void nbr_total_kernel(const long* __restrict__ offset_end, const int*
   if (threadIdx.x == 0) { total[0] = offset_end[0]; total[1] = (long)overflow[0]; }
 }
 
-// `make_geom` (periodic branch) + the coarsening loop of hermnet_neighbor_count, restated for ONE device thread: the cell
-// is read from device memory (float32 values, widened: the numbers a host copy of the same tensor gives), every step in
-// float64 without fused multiply-adds, so that the geometry -- and with it the list -- is bit for bit the host's.
-// A cell the host refuses (singular, or so small that a cutoff sphere reaches beyond kMaxImg bins) cannot be a return code
-// here: flag bit 3 is raised and the geometry is replaced by an inert one (zero matrices, one bin, reach 1, a negative
-// cutoff), on which the following kernels stay inside their arrays and list no pair; the caller discards such a step.
+// The geometry of a cell in DEVICE memory, by one thread: the float32 values are widened (the numbers a host copy of the same
+// tensor gives) and handed to nbr_make_geom, so the geometry -- and with it the list -- is bit for bit the host form's.
+// A cell the host refuses cannot be a return code here: flag bit 3 is raised and the geometry is an inert one of reach 1,
+// on which no pair is listed; the caller discards such a step.
 __global__ void nbr_geom_kernel(const float* __restrict__ cell, double rc, int N, NbrGeom* __restrict__ out,
                                 int* __restrict__ overflow) {
-#pragma clang fp contract(off)
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  NbrGeom g;
-  g.rc2 = rc * rc;
-  g.periodic = 1;
   double c[9];
-  bool bad = false;
-  for (int k = 0; k < 9; ++k) { c[k] = (double)cell[k]; g.cell[k] = c[k]; }
-  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-  if (!(fabs(det) >= 1e-12) || !(fabs(det) <= 1.0e300)) bad = true;      // (also NaN / Inf, which the host never sees)
-  if (!bad) {
-    g.inv[0] = (c[4] * c[8] - c[5] * c[7]) / det; g.inv[1] = (c[2] * c[7] - c[1] * c[8]) / det; g.inv[2] = (c[1] * c[5] - c[2] * c[4]) / det;
-    g.inv[3] = (c[5] * c[6] - c[3] * c[8]) / det; g.inv[4] = (c[0] * c[8] - c[2] * c[6]) / det; g.inv[5] = (c[2] * c[3] - c[0] * c[5]) / det;
-    g.inv[6] = (c[3] * c[7] - c[4] * c[6]) / det; g.inv[7] = (c[1] * c[6] - c[0] * c[7]) / det; g.inv[8] = (c[0] * c[4] - c[1] * c[3]) / det;
-    for (int k = 0; k < 3; ++k) {
-      const double h = 1.0 / sqrt(g.inv[k] * g.inv[k] + g.inv[3 + k] * g.inv[3 + k] + g.inv[6 + k] * g.inv[6 + k]);
-      if (!(h > 0.0) || !(h <= 1.0e300)) { bad = true; break; }
-      const double q = floor(h / rc);
-      int nb = q > 1024.0 ? 1024 : (int)q;
-      if (nb < 1) nb = 1;
-      g.nbins[k] = nb;
-      const double r = ceil(rc / (h / nb) - 1e-12);
-      int reach = r > (double)(kMaxImg + 1) ? kMaxImg + 1 : (int)r;
-      if (reach < 1) reach = 1;
-      if (reach > kMaxImg) { bad = true; break; }
-      g.reach[k] = reach;
-      g.lo[k] = 0.0;
-    }
-  }
-  if (bad) {
-    for (int k = 0; k < 9; ++k) { g.cell[k] = 0.0; g.inv[k] = 0.0; }
-    for (int k = 0; k < 3; ++k) { g.nbins[k] = 1; g.reach[k] = 1; g.lo[k] = 0.0; }
-    g.rc2 = -1.0;                   // (no distance is below it: no pair is listed)
+  for (int k = 0; k < 9; ++k) c[k] = (double)cell[k];
+  NbrGeom g;
+  if (!nbr_make_geom(c, nullptr, nullptr, rc, N, g)) {
+    nbr_inert_geom(g, 1, 1);
     overflow[0] = 8;
-  } else {
-    long nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-    while (nbins > 8l * N + 64) {   // must mirror hermnet_neighbor_count
-      int kmax = 0;
-      for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
-      if (g.nbins[kmax] <= 1) break;
-      g.nbins[kmax] = (g.nbins[kmax] + 1) / 2;
-      nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-    }
   }
   *out = g;
 }
@@ -394,80 +405,11 @@ __global__ __launch_bounds__(kBlock) void nbr_batch_ptr_kernel(const long* __res
   for (long b = pc + 1; b <= cc; ++b) ptr[b] = i;
 }
 
-// nbr_geom_kernel's arithmetic for one structure of a batch, statement for statement (the single search's kernel keeps its
-// own text, and with it its instructions): true = a usable geometry in `g`, false = a degenerate cell, `g` half written.
-__device__ __forceinline__ bool nbr_periodic_geom(const float* __restrict__ cell, double rc, int N, NbrGeom& g) {
-#pragma clang fp contract(off)
-  g.rc2 = rc * rc;
-  g.periodic = 1;
-  double c[9];
-  for (int k = 0; k < 9; ++k) { c[k] = (double)cell[k]; g.cell[k] = c[k]; }
-  const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-  if (!(fabs(det) >= 1e-12) || !(fabs(det) <= 1.0e300)) return false;    // (also NaN / Inf, which the host never sees)
-  g.inv[0] = (c[4] * c[8] - c[5] * c[7]) / det; g.inv[1] = (c[2] * c[7] - c[1] * c[8]) / det; g.inv[2] = (c[1] * c[5] - c[2] * c[4]) / det;
-  g.inv[3] = (c[5] * c[6] - c[3] * c[8]) / det; g.inv[4] = (c[0] * c[8] - c[2] * c[6]) / det; g.inv[5] = (c[2] * c[3] - c[0] * c[5]) / det;
-  g.inv[6] = (c[3] * c[7] - c[4] * c[6]) / det; g.inv[7] = (c[1] * c[6] - c[0] * c[7]) / det; g.inv[8] = (c[0] * c[4] - c[1] * c[3]) / det;
-  for (int k = 0; k < 3; ++k) {
-    const double h = 1.0 / sqrt(g.inv[k] * g.inv[k] + g.inv[3 + k] * g.inv[3 + k] + g.inv[6 + k] * g.inv[6 + k]);
-    if (!(h > 0.0) || !(h <= 1.0e300)) return false;
-    const double q = floor(h / rc);
-    int nb = q > 1024.0 ? 1024 : (int)q;
-    if (nb < 1) nb = 1;
-    g.nbins[k] = nb;
-    const double r = ceil(rc / (h / nb) - 1e-12);
-    int reach = r > (double)(kMaxImg + 1) ? kMaxImg + 1 : (int)r;
-    if (reach < 1) reach = 1;
-    if (reach > kMaxImg) return false;
-    g.reach[k] = reach;
-    g.lo[k] = 0.0;
-  }
-  long nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-  while (nbins > 8l * N + 64) {   // must mirror hermnet_neighbor_count and nbr_geom_kernel
-    int kmax = 0;
-    for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
-    if (g.nbins[kmax] <= 1) break;
-    g.nbins[kmax] = (g.nbins[kmax] + 1) / 2;
-    nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-  }
-  return true;
-}
-
-// `make_geom`'s open branch + the coarsening loop of hermnet_neighbor_count for one device thread, from the float32
-// bounding box of the structure (what the host form is handed): float64, no fused multiply-adds, like the periodic one.
-__device__ __forceinline__ bool nbr_open_geom(const float* __restrict__ lo, const float* __restrict__ hi, double rc, int N,
-                                              NbrGeom& g) {
-#pragma clang fp contract(off)
-  g.rc2 = rc * rc;
-  g.periodic = 0;
-  for (int k = 0; k < 9; ++k) { g.cell[k] = (k % 4 == 0) ? 1.0 : 0.0; g.inv[k] = 0.0; }
-  for (int k = 0; k < 3; ++k) {
-    const double span = (double)hi[k] - (double)lo[k] + 2e-6;
-    if (!(span > 0.0) || !(span <= 1.0e300)) return false;               // (NaN / Inf coordinates)
-    const double q = floor(span / rc);
-    int nb = q > 1024.0 ? 1024 : (int)q;
-    if (nb < 1) nb = 1;
-    g.nbins[k] = nb;
-    g.lo[k] = (double)lo[k] - 1e-6;
-    g.inv[4 * k] = nb / span;                                            // 1 / bin width (>= rc wide)
-    g.reach[k] = 1;
-  }
-  long nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-  while (nbins > 8l * N + 64) {   // must mirror hermnet_neighbor_count
-    int kmax = 0;
-    for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
-    if (g.nbins[kmax] <= 1) break;
-    const int nb = (g.nbins[kmax] + 1) / 2;
-    g.inv[4 * kmax] *= (double)nb / g.nbins[kmax];
-    g.nbins[kmax] = nb;
-    nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-  }
-  return true;
-}
-
 // One workgroup per structure: the bounding box of an open structure (min / max are exact in any order), then ONE thread
-// writes its NbrGeom and its bin count (at most 8 N_b + 64, the bound of the single search: the lists are the same bit for
-// bit).  A degenerate cell raises flag bit 3 for that structure alone.  It, an empty structure and every structure of a
-// batch with flag bit 4 get a geometry of reach -1: an atom of such a structure visits no bin and lists no pair.
+// makes its NbrGeom with nbr_make_geom (from the widened float32 cell or box, for the structure's own atom count: the
+// single search's geometry, so the lists are the same bit for bit) and writes its bin count.  A degenerate cell raises flag
+// bit 3 for that structure alone.  It, an empty structure and every structure of a batch with flag bit 4 get an inert
+// geometry of reach -1: an atom of such a structure visits no bin and lists no pair.
 __global__ __launch_bounds__(kBlock) void nbr_batch_geom_kernel(const float* __restrict__ pos, const int* __restrict__ ptr,
                                                                const float* __restrict__ cells, double rc, int B,
                                                                NbrGeom* __restrict__ geom, int* __restrict__ nbin_count,
@@ -495,20 +437,17 @@ __global__ __launch_bounds__(kBlock) void nbr_batch_geom_kernel(const float* __r
   NbrGeom g;
   bool ok = nb_atoms > 0 && (atomicOr(overflow, 0) & 16) == 0;
   if (ok) {
+    double in[9];                                  // the cell, or the box's corners: lo in in[0..2], hi in in[3..5]
     if (cells != nullptr) {
-      ok = nbr_periodic_geom(cells + 9 * (long)b, rc, nb_atoms, g);
+      for (int k = 0; k < 9; ++k) in[k] = (double)cells[9 * (long)b + k];
+      ok = nbr_make_geom(in, nullptr, nullptr, rc, nb_atoms, g);
     } else {
-      const float lo[3] = {red[0][0], red[1][0], red[2][0]}, hi[3] = {red[3][0], red[4][0], red[5][0]};
-      ok = nbr_open_geom(lo, hi, rc, nb_atoms, g);
+      for (int k = 0; k < 6; ++k) in[k] = (double)red[k][0];
+      ok = nbr_make_geom(nullptr, in, in + 3, rc, nb_atoms, g);
     }
     if (!ok) atomicOr(overflow, 8);
   }
-  if (!ok) {
-    g.periodic = cells != nullptr;
-    for (int k = 0; k < 9; ++k) { g.cell[k] = 0.0; g.inv[k] = 0.0; }
-    for (int k = 0; k < 3; ++k) { g.nbins[k] = 1; g.reach[k] = -1; g.lo[k] = 0.0; }
-    g.rc2 = -1.0;
-  }
+  if (!ok) nbr_inert_geom(g, cells != nullptr, -1);
   geom[b] = g;
   nbin_count[b] = g.nbins[0] * g.nbins[1] * g.nbins[2];
   if (b == 0) nbin_count[B] = 0;
@@ -517,66 +456,52 @@ __global__ void nbr_zero_total_kernel(long* __restrict__ total) {
   if (threadIdx.x < 2) total[threadIdx.x] = 0;
 }
 
+// ---- host side: ONE workspace layout, ONE counting pass and ONE of each fill tail for the three forms of the search:
+// the single search with its cell on the host (G = NbrGeom) or in device memory (const NbrGeom*), and the batch
+// (NbrBatch).  An entry point checks its own arguments, carves the workspace, produces its geometry and calls these.
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-int key_bits(int N) {
-  double v = (double)N * (double)N * (double)(kCode * kCode * kCode);
-  int b = 1;
-  while (b < 64 && ldexp(1.0, b) < v) ++b;
-  return b;
-}
 
 struct NbrWork {
   double* fw; int* wrap; unsigned* bin; int* bin_fill; int* ids_sorted; int* bin_start;
-  int* count; long* offset; int* overflow; unsigned long long* stash; void* temp; size_t temp_bytes;
+  int* count; long* offset; int* overflow; unsigned long long* stash;
+  int* graph; int* ptr; int* nbin_count; int* bin_base; NbrGeom* geom;      // a batch's per-structure arrays (B > 0)
+  void* temp; size_t temp_bytes;
+  int stash_slot;          // keys per atom that `stash` holds
 };
 
-size_t temp_bytes_for(int N) {      // scan scratch for the longer of the two scans (bins: <= 8 N + 65 counters; atoms: N + 1)
-  return scan_temp_bytes(8 * N + 66);
+// Bins a workspace has counters for (B = 0: one structure, whose grid is coarsened to this bound; a batch: the sum of its
+// structures' bounds).
+long bins_bound(int N, int B) { return B ? 8l * N + 64l * B : 8l * (N > 0 ? N : 1) + 64; }
+
+size_t workspace_for(int N, int B, int stash) {
+  const long nbins = bins_bound(N, B);
+  size_t bytes = align256(sizeof(double) * 3 * (size_t)N) + align256(sizeof(int) * 3 * (size_t)N) + 2 * align256(sizeof(int) * (size_t)N) +
+                 2 * align256(sizeof(int) * (size_t)(nbins + 1)) + align256(sizeof(int) * (size_t)(N + 1)) +
+                 align256(sizeof(long) * (size_t)(N + 1)) + 256 + align256(sizeof(unsigned long long) * (size_t)N * stash);
+  if (B)
+    bytes += align256(sizeof(int) * (size_t)(N > 0 ? N : 1)) + 3 * align256(sizeof(int) * ((size_t)B + 1)) +
+             align256(sizeof(NbrGeom) * (size_t)B);
+  return bytes + align256(scan_temp_bytes((int)nbins + 2)) + 512;      // (scratch of the longer scan: the bins' counters)
 }
 
-int make_geom(const double* cell_host, const double* lo_host, const double* hi_host, double rc, NbrGeom& g, long& nbins) {
-  g.rc2 = rc * rc;
-  if (cell_host) {
-    g.periodic = 1;
-    double c[9];
-    for (int k = 0; k < 9; ++k) { c[k] = cell_host[k]; g.cell[k] = c[k]; }
-    const double det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6]);
-    if (fabs(det) < 1e-12) return HN_ERR_BAD_ARG;
-    g.inv[0] = (c[4] * c[8] - c[5] * c[7]) / det; g.inv[1] = (c[2] * c[7] - c[1] * c[8]) / det; g.inv[2] = (c[1] * c[5] - c[2] * c[4]) / det;
-    g.inv[3] = (c[5] * c[6] - c[3] * c[8]) / det; g.inv[4] = (c[0] * c[8] - c[2] * c[6]) / det; g.inv[5] = (c[2] * c[3] - c[0] * c[5]) / det;
-    g.inv[6] = (c[3] * c[7] - c[4] * c[6]) / det; g.inv[7] = (c[1] * c[6] - c[0] * c[7]) / det; g.inv[8] = (c[0] * c[4] - c[1] * c[3]) / det;
-    for (int k = 0; k < 3; ++k) {
-      // plane spacing along axis k = 1 / |column k of inv|
-      const double h = 1.0 / sqrt(g.inv[k] * g.inv[k] + g.inv[3 + k] * g.inv[3 + k] + g.inv[6 + k] * g.inv[6 + k]);
-      int nb = (int)floor(h / rc);
-      if (nb < 1) nb = 1;
-      if (nb > 1024) nb = 1024;
-      g.nbins[k] = nb;
-      g.reach[k] = (int)ceil(rc / (h / nb) - 1e-12);
-      if (g.reach[k] < 1) g.reach[k] = 1;
-      if (g.reach[k] > kMaxImg) return HN_ERR_BAD_ARG;       // cell far smaller than the cutoff
-      g.lo[k] = 0.0;
-    }
-  } else {
-    g.periodic = 0;
-    for (int k = 0; k < 9; ++k) { g.cell[k] = (k % 4 == 0) ? 1.0 : 0.0; g.inv[k] = 0.0; }
-    for (int k = 0; k < 3; ++k) {
-      const double span = hi_host[k] - lo_host[k] + 2e-6;
-      int nb = (int)floor(span / rc);
-      if (nb < 1) nb = 1;
-      if (nb > 1024) nb = 1024;
-      g.nbins[k] = nb;
-      g.lo[k] = lo_host[k] - 1e-6;
-      g.inv[4 * k] = nb / span;                               // 1 / bin width (>= rc wide)
-      g.reach[k] = 1;
-    }
+int clamp_stash(int stash) { return stash < 8 ? 8 : (stash > kStash ? kStash : stash); }
+
+bool keys_fit(int N) { return (double)N * N * 4913.0 < 1.8e19; }      // the keys (i N + j) 17^3 + code(S) stay inside 64 bits
+
+bool batch_shape_ok(int N, int B) { return N >= 0 && B > 0 && bins_bound(N, B) + 2 <= 0x7fffffffl && keys_fit(N); }
+
+// The arrays of a workspace of `workspace_bytes` for N > 0 atoms (B = 0: one structure).  The per-atom stash slot is the
+// largest one <= kStash whose workspace fits: every call of a search derives it from the same (N, B, workspace_bytes), so
+// they agree.  false = not even the smallest slot (8 keys) fits.
+bool carve(void* workspace, size_t workspace_bytes, int N, int B, NbrWork& w) {
+  int lo = 0, hi = kStash;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) / 2;
+    if (workspace_for(N, B, mid) <= workspace_bytes) lo = mid; else hi = mid - 1;
   }
-  nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-  return HN_OK;
-}
-
-void carve(void* workspace, int N, long nbins, int stash, NbrWork& w) {
+  if (lo < 8) return false;
+  w.stash_slot = lo;
+  const long nbins = bins_bound(N, B);
   char* p = reinterpret_cast<char*>(workspace);
   auto take = [&](size_t bytes) { void* r = p; p += align256(bytes); return r; };
   w.fw = (double*)take(sizeof(double) * 3 * (size_t)N);
@@ -588,47 +513,90 @@ void carve(void* workspace, int N, long nbins, int stash, NbrWork& w) {
   w.count = (int*)take(sizeof(int) * (size_t)(N + 1));
   w.offset = (long*)take(sizeof(long) * (size_t)(N + 1));
   w.overflow = (int*)take(256);
-  w.stash = (unsigned long long*)take(sizeof(unsigned long long) * (size_t)N * stash);
-  w.temp = p;
-}
-
-size_t fixed_bytes(int N, long nbins, int stash) {
-  return align256(sizeof(double) * 3 * (size_t)N) + align256(sizeof(int) * 3 * (size_t)N) + 2 * align256(sizeof(int) * (size_t)N) +
-         2 * align256(sizeof(int) * (size_t)(nbins + 1)) + align256(sizeof(int) * (size_t)(N + 1)) +
-         align256(sizeof(long) * (size_t)(N + 1)) + 256 + align256(sizeof(unsigned long long) * (size_t)N * stash);
-}
-
-size_t workspace_for(int num_atoms, int stash) {
-  // the bin grid is coarsened to at most 8 bins per atom
-  const long nbins = 8l * (num_atoms > 0 ? num_atoms : 1) + 64;
-  return fixed_bytes(num_atoms, nbins, stash) + align256(temp_bytes_for(num_atoms > 0 ? num_atoms : 1)) + 512;
-}
-
-// the per-atom stash slot a workspace of this size provides: the largest value <= kStash whose workspace fits
-// (both calls of a search derive it from the same (num_atoms, workspace_bytes), so they agree)
-int stash_of(int num_atoms, size_t workspace_bytes) {
-  int lo = 0, hi = kStash;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (workspace_for(num_atoms, mid) <= workspace_bytes) lo = mid; else hi = mid - 1;
+  w.stash = (unsigned long long*)take(sizeof(unsigned long long) * (size_t)N * w.stash_slot);
+  w.graph = w.ptr = w.nbin_count = w.bin_base = nullptr;
+  w.geom = nullptr;
+  if (B) {
+    w.graph = (int*)take(sizeof(int) * (size_t)N);
+    w.ptr = (int*)take(sizeof(int) * ((size_t)B + 1));
+    w.nbin_count = (int*)take(sizeof(int) * ((size_t)B + 1));
+    w.bin_base = (int*)take(sizeof(int) * ((size_t)B + 1));
+    w.geom = (NbrGeom*)take(sizeof(NbrGeom) * (size_t)B);
   }
-  return lo;
+  w.temp = p;
+  w.temp_bytes = workspace_bytes - (size_t)(p - (char*)workspace);
+  return true;
+}
+
+int launched() { return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH; }
+
+// The counting pass on a geometry that exists (G by value) or that earlier launches of the stream make (the two device
+// forms): bin -> atoms sorted by bin -> every atom's pairs counted and their keys stashed -> offsets -> total_device =
+// (pairs found, flags).  `nbins`: counters to clear and scan -- the grid's bins or, where only the device knows the grid,
+// the workspace's bound (counters beyond the grid's bins stay zero).  `clear`: the pass resets the flags itself; the
+// device forms did so before their geometry kernels, which raise flags of their own.
+template <class G>
+int count_pass(const float* pos, int N, G g, long nbins, const NbrWork& w, bool clear, const unsigned char* target_ok,
+               int target_is_j, long* total_device, hipStream_t s) {
+  hipLaunchKernelGGL(nbr_bin_kernel<G>, grid_for(N), dim3(kBlock), 0, s, pos, N, g, w.fw, w.wrap, w.bin);
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
+  hipLaunchKernelGGL(nbr_bin_hist_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_fill);
+  if (exclusive_scan_i32(w.bin_fill, w.bin_start, (int)nbins + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
+  hipLaunchKernelGGL(nbr_bin_scatter_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_start, w.bin_fill, w.ids_sorted);
+  if (clear) hipLaunchKernelGGL(nbr_clear_kernel, dim3(1), dim3(64), 0, s, w.count + N, w.overflow);
+  hipLaunchKernelGGL((nbr_pairs_kernel<0, G>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
+                     g, (const long*)nullptr, w.count, w.stash, w.overflow, target_ok, target_is_j, w.stash_slot);
+  if (exclusive_scan_i32_to_long(w.count, w.offset, N + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
+  hipLaunchKernelGGL(nbr_total_kernel, dim3(1), dim3(64), 0, s, w.offset + N, w.overflow, total_device);
+  return launched();
+}
+
+// The exact list after the host read of E: the stashed keys rank-sorted per atom and decoded, behind (stash_ok = 0: an atom
+// had more pairs than its stash slot) a second pass over the candidates into `keys`.
+template <class G>
+int fill_exact(int N, G g, const NbrWork& w, const unsigned char* target_ok, int target_is_j, long num_edges, float shift_sign,
+               int source_first, int stash_ok, unsigned long long* keys, long* edge_index, float* edge_shift, hipStream_t s) {
+  if (!stash_ok)
+    hipLaunchKernelGGL((nbr_pairs_kernel<1, G>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
+                       g, w.offset, (int*)nullptr, keys, w.overflow, target_ok, target_is_j, 0);
+  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s, stash_ok ? w.stash : keys,
+                     stash_ok ? w.stash_slot : 0, w.count, w.offset, N, num_edges, shift_sign, source_first, edge_index, edge_shift);
+  return launched();
+}
+
+// The padded list: the stashed keys, rank-sorted per atom, into the first `capacity` columns, NULL edges behind them, and the
+// count + flags for whoever reads them (the host: at the END of the step).
+int fill_padded(int N, const NbrWork& w, long capacity, float shift_sign, int source_first, long* edge_index, float* edge_shift,
+                long* total_device, hipStream_t s) {
+  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s, w.stash, w.stash_slot, w.count, w.offset, N,
+                     capacity, shift_sign, source_first, edge_index, edge_shift);
+  hipLaunchKernelGGL(nbr_pad_kernel, grid_for(capacity), dim3(kBlock), 0, s, w.offset, w.overflow, N, capacity, edge_index,
+                     edge_shift, total_device);
+  return launched();
 }
 
 }  // namespace
 
-extern "C" size_t hermnet_neighbor_workspace(int num_atoms) { return workspace_for(num_atoms, kStash); }
+extern "C" size_t hermnet_neighbor_workspace(int num_atoms) { return workspace_for(num_atoms, 0, kStash); }
 extern "C" size_t hermnet_neighbor_workspace_for(int num_atoms, int stash_per_atom) {
-  const int st = stash_per_atom < 8 ? 8 : (stash_per_atom > kStash ? kStash : stash_per_atom);
-  return workspace_for(num_atoms, st);
+  return workspace_for(num_atoms, 0, clamp_stash(stash_per_atom));
+}
+extern "C" size_t hermnet_neighbor_batch_workspace(int num_atoms, int num_graphs, int stash_per_atom) {
+  return batch_shape_ok(num_atoms, num_graphs) ? workspace_for(num_atoms, num_graphs, clamp_stash(stash_per_atom)) : 0;
 }
 
-namespace {
-int stash_checked(int num_atoms, size_t workspace_bytes) {
-  const int st = stash_of(num_atoms, workspace_bytes);
-  return st >= 8 ? st : 0;
+extern "C" int hermnet_host_neighbor_geometry(const double* cell_host, const double* lo_host, const double* hi_host, double rc,
+                                              int num_atoms, double* geom_host, int* grid_host) {
+  if (num_atoms < 1 || !(rc > 0.0) || !geom_host || !grid_host || (!cell_host && (!lo_host || !hi_host))) return HN_ERR_BAD_ARG;
+  NbrGeom g;
+  if (!nbr_make_geom(cell_host, lo_host, hi_host, rc, num_atoms, g)) return HN_ERR_BAD_ARG;
+  for (int k = 0; k < 9; ++k) { geom_host[k] = g.cell[k]; geom_host[9 + k] = g.inv[k]; }
+  for (int k = 0; k < 3; ++k) { geom_host[18 + k] = g.lo[k]; grid_host[k] = g.nbins[k]; grid_host[3 + k] = g.reach[k]; }
+  geom_host[21] = g.rc2;
+  grid_host[6] = g.periodic;
+  return HN_OK;
 }
-}  // namespace
 
 extern "C" int hermnet_neighbor_count(const float* pos, int num_atoms, const double* cell_host,
                                       const double* lo_host, const double* hi_host, double rc,
@@ -641,71 +609,27 @@ extern "C" int hermnet_neighbor_count(const float* pos, int num_atoms, const dou
   if (N == 0) return hipMemsetAsync(total_device, 0, 2 * sizeof(long), s) == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
   if (!pos) return HN_ERR_BAD_ARG;
   NbrGeom g;
-  long nbins = 0;
-  int rc_ = make_geom(cell_host, lo_host, hi_host, rc, g, nbins);
-  if (rc_) return rc_;
-  if (nbins > 8l * N + 64) {   // sparse box: coarsen the grid (bins only get wider, still >= rc)
-    while (nbins > 8l * N + 64) {
-      int kmax = 0;
-      for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
-      if (g.nbins[kmax] <= 1) break;
-      const int nb = (g.nbins[kmax] + 1) / 2;
-      if (!g.periodic) g.inv[4 * kmax] *= (double)nb / g.nbins[kmax];
-      g.nbins[kmax] = nb;
-      nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-    }
-  }
-  const int stash = stash_checked(N, workspace_bytes);
-  if (stash == 0) return HN_ERR_BAD_ARG;
   NbrWork w;
-  carve(workspace, N, 8l * N + 64, stash, w);
-  w.temp_bytes = workspace_bytes - (size_t)((char*)w.temp - (char*)workspace);
-  hipLaunchKernelGGL(nbr_bin_kernel<NbrGeom>, grid_for(N), dim3(kBlock), 0, s, pos, N, g, w.fw, w.wrap, w.bin);
-  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
-  hipLaunchKernelGGL(nbr_bin_hist_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_fill);
-  if (exclusive_scan_i32(w.bin_fill, w.bin_start, (int)nbins + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
-  hipLaunchKernelGGL(nbr_bin_scatter_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_start, w.bin_fill, w.ids_sorted);
-  hipLaunchKernelGGL(nbr_clear_kernel, dim3(1), dim3(64), 0, s, w.count + N, w.overflow);
-  hipLaunchKernelGGL((nbr_pairs_kernel<0, NbrGeom>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
-                     g, (const long*)nullptr, w.count, w.stash, w.overflow, target_ok, g.periodic, stash);
-  if (exclusive_scan_i32_to_long(w.count, w.offset, N + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
-  // total_device = (pairs found, flags of the pass)
-  hipLaunchKernelGGL(nbr_total_kernel, dim3(1), dim3(64), 0, s, w.offset + N, w.overflow, total_device);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  if (!nbr_make_geom(cell_host, lo_host, hi_host, rc, N, g) || !carve(workspace, workspace_bytes, N, 0, w)) return HN_ERR_BAD_ARG;
+  return count_pass(pos, N, g, (long)g.nbins[0] * g.nbins[1] * g.nbins[2], w, true, target_ok, g.periodic, total_device, s);
 }
 
-// The counting pass with the cell in DEVICE memory (periodic cells; `cell` [9] float32, rows = lattice vectors): nothing
-// about the cell is known on the host, so the launch sizes that follow the bin count take the bound the workspace is
-// carved for (8 N + 64 bins; counters beyond the grid's bins stay zero) and the geometry lives in the workspace.
+// The cell in DEVICE memory (periodic cells; `cell` [9] float32, rows = lattice vectors): nothing about it is known on the
+// host, so the launch sizes that follow the bin count take the bound the workspace is carved for, and the geometry lives
+// in the workspace (the flags' 256-byte block: two ints of flags in front, the geometry behind them).
 extern "C" int hermnet_neighbor_count_devcell(const float* pos, int num_atoms, const float* cell, double rc,
                                               void* workspace, size_t workspace_bytes, const unsigned char* target_ok,
                                               long* total_device, void* stream) {
   const int N = num_atoms;
   if (N <= 0 || !(rc > 0.0) || !pos || !cell || !workspace || !total_device) return HN_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int stash = stash_checked(N, workspace_bytes);
-  if (stash == 0) return HN_ERR_BAD_ARG;
-  const long nbins = 8l * N + 64;
   NbrWork w;
-  carve(workspace, N, nbins, stash, w);
-  w.temp_bytes = workspace_bytes - (size_t)((char*)w.temp - (char*)workspace);
-  // (the flags' 256-byte block: two ints of flags in front, the geometry behind them)
+  if (!carve(workspace, workspace_bytes, N, 0, w)) return HN_ERR_BAD_ARG;
   static_assert(sizeof(NbrGeom) + 32 <= 256, "NbrGeom must fit behind the flags");
   NbrGeom* g = reinterpret_cast<NbrGeom*>(reinterpret_cast<char*>(w.overflow) + 32);
   hipLaunchKernelGGL(nbr_clear_kernel, dim3(1), dim3(64), 0, s, w.count + N, w.overflow);
   hipLaunchKernelGGL(nbr_geom_kernel, dim3(1), dim3(64), 0, s, cell, rc, N, g, w.overflow);
-  hipLaunchKernelGGL(nbr_bin_kernel<const NbrGeom*>, grid_for(N), dim3(kBlock), 0, s, pos, N, (const NbrGeom*)g, w.fw, w.wrap, w.bin);
-  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
-  hipLaunchKernelGGL(nbr_bin_hist_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_fill);
-  if (exclusive_scan_i32(w.bin_fill, w.bin_start, (int)nbins + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
-  hipLaunchKernelGGL(nbr_bin_scatter_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_start, w.bin_fill, w.ids_sorted);
-  hipLaunchKernelGGL((nbr_pairs_kernel<0, const NbrGeom*>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted,
-                     w.bin_start, N, (const NbrGeom*)g, (const long*)nullptr, w.count, w.stash, w.overflow, target_ok, 1, stash);
-  if (exclusive_scan_i32_to_long(w.count, w.offset, N + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(nbr_total_kernel, dim3(1), dim3(64), 0, s, w.offset + N, w.overflow, total_device);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  return count_pass(pos, N, (const NbrGeom*)g, bins_bound(N, 0), w, false, target_ok, 1, total_device, s);
 }
 
 extern "C" int hermnet_neighbor_fill_padded(int num_atoms, void* workspace, size_t workspace_bytes, long capacity,
@@ -713,19 +637,10 @@ extern "C" int hermnet_neighbor_fill_padded(int num_atoms, void* workspace, size
                                             long* total_device, void* stream) {
   const int N = num_atoms;
   if (N <= 0 || capacity <= 0 || capacity > 0x7fffffffl || !workspace || !edge_index || !total_device) return HN_ERR_BAD_ARG;
-  if ((double)N * N * 4913.0 >= 1.8e19) return HN_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int stash = stash_checked(N, workspace_bytes);
-  if (stash == 0) return HN_ERR_BAD_ARG;
   NbrWork w;
-  carve(workspace, N, 8l * N + 64, stash, w);
-  // the stashed keys of the counting pass, rank-sorted per atom, into the first `capacity` columns ...
-  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s, w.stash, stash, w.count, w.offset, N,
-                     capacity, shift_sign, source_first, edge_index, edge_shift);
-  // ... NULL edges behind them, and the count + flags for whoever reads them (the host: at the END of the step)
-  hipLaunchKernelGGL(nbr_pad_kernel, grid_for(capacity), dim3(kBlock), 0, s, w.offset, w.overflow, N, capacity, edge_index,
-                     edge_shift, total_device);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  if (!keys_fit(N) || !carve(workspace, workspace_bytes, N, 0, w)) return HN_ERR_BAD_ARG;
+  return fill_padded(N, w, capacity, shift_sign, source_first, edge_index, edge_shift, total_device,
+                     reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int hermnet_neighbor_fill(const float* pos, int num_atoms, const double* cell_host,
@@ -736,129 +651,37 @@ extern "C" int hermnet_neighbor_fill(const float* pos, int num_atoms, const doub
                                      void* stream) {
   const int N = num_atoms;
   if (N <= 0 || num_edges < 0 || !workspace || !edge_index) return HN_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (num_edges == 0) return HN_OK;
-  if ((double)N * N * 4913.0 >= 1.8e19 || num_edges > 0x7fffffffl || (!stash_ok && !keys)) return HN_ERR_BAD_ARG;
+  if (!keys_fit(N) || num_edges > 0x7fffffffl || (!stash_ok && !keys)) return HN_ERR_BAD_ARG;
   NbrGeom g;
-  long nbins = 0;
-  int rc_ = make_geom(cell_host, lo_host, hi_host, rc, g, nbins);
-  if (rc_) return rc_;
-  while (nbins > 8l * N + 64) {   // must mirror hermnet_neighbor_count
-    int kmax = 0;
-    for (int k = 1; k < 3; ++k) if (g.nbins[k] > g.nbins[kmax]) kmax = k;
-    if (g.nbins[kmax] <= 1) break;
-    const int nb = (g.nbins[kmax] + 1) / 2;
-    if (!g.periodic) g.inv[4 * kmax] *= (double)nb / g.nbins[kmax];
-    g.nbins[kmax] = nb;
-    nbins = (long)g.nbins[0] * g.nbins[1] * g.nbins[2];
-  }
-  const int stash = stash_checked(N, workspace_bytes);
-  if (stash == 0) return HN_ERR_BAD_ARG;
   NbrWork w;
-  carve(workspace, N, 8l * N + 64, stash, w);
-  w.temp_bytes = workspace_bytes - (size_t)((char*)w.temp - (char*)workspace);
-  if (!stash_ok)    // an atom had more pairs than its stash slot: second pass over the candidates into `keys`
-    hipLaunchKernelGGL((nbr_pairs_kernel<1, NbrGeom>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted, w.bin_start, N,
-                       g, w.offset, (int*)nullptr, keys, w.overflow, target_ok, g.periodic, 0);
-  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s,
-                     stash_ok ? w.stash : keys, stash_ok ? stash : 0, w.count, w.offset, N, num_edges, shift_sign,
-                     source_first, edge_index, edge_shift);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  if (!nbr_make_geom(cell_host, lo_host, hi_host, rc, N, g) || !carve(workspace, workspace_bytes, N, 0, w)) return HN_ERR_BAD_ARG;
+  return fill_exact(N, g, w, target_ok, g.periodic, num_edges, shift_sign, source_first, stash_ok, keys, edge_index, edge_shift,
+                    reinterpret_cast<hipStream_t>(stream));
 }
 
 // ---- the search of a batch of structures (`batch` [N] int64 non-decreasing, `cells` [B,9] float32 in device memory or
-// NULL for open structures): the pipeline above with one geometry per structure, all of them made on the device.  The
-// workspace is the single search's for 8 N + 64 B bins, with the per-structure arrays behind it.
-namespace {
-
-struct NbrBatchWork {
-  NbrWork w;
-  int* graph; int* ptr; int* nbin_count; int* bin_base; NbrGeom* geom;
-};
-
-long batch_bins(int N, int B) { return 8l * N + 64l * B; }
-
-size_t batch_extra_bytes(int N, int B) {
-  return align256(sizeof(int) * (size_t)(N > 0 ? N : 1)) + 3 * align256(sizeof(int) * ((size_t)B + 1)) +
-         align256(sizeof(NbrGeom) * (size_t)B);
-}
-
-size_t batch_workspace_for(int N, int B, int stash) {
-  const long nbins = batch_bins(N, B);
-  return fixed_bytes(N, nbins, stash) + batch_extra_bytes(N, B) + align256(scan_temp_bytes((int)nbins + 2)) + 512;
-}
-
-bool batch_shape_ok(int N, int B) {
-  if (N < 0 || B <= 0 || batch_bins(N, B) + 2 > 0x7fffffffl) return false;
-  return (double)N * N * 4913.0 < 1.8e19;                    // the keys (i N + j) 17^3 + code(S) stay inside 64 bits
-}
-
-int batch_stash_checked(int N, int B, size_t workspace_bytes) {
-  int lo = 0, hi = kStash;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) / 2;
-    if (batch_workspace_for(N, B, mid) <= workspace_bytes) lo = mid; else hi = mid - 1;
-  }
-  return lo >= 8 ? lo : 0;
-}
-
-void carve_batch(void* workspace, size_t workspace_bytes, int N, int B, int stash, NbrBatchWork& bw) {
-  carve(workspace, N, batch_bins(N, B), stash, bw.w);
-  char* p = reinterpret_cast<char*>(bw.w.temp);
-  auto take = [&](size_t bytes) { void* r = p; p += align256(bytes); return r; };
-  bw.graph = (int*)take(sizeof(int) * (size_t)(N > 0 ? N : 1));
-  bw.ptr = (int*)take(sizeof(int) * ((size_t)B + 1));
-  bw.nbin_count = (int*)take(sizeof(int) * ((size_t)B + 1));
-  bw.bin_base = (int*)take(sizeof(int) * ((size_t)B + 1));
-  bw.geom = (NbrGeom*)take(sizeof(NbrGeom) * (size_t)B);
-  bw.w.temp = p;
-  bw.w.temp_bytes = workspace_bytes - (size_t)(p - (char*)workspace);
-}
-
-}  // namespace
-
-extern "C" size_t hermnet_neighbor_batch_workspace(int num_atoms, int num_graphs, int stash_per_atom) {
-  if (!batch_shape_ok(num_atoms, num_graphs)) return 0;
-  const int st = stash_per_atom < 8 ? 8 : (stash_per_atom > kStash ? kStash : stash_per_atom);
-  return batch_workspace_for(num_atoms, num_graphs, st);
-}
-
+// NULL for open structures): one geometry per structure, all of them made on the device; the workspace is the single
+// search's for 8 N + 64 B bins, with the per-structure arrays behind it.
 extern "C" int hermnet_neighbor_batch_count(const float* pos, int num_atoms, const long* batch, int num_graphs,
                                             const float* cells, double rc, void* workspace, size_t workspace_bytes,
                                             long* total_device, void* stream) {
   const int N = num_atoms, B = num_graphs;
   if (!batch_shape_ok(N, B) || !(rc > 0.0) || !workspace || !total_device) return HN_ERR_BAD_ARG;
   if (N > 0 && (!pos || !batch)) return HN_ERR_BAD_ARG;
-  const int stash = batch_stash_checked(N, B, workspace_bytes);
-  if (stash == 0) return HN_ERR_BAD_ARG;
+  NbrWork w;
+  if (!carve(workspace, workspace_bytes, N, B, w)) return HN_ERR_BAD_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   if (N == 0) {
     hipLaunchKernelGGL(nbr_zero_total_kernel, dim3(1), dim3(64), 0, s, total_device);
-    return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+    return launched();
   }
-  const long nbins = batch_bins(N, B);
-  NbrBatchWork bw;
-  carve_batch(workspace, workspace_bytes, N, B, stash, bw);
-  NbrWork& w = bw.w;
-  const NbrBatch g = {bw.geom, bw.graph, bw.bin_base};
   hipLaunchKernelGGL(nbr_clear_kernel, dim3(1), dim3(64), 0, s, w.count + N, w.overflow);
-  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(B + 1l), dim3(kBlock), 0, s, bw.ptr, B + 1l);
-  hipLaunchKernelGGL(nbr_batch_ptr_kernel, grid_for(N + 1l), dim3(kBlock), 0, s, batch, N, B, bw.graph, bw.ptr, w.overflow);
-  hipLaunchKernelGGL(nbr_batch_geom_kernel, dim3(B), dim3(kBlock), 0, s, pos, bw.ptr, cells, rc, B, bw.geom, bw.nbin_count,
-                     w.overflow);
-  if (exclusive_scan_i32(bw.nbin_count, bw.bin_base, B + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(nbr_bin_kernel<NbrBatch>, grid_for(N), dim3(kBlock), 0, s, pos, N, g, w.fw, w.wrap, w.bin);
-  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
-  hipLaunchKernelGGL(nbr_bin_hist_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_fill);
-  if (exclusive_scan_i32(w.bin_fill, w.bin_start, (int)nbins + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(nbins + 1), dim3(kBlock), 0, s, w.bin_fill, nbins + 1);
-  hipLaunchKernelGGL(nbr_bin_scatter_kernel, grid_for(N), dim3(kBlock), 0, s, w.bin, N, w.bin_start, w.bin_fill, w.ids_sorted);
-  hipLaunchKernelGGL((nbr_pairs_kernel<0, NbrBatch>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted,
-                     w.bin_start, N, g, (const long*)nullptr, w.count, w.stash, w.overflow, (const unsigned char*)nullptr, 0,
-                     stash);
-  if (exclusive_scan_i32_to_long(w.count, w.offset, N + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
-  hipLaunchKernelGGL(nbr_total_kernel, dim3(1), dim3(64), 0, s, w.offset + N, w.overflow, total_device);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  hipLaunchKernelGGL(nbr_zero_kernel, grid_for(B + 1l), dim3(kBlock), 0, s, w.ptr, B + 1l);
+  hipLaunchKernelGGL(nbr_batch_ptr_kernel, grid_for(N + 1l), dim3(kBlock), 0, s, batch, N, B, w.graph, w.ptr, w.overflow);
+  hipLaunchKernelGGL(nbr_batch_geom_kernel, dim3(B), dim3(kBlock), 0, s, pos, w.ptr, cells, rc, B, w.geom, w.nbin_count, w.overflow);
+  if (exclusive_scan_i32(w.nbin_count, w.bin_base, B + 1, w.temp, w.temp_bytes, s) != HN_OK) return HN_ERR_BAD_ARG;
+  return count_pass(pos, N, NbrBatch{w.geom, w.graph, w.bin_base}, bins_bound(N, B), w, false, nullptr, 0, total_device, s);
 }
 
 extern "C" int hermnet_neighbor_batch_fill(int num_atoms, int num_graphs, void* workspace, size_t workspace_bytes,
@@ -868,21 +691,11 @@ extern "C" int hermnet_neighbor_batch_fill(int num_atoms, int num_graphs, void* 
   if (!batch_shape_ok(N, B) || N == 0 || num_edges < 0 || num_edges > 0x7fffffffl || !workspace || !edge_index)
     return HN_ERR_BAD_ARG;
   if (num_edges > 0 && !stash_ok && !keys) return HN_ERR_BAD_ARG;
-  const int stash = batch_stash_checked(N, B, workspace_bytes);
-  if (stash == 0) return HN_ERR_BAD_ARG;
+  NbrWork w;
+  if (!carve(workspace, workspace_bytes, N, B, w)) return HN_ERR_BAD_ARG;
   if (num_edges == 0) return HN_OK;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  NbrBatchWork bw;
-  carve_batch(workspace, workspace_bytes, N, B, stash, bw);
-  NbrWork& w = bw.w;
-  if (!stash_ok) {  // an atom had more pairs than its stash slot: second pass over the candidates into `keys`
-    const NbrBatch g = {bw.geom, bw.graph, bw.bin_base};
-    hipLaunchKernelGGL((nbr_pairs_kernel<1, NbrBatch>), grid_for((long)N * 64), dim3(kBlock), 0, s, w.fw, w.wrap, w.ids_sorted,
-                       w.bin_start, N, g, w.offset, (int*)nullptr, keys, w.overflow, (const unsigned char*)nullptr, 0, 0);
-  }
-  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s, stash_ok ? w.stash : keys,
-                     stash_ok ? stash : 0, w.count, w.offset, N, num_edges, shift_sign, source_first, edge_index, edge_shift);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  return fill_exact(N, NbrBatch{w.geom, w.graph, w.bin_base}, w, nullptr, 0, num_edges, shift_sign, source_first, stash_ok, keys,
+                    edge_index, edge_shift, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int hermnet_neighbor_batch_fill_padded(int num_atoms, int num_graphs, void* workspace, size_t workspace_bytes,
@@ -892,15 +705,8 @@ extern "C" int hermnet_neighbor_batch_fill_padded(int num_atoms, int num_graphs,
   if (!batch_shape_ok(N, B) || N == 0 || capacity <= 0 || capacity > 0x7fffffffl || !workspace || !edge_index ||
       !total_device)
     return HN_ERR_BAD_ARG;
-  const int stash = batch_stash_checked(N, B, workspace_bytes);
-  if (stash == 0) return HN_ERR_BAD_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  NbrBatchWork bw;
-  carve_batch(workspace, workspace_bytes, N, B, stash, bw);
-  NbrWork& w = bw.w;
-  hipLaunchKernelGGL(nbr_sort_decode_kernel, grid_for((long)N * 64), dim3(kBlock), 0, s, w.stash, stash, w.count, w.offset, N,
-                     capacity, shift_sign, source_first, edge_index, edge_shift);
-  hipLaunchKernelGGL(nbr_pad_kernel, grid_for(capacity), dim3(kBlock), 0, s, w.offset, w.overflow, N, capacity, edge_index,
-                     edge_shift, total_device);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+  NbrWork w;
+  if (!carve(workspace, workspace_bytes, N, B, w)) return HN_ERR_BAD_ARG;
+  return fill_padded(N, w, capacity, shift_sign, source_first, edge_index, edge_shift, total_device,
+                     reinterpret_cast<hipStream_t>(stream));
 }

@@ -17,6 +17,33 @@ path uses hipMemsetAsync / hipMemcpyAsync any more (csrc/relation_kernels.hip: z
 import torch
 
 
+def _energy_forces(model, data, pos, stress):
+    """(energy, forces) of `data`, with `stress` (energy, forces, virial): ONE forward and ONE backward either way."""
+    if stress:
+        from .stress import energy_forces_virial
+        return tuple(energy_forces_virial(model, data, pos))
+    e = model(data)
+    f = -torch.autograd.grad(e.sum(), pos)[0]
+    return e.detach(), f
+
+
+def _capture(step, warmup):
+    """`warmup` eager runs of `step()` on a side stream (caches, weights, library workspaces), then one run captured:
+    returns (graph, what the captured run returned: the static outputs)."""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = step()
+    torch.cuda.synchronize()
+    return graph, out
+
+
 class GraphedStep(object):
     """energy, forces = step(pos) for a fixed graph topology.
 
@@ -36,32 +63,17 @@ class GraphedStep(object):
         self.virial = None
         self.pos = data.pos.detach().clone().requires_grad_(True)      # static input
         data.pos = self.pos
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):                                      # caches, weights, library workspaces
-                self._eager()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            out = self._eager()
+        self.graph, out = _capture(self._eager, warmup)
         self.energy, self.forces = out[:2]
         if self.stress:
             self.virial = out[2]
-        torch.cuda.synchronize()
         # the captured topology: the tensor OBJECTS (kept alive here, so their addresses cannot be handed to a rebuilt
         # list of the same size) and their versions (in-place edits); taken after the first forward, which fills in a
         # missing `batch`
         self._topo = self._topology(data)
 
     def _eager(self):
-        if self.stress:
-            from .stress import energy_forces_virial
-            return energy_forces_virial(self.model, self.data, self.pos)
-        e = self.model(self.data)
-        f = -torch.autograd.grad(e.sum(), self.pos)[0]
-        return e.detach(), f
+        return _energy_forces(self.model, self.data, self.pos, self.stress)
 
     @staticmethod
     def _topology(data):
@@ -130,21 +142,24 @@ class GraphedMDStep(object):
                                                            reference_compat=self.reference_compat)[0].size(1)))
         self._capture(int(capacity))
 
-    def _eager(self):
+    def _data(self):
+        """(the step's `Data` on a freshly searched padded list, the list's `total`)."""
         from .data import Data
         from .neighbor import neighbor_search_padded
         ei, sh, total = neighbor_search_padded(self.pos.detach(), self.model.rc, self.cell, self.capacity,
                                                reference_compat=self.reference_compat, device_cell=self.variable_cell)
-        d = Data(pos=self.pos, atomic_number=self.z, batch=self.batch, cell=self.cell.reshape(1, 3, 3), edge_index=ei,
-                 edge_shift=sh)
+        return Data(pos=self.pos, atomic_number=self.z, batch=self.batch, cell=self.cell.reshape(1, 3, 3), edge_index=ei,
+                    edge_shift=sh), total
+
+    def _eager(self):
+        """search + step: (energy, forces, total), with `stress` (energy, forces, virial, total), and behind them everything
+        a caller copies to the host per step as ONE array (`fetch`): energies | (edges, flags) | forces (| virial)."""
+        d, total = self._data()
         d._hn_edge_count = total
-        if self.stress:
-            from .stress import energy_forces_virial
-            e, f, w = energy_forces_virial(self.model, d, self.pos)
-            return e, f, total, w
-        e = self.model(d)
-        f = -torch.autograd.grad(e.sum(), self.pos)[0]
-        return e.detach(), f, total
+        out = _energy_forces(self.model, d, self.pos, self.stress)
+        parts = [out[0].double().reshape(-1), total.double(), out[1].double().reshape(-1)]
+        parts += [w.double().reshape(-1) for w in out[2:]]
+        return out + (total, torch.cat(parts))
 
     def stale(self):
         """True once the model's derived weight copies were dropped after the capture (`load_state_dict`, `.to()`,
@@ -154,26 +169,11 @@ class GraphedMDStep(object):
     def _capture(self, capacity):
         self.capacity = capacity
         self._epoch = self.model.__dict__.get("_cache_epoch", 0)
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(self._warmup):        # caches (cell on the host, element counts, row layout), library state
-                self._eager()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            out = self._eager()
-            self.energy, self.forces, self.total = out[:3]
-            # everything a caller copies to the host per step, as ONE array (`fetch`): energies | (edges, flags) | forces
-            # (| virial with `stress`)
-            parts = [self.energy.double().reshape(-1), self.total.double(), self.forces.double().reshape(-1)]
-            if self.stress:
-                self.virial = out[3]
-                parts.append(self.virial.double().reshape(-1))
-            self.packed = torch.cat(parts)
+        self.graph, out = _capture(self._eager, self._warmup)      # (warm-up: also the cell on the host, the row layout)
+        self.energy, self.forces, self.total, self.packed = out[0], out[1], out[-2], out[-1]
+        if self.stress:
+            self.virial = out[2]
         self._host = None
-        torch.cuda.synchronize()
 
     def __call__(self, pos=None, cell=None):
         """`pos` [N,3]: a device tensor, or a float32 host tensor (uploaded straight into the captured input); `cell` [3,3]
@@ -272,7 +272,7 @@ class GraphedBatchMDStep(GraphedMDStep):
             capacity = padded_capacity(int((out if cell is None else out[0]).size(1)))
         self._capture(int(capacity))
 
-    def _eager(self):
+    def _data(self):
         from .data import Data
         from .neighbor import neighbor_search_padded
         ei, sh, total = neighbor_search_padded(self.pos.detach(), self.model.rc, self.cell, self.capacity,
@@ -281,11 +281,4 @@ class GraphedBatchMDStep(GraphedMDStep):
         d = Data(pos=self.pos, atomic_number=self.z, batch=self.batch, edge_index=ei)
         if self.cell is not None:
             d.cell, d.edge_shift = self.cell, sh
-        d._hn_edge_count = total
-        if self.stress:
-            from .stress import energy_forces_virial
-            e, f, w = energy_forces_virial(self.model, d, self.pos)
-            return e, f, total, w
-        e = self.model(d)
-        f = -torch.autograd.grad(e.sum(), self.pos)[0]
-        return e.detach(), f, total
+        return d, total

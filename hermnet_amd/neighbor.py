@@ -157,63 +157,9 @@ _STASH = {}       # device -> keys per atom of the search's stash slot (csrc/nei
 _STASH_DEFAULT = 96       # fcc at rc = 5 A: 43 pairs per atom; 8 bytes per key and atom of workspace
 
 
-def _stash_workspace_bytes(lib, N, dev):
-    """Workspace of a search whose per-atom stash slot holds the current hint of this device (the slot size follows from
-    the workspace size: include/hermnet_hip.h, hermnet_neighbor_workspace_for)."""
-    return lib.hermnet_neighbor_workspace_for(N, _STASH.get(str(dev), _STASH_DEFAULT))
-
-
 def _stash_overflowed(dev):
     """An atom had more pairs than its slot (flag bit 1): the following searches get the largest slot."""
     _STASH[str(dev)] = 160
-
-
-def _neighbor_search_device(pos, rc, cell, reference_compat, target_mask=None):
-    """Device cell list (`csrc/neighbor_kernels.hip`); same result as the host path, tensors stay on the GPU.
-    `target_mask` [N] bool/uint8: list only the pairs whose target atom (row 1) is flagged (atom shards)."""
-    import ctypes
-    from . import _lib
-    lib = _lib.load()
-    P = _lib.ptr
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    dev = pos.device
-    p32 = pos.detach().float().contiguous()
-    N = int(p32.size(0))
-    dbl3 = ctypes.c_double * 3
-    cell_h = lo_h = hi_h = None
-    if cell is not None:
-        cell_h = (ctypes.c_double * 9)(*_cell_on_host(cell))
-    elif N > 0:
-        mm = torch.stack([p32.min(0).values, p32.max(0).values]).double().cpu().tolist()
-        lo_h, hi_h = dbl3(*mm[0]), dbl3(*mm[1])
-    else:
-        lo_h, hi_h = dbl3(0, 0, 0), dbl3(1, 1, 1)
-    mask = None
-    if target_mask is not None:
-        mask = target_mask if target_mask.dtype == torch.uint8 else target_mask.to(torch.uint8)
-        mask = mask.contiguous()
-        if mask.numel() != N or mask.device != dev:
-            raise ValueError("target_mask must be [N] on the device of pos")
-    ws_bytes = _stash_workspace_bytes(lib, N, dev)
-    work = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    total = torch.zeros(2, dtype=torch.long, device=dev)
-    args = (P(p32), N, cell_h, lo_h, hi_h, float(rc), P(work), ws_bytes)
-    _lib.check(lib.hermnet_neighbor_count(*args, P(mask), P(total), stream), "hermnet_neighbor_count")
-    E, flags = total.tolist()                                # the one host read of the search
-    if flags & 2:
-        _stash_overflowed(dev)                               # (this search finishes in its two-pass form)
-    if flags & 1:                                            # an image shift beyond +-8 cells: the host path handles it
-        return None
-    edge_index = torch.empty(2, E, dtype=torch.long, device=dev)
-    periodic = cell is not None
-    shift = torch.empty(E, 3, dtype=torch.float32, device=dev) if periodic else None
-    if E > 0:
-        stash_ok = 0 if (flags & 2) else 1
-        keys = None if stash_ok else torch.empty(E, dtype=torch.long, device=dev)
-        sign = 1.0 if reference_compat else -1.0
-        _lib.check(lib.hermnet_neighbor_fill(*args, E, sign, 0 if periodic else 1, stash_ok, P(keys), P(mask),
-                                             P(edge_index), P(shift), stream), "hermnet_neighbor_fill")
-    return (edge_index, shift) if periodic else edge_index
 
 
 def _batch_args(pos, cell, batch, num_graphs):
@@ -241,22 +187,6 @@ def _batch_args(pos, cell, batch, num_graphs):
     return p32, b64, cells, B
 
 
-def _batch_count(lib, p32, b64, cells, B, rc, total):
-    """The counting pass of a batched search (csrc/neighbor_kernels.hip); returns (workspace, its size)."""
-    import ctypes
-    from . import _lib
-    P = _lib.ptr
-    N = int(p32.size(0))
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    ws_bytes = lib.hermnet_neighbor_batch_workspace(N, B, _STASH.get(str(p32.device), _STASH_DEFAULT))
-    if ws_bytes == 0:
-        raise RuntimeError("batched neighbour search: %d atoms in %d graphs are beyond the search's index range" % (N, B))
-    work = torch.empty(ws_bytes, dtype=torch.uint8, device=p32.device)
-    _lib.check(lib.hermnet_neighbor_batch_count(P(p32), N, P(b64), B, P(cells), float(rc), P(work), ws_bytes, P(total), stream),
-               "hermnet_neighbor_batch_count")
-    return work, ws_bytes
-
-
 def _batch_flags_error(flags):
     if flags & 16:
         raise ValueError("batched neighbour search: `batch` must be non-decreasing with values in [0, num_graphs)")
@@ -264,22 +194,80 @@ def _batch_flags_error(flags):
         raise RuntimeError("batched neighbour search: a cell of the batch is singular or far smaller than the cutoff")
 
 
-def _neighbor_search_device_batched(pos, rc, cell, batch, num_graphs, reference_compat):
-    """`_neighbor_search_device` for a batch of structures: one pass, one host read of (E, flags)."""
+def _device_search(pos, rc, cell, reference_compat, target_mask=None, device_cell=False, batch=None, num_graphs=None,
+                   capacity=None):
+    """The device cell list (`csrc/neighbor_kernels.hip`) in every form: one structure with its cell on the host or
+    (`device_cell`) in device memory, or a batch (`batch` / `num_graphs`).  All of them prepare their arguments, size the
+    workspace from the stash hint of the device and run their counting pass; then
+      * `capacity` None: the exact list after ONE host read of (E, flags) -- what `neighbor_search` returns, or None where
+        the host path has to answer (flag bit 0: an image shift beyond +-8 cells);
+      * otherwise the padded list without a host read: (edge_index, edge_shift, total), see `neighbor_search_padded`."""
     import ctypes
     from . import _lib
     lib = _lib.load()
     P = _lib.ptr
-    p32, b64, cells, B = _batch_args(pos, cell, batch, num_graphs)
-    dev, N, periodic = p32.device, int(p32.size(0)), cells is not None
-    if N == 0:
-        ei = torch.empty(2, 0, dtype=torch.long, device=dev)
-        return (ei, torch.empty(0, 3, dtype=torch.float32, device=dev)) if periodic else ei
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    total = torch.zeros(2, dtype=torch.long, device=dev)
-    work, ws_bytes = _batch_count(lib, p32, b64, cells, B, rc, total)
+    batched, padded, periodic = batch is not None or num_graphs is not None, capacity is not None, cell is not None
+    if batched:
+        p32, b64, cells, B = _batch_args(pos, cell, batch, num_graphs)
+    else:
+        p32 = pos.detach().float().contiguous()
+    dev, N = p32.device, int(p32.size(0))
+    hint = _STASH.get(str(dev), _STASH_DEFAULT)       # keys per atom of the stash slot: the workspace's size decides it
+    mask = None
+    if batched:
+        if N == 0:
+            if padded:
+                raise ValueError("a padded batched search needs at least one atom")
+            ei = torch.empty(2, 0, dtype=torch.long, device=dev)
+            return (ei, torch.empty(0, 3, dtype=torch.float32, device=dev)) if periodic else ei
+        ws_bytes = lib.hermnet_neighbor_batch_workspace(N, B, hint)
+        if ws_bytes == 0:
+            raise RuntimeError("batched neighbour search: %d atoms in %d graphs are beyond the search's index range" % (N, B))
+        count, head = lib.hermnet_neighbor_batch_count, (P(p32), N, P(b64), B, P(cells), float(rc))
+    else:
+        ws_bytes = lib.hermnet_neighbor_workspace_for(N, hint)
+        if device_cell:
+            if cell is None or not cell.is_cuda or cell.dtype != torch.float32 or cell.numel() != 9 or not cell.is_contiguous():
+                raise ValueError("device_cell=True needs a contiguous float32 [3,3] cell on the GPU")
+            if N == 0:
+                raise ValueError("device_cell=True needs at least one atom")
+            count, head = lib.hermnet_neighbor_count_devcell, (P(p32), N, P(cell), float(rc))
+        else:
+            dbl3 = ctypes.c_double * 3
+            cell_h, lo_h, hi_h = None, dbl3(0, 0, 0), dbl3(1, 1, 1)
+            if periodic:
+                cell_h, lo_h, hi_h = (ctypes.c_double * 9)(*_cell_on_host(cell)), None, None
+            elif N > 0:       # (an open structure's bounding box is a host read of its own: periodic cells are the MD case)
+                mm = torch.stack([p32.min(0).values, p32.max(0).values]).double().cpu().tolist()
+                lo_h, hi_h = dbl3(*mm[0]), dbl3(*mm[1])
+            count, head = lib.hermnet_neighbor_count, (P(p32), N, cell_h, lo_h, hi_h, float(rc))
+        if target_mask is not None:
+            mask = (target_mask if target_mask.dtype == torch.uint8 else target_mask.to(torch.uint8)).contiguous()
+            if mask.numel() != N or mask.device != dev:
+                raise ValueError("target_mask must be [N] on the device of pos")
+    work = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    total = torch.empty(2, dtype=torch.long, device=dev) if padded else torch.zeros(2, dtype=torch.long, device=dev)
+    masks = () if batched else (P(mask),)             # (target masks are not part of the batched entry points)
+    _lib.check(count(*head, P(work), ws_bytes, *masks, P(total), stream), count.__name__)
+    source_first = 0 if periodic else 1
+    sign = 1.0 if reference_compat else -1.0
+    if padded:
+        cap = int(capacity)
+        edge_index = torch.empty(2, cap, dtype=torch.long, device=dev)
+        shift = torch.empty(cap, 3, dtype=torch.float32, device=dev) if periodic else None
+        if switches.debug_poison():
+            # (tests: a column the search leaves unwritten would send the relation build far out of bounds)
+            edge_index.fill_(0x3f3f3f3f3f3f3f3f)
+            if shift is not None:
+                shift.fill_(float("nan"))
+        fill, shape = (lib.hermnet_neighbor_batch_fill_padded, (N, B)) if batched else (lib.hermnet_neighbor_fill_padded, (N,))
+        _lib.check(fill(*shape, P(work), ws_bytes, cap, sign, source_first, P(edge_index), P(shift), P(total), stream),
+                   fill.__name__)
+        return edge_index, shift, total
     E, flags = total.tolist()                                # the one host read of the search
-    _batch_flags_error(flags)
+    if batched:
+        _batch_flags_error(flags)
     if flags & 2:
         _stash_overflowed(dev)                               # (this search finishes in its two-pass form)
     if flags & 1:                                            # an image shift beyond +-8 cells: the host path handles it
@@ -289,40 +277,23 @@ def _neighbor_search_device_batched(pos, rc, cell, batch, num_graphs, reference_
     if E > 0:
         stash_ok = 0 if (flags & 2) else 1
         keys = None if stash_ok else torch.empty(E, dtype=torch.long, device=dev)
-        _lib.check(lib.hermnet_neighbor_batch_fill(N, B, P(work), ws_bytes, E, 1.0 if reference_compat else -1.0,
-                                                   0 if periodic else 1, stash_ok, P(keys), P(edge_index), P(shift), stream),
-                   "hermnet_neighbor_batch_fill")
+        fill, shape = (lib.hermnet_neighbor_batch_fill, (N, B)) if batched else (lib.hermnet_neighbor_fill, head)
+        _lib.check(fill(*shape, P(work), ws_bytes, E, sign, source_first, stash_ok, P(keys), *masks, P(edge_index), P(shift),
+                        stream), fill.__name__)
     return (edge_index, shift) if periodic else edge_index
 
 
-def _neighbor_search_padded_batched(pos, rc, cell, capacity, reference_compat, batch, num_graphs):
-    """`neighbor_search_padded` for a batch of structures: nothing about them is read on the host (pass `num_graphs`)."""
-    import ctypes
-    from . import _lib
-    lib = _lib.load()
-    P = _lib.ptr
-    p32, b64, cells, B = _batch_args(pos, cell, batch, num_graphs)
-    dev, N, cap, periodic = p32.device, int(p32.size(0)), int(capacity), cells is not None
-    if N == 0:
-        raise ValueError("a padded batched search needs at least one atom")
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    total = torch.empty(2, dtype=torch.long, device=dev)
-    edge_index = torch.empty(2, cap, dtype=torch.long, device=dev)
-    shift = torch.empty(cap, 3, dtype=torch.float32, device=dev) if periodic else None
-    if switches.debug_poison():
-        edge_index.fill_(0x3f3f3f3f3f3f3f3f)
-        if shift is not None:
-            shift.fill_(float("nan"))
-    work, ws_bytes = _batch_count(lib, p32, b64, cells, B, rc, total)
-    _lib.check(lib.hermnet_neighbor_batch_fill_padded(N, B, P(work), ws_bytes, cap, 1.0 if reference_compat else -1.0,
-                                                      0 if periodic else 1, P(edge_index), P(shift), P(total), stream),
-               "hermnet_neighbor_batch_fill_padded")
-    return edge_index, shift, total
+def _lists_as_tensors(i, j, s, periodic, reference_compat, dev):
+    """(i, j, S) of the numpy list in `neighbor_search`'s calling conventions: periodic [i; j] with edge_shift = -S (+S with
+    `reference_compat`); open [j; i], radius_graph's: row 0 = source (neighbour), row 1 = target (centre)."""
+    if not periodic:
+        return torch.from_numpy(np.vstack([j, i])).long().to(dev)
+    sign = 1.0 if reference_compat else -1.0
+    return torch.from_numpy(np.vstack([i, j])).long().to(dev), torch.from_numpy(sign * s.astype(np.float32)).float().to(dev)
 
 
 def _neighbor_search_host_batched(pos, rc, cell, batch, num_graphs, reference_compat):
     """The batched search on the host: `neighbor_list` per structure, the atom offsets added."""
-    dev = pos.device
     p = pos.detach().cpu().numpy()
     b = batch.detach().cpu().numpy().astype(np.int64)
     cells = None if cell is None else cell.detach().cpu().numpy().reshape(-1, 3, 3)
@@ -338,11 +309,8 @@ def _neighbor_search_host_batched(pos, rc, cell, batch, num_graphs, reference_co
     for g in range(B):
         i, j, s = neighbor_list(p[ptr[g]:ptr[g + 1]], rc, None if cells is None else cells[g])
         ii.append(i + ptr[g]), jj.append(j + ptr[g]), ss.append(s)
-    i, j, s = np.concatenate(ii), np.concatenate(jj), np.concatenate(ss)
-    if cells is None:
-        return torch.from_numpy(np.vstack([j, i])).long().to(dev)
-    sign = 1.0 if reference_compat else -1.0
-    return (torch.from_numpy(np.vstack([i, j])).long().to(dev), torch.from_numpy(sign * s.astype(np.float32)).float().to(dev))
+    return _lists_as_tensors(np.concatenate(ii), np.concatenate(jj), np.concatenate(ss), cells is not None, reference_compat,
+                             pos.device)
 
 
 def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, target_mask=None, device_cell=False, batch=None,
@@ -367,60 +335,13 @@ def neighbor_search_padded(pos, rc, cell, capacity, reference_compat=False, targ
     read on the device (the cells as with `device_cell=True`), so the call is capturable for periodic and open batches
     alike; the list is the structures' lists concatenated with their atom offsets.  Flag bit 3 then marks a degenerate cell
     of one structure (which lists no pair; the others are complete), bit 4 a `batch` that decreases (no pair at all)."""
-    import ctypes
-    from . import _lib
     if not pos.is_cuda:
         raise RuntimeError("neighbor_search_padded runs on the device list only")
     if cell is None and reference_compat:
         raise NotImplementedError("the reference pipeline's 32-neighbour cap needs the exact list (neighbor_search)")
-    if batch is not None or num_graphs is not None:
-        if target_mask is not None:
-            raise NotImplementedError("target_mask is not part of the batched search")
-        return _neighbor_search_padded_batched(pos, rc, cell, capacity, reference_compat, batch, num_graphs)
-    lib = _lib.load()
-    P = _lib.ptr
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    dev = pos.device
-    p32 = pos.detach().float().contiguous()
-    N, cap = int(p32.size(0)), int(capacity)
-    dbl3 = ctypes.c_double * 3
-    cell_h = lo_h = hi_h = None
-    if device_cell:
-        if cell is None or not cell.is_cuda or cell.dtype != torch.float32 or cell.numel() != 9 or not cell.is_contiguous():
-            raise ValueError("device_cell=True needs a contiguous float32 [3,3] cell on the GPU")
-        if N == 0:
-            raise ValueError("device_cell=True needs at least one atom")
-    elif cell is not None:
-        cell_h = (ctypes.c_double * 9)(*_cell_on_host(cell))
-    else:       # (an open system's bounding box is a host read of its own: periodic cells are the MD case)
-        mm = torch.stack([p32.min(0).values, p32.max(0).values]).double().cpu().tolist()
-        lo_h, hi_h = dbl3(*mm[0]), dbl3(*mm[1])
-    mask = None
-    if target_mask is not None:
-        mask = (target_mask if target_mask.dtype == torch.uint8 else target_mask.to(torch.uint8)).contiguous()
-        if mask.numel() != N or mask.device != dev:
-            raise ValueError("target_mask must be [N] on the device of pos")
-    ws_bytes = _stash_workspace_bytes(lib, N, dev)
-    work = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    total = torch.empty(2, dtype=torch.long, device=dev)
-    edge_index = torch.empty(2, cap, dtype=torch.long, device=dev)
-    periodic = cell is not None
-    shift = torch.empty(cap, 3, dtype=torch.float32, device=dev) if periodic else None
-    if switches.debug_poison():
-        # (tests: a column the search leaves unwritten would send the relation build far out of bounds)
-        edge_index.fill_(0x3f3f3f3f3f3f3f3f)
-        if shift is not None:
-            shift.fill_(float("nan"))
-    if device_cell:
-        _lib.check(lib.hermnet_neighbor_count_devcell(P(p32), N, P(cell), float(rc), P(work), ws_bytes, P(mask), P(total), stream),
-                   "hermnet_neighbor_count_devcell")
-    else:
-        _lib.check(lib.hermnet_neighbor_count(P(p32), N, cell_h, lo_h, hi_h, float(rc), P(work), ws_bytes, P(mask), P(total),
-                                              stream), "hermnet_neighbor_count")
-    sign = 1.0 if reference_compat else -1.0
-    _lib.check(lib.hermnet_neighbor_fill_padded(N, P(work), ws_bytes, cap, sign, 0 if periodic else 1, P(edge_index), P(shift),
-                                                P(total), stream), "hermnet_neighbor_fill_padded")
-    return edge_index, shift, total
+    if (batch is not None or num_graphs is not None) and target_mask is not None:
+        raise NotImplementedError("target_mask is not part of the batched search")
+    return _device_search(pos, rc, cell, reference_compat, target_mask, device_cell, batch, num_graphs, int(capacity))
 
 
 def padded_list_ok(total):
@@ -474,36 +395,20 @@ def neighbor_search(pos, rc, cell=None, reference_compat=False, target_mask=None
     """
     if cell is None and reference_compat:
         return _cap_neighbors(neighbor_search(pos, rc, None, False, target_mask, batch, num_graphs), 32)
-    if batch is not None or num_graphs is not None:
-        if target_mask is not None:
-            raise NotImplementedError("target_mask is not part of the batched search")
-        if batch is None:
-            raise ValueError("num_graphs without batch")
-        if pos.is_cuda:
-            out = _neighbor_search_device_batched(pos, rc, cell, batch, num_graphs, reference_compat)
-            if out is not None:
-                return out
-        return _neighbor_search_host_batched(pos, rc, cell, batch, num_graphs, reference_compat)
+    batched = batch is not None or num_graphs is not None
+    if batched and target_mask is not None:
+        raise NotImplementedError("target_mask is not part of the batched search")
+    if batched and batch is None:
+        raise ValueError("num_graphs without batch")
     if pos.is_cuda:
-        out = _neighbor_search_device(pos, rc, cell, reference_compat, target_mask)
+        out = _device_search(pos, rc, cell, reference_compat, target_mask, batch=batch, num_graphs=num_graphs)
         if out is not None:
             return out
-    dev = pos.device
+    if batched:
+        return _neighbor_search_host_batched(pos, rc, cell, batch, num_graphs, reference_compat)
     p = pos.detach().cpu().numpy()
-    keep = None if target_mask is None else target_mask.detach().cpu().numpy().astype(bool)
-    if cell is None:
-        i, j, _ = neighbor_list(p, rc, None)
-        if keep is not None:
-            sel = keep[i]
-            i, j = i[sel], j[sel]
-        # radius_graph convention: row 0 = source (neighbour), row 1 = target (centre)
-        return torch.from_numpy(np.vstack([j, i])).long().to(dev)
-    c = cell.detach().cpu().numpy().reshape(-1, 3, 3)[0]
-    i, j, s = neighbor_list(p, rc, c)
-    if keep is not None:
-        sel = keep[j]
+    i, j, s = neighbor_list(p, rc, None if cell is None else cell.detach().cpu().numpy().reshape(-1, 3, 3)[0])
+    if target_mask is not None:       # the target atom (row 1): i of an open list ([j; i]), j of a periodic one ([i; j])
+        sel = target_mask.detach().cpu().numpy().astype(bool)[i if cell is None else j]
         i, j, s = i[sel], j[sel], s[sel]
-    edge_index = torch.from_numpy(np.vstack([i, j])).long()
-    sign = 1.0 if reference_compat else -1.0
-    edge_shift = torch.from_numpy(sign * s.astype(np.float32)).float()
-    return edge_index.to(dev), edge_shift.to(dev)
+    return _lists_as_tensors(i, j, s, cell is not None, reference_compat, pos.device)

@@ -19,7 +19,7 @@
  * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -827,6 +827,17 @@ int hermnet_host_rbf_row(const float* offset_host, int num_rbf, float inv_rc, fl
                          int env_kind, int env_p, const float* wt_host /* [R,C] */,
                          const float* b_host /* [C] */, int C, float d,
                          float* rb_host /* [C] */, float* drb_host /* [C] */);
+
+/* Host-side (CPU) probe of the neighbour search's cell-list geometry: the ONE routine that hermnet_neighbor_count /
+ * _fill run on the host and that the device-cell and batch forms run in a kernel (csrc/neighbor_kernels.hip,
+ * nbr_make_geom), so that its arithmetic can be checked without a GPU.  cell_host: 9 doubles (rows = lattice vectors), or
+ * NULL with the corners lo_host / hi_host [3] of an open structure's bounding box; num_atoms >= 1 bounds the grid (at most
+ * 8 num_atoms + 64 bins).  geom_host [22] = cell [9] | inverse [9] | lo [3] | rc^2; grid_host [7] = nbins [3] | reach [3] |
+ * periodic.  HN_ERR_BAD_ARG: a missing pointer, rc <= 0, num_atoms < 1, or a degenerate geometry -- a singular cell, one so
+ * small that the cutoff reaches beyond 8 bins, a cell or box that is not finite (the search's host form once sent the
+ * latter through an undefined cast; it refuses them now).  All pointers are HOST pointers. */
+int hermnet_host_neighbor_geometry(const double* cell_host, const double* lo_host, const double* hi_host, double rc,
+                                   int num_atoms, double* geom_host /* [22] */, int* grid_host /* [7] */);
 
 #ifdef __cplusplus
 }

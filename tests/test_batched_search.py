@@ -259,6 +259,26 @@ def test_open_batch_with_an_empty_graph_lists_no_pair_across_graphs():
 
 
 @pytest.mark.gpu
+def test_open_batch_equals_three_single_device_searches_coarsened_grid_included():
+    """The batch's geometry is the single search's for open structures too: a 20-atom ball, a single atom, and two atoms
+    60 A apart with nothing between them (10 x 6 x 2 bins of the cutoff's width against the 8 * 2 + 64 that two atoms are
+    allowed: their grid is coarsened) give the concatenation of the three single device searches, atom offsets added."""
+    dev = _dev()
+    far = np.array([[-30.0, -17.0, -9.5], [22.0, 13.0, 4.5]])
+    assert 60.0 < np.linalg.norm(far[1] - far[0]) and np.prod(np.floor((far[1] - far[0]) / RC)) > 8 * 2 + 64
+    per = [(_ball(20, 4.0, 61), None), (_ball(1, 1.0, 62), None), (far, None)]
+    pos, batch, _ = _join(per)
+    i, j, s = _host_lists(pos, batch, None, 3)
+    p, b, _ = _to(dev, pos, batch, None)
+    ei = hn.neighbor_search(p, RC, None, batch=b, num_graphs=3)       # ONE call
+    ptr = _ptr(batch, 3)
+    singles = [hn.neighbor_search(p[ptr[g]:ptr[g + 1]], RC) for g in range(3)]
+    assert singles[1].size(1) == 0 and singles[2].size(1) == 0 and singles[0].size(1) > 0
+    assert torch.equal(ei, torch.cat([e + int(ptr[g]) for g, e in enumerate(singles)], 1))
+    assert torch.equal(ei.cpu(), _as_tensors(i, j, s, False)[0])
+
+
+@pytest.mark.gpu
 def test_an_atom_with_more_pairs_than_its_stash_slot_takes_the_two_pass_fill(monkeypatch):
     dev = _dev()
     monkeypatch.setattr(neighbor, "_STASH", {})           # the default slot of 96 keys per atom

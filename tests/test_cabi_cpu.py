@@ -106,6 +106,119 @@ def test_banded_rbf_derivative_vs_finite_difference():
         assert np.allclose((rp - rm) / (2 * h), dr, rtol=1e-5, atol=1e-7)
 
 
+def _geometry_f64(cell, lo, hi, rc, n):
+    """The cell-list geometry of the neighbour search (csrc/neighbor_kernels.hip, nbr_make_geom) restated in scalar
+    np.float64 operations, one rounding each, in the routine's order: (22 doubles, 7 ints), or None for a geometry it
+    refuses."""
+    f = np.float64
+    rc = f(rc)
+    inv = [f(0.0)] * 9
+    with np.errstate(all="ignore"):
+        if cell is not None:
+            c = [f(v) for v in cell]
+            out_cell = list(c)
+            det = c[0] * (c[4] * c[8] - c[5] * c[7]) - c[1] * (c[3] * c[8] - c[5] * c[6]) + c[2] * (c[3] * c[7] - c[4] * c[6])
+            if not (abs(det) >= 1e-12) or not (abs(det) <= 1.0e300):
+                return None
+            inv = [(c[4] * c[8] - c[5] * c[7]) / det, (c[2] * c[7] - c[1] * c[8]) / det, (c[1] * c[5] - c[2] * c[4]) / det,
+                   (c[5] * c[6] - c[3] * c[8]) / det, (c[0] * c[8] - c[2] * c[6]) / det, (c[2] * c[3] - c[0] * c[5]) / det,
+                   (c[3] * c[7] - c[4] * c[6]) / det, (c[1] * c[6] - c[0] * c[7]) / det, (c[0] * c[4] - c[1] * c[3]) / det]
+        else:
+            out_cell = [f(1.0) if k % 4 == 0 else f(0.0) for k in range(9)]
+        nbins, reach, out_lo = [0] * 3, [0] * 3, [f(0.0)] * 3
+        for k in range(3):
+            if cell is not None:
+                h = f(1.0) / np.sqrt(inv[k] * inv[k] + inv[3 + k] * inv[3 + k] + inv[6 + k] * inv[6 + k])
+            else:
+                h = f(hi[k]) - f(lo[k]) + f(2e-6)
+            if not (h > 0.0) or not (h <= 1.0e300):
+                return None
+            q = np.floor(h / rc)
+            nbins[k] = max(1, 1024 if q > 1024.0 else int(q))
+            if cell is not None:
+                r = np.ceil(rc / (h / f(nbins[k])) - f(1e-12))
+                reach[k] = max(1, 9 if r > 9.0 else int(r))
+                if reach[k] > 8:
+                    return None
+            else:
+                out_lo[k] = f(lo[k]) - f(1e-6)
+                inv[4 * k] = f(nbins[k]) / h
+                reach[k] = 1
+        while nbins[0] * nbins[1] * nbins[2] > 8 * n + 64:
+            kmax = 0
+            for k in (1, 2):
+                if nbins[k] > nbins[kmax]:
+                    kmax = k
+            if nbins[kmax] <= 1:
+                break
+            nb = (nbins[kmax] + 1) // 2
+            if cell is None:
+                inv[4 * kmax] = inv[4 * kmax] * (f(nb) / f(nbins[kmax]))
+            nbins[kmax] = nb
+        return np.array(out_cell + inv + out_lo + [rc * rc], dtype=np.float64), nbins + reach + [0 if cell is None else 1]
+
+
+def _cube(a):
+    return [a, 0, 0, 0, a, 0, 0, 0, a]
+
+
+_GEOMETRY_CASES = {       # name: (cell or None, lo, hi, rc, atoms)
+    "cubic 10.86 A": (_cube(10.86), None, None, 5.0, 64),
+    "triclinic": ([9.3, 0.4, -0.7, 2.1, 11.2, 0.3, -1.6, 3.3, 14.9], None, None, 5.0, 96),
+    "cell smaller than the cutoff (reach 2)": (_cube(3.6), None, None, 5.0, 4),
+    "sheared cell smaller than the cutoff (reach above 2)": ([1.3, 0.2, 0, 0, 2.2, 0.1, 0.3, 0, 3.1], None, None, 5.0, 2),
+    "one atom in a 100 A cube, periodic": (_cube(100.0), None, None, 5.0, 1),
+    "one atom in a 100 A cube, open": (None, [0.0, 0.0, 0.0], [100.0, 100.0, 100.0], 5.0, 1),
+    "open box of a single atom": (None, [1.25, -3.5, 0.75], [1.25, -3.5, 0.75], 5.0, 1),
+}
+_GEOMETRY_REFUSED = {
+    "singular cell": ([4.0, 0, 0, 0, 4.0, 4.0, 0, 4.0, 4.0], None, None, 5.0, 8),
+    "reach 9": (_cube(0.6), None, None, 5.0, 8),
+    "NaN entry": ([10.0, 0, 0, 0, float("nan"), 0, 0, 0, 10.0], None, None, 5.0, 8),
+    "open box with an infinite corner": (None, [0.0, 0.0, 0.0], [3.0, float("inf"), 3.0], 5.0, 8),
+}
+
+
+def _host_geometry(lib, cell, lo, hi, rc, n):
+    arr = lambda v, k: None if v is None else (ctypes.c_double * k)(*v)
+    geom, grid = np.full(22, -7.0), np.full(7, -7, dtype=np.int32)
+    rcode = lib.hermnet_host_neighbor_geometry(arr(cell, 9), arr(lo, 3), arr(hi, 3), rc, n, geom.ctypes.data, grid.ctypes.data)
+    return rcode, geom, grid
+
+
+@pytest.mark.parametrize("name", sorted(_GEOMETRY_CASES))
+def test_neighbour_geometry_equals_its_float64_restatement_bit_for_bit(name):
+    """hermnet_host_neighbor_geometry runs the ONE geometry routine of the search on the host: all 29 values equal the
+    scalar float64 restatement above, bit for bit (no tolerance: every form of the search must bin alike)."""
+    cell, lo, hi, rc, n = _GEOMETRY_CASES[name]
+    rcode, geom, grid = _host_geometry(_lib.load(), cell, lo, hi, rc, n)
+    want_geom, want_grid = _geometry_f64(cell, lo, hi, rc, n)
+    assert rcode == 0
+    assert np.array_equal(geom.view(np.uint64), want_geom.view(np.uint64)), (geom, want_geom)
+    assert grid.tolist() == want_grid, (grid.tolist(), want_grid)
+    nb, reach = grid[:3], grid[3:6]
+    assert int(nb[0]) * int(nb[1]) * int(nb[2]) <= 8 * n + 64 and grid[6] == (cell is not None)
+    if "reach" in name:
+        assert 2 <= reach.max() <= 8
+    if "100 A" in name:       # 20 bins per axis, 72 allowed: eight rounds of the coarsening loop, the first largest axis first
+        assert nb.tolist() == [3, 3, 5]
+    if name == "open box of a single atom":
+        assert nb.tolist() == [1, 1, 1] and np.all(geom[[9, 13, 17]] == 1.0 / 2e-6)
+
+
+@pytest.mark.parametrize("name", sorted(_GEOMETRY_REFUSED))
+def test_neighbour_geometry_refuses_degenerate_cells_and_boxes(name):
+    cell, lo, hi, rc, n = _GEOMETRY_REFUSED[name]
+    assert _geometry_f64(cell, lo, hi, rc, n) is None
+    assert _host_geometry(_lib.load(), cell, lo, hi, rc, n)[0] == 1                  # HN_ERR_BAD_ARG
+    # ... as it does a call without its pointers, a cutoff that is not positive, and no atom
+    lib, good = _lib.load(), _GEOMETRY_CASES["cubic 10.86 A"]
+    assert _host_geometry(lib, None, None, None, 5.0, 8)[0] == 1 and _host_geometry(lib, None, [0.0] * 3, None, 5.0, 8)[0] == 1
+    assert _host_geometry(lib, good[0], None, None, 0.0, 8)[0] == 1 and _host_geometry(lib, good[0], None, None, float("nan"), 8)[0] == 1
+    assert _host_geometry(lib, good[0], None, None, 5.0, 0)[0] == 1
+    assert lib.hermnet_host_neighbor_geometry((ctypes.c_double * 9)(*good[0]), None, None, 5.0, 8, None, None) == 1
+
+
 def test_default_message_kernels_fit_their_register_budget(tmp_path):
     """The channel-per-lane backward must stay at 4 waves per SIMD (<= 128 VGPRs at 1024 threads) without scratch:
     a spill or a fifth-wave-less build is a silent 2x.  Checked on the code hipcc generates for gfx950 (no GPU)."""
