@@ -13,12 +13,21 @@ DDP for training, `example/dist_train.py:25,67`).  The build shards the hot path
     positions use the same exchange once per step, the energy is one scalar all-reduce.
 
 Every rank derives the complete plan from the global coordinates (the calculators have all
-coordinates anyway), so there is no negotiation step.  Two planners:
+coordinates anyway), so there is no negotiation step.  Every planner returns one `ShardPlan`:
 
-  * `partition_slab` (the production path): pure geometry on the device.  Owners = equal-count slabs;
-    the halo of a rank = the atoms within rc of its slab along the slab axis (periodic); the rank runs the
-    cutoff neighbour search ONLY over its owned + halo atoms and keeps the edges whose target it owns.  Cost
-    per rank ~ N / world; nothing of size E_global is ever built.
+  * the geometric planners (the production path): pure geometry on the device, nothing of size E_global is ever
+    built.  All three cut in the coordinate of `_cut_coordinates`, share the local order [interior | owned near a
+    face | halo] and build their plan in `_geometric_plan`; `slab_data` then lists, per step, the cutoff pairs among
+    the rank's owned + halo atoms whose target it owns (cost per rank ~ N / world).
+      - `plan_slab`: equal-count slabs along one axis; the halo of a rank = the atoms within rc + skin of its slab;
+      - `plan_blocks`: hierarchical equal-count cuts along up to three axes (boxes); the halo = the atoms within
+        rc + skin of the box along every cut axis.  Its cut rule differs from `plan_slab`'s when N is no multiple of
+        the world size: a (1, 1, world) grid is NOT the slab plan.  Both end in `_finish_plan` (exchange lists from
+        the owners and the reach masks);
+      - `plan_self_peer`: the slabs of `plan_slab` for `virtual` ranks, all living on ONE rank that exchanges ghost
+        rows with itself -- the production exchange with real payload on one GPU.
+    `partition_slab` / `partition_blocks` / `partition_self_peer` = the plan + its first `slab_data`; `SlabStepper`
+    keeps a plan along a trajectory while it is valid under the Verlet skin.
   * `partition` (planning from a GLOBAL edge list on the host: batches of molecules, tests): exact halos
     (only atoms that really send an edge across).
 """
@@ -165,17 +174,51 @@ class HaloOverlap(object):
     "run interior edges while the halo is in flight"), and mirrors that in its backward.
 
     plan       ExchangePlan in relation-row order
+    tile_rows  rows per tile of the node pre kernels at the model's width (what `bwd_first` is widened to)
     windows    [W,2] int32 (device): row ranges that contain every halo row (one per element block)
     fwd_early  [T,2] int32 (device): per relation the TARGET rows that read no halo row -- their messages run while the
                exchange is in flight; fwd_late: the rest of the relation's row block (incl. the halo rows themselves)
+    early_rows / late_rows: the rows in all `fwd_early` / `fwd_late` ranges (host ints)
     bwd_first  (device [k,2] int32, host [(lo, hi)]): the SOURCE rows whose gradients travel -- the halo windows widened to
                the node kernels' row tiles --, computed and sent first; bwd_rest: every other row, computed meanwhile.
     bwd_first_rows / bwd_rest_rows: the same cut at row granularity (the exact halo windows and their complement): what the
                "proj" form of the exchange uses (layer.py: projected rows travel, no node kernel runs on a subset of tiles)."""
 
-    def __init__(self, plan, windows, fwd_early=None, fwd_late=None, bwd_first=None, bwd_rest=None):
-        self.plan, self.windows = plan, windows
-        self.fwd_early, self.fwd_late, self.bwd_first, self.bwd_rest = fwd_early, fwd_late, bwd_first, bwd_rest
+    __slots__ = ("plan", "tile_rows", "windows", "fwd_early", "fwd_late", "early_rows", "late_rows", "bwd_first", "bwd_rest",
+                 "bwd_first_rows", "bwd_rest_rows")
+
+    def __init__(self, plan, graph, late_local, tile_rows):
+        """`plan`: the exchange lists in the row order of `graph`; `late_local` [N_loc] bool: the local atoms that may read
+        a halo row or are one (None: every atom).  Two small host reads (the T + 1 halo windows, the early / late ranges)."""
+        self.plan, self.tile_rows = plan, tile_rows
+        dev = graph.row_of_node.device
+        if graph.num_src:      # HTNet: the exchange and the node projection live in SOURCE rows (blocks of B rows per
+            Te, B = graph.T // graph.triadic_pairs, graph.block          # element), the messages land in virtual rows
+            src_rowptr = torch.arange(Te + 1, dtype=torch.int32, device=dev) * B
+            n_src = graph.num_src
+        else:
+            src_rowptr, n_src = graph.type_rowptr, graph.N
+        self.windows = HaloOverlap.row_windows(plan.recv_idx, src_rowptr, n_src)
+        late = late_local
+        if late is None:                  # no classification: every owned atom may read a halo row
+            late = torch.ones(graph.row_of_node.numel(), dtype=torch.bool, device=dev)
+        if plan.recv_idx.numel() == 0:    # no halo atom here: nothing is late (the rank still joins the exchange)
+            late = torch.zeros_like(late)
+        late_rows = graph.row_of_node.index_select(0, torch.nonzero(late).reshape(-1))
+        if graph.num_src:                 # a late atom is late in every pair relation of its element
+            P_ = graph.triadic_pairs
+            c, ii = late_rows // B, late_rows % B
+            k = torch.arange(P_, device=dev)
+            late_rows = ((c[:, None] * P_ + k[None, :]) * B + ii[:, None]).reshape(-1)
+            late_rows = late_rows[c.repeat_interleave(P_) < Te]          # (atoms of unlisted elements: no target rows)
+        self.fwd_early, self.fwd_late = HaloOverlap.target_ranges(late_rows, graph.type_rowptr)
+        el = torch.stack([self.fwd_early, self.fwd_late]).cpu()
+        self.early_rows = int((el[0, :, 1] - el[0, :, 0]).clamp(min=0).sum())
+        self.late_rows = int((el[1, :, 1] - el[1, :, 0]).clamp(min=0).sum())
+        win_host = self.windows.cpu().tolist()
+        self.bwd_first, self.bwd_rest = HaloOverlap.source_ranges(win_host, tile_rows, n_src, dev)
+        # the same cut at row granularity: the "proj" exchange (layer.py) runs no node kernel on a subset of the tiles
+        self.bwd_first_rows, self.bwd_rest_rows = HaloOverlap.source_ranges(win_host, 1, n_src, dev)
 
     @staticmethod
     def row_windows(halo_rows, type_rowptr, num_rows):
@@ -345,27 +388,52 @@ class SumAcrossRanks(torch.autograd.Function):
 
 
 class ShardPlan(object):
-    """What HVNet.forward needs to run one rank's share: see `partition`."""
+    """What HVNet.forward needs to run one rank's share.  Every field a plan can have is declared here (a misspelt
+    assignment raises); the planners (`partition`, `_geometric_plan`) pass what they know, `slab_data` refreshes
+    `has_in_edges` / `has_in_pairs` per step, the rest stays None."""
 
-    def __init__(self, rank, world, owned_global, halo_global, atom_plan, owned_mask, num_graphs, group=None):
-        self.rank, self.world = rank, world
+    __slots__ = ("rank", "world", "group", "num_graphs", "num_atoms_global", "owned_global", "halo_global", "owned_local",
+                 "local_global", "owned_mask", "late_local", "atom_plan", "halo_pos_local", "z_with_in_edges",
+                 "zz_with_in_edges", "has_in_edges", "has_in_pairs", "rc", "skin", "pos_ref", "z_local", "batch_local",
+                 "target_mask", "cell", "serves_slab", "virtual", "wrap_axis", "_row_plan", "_zl_index", "_graph_order",
+                 "_owned_rows")
+
+    def __init__(self, rank, world, owned_global, halo_global, atom_plan, owned_mask, num_graphs=1, group=None,
+                 num_atoms_global=None, owned_local=None, local_global=None, late_local=None, halo_pos_local=False,
+                 z_with_in_edges=None, zz_with_in_edges=None, has_in_edges=None, has_in_pairs=None, rc=None, skin=None,
+                 pos_ref=None, z_local=None, batch_local=None, target_mask=None, cell=None, serves_slab=None, virtual=None,
+                 wrap_axis=None):
+        self.rank, self.world, self.group = rank, world, group
         self.num_graphs = int(num_graphs)     # of the GLOBAL batch (a rank may own no atom of some graph)
+        self.num_atoms_global = num_atoms_global    # atoms of the whole structure (every atom has exactly one owner)
         self.owned_global = owned_global      # LongTensor: global ids of owned atoms in local order
-        self.halo_global = halo_global        # LongTensor: global ids of halo atoms, ascending
-        self.owned_local = None               # LongTensor: local ids of the owned atoms (set by `partition`)
-        self.local_global = None              # LongTensor: global id of every local atom
-        self.atom_plan = atom_plan            # ExchangePlan in local atom order
+        self.halo_global = halo_global        # LongTensor: global ids of halo atoms in local order
+        self.owned_local = owned_local        # LongTensor: local ids of the owned atoms
+        self.local_global = local_global      # LongTensor: global id of every local atom
         self.owned_mask = owned_mask          # BoolTensor [N_loc]
-        self.group = group
-        self.z_with_in_edges = None           # atomic numbers that receive >= 1 edge GLOBALLY (hermnet.py:56-57): a set
-        self.has_in_edges = None              # ... or the same as a device array [128] of 0/1 (slab plans)
-        self.zz_with_in_edges = None          # (target Z, source Z) pairs joined by >= 1 edge globally: a set ...
-        self.has_in_pairs = None              # ... or a device array [128 * 128] of 0/1 (slab plans)
+        self.late_local = late_local          # BoolTensor [N_loc]: local atoms that may READ a halo atom's row (or are halo
+                                              # atoms); the others' messages run while the halo exchange is in flight
+        self.atom_plan = atom_plan            # ExchangePlan in local atom order
+        self.halo_pos_local = halo_pos_local  # True: Data.pos already holds the halo atoms' coordinates (geometric plans)
+        self.z_with_in_edges = z_with_in_edges      # atomic numbers that receive >= 1 edge GLOBALLY (hermnet.py:56-57): a set
+        self.has_in_edges = has_in_edges            # ... or the same as a device array [128] of 0/1 (geometric plans)
+        self.zz_with_in_edges = zz_with_in_edges    # (target Z, source Z) pairs joined by >= 1 edge globally: a set ...
+        self.has_in_pairs = has_in_pairs            # ... or a device array [128 * 128] of 0/1 (geometric plans)
+        # geometric plans (`_geometric_plan`): what `slab_data` needs to list the pairs of the current coordinates
+        self.rc, self.skin = rc, skin         # the cutoff and the Verlet skin the halo was sized for
+        self.pos_ref = pos_ref                # [N,3]: the GLOBAL coordinates the plan was made from (`plan_moved`)
+        self.z_local, self.batch_local = z_local, batch_local       # [N_loc]: atomic numbers / graph ids (zeros)
+        self.target_mask = target_mask        # uint8 [N_loc]: `owned_mask` as the neighbour search takes it
+        self.cell = cell                      # [1,3,3] or None (open system)
+        # self-peer plans (`plan_self_peer`)
+        self.serves_slab = serves_slab        # LongTensor [N_loc]: the virtual slab every local row serves
+        self.virtual = virtual                # number of virtual slabs
+        self.wrap_axis = wrap_axis            # virtual == 1: the slab axis (a pair uses a ghost iff it crosses that boundary)
+        # caches
         self._row_plan = None                 # (row_of_node tensor, atom_plan in that row order, HaloOverlap)
         self._zl_index = None                 # ((element list, device), its index tensor) for `rel_active`
-        self.halo_pos_local = False           # True: Data.pos already holds the halo atoms' coordinates (slab plans)
-        self.late_local = None                # BoolTensor [N_loc]: local atoms that may READ a halo atom's row (or are halo
-                                              # atoms); the others' messages run while the halo exchange is in flight
+        self._graph_order = None              # (batch tensor, its version, perm, lengths) for `graph_order`
+        self._owned_rows = None               # (row_of_node tensor, row mask) for `owned_rows`
 
     @property
     def n_owned(self):
@@ -401,7 +469,7 @@ class ShardPlan(object):
     def graph_order(self, batch):
         """(perm, lengths): the local atoms sorted by graph id (stable) and the number of local atoms of each of the
         `num_graphs` graphs -- what an ordered per-graph reduction needs; cached per `batch` tensor (one sort per plan)."""
-        c = getattr(self, "_graph_order", None)
+        c = self._graph_order
         if c is None or c[0] is not batch or c[1] != batch._version:
             perm = torch.argsort(batch, stable=True)
             lengths = torch.bincount(batch, minlength=self.num_graphs)
@@ -411,20 +479,12 @@ class ShardPlan(object):
     def owned_rows(self, graph, rows):
         """[rows] float 0 / 1: the node rows (HVNet: graph.N; HTNet: its source rows) that hold an OWNED atom (halo atoms and
         padding rows: 0) -- the read-out's row mask on a shard; cached with the row layout."""
-        c = getattr(self, "_owned_rows", None)
+        c = self._owned_rows
         if c is None or c[0] is not graph.row_of_node or c[1].numel() != rows:
             m = torch.zeros(rows, dtype=torch.float32, device=graph.row_of_node.device)
             m.index_copy_(0, graph.row_of_node, self.owned_mask.to(torch.float32))
             c = self._owned_rows = (graph.row_of_node, m)
         return c[1]
-
-    @property
-    def num_atoms_global(self):
-        """Atoms of the whole structure (single-structure plans: every atom is owned by exactly one rank)."""
-        n = getattr(self, "_n_global", None)
-        if n is None:
-            raise RuntimeError("this plan does not know the size of the whole structure (set plan._n_global)")
-        return n
 
     def row_plan(self, row_of_node):
         """The atom exchange lists in the relation-row order of `row_of_node` (cached per tensor: the row layout of an
@@ -434,55 +494,23 @@ class ShardPlan(object):
         return self._row_plan[1]
 
     def halo_overlap(self, graph, tile_rows=64):
-        """`HaloOverlap` of this plan for the row layout of `graph` (cached with the row plan; one host read of the
-        T + 1 halo windows when it is made).  `tile_rows`: rows per tile of the node pre kernels at the model's width."""
-        plan = self.row_plan(graph.row_of_node)
+        """`HaloOverlap` of this plan for the row layout of `graph` (cached with the row plan).  `tile_rows`: rows per tile
+        of the node pre kernels at the model's width."""
+        rows = self.row_plan(graph.row_of_node)
         if self._row_plan[2] is None or self._row_plan[2].tile_rows != tile_rows:
-            dev = graph.row_of_node.device
-            if graph.num_src:      # HTNet: the exchange and the node projection live in SOURCE rows (blocks of B rows per
-                Te, B = graph.T // graph.triadic_pairs, graph.block          # element), the messages land in virtual rows
-                src_rowptr = torch.arange(Te + 1, dtype=torch.int32, device=dev) * B
-                n_src = graph.num_src
-            else:
-                src_rowptr, n_src = graph.type_rowptr, graph.N
-            win = HaloOverlap.row_windows(plan.recv_idx, src_rowptr, n_src)
-            ov = HaloOverlap(plan, win)
-            ov.tile_rows = tile_rows
-            if True:
-                late = self.late_local
-                if late is None:                  # no classification: every owned atom may read a halo row
-                    late = torch.ones(graph.row_of_node.numel(), dtype=torch.bool, device=dev)
-                if plan.recv_idx.numel() == 0:    # no halo atom here: nothing is late (the rank still joins the exchange)
-                    late = torch.zeros_like(late)
-                late_rows = graph.row_of_node.index_select(0, torch.nonzero(late).reshape(-1))
-                if graph.num_src:                 # a late atom is late in every pair relation of its element
-                    P_ = graph.triadic_pairs
-                    c, ii = late_rows // B, late_rows % B
-                    k = torch.arange(P_, device=dev)
-                    late_rows = ((c[:, None] * P_ + k[None, :]) * B + ii[:, None]).reshape(-1)
-                    late_rows = late_rows[c.repeat_interleave(P_) < Te]          # (atoms of unlisted elements: no target rows)
-                ov.fwd_early, ov.fwd_late = HaloOverlap.target_ranges(late_rows, graph.type_rowptr)
-                el = torch.stack([ov.fwd_early, ov.fwd_late]).cpu()          # (one more small host read per plan)
-                ov.early_rows = int((el[0, :, 1] - el[0, :, 0]).clamp(min=0).sum())
-                ov.late_rows = int((el[1, :, 1] - el[1, :, 0]).clamp(min=0).sum())
-                win_host = win.cpu().tolist()
-                ov.bwd_first, ov.bwd_rest = HaloOverlap.source_ranges(win_host, tile_rows, n_src, dev)
-                # the same cut at row granularity: the "proj" exchange (layer.py) runs no node kernel on a subset of the tiles
-                ov.bwd_first_rows, ov.bwd_rest_rows = HaloOverlap.source_ranges(win_host, 1, n_src, dev)
-            self._row_plan = self._row_plan[:2] + (ov,)
+            self._row_plan = self._row_plan[:2] + (HaloOverlap(rows, graph, self.late_local, tile_rows),)
         return self._row_plan[2]
 
     def to(self, device):
-        self.owned_global = self.owned_global.to(device)
-        self.halo_global = self.halo_global.to(device)
-        self.owned_mask = self.owned_mask.to(device)
-        self.owned_local = self.owned_local.to(device)
-        self.local_global = self.local_global.to(device)
-        if self.late_local is not None:
-            self.late_local = self.late_local.to(device)
+        """Moves every tensor field, the exchange lists included; the caches are keyed to tensors of the old device and go."""
+        for name in self.__slots__:
+            v = getattr(self, name)
+            if torch.is_tensor(v):
+                setattr(self, name, v.to(device))
         p = self.atom_plan
         self.atom_plan = ExchangePlan(p.send_idx.to(device), p.send_counts, p.recv_idx.to(device), p.recv_counts,
                                       p.group)
+        self._row_plan = self._zl_index = self._graph_order = self._owned_rows = None
         return self
 
 
@@ -569,42 +597,53 @@ def partition(data, rank, world, axis=None, group=None):
         if data.get("edge_shift") is not None:
             kw["edge_shift"] = data.edge_shift[torch.from_numpy(np.nonzero(emask)[0])]
     local = Data(**kw)
-    owned_mask = torch.from_numpy(is_owned.copy())
     num_graphs = int(data.batch.max()) + 1 if data.get("batch") is not None and n > 0 else 1
+    late = ~is_owned                                   # halo atoms, and the owned atoms that have a halo source
+    late[ltgt[~is_owned[lsrc]]] = True
+    z_np = data.atomic_number.cpu().numpy()
     plan = ShardPlan(rank, world, torch.from_numpy(owned), torch.from_numpy(np.sort(halo)),
                      ExchangePlan(torch.from_numpy(send_idx), send_counts, torch.from_numpy(recv_idx), recv_counts,
                                   group),
-                     owned_mask, num_graphs, group)
-    plan.owned_local = torch.from_numpy(np.nonzero(is_owned)[0])
-    plan.local_global = torch.from_numpy(local_ids.copy())
-    plan._n_global = int(n)
-    late = ~is_owned                                   # halo atoms, and the owned atoms that have a halo source
-    late[ltgt[~is_owned[lsrc]]] = True
-    plan.late_local = torch.from_numpy(late.copy())
-    z_np = data.atomic_number.cpu().numpy()
-    plan.z_with_in_edges = set(int(v) for v in np.unique(z_np[tgt]))
-    plan.zz_with_in_edges = set((int(a), int(b)) for a, b in np.unique(np.stack([z_np[tgt], z_np[src]], 1), axis=0))
+                     torch.from_numpy(is_owned.copy()), num_graphs, group, num_atoms_global=int(n),
+                     owned_local=torch.from_numpy(np.nonzero(is_owned)[0]), local_global=torch.from_numpy(local_ids.copy()),
+                     late_local=torch.from_numpy(late.copy()),
+                     z_with_in_edges=set(int(v) for v in np.unique(z_np[tgt])),
+                     zz_with_in_edges=set((int(a), int(b))
+                                          for a, b in np.unique(np.stack([z_np[tgt], z_np[src]], 1), axis=0)))
     local._hn_shard = plan
     return local, plan
 
 
-def _axis_coordinate(pos, cell, axis):
-    """(coordinate along the slab axis in [0,1) for periodic cells / Cartesian for open systems, axis, margin):
-    `margin` = rc-independent factor such that `rc * margin` is the cutoff expressed in that coordinate."""
+def _cut_coordinates(pos, cell, axes=None):
+    """{axis: (coordinate [N] float64, margin)} for every axis in `axes` (None: the one default slab axis -- the longest
+    cell vector / the largest extent of an open system).  The coordinate is what the planners cut and measure reach in:
+    fractional in [0,1) for periodic cells, Cartesian for open systems; `margin` = rc-independent factor such that
+    `rc * margin` is the cutoff expressed in that coordinate.  THE one place that computes it: ranks that disagreed in
+    the last bit would disagree about owners.  It is also where every geometric planner refuses a structure without atoms."""
+    if pos.size(0) == 0:
+        raise ValueError("cannot shard a structure without atoms")
     p64 = pos.detach().double()
-    if cell is not None:
-        c = cell.detach().double().reshape(-1, 3, 3)[0].cpu()
-        if axis is None:
-            axis = int(torch.argmax(c.norm(dim=1)))
-        inv = torch.linalg.inv(c)
-        col = inv[:, axis].to(p64.device)
+    if cell is None:
+        if axes is None:
+            axes = (int(torch.argmax(p64.max(0).values - p64.min(0).values)),)
+        return {a: (p64[:, a].clone(), 1.0) for a in axes}
+    c = cell.detach().double().reshape(-1, 3, 3)[0].cpu()
+    if axes is None:
+        axes = (int(torch.argmax(c.norm(dim=1))),)
+    inv = torch.linalg.inv(c)
+    out = {}
+    for a in axes:
+        col = inv[:, a].to(p64.device)
         # elementwise, fixed order: every rank must get bit-identical coordinates (no BLAS here)
         frac = p64[:, 0] * col[0] + p64[:, 1] * col[1] + p64[:, 2] * col[2]
-        return frac - torch.floor(frac), axis, float(inv[:, axis].norm())     # 1 / plane spacing
-    if axis is None:
-        ext = (p64.max(0).values - p64.min(0).values) if p64.size(0) > 0 else torch.zeros(3)
-        axis = int(torch.argmax(ext))
-    return p64[:, axis].clone(), axis, 1.0
+        out[a] = (frac - torch.floor(frac), float(inv[:, a].norm()))           # margin: 1 / plane spacing
+    return out
+
+
+def _axis_coordinate(pos, cell, axis):
+    """(coordinate along the slab axis, axis, margin) from `_cut_coordinates`; `axis` None: the default slab axis."""
+    (axis, (coord, margin)), = _cut_coordinates(pos, cell, None if axis is None else (axis,)).items()
+    return coord, axis, margin
 
 
 def slab_owner_device(pos, cell, world, axis=None):
@@ -652,55 +691,15 @@ def plan_slab(pos, atomic_number, cell, rc, rank, world, axis=None, group=None, 
     every source within rc of an owned atom is still a local atom: the plan stays valid and only the neighbour
     list is rebuilt (`slab_data`).  All peers' send lists come from ONE [world, N] mask; one host read (the
     2 x world counts)."""
-    dev = pos.device
-    n = pos.size(0)
     owner, coord, (lo, hi), axis, margin = slab_owner_device(pos, cell, world, axis)
-    periodic = cell is not None
     reach = (float(rc) + float(skin)) * margin * (1.0 + 1e-9) + 1e-12
     mine = owner == rank
     # near[p, a]: atom a lies within reach of slab p (atoms of slab p itself included)
-    near = _within_cutoff_of_slab(coord[None, :], lo[:, None], hi[:, None], reach, periodic)
-    halo_mask = near[rank] & ~mine
-    send_mask = near & mine[None, :]
-    send_mask[rank] = False
-    # receive: my halo grouped by owner (ascending id inside a group); send: for every peer, the atoms I own
-    # that lie within reach of ITS slab -- the same set and order the peer derives for its receive list
+    near = _within_cutoff_of_slab(coord[None, :], lo[:, None], hi[:, None], reach, cell is not None)
     # owned atoms that can have a source outside the slab: within `reach` of one of its faces (a source within rc of an
-    # atom further inside lies strictly between the faces, i.e. is owned -- also after moves of up to skin/2 each).
-    # They follow the interior atoms in the local order, so every relation's row block reads
-    # [interior | boundary | halo]: the messages into the interior rows run while the halo exchange is in flight.
+    # atom further inside lies strictly between the faces, i.e. is owned -- also after moves of up to skin/2 each)
     near_face = mine & ((coord - lo[rank] <= reach) | (hi[rank] - coord <= reach))
-    interior = torch.nonzero(mine & ~near_face).reshape(-1)
-    boundary = torch.nonzero(near_face).reshape(-1)
-    owned = torch.cat([interior, boundary])                                         # each part in ascending global id
-    halo = torch.nonzero(halo_mask).reshape(-1)                                     # ascending global id
-    local_ids = torch.cat([owned, halo])
-    n_owned = owned.numel()
-    g2l = torch.full((n,), -1, dtype=torch.long, device=dev)
-    g2l[local_ids] = torch.arange(local_ids.numel(), device=dev)
-    halo_owner = owner[halo]
-    recv_idx = g2l[halo[torch.argsort(halo_owner, stable=True)]]
-    pairs = torch.nonzero(send_mask)                                                # (peer, atom), peer-major
-    send_idx = g2l[pairs[:, 1]]
-    counts = torch.stack([torch.bincount(halo_owner, minlength=world),
-                          torch.bincount(pairs[:, 0], minlength=world)]).cpu().tolist()   # the host read of the plan
-    is_owned = torch.zeros(local_ids.numel(), dtype=torch.bool, device=dev)
-    is_owned[:n_owned] = True
-    plan = ShardPlan(rank, world, owned, halo, ExchangePlan(send_idx, counts[1], recv_idx, counts[0], group),
-                     is_owned, 1, group)
-    plan.owned_local = torch.arange(n_owned, device=dev)
-    plan.local_global = local_ids
-    plan._n_global = int(n)
-    plan.rc, plan.skin = float(rc), float(skin)
-    plan.pos_ref = pos.detach().clone()
-    plan.z_local = atomic_number[local_ids]
-    plan.batch_local = torch.zeros(local_ids.numel(), dtype=torch.long, device=dev)
-    plan.target_mask = is_owned.to(torch.uint8)
-    plan.cell = None if cell is None else cell.detach().reshape(1, 3, 3)
-    plan.halo_pos_local = True            # `slab_data` fills the halo coordinates itself
-    plan.late_local = torch.ones(local_ids.numel(), dtype=torch.bool, device=dev)
-    plan.late_local[:interior.numel()] = False
-    return plan
+    return _finish_plan(pos, atomic_number, cell, rc, skin, rank, world, group, owner, mine, near, near_face)
 
 
 def plan_self_peer(pos, atomic_number, cell, rc, virtual=2, axis=None, group=None, skin=0.0):
@@ -737,34 +736,17 @@ def plan_self_peer(pos, atomic_number, cell, rc, virtual=2, axis=None, group=Non
     near_face = (coord - lo_a <= reach) | (hi_a - coord <= reach)
     interior = torch.nonzero(~near_face).reshape(-1)
     boundary = torch.nonzero(near_face).reshape(-1)
-    owned = torch.cat([interior, boundary])
-    local_ids = torch.cat([owned, pairs[:, 1]])
+    local_ids = torch.cat([interior, boundary, pairs[:, 1]])
     g2l = torch.empty(n, dtype=torch.long, device=dev)
-    g2l[owned] = torch.arange(n, device=dev)
+    g2l[local_ids[:n]] = torch.arange(n, device=dev)
     k = int(pairs.size(0))                                                         # the host read of the plan
     send_idx = g2l.index_select(0, pairs[:, 1])
     recv_idx = n + torch.arange(k, device=dev)
-    is_owned = torch.zeros(n + k, dtype=torch.bool, device=dev)
-    is_owned[:n] = True
-    plan = ShardPlan(0, 1, owned, pairs[:, 1].contiguous(), ExchangePlan(send_idx, [k], recv_idx, [k], group),
-                     is_owned, 1, group)
-    plan.owned_local = torch.arange(n, device=dev)
-    plan.local_global = local_ids
-    plan._n_global = int(n)
-    plan.rc, plan.skin = float(rc), float(skin)
-    plan.pos_ref = pos.detach().clone()
-    plan.z_local = atomic_number[local_ids]
-    plan.batch_local = torch.zeros(n + k, dtype=torch.long, device=dev)
-    plan.target_mask = is_owned.to(torch.uint8)
-    plan.cell = None if cell is None else cell.detach().reshape(1, 3, 3)
-    plan.halo_pos_local = True
-    plan.late_local = torch.ones(n + k, dtype=torch.bool, device=dev)
-    plan.late_local[:interior.numel()] = False
     # the virtual slab every local row SERVES: an owned row its own, a ghost row the slab it was made for
-    plan.serves_slab = torch.cat([slab.index_select(0, owned), pairs[:, 0]]).contiguous()
-    plan.virtual = V
-    plan.wrap_axis = axis if V == 1 else None
-    return plan
+    serves = torch.cat([slab.index_select(0, local_ids[:n]), pairs[:, 0]]).contiguous()
+    return _geometric_plan(pos, atomic_number, cell, rc, skin, 0, 1, group, local_ids, n, interior.numel(),
+                           ExchangePlan(send_idx, [k], recv_idx, [k], group),
+                           serves_slab=serves, virtual=V, wrap_axis=axis if V == 1 else None)
 
 
 def partition_self_peer(pos, atomic_number, cell, rc, virtual=2, axis=None, group=None, reference_compat=False, skin=0.0):
@@ -832,25 +814,10 @@ def plan_blocks(pos, atomic_number, cell, rc, rank, world, grid=None, group=None
     grid = tuple(int(g_) for g_ in grid)
     if grid[0] * grid[1] * grid[2] != world:
         raise ValueError("grid %r does not multiply to the world size %d" % (grid, world))
-    periodic = cell is not None
-    p64 = pos.detach().double()
-    coords, margins = [], []
-    if periodic:
-        c = cell.detach().double().reshape(-1, 3, 3)[0].cpu()
-        inv = torch.linalg.inv(c)
-        for a in range(3):
-            col = inv[:, a].to(dev)
-            # elementwise, fixed order: every rank must get bit-identical coordinates (no BLAS here)
-            fr = p64[:, 0] * col[0] + p64[:, 1] * col[1] + p64[:, 2] * col[2]
-            coords.append(fr - torch.floor(fr))
-            margins.append(float(inv[:, a].norm()))
-    else:
-        for a in range(3):
-            coords.append(p64[:, a].clone())
-            margins.append(1.0)
+    cut = _cut_coordinates(pos, cell, range(3))
     owner = torch.zeros(n, dtype=torch.long, device=dev)
     for a in range(3):                                    # hierarchical equal-count cuts
-        owner = owner * grid[a] + _equal_count_cuts(coords[a], owner, grid[a])
+        owner = owner * grid[a] + _equal_count_cuts(cut[a][0], owner, grid[a])
     mine = owner == rank
     # every rank's box along the cut axes: [lo, hi] of its atoms' coordinates (nan for an empty rank: reaches nothing)
     near = torch.ones(world, n, dtype=torch.bool, device=dev)
@@ -859,19 +826,25 @@ def plan_blocks(pos, atomic_number, cell, rc, rank, world, grid=None, group=None
     for a in range(3):
         if grid[a] == 1:
             continue
-        reach = (float(rc) + float(skin)) * margins[a] * (1.0 + 1e-9) + 1e-12
-        lo = big.clone().scatter_reduce(0, owner, coords[a], "amin")
-        hi = (-big).clone().scatter_reduce(0, owner, coords[a], "amax")
+        coord, margin = cut[a]
+        reach = (float(rc) + float(skin)) * margin * (1.0 + 1e-9) + 1e-12
+        lo = big.clone().scatter_reduce(0, owner, coord, "amin")
+        hi = (-big).clone().scatter_reduce(0, owner, coord, "amax")
         empty = lo > hi
         lo = torch.where(empty, torch.full_like(lo, float("nan")), lo)
         hi = torch.where(empty, torch.full_like(hi, float("nan")), hi)
-        near &= _within_cutoff_of_slab(coords[a][None, :], lo[:, None], hi[:, None], reach, periodic)
-        near_face |= mine & ((coords[a] - lo[rank] <= reach) | (hi[rank] - coords[a] <= reach))
+        near &= _within_cutoff_of_slab(coord[None, :], lo[:, None], hi[:, None], reach, cell is not None)
+        near_face |= mine & ((coord - lo[rank] <= reach) | (hi[rank] - coord <= reach))
     return _finish_plan(pos, atomic_number, cell, rc, skin, rank, world, group, owner, mine, near, near_face)
 
 
 def _finish_plan(pos, atomic_number, cell, rc, skin, rank, world, group, owner, mine, near, near_face):
-    """Local order, exchange lists and plan object from the owners and the geometric reach masks (`plan_blocks`)."""
+    """The shared tail of `plan_slab` and `plan_blocks`: local order, exchange lists and the plan from the owners and the
+    geometric reach masks -- owner [N], mine [N] = owner == rank, near [world, N] (atom a lies within reach of rank p's
+    slab / box, its own atoms included), near_face [N] (my atoms within reach of a face of my slab / box).
+    Receive: my halo grouped by owner (ascending id inside a group); send: for every peer, the atoms I own that lie within
+    reach of ITS slab -- the same set and order the peer derives for its receive list.  All peers' send lists come from
+    ONE [world, N] mask; one host read (the 2 x world counts)."""
     dev = pos.device
     n = pos.size(0)
     halo_mask = near[rank] & ~mine
@@ -879,10 +852,8 @@ def _finish_plan(pos, atomic_number, cell, rc, skin, rank, world, group, owner, 
     send_mask[rank] = False
     interior = torch.nonzero(mine & ~near_face).reshape(-1)
     boundary = torch.nonzero(near_face).reshape(-1)
-    owned = torch.cat([interior, boundary])
     halo = torch.nonzero(halo_mask).reshape(-1)
-    local_ids = torch.cat([owned, halo])
-    n_owned = owned.numel()
+    local_ids = torch.cat([interior, boundary, halo])                               # each part in ascending global id
     g2l = torch.full((n,), -1, dtype=torch.long, device=dev)
     g2l[local_ids] = torch.arange(local_ids.numel(), device=dev)
     halo_owner = owner[halo]
@@ -891,23 +862,31 @@ def _finish_plan(pos, atomic_number, cell, rc, skin, rank, world, group, owner, 
     send_idx = g2l[pairs[:, 1]]
     counts = torch.stack([torch.bincount(halo_owner, minlength=world),
                           torch.bincount(pairs[:, 0], minlength=world)]).cpu().tolist()   # the host read of the plan
-    is_owned = torch.zeros(local_ids.numel(), dtype=torch.bool, device=dev)
+    return _geometric_plan(pos, atomic_number, cell, rc, skin, rank, world, group, local_ids,
+                           interior.numel() + boundary.numel(), interior.numel(),
+                           ExchangePlan(send_idx, counts[1], recv_idx, counts[0], group))
+
+
+def _geometric_plan(pos, atomic_number, cell, rc, skin, rank, world, group, local_ids, n_owned, n_interior, exchange,
+                    **self_peer):
+    """The `ShardPlan` of ONE structure planned from its coordinates (`plan_slab`, `plan_blocks`, `plan_self_peer`).
+    `local_ids`: global id of every local atom in the local order [interior | owned near a face | halo], so every
+    relation's row block reads the same way: the messages into the interior rows run while the halo exchange is in flight,
+    and "rows that wait for the exchange" are T windows for the node kernels and a row range per relation for the message
+    kernels.  Carries what `slab_data` needs for every later step (`halo_pos_local`: it fills the halo coordinates itself)."""
+    dev = pos.device
+    n_local = local_ids.numel()
+    is_owned = torch.zeros(n_local, dtype=torch.bool, device=dev)
     is_owned[:n_owned] = True
-    plan = ShardPlan(rank, world, owned, halo, ExchangePlan(send_idx, counts[1], recv_idx, counts[0], group),
-                     is_owned, 1, group)
-    plan.owned_local = torch.arange(n_owned, device=dev)
-    plan.local_global = local_ids
-    plan._n_global = int(n)
-    plan.rc, plan.skin = float(rc), float(skin)
-    plan.pos_ref = pos.detach().clone()
-    plan.z_local = atomic_number[local_ids]
-    plan.batch_local = torch.zeros(local_ids.numel(), dtype=torch.long, device=dev)
-    plan.target_mask = is_owned.to(torch.uint8)
-    plan.cell = None if cell is None else cell.detach().reshape(1, 3, 3)
-    plan.halo_pos_local = True            # `slab_data` fills the halo coordinates itself
-    plan.late_local = torch.ones(local_ids.numel(), dtype=torch.bool, device=dev)
-    plan.late_local[:interior.numel()] = False
-    return plan
+    late = torch.ones(n_local, dtype=torch.bool, device=dev)
+    late[:n_interior] = False
+    return ShardPlan(rank, world, local_ids[:n_owned], local_ids[n_owned:], exchange, is_owned, 1, group,
+                     num_atoms_global=int(pos.size(0)), owned_local=torch.arange(n_owned, device=dev),
+                     local_global=local_ids, late_local=late, halo_pos_local=True, rc=float(rc), skin=float(skin),
+                     pos_ref=pos.detach().clone(), z_local=atomic_number[local_ids],
+                     batch_local=torch.zeros(n_local, dtype=torch.long, device=dev),
+                     target_mask=is_owned.to(torch.uint8), cell=None if cell is None else cell.detach().reshape(1, 3, 3),
+                     **self_peer)
 
 
 def partition_blocks(pos, atomic_number, cell, rc, rank, world, grid=None, group=None, reference_compat=False, skin=0.0):
@@ -917,15 +896,21 @@ def partition_blocks(pos, atomic_number, cell, rc, rank, world, grid=None, group
 
 
 def slab_data(plan, pos, reference_compat=False, capacity=None, want_moved=False):
-    """This rank's `Data` for the current coordinates under a plan that is still valid (`plan_moved` says whether it
-    is): the cutoff pairs among the local atoms whose TARGET is owned, listed directly by the neighbour search
+    """This rank's `Data` for the current coordinates under a valid plan: `_slab_step` without its two flags."""
+    return _slab_step(plan, pos, reference_compat, capacity, want_moved)[0]
+
+
+def _slab_step(plan, pos, reference_compat=False, capacity=None, want_moved=False):
+    """(local, moved, list_bad): this rank's `Data` for the current coordinates under a plan that is still valid
+    (`plan_moved` says whether it is) and two 0-d device flags for `SlabStepper`.  `local`: the cutoff pairs among the local atoms whose TARGET is owned, listed directly by the neighbour search
     (`target_mask`; nothing of the other pairs is built or filtered afterwards).  Halo rows of `pos` hold the atoms'
     coordinates (every rank has them all): no coordinate exchange in the forward pass, HVNet.forward only routes the
     halo rows' force contributions back to the owners (`HaloGradReturn`).  One host read (the edge count of the
     search) -- or none: with `capacity` (periodic cells on the GPU) the list is padded to that many columns with NULL edges
     (`neighbor.neighbor_search_padded`), `local._hn_edge_count` holds (E, flags) on the device, and the caller checks
-    them when it copies the step's results to the host anyway (`SlabStepper.check`).  `want_moved`: `local._hn_moved` =
-    `plan_moved(plan, pos)` (on the GPU from the same launch as the relation flags)."""
+    them when it copies the step's results to the host anyway (`SlabStepper.check`).  `moved` = `plan_moved(plan, pos)` if
+    `want_moved` (on the GPU from the same launch as the relation flags), else None; `list_bad`: some rank's padded list is
+    incomplete (reduced with the relation flags: the same on every rank)."""
     from .neighbor import neighbor_search, neighbor_search_padded
     dev = pos.device
     pos_l = pos.detach().index_select(0, plan.local_global)
@@ -943,7 +928,7 @@ def slab_data(plan, pos, reference_compat=False, capacity=None, want_moved=False
             # structure.  The local order is owned-then-halo, so the cap is applied on global ids here (the capped list
             # of a shard is then exactly the unsharded capped list restricted to the owned targets).
             ei = _cap_by_global_source(ei, plan.local_global, int(plan.pos_ref.size(0)), 32)
-    serves = getattr(plan, "serves_slab", None)
+    serves = plan.serves_slab
     if serves is not None:
         # self-peer plan: an atom near a cut exists twice among the local rows (its owned row and a ghost row per slab it
         # reaches); a pair j -> i is kept through the ONE instance of j that serves i's virtual slab (the owned row when both
@@ -967,7 +952,6 @@ def slab_data(plan, pos, reference_compat=False, capacity=None, want_moved=False
     # hermnet.py:56-57: a relation is skipped when NO atom of its element receives an edge anywhere in the structure;
     # kept on the device (the relation build takes the flags as a device array: no host read per step)
     # (flags per (target element, source element): HTNet's relations are skipped pair-wise; HVNet reads the row maxima)
-    # (the NULL edges of a padded list -- endpoints -1 -- raise the spare slot behind the table)
     # (slot 128 * 128: where the NULL edges of a padded list -- endpoints -1 -- land; slot 128 * 128 + 1: "this rank's padded
     # list is incomplete", so that the SAME reduction tells every rank whether the step has to be repeated anywhere)
     moved = None
@@ -1004,13 +988,10 @@ def slab_data(plan, pos, reference_compat=False, capacity=None, want_moved=False
             has_in = h.to(dev)
         else:
             dist.all_reduce(has_in, op=dist.ReduceOp.MAX, group=plan.group)
-    local._hn_list_bad = has_in[128 * 128 + 1]               # 0-d, on the device, the same on every rank
-    local._hn_moved = moved
-    has_in = has_in[:128 * 128]
-    plan.has_in_pairs = has_in
-    plan.has_in_edges = has_in.view(128, 128).amax(dim=1)
+    plan.has_in_pairs = has_in[:128 * 128]
+    plan.has_in_edges = plan.has_in_pairs.view(128, 128).amax(dim=1)
     local._hn_shard = plan
-    return local
+    return local, moved, has_in[128 * 128 + 1]
 
 
 def _cap_by_global_source(edge_index, local_global, n_global, cap):
@@ -1086,8 +1067,7 @@ class SlabStepper(object):
         self.plan = None
         self.replans = 0
         self.repeats = 0                 # steps that `check` asked to be taken again
-        self._cell_key = None
-        self._z_key = (None, None)
+        self._watched = (None, None)     # (tensor, version) of the cell and of the atomic numbers at the last call
         self._capacity = None            # columns of the next padded list (None: exact search)
         self._pending = None             # (moved flag [0-d bool], total [2] or None) of the step not checked yet
         self._force_replan = False
@@ -1108,12 +1088,12 @@ class SlabStepper(object):
 
     def _exact(self, pos):
         from .neighbor import padded_capacity
-        local = slab_data(self.plan, pos, self.reference_compat)
+        local, _, bad = _slab_step(self.plan, pos, self.reference_compat)
         self._pending = None
         if self.deferred and self.cell is not None and pos.is_cuda:
             self._capacity = padded_capacity(int(local.edge_index.size(1)))     # (the count is on the host already)
             # (another rank may be on a padded list that turns out incomplete: every rank reads the same reduced flag)
-            self._pending = (plan_moved(self.plan, pos), None, local._hn_list_bad)
+            self._pending = (plan_moved(self.plan, pos), None, bad)
         return local, self.plan
 
     def check(self):
@@ -1144,18 +1124,17 @@ class SlabStepper(object):
             self.repeats += 1
         return ok
 
+    def _watched_changed(self):
+        """The cell (NPT: the slab bounds move) or the atomic numbers (a species swap: `plan.z_local`) were replaced, edited
+        in place, or the cell came or went since the last call; remembers the present ones."""
+        now = tuple(None if t is None else (t, t._version) for t in (self.cell, self.z))
+        was, self._watched = self._watched, now
+        return any((a is None) != (b is None) or (a is not None and (a[0] is not b[0] or a[1] != b[1]))
+                   for a, b in zip(now, was))
+
     def __call__(self, pos):
-        # (a cell that was replaced or edited in place -- NPT -- moves the slab bounds: plan again)
-        cell_key = None if self.cell is None else (self.cell, self.cell._version)
-        z_key = (self.z, self.z._version)          # an in-place species swap changes plan.z_local
-        if self.plan is not None and (z_key[0] is not self._z_key[0] or z_key[1] != self._z_key[1]):
+        if self._watched_changed():
             self.plan = None
-        self._z_key = z_key
-        if self.plan is not None and (cell_key is None) != (self._cell_key is None):
-            self.plan = None
-        if self.plan is not None and cell_key is not None and (cell_key[0] is not self._cell_key[0] or cell_key[1] != self._cell_key[1]):
-            self.plan = None
-        self._cell_key = cell_key
         if self.plan is None or self.plan.pos_ref.shape != pos.shape or self._force_replan:
             self._replan(pos)
             return self._exact(pos)
@@ -1165,8 +1144,7 @@ class SlabStepper(object):
                     self._replan(pos)
                 return self._exact(pos)
             # optimistic: the plan as it is, the list padded; both flags stay on the device until `check`
-            local = slab_data(self.plan, pos, self.reference_compat, capacity=self._capacity, want_moved=True)
-            moved, bad = local._hn_moved, local._hn_list_bad
+            local, moved, bad = _slab_step(self.plan, pos, self.reference_compat, capacity=self._capacity, want_moved=True)
             if self._pending is not None:
                 # several steps between two `check()`s: the flags are STICKY -- an earlier step that was invalid keeps the
                 # answer False (two tiny launches, only on this path; the counts are the latest list's)

@@ -743,6 +743,102 @@ def test_self_peer_plan_lists_every_pair_once_through_the_right_instance():
         assert not bool(plan.late_local[tgt[cross]].logical_not().any())      # only late rows read ghosts
 
 
+# ---------------------------------------------------------------------------------------------
+# The plan object and what the planners share.
+# ---------------------------------------------------------------------------------------------
+def _one_plan_per_planner():
+    """{planner: (local, plan)} on the host: rank 1 of 2 of the 108-atom alloy (self-peer: its one rank)."""
+    from hermnet_amd.sharding import partition, partition_blocks, partition_self_peer, partition_slab
+    d = Golden("alloy108").data()
+    geo = (d.pos, d.atomic_number, d.cell, 5.0)
+    return {"partition": partition(d, 1, 2), "slab": partition_slab(*geo, 1, 2, skin=0.5),
+            "blocks": partition_blocks(*geo, 1, 2, grid=(1, 2, 1)), "self_peer": partition_self_peer(*geo, virtual=2)}
+
+
+def _tensors_in(v):
+    if torch.is_tensor(v):
+        yield v
+    elif isinstance(v, (tuple, list)):
+        for item in v:
+            yield from _tensors_in(item)
+
+
+def test_shard_plan_declares_its_fields_and_moves_all_of_them():
+    """A `ShardPlan` takes no attribute it does not declare (a misspelt field raises instead of creating a new one), and
+    `to()` leaves no tensor behind: every declared field, the exchange lists and whatever a cache holds.  The "meta" device
+    is the one other device a host has."""
+    from hermnet_amd.sharding import ShardPlan
+    for planner, (local, plan) in _one_plan_per_planner().items():
+        with pytest.raises(AttributeError):
+            plan.serves_slabs = None
+        with pytest.raises(AttributeError):
+            plan._n_global = 108
+        assert plan.num_atoms_global == 108
+        plan.graph_order(local.batch)                               # a cache that holds tensors
+        before = [name for name in ShardPlan.__slots__ if any(True for _ in _tensors_in(getattr(plan, name)))]
+        assert {"owned_global", "halo_global", "owned_local", "local_global", "owned_mask", "late_local", "_graph_order"} <= set(before)
+        if planner != "partition":
+            assert {"pos_ref", "z_local", "batch_local", "target_mask", "cell", "has_in_edges", "has_in_pairs"} <= set(before)
+        assert ("serves_slab" in before) == (planner == "self_peer")
+        assert plan.to("meta") is plan
+        for name in ShardPlan.__slots__:
+            for t in _tensors_in(getattr(plan, name)):
+                assert t.device.type == "meta", (planner, name)
+        assert plan.atom_plan.send_idx.device.type == plan.atom_plan.recv_idx.device.type == "meta"
+        assert plan.owned_global.shape == plan.owned_local.shape and plan.local_global.shape == plan.owned_mask.shape
+
+
+def test_geometric_planners_refuse_a_structure_without_atoms():
+    from hermnet_amd.sharding import plan_blocks, plan_self_peer, plan_slab
+    pos, z = torch.zeros(0, 3), torch.zeros(0, dtype=torch.long)
+    for cell in (torch.eye(3) * 10.0, None):
+        with pytest.raises(ValueError, match="without atoms"):
+            plan_slab(pos, z, cell, 5.0, 0, 2)
+        with pytest.raises(ValueError, match="without atoms"):
+            plan_blocks(pos, z, cell, 5.0, 0, 2, grid=(1, 2, 1))
+        with pytest.raises(ValueError, match="without atoms"):
+            plan_self_peer(pos, z, cell, 5.0, virtual=2)
+
+
+def test_cut_coordinates_of_a_triclinic_cell_are_the_fixed_order_expression():
+    """The coordinate every planner cuts in, for all three axes of a triclinic cell: frac_a = x inv[0,a] + y inv[1,a] +
+    z inv[2,a] in float64, summed left to right, wrapped into [0, 1); margin = |column a of the inverse cell| -- restated
+    here with numpy, bit for bit (ranks that disagreed in the last bit would disagree about owners)."""
+    from hermnet_amd.sharding import _axis_coordinate, _cut_coordinates
+    cell = torch.tensor([[11.0, 0.3, -0.2], [1.7, 9.5, 0.4], [-2.3, 0.9, 13.1]])
+    pos = (torch.rand(257, 3, generator=torch.Generator().manual_seed(11)) * 40.0 - 12.0)      # also outside the cell
+    inv = torch.linalg.inv(cell.double()).numpy()
+    p = pos.double().numpy()
+    cut = _cut_coordinates(pos, cell.reshape(1, 3, 3), range(3))
+    assert sorted(cut) == [0, 1, 2]
+    for a in range(3):
+        frac = p[:, 0] * inv[0, a] + p[:, 1] * inv[1, a] + p[:, 2] * inv[2, a]
+        coord, margin = cut[a]
+        assert coord.dtype == torch.float64 and torch.equal(coord, torch.from_numpy(frac - np.floor(frac)))
+        # (a host float that only scales the reach, not part of the bit-identical coordinate: a three-term norm to 4 ulp)
+        assert abs(margin - float(np.linalg.norm(inv[:, a]))) <= 4 * np.finfo(np.float64).eps * margin
+        one, axis, one_margin = _axis_coordinate(pos, cell, a)
+        assert axis == a and one_margin == margin and torch.equal(one, coord)
+    assert _axis_coordinate(pos, cell, None)[1] == 2                 # default: the longest cell vector
+    open_cut = _cut_coordinates(pos, None, range(3))
+    assert all(torch.equal(open_cut[a][0], pos[:, a].double()) and open_cut[a][1] == 1.0 for a in range(3))
+
+
+def test_slab_data_keeps_its_step_flags_off_the_data():
+    """The displacement flag and the incomplete-list flag of a step go to `SlabStepper` as return values of the internal
+    form; the `Data` carries the plan (and, padded, the edge count) only."""
+    from hermnet_amd.sharding import _slab_step, slab_data
+    d = Golden("alloy108").data()
+    local, plan = _one_plan_per_planner()["slab"]
+    for again in (slab_data(plan, d.pos), slab_data(plan, d.pos, want_moved=True)):
+        assert "_hn_moved" not in again and "_hn_list_bad" not in again
+        assert again._hn_shard is plan and torch.equal(again.edge_index, local.edge_index)
+    step, moved, bad = _slab_step(plan, d.pos + 0.3, want_moved=True)
+    assert "_hn_moved" not in step and "_hn_list_bad" not in step
+    assert bool(moved) and not bool(bad)                            # 0.3 A along every axis > skin / 2 = 0.25 A
+    assert _slab_step(plan, d.pos)[1] is None
+
+
 def _htnet_worker(rank, world, port, out, planner):
     sys.path.insert(0, HERE)
     sys.path.insert(0, os.path.dirname(HERE))
