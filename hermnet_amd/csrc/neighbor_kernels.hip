@@ -265,17 +265,22 @@ __global__ __launch_bounds__(kBlock) void nbr_pairs_kernel(const double* __restr
           if (hit) {
             const int S[3] = {img[0] - wrap[3 * j] + wrap[3 * i], img[1] - wrap[3 * j + 1] + wrap[3 * i + 1],
                               img[2] - wrap[3 * j + 2] + wrap[3 * i + 2]};
-            if (S[0] < -kMaxImg || S[0] > kMaxImg || S[1] < -kMaxImg || S[1] > kMaxImg || S[2] < -kMaxImg ||
-                S[2] > kMaxImg)
-              atomicOr(overflow, 1);
+            const bool over = S[0] < -kMaxImg || S[0] > kMaxImg || S[1] < -kMaxImg || S[1] > kMaxImg || S[2] < -kMaxImg ||
+                              S[2] > kMaxImg;
+            if (over) atomicOr(overflow, 1);
             const unsigned long long code =
                 (unsigned long long)(((S[0] + kMaxImg) * kCode + (S[1] + kMaxImg)) * kCode + (S[2] + kMaxImg));
             // position inside the atom's key range: hits of earlier lanes first (the keys are sorted afterwards,
             // so only "each slot written once" matters)
             const int slot = __popcll(m & ((1ull << lane) - 1ull));
+            // A shift outside the code's range (flag bit 0) has no key: its code would carry into the neighbouring axis
+            // (S = (0, 0, 9) reads back as (0, 1, -8), a pair of this atom with a shift it does not have) or into the
+            // pair field.  Such a hit takes a key from the top of the range instead, one per position of the atom's
+            // run: above every real key (keys_fit), unique for the rank sort, and decoded as a NULL edge.
             if (FILL || n + slot < stash)
-              keys[out + slot] = ((unsigned long long)i * (unsigned long long)N + (unsigned long long)j) *
-                                     (unsigned long long)(kCode * kCode * kCode) + code;
+              keys[out + slot] = over ? ~0ull - (unsigned long long)(n + slot)
+                                      : ((unsigned long long)i * (unsigned long long)N + (unsigned long long)j) *
+                                            (unsigned long long)(kCode * kCode * kCode) + code;
           }
           const int nh = __popcll(m);
           out += nh;
@@ -314,8 +319,9 @@ __global__ __launch_bounds__(kBlock) void nbr_sort_decode_kernel(const unsigned 
     const int code = (int)(key - pair * c3);
     const unsigned long long ii = pair / (unsigned long long)N;
     const long j = (long)(pair - ii * (unsigned long long)N);
-    // a key whose image shift left the code's range (flag bit 0) has spilled into the pair field: the pair it decodes to is
-    // not this atom's -- such a column becomes a NULL edge, never an index that a later kernel would follow out of bounds
+    // a key whose image shift left the code's range (flag bit 0) lies above every real key (nbr_pairs_kernel): the pair it
+    // decodes to is not this atom's -- such a column becomes a NULL edge, never an index that a later kernel would follow
+    // out of bounds, and never a pair with a shift it does not have
     const bool ok = ii == (unsigned long long)i;
     edge_index[e] = ok ? (swap_rows ? j : (long)i) : -1;
     edge_index[E + e] = ok ? (swap_rows ? (long)i : j) : -1;

@@ -139,7 +139,10 @@ typedef struct hn_graph {
  * between the two calls, the caller provides `capacity` columns; the pairs found fill the first E of them, the rest
  * become NULL edges (-1, -1; shift 0), and total_device = (E, flags) is written for a read at the END of the step
  * (flags as above, plus bit 2: E > capacity).  With bit 1 or 2 set the list is incomplete: repeat the search in its
- * two-call form with a larger capacity.  hermnet_build_relations files NULL edges behind every row (they are in no CSR /
+ * two-call form with a larger capacity.  With bit 0 set it is incomplete too: E counts every pair, and a pair whose
+ * shift has a component beyond +-8 takes a NULL edge at the end of its atom's columns -- every other column is a pair
+ * with the shift it has; the host list answers such coordinates.
+ * hermnet_build_relations files NULL edges behind every row (they are in no CSR /
  * CSC segment), so every kernel of the step runs on the padded arrays with num_edges = capacity -- a fixed launch
  * geometry: search + step can be captured into ONE hipGraph that stays valid across list rebuilds.  Call after
  * hermnet_neighbor_count on the same workspace. */
