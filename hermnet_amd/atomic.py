@@ -12,11 +12,10 @@
 Refused (NotImplementedError): atom-sharded data, HTNet, train() / create_graph.  (With `trn_mean` on a batch of several
 graphs the call reads the host -- a bincount -- and cannot be captured into a hipGraph; without it nothing does.)
 """
-import copy
-
 import torch
 
 from .ops import AtomSink
+from .stress import evaluate_with_sink
 
 
 def atom_properties(model, data, *, virials=True, trn_mean=0.0):
@@ -29,17 +28,8 @@ def atom_properties(model, data, *, virials=True, trn_mean=0.0):
                            % pos.device)
     if model.training:
         model.eval()
-    d = copy.copy(data)
-    if not (pos.requires_grad and pos.is_leaf):
-        pos = pos.detach().requires_grad_(True)
-        d.pos = pos
     sink = AtomSink(virials)
-    d._hn_atom_props = sink
-    with torch.enable_grad():
-        energy = model(d)
-        g = torch.autograd.grad(energy.sum(), pos, allow_unused=True)[0] if energy.requires_grad else None
-    forces = torch.zeros_like(pos) if g is None else -g
-    energy = energy.detach()
+    d, pos, energy, forces = evaluate_with_sink(model, data, sink)
     n = pos.size(0)
     batch = d.batch.long() if d.get("batch") is not None else torch.zeros(n, dtype=torch.long, device=pos.device)
     energies = sink.energies
@@ -47,7 +37,7 @@ def atom_properties(model, data, *, virials=True, trn_mean=0.0):
         energy = energy + trn_mean
         cnt = torch.bincount(batch, minlength=energy.numel()).clamp(min=1).to(energies.dtype)
         energies = energies + trn_mean / cnt.index_select(0, batch)
-    out = {"energy": energy, "forces": forces.detach(), "energies": energies}
+    out = {"energy": energy, "forces": forces, "energies": energies}
     if virials:
         # (no gradient reached the edge geometry -- e.g. no edge at all: every virial is zero)
         out["virials"] = sink.virials if sink.virials is not None else torch.zeros(n, 3, 3, dtype=pos.dtype, device=pos.device)

@@ -1,12 +1,11 @@
 """HVNet / HeteroVertexConv with the reference's constructor, `forward(data)` signature and
 state_dict keys (`HermNet/hermnet.py`), executing the hot path on MI355X."""
-import os
 from typing import Dict, List, Union
 
 import torch
 from torch import nn
 
-from . import switches
+from . import nodeops, switches
 from .elements import atomic_numbers
 from .ops import EdgeGeometry, TrueEdgeGradient, edge_radial_tables
 from .relations import RelationalGraph
@@ -26,81 +25,81 @@ class HeteroVertexConv(nn.Module):
         self._weights = None
 
     def forward(self, data):
-        """data must come from `HVNet.forward` (carries the relation-ordered graph)."""
-        g = data.get("_hn_graph")
-        if g is None:
+        """data must come from `HVNet.forward` (carries the `layer.StepState` of this evaluation).  Says which of the four
+        ways the layer runs: materialised basis, `switches.fused_layer = False`, GEMM layer, chain layer."""
+        step = data.get("_hn_step")
+        if step is None:
             raise RuntimeError("HeteroVertexConv.forward needs a Data prepared by HVNet.forward")
-        # atom shards: the halo rows of (x, vec) are still with their owners (HVNet.forward leaves the exchange to the
-        # layer that consumes them).  The fused chain path overlaps it with its node projection; every other path runs
-        # it first.
-        halo, data._hn_halo = data.get("_hn_halo"), None
-        step = data._hn_step                     # (layer.StepState of this evaluation)
-        li = step.layer
-        ready = data.get("_hn_weights")          # (HVNet.forward refreshed every layer's copies up front: guard.ParamGuard)
+        g, li = step.graph, step.layer
+        # atom shards: the halo rows of (x, vec) are still with their owners (HVNet._run_layers leaves the exchange to the layer
+        # that consumes them).  The fused chain path overlaps it with its node projection; every other path runs it first.
+        halo, step.halo = step.halo, None
+        ready = step.weights                     # (HVNet._prepare refreshed every layer's copies up front: guard.ParamGuard)
         w = ready[li] if (ready is not None and ready[li].mods[0] is next(iter(self.mods.values()))) else None
-        if w is None and data.get("_hn_edge_embed") is None and switches.fused_layer:
+        if w is None and step.edge_embed is None and switches.fused_layer:
             if self._weights is None:
                 self._weights = LayerWeights(self.mods.values())
             w = self._weights.refresh()
-        # (the exchange inside the layer needs the chain kernels and the channel-per-lane backward, which takes row ranges;
-        # switches.halo_overlap() == "0" runs the blocking exchange in front of the layer instead)
-        if halo is not None and not (w is not None and w.chain and switches.node_chain
-                                     and halo.fwd_early is not None and g.N * 3 * data.x.size(1) * 4 < 2 ** 32
-                                     # (a rank that neither sends nor receives joins the collective in its plain form:
-                                     # nothing to hide, and the asynchronous form costs ~15 us of stream hand-offs)
-                                     and sum(halo.plan.recv_counts) + sum(halo.plan.send_counts) > 0
-                                     and switches.halo_overlap() != "0"):
+        if halo is not None and _exchange_first(halo, w, g, data.x):
             data.x, data.vec = HaloExchangeFeatures.apply(data.x, data.vec, halo.plan)
             halo = None
-        if data.get("_hn_edge_embed") is not None:
+        if step.edge_embed is not None:
             # optional radial bases (Bessel / Bernstein): materialised basis, device ops + autograd
-            data.x, data.vec = relational_layer(self.mods.values(), data.x, data.vec, data._hn_edge, g, None,
-                                                edge_embed=data._hn_edge_embed)
+            data.x, data.vec = relational_layer(self.mods.values(), data.x, data.vec, step.edge, g, None,
+                                                edge_embed=step.edge_embed)
             return data
         if not switches.fused_layer:
             # debugging path: same kernels for the edge part, node algebra through PyTorch autograd
-            data.x, data.vec = relational_layer(self.mods.values(), data.x, data.vec, data._hn_edge, g, data._hn_rbf)
+            data.x, data.vec = relational_layer(self.mods.values(), data.x, data.vec, step.edge, g, step.rbf)
             return data
-        handles = data.get("_hn_edge_handles")
-        edge = data._hn_edge if handles is None else handles[li]
-        node, data._hn_chain_node = data.get("_hn_chain_node"), None
+        edge = step.edge if step.edge_handles is None else step.edge_handles[li]
+        node, step.chain_node = step.chain_node, None
         if not (w.chain and switches.node_chain):
             # library GEMMs joined by the stage kernels (the only path for widths the chain kernels are not instantiated for)
             if halo is not None:
                 raise RuntimeError("the in-layer halo exchange belongs to the chain path")
-            data.x, data.vec = GemmRelationalLayer.apply(data.x, data.vec, edge, g, data._hn_rbf, w, step)
+            data.x, data.vec = GemmRelationalLayer.apply(data.x, data.vec, edge, g, step.rbf, w, step)
             return data
-        # (x, vec) straight from the chain layer below -- both still carry THAT autograd node (an in-place exchange of halo
-        # rows or any other op in between replaces it) -- and this layer is their only reader: its backward may hand its
-        # input gradients down as partial sums (layer.Route, `defer`)
-        # (not under anomaly detection -- its NaN check would read the not-yet-filled buffers -- and not when a tensor hook
-        # would: both are debugging situations, which get the finishing launches; switches.defer_sums() forces them)
-        straight = (node is not None and data.vec is not None and data.x.grad_fn is node and data.vec.grad_fn is node
-                    and not g.num_src and not torch.is_anomaly_enabled()
-                    and not getattr(data.x, "_backward_hooks", None) and not getattr(data.vec, "_backward_hooks", None))
-        if halo is not None:
-            # atom shards: the exchange in its "proj" form; switches.halo_overlap() "1": the round-4 form, x | vec rows
-            route = Route("proj" if straight and switches.halo_overlap() not in ("0", "1") else "rows", halo)
-        else:
-            whole = data.get("_hn_shard") is None or data.get("_hn_lone")     # (no peers: the unsharded forms)
-            # the node projection of THIS x, already computed by the fused update launch of the layer below
-            pre = step.pre_next.pop(li, None)
-            if pre is not None and not (pre[0].data_ptr() == data.x.data_ptr() and pre[0].shape == data.x.shape):
-                pre = None
-            # the next layer's weights: its projection of the rows this layer produces can run inside this layer's update launch
-            w_next = ready[li + 1] if (ready is not None and li + 1 < len(ready) and whole) else None
-            # (HVNet.forward: this is the last layer and the read-out takes its x only)
-            last, data._hn_last = bool(data.get("_hn_last")) and not g.num_src and w_next is None, None
-            route = Route(defer=straight and whole, pre=None if pre is None else pre[1], w_next=w_next, last=last)
-        data.x, data.vec = FusedRelationalLayer.apply(data.x, data.vec, edge, g, data._hn_rbf, w, step, route)
-        data._hn_chain_node = None if g.num_src else data.x.grad_fn
+        route = _chain_route(data, step, node, halo)
+        data.x, data.vec = FusedRelationalLayer.apply(data.x, data.vec, edge, g, step.rbf, w, step, route)
+        step.chain_node = None if g.num_src else data.x.grad_fn
         return data
 
 
-def nodeops_tile_rows(Hp):
-    """Rows per tile of the node pre kernels at padded width Hp (64 when the width has no chain kernels: unused then)."""
-    from . import nodeops
-    return nodeops.chain_tile_rows(Hp) or 64
+def _exchange_first(halo, w, g, x):
+    """The blocking exchange runs in front of the layer, unless the layer can run it inside: that needs the chain kernels and
+    the channel-per-lane backward, which takes row ranges; switches.halo_overlap() == "0" asks for the blocking form."""
+    return not (w is not None and w.chain and switches.node_chain
+                and halo.fwd_early is not None and g.N * 3 * x.size(1) * 4 < 2 ** 32
+                # (a rank that neither sends nor receives joins the collective in its plain form:
+                # nothing to hide, and the asynchronous form costs ~15 us of stream hand-offs)
+                and sum(halo.plan.recv_counts) + sum(halo.plan.send_counts) > 0
+                and switches.halo_overlap() != "0")
+
+
+def _chain_route(data, step, node, halo):
+    """The `layer.Route` of chain layer `step.layer`; `node`: the autograd node the chain layer below left, `halo`: still due."""
+    g, li, ready = step.graph, step.layer, step.weights
+    # (x, vec) straight from the chain layer below -- both still carry THAT autograd node (an in-place exchange of halo
+    # rows or any other op in between replaces it) -- and this layer is their only reader: its backward may hand its
+    # input gradients down as partial sums (layer.Route, `defer`)
+    # (not under anomaly detection -- its NaN check would read the not-yet-filled buffers -- and not when a tensor hook
+    # would: both are debugging situations, which get the finishing launches; switches.defer_sums() forces them)
+    straight = (node is not None and data.vec is not None and data.x.grad_fn is node and data.vec.grad_fn is node
+                and not g.num_src and not torch.is_anomaly_enabled()
+                and not getattr(data.x, "_backward_hooks", None) and not getattr(data.vec, "_backward_hooks", None))
+    if halo is not None:
+        # atom shards: the exchange in its "proj" form; switches.halo_overlap() "1": the round-4 form, x | vec rows
+        return Route("proj" if straight and switches.halo_overlap() not in ("0", "1") else "rows", halo)
+    # the node projection of THIS x, already computed by the fused update launch of the layer below
+    pre = step.pre_next.pop(li, None)
+    if pre is not None and not (pre[0].data_ptr() == data.x.data_ptr() and pre[0].shape == data.x.shape):
+        pre = None
+    # the next layer's weights: its projection of the rows this layer produces can run inside this layer's update launch
+    w_next = ready[li + 1] if (ready is not None and li + 1 < len(ready) and step.whole) else None
+    # (HVNet._run_layers: this is the last layer and the read-out takes its x only)
+    last = step.last and not g.num_src and w_next is None
+    return Route(defer=straight and step.whole, pre=None if pre is None else pre[1], w_next=w_next, last=last)
 
 
 class GraphEnergies(torch.autograd.Function):
@@ -278,16 +277,6 @@ class HVNet(nn.Module):
         d = torch.where(d.abs() <= 1.0e-6, torch.full_like(d, 1.0e-6), d)           # hermnet.py:146-147
         return torch.cat([D / d[:, None], d[:, None]], dim=1), None
 
-    @staticmethod
-    def _check_atom_props(train, shard):
-        """Per-atom outputs and the per-graph virial are first-order eval() results of whole, unsharded graphs: refuse the
-        rest.  (Nothing on their path reads the host, so they may run inside a captured hipGraph.)"""
-        if train:
-            raise NotImplementedError("per-atom outputs / virials are eval() results: not in train() or with eval_param_grads")
-        if shard is not None:
-            raise NotImplementedError("per-atom outputs / virials of atom-sharded data: the ghost atoms' shares would have to "
-                                      "be sent back to their owners, which is not implemented")
-
     def _atom_energies(self, e_rows, graph, batch):
         """The read-out term of every atom (hermnet.py:129) in atom order; intensive models: divided by its graph's atom
         count, so that the terms of a graph sum to its energy."""
@@ -306,9 +295,16 @@ class HVNet(nn.Module):
         `eval()` (calculators, MD, validation -- `calculator.py:73`, `lmp_calc.py:46`, `dist_train.py:109`):
         the fused gfx950 kernels, first-order gradients w.r.t. pos / cell; ALL parameters are constants there
         (no parameter receives a gradient; set `model.eval_param_grads = True` to get them in eval()).
-        `train()` with grad mode on
-        (`dist_train.py:81-99`): every op is a differentiable device op, so `autograd.grad(E, pos,
+        `train()` with grad mode on (`dist_train.py:81-99`): every op is a differentiable device op, so `autograd.grad(E, pos,
         create_graph=True)` and `loss.backward()` give the gradients of all parameters."""
+        step = data._hn_step = self._prepare(data)
+        data = self._run_layers(data, step)
+        return self._read_out(data, step)
+
+    def _prepare(self, data):
+        """Everything in front of the layers -> the `layer.StepState` of this evaluation: checks, graph, the shard's position
+        exchange, embedding, weights, edge geometry, radial tables, edge embedding, edge-gradient sink.  Leaves (x, vec) on
+        `data` (the reference's contract; forward hooks read them) and `data._hn_graph / _hn_edge / _hn_edge_embed` for readers."""
         pos = data.pos
         self._require_device(pos)
         self._require_fp32(pos)
@@ -320,8 +316,7 @@ class HVNet(nn.Module):
         # atom-sharded evaluation (hermnet_amd/sharding.py): this rank's atoms + one-hop halo
         shard = data.get("_hn_shard")
         # a padded neighbour list (neighbor.neighbor_search_padded: NULL edges behind the real ones, the count on the device)
-        padded = data.get("_hn_edge_count") is not None
-        if padded and train:
+        if data.get("_hn_edge_count") is not None and train:
             raise NotImplementedError("a padded neighbour list runs through the fused eval() path")
         fused = self.radial_basis.fused and not train
         # (the 16-lanes-per-edge backward stages a whole weight tile: num_rbf <= 176; the channel-per-lane form, which takes
@@ -329,34 +324,34 @@ class HVNet(nn.Module):
         # basis takes the materialised route instead of failing in the backward: ADVICE r5)
         if fused and self.radial_basis.num_radial > 176 and pos.size(0) * 1.2 * 3 * ((self.hidden_channels + 63) // 64 * 64) * 4 >= 2 ** 32:
             fused = False
-        # per-atom outputs (atomic.atom_properties, the ASE calculator's `energies` / `stresses`): an ops.AtomSink of this call
+        # per-atom outputs (atomic.atom_properties, the ASE calculator's `energies` / `stresses`): an ops.AtomSink of this call.
+        # They and the per-graph virial are first-order eval() results of whole, unsharded graphs: the rest is refused.
+        # (Nothing on their path reads the host, so they may run inside a captured hipGraph.)
         props = data.get("_hn_atom_props")
-        if props is not None:
-            self._check_atom_props(train, shard)
+        if props is not None and train:
+            raise NotImplementedError("per-atom outputs / virials are eval() results: not in train() or with eval_param_grads")
+        if props is not None and shard is not None:
+            raise NotImplementedError("per-atom outputs / virials of atom-sharded data: the ghost atoms' shares would have to "
+                                      "be sent back to their owners, which is not implemented")
         graph = self._build_graph(data, zl, shard)
         if props is not None and graph.num_src:
             raise NotImplementedError("per-atom outputs: HTNet's triadic graphs are not supported")
         rbf = self.radial_basis.descriptor() if fused else None
-        row_plan = None
+        # ONE rank that neither sends nor receives a row (a plain world-1 plan): nothing to exchange with anybody -- the
+        # collectives (and the stream hand-offs they cost: ~0.12 ms per step, round 4) are skipped and the layers take
+        # the unsharded forms (deferred sums).  With peers every rank joins every collective, rows or not.
+        whole = True
         if shard is not None:
             if train:
                 raise NotImplementedError("atom-sharded evaluation is first-order (energy/forces); train with "
                                           "DistributedDataParallel over whole graphs (example/dist_train.py:63)")
             if shard.owned_mask.device != pos.device:
                 shard.to(pos.device)
-            # ONE rank that neither sends nor receives a row (a plain world-1 plan): nothing to exchange with anybody -- the
-            # collectives (and the stream hand-offs they cost: ~0.12 ms per step, round 4) are skipped and the layers take
-            # the unsharded forms (deferred sums).  With peers every rank joins every collective, rows or not.
-            lone = shard.world == 1 and shard.atom_plan.send_idx.numel() == 0 and shard.atom_plan.recv_idx.numel() == 0
-            data._hn_lone = lone
-            if lone:
-                pass
-            elif shard.halo_pos_local:     # coordinates are there; their gradients still go home
-                pos = HaloGradReturn.apply(pos, shard.atom_plan)
-            else:
-                pos = HaloExchange.apply(pos, shard.atom_plan)              # halo coordinates from their owners
-            if not lone:
-                row_plan = shard.row_plan(graph.row_of_node)
+            whole = shard.world == 1 and shard.atom_plan.send_idx.numel() == 0 and shard.atom_plan.recv_idx.numel() == 0
+            if not whole:
+                # halo coordinates from their owners; `halo_pos_local`: they are there, their gradients still go home
+                pos = (HaloGradReturn if shard.halo_pos_local else HaloExchange).apply(pos, shard.atom_plan)
+                shard.row_plan(graph.row_of_node)      # (the exchange lists in row order, cached: `shard.halo_overlap`)
         # hermnet.py:123, row order (pads: Z=0).  eval(): every parameter is a constant, the embedding included
         # (the fused layers produce no parameter gradients; a partial set would be worse than none)
         if train and pos.is_cuda:
@@ -369,21 +364,15 @@ class HVNet(nn.Module):
         if Hp != H:
             # widths that are not a multiple of 64 run on the same kernels with zero-padded channels (layer.LayerWeights)
             x = torch.nn.functional.pad(x, (0, Hp - H))
-        data._hn_weights = None
-        if fused and switches.fused_layer:
-            data._hn_weights = self._refresh_weights(pos.device)
+        weights = self._refresh_weights(pos.device) if fused and switches.fused_layer else None
         if train:
             edge, edge_parts = self._edge_geometry_autograd(pos, data.get("cell"), graph)
+        elif props is not None and (props.want_virials or props.want_graph_virial):
+            edge = EdgeGeometry.apply(pos, data.get("cell"), graph, props)    # (its backward fills props.virials)
         else:
-            if props is not None and (props.want_virials or props.want_graph_virial):
-                edge = EdgeGeometry.apply(pos, data.get("cell"), graph, props)    # (its backward fills props.virials)
-            else:
-                edge = EdgeGeometry.apply(pos, data.get("cell"), graph)      # with_edge, hermnet.py:133-152
-
-        vec = None                                                          # zeros, hermnet.py:124
+            edge = EdgeGeometry.apply(pos, data.get("cell"), graph)          # with_edge, hermnet.py:133-152
         if not fused and not train:
             edge = TrueEdgeGradient.apply(edge)      # autograd's (rhat, d) gradients -> Cartesian for the kernel
-        data._hn_graph, data._hn_edge, data._hn_rbf = graph, edge, rbf
         graph.fwd_taps = None      # (records of an earlier step's coordinates must not feed this step's forward)
         if fused and edge.requires_grad and edge.is_cuda:
             # forces wanted: the backward message kernels read the radial quantities of an edge from this table, the
@@ -391,20 +380,19 @@ class HVNet(nn.Module):
             graph.edge_table, graph.fwd_taps = edge_radial_tables(graph, rbf, edge.detach())
         # rmnet.py:168-172 for the optional bases only: [E,R] basis from the kernel's distances
         if fused:
-            data._hn_edge_embed = None
+            edge_embed = None
         elif train and pos.is_cuda and self.radial_basis.rbf_name == "gaussian" and H % 4 == 0 and graph.T > 0:
             # train(): the basis sorted by (relation, distance bucket) and cut to the bucket's 32 centres (trainops.BucketedBasis)
-            parts = edge_parts
-            Ek = graph.rel_edge_total()              # (no host read when every atom has an element of the model)
-            data._hn_edge_embed = self.radial_basis.bucketed(edge[:, 3] if parts is None else parts[1], Ek, graph.T,
-                                                             graph.rel_edge_bounds_dev())
+            parts, Ek = edge_parts, graph.rel_edge_total()              # (no host read when every atom has an element of the model)
+            edge_embed = self.radial_basis.bucketed(edge[:, 3] if parts is None else parts[1], Ek, graph.T,
+                                                    graph.rel_edge_bounds_dev())
             if parts is not None:
-                data._hn_edge_embed.set_unit_vectors(edge, parts[0], Ek)
+                edge_embed.set_unit_vectors(edge, parts[0], Ek)
         else:
-            data._hn_edge_embed = self.radial_basis(edge[:, 3])
-        data.x, data.vec = x, vec
-        data._hn_edge_handles = data._hn_halo = data._hn_chain_node = None
-        step = data._hn_step = StepState()       # (what the layers of this evaluation hand to each other)
+            edge_embed = self.radial_basis(edge[:, 3])
+        data.x, data.vec = x, None                                          # (vec: zeros, hermnet.py:124)
+        data._hn_graph, data._hn_edge, data._hn_edge_embed = graph, edge, edge_embed
+        step = StepState(graph, edge, rbf, edge_embed, train=train, fused=fused, whole=whole, weights=weights)
         if fused and edge.requires_grad and switches.fused_layer:
             # one reduction of the edge gradients per step instead of one per layer (layer.EdgeFanout)
             # (atoms of an unknown element own the rows past type_rowptr[T]; only edges INTO them go unwritten)
@@ -412,95 +400,95 @@ class HVNet(nn.Module):
             # walks the CSC segments, and NULL edges are in none)
             all_known = graph.num_src == 0 and graph.N == graph.type_rowptr_host[-1]
             step.edge_sink = EdgeGradSink(len(self.hermconvs), Hp // 64, graph.E, pos.device, zero=not all_known)
-            data._hn_edge_handles = EdgeFanout.apply(edge, step.edge_sink)
+            step.edge_handles = EdgeFanout.apply(edge, step.edge_sink)
+        return step
+
+    def _run_layers(self, data, step):
+        """The layers, on (data.x, data.vec).  Atom shards: one exchange per layer, (x | vec) rows of halo atoms, 4H floats each,
+        due before the next layer reads them and run BY that layer (overlapped with its node projection where it can)."""
+        graph, edge, L = step.graph, step.edge, len(self.hermconvs)
         for li, conv in enumerate(self.hermconvs):
             step.layer = li
             # The read-out takes x only: in an energy / force evaluation (parameters constant, forces the only gradient) the
             # LAST layer's vec feeds nothing, and its layer may leave it out (layer.Route: `last`; data.vec is None behind it).
             # A forward hook on the layer is somebody who reads it: the general form.
-            data._hn_last = (li + 1 == len(self.hermconvs) and fused and switches.fused_layer and switches.dead_ends
+            step.last = bool(li + 1 == L and step.fused and switches.fused_layer and switches.dead_ends
                              and type(conv) is HeteroVertexConv        # (HTNet's layer reads both outputs: PairMean)
                              and edge.requires_grad and not conv._forward_hooks
                              and not torch.nn.modules.module._global_forward_hooks)
             data = conv(data)
-            if row_plan is not None and li + 1 < len(self.hermconvs):
-                # one exchange per layer: (x | vec) rows of halo atoms, 4H floats each -- due before the next layer reads
-                # them, run BY that layer (overlapped with its node projection where it can, HeteroVertexConv.forward)
-                data._hn_halo = shard.halo_overlap(graph, nodeops_tile_rows(Hp))
+            if not step.whole and li + 1 < L:
+                # (rows per tile of the node pre kernels at this width; 64 where it has no chain kernels: unused then)
+                step.halo = data._hn_shard.halo_overlap(graph, nodeops.chain_tile_rows(data.x.size(1)) or 64)
+        # (the step stays on the caller's Data: it keeps neither the model's weight copies nor the autograd graph)
+        step.weights = step.edge_handles = step.halo = step.chain_node = None
         graph._keep = None
-        x = data.x
-        if Hp != H:
-            x = x[:, :H]                                                    # the read-out sees the real channels
+        return data
 
-        head_params = (self.out_energy[0].weight, self.out_energy[0].bias, self.out_energy[2].weight,
-                       self.out_energy[2].bias)
-        single = shard is None and graph.num_graphs == 1
-        # one structure on an atom shard (the sharded MD case): the read-out masks the rows of halo atoms like it masks padding
-        # rows, the rank's share is ONE ordered sum over its rows -- no gather back to atom order, no mask product, no count
-        # (round 6: ~10 small launches per step less, forward and backward)
-        shard_rows = None
-        if (shard is not None and shard.num_graphs == 1 and not train and fused
-                and switches.fused_layer and (self.hidden_channels // 2) % 4 == 0):
-            shard_rows = shard.owned_rows(graph, x.size(0))
-        if train or not fused or (self.hidden_channels // 2) % 4 != 0 or not switches.fused_layer:
-            if train and x.is_cuda:
-                # (the same nn.Sequential, its two Linears through trainops.TallBmm: weight gradients over ~2e4 rows)
-                from .trainops import tall_linear
-                h_ = tall_linear(x, self.out_energy[0].weight, self.out_energy[0].bias)
-                e_rows = tall_linear(self.out_energy[1](h_), self.out_energy[2].weight, self.out_energy[2].bias).squeeze(1)
-            else:
-                e_rows = self.out_energy(x).squeeze(1)                      # hermnet.py:129, row order
-            if single:
-                e_rows = e_rows * graph.row_real
-        else:
-            e_rows = EnergyHead.apply(x.contiguous(), *[p.detach() for p in head_params],
-                                      graph.row_real if single else shard_rows)
+    def _read_out(self, data, step):
+        """`out_energy` on every row, then the per-graph sums (hermnet.py:129-130) -> energy [num_graphs]."""
+        graph, shard, H = step.graph, data.get("_hn_shard"), self.hidden_channels
+        x = data.x if data.x.size(1) == H else data.x[:, :H]               # the read-out sees the real channels
+        head = step.fused and not step.train and switches.fused_layer and (H // 2) % 4 == 0      # (the EnergyHead kernels)
+        # Rows that do not count are masked where the energies are made and the sum runs over the rows: no gather back to atom
+        # order (its backward is an index_put, ~50 us), no mask product, no count.  One graph: the padding rows.  One structure on
+        # an atom shard (the sharded MD case): the halo atoms' rows too (round 6: ~10 small launches per step less, each way).
+        mask = graph.row_real if shard is None and graph.num_graphs == 1 else None
+        if shard is not None and shard.num_graphs == 1 and head:
+            mask = shard.owned_rows(graph, x.size(0))
+        e_rows = self._row_energies(x, step.train, head, mask)
+        props = data.get("_hn_atom_props")
         if props is not None and props.want_energies:
             props.energies = self._atom_energies(e_rows, graph, data.batch)
-        if shard_rows is not None:
+        return self._graph_energies(e_rows, graph, data.batch, shard, mask is not None)
+
+    def _row_energies(self, x, train, head, mask):
+        """The read-out term of every row (hermnet.py:129), row order; `mask` [rows] (optional) multiplies it."""
+        if head:
+            return EnergyHead.apply(x.contiguous(), self.out_energy[0].weight.detach(), self.out_energy[0].bias.detach(),
+                                    self.out_energy[2].weight.detach(), self.out_energy[2].bias.detach(), mask)
+        if train and x.is_cuda:
+            # (the same nn.Sequential, its two Linears through trainops.TallBmm: weight gradients over ~2e4 rows)
+            from .trainops import tall_linear
+            h_ = tall_linear(x, self.out_energy[0].weight, self.out_energy[0].bias)
+            e_rows = tall_linear(self.out_energy[1](h_), self.out_energy[2].weight, self.out_energy[2].bias).squeeze(1)
+        else:
+            e_rows = self.out_energy(x).squeeze(1)
+        return e_rows if mask is None else e_rows * mask
+
+    def _graph_energies(self, e_rows, graph, batch, shard, masked):
+        """Per-graph energies [num_graphs] from the per-row terms (hermnet.py:130: scatter(per_atom_energy, batch, sum | mean)), every
+        form but the last an ORDERED sum, bit-reproducible run to run.  `masked`: rows that do not count are zero already."""
+        if shard is not None and masked:         # one structure on an atom shard: the rank's share is ONE sum over its rows
             energy = e_rows.sum().reshape(1)
             if shard.world > 1:
                 energy = SumAcrossRanks.apply(energy, shard.group)
-            if self.intensive:               # (mean over the atoms of the WHOLE structure: every rank knows their number)
-                energy = energy / max(shard.num_atoms_global, 1)
-            return energy
-        if single:
-            # one graph: padding rows are masked instead of gathering back to atom order (the gather's
-            # backward is an index_put, ~50 us); fixed summation order, bit-reproducible
+            # (intensive: the mean over the atoms of the WHOLE structure, every rank knows their number)
+            return energy / max(shard.num_atoms_global, 1) if self.intensive else energy
+        if masked:                               # one graph
             energy = e_rows.sum().reshape(1)
-            if self.intensive:
-                energy = energy / max(graph.num_atoms, 1)
-            return energy
-        batch = data.batch.long()
-        if shard is None and graph.graph_perm is not None:
-            # scatter(per_atom_energy, batch, reduce=sum|mean) (hermnet.py:130) as an ordered segment reduction: no atomics,
-            # so the energies are bit-reproducible run to run
+            return energy / max(graph.num_atoms, 1) if self.intensive else energy
+        batch = batch.long()
+        if shard is None and graph.graph_perm is not None:       # several graphs: an ordered segment reduction, no atomics
             energy = GraphEnergies.apply(e_rows, graph, batch)
-            if self.intensive:
-                energy = energy / graph.graph_lengths.clamp(min=1).to(energy.dtype)
-            return energy
+            return energy / graph.graph_lengths.clamp(min=1).to(energy.dtype) if self.intensive else energy
         per_atom_energy = e_rows.index_select(0, graph.row_of_node)         # back in atom order
         if shard is not None:
             own = shard.owned_mask.to(per_atom_energy.dtype)
             e_own = per_atom_energy * own
-            if shard.num_graphs == 1:      # one structure (the sharded MD case): ordered sums, bit-reproducible
+            if shard.num_graphs == 1:      # one structure whose rows were not masked: ordered sums
                 energy, cnt = e_own.sum().reshape(1), own.sum().reshape(1)
             else:
-                # several graphs on a shard: the local atoms sorted by graph (stable, cached with the plan), then ORDERED
-                # segment sums -- no index_add atomics, so a rank's share is bit-reproducible run to run like everything else
+                # several graphs: the local atoms sorted by graph (stable, cached with the plan), then ORDERED segment sums
                 perm, lengths = shard.graph_order(batch)
                 energy = torch.segment_reduce(e_own.index_select(0, perm), "sum", lengths=lengths, unsafe=True)
                 cnt = torch.segment_reduce(own.index_select(0, perm), "sum", lengths=lengths, unsafe=True)
             if shard.world > 1:
                 energy, cnt = SumAcrossRanks.apply(energy, shard.group), (SumAcrossRanks.apply(cnt, shard.group) if self.intensive else cnt)
-            if self.intensive:
-                energy = energy / cnt.clamp(min=1)
-            return energy
+            return energy / cnt.clamp(min=1) if self.intensive else energy
         # (train(): segment_reduce has no second derivative)
-        energy = torch.zeros(graph.num_graphs, dtype=x.dtype, device=x.device).index_add(0, batch, per_atom_energy)
-        if self.intensive:
-            energy = energy / graph.graph_lengths.clamp(min=1).to(energy.dtype)
-        return energy
+        energy = torch.zeros(graph.num_graphs, dtype=e_rows.dtype, device=e_rows.device).index_add(0, batch, per_atom_energy)
+        return energy / graph.graph_lengths.clamp(min=1).to(energy.dtype) if self.intensive else energy
 
 
 def triadic_relations(elems):
@@ -522,9 +510,9 @@ class HeteroTriadicConv(HeteroVertexConv):
 
     def forward(self, data):
         data = super().forward(data)                   # (x, vec) in target rows [T * P * B, ...]
-        g = data._hn_graph
+        g = data._hn_step.graph
         P_, B_, Te = g.triadic_pairs, g.block, g.T // g.triadic_pairs
-        if data.get("_hn_edge_embed") is not None:     # train(): plain torch ops, differentiable to any order
+        if data._hn_step.edge_embed is not None:       # train(): plain torch ops, differentiable to any order
             H = data.x.size(1)
             xo = data.x.view(Te, P_, B_, H).mean(1).reshape(Te * B_, H)
             vo = data.vec.view(Te, P_, B_, 3, H).mean(1).reshape(Te * B_, 3, H)

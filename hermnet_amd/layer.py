@@ -200,12 +200,27 @@ class EdgeFanout(torch.autograd.Function):
 
 
 class StepState(object):
-    """What the layers of ONE evaluation hand to each other, indexed by layer.  `HVNet.forward` creates it and every layer
-    receives it, so a new step starts empty and no other model or step in the process sees it."""
+    """The context of ONE evaluation (`data._hn_step`): what `HVNet._prepare` leaves for the layers and what the layers hand to
+    each other, indexed by layer.  Every forward creates its own, so no other step or model sees it; undeclared fields raise."""
 
-    def __init__(self):
-        self.edge_sink = None           # EdgeGradSink of this step, where the edge gradients are wanted
-        self.layer = 0                  # index of the layer that is running its forward (HVNet.forward's loop)
+    __slots__ = ("graph", "edge", "rbf", "edge_embed", "train", "fused", "whole", "weights", "edge_sink", "edge_handles",
+                 "layer", "last", "halo", "chain_node", "pending", "pre_next")
+
+    def __init__(self, graph=None, edge=None, rbf=None, edge_embed=None, train=False, fused=False, whole=True, weights=None):
+        self.graph = graph              # _prepare: relation-ordered graph of this neighbour list; every layer, the read-out
+        self.edge = edge                # _prepare: edge geometry [E,4] = (rhat, d); layers that got no handle
+        self.rbf = rbf                  # _prepare: the radial basis' descriptor for the kernels (None: materialised); layers
+        self.edge_embed = edge_embed    # _prepare: the materialised basis of the optional bases / train(), else None; layers
+        self.train = train              # _prepare: the differentiable device-op path; the read-out
+        self.fused = fused              # _prepare: the basis is evaluated inside the kernels; the loop's `last`, the read-out
+        self.whole = whole              # _prepare: no shard, or a lone world-1 plan (the unsharded forms); the loop, Route
+        self.weights = weights          # _prepare: the list from `_refresh_weights` or None; layers; dropped behind the loop
+        self.edge_sink = None           # _prepare: EdgeGradSink of this step, where the edge gradients are wanted; backwards
+        self.edge_handles = None        # _prepare: one handle per layer from `EdgeFanout`; layers; dropped behind the loop
+        self.layer = 0                  # _run_layers: index of the layer that is running its forward; that layer
+        self.last = False               # _run_layers: this layer may run short (the read-out takes its x only); that layer
+        self.halo = None                # _run_layers: the exchange still due for the next layer; that layer takes it
+        self.chain_node = None          # a chain layer: the autograd node of its outputs; the layer above takes it
         self.pending = {}               # consuming layer -> nodeops.PendingGrads, from one layer's backward to the next one's
         self.pre_next = {}              # layer -> (x, its node projection), left by the fused update launch of the layer below
 

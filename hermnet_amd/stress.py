@@ -32,11 +32,15 @@ def stress_of_virial(virial, cell):
     return -0.5 * (w + w.transpose(1, 2)) * inv[:, None, None]
 
 
-def energy_forces_virial(model, d, pos):
-    """(energy [B] detached, forces [N,3], virial [B,3,3]) of `model` on `d`, whose `pos` is the leaf `pos`: one forward, one
-    `autograd.grad`; the sink travels on `d` for this call only.  (The body shared by `energy_forces_stress` and the
-    captured steps: no host read.)"""
-    sink = AtomSink(virials=False, graph_virial=True, energies=False)
+def evaluate_with_sink(model, data, sink, pos=None):
+    """One forward of `model` and ONE `autograd.grad(E.sum(), pos)` with `sink` (ops.AtomSink) travelling on the Data for this
+    call only -> (d, pos, energy [B] detached, forces [N,3]).  `pos` None: the caller's `data` is not modified, the call runs
+    on a shallow copy `d` whose `pos` is a leaf; else `data` is the caller's own copy and `pos` its leaf.  No host read."""
+    d = data
+    if pos is None:
+        d, pos = copy.copy(data), data.pos
+        if not (pos.requires_grad and pos.is_leaf):
+            pos = d.pos = pos.detach().requires_grad_(True)
     d._hn_atom_props = sink
     try:
         with torch.enable_grad():
@@ -44,11 +48,18 @@ def energy_forces_virial(model, d, pos):
             g = torch.autograd.grad(energy.sum(), pos, allow_unused=True)[0] if energy.requires_grad else None
     finally:
         d._hn_atom_props = None
-    forces = torch.zeros_like(pos) if g is None else -g
+    return d, pos, energy.detach(), (torch.zeros_like(pos) if g is None else -g).detach()
+
+
+def energy_forces_virial(model, d, pos):
+    """(energy [B] detached, forces [N,3], virial [B,3,3]) of `model` on `d`, whose `pos` is the leaf `pos` (None: any `d`, which
+    is not modified).  (The body shared by `energy_forces_stress` and the captured steps.)"""
+    sink = AtomSink(virials=False, graph_virial=True, energies=False)
+    _, pos, energy, forces = evaluate_with_sink(model, d, sink, pos)
     virial = sink.graph_virial
     if virial is None:           # (no gradient reached the edge geometry -- e.g. no edge at all: the virial is zero)
         virial = torch.zeros(energy.numel(), 3, 3, dtype=pos.dtype, device=pos.device)
-    return energy.detach(), forces.detach(), virial
+    return energy, forces, virial
 
 
 def energy_forces_stress(model, data, *, trn_mean=0.0):
@@ -63,15 +74,10 @@ def energy_forces_stress(model, data, *, trn_mean=0.0):
     if data.get("_hn_shard") is not None:
         raise NotImplementedError("energy_forces_stress of atom-sharded data: the ghost atoms' shares would have to be sent "
                                   "back to their owners, which is not implemented")
-    pos = data.pos
-    if not pos.is_cuda:
+    if not data.pos.is_cuda:
         raise RuntimeError("hermnet_amd.energy_forces_stress runs on MI355X only (data is on %s); there is no CPU fallback"
-                           % pos.device)
-    d = copy.copy(data)
-    if not (pos.requires_grad and pos.is_leaf):
-        pos = pos.detach().requires_grad_(True)
-        d.pos = pos
-    energy, forces, virial = energy_forces_virial(model, d, pos)
+                           % data.pos.device)
+    energy, forces, virial = energy_forces_virial(model, data, None)
     if trn_mean:
         energy = energy + trn_mean
-    return {"energy": energy, "forces": forces, "virial": virial, "stress": stress_of_virial(virial, d.get("cell"))}
+    return {"energy": energy, "forces": forces, "virial": virial, "stress": stress_of_virial(virial, data.get("cell"))}

@@ -1299,6 +1299,43 @@ def test_fused_layer_equals_autograd_composed_layer(name, monkeypatch):
     assert rel_err(res[0][1], res[1][1]) < 5e-6
 
 
+@pytest.mark.parametrize("case", ["eval", "train", "htnet"])
+def test_an_evaluation_leaves_only_its_declared_names_on_the_data(case):
+    """The 108-atom alloy at width 128 with two layers -- the smallest model that reaches the short last layer, the deferred
+    sums and a layer boundary -- in eval(), in train() with create_graph=True and as HTNet: behind the forward and its backward
+    the Data holds the four names an evaluation leaves for readers and nothing else of the package's; the rest of what the
+    stages hand to each other lives on the `layer.StepState` and goes with it."""
+    dev = _dev()
+    g = Golden("alloy108")
+    torch.manual_seed(3)
+    Model = hn.HTNet if case == "htnet" else hn.HVNet
+    model = Model(g.elems, rc=5.0, num_layers=2, hidden_channels=128, num_rbf=128)
+    model.load_state_dict(synth.synth_state_dict(model.state_dict(), 7))
+    model = model.to(dev)
+    d = g.data().to(dev)
+    d.pos.requires_grad_(True)
+    if case == "train":
+        model.train()
+        e = model(d)
+        f = -torch.autograd.grad(e.sum(), d.pos, create_graph=True)[0]
+        (e.sum() + (f ** 2).sum()).backward()
+        assert all(p.grad is None or torch.isfinite(p.grad).all() for p in model.parameters())
+        assert sum(p.grad is not None for p in model.parameters()) > 0
+    else:
+        model.eval()
+        for p in model.parameters():
+            p.requires_grad_(False)
+        e = model(d)
+        f = -torch.autograd.grad(e.sum(), d.pos)[0]
+    assert torch.isfinite(e).all() and torch.isfinite(f).all() and float(f.abs().max()) > 0
+    assert {k for k in d.keys() if k.startswith("_hn_")} == {"_hn_step", "_hn_graph", "_hn_edge", "_hn_edge_embed"}
+    step = d._hn_step
+    assert step.graph is d._hn_graph and step.edge is d._hn_edge and step.edge_embed is d._hn_edge_embed
+    assert step.weights is None and step.edge_handles is None and not step.pending and not step.pre_next
+    if case == "eval":
+        assert d.vec is None                     # (behind the short last layer: tests/test_dead_ends.py)
+
+
 class _LaunchCounter(object):
     """ops.set_kernel_timer hook that only counts the library launches by name."""
 

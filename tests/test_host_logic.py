@@ -535,3 +535,157 @@ def test_parameter_gradients_are_not_formed_in_a_pass_that_does_not_ask_for_them
     ((f ** 2).sum() + e).backward()
     for got, ref in zip((pos, w, b, B, bias), [ref_pos] + params):
         assert torch.allclose(got.grad, ref.grad, rtol=1e-10, atol=1e-10)
+
+
+_REF_NODEOPS = ["energy_head_fwd", "energy_head_bwd", "layernorm_fwd", "layernorm_bwd", "ssilu_fwd", "ssilu_bwd", "update_mid",
+                "update_out", "update_out_bwd", "update_mid_bwd", "node_pre_fwd", "node_pre_bwd", "node_update_fwd",
+                "node_update_bwd", "node_update_pre_fwd", "node_pre_fwd16", "node_pre_bwd16"]
+_STEP_OUTPUTS = {"_hn_step", "_hn_graph", "_hn_edge", "_hn_edge_embed"}
+
+
+def _reference_ops(monkeypatch, fused_layer=True):
+    """The monkeypatched reference ops of `test_fused_layer_orchestration_matches_golden` (fused_layer False: of
+    `test_host_pipeline_with_reference_ops_matches_golden`)."""
+    import hermnet_amd.hermnet as hmod
+    import hermnet_amd.layer as lmod
+    import hermnet_amd.rmnet as rmod
+    from hermnet_amd import switches
+    monkeypatch.setattr(switches, "fused_layer", fused_layer)
+    monkeypatch.setattr(hmod.HVNet, "_require_device", staticmethod(lambda pos: None))
+    if not fused_layer:
+        monkeypatch.setattr(hmod, "EdgeGeometry", _FakeFn(lambda pos, cell, graph: ref_ops.geometry_ref(pos, graph, cell)))
+        monkeypatch.setattr(rmod, "MessageScatter", _FakeFn(ref_ops.message_scatter_ref))
+        return
+    monkeypatch.setattr(hmod, "EdgeGeometry", ref_ops.RefEdgeGeometry)
+    for fn in _REF_NODEOPS:
+        monkeypatch.setattr(lmod.nodeops, fn, getattr(ref_ops, fn))
+    monkeypatch.setattr(lmod, "_msg_fwd", ref_ops.msg_fwd)
+    monkeypatch.setattr(lmod, "_msg_bwd", ref_ops.msg_bwd)
+
+
+def _frozen_model(g):
+    model = g.model()
+    for p in model.parameters():
+        p.requires_grad_(False)
+    return model
+
+
+@pytest.mark.parametrize("fused_layer", [True, False])
+def test_an_evaluation_leaves_only_its_declared_names_on_the_data(fused_layer, monkeypatch):
+    """What one evaluation hands from stage to stage lives on its `layer.StepState`: behind a forward and its backward the
+    caller's Data holds the four names left for readers and nothing else of the package's."""
+    _reference_ops(monkeypatch, fused_layer)
+    g = Golden("alloy108")
+    model = _frozen_model(g)
+    d = g.data()
+    d.pos.requires_grad_(True)
+    e = model(d)
+    f = -torch.autograd.grad(e.sum(), d.pos)[0]
+    assert rel_err(f, g.forces) < 1e-5
+    assert {k for k in d.keys() if k.startswith("_hn_")} == _STEP_OUTPUTS
+    step = d._hn_step
+    assert step.graph is d._hn_graph and step.edge is d._hn_edge and step.edge_embed is d._hn_edge_embed
+    # (nothing of the model or of the autograd graph stays behind on the step either)
+    assert step.weights is None and step.edge_handles is None and step.halo is None and step.chain_node is None
+
+
+def test_step_state_refuses_undeclared_fields():
+    from hermnet_amd.layer import StepState
+    step = StepState()
+    step.layer = 3
+    with pytest.raises(AttributeError):
+        step.layr = 4
+    with pytest.raises(AttributeError):
+        step.hallo = None
+
+
+def test_two_steps_on_one_data_cannot_see_each_others_state(monkeypatch):
+    """Two forwards on the SAME Data at the same positions, then the backward of the first energy and of the second: both
+    force arrays are the lone evaluation's bit for bit, and both steps end with nothing pending -- with everything the
+    layers can hand to each other in flight (gradients as partial sums, the next layer's projection: boundary mode 1).
+    (Deterministic algorithms: the scatter-adds of the CPU restatements otherwise add in an order that differs run to run.)"""
+    import hermnet_amd.layer as lmod
+    from hermnet_amd import switches
+    _reference_ops(monkeypatch)
+    monkeypatch.setattr(lmod, "_bwd_sums_deferrable", lambda graph, H: True)
+    monkeypatch.setattr(switches, "boundary_mode", 1)
+    g = Golden("alloy108")
+    model = _frozen_model(g)
+    deterministic = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        lone = g.data()
+        lone.pos.requires_grad_(True)
+        e0 = model(lone)
+        f0 = -torch.autograd.grad(e0.sum(), lone.pos)[0]
+        d = g.data()
+        d.pos.requires_grad_(True)
+        e1 = model(d)
+        step1 = d._hn_step
+        e2 = model(d)
+        step2 = d._hn_step
+        f1 = -torch.autograd.grad(e1.sum(), d.pos)[0]
+        f2 = -torch.autograd.grad(e2.sum(), d.pos)[0]
+    finally:
+        torch.use_deterministic_algorithms(deterministic)
+    assert step1 is not step2
+    assert torch.equal(e1, e0) and torch.equal(e2, e0)
+    assert torch.equal(f1, f0) and torch.equal(f2, f0)
+    assert rel_err(f0, g.forces) < 1e-5
+    for step in (step1, step2):
+        assert not step.pending and not step.pre_next
+
+
+class _StubPlan(object):
+    """What the read-out's sums read of a `sharding.ShardPlan`."""
+    world, group = 1, None
+
+    def __init__(self, owned_mask, num_graphs, num_atoms_global):
+        self.owned_mask, self.num_graphs, self.num_atoms_global = owned_mask, num_graphs, num_atoms_global
+
+    def graph_order(self, batch):
+        return torch.argsort(batch, stable=True), torch.bincount(batch, minlength=self.num_graphs)
+
+
+@pytest.mark.parametrize("intensive", [False, True])
+def test_read_out_sums_in_their_five_forms(intensive):
+    """`HVNet._graph_energies` on hand-made per-row energies; the expected value of every form is the expression the read-out
+    used before it was cut out of `HVNet.forward`."""
+    from types import SimpleNamespace
+    from hermnet_amd.hermnet import GraphEnergies
+    model = hn.HVNet(["Si"], num_layers=1, hidden_channels=8, num_rbf=4, intensive=intensive)
+    gen = torch.Generator().manual_seed(5)
+    e_rows = torch.randn(9, generator=gen)
+    row_of_node = torch.tensor([0, 2, 3, 5, 6, 8])          # (rows 1, 4, 7: padding)
+    batch = torch.tensor([1, 0, 1, 1, 0, 1])
+    lengths = torch.bincount(batch, minlength=2)
+    one = SimpleNamespace(num_graphs=1, num_atoms=6, row_of_node=row_of_node, graph_perm=None, graph_lengths=None)
+    two = SimpleNamespace(num_graphs=2, num_atoms=6, row_of_node=row_of_node, graph_perm=torch.argsort(batch, stable=True),
+                          graph_lengths=lengths, _row_graph=None)
+    two_train = SimpleNamespace(num_graphs=2, num_atoms=6, row_of_node=row_of_node, graph_perm=None, graph_lengths=lengths)
+    own = torch.tensor([1, 1, 0, 1, 0, 1], dtype=torch.bool)
+    per_atom = e_rows.index_select(0, row_of_node)
+    e_own, ownf = per_atom * own.to(per_atom.dtype), own.to(per_atom.dtype)
+    perm = torch.argsort(batch, stable=True)
+    seg = lambda v: torch.segment_reduce(v.index_select(0, perm), "sum", lengths=lengths, unsafe=True)
+    div = (lambda e, n: e / n) if intensive else (lambda e, n: e)
+    zero = torch.zeros(1, dtype=torch.long)
+    table = [
+        # (case, graph, batch, shard, masked, expected)
+        ("shard, one graph, owned rows", one, zero.expand(6), _StubPlan(own, 1, 11), True,
+         div(e_rows.sum().reshape(1), max(11, 1))),
+        ("single graph", one, zero.expand(6), None, True, div(e_rows.sum().reshape(1), max(one.num_atoms, 1))),
+        ("ordered segment sums", two, batch, None, False,
+         div(GraphEnergies.apply(e_rows, two, batch), lengths.clamp(min=1).to(e_rows.dtype))),
+        ("shard, atom order, one graph", one, zero.expand(6), _StubPlan(own, 1, 11), False,
+         div(e_own.sum().reshape(1), ownf.sum().reshape(1).clamp(min=1))),
+        ("shard, atom order, two graphs", two_train, batch, _StubPlan(own, 2, 11), False,
+         div(seg(e_own), seg(ownf).clamp(min=1))),
+        ("train: index_add", two_train, batch, None, False,
+         div(torch.zeros(2, dtype=e_rows.dtype).index_add(0, batch, per_atom), lengths.clamp(min=1).to(e_rows.dtype))),
+    ]
+    for case, graph, b, shard, masked, want in table:
+        got = model._graph_energies(e_rows, graph, b, shard, masked)
+        assert got.shape == want.shape and torch.equal(got, want), case
+    # (the ordered form is the plain scatter of the reference, hermnet.py:130, up to the order of the additions)
+    assert torch.allclose(table[2][5], table[5][5], rtol=1e-6, atol=1e-6)
