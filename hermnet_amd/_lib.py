@@ -171,6 +171,15 @@ SIGNATURES = {
     "hermnet_host_rbf_row": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
                                             ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float, c_fp, c_fp]),
     "hermnet_host_neighbor_geometry": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_double, ctypes.c_int, c_fp, c_fp]),
+    "hermnet_md_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_ulong] + [c_fp] * 16),
+    "hermnet_md_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] + [c_fp] * 12 +
+                          [ctypes.c_long, c_fp, c_fp]),
+    "hermnet_md_noise": (ctypes.c_int, [ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int, c_fp, c_fp, c_fp]),
+    "hermnet_host_md_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_ulong] +
+                                [c_fp] * 15),
+    "hermnet_host_md_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] + [c_fp] * 12 +
+                               [ctypes.c_long, c_fp]),
+    "hermnet_host_md_noise": (ctypes.c_int, [ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int, c_fp, c_fp]),
 }
 
 _lib = None

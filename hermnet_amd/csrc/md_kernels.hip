@@ -1,0 +1,321 @@
+// gfx950: the device-resident MD integrator (hermnet_amd/md.py: DeviceMD).  Two entry points bracket the captured step --
+// hermnet_md_advance in front of the neighbour search, hermnet_md_finish behind the force backward -- so that a replay of the
+// hipGraph IS a time step: coordinates, velocities, thermostat noise, halt logic and the observables log never leave the
+// device.  Plain streaming passes (one thread per atom, 256-lane workgroups, 48 B of float64 state per atom and pass).
+//
+// The arithmetic is md_step.h's, shared with the host twins at the end of this file; contraction is off for the whole
+// file, so device, host twin and a numpy float64 transcription agree bit for bit.
+//
+// state [4] int64 = (step, halt code, step at which it halted, mode).  Halted (code != 0): every kernel here returns at
+// once.  Mode 1 ("prime"): advance only rewrites the float32 input, finish only copies the forces to f_prev and clears the
+// mode -- the same capture serves the first force evaluation and the one behind a recapture.
+// Who writes `state`: the LAST kernel of hermnet_md_finish alone (one workgroup), so every other workgroup of a step reads
+// the words the step began with, whatever the order they are scheduled in.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/hermnet_hip.h"
+#include "md_step.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+struct MdAdvanceArgs {
+  int n, num_graphs, flags;
+  double *x, *v, *x0, *v0;
+  int *image, *image0;
+  const float* f_prev;
+  const double *kick, *c1, *sigma;
+  const long* batch;
+  const float* cell;
+  const double* inv_cell;
+  float* pos32;
+  const long* state;
+  double dt;
+  uint64_t seed;
+};
+
+struct MdFinishArgs {
+  int n, num_graphs;
+  double *x, *v;
+  const double *x0, *v0;
+  int* image;
+  const int* image0;
+  float* f_prev;
+  const float *forces, *energy;
+  const long* total;
+  long capacity;
+  const double *kick, *half_mass;
+  const int* graph_ptr;
+  float* pos32;
+  double *ke_atom, *log;
+  long log_steps;
+  long* state;
+};
+
+__host__ __device__ inline void md_advance_one(const MdAdvanceArgs& a, int i, long step, long mode) {
+  double x[3], v[3];
+  for (int k = 0; k < 3; ++k) x[k] = a.x[3 * (size_t)i + k];
+  if (mode == 0) {
+    int image[3];
+    float f[3];
+    for (int k = 0; k < 3; ++k) {
+      v[k] = a.v[3 * (size_t)i + k];
+      image[k] = a.image[3 * (size_t)i + k];
+      f[k] = a.f_prev[3 * (size_t)i + k];
+      a.x0[3 * (size_t)i + k] = x[k];
+      a.v0[3 * (size_t)i + k] = v[k];
+      a.image0[3 * (size_t)i + k] = image[k];
+    }
+    long g = a.batch ? a.batch[i] : 0;
+    g = g < 0 ? 0 : (g >= a.num_graphs ? a.num_graphs - 1 : g);      // (a broken `batch` must not read out of bounds)
+    const int langevin = a.flags & HN_MD_LANGEVIN;
+    double xi[3] = {0.0, 0.0, 0.0};
+    if (langevin) {
+      uint32_t w[8];
+      md_noise_words(a.seed, (uint64_t)step, (uint32_t)i, w);
+      md_gaussians(w, xi);
+    }
+    md_advance_atom(x, v, f, a.kick[i], a.dt, langevin, langevin ? a.c1[g] : 0.0, langevin ? a.sigma[i] : 0.0, xi);
+    if (a.flags & HN_MD_WRAP) {
+      double cell[9], inv[9];
+      for (int k = 0; k < 9; ++k) {
+        cell[k] = (double)a.cell[9 * g + k];
+        inv[k] = a.inv_cell[9 * g + k];
+      }
+      md_wrap_atom(x, image, cell, inv);
+    }
+    for (int k = 0; k < 3; ++k) {
+      a.x[3 * (size_t)i + k] = x[k];
+      a.v[3 * (size_t)i + k] = v[k];
+      a.image[3 * (size_t)i + k] = image[k];
+    }
+  }
+  for (int k = 0; k < 3; ++k) a.pos32[3 * (size_t)i + k] = (float)x[k];
+}
+
+__host__ __device__ inline void md_finish_one(const MdFinishArgs& a, int i, long code, long mode) {
+  if (mode != 0) {
+    if (code == 0)
+      for (int k = 0; k < 3; ++k) a.f_prev[3 * (size_t)i + k] = a.forces[3 * (size_t)i + k];
+    return;
+  }
+  if (code != 0) {        // the step is void: back to the state it began with
+    for (int k = 0; k < 3; ++k) {
+      const double x = a.x0[3 * (size_t)i + k];
+      a.x[3 * (size_t)i + k] = x;
+      a.v[3 * (size_t)i + k] = a.v0[3 * (size_t)i + k];
+      a.image[3 * (size_t)i + k] = a.image0[3 * (size_t)i + k];
+      a.pos32[3 * (size_t)i + k] = (float)x;
+    }
+    return;
+  }
+  double v[3];
+  float f[3];
+  for (int k = 0; k < 3; ++k) {
+    v[k] = a.v[3 * (size_t)i + k];
+    f[k] = a.forces[3 * (size_t)i + k];
+  }
+  a.ke_atom[i] = md_finish_atom(v, f, a.kick[i], a.half_mass[i]);
+  for (int k = 0; k < 3; ++k) {
+    a.v[3 * (size_t)i + k] = v[k];
+    a.f_prev[3 * (size_t)i + k] = f[k];
+  }
+}
+
+__host__ __device__ inline int md_not_finite(float e) { return !(e - e == 0.0f); }
+
+__global__ __launch_bounds__(256) void md_advance_kernel(MdAdvanceArgs a) {
+  const long step = a.state[0], code = a.state[1], mode = a.state[3];
+  if (code != 0) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < a.n) md_advance_one(a, i, step, mode);
+}
+
+// Every workgroup works the step's halt code out for itself (B energies from the cache: nothing to what a launch costs).
+__device__ inline long md_block_code(const MdFinishArgs& a) {
+  int bad = 0;
+  for (int g = threadIdx.x; g < a.num_graphs; g += blockDim.x) bad |= md_not_finite(a.energy[g]);
+  bad = __syncthreads_or(bad);
+  return md_step_code(a.total[0], a.total[1], a.capacity, bad);
+}
+
+__global__ __launch_bounds__(256) void md_finish_atoms_kernel(MdFinishArgs a) {
+  const long halted = a.state[1], mode = a.state[3];
+  if (halted != 0) return;
+  const long code = md_block_code(a);
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < a.n) md_finish_one(a, i, code, mode);
+}
+
+// One workgroup per graph: its atoms' kinetic energies in a fixed order (lane-strided partial sums, then a fixed tree),
+// and the graph's log row.
+__global__ __launch_bounds__(256) void md_log_kernel(MdFinishArgs a) {
+  __shared__ double part[256];
+  const long step = a.state[0], halted = a.state[1], mode = a.state[3];
+  if (halted != 0 || mode != 0) return;
+  if (md_block_code(a) != 0) return;
+  const int g = blockIdx.x, lo = max(a.graph_ptr[g], 0), hi = min(a.graph_ptr[g + 1], a.n);
+  double s = 0.0;
+  for (int i = lo + (int)threadIdx.x; i < hi; i += 256) s = s + a.ke_atom[i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int m = 128; m >= 1; m >>= 1) {
+    if ((int)threadIdx.x < m) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + m];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    double* row = a.log + ((size_t)(step % a.log_steps) * a.num_graphs + g) * 3;
+    row[0] = (double)a.energy[g];
+    row[1] = part[0];
+    row[2] = (double)a.total[0];
+  }
+}
+
+__global__ __launch_bounds__(64) void md_commit_kernel(MdFinishArgs a) {
+  const long step = a.state[0], halted = a.state[1], mode = a.state[3];
+  if (halted != 0) return;
+  const long code = md_block_code(a);
+  if (threadIdx.x != 0) return;
+  if (code != 0) {
+    a.state[1] = code;
+    a.state[2] = step;
+  } else if (mode == 0) {
+    a.state[0] = step + 1;
+  }
+  if (mode != 0) a.state[3] = 0;
+}
+
+__global__ __launch_bounds__(256) void md_noise_kernel(uint64_t seed, uint64_t step, int n, uint32_t* words, double* gauss) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  uint32_t w[8];
+  double xi[3];
+  md_noise_words(seed, step, (uint32_t)i, w);
+  md_gaussians(w, xi);
+  if (words)
+    for (int k = 0; k < 8; ++k) words[8 * (size_t)i + k] = w[k];
+  if (gauss)
+    for (int k = 0; k < 3; ++k) gauss[3 * (size_t)i + k] = xi[k];
+}
+
+bool md_advance_args_ok(const MdAdvanceArgs& a) {
+  if (a.n < 0 || a.num_graphs < 1 || (a.flags & ~(HN_MD_LANGEVIN | HN_MD_WRAP))) return false;
+  if (a.n == 0) return true;
+  if (!a.x || !a.v || !a.x0 || !a.v0 || !a.image || !a.image0 || !a.f_prev || !a.kick || !a.pos32 || !a.state) return false;
+  if ((a.flags & HN_MD_LANGEVIN) && (!a.c1 || !a.sigma)) return false;
+  if ((a.flags & HN_MD_WRAP) && (!a.cell || !a.inv_cell)) return false;
+  return true;
+}
+
+bool md_finish_args_ok(const MdFinishArgs& a) {
+  if (a.n < 0 || a.num_graphs < 1 || a.log_steps < 1 || a.capacity < 0) return false;
+  if (!a.state || !a.energy || !a.total || !a.graph_ptr || !a.log) return false;
+  if (a.n == 0) return true;
+  return a.x && a.v && a.x0 && a.v0 && a.image && a.image0 && a.f_prev && a.forces && a.kick && a.half_mass && a.pos32 &&
+         a.ke_atom;
+}
+
+}  // namespace
+
+extern "C" int hermnet_md_advance(int num_atoms, int num_graphs, int flags, double dt, unsigned long seed, double* x, double* v, double* x0,
+                                  double* v0, int* image, int* image0, const float* f_prev, const double* kick,
+                                  const double* c1, const double* sigma, const long* batch, const float* cell,
+                                  const double* inv_cell, float* pos32, const long* state, void* stream) {
+  const MdAdvanceArgs a = {num_atoms, num_graphs, flags, x, v, x0, v0, image, image0, f_prev, kick, c1, sigma, batch, cell, inv_cell, pos32,
+                           state, dt, (uint64_t)seed};
+  if (!md_advance_args_ok(a)) return HN_ERR_BAD_ARG;
+  if (num_atoms == 0) return HN_OK;
+  hipLaunchKernelGGL(md_advance_kernel, dim3((unsigned)((num_atoms + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_md_finish(int num_atoms, int num_graphs, const int* graph_ptr, const float* forces, const float* energy,
+                                 const long* total, long capacity, double* x, double* v, const double* x0, const double* v0,
+                                 int* image, const int* image0, float* f_prev, const double* kick, const double* half_mass,
+                                 float* pos32, double* ke_atom, double* log, long log_steps, long* state, void* stream) {
+  const MdFinishArgs a = {num_atoms, num_graphs, x, v, x0, v0, image, image0, f_prev, forces, energy, total, capacity, kick,
+                          half_mass, graph_ptr, pos32, ke_atom, log, log_steps, state};
+  if (!md_finish_args_ok(a)) return HN_ERR_BAD_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (num_atoms > 0)
+    hipLaunchKernelGGL(md_finish_atoms_kernel, dim3((unsigned)((num_atoms + 255) / 256)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(md_log_kernel, dim3((unsigned)num_graphs), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(md_commit_kernel, dim3(1), dim3(64), 0, s, a);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+extern "C" int hermnet_md_noise(unsigned long seed, unsigned long step, int n, unsigned* out_words, double* out_gauss,
+                                void* stream) {
+  if (n < 0 || (!out_words && !out_gauss)) return HN_ERR_BAD_ARG;
+  if (n == 0) return HN_OK;
+  hipLaunchKernelGGL(md_noise_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (uint64_t)seed,
+                     (uint64_t)step, n, out_words, out_gauss);
+  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
+}
+
+// ---- host twins: the same functions in a CPU loop (all pointers HOST pointers) ----------------------------------------------
+extern "C" int hermnet_host_md_noise(unsigned long seed, unsigned long step, int n, unsigned* out_words_host,
+                                     double* out_gauss_host) {
+  if (n < 0 || (!out_words_host && !out_gauss_host)) return HN_ERR_BAD_ARG;
+  for (int i = 0; i < n; ++i) {
+    uint32_t w[8];
+    double xi[3];
+    md_noise_words((uint64_t)seed, (uint64_t)step, (uint32_t)i, w);
+    md_gaussians(w, xi);
+    if (out_words_host)
+      for (int k = 0; k < 8; ++k) out_words_host[8 * (size_t)i + k] = w[k];
+    if (out_gauss_host)
+      for (int k = 0; k < 3; ++k) out_gauss_host[3 * (size_t)i + k] = xi[k];
+  }
+  return HN_OK;
+}
+
+extern "C" int hermnet_host_md_advance(int num_atoms, int num_graphs, int flags, double dt, unsigned long seed, double* x_host, double* v_host,
+                                       double* x0_host, double* v0_host, int* image_host, int* image0_host,
+                                       const float* f_prev_host, const double* kick_host, const double* c1_host,
+                                       const double* sigma_host, const long* batch_host, const float* cell_host,
+                                       const double* inv_cell_host, float* pos32_host, const long* state_host) {
+  const MdAdvanceArgs a = {num_atoms, num_graphs, flags, x_host, v_host, x0_host, v0_host, image_host, image0_host, f_prev_host, kick_host,
+                           c1_host, sigma_host, batch_host, cell_host, inv_cell_host, pos32_host, state_host, dt, (uint64_t)seed};
+  if (!md_advance_args_ok(a)) return HN_ERR_BAD_ARG;
+  if (num_atoms == 0 || state_host[1] != 0) return HN_OK;
+  for (int i = 0; i < num_atoms; ++i) md_advance_one(a, i, state_host[0], state_host[3]);
+  return HN_OK;
+}
+
+extern "C" int hermnet_host_md_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const float* forces_host,
+                                      const float* energy_host, const long* total_host, long capacity, double* x_host,
+                                      double* v_host, const double* x0_host, const double* v0_host, int* image_host,
+                                      const int* image0_host, float* f_prev_host, const double* kick_host,
+                                      const double* half_mass_host, float* pos32_host, double* ke_atom_host, double* log_host,
+                                      long log_steps, long* state_host) {
+  const MdFinishArgs a = {num_atoms, num_graphs, x_host, v_host, x0_host, v0_host, image_host, image0_host, f_prev_host,
+                          forces_host, energy_host, total_host, capacity, kick_host, half_mass_host, graph_ptr_host, pos32_host,
+                          ke_atom_host, log_host, log_steps, state_host};
+  if (!md_finish_args_ok(a)) return HN_ERR_BAD_ARG;
+  const long step = state_host[0], mode = state_host[3];
+  if (state_host[1] != 0) return HN_OK;
+  int bad = 0;
+  for (int g = 0; g < num_graphs; ++g) bad |= md_not_finite(energy_host[g]);
+  const long code = md_step_code(total_host[0], total_host[1], capacity, bad);
+  for (int i = 0; i < num_atoms; ++i) md_finish_one(a, i, code, mode);
+  if (code == 0 && mode == 0) {
+    for (int g = 0; g < num_graphs; ++g) {
+      double s = 0.0;
+      const int lo = graph_ptr_host[g] < 0 ? 0 : graph_ptr_host[g], hi = graph_ptr_host[g + 1] > num_atoms ? num_atoms : graph_ptr_host[g + 1];
+      for (int i = lo; i < hi; ++i) s = s + ke_atom_host[i];
+      double* row = log_host + ((size_t)(step % log_steps) * num_graphs + g) * 3;
+      row[0] = (double)energy_host[g];
+      row[1] = s;
+      row[2] = (double)total_host[0];
+    }
+    state_host[0] = step + 1;
+  }
+  if (code != 0) {
+    state_host[1] = code;
+    state_host[2] = step;
+  }
+  if (mode != 0) state_host[3] = 0;
+  return HN_OK;
+}

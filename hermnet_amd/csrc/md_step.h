@@ -1,0 +1,102 @@
+// The per-atom arithmetic of the device-resident integrator (md_kernels.hip): ONE text for the device kernels, their host
+// twins (hermnet_host_md_advance / _finish) and -- transcribed operation by operation -- the numpy float64 references of
+// tests/test_md_host.py.  Only IEEE +, x and floor on doubles, one rounding each (contraction off), in the order written:
+// device, host and numpy agree bit for bit.  Everything that needs exp / sqrt / a division (kick, c1, sigma, the inverse
+// cell) is made once on the host in float64; log / cos / sqrt appear in the Gaussian noise alone (md_gaussians).
+#ifndef HERMNET_MD_STEP_H
+#define HERMNET_MD_STEP_H
+
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define HN_HD __host__ __device__
+#else
+#define HN_HD
+#endif
+
+// ---- Philox4x32-10 (Salmon et al., SC'11; the Random123 known answers are checked in tests/test_md_host.py) --------------
+HN_HD inline void md_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+  uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+  for (int r = 0; r < 10; ++r) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+    const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// The eight words of (seed, step, atom): counter (atom, step low, step high, stream), stream 0 then stream 1.
+HN_HD inline void md_noise_words(uint64_t seed, uint64_t step, uint32_t atom, uint32_t w[8]) {
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  uint32_t ctr[4] = {atom, (uint32_t)step, (uint32_t)(step >> 32), 0u};
+  md_philox4x32_10(ctr, key, w);
+  ctr[3] = 1u;
+  md_philox4x32_10(ctr, key, w + 4);
+}
+
+// Two words -> a 53-bit integer; u1 = (k + 1) 2^-53 in (0, 1] (its log is finite), u2 = k 2^-53 in [0, 1).
+HN_HD inline double md_u53(uint32_t hi, uint32_t lo) {
+  return (double)(((uint64_t)(hi >> 5) << 26) | (uint64_t)(lo >> 6));
+}
+
+// Three standard Gaussians by Box-Muller in float64: stream 0 gives the pair (cos, sin), stream 1 the third (cos).
+HN_HD inline void md_gaussians(const uint32_t w[8], double xi[3]) {
+  const double two_pi = 6.283185307179586476925286766559, s = 1.0 / 9007199254740992.0;
+  const double ra = sqrt(-2.0 * log((md_u53(w[0], w[1]) + 1.0) * s)), ta = two_pi * (md_u53(w[2], w[3]) * s);
+  const double rb = sqrt(-2.0 * log((md_u53(w[4], w[5]) + 1.0) * s)), tb = two_pi * (md_u53(w[6], w[7]) * s);
+  xi[0] = ra * cos(ta);
+  xi[1] = ra * sin(ta);
+  xi[2] = rb * cos(tb);
+}
+
+// ---- the step -------------------------------------------------------------------------------------------------------------
+// Triclinic wrap: s = x cell^-1 (rows of `cell` are the lattice vectors), x -= floor(s) cell, image += floor(s).  A
+// coordinate that is not finite, or 2^30 cells away, is left alone (the cast below would be undefined).
+HN_HD inline void md_wrap_atom(double x[3], int image[3], const double cell[9], const double inv[9]) {
+#pragma clang fp contract(off)
+  double n[3];
+  for (int k = 0; k < 3; ++k) {
+    const double s = (x[0] * inv[k] + x[1] * inv[3 + k]) + x[2] * inv[6 + k];
+    const double fl = floor(s);
+    n[k] = (fl >= -1073741824.0 && fl <= 1073741824.0) ? fl : 0.0;
+  }
+  for (int j = 0; j < 3; ++j) x[j] = x[j] - ((n[0] * cell[j] + n[1] * cell[3 + j]) + n[2] * cell[6 + j]);
+  for (int k = 0; k < 3; ++k) image[k] += (int)n[k];
+}
+
+// The first half of a step, up to the coordinates the forces are evaluated at.  NVE (velocity Verlet): v += kick f,
+// x += dt v.  Langevin (BAOAB): v += kick f, x += dt/2 v, v = c1 v + sigma xi, x += dt/2 v.  f: the last accepted forces.
+HN_HD inline void md_advance_atom(double x[3], double v[3], const float f[3], double kick, double dt, int langevin, double c1,
+                                  double sigma, const double xi[3]) {
+#pragma clang fp contract(off)
+  for (int k = 0; k < 3; ++k) v[k] = v[k] + kick * (double)f[k];
+  if (!langevin) {
+    for (int k = 0; k < 3; ++k) x[k] = x[k] + dt * v[k];
+  } else {
+    const double h = 0.5 * dt;
+    for (int k = 0; k < 3; ++k) x[k] = x[k] + h * v[k];
+    for (int k = 0; k < 3; ++k) v[k] = c1 * v[k] + sigma * xi[k];
+    for (int k = 0; k < 3; ++k) x[k] = x[k] + h * v[k];
+  }
+}
+
+// The second half kick with the new forces; returns the atom's kinetic energy half_mass |v|^2.
+HN_HD inline double md_finish_atom(double v[3], const float f[3], double kick, double half_mass) {
+#pragma clang fp contract(off)
+  for (int k = 0; k < 3; ++k) v[k] = v[k] + kick * (double)f[k];
+  return half_mass * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+}
+
+// Halt code of a step from what the force evaluation left behind: the list's flags (+ bit 2 where only the count says
+// so) in the low bits, HN_MD_HALT_NONFINITE for an energy that is not finite (the stale-weight guard answers with NaN).
+HN_HD inline long long md_step_code(long long found, long long flags, long long capacity, int nonfinite) {
+  long long code = flags & 255;
+  if (found > capacity) code |= 4;
+  if (nonfinite) code |= 256;
+  return code;
+}
+
+#endif  // HERMNET_MD_STEP_H

@@ -122,9 +122,10 @@ class GraphedMDStep(object):
     stays valid for the next sane cell."""
 
     def __init__(self, model, atomic_number, cell, pos, capacity=None, warmup=3, reference_compat=False, stress=False,
-                 variable_cell=False):
+                 variable_cell=False, hooks=None):
         from .neighbor import neighbor_search, padded_capacity
         self.reference_compat = bool(reference_compat)      # edge conventions of the reference's own pipeline (neighbor.py)
+        self._hooks = hooks
         if not pos.is_cuda or cell is None:
             raise RuntimeError("GraphedMDStep needs GPU tensors and a periodic cell")
         if model.training:
@@ -161,6 +162,17 @@ class GraphedMDStep(object):
         parts += [w.double().reshape(-1) for w in out[2:]]
         return out + (total, torch.cat(parts))
 
+    def _step(self):
+        """What is captured: `_eager()`, or with `hooks=(before, behind)` (md.DeviceMD: the integrator's kernels)
+        `before(self)`, `_eager()`, `behind(self, its results)` -- work enqueued in front of the search and behind the force
+        backward becomes part of every replay."""
+        if self._hooks is None:
+            return self._eager()
+        self._hooks[0](self)
+        out = self._eager()
+        self._hooks[1](self, out)
+        return out
+
     def stale(self):
         """True once the model's derived weight copies were dropped after the capture (`load_state_dict`, `.to()`,
         `train()` / `eval()`, `invalidate_caches()`): the captured launches read the OLD copies -- capture again."""
@@ -169,7 +181,7 @@ class GraphedMDStep(object):
     def _capture(self, capacity):
         self.capacity = capacity
         self._epoch = self.model.__dict__.get("_cache_epoch", 0)
-        self.graph, out = _capture(self._eager, self._warmup)      # (warm-up: also the cell on the host, the row layout)
+        self.graph, out = _capture(self._step, self._warmup)      # (warm-up: also the cell on the host, the row layout)
         self.energy, self.forces, self.total, self.packed = out[0], out[1], out[-2], out[-1]
         if self.stress:
             self.virial = out[2]
@@ -250,8 +262,9 @@ class GraphedBatchMDStep(GraphedMDStep):
     degenerate cell of one replica -- that replica listed no pair, discard the step --, bit 4 a `batch` that decreases."""
 
     def __init__(self, model, atomic_number, cell, pos, batch, num_graphs, capacity=None, warmup=3, reference_compat=False,
-                 stress=False):
+                 stress=False, hooks=None):
         from .neighbor import neighbor_search, padded_capacity
+        self._hooks = hooks
         if not pos.is_cuda:
             raise RuntimeError("GraphedBatchMDStep needs GPU tensors")
         if model.training:

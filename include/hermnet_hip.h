@@ -19,7 +19,7 @@
  * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -841,6 +841,64 @@ int hermnet_host_rbf_row(const float* offset_host, int num_rbf, float inv_rc, fl
  * latter through an undefined cast; it refuses them now).  All pointers are HOST pointers. */
 int hermnet_host_neighbor_geometry(const double* cell_host, const double* lo_host, const double* hi_host, double rc,
                                    int num_atoms, double* geom_host /* [22] */, int* grid_host /* [7] */);
+
+/* Device-resident MD (added within ABI v13: new entry points only; hermnet_amd/md.py: DeviceMD; csrc/md_kernels.hip, md_step.h).
+ * The reference leaves dynamics to ASE on the host (/root/reference/HermNet/plugin/ase_interface/calculator.py:49: one
+ * list + model call per step).  Here hermnet_md_advance is enqueued in FRONT of the captured neighbour search and
+ * hermnet_md_finish BEHIND the force backward, so that one replay of the step's hipGraph is one time step and nothing is
+ * read or written by the host in between.  Units: eV, Angstrom, fs; masses enter through the caller's coefficients only.
+ *
+ * Caller-owned state (all allocated outside the capture):
+ *   x, v, x0, v0 [N,3] float64  coordinates / velocities and their start-of-step backup;   f_prev [N,3] float32 the last
+ *   accepted forces (the step's own force output does not exist when advance is recorded);   image, image0 [N,3] int32
+ *   lattice vectors removed by wrapping (x + image cell = the unwrapped path) and their backup;   kick [N] = dt / (2 m_i);
+ *   half_mass [N] = m_i / 2 (0 for an atom that is held);   c1 [B], sigma [N] the Langevin coefficients exp(-friction dt)
+ *   and sqrt(kB T (1 - c1^2) / m_i);   batch [N] int64 non-decreasing or NULL (one graph), graph_ptr [B+1] int32 its atom
+ *   ranges;   cell [B,9] float32 -- the tensor the search reads -- and inv_cell [B,9] float64 its inverse (made once on the
+ *   host: the kernels only add, multiply and floor);   pos32 [N,3] float32 the captured coordinate input of the model;
+ *   ke_atom [N] float64 scratch;   log [log_steps,B,3] float64 ring of (E_pot, E_kin, edges found) per step and graph;
+ *   state [4] int64 = (step, halt code, step at which it halted, mode).
+ *
+ * hermnet_md_advance   halt code != 0: nothing.  mode 1 ("prime"): pos32 = float(x), nothing else.  Otherwise x0, v0, image0
+ *   = x, v, image, then NVE (velocity Verlet) v += kick f_prev, x += dt v, or with HN_MD_LANGEVIN BAOAB: v += kick f_prev,
+ *   x += dt/2 v, v = c1 v + sigma xi, x += dt/2 v; with HN_MD_WRAP s = x cell^-1, x -= floor(s) cell, image += floor(s);
+ *   pos32 = float(x).
+ * hermnet_md_finish    halt code != 0: nothing.  The step's code = the list's flags total[1] (low 8 bits; bit 2 also where
+ *   total[0] > capacity) | HN_MD_HALT_NONFINITE if an energy [B] is not finite.  mode 1: f_prev = forces if the code is 0;
+ *   mode = 0 (no kick, no log row, no step).  Code != 0: x, v, image = x0, v0, image0, pos32 = float(x), state = (step, code,
+ *   step, 0), no log row: the state is that of the last completed step and every later replay changes nothing.  Code 0:
+ *   v += kick forces, f_prev = forces, log[step % log_steps][g] = (energy[g], sum of half_mass |v|^2 over graph g -- float64,
+ *   fixed order, no atomics --, total[0]), step += 1.  Three launches; only the last one writes `state`.
+ * Noise: xi of (seed, step, atom) from Philox4x32-10 with key (seed low, seed high) and counters (atom, step low, step high,
+ *   stream): stream 0 gives words w0..w3, stream 1 w4..w7; u(a, b) = ((a >> 5) 2^26 + (b >> 6)); Box-Muller in float64:
+ *   r = sqrt(-2 log((u(w0,w1) + 1) 2^-53)), t = 2 pi u(w2,w3) 2^-53, xi = (r cos t, r sin t, the cosine branch of w4..w7).
+ *   It depends on nothing else (launch geometry, how a run is split).  hermnet_md_noise writes out_words [n,8] uint32 and
+ *   out_gauss [n,3] float64 (either may be NULL) for atoms 0..n-1.
+ * The per-atom arithmetic is IEEE +, x, floor on doubles, one rounding each, no contraction; the hermnet_host_md_* twins run
+ * the same text in a CPU loop on HOST pointers (no stream), bit for bit what the device computes for the same forces and xi. */
+#define HN_MD_LANGEVIN 1
+#define HN_MD_WRAP 2
+#define HN_MD_HALT_NONFINITE 256
+int hermnet_md_advance(int num_atoms, int num_graphs, int flags, double dt, unsigned long seed, double* x, double* v, double* x0,
+                       double* v0, int* image, int* image0, const float* f_prev, const double* kick, const double* c1,
+                       const double* sigma, const long* batch, const float* cell, const double* inv_cell, float* pos32,
+                       const long* state, void* stream);
+int hermnet_md_finish(int num_atoms, int num_graphs, const int* graph_ptr, const float* forces, const float* energy,
+                      const long* total, long capacity, double* x, double* v, const double* x0, const double* v0, int* image,
+                      const int* image0, float* f_prev, const double* kick, const double* half_mass, float* pos32,
+                      double* ke_atom, double* log, long log_steps, long* state, void* stream);
+int hermnet_md_noise(unsigned long seed, unsigned long step, int n, unsigned* out_words, double* out_gauss, void* stream);
+int hermnet_host_md_advance(int num_atoms, int num_graphs, int flags, double dt, unsigned long seed, double* x_host,
+                            double* v_host, double* x0_host, double* v0_host, int* image_host, int* image0_host,
+                            const float* f_prev_host, const double* kick_host, const double* c1_host, const double* sigma_host,
+                            const long* batch_host, const float* cell_host, const double* inv_cell_host, float* pos32_host,
+                            const long* state_host);
+int hermnet_host_md_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const float* forces_host,
+                           const float* energy_host, const long* total_host, long capacity, double* x_host, double* v_host,
+                           const double* x0_host, const double* v0_host, int* image_host, const int* image0_host,
+                           float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
+                           double* ke_atom_host, double* log_host, long log_steps, long* state_host);
+int hermnet_host_md_noise(unsigned long seed, unsigned long step, int n, unsigned* out_words_host, double* out_gauss_host);
 
 #ifdef __cplusplus
 }

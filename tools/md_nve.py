@@ -4,7 +4,10 @@
 that the forces are the gradient of the energy the model reports: the total energy must stay put while kinetic and
 potential energy trade places.
 
-    python tools/md_nve.py [--reps 6 6 6] [--steps 200] [--dt 0.5] [--temp 300]
+    python tools/md_nve.py [--reps 6 6 6] [--steps 200] [--dt 0.5] [--temp 300] [--device-md]
+
+`--device-md`: the same trajectory (same cell, model and start velocities) through `hermnet_amd.DeviceMD` -- the integrator
+inside the replayed graph, float64 coordinates, one `fetch()` at the end instead of a host round trip per step.
 
 Units: eV, Angstrom, amu, fs (the synthetic model is random-initialised: the numbers mean nothing physically)."""
 import argparse
@@ -33,7 +36,8 @@ def energy_forces(model, pos, z, cell, rc, fixed=None):
     return float(e.detach()[0]), f
 
 
-def run(reps=(6, 6, 6), steps=200, dt=0.5, temp=300.0, seed=0, rc=5.0, log=None, state_seed=11, fixed_list=False):
+def run(reps=(6, 6, 6), steps=200, dt=0.5, temp=300.0, seed=0, rc=5.0, log=None, state_seed=11, fixed_list=False,
+        device_md=False):
     dev = torch.device("cuda:0")
     pos_np, cell_np, z_np = synth.fcc_alloy_atoms(reps=reps, seed=seed)
     pos = torch.from_numpy(pos_np).float().to(dev)
@@ -48,6 +52,23 @@ def run(reps=(6, 6, 6), steps=200, dt=0.5, temp=300.0, seed=0, rc=5.0, log=None,
     gen = torch.Generator(device="cpu").manual_seed(seed + 1)
     v = (torch.randn(pos.shape, generator=gen).to(dev) * torch.sqrt(KB * temp / m))
     v -= (v * m).sum(0) / m.sum()                      # no centre-of-mass drift
+    if device_md:
+        if fixed_list:
+            raise SystemExit("--device-md rebuilds the list inside every replay: there is no --fixed-list form of it")
+        md = hn.DeviceMD(model, z, cell, pos_np, [MASS[int(v_)] for v_ in z_np], dt, velocities=v.double().cpu().numpy(),
+                         log_steps=max(steps, 1))
+        e_kin0 = float(0.5 * (m * v * v).sum())
+        md.fetch()                                     # (synchronises: the energy of the start coordinates is there)
+        hist = [(float(md.step.energy[0]), e_kin0)]
+        md.run(steps)
+        s = md.fetch()
+        if s.halted:
+            print("halted at step %d with code %d (resume() recaptures)" % (s.halt_step, s.halt_code))
+        hist += [(float(r[0, 0]), float(r[0, 1])) for r in s.log]
+        if log:
+            for step in range(0, len(hist), log):
+                print("step %4d  E_pot %+.6f  E_kin %.6f  E_tot %+.6f" % ((step,) + hist[step] + (sum(hist[step]),)))
+        return hist
     box = torch.diagonal(cell)
     # fixed_list: the step-0 neighbour list for the whole run (coordinates then stay unwrapped, its image shifts stay
     # valid).  The model's energy is NOT continuous when an edge enters or leaves the list -- rbf_proj's bias is outside
@@ -78,8 +99,10 @@ if __name__ == "__main__":
     ap.add_argument("--dt", type=float, default=0.5)
     ap.add_argument("--temp", type=float, default=300.0)
     ap.add_argument("--fixed-list", action="store_true")
+    ap.add_argument("--device-md", action="store_true")
     a = ap.parse_args()
-    h = run(tuple(a.reps), a.steps, a.dt, a.temp, log=max(a.steps // 10, 1), fixed_list=a.fixed_list)
+    h = run(tuple(a.reps), a.steps, a.dt, a.temp, log=max(a.steps // 10, 1), fixed_list=a.fixed_list,
+            device_md=a.device_md)
     et = [p + k for p, k in h]
     ek = [k for _, k in h]
     print("atoms %d  steps %d  dt %.2f fs:  E_tot drift %.3e eV (max |E_tot - E_tot0|),  E_kin range %.3e eV"
