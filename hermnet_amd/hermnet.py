@@ -125,14 +125,14 @@ class _GraphSpread(torch.autograd.Function):
     @staticmethod
     def forward(ctx, ge, graph, batch, rows):
         ctx.graph, ctx.batch = graph, batch
-        rg = getattr(graph, "_row_graph", None)
-        if rg is None or rg[0].numel() != rows:
+        def make():
             # graph index of every row of e_rows and a 0 / 1 mask of the rows that hold an atom (HTNet: source rows)
             idx = torch.zeros(rows, dtype=torch.long, device=ge.device).scatter_(0, graph.row_of_node, batch)
             real = torch.zeros(rows, dtype=ge.dtype, device=ge.device).scatter_(
                 0, graph.row_of_node, torch.ones(graph.row_of_node.numel(), dtype=ge.dtype, device=ge.device))
-            rg = graph._row_graph = (idx, real)
-        return ge.index_select(0, rg[0]) * rg[1]
+            return idx, real
+        idx, real = graph.derived("row_graph", make, key=rows)
+        return ge.index_select(0, idx) * real
 
     @staticmethod
     def backward(ctx, c_rows):
@@ -422,7 +422,6 @@ class HVNet(nn.Module):
                 step.halo = data._hn_shard.halo_overlap(graph, nodeops.chain_tile_rows(data.x.size(1)) or 64)
         # (the step stays on the caller's Data: it keeps neither the model's weight copies nor the autograd graph)
         step.weights = step.edge_handles = step.halo = step.chain_node = None
-        graph._keep = None
         return data
 
     def _read_out(self, data, step):

@@ -131,7 +131,7 @@ def _bwd_sums_deferrable(graph, H):
     keeps two or three workgroups per CU and forms the sums half a wave per row (measured, same job: 2.98 vs 3.01 ms at
     configs[1], 27.2 vs 27.6 ms at 100k atoms); the wide kernels (one workgroup per CU) lose more in their prologue than
     the two launches cost (H = 512: 22.5 vs 20.8 ms), so they keep the launches."""
-    return (H == 128 and graph.edge_table is not None and not graph.num_src and getattr(graph, "res_row", None) is None
+    return (H == 128 and graph.edge_table is not None and not graph.num_src and graph.res_row is None
             and _lib.get_option("bwd_lanes16") == 0
             and graph.N * 3 * H * 4 < 2 ** 32 and switches.defer_sums())
 

@@ -270,27 +270,13 @@ def weight_fragments16(w):
 def update_tile_rows(graph, H):
     """16 or the default tile height: which form of the update kernels shortens the launch for this row layout
     (cached on the graph: it depends on the row counts only)."""
-    tr = getattr(graph, "_upd_tile", None)
-    if tr is None or tr[0] != H:
-        tr = (H, int(_lib.load().hermnet_node_update_tile_rows(_rowptr_host(graph), graph.N, graph.T, H)))
-        try:
-            graph._upd_tile = tr
-        except AttributeError:
-            pass
-    return tr[1]
+    return graph.derived("upd_tile", lambda: int(_lib.load().hermnet_node_update_tile_rows(
+        _rowptr_host(graph), graph.N, graph.T, H)), key=H)
 
 
 def _rowptr_host(graph):
     import ctypes
-    c = getattr(graph, "_rowptr_c", None)
-    if c is None:
-        vals = list(graph.type_rowptr_host)
-        c = (ctypes.c_int * len(vals))(*vals)
-        try:
-            graph._rowptr_c = c
-        except AttributeError:
-            pass
-    return c
+    return graph.derived("rowptr_c", lambda: (ctypes.c_int * len(graph.type_rowptr_host))(*graph.type_rowptr_host))
 
 
 def node_pre_fwd(x, w, T, src_ranges=None, windows=None, mode=0, out=None):
@@ -412,7 +398,7 @@ def fused_boundary_supported(graph, H, w, w_next=None):
     """The layer boundary as one node launch each way (csrc/node_chain16.hip): width 128, HVNet rows, and a row layout whose
     update kernels run on 16-row tiles (small grids: nodeops.update_tile_rows).  `w_next`: the next layer's weights (forward
     fusion: same width and relation count)."""
-    if H != 128 or getattr(w, "w1f16", None) is None or graph.num_src or getattr(graph, "res_row", None) is not None:
+    if H != 128 or getattr(w, "w1f16", None) is None or graph.num_src or graph.res_row is not None:
         return False
     if w_next is not None and (getattr(w_next, "w1f16", None) is None or w_next.b1cat.numel() != graph.T * H):
         return False

@@ -6,15 +6,26 @@ neighbour list: atoms are renumbered by (relation of their element, id) and the
 edge list is kept in two orders,
   CSR  (row(target), edge id)                      -> forward segmented sums,
   CSC  (relation(target), row(source), CSR pos)    -> backward segmented sums,
-plus the out-adjacency by source row for the position gradient.  All index
-arrays are int32 device tensors.  One small D2H copy (T+1 row offsets and T edge
-counts) tells the host where each relation's rows start.
+plus (torch build only) the out-adjacency by source row.  All index arrays are
+int32 device tensors.  One small D2H copy (atoms per relation, number of graphs)
+tells the host where each relation's rows start.
+
+Every piece is stated once and the four builds (HVNet / HTNet, torch / native)
+are assembled from them: `_classify` (relation of every atom, the host read),
+`RelationalGraph._layout` (where the relations' rows start), `_source_rows`
+(rows of the atoms), `_order_edges` (CSR + CSC, one key-width rule),
+`_active_relations`, `_graph_order`, `_src_ranges`; the native builds share
+`_atom_counts`, `_native_rows` / `_finish_native_rows` (row arrays, kept per
+atom set) and `_native_edges` (output arrays + `RelationsOut`).  The torch
+builds define the result bit for bit.  Other modules keep values derived from
+the immutable graph through `RelationalGraph.derived`.
 """
-import os
+import ctypes
 
 import torch
 
-from . import switches
+from . import _lib, switches
+from .ops import _stream
 
 _COUNT_CACHE = []      # most recent first: (z tensor, version, batch tensor, version, z_list, result)
 _CONST_CACHE = {}
@@ -40,6 +51,140 @@ def _cached_u8(values, dev):
     return t
 
 
+def _classify(atomic_number, batch, z_list):
+    """The torch restatement of `hermnet_relation_counts`: (relation of every atom [NA] -- the first matching element, T
+    for "not in elems" (hermnet.py:53 finds none) --, atoms per relation + unknown [T+1] on the device, the same on the
+    host, number of graphs), with the one host sync of a torch build."""
+    dev, NA, T = atomic_number.device, int(atomic_number.numel()), len(z_list)
+    eq = atomic_number.long()[:, None] == torch.tensor(list(z_list), dtype=torch.long, device=dev)[None, :]
+    rel = torch.where(eq.any(1), eq.int().argmax(1), torch.full((NA,), T, dtype=torch.long, device=dev))
+    counts = torch.zeros(T + 1, dtype=torch.long, device=dev).index_add_(0, rel, torch.ones_like(rel))
+    nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
+    host = torch.cat([counts, nb]).cpu().tolist()
+    return rel, counts, host[:T + 1], int(host[-1])
+
+
+def _source_rows(rel, counts, starts, n_rows, z):
+    """Rows of the atoms: sorted by (relation, id), relation t from row `starts[t]` on, unknown elements from `starts[T]`
+    (`RelationalGraph._layout`).  -> (node_order [NA], row_of_node [NA], z_rows [n_rows], row_real [n_rows] 1 / 0,
+    local [NA] index of every atom within its relation).  HTNet's source rows are HVNet's uniform layout."""
+    dev, NA, T = rel.device, int(rel.numel()), len(starts) - 1
+    node_order = torch.sort(rel.to(torch.int32), stable=True).indices
+    first_sorted = torch.zeros(T + 1, dtype=torch.long, device=dev)
+    first_sorted[1:] = torch.cumsum(counts[:T], 0)          # position of each relation in the sorted list
+    rel_sorted = rel[node_order]
+    local_sorted = torch.arange(NA, device=dev) - first_sorted[rel_sorted]
+    row_of_node, local = torch.empty_like(node_order), torch.empty_like(node_order)
+    row_of_node[node_order] = local_sorted + torch.tensor(starts, dtype=torch.long, device=dev)[rel_sorted]
+    local[node_order] = local_sorted
+    z_rows = torch.zeros(n_rows, dtype=torch.long, device=dev)
+    z_rows[row_of_node] = z
+    row_real = torch.zeros(n_rows, dtype=torch.float32, device=dev)
+    row_real[row_of_node] = 1.0
+    return node_order, row_of_node, z_rows, row_real, local
+
+
+def _group(keys, n_keys, n_groups=None, wide=None):
+    """Stable sort of integer keys < n_keys -> (sorted keys, permutation, row pointer [n_groups + 1] of the keys
+    < n_groups (default: all); by searchsorted, which does not sync the host as bincount does).  The one key-width rule:
+    int32 keys (half the radix passes) whenever the largest key fits; `wide` forces either width (tests)."""
+    wide = n_keys > 2 ** 31 if wide is None else wide
+    s, perm = torch.sort(keys.to(torch.long if wide else torch.int32), stable=True)
+    s = s.long()
+    return s, perm, torch.searchsorted(s, torch.arange((n_keys if n_groups is None else n_groups) + 1, device=keys.device))
+
+
+def _order_edges(target_row, source_row, rel_of_target, n_target_rows, n_source_rows, n_rel, wide=None):
+    """The two edge orders: CSR = (target row, edge id), CSC = (relation of the target, source row, CSR position); edges
+    of relation n_rel (unknown-element targets) sort behind the CSC row pointer.  All int32 but the CSR permutation.
+    -> (csr_perm, csr_src, csr_rowptr [n_target_rows + 1], csc_pos, csc_tgt, csc_rowptr [n_rel n_source_rows + 1])"""
+    i32 = torch.int32
+    tgt_sorted, csr_perm, csr_rowptr = _group(target_row, n_target_rows, wide=wide)
+    csr_src = source_row[csr_perm]
+    _, csc_pos, csc_rowptr = _group(rel_of_target[csr_perm] * n_source_rows + csr_src, (n_rel + 1) * n_source_rows,
+                                    n_rel * n_source_rows, wide)
+    return csr_perm, csr_src.to(i32), csr_rowptr.to(i32), csc_pos.to(i32), tgt_sorted[csc_pos].to(i32), csc_rowptr.to(i32)
+
+
+def _active_relations(rel_active, dev, edges_per_relation=None):
+    """Which relations run.  Torch form (`edges_per_relation` given): bool [n_rel], by default "it receives an edge".
+    Native form: uint8 device flags or None (the kernel decides by the edges).  `rel_active` (list, or device tensor:
+    slab plans, no host read): the caller knows better, e.g. a shard whose relation has edges on other ranks only."""
+    native = edges_per_relation is None
+    if rel_active is None:
+        return None if native else edges_per_relation > 0
+    if torch.is_tensor(rel_active):
+        return rel_active.to(device=dev, dtype=torch.uint8 if native else torch.bool).contiguous()
+    flags = tuple(bool(a) for a in rel_active)
+    return _cached_u8(flags, dev) if native else torch.tensor(flags, dtype=torch.bool, device=dev)
+
+
+def _graph_order(batch, num_graphs, cache=None):
+    """Deterministic per-graph read-out: (atoms grouped by graph, stable; segment lengths), or (None, None) for one graph.
+    It depends on the batch vector only: the native builds keep it in `cache`, their row arrays of the atom set."""
+    if batch is None or num_graphs <= 1:
+        return None, None
+    if cache is None or "graph_perm" not in cache:
+        b64 = batch.long()
+        order = (torch.argsort(b64, stable=True),
+                 torch.zeros(num_graphs, dtype=torch.long, device=batch.device).index_add_(0, b64, torch.ones_like(b64)))
+        if cache is None:
+            return order
+        cache["graph_perm"], cache["graph_lengths"] = order
+    return cache["graph_perm"], cache["graph_lengths"]
+
+
+def _src_ranges(T, B, cnt_host, dev):
+    """HTNet [T P, 4]: relation (c; p, q) gathers sources of elements p and q only (the x_proj chain skips the other
+    rows): rows [p B, p B + N_p) and, for q != p, [q B, q B + N_q)."""
+    per_pair = tuple(v for p in range(T) for q in range(p, T)
+                     for v in (p * B, p * B + cnt_host[p], (q * B if q != p else 0), (q * B + cnt_host[q] if q != p else 0)))
+    return _cached_i32(per_pair * T, dev).view(T * T * (T + 1) // 2, 4)
+
+
+def _native_rows(rows_cache, key, NA, n_rows, dev):
+    """Row arrays of a native build, which depend on the atoms only: those of `rows_cache[key]`, or new ones for the
+    kernel to fill.  -> (rows, ready)"""
+    rows = rows_cache.get(key)
+    if rows is not None:
+        return rows, True
+    e32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    return dict(node_order=e32(NA), row_of_node=e32(NA), z_rows=e32(n_rows),
+                row_real=torch.empty(n_rows, dtype=torch.float32, device=dev)), False
+
+
+def _finish_native_rows(g, rows, rows_cache, key, batch):
+    """After the kernel: int64 copies for the host code's gathers (embedding, index_select) and `batch32`, made once per
+    atom set and kept in `rows_cache[key]`."""
+    if key not in rows_cache:
+        rows["z_rows64"] = rows["z_rows"].long()
+        rows["row_of_node64"] = rows["row_of_node"].long()
+        rows["node_order64"] = rows["node_order"].long()
+        rows["batch32"] = None if batch is None else batch.to(torch.int32).contiguous()
+        if len(rows_cache) > 4:
+            rows_cache.clear()
+        rows_cache[key] = rows
+    g.z_rows, g.row_of_node, g.node_order = rows["z_rows64"], rows["row_of_node64"], rows["node_order64"]
+    g.batch32 = rows["batch32"]
+
+
+def _native_edges(g, rows, n_target_rows, n_csc_rows, E, edge_shift, dev):
+    """Allocate the edge arrays of a native build on `g` (no out-adjacency: the position gradient reads the out-edges
+    from the CSC order, ops.EdgeGeometry).  -> (`_lib.RelationsOut` over them and `rows`, the contiguous input shifts)"""
+    P = _lib.ptr
+    e32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    g.row_active = torch.empty(n_target_rows, dtype=torch.float32, device=dev)
+    g.csr_rowptr, g.csr_src, g.csr_perm, g.src_id, g.tgt_id = e32(n_target_rows + 1), e32(E), e32(E), e32(E), e32(E)
+    g.csc_rowptr, g.csc_tgt, g.csc_pos = e32(n_csc_rows + 1), e32(E), e32(E)
+    g.out_rowptr = g.out_edges = None
+    shift = None if edge_shift is None else edge_shift.float().contiguous()
+    g.shift = None if shift is None else torch.empty(E, 3, dtype=torch.float32, device=dev)
+    out = _lib.RelationsOut(P(rows["node_order"]), P(rows["row_of_node"]), P(rows["z_rows"]), P(rows["row_real"]),
+                            P(g.row_active), P(g.csr_rowptr), P(g.csr_src), P(g.csr_perm), P(g.src_id), P(g.tgt_id),
+                            P(g.shift), P(g.csc_rowptr), P(g.csc_tgt), P(g.csc_pos), None, None)
+    return out, shift
+
+
 class RelationalGraph(object):
     """Rows = atoms in relation order.  With `uniform` layout every relation owns a block of
     `block` = max_t N_t rows (short relations are padded with inert rows), so the per-relation node
@@ -47,20 +192,23 @@ class RelationalGraph(object):
     after the T blocks.  Without it (very unbalanced compositions) blocks are tight and the host
     loops over relations."""
 
+    _DERIVED = ("_rowptr_c",        # nodeops._rowptr_host: type_rowptr_host as a ctypes int array
+                "_upd_tile",        # nodeops.update_tile_rows: tile rows of the update kernels for this row layout, keyed on H
+                "_row_keys",        # trainops._row_keys: gather / segmented-sum keys of the differentiable path
+                "_edge_atoms64",    # trainops._edge_atoms: (source, target) atom of every edge as int64
+                "_edge_sum_keys",   # trainops._edge_sum_keys: row keys of the adjoint of EdgeDiff
+                "_row_graph")       # hermnet._GraphSpread: graph index and 0 / 1 mask of every row, keyed on the row count
     __slots__ = ("N", "E", "T", "num_atoms", "uniform", "block", "node_order", "row_of_node", "z_rows",
                  "type_rowptr", "type_rowptr_host", "csr_rowptr", "csr_src", "csr_perm", "csc_rowptr", "csc_tgt",
                  "csc_pos", "out_rowptr", "out_edges", "src_id", "tgt_id", "shift", "row_active", "row_real",
-                 "batch_rows", "batch32", "num_graphs", "graph_perm", "graph_lengths", "device", "_cstruct", "_rel_bounds",
-                 "edge_table", "fwd_taps", "num_src", "res_row", "triadic_pairs", "src_real", "_rowptr_c", "src_ranges", "_row_keys",
-                 "_upd_tile", "ready", "_keep", "_edge_atoms64", "_edge_sum_keys", "_row_graph", "_all_known")
+                 "batch32", "num_graphs", "graph_perm", "graph_lengths", "device", "_cstruct", "_rel_bounds",
+                 "edge_table", "fwd_taps", "num_src", "res_row", "triadic_pairs", "src_real", "src_ranges",
+                 "_all_known") + _DERIVED
 
     def __init__(self):
         self._cstruct = None
         self._rel_bounds = None
         self._all_known = False    # every atom has an element of the model (host knowledge from the atom counts): Ek == E
-        self._rowptr_c = None      # type_rowptr_host as a ctypes int array (nodeops._rowptr_host)
-        self._upd_tile = None      # (H, tile rows of the update kernels for this row layout) (nodeops.update_tile_rows)
-        self._row_keys = None      # gather / segmented-sum keys of the differentiable path (trainops._row_keys)
         self.edge_table = None     # [E+1,32] per-edge radial records of the current step, CSC order (set by HVNet.forward)
         self.fwd_taps = None       # [E,16] per-edge tap records of the current step, CSR order (set with edge_table), or None
         self.num_src = 0           # separate source-row space (HTNet): rows of xh / vec; 0 = same rows as the targets
@@ -68,10 +216,18 @@ class RelationalGraph(object):
         self.triadic_pairs = 0     # HTNet: pair relations per centre element (target rows = T_elem * pairs * block)
         self.src_real = None       # HTNet: [num_src] 1 for source rows that hold an atom
         self.src_ranges = None     # HTNet: [T,4] int32, the two source-row ranges a relation gathers from (nodeops.node_pre_fwd)
-        self._edge_atoms64 = None  # trainops.EdgeDiff: (source, target) atom of every edge as int64
-        self._edge_sum_keys = None
-        self._row_graph = None     # hermnet.GraphEnergies: graph index of every row
-        self._keep = None
+        for slot in self._DERIVED:
+            setattr(self, slot, None)
+
+    def derived(self, name, make, key=None):
+        """A value that follows from this (immutable) graph alone, made on first use and kept in the declared slot
+        `_<name>`; one made under another `key` is made again."""
+        slot = "_" + name
+        hit = getattr(self, slot)
+        if hit is None or hit[0] != key:
+            hit = (key, make())
+            setattr(self, slot, hit)
+        return hit[1]
 
     def rel_edge_bounds(self):
         """CSR edge ranges of the relations: edges of relation t are [b[t], b[t+1]) (rows are relation-ordered and
@@ -128,20 +284,16 @@ class RelationalGraph(object):
         types and batch assignment do not change along an MD trajectory).  Keyed on the identity of the caller's
         tensor OBJECTS, which the cache keeps alive: an address alone could be reused by a different tensor of the
         same size."""
-        from . import _lib
-        lib = _lib.load()
-        dev = atomic_number.device
-        NA, T = int(atomic_number.numel()), len(z_list)
+        dev, NA, T = atomic_number.device, int(atomic_number.numel()), len(z_list)
         i32, P = torch.int32, _lib.ptr
         for ent in _COUNT_CACHE:
             if (ent[0] is atomic_number and ent[1] == atomic_number._version and ent[2] is batch
                     and ent[3] == (None if batch is None else batch._version) and ent[4] == tuple(z_list)):
                 return ent[5]
-        from .ops import _stream
         z = atomic_number.long().contiguous()
         zl = torch.tensor(list(z_list), dtype=i32, device=dev)
         counts = torch.empty(T + 1, dtype=i32, device=dev)
-        _lib.check(lib.hermnet_relation_counts(P(z), NA, P(zl), T, P(counts), _stream()), "hermnet_relation_counts")
+        _lib.check(_lib.load().hermnet_relation_counts(P(z), NA, P(zl), T, P(counts), _stream()), "hermnet_relation_counts")
         nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
         host = torch.cat([counts.long(), nb]).cpu().tolist()
         hit = (zl, host[:T + 1], int(host[-1]), z, {})
@@ -152,182 +304,68 @@ class RelationalGraph(object):
 
     @staticmethod
     def _build_native(atomic_number, edge_index, z_list, edge_shift, batch, rel_active, uniform):
-        import ctypes
-        from . import _lib
-        from .ops import _stream
-        lib = _lib.load()
+        lib, P = _lib.load(), _lib.ptr
         g = RelationalGraph()
         dev = atomic_number.device
         NA, E, T = int(atomic_number.numel()), int(edge_index.size(1)), len(z_list)
         g.num_atoms, g.E, g.T, g.device = NA, E, T, dev
         ei = edge_index.long().contiguous()
-        i32, P = torch.int32, _lib.ptr
-        hit = RelationalGraph._atom_counts(atomic_number, batch, z_list)
-        zl, cnt_host, g.num_graphs, z = hit[:4]
-        rows_cache = hit[4]                   # {(uniform layout key): row arrays}: they depend on the atoms only
+        zl, cnt_host, g.num_graphs, z, rows_cache = RelationalGraph._atom_counts(atomic_number, batch, z_list)
         g.uniform, g.block, starts, N = RelationalGraph._layout(cnt_host, T, uniform)
         g.N, g.type_rowptr_host = N, starts[:T + 1]
         g._all_known = int(cnt_host[T]) == 0
         g.type_rowptr = _cached_i32(tuple(starts[:T + 1]), dev)
-        e32 = lambda n: torch.empty(n, dtype=i32, device=dev)
-        rows = rows_cache.get((g.uniform, N))
-        rows_ready = rows is not None
-        if rows is None:
-            rows = dict(node_order=e32(NA), row_of_node=e32(NA), z_rows=e32(N),
-                        row_real=torch.empty(N, dtype=torch.float32, device=dev))
+        key = (g.uniform, N)
+        rows, rows_ready = _native_rows(rows_cache, key, NA, N, dev)
         g.row_real = rows["row_real"]
-        g.row_active = torch.empty(N, dtype=torch.float32, device=dev)
-        g.csr_rowptr, g.csr_src, g.csr_perm, g.src_id, g.tgt_id = e32(N + 1), e32(E), e32(E), e32(E), e32(E)
-        g.csc_rowptr, g.csc_tgt, g.csc_pos = e32(T * N + 1), e32(E), e32(E)
-        # (no out-adjacency: the position gradient reads the out-edges from the CSC order, ops.EdgeGeometry)
-        g.out_rowptr = g.out_edges = None
-        shift = None if edge_shift is None else edge_shift.float().contiguous()
-        g.shift = None if shift is None else torch.empty(E, 3, dtype=torch.float32, device=dev)
-        if torch.is_tensor(rel_active):       # device flags (slab plans, sharding.py): no host read
-            act = rel_active.to(device=dev, dtype=torch.uint8).contiguous()
-        else:
-            act = None if rel_active is None else _cached_u8(tuple(bool(a) for a in rel_active), dev)
+        out, shift = _native_edges(g, rows, N, T * N, E, edge_shift, dev)
+        act = _active_relations(rel_active, dev)
         wbytes = lib.hermnet_build_relations_workspace(NA, N, E, T)
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-        out = _lib.RelationsOut(P(rows["node_order"]), P(rows["row_of_node"]), P(rows["z_rows"]), P(g.row_real), P(g.row_active),
-                                P(g.csr_rowptr), P(g.csr_src), P(g.csr_perm), P(g.src_id), P(g.tgt_id), P(g.shift),
-                                P(g.csc_rowptr), P(g.csc_tgt), P(g.csc_pos), P(g.out_rowptr), P(g.out_edges))
         _lib.check(lib.hermnet_build_relations(P(z), P(ei), P(shift), NA, E, P(zl), T, P(g.type_rowptr), N, P(act), ctypes.byref(out),
                                                1 if rows_ready else 0, P(work), wbytes, _stream()), "hermnet_build_relations")
-        if not rows_ready:
-            # int64 copies for the host code's gathers (embedding, index_select), made once per atom set
-            rows["z_rows64"] = rows["z_rows"].long()
-            rows["row_of_node64"] = rows["row_of_node"].long()
-            rows["node_order64"] = rows["node_order"].long()
-            rows["batch32"] = None if batch is None else batch.to(i32).contiguous()
-            if len(rows_cache) > 4:
-                rows_cache.clear()
-            rows_cache[(g.uniform, N)] = rows
-        g.z_rows, g.row_of_node, g.node_order = rows["z_rows64"], rows["row_of_node64"], rows["node_order64"]
-        g.batch32 = rows["batch32"]
-        g.batch_rows = None
-        if batch is not None and g.num_graphs > 1:
-            if "graph_perm" not in rows:          # (depends on the batch vector only, like the row layout: once per atom set)
-                b64 = batch.long()
-                rows["graph_perm"] = torch.argsort(b64, stable=True)
-                rows["graph_lengths"] = torch.zeros(g.num_graphs, dtype=torch.long, device=dev).index_add_(
-                    0, b64, torch.ones_like(b64))
-            g.graph_perm, g.graph_lengths = rows["graph_perm"], rows["graph_lengths"]
-        else:
-            g.graph_perm = None
-            g.graph_lengths = None
+        _finish_native_rows(g, rows, rows_cache, key, batch)
+        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs, rows)
         return g
 
     @staticmethod
     def _build_torch(atomic_number, edge_index, z_list, edge_shift=None, batch=None, rel_active=None, uniform=None):
         g = RelationalGraph()
-        dev = atomic_number.device
-        NA = int(atomic_number.numel())
-        E = int(edge_index.size(1))
-        T = len(z_list)
+        dev, i32 = atomic_number.device, torch.int32
+        NA, E, T = int(atomic_number.numel()), int(edge_index.size(1)), len(z_list)
         g.num_atoms, g.E, g.T, g.device = NA, E, T, dev
         z = atomic_number.long()
-        zl = torch.tensor(list(z_list), dtype=torch.long, device=dev)
-        eq = z[:, None] == zl[None, :]
-        # relation of each atom: first matching element, T for "not in elems" (hermnet.py:53 finds none)
-        rel = torch.where(eq.any(1), eq.int().argmax(1), torch.full((NA,), T, dtype=torch.long, device=dev))
-        counts = torch.zeros(T + 1, dtype=torch.long, device=dev).index_add_(0, rel, torch.ones_like(rel))
-        nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
-        host = torch.cat([counts, nb]).cpu().tolist()          # the one host sync of the build
-        cnt_host, g.num_graphs = host[:T + 1], int(host[-1])
+        rel, counts, cnt_host, g.num_graphs = _classify(z, batch, z_list)
         g.uniform, g.block, starts, N = RelationalGraph._layout(cnt_host, T, uniform)
-        g.N = N                                                 # rows (>= atoms when padded)
-        g.type_rowptr_host = starts[:T + 1]
-
-        ar = torch.arange(NA, device=dev)
-        g.node_order = torch.sort(rel.to(torch.int32), stable=True).indices   # atoms sorted by (relation, id)
-        first_sorted = torch.zeros(T + 1, dtype=torch.long, device=dev)
-        first_sorted[1:] = torch.cumsum(counts[:T], 0)          # position of each relation in the sorted list
-        starts_d = torch.tensor(starts, dtype=torch.long, device=dev)
-        rel_sorted = rel[g.node_order]
-        rows_sorted = ar - first_sorted[rel_sorted] + starts_d[rel_sorted]
-        g.row_of_node = torch.empty_like(g.node_order)
-        g.row_of_node[g.node_order] = rows_sorted
-        g.z_rows = torch.zeros(N, dtype=torch.long, device=dev)
-        g.z_rows[g.row_of_node] = z
-        g.row_real = torch.zeros(N, dtype=torch.float32, device=dev)
-        g.row_real[g.row_of_node] = 1.0
-        rel_row = torch.full((N,), T, dtype=torch.long, device=dev)
-        for t in range(T):
-            rel_row[starts[t]:(starts[t + 1] if t + 1 <= T else N)] = t
-        rel_row[starts[T]:] = T
-
-        def rowptr_of(sorted_keys, nkeys):
-            """CSR row pointer of an ascending key list (no host sync, unlike bincount)."""
-            return torch.searchsorted(sorted_keys, torch.arange(nkeys + 1, device=dev))
+        g.N, g.type_rowptr_host = N, starts[:T + 1]             # rows (>= atoms when padded)
+        g.type_rowptr = torch.tensor(starts[:T + 1], dtype=i32, device=dev)
+        g.node_order, g.row_of_node, g.z_rows, g.row_real, _ = _source_rows(rel, counts, starts, N, z)
 
         src, tgt = edge_index[0].long(), edge_index[1].long()
-        rs, rt = g.row_of_node[src], g.row_of_node[tgt]
-        i32k = torch.int32 if (T + 1) * N < 2 ** 31 else torch.long   # narrow keys: half the radix passes
-        rt_s, csr_perm = torch.sort(rt.to(i32k), stable=True)
-        rt_s = rt_s.long()
-        csr_src = rs[csr_perm]
-        csr_rowptr = rowptr_of(rt_s, N)
-
-        key2 = rel_row[rt_s] * N + csr_src                      # (relation(target), row(source))
-        key2_s, csc_pos = torch.sort(key2.to(i32k), stable=True)
-        key2_s = key2_s.long()
-        csc_tgt = rt_s[csc_pos]
-        csc_rowptr = rowptr_of(key2_s, T * N)
-
-        src_s, out_edges = torch.sort(csr_src.to(i32k), stable=True)
-        src_s = src_s.long()
-        out_rowptr = rowptr_of(src_s, N)
+        g.csr_perm, g.csr_src, g.csr_rowptr, g.csc_pos, g.csc_tgt, g.csc_rowptr = _order_edges(
+            g.row_of_node[tgt], g.row_of_node[src], rel[tgt], N, N, T)
+        # out-adjacency by source row (tests read it; the device build leaves it off: ops.EdgeGeometry reads the CSC order)
+        _, out_edges, out_rowptr = _group(g.csr_src, N)
+        g.out_rowptr, g.out_edges = out_rowptr.to(i32), out_edges.to(i32)
+        g.src_id, g.tgt_id = src[g.csr_perm].to(i32), tgt[g.csr_perm].to(i32)
+        g.shift = None if edge_shift is None else edge_shift[g.csr_perm].float().contiguous()
 
         # hermnet.py:56-57: a relation without edges is skipped -> its rows stay zero; rows of
         # unknown-type atoms (hermnet.py:51) and padding rows are zero as well.
-        # (`rel_active`: the caller knows better, e.g. a shard whose relation has edges on other ranks only)
-        if rel_active is None:
-            tn = torch.arange(T + 1, device=dev) * N
-            act = torch.cat([(csc_rowptr[tn[1:]] - csc_rowptr[tn[:-1]]) > 0,
-                             torch.zeros(1, dtype=torch.bool, device=dev)])
-        elif torch.is_tensor(rel_active):
-            act = torch.cat([rel_active.to(dev).bool(), torch.zeros(1, dtype=torch.bool, device=dev)])
-        else:
-            act = torch.tensor([bool(a) for a in rel_active] + [False], dtype=torch.bool, device=dev)
-        g.row_active = act[rel_row].float() * g.row_real
-
-        i32 = torch.int32
-        g.type_rowptr = starts_d[:T + 1].to(i32)
-        g.csr_rowptr = csr_rowptr.to(i32)
-        g.csr_src = csr_src.to(i32)
-        g.csr_perm = csr_perm
-        g.csc_rowptr = csc_rowptr.to(i32)
-        g.csc_tgt = csc_tgt.to(i32)
-        g.csc_pos = csc_pos.to(i32)
-        g.out_rowptr = out_rowptr.to(i32)
-        g.out_edges = out_edges.to(i32)
-        g.src_id = src[csr_perm].to(i32)
-        g.tgt_id = tgt[csr_perm].to(i32)
-        g.shift = None if edge_shift is None else edge_shift[csr_perm].float().contiguous()
+        tn = torch.arange(T + 1, device=dev) * N
+        act = _active_relations(rel_active, dev, g.csc_rowptr[tn[1:]] - g.csc_rowptr[tn[:-1]])
+        act = torch.cat([act, torch.zeros(1, dtype=torch.bool, device=dev)])
+        g.row_active = torch.zeros(N, dtype=torch.float32, device=dev)
+        g.row_active[g.row_of_node] = act[rel].float()          # a row runs iff it holds an atom whose relation runs
         g.batch32 = None if batch is None else batch.to(i32).contiguous()
-        g.batch_rows = None
-        if batch is not None:
-            g.batch_rows = torch.zeros(N, dtype=torch.long, device=dev)
-            g.batch_rows[g.row_of_node] = batch.long()
-        # deterministic per-graph read-out: atoms grouped by graph (stable) + segment lengths
-        if batch is not None and g.num_graphs > 1:
-            g.graph_perm = torch.argsort(batch.long(), stable=True)
-            g.graph_lengths = torch.zeros(g.num_graphs, dtype=torch.long, device=dev).index_add_(
-                0, batch.long(), torch.ones_like(batch.long()))
-        else:
-            g.graph_perm = None
-            g.graph_lengths = None
+        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs)
         return g
 
     @staticmethod
     def _build_triadic_native(atomic_number, edge_index, z_list, edge_shift, batch, rel_active=None):
         """`build_triadic` through `hermnet_build_triadic` (csrc/relation_kernels.hip); None when an atom is of an
         element outside `z_list` (the torch build handles those)."""
-        import ctypes
-        from . import _lib
-        from .ops import _stream
-        lib = _lib.load()
+        lib, P = _lib.load(), _lib.ptr
         dev = atomic_number.device
         NA, E0, T = int(atomic_number.numel()), int(edge_index.size(1)), len(z_list)
         zl, cnt_host, num_graphs, z, rows_cache = RelationalGraph._atom_counts(atomic_number, batch, z_list)
@@ -343,58 +381,23 @@ class RelationalGraph(object):
         g.N, g.num_src, g.triadic_pairs, g.E = Nt, Ns, Pn, E
         g.type_rowptr_host = [r * B for r in range(TR + 1)]
         g.type_rowptr = _cached_i32(tuple(g.type_rowptr_host), dev)
-        i32, P = torch.int32, _lib.ptr
-        e32 = lambda n: torch.empty(n, dtype=i32, device=dev)
-        rows = rows_cache.get(("triadic", B))
-        rows_ready = rows is not None
-        if rows is None:
-            rows = dict(node_order=e32(NA), row_of_node=e32(NA), z_rows=e32(Ns),
-                        src_real=torch.empty(Ns, dtype=torch.float32, device=dev))
-        g.src_real = g.row_real = rows["src_real"]                 # the energy read-out masks SOURCE rows
-        g.row_active = torch.empty(Nt, dtype=torch.float32, device=dev)
-        tgt_real = torch.empty(Nt, dtype=torch.float32, device=dev)
-        g.res_row = e32(Nt)
-        g.csr_rowptr, g.csr_src, g.csr_perm, g.src_id, g.tgt_id = e32(Nt + 1), e32(E), e32(E), e32(E), e32(E)
-        g.csc_rowptr, g.csc_tgt, g.csc_pos = e32(TR * Ns + 1), e32(E), e32(E)
-        g.out_rowptr = g.out_edges = None
+        key = ("triadic", B)
+        rows, rows_ready = _native_rows(rows_cache, key, NA, Ns, dev)
+        g.src_real = g.row_real = rows["row_real"]                 # the energy read-out masks SOURCE rows
         ei = edge_index.long().contiguous()
-        shift = None if edge_shift is None else edge_shift.float().contiguous()
-        g.shift = None if shift is None else torch.empty(E, 3, dtype=torch.float32, device=dev)
+        out, shift = _native_edges(g, rows, Nt, TR * Ns, E, edge_shift, dev)
+        tgt_real = torch.empty(Nt, dtype=torch.float32, device=dev)
+        g.res_row = torch.empty(Nt, dtype=torch.int32, device=dev)
         counts_d = _cached_i32(tuple(cnt_host[:T]), dev)
         wbytes = lib.hermnet_build_triadic_workspace(NA, E0, T, B)
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-        out = _lib.RelationsOut(P(rows["node_order"]), P(rows["row_of_node"]), P(rows["z_rows"]), P(rows["src_real"]),
-                                P(g.row_active), P(g.csr_rowptr), P(g.csr_src), P(g.csr_perm), P(g.src_id), P(g.tgt_id),
-                                P(g.shift), P(g.csc_rowptr), P(g.csc_tgt), P(g.csc_pos), None, None)
-        if torch.is_tensor(rel_active):
-            act = rel_active.to(device=dev, dtype=torch.uint8).contiguous()
-        else:
-            act = None if rel_active is None else _cached_u8(tuple(bool(a) for a in rel_active), dev)
+        act = _active_relations(rel_active, dev)
         _lib.check(lib.hermnet_build_triadic(P(z), P(ei), P(shift), NA, E0, P(zl), T, B, P(counts_d), P(act), ctypes.byref(out),
                                              P(tgt_real), P(g.res_row), 1 if rows_ready else 0, P(work), wbytes, _stream()),
                    "hermnet_build_triadic")
-        if not rows_ready:
-            rows["z_rows64"] = rows["z_rows"].long()
-            rows["row_of_node64"] = rows["row_of_node"].long()
-            rows["node_order64"] = rows["node_order"].long()
-            rows["batch32"] = None if batch is None else batch.to(i32).contiguous()
-            if len(rows_cache) > 4:
-                rows_cache.clear()
-            rows_cache[("triadic", B)] = rows
-        g.z_rows, g.row_of_node, g.node_order = rows["z_rows64"], rows["row_of_node64"], rows["node_order64"]
-        g.batch32 = rows["batch32"]
-        g.batch_rows = None
-        pairs = [(p, q) for p in range(T) for q in range(p, T)]
-        g.src_ranges = _cached_i32(tuple(v for _c in range(T) for (p_, q_) in pairs
-                                         for v in (p_ * B, p_ * B + cnt_host[p_], (q_ * B if q_ != p_ else 0),
-                                                   (q_ * B + cnt_host[q_] if q_ != p_ else 0))), dev).view(TR, 4)
-        if batch is not None and g.num_graphs > 1:
-            g.graph_perm = torch.argsort(batch.long(), stable=True)
-            g.graph_lengths = torch.zeros(g.num_graphs, dtype=torch.long, device=dev).index_add_(
-                0, batch.long(), torch.ones_like(batch.long()))
-        else:
-            g.graph_perm = None
-            g.graph_lengths = None
+        _finish_native_rows(g, rows, rows_cache, key, batch)
+        g.src_ranges = _src_ranges(T, B, cnt_host, dev)
+        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs, rows)
         return g
 
     @staticmethod
@@ -420,42 +423,20 @@ class RelationalGraph(object):
             if g is not None:
                 return g
         g = RelationalGraph()
-        dev = atomic_number.device
-        NA, E0, T = int(atomic_number.numel()), int(edge_index.size(1)), len(z_list)
+        dev, i32 = atomic_number.device, torch.int32
+        NA, T = int(atomic_number.numel()), len(z_list)
         pairs = [(p, q) for p in range(T) for q in range(p, T)]
         P = len(pairs)
         TR = T * P
         z = atomic_number.long()
-        zl = torch.tensor(list(z_list), dtype=torch.long, device=dev)
-        eq = z[:, None] == zl[None, :]
-        rel = torch.where(eq.any(1), eq.int().argmax(1), torch.full((NA,), T, dtype=torch.long, device=dev))
-        counts = torch.zeros(T + 1, dtype=torch.long, device=dev).index_add_(0, rel, torch.ones_like(rel))
-        nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
-        host = torch.cat([counts, nb]).cpu().tolist()          # the one host sync of the build
-        cnt_host, g.num_graphs = host[:T + 1], int(host[-1])
-        B = max(cnt_host[:T]) if T > 0 else 0
-        Ns, Nt = T * B + cnt_host[T], TR * B
+        rel, counts, cnt_host, g.num_graphs = _classify(z, batch, z_list)
+        _, B, starts, Ns = RelationalGraph._layout(cnt_host, T, True)
+        Nt = TR * B
         g.num_atoms, g.T, g.device, g.uniform, g.block = NA, TR, dev, True, B
         g.N, g.num_src, g.triadic_pairs = Nt, Ns, P
         g.type_rowptr_host = [r * B for r in range(TR + 1)]
-        i32 = torch.int32
         g.type_rowptr = torch.tensor(g.type_rowptr_host, dtype=i32, device=dev)
-
-        # source rows: (element, id) order, element blocks of B rows, unknown elements behind
-        g.node_order = torch.sort(rel.to(i32), stable=True).indices
-        first_sorted = torch.zeros(T + 1, dtype=torch.long, device=dev)
-        first_sorted[1:] = torch.cumsum(counts[:T], 0)
-        rel_sorted = rel[g.node_order]
-        local_sorted = torch.arange(NA, device=dev) - first_sorted[rel_sorted]
-        rows_sorted = local_sorted + rel_sorted * B
-        g.row_of_node = torch.empty_like(g.node_order)
-        g.row_of_node[g.node_order] = rows_sorted
-        local = torch.empty_like(g.node_order)
-        local[g.node_order] = local_sorted
-        g.z_rows = torch.zeros(Ns, dtype=torch.long, device=dev)
-        g.z_rows[g.row_of_node] = z
-        g.src_real = torch.zeros(Ns, dtype=torch.float32, device=dev)
-        g.src_real[g.row_of_node] = 1.0
+        g.node_order, g.row_of_node, g.z_rows, g.src_real, local = _source_rows(rel, counts, starts, Ns, z)
         g.row_real = g.src_real                                   # energy read-out masks SOURCE rows
 
         # expanded edge list: edge (j -> i) once per pair containing element(j)
@@ -465,28 +446,14 @@ class RelationalGraph(object):
             pair_of[e_] = torch.tensor(ks, dtype=torch.long, device=dev)
         src, tgt = edge_index[0].long(), edge_index[1].long()
         tj, ti = rel[src], rel[tgt]
-        ok = (tj < T) & (ti < T)
-        eid = torch.nonzero(ok).reshape(-1)
+        eid = torch.nonzero((tj < T) & (ti < T)).reshape(-1)
         eid_x = eid.repeat_interleave(T)                           # expanded: (edge id major, pair minor)
-        k_x = pair_of[tj[eid]].reshape(-1)
-        ti_x = ti[eid_x]
-        rel_x = ti_x * P + k_x
+        rel_x = ti[eid_x] * P + pair_of[tj[eid]].reshape(-1)
         vt_x = rel_x * B + local[tgt[eid_x]]                       # virtual target row
-        rs_x = g.row_of_node[src[eid_x]]                           # source row
-        E = int(eid_x.numel())
-        g.E = E
-        big = TR * max(Ns, 1) + 1 >= 2 ** 31
-        kt = torch.long if big else i32
-        vt_s, csr_perm = torch.sort(vt_x.to(kt), stable=True)
-        vt_s = vt_s.long()
-        csr_src = rs_x[csr_perm]
-        ar = lambda n: torch.arange(n + 1, device=dev)
-        csr_rowptr = torch.searchsorted(vt_s, ar(Nt))
-        key2 = (rel_x[csr_perm] * Ns + csr_src)
-        key2_s, csc_pos = torch.sort(key2.to(kt), stable=True)
-        csc_rowptr = torch.searchsorted(key2_s.long(), ar(TR * Ns))
-        g.csr_rowptr, g.csr_src, g.csr_perm = csr_rowptr.to(i32), csr_src.to(i32), eid_x[csr_perm]
-        g.csc_rowptr, g.csc_pos, g.csc_tgt = csc_rowptr.to(i32), csc_pos.to(i32), vt_s[csc_pos].to(i32)
+        g.E = int(eid_x.numel())
+        csr_perm, g.csr_src, g.csr_rowptr, g.csc_pos, g.csc_tgt, g.csc_rowptr = _order_edges(
+            vt_x, g.row_of_node[src[eid_x]], rel_x, Nt, Ns, TR)
+        g.csr_perm = eid_x[csr_perm]
         g.out_rowptr = g.out_edges = None
         g.src_id, g.tgt_id = src[g.csr_perm].to(i32), tgt[g.csr_perm].to(i32)
         g.shift = None if edge_shift is None else edge_shift[g.csr_perm].float().contiguous()
@@ -494,41 +461,19 @@ class RelationalGraph(object):
         rows = torch.arange(Nt, device=dev)
         r_rel, r_loc = rows // max(B, 1), rows % max(B, 1)
         r_el = r_rel // P
-        cnt_d = counts[:T]
-        row_real = (r_loc < cnt_d[r_el.clamp(max=max(T - 1, 0))]).float() if Nt > 0 else torch.zeros(0, device=dev)
+        row_real = (r_loc < counts[:T][r_el.clamp(max=max(T - 1, 0))]).float() if Nt > 0 else torch.zeros(0, device=dev)
         tn = torch.arange(TR + 1, device=dev) * B
-        rel_edges = csr_rowptr[tn[1:]] - csr_rowptr[tn[:-1]] if TR > 0 else torch.zeros(0, dtype=torch.long, device=dev)
-        # (`rel_active` [T P]: the caller knows better, e.g. a shard whose relation has edges on other ranks only)
-        if rel_active is None:
-            act = rel_edges > 0
-        elif torch.is_tensor(rel_active):
-            act = rel_active.to(dev).bool()
-        else:
-            act = torch.tensor([bool(a) for a in rel_active], dtype=torch.bool, device=dev)
+        act = _active_relations(rel_active, dev, g.csr_rowptr[tn[1:]] - g.csr_rowptr[tn[:-1]])
         g.row_active = act[r_rel].float() * row_real if Nt > 0 else row_real
         g.res_row = (r_el * B + r_loc).to(i32)
-        # relation (c; p, q) gathers sources of elements p and q only: the x_proj chain skips the other rows
-        g.src_ranges = _cached_i32(tuple(v for _c in range(T) for (p_, q_) in pairs
-                                         for v in (p_ * B, p_ * B + cnt_host[p_], (q_ * B if q_ != p_ else 0),
-                                                   (q_ * B + cnt_host[q_] if q_ != p_ else 0))), dev).view(TR, 4)
+        g.src_ranges = _src_ranges(T, B, cnt_host, dev)
         g.batch32 = None if batch is None else batch.to(i32).contiguous()
-        g.batch_rows = None
-        if batch is not None and g.num_graphs > 1:
-            g.graph_perm = torch.argsort(batch.long(), stable=True)
-            g.graph_lengths = torch.zeros(g.num_graphs, dtype=torch.long, device=dev).index_add_(
-                0, batch.long(), torch.ones_like(batch.long()))
-        else:
-            g.graph_perm = None
-            g.graph_lengths = None
+        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs)
         return g
 
     def as_struct(self):
-        from . import _lib
         if self._cstruct is None:      # the graph is immutable: build the ctypes view once, not per launch
-            self._cstruct = self._make_struct(_lib)
+            self._cstruct = _lib.Graph(self.N, self.E, self.T, self.type_rowptr.data_ptr(), self.csr_rowptr.data_ptr(),
+                                       self.csr_src.data_ptr(), self.csc_rowptr.data_ptr(), self.csc_tgt.data_ptr(),
+                                       self.csc_pos.data_ptr(), self.num_src, _lib.ptr(self.res_row))
         return self._cstruct
-
-    def _make_struct(self, _lib):
-        return _lib.Graph(self.N, self.E, self.T, self.type_rowptr.data_ptr(), self.csr_rowptr.data_ptr(),
-                          self.csr_src.data_ptr(), self.csc_rowptr.data_ptr(), self.csc_tgt.data_ptr(),
-                          self.csc_pos.data_ptr(), self.num_src, None if self.res_row is None else self.res_row.data_ptr())

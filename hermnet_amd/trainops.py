@@ -249,23 +249,19 @@ class _EdgeDiffT(torch.autograd.Function):
 
 def _edge_atoms(graph):
     """(source atom, target atom) of every CSR edge as int64, once per graph."""
-    ea = getattr(graph, "_edge_atoms64", None)
-    if ea is None:
-        ea = graph._edge_atoms64 = (graph.src_id.long(), graph.tgt_id.long())
-    return ea
+    return graph.derived("edge_atoms64", lambda: (graph.src_id.long(), graph.tgt_id.long()))
 
 
 def _edge_sum_keys(graph):
     """Row keys of the adjoint of EdgeDiff: every CSR edge by its target row; the CSC edges by (relation, source row)."""
-    ks = getattr(graph, "_edge_sum_keys", None)
-    if ks is None:
+    def make():
         T, N = graph.T, graph.N
         rp = graph.csr_rowptr.long()
         k_t = _RowKey(None, None, rp[1:] - rp[:-1], N)
         crp = graph.csc_rowptr.long()[:T * N + 1]
         k_s = _RowKey(None, graph.csc_pos.long(), crp[1:] - crp[:-1], T * N)
-        ks = graph._edge_sum_keys = (k_t, k_s, T, N)
-    return ks
+        return k_t, k_s, T, N
+    return graph.derived("edge_sum_keys", make)
 
 
 class BucketedBasis(object):
@@ -1109,9 +1105,10 @@ def _row_keys(graph, T, Nt, Ns, Ek):
     their (relation, source) rows of xh.view(T Ns, 3H), key of the residual rows or None) for `message_scatter_generic`,
     from the graph's CSR / CSC orders; built once per graph.  Nt = Ns for HVNet; HTNet has one target row per atom and
     pair relation and reads the residual from the atom's own source row (`graph.res_row`)."""
-    keys = getattr(graph, "_row_keys", None)
-    if keys is not None:
-        return keys
+    return graph.derived("row_keys", lambda: _make_row_keys(graph, T, Nt, Ns, Ek))
+
+
+def _make_row_keys(graph, T, Nt, Ns, Ek):
     dev = graph.csr_rowptr.device
     rowptr = graph.csr_rowptr.long()
     nk = int(graph.type_rowptr_host[-1])
@@ -1136,8 +1133,7 @@ def _row_keys(graph, T, Nt, Ns, Ek):
         k_res = _RowKey(res, order_r, _run_lengths(res.index_select(0, order_r), Ns), Ns)
     # rows of a known element (the others stay zero, hermnet.py:51): once per graph, not once per layer
     known = torch.arange(Nt, device=dev) < graph.type_rowptr[T:T + 1].long()
-    graph._row_keys = (k_tgt, k_all, k_xh, k_res, known.to(torch.float32))
-    return graph._row_keys
+    return k_tgt, k_all, k_xh, k_res, known.to(torch.float32)
 
 
 _SCALE = {}

@@ -1546,7 +1546,8 @@ def test_native_relation_build_is_bit_exact(name, uniform, monkeypatch):
            (ref.N, ref.E, ref.T, ref.num_atoms, ref.uniform, ref.block, ref.num_graphs)
     assert nat.type_rowptr_host == ref.type_rowptr_host
     for f in ["node_order", "row_of_node", "z_rows", "type_rowptr", "csr_rowptr", "csr_src", "csr_perm", "csc_rowptr",
-              "csc_tgt", "csc_pos", "out_rowptr", "out_edges", "src_id", "tgt_id", "row_real", "row_active", "shift"]:
+              "csc_tgt", "csc_pos", "out_rowptr", "out_edges", "src_id", "tgt_id", "row_real", "row_active", "shift",
+              "graph_perm", "graph_lengths"]:
         a, b = getattr(nat, f), getattr(ref, f)
         if f in ("out_rowptr", "out_edges") and a is None:
             continue     # the device build skips the out-adjacency (the position gradient reads the CSC order); see below

@@ -149,6 +149,44 @@ def test_relational_graph_structure(name, uniform):
     assert torch.equal(gr.row_active, has_edges[rel_row].float() * gr.row_real)
 
 
+def _small_relation_case(case):
+    """(atomic numbers, 30 random edges, z_list).  "5_1_0+2": three listed elements with 5 / 1 / 0 atoms and 2 atoms of an
+    unlisted element (8 atoms); "12": the same with 4 atoms of a second unlisted element (12 atoms); "one": one element."""
+    z = {"5_1_0+2": [13] * 5 + [28] + [79] * 2, "12": [13] * 5 + [28] + [79] * 2 + [47] * 4, "one": [14] * 6}[case]
+    gen = torch.Generator().manual_seed(12)
+    z = torch.tensor(z)[torch.randperm(len(z), generator=gen)]
+    return z, torch.randint(0, z.numel(), (2, 30), generator=gen), ([14] if case == "one" else [13, 28, 29])
+
+
+@pytest.mark.parametrize("case", ["5_1_0+2", "12", "one"])
+def test_triadic_source_rows_are_the_uniform_vertex_layout(case):
+    """The statement `relations._source_rows` rests on: HTNet's source rows are HVNet's `uniform=True` rows (an element
+    without atoms and atoms of unlisted elements included)."""
+    z, ei, zl = _small_relation_case(case)
+    hv = RelationalGraph._build_torch(z, ei, zl, uniform=True)
+    ht = RelationalGraph.build_triadic(z, ei, zl)
+    assert ht.num_src == hv.N and ht.block == hv.block
+    for a, b in [("node_order", "node_order"), ("row_of_node", "row_of_node"), ("z_rows", "z_rows"), ("src_real", "row_real")]:
+        x, y = getattr(ht, a), getattr(hv, b)
+        assert x.dtype == y.dtype and x.shape == y.shape and torch.equal(x, y), a
+
+
+@pytest.mark.parametrize("case", ["5_1_0+2", "12"])
+def test_edge_orders_do_not_depend_on_the_sort_key_width(case):
+    """`relations._order_edges` with int32 and with int64 sort keys (forced; the rule takes int64 from 2^31 keys on): the
+    same arrays, which are the graph's."""
+    from hermnet_amd import relations
+    z, ei, zl = _small_relation_case(case)
+    g = RelationalGraph._build_torch(z, ei, zl, uniform=True)
+    rel = relations._classify(z, None, zl)[0]
+    args = (g.row_of_node[ei[1]], g.row_of_node[ei[0]], rel[ei[1]], g.N, g.N, len(zl))
+    narrow, wide = relations._order_edges(*args, wide=False), relations._order_edges(*args, wide=True)
+    mine = (g.csr_perm, g.csr_src, g.csr_rowptr, g.csc_pos, g.csc_tgt, g.csc_rowptr)
+    assert len(narrow) == len(wide) == len(mine) == 6
+    for a, b, c in zip(narrow, wide, mine):
+        assert a.dtype == b.dtype == c.dtype and torch.equal(a, b) and torch.equal(a, c)
+
+
 def test_state_dict_layout_matches_reference():
     g = Golden("alloy108")
     keys = list(g.model().state_dict().keys())     # Golden.model() verifies the sha256 over keys+values

@@ -226,12 +226,21 @@ def test_native_triadic_build_is_the_torch_build(case, monkeypatch):
         assert g.type_rowptr_host == ref.type_rowptr_host
         for k in ["type_rowptr", "node_order", "row_of_node", "z_rows", "src_real", "row_real", "row_active", "res_row",
                   "csr_rowptr", "csr_src", "csr_perm", "src_id", "tgt_id", "shift", "csc_rowptr", "csc_tgt", "csc_pos",
-                  "src_ranges", "batch32"]:
+                  "src_ranges", "batch32", "graph_perm", "graph_lengths"]:     # (second pass: the cached read-out order)
             a, b = getattr(g, k), getattr(ref, k)
             assert (a is None) == (b is None), k
             if a is not None:
                 assert a.shape == b.shape and torch.equal(a.long() if not a.is_floating_point() else a,
                                                           b.long() if not b.is_floating_point() else b), k
+    # override of the relation activity (atom shards): only the first relation on, as a list and as device flags
+    flags = [True] + [False] * (ref.T - 1)
+    for rel_active in (flags, torch.tensor(flags, device=dev)):
+        monkeypatch.setattr(switches, "native_relations", False)
+        ref2 = RelationalGraph.build_triadic(*args, rel_active=rel_active)
+        monkeypatch.setattr(switches, "native_relations", True)
+        g2 = RelationalGraph.build_triadic(*args, rel_active=rel_active)
+        assert g2.row_active.shape == ref2.row_active.shape and torch.equal(g2.row_active, ref2.row_active)
+        assert bool((ref2.row_active[ref.block:] == 0).all()) and float(ref2.row_active.sum()) > 0
 
 
 @pytest.mark.gpu

@@ -16,6 +16,12 @@ from helpers import Golden, rel_err
 HERE = os.path.dirname(os.path.abspath(__file__))
 
 
+def _shared_dict():
+    """The dict the workers report into.  Its server is SPAWNED like the workers: a forked one inherits the heap of the
+    pytest process, and a garbage collection there finalises objects of a GPU runtime that does not survive a fork."""
+    return mp.get_context("spawn").Manager().dict()
+
+
 def _patch_cpu_ops(monkeypatch=None):
     """Kernels -> PyTorch restatements.  Worker processes patch for good; the pytest process passes `monkeypatch`."""
     import hermnet_amd.hermnet as hmod
@@ -64,8 +70,7 @@ def _worker(rank, world, name, port, out):
 @pytest.mark.parametrize("name,world", [("alloy108", 2), ("alloy108", 3), ("mol16", 2), ("c1_si64", 2)])
 def test_sharded_energy_and_forces_match_single_process(name, world):
     port = 29500 + (os.getpid() + hash((name, world))) % 2000
-    mgr = mp.Manager()
-    out = mgr.dict()
+    out = _shared_dict()
     mp.spawn(_worker, args=(world, name, port, out), nprocs=world, join=True)
     g = Golden(name)
     forces = np.zeros_like(g.forces.numpy())
@@ -136,8 +141,7 @@ def test_sharded_hip_path_matches_reference_golden(name, world):
     """The HIP kernels in atom-sharded mode (2-3 ranks sharing the GPU, host-staged exchange) vs the
     reference's energies/forces; the RCCL exchange differs only in the collective call."""
     port = 31500 + (os.getpid() + hash((name, world))) % 2000
-    mgr = mp.Manager()
-    out = mgr.dict()
+    out = _shared_dict()
     mp.spawn(_gpu_worker, args=(world, name, port, out), nprocs=world, join=True)
     g = Golden(name)
     forces = np.zeros_like(g.forces.numpy())
@@ -181,7 +185,7 @@ def test_rccl_backend_single_rank_smoke():
     numbers; the exchanges themselves run with payload in test_self_peer_exchange_over_rccl_carries_rows."""
     name = "alloy108"
     port = 35500 + os.getpid() % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_rccl_worker, args=(1, name, port, out), nprocs=1, join=True)
     g = Golden(name)
     e, f, owned = out[0]
@@ -288,7 +292,7 @@ def test_sharded_step_takes_no_host_synchronisation():
     has jumped past skin / 2 is reported by `check()` and taken again on a new plan; energies and forces equal the
     unsharded evaluation."""
     port = 36200 + os.getpid() % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_rccl_syncfree_worker, args=(1, port, out), nprocs=1, join=True)
     r = out[0]
     assert r["control"], "the guard did not notice the plain stepper's host reads: the test has no teeth"
@@ -602,7 +606,7 @@ def test_slab_partition_world8_gloo_matches_single_process(monkeypatch, overlap)
     from hermnet_amd import synth
     world = 8
     port = 33500 + os.getpid() % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_slab_worker, args=(world, port, out, overlap), nprocs=world, join=True)
     _patch_cpu_ops(monkeypatch)
     d = synth.fcc_alloy(reps=(3, 3, 24))
@@ -685,7 +689,7 @@ def test_self_peer_plan_on_one_rank_matches_single_process(monkeypatch, virtual)
     import hermnet_amd as hn
     from hermnet_amd import synth
     port = 34100 + (os.getpid() + virtual) % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_self_peer_worker, args=(1, port, out, virtual), nprocs=1, join=True)
     _patch_cpu_ops(monkeypatch)
     d = synth.fcc_alloy(reps=(3, 3, 24))
@@ -875,7 +879,7 @@ def test_htnet_sharded_matches_single_process(monkeypatch, planner, world):
     import hermnet_amd as hn
     from hermnet_amd import synth
     port = 35500 + (os.getpid() + world) % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_htnet_worker, args=(world, port, out, planner), nprocs=world, join=True)
     _patch_cpu_ops(monkeypatch)
     d = synth.fcc_alloy(reps=(3, 3, 12))
@@ -1029,7 +1033,7 @@ def test_slab_stepper_along_a_trajectory_matches_single_gpu():
     step energy and forces equal the unsharded evaluation of the same coordinates."""
     world = 2
     port = 38500 + os.getpid() % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_gpu_stepper_worker, args=(world, port, out), nprocs=world, join=True)
     n = out[0][0]["f_ref"].shape[0]
     for it in range(6):
@@ -1136,7 +1140,7 @@ def test_self_peer_exchange_over_rccl_carries_rows():
     cases = [("c2_golden", (10, 10, 25), 5, 2), ("slab864", (3, 3, 24), 3, 2), ("rank_of_8", (10, 10, 31), 5, 1),
              ("c4_100k", (10, 10, 250), 5, 2)]
     port = 36900 + os.getpid() % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_rccl_self_peer_worker, args=(1, port, out, cases), nprocs=1, join=True)
     for name, reps, layers, virtual in cases:
         r = out[0][name]
@@ -1168,7 +1172,7 @@ def test_sharded_100k_cell_matches_single_gpu(world, reps, overlap, kind):
     round-4 form (x | vec rows around windowed node launches), bit-identical to the blocking exchange ("0"); all with poisoned
     halo rows; kind = "htnet": the triadic model through the same sharding (its virtual target rows keep the round-4 form).)"""
     port = 37500 + (os.getpid() + world) % 2000
-    out = mp.Manager().dict()
+    out = _shared_dict()
     mp.spawn(_gpu_slab_worker, args=(world, reps, port, out, overlap, kind), nprocs=world, join=True)
     n = 4 * reps[0] * reps[1] * reps[2]
     e_ref, f_ref = torch.from_numpy(out[0]["e_ref"]), torch.from_numpy(out[0]["f_ref"])

@@ -161,7 +161,8 @@ def test_ddp_gradients_are_the_rank_average():
     with the same gradients, equal to the mean of the two single-process half-batch gradients."""
     name, world = "train_mol8_h64", 2
     port = 33500 + os.getpid() % 2000
-    out = mp.Manager().dict()
+    # (a spawned server, like the workers: a forked one would inherit this process's GPU runtime objects)
+    out = mp.get_context("spawn").Manager().dict()
     mp.spawn(_ddp_worker, args=(world, name, port, out), nprocs=world, join=True)
     for k in out[0]:
         assert np.array_equal(out[0][k], out[1][k]), k
