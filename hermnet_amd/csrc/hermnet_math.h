@@ -29,6 +29,7 @@
 struct HnEnv {
   float val;   // env(u)
   float der;   // d env / d u
+  float sval;  // env(u) for the slope of a tap, d (env g) / d u = der g + sval g': relatively accurate up to the cutoff
 };
 
 HN_HD float hn_powi(float u, int p) {
@@ -37,10 +38,27 @@ HN_HD float hn_powi(float u, int p) {
   return r;
 }
 
+// The polynomial envelope just below the cutoff, w = 1 - u <= 1 / (2p):  env = int_0^w K (1 - s)^(p-1) s^2 ds
+//   = K w^3 sum_{i < p} (-1)^i C(p-1, i) w^i / (i + 3),  K = p(p+1)(p+2)/2  (every term is below half the one before it:
+// no cancellation).  `1 - u^p (...)` below is good to an ulp of 1: at w = 1e-4 that is 1.2e-8 where env is 3.5e-11.
+// The slope of a tap, d (env g) / d u = env' g + env g', has g' = 2 coeff (u - mu) g with |2 coeff (u - mu)| up to
+// 6 (R - 1): with that env its second term is off by up to 6 (R - 1) x 1.2e-8 g, where the whole slope is ~105 w^2 g =
+// 1e-6 g.  (tests/test_message_rows.py judges every edge gradient on its own scale and found it.)
+HN_HD float hn_envelope_near_cutoff(float w, int p) {
+  const float fp = (float)p;
+  float c = 1.0f, wi = 1.0f, s = 0.0f;   // c = (-1)^i C(p-1, i)
+  for (int i = 0; i < p; ++i) {
+    s += c * wi / (float)(i + 3);
+    c = -c * (float)(p - 1 - i) / (float)(i + 1);
+    wi *= w;
+  }
+  return 0.5f * fp * (fp + 1.0f) * (fp + 2.0f) * w * w * w * s;
+}
+
 // rmnet.py:186-193 (polynomial, exponent p) and rmnet.py:206-208 (exponential).
 HN_HD HnEnv hn_envelope(float u, int kind, int p) {
   HnEnv e;
-  if (!(u < 1.0f)) { e.val = 0.0f; e.der = 0.0f; return e; }
+  if (!(u < 1.0f)) { e.val = 0.0f; e.der = 0.0f; e.sval = 0.0f; return e; }
   if (kind == 0) {
     // 1 + a u^p + b u^(p+1) + c u^(p+2)  ==  1 - u^p (1 + p w + p(p+1)/2 w^2),  w = 1 - u  (exact identity).
     // The reference's left-to-right fp32 sum cancels terms of magnitude ~p^2 and carries ~2e-6 absolute
@@ -52,6 +70,8 @@ HN_HD HnEnv hn_envelope(float u, int kind, int p) {
     e.val = 1.0f - up * (1.0f + w * (fp + 0.5f * fp * (fp + 1.0f) * w));
     const float K = 0.5f * fp * (fp + 1.0f) * (fp + 2.0f);
     e.der = -K * up1 * w * w;
+    // (val keeps its bits: the forward kernels and their tap records hold it)
+    e.sval = (w * (2.0f * fp) <= 1.0f && p >= 1) ? hn_envelope_near_cutoff(w, p) : e.val;
   } else {
     const float den = (1.0f - u) * (1.0f + u);
     const float q = -(u * u) / den;
@@ -61,6 +81,7 @@ HN_HD HnEnv hn_envelope(float u, int kind, int p) {
     e.val = expf(q);
 #endif
     e.der = -(2.0f * u) / (den * den) * e.val;
+    e.sval = e.val;
   }
   return e;
 }

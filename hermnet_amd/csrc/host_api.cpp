@@ -27,7 +27,7 @@ extern "C" int hermnet_host_rbf_row(const float* offset, int R, float inv_rc, fl
   const float u = d * inv_rc;
   const HnEnv env = hn_envelope(u, env_kind, env_p);
   const int lo = hn_window_lo(u, R);
-  const float c0 = inv_rc * env.der, c1 = inv_rc * env.val * 2.0f * coeff;
+  const float c0 = inv_rc * env.der, c1 = inv_rc * env.sval * 2.0f * coeff;
   for (int c = 0; c < C; ++c) {
     float s0 = 0.f, s1 = 0.f;
     for (int m = 0; m < HN_TAPS; ++m) {

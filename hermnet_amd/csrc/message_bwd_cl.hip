@@ -131,7 +131,7 @@ __global__ __launch_bounds__(256) void edge_table_kernel(const float4* __restric
     const float u = g.w * inv_rc;
     const HnEnv env = hn_envelope(u, env_kind, env_p);
     const int lo = hn_window_lo(u, R);
-    const float c0 = inv_rc * env.der, c1 = inv_rc * env.val * 2.0f * coeff;    // d rbfh / d d = c0 S0 + c1 S1
+    const float c0 = inv_rc * env.der, c1 = inv_rc * env.sval * 2.0f * coeff;   // d rbfh / d d = c0 S0 + c1 S1
 #pragma unroll
     for (int m = 0; m < HN_TAPS; ++m) {
       int k = lo + m;

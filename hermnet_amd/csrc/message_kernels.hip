@@ -593,7 +593,7 @@ __global__ __launch_bounds__(BWD_NW * 64, BWD_NW / 4) void message_scatter_bwd_k
           rbf_taps<true>(tb, g_, gd_);
           HN_SB;
           // d rbfh / d d = inv_rc * (env' S0 + env * 2 coeff S1)
-          const float c0 = a.inv_rc * env.der, c1 = a.inv_rc * env.val * 2.0f * a.coeff;
+          const float c0 = a.inv_rc * env.der, c1 = a.inv_rc * env.sval * 2.0f * a.coeff;
           const float rd[3] = {g.x, g.y, g.z};
           // padding slots: every term is linear in (gx1, gvec1), so scale those by 0
           const float lv = cur.live ? 1.0f : 0.0f;

@@ -89,3 +89,71 @@ def rel_err(a, b):
     """max |a-b| / max |b|  (forces have components near zero)."""
     a, b = a.detach(), b.detach()
     return float((a - b).abs().max() / b.abs().max().clamp(min=1e-30))
+
+
+def row_err(a, b):
+    """Per-row relative error: max |a - b| over a row / max |b| over that row (rows at very different scales each count)."""
+    a, b = a.detach().cpu().double().reshape(a.shape[0], -1), b.detach().cpu().double().reshape(b.shape[0], -1)
+    return (a - b).abs().amax(1) / b.abs().amax(1).clamp(min=1e-300)
+
+
+FLT_MIN = 2.0 ** -126     # the smallest normal float32: below it the values are 2^-149 apart, whatever their size
+
+
+def judge_rows(got, ref64, ref32, floor, what, rows=slice(None), tiny=0.0):
+    """Every row of `got` on its own scale against the fp64 restatement `ref64`: a row passes if its `row_err` is at most
+    max(floor, 8 x base), base = the error the fp32 restatement `ref32` makes on that row (cancellation costs fp32 itself
+    digits; a kernel must not cost more than 8 x that).  A row whose fp64 reference is identically zero passes only if it
+    is exactly zero; such rows are not "live" and do not enter the figures returned:
+    (share of the live rows on which 8 x base, not the floor, decided; worst err / bound over the live rows).
+    `tiny` (FLT_MIN where rows may underflow): a row smaller than that is held to `floor` x tiny, not to `floor` x its own
+    size -- float32 has no relative precision below FLT_MIN; a sum of H <= 128 terms each rounded to the 2^-149 grid is
+    within 128 x 2^-150 = 8e-6 FLT_MIN, inside every floor used here."""
+    assert bool(torch.isfinite(got).all()), what
+    err, base = row_err(got[rows], ref64[rows]), row_err(ref32[rows], ref64[rows])
+    r64 = ref64[rows].detach().cpu().double()
+    size = r64.reshape(r64.shape[0], -1).abs().amax(1)
+    floors = floor * torch.clamp(tiny / size.clamp(min=1e-300), min=1.0) if tiny else torch.full_like(err, floor)
+    bound = torch.maximum(floors, 8.0 * base)
+    bad = err > bound
+    assert not bool(bad.any()), (what, int(bad.sum()), float(err[bad].max()), float(base[bad].max()))
+    live = size > 0
+    if not bool(live.any()):
+        return 0.0, 0.0
+    return float((8.0 * base[live] > floors[live]).double().mean()), float((err[live] / bound[live]).max())
+
+
+def edge_grad_scale(outs, edge, cots, to_cartesian=None):
+    """A_e = sum_c max_k |gD_e^(c)| [E]: a per-edge scale of the edge gradient that does not cancel over the channels.
+    gD^(c) is the gradient of the fp64 restatement's outputs `outs` (channel last) w.r.t. its edge input `edge` with the
+    cotangents `cots` restricted to channel c -- passed through `to_cartesian` where the edge input is not the edge vector
+    itself --: one backward pass per channel through the retained graph."""
+    H = outs[0].shape[-1]
+    A = torch.zeros(edge.shape[0], dtype=edge.dtype)
+    for c in range(H):
+        only = [torch.zeros_like(g) for g in cots]
+        for o, g in zip(only, cots):
+            o[..., c] = g[..., c]
+        (gD,) = torch.autograd.grad(outs, [edge], only, retain_graph=True)
+        A += (gD if to_cartesian is None else to_cartesian(gD)).abs().amax(1)
+    return A
+
+
+def judge_edges(got, ref64, ref32, scale, floor, what, tiny=FLT_MIN):
+    """The edge rule: |got_e - ref64_e|_inf <= max(floor x A_e, 8 x base_e) for every edge, A_e = `scale` (edge_grad_scale),
+    base_e = |ref32_e - ref64_e|_inf.  An edge with A_e = 0 (no gradient in any channel) passes only if it is exactly
+    zero and is not live; one with A_e < `tiny` = FLT_MIN is held to floor x FLT_MIN (judge_rows: a cotangent row at 1e-30
+    times a source row at 1e-6 over d = 1e+4 is a gradient of 1e-40).  Returns judge_rows' two figures, plus
+    max_e base_e / A_e over the live edges."""
+    assert bool(torch.isfinite(got).all()), what
+    g, r64, r32 = (t.detach().cpu().double() for t in (got, ref64, ref32))
+    err, base = (g - r64).abs().amax(1), (r32 - r64).abs().amax(1)
+    bound = torch.maximum(floor * torch.where(scale > 0, scale.clamp(min=tiny), scale), 8.0 * base)
+    bad = err > bound
+    assert not bool(bad.any()), (what, int(bad.sum()), float((err[bad] / scale[bad].clamp(min=1e-300)).max()),
+                                 float((base[bad] / scale[bad].clamp(min=1e-300)).max()))
+    live = scale > 0
+    if not bool(live.any()):
+        return 0.0, 0.0, 0.0
+    return (float((8.0 * base[live] > floor * scale[live].clamp(min=tiny)).double().mean()), float((err[live] / bound[live]).max()),
+            float((base[live] / scale[live]).max()))

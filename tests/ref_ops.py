@@ -16,20 +16,42 @@ def geometry_ref(pos, graph, cell):
     return torch.cat([D / d[:, None], d[:, None]], dim=1)
 
 
-def envelope_ref(u, kind, p):
-    if kind == 0:
+def envelope_ref(u, kind, p, factored=False):
+    """rmnet.py:175-208.  `u` is masked BEFORE the expression as well as behind it: beyond the cutoff the expression is
+    evaluated at 0, so the gradient there is exactly 0 (torch.where alone hands the NaN of exp(-u^2 / 0) or of inf * 0
+    through its backward).  `factored`: the polynomial as 1 - u^p (1 + p w + p(p+1)/2 w^2), w = 1 - u -- the same
+    polynomial (hermnet_math.h: hn_envelope) without the reference's left-to-right cancellation of terms of size ~p^2."""
+    inside = u < 1
+    us = torch.where(inside, u, torch.zeros_like(u))
+    if kind == 0 and factored:
+        w = 1 - us
+        val = 1 - us ** p * (1 + p * w + (p * (p + 1) / 2) * w * w)
+    elif kind == 0:
         a = -(p + 1) * (p + 2) / 2
         b = p * (p + 2)
         c = -p * (p + 1) / 2
-        val = 1 + a * u ** p + b * u ** (p + 1) + c * u ** (p + 2)
+        val = 1 + a * us ** p + b * us ** (p + 1) + c * us ** (p + 2)
     else:
-        val = torch.exp(-(u ** 2) / ((1 - u) * (1 + u)))
-    return torch.where(u < 1, val, torch.zeros_like(u))
+        val = torch.exp(-(us ** 2) / ((1 - us) * (1 + us)))
+    return torch.where(inside, val, torch.zeros_like(u))
 
 
-def message_scatter_ref(xh, vec, x, edge, wt, brbf, graph, rbf):
+def window_lo_ref(d, inv_rc, R):
+    """hermnet_math.h: hn_window_lo in torch, on the fp32 distances the kernels see: lowest tap of the 12-tap window,
+    in [-5, R] (taps outside [0, R) meet zero rows)."""
+    u = d.float() * torch.tensor(inv_rc, dtype=torch.float32)
+    t = (u * float(R - 1)).clamp(0.0, float(R + 5))
+    return t.to(torch.int64) - 5
+
+
+def message_scatter_ref(xh, vec, x, edge, wt, brbf, graph, rbf, factored=False, band=None, per_relation=False, residual=None):
     """Same contract as hermnet_message_scatter_fwd.  xh [T,Ns,3H]; wt [T,R,3H]; outputs in TARGET rows
-    (graph.N; = source rows unless graph.num_src / graph.res_row are set: HTNet's virtual target rows)."""
+    (graph.N; = source rows unless graph.num_src / graph.res_row are set: HTNet's virtual target rows).
+    `factored`: envelope_ref's.  `band` = (lo [E] int64, taps): only the taps lo .. lo + taps - 1 of every edge (the
+    kernels' banding, window_lo_ref) instead of all R.  `per_relation` (implied by `band`): the projection as one
+    [E,R] x [R,3H] product per relation instead of one over a gathered [E,R,3H] weight -- the same sums.  `residual` =
+    (x rows, vec rows or None) [N, ...]: the residual's operands where they are not to be x / vec (through res_row)
+    themselves -- the kernels' backward contract with virtual target rows leaves the residual's identity term to the host."""
     T, _, H3 = xh.shape
     N = graph.N
     H = H3 // 3
@@ -43,12 +65,20 @@ def message_scatter_ref(xh, vec, x, edge, wt, brbf, graph, rbf):
     known = rel_e < T
     rhat, d = edge[:, :3], edge[:, 3]
     u = d * rbf.inv_rc
-    env = envelope_ref(u, rbf.env_kind, rbf.env_p)
+    env = envelope_ref(u, rbf.env_kind, rbf.env_p, factored)
     off = rbf.offset.to(dt)
     coeff = -0.5 / float(off[1] - off[0]) ** 2
     emb = env[:, None] * torch.exp(coeff * (u[:, None] - off[None, :]) ** 2)        # [E,R]
     re = rel_e.clamp(max=T - 1)
-    rb = torch.einsum('er,erc->ec', emb, wt[re]) + brbf[re]                          # [E,3H]
+    if band is None and not per_relation:
+        rb = torch.einsum('er,erc->ec', emb, wt[re]) + brbf[re]                      # [E,3H]
+    else:
+        if band is not None:
+            lo, taps = band
+            k = torch.arange(off.numel(), device=x.device)[None, :]
+            emb = emb * ((k >= lo[:, None]) & (k < lo[:, None] + taps)).to(dt)
+        onehot = torch.nn.functional.one_hot(re, T).to(dt)                           # [E,T]
+        rb = sum(onehot[:, t:t + 1] * (emb @ wt[t]) for t in range(T)) + brbf[re]
     m = xh[re, src] * rb
     s, a, b = m[:, :H], m[:, H:2 * H], m[:, 2 * H:]
     mv = b[:, None, :] * rhat[:, :, None]
@@ -61,8 +91,10 @@ def message_scatter_ref(xh, vec, x, edge, wt, brbf, graph, rbf):
     rk = (rel_row < T).to(dt)
     res = getattr(graph, "res_row", None)
     xr = x if res is None else x[res.long()]
-    x1 = (xr + dx) * (1 / math.sqrt(2.0)) * rk[:, None]
     v0 = torch.zeros_like(dv) if vec is None else (vec if res is None else vec[res.long()])
+    if residual is not None:
+        xr, v0 = residual[0], (torch.zeros_like(dv) if residual[1] is None else residual[1])
+    x1 = (xr + dx) * (1 / math.sqrt(2.0)) * rk[:, None]
     vec1 = (v0 + dv) * rk[:, None, None]
     return x1, vec1
 

@@ -17,7 +17,7 @@ from hermnet_amd import synth
 from hermnet_amd.ops import EdgeGeometry, MessageScatter
 from hermnet_amd.relations import RelationalGraph
 from hermnet_amd.elements import atomic_numbers
-from helpers import Golden, SMALL_CASES, NONGAUSS_CASES, rel_err
+from helpers import Golden, SMALL_CASES, NONGAUSS_CASES, rel_err, judge_rows
 import ref_ops
 
 pytestmark = pytest.mark.gpu
@@ -327,7 +327,9 @@ def test_node_kernels_match_pytorch_restatement():
                                                    # (csrc/node_chain_wide.hip; odd multiples leave a round half empty)
                                                    (192, 3, (40, 33, 50), None, 0), (320, 2, (70, 29), None, 0),
                                                    (384, 3, (33, 64, 31), False, 0), (448, 2, (50, 41), None, 0),
-                                                   (512, 3, (40, 33, 50), None, 0), (512, 1, (700,), None, 0)])
+                                                   (512, 3, (40, 33, 50), None, 0), (512, 1, (700,), None, 0),
+                                                   # a padded width whose second column block is partly empty: 100 -> 128
+                                                   (128, 3, (70, 91, 45), None, 100)])
 def test_node_chain_kernels_match_restatement(H, T, counts, uniform, hr):
     _node_chain_case(H, T, counts, uniform, hr)
 
@@ -503,15 +505,23 @@ def _node_chain_case(H, T, counts, uniform, hr):
     from test_host_logic import _layer_weights_and_graph
     from hermnet_amd import nodeops
     dev = _dev()
-    w, g = _layer_weights_and_graph(H, T, counts, uniform=uniform, unknown=5)
-    w.h_real = hr
-    if hr:      # zero-padded channels: the padded rows / columns of every weight are zero (layer.LayerWeights.refresh)
-        pytest.skip("padded widths are covered by the model-level tests (test_other_widths_vs_oracle)")
+    # hr: modules of hidden_channels = hr, which layer.LayerWeights.refresh pads to H itself (zero rows / columns in every
+    # weight, h_real = hr for the LayerNorm statistics); the operands carry zeros in the padded channels
+    w, g = _layer_weights_and_graph(hr or H, T, counts, uniform=uniform, unknown=5)
+    assert w.h_real == hr and w.w1cat.size(1) == H
     gen = torch.Generator().manual_seed(2)
     N = g.N
-    rnd = lambda *s_: torch.randn(*s_, generator=gen)
+    chan = torch.zeros(H)
+    chan[:hr or H] = 1.0
+    rnd = lambda *s_: torch.randn(*s_, generator=gen) * chan.repeat(s_[-1] // H)
     x, x1, vec1 = rnd(N, H), rnd(N, H), rnd(N, 3, H)
     gxh, gxo, gvo, add = rnd(T, N, 3 * H) * 0.3, rnd(N, H), rnd(N, 3, H), rnd(N, H)
+    pad = chan == 0
+
+    def padded_channels_are_zero(*outs):
+        """Padded channels are exactly zero in everything the kernels hand on ([.., parts * H] arrays part by part)."""
+        for t_ in outs:
+            assert not bool(t_.reshape(-1, H)[:, pad.to(t_.device)].any())
     # device copies of the weights and the graph
     import copy
     wd = copy.copy(w)
@@ -527,10 +537,12 @@ def _node_chain_case(H, T, counts, uniform, hr):
     hb_r, xh_r, mean_r, rstd_r = ref_ops.node_pre_fwd(d64(x), w, T)
     assert rel_err(hb.cpu().double(), hb_r) < 2e-6 and rel_err(xh.cpu().double(), xh_r) < 2e-6
     assert rel_err(mean.cpu().double(), mean_r) < 2e-6 and rel_err(rstd.cpu().double(), rstd_r) < 2e-6
+    padded_channels_are_zero(hb, xh)
     for a in (None, add):
         gx = nodeops.node_pre_bwd(c(gxh), hb, c(x), mean, rstd, wd, add=None if a is None else c(a))
         gx_r = ref_ops.node_pre_bwd(d64(gxh), hb_r, d64(x), mean_r, rstd_r, w, add=None if a is None else d64(a))
         assert rel_err(gx.cpu().double(), gx_r) < 5e-6
+        padded_channels_are_zero(gx)
     # row windows (atom shards: the halo exchange sits between two launches that partition the row tiles): the tiles
     # outside the windows, then the tiles that touch one, give bit for bit what one launch gives -- poisoned buffers
     # in between, windows that are empty, ragged and straddling a tile border
@@ -557,10 +569,15 @@ def _node_chain_case(H, T, counts, uniform, hr):
             real = (g.row_real[:nk] != 0) if g.row_real is not None else slice(None)
             a, b = a[real], b[real]
         assert rel_err(a, b) < 3e-6, k
+    # (nrm = sqrt(|v2|^2 + 1e-8) is 1e-4 in a padded channel, in the kernel as in the restatement: the zero columns of
+    # xvec_proj[0] take it out of everything behind it)
+    rows = real.to(dev) if torch.is_tensor(real) else real
+    padded_channels_are_zero(xo, vo, *(t_[:nk][rows] for t_ in (vp, h2b, q23)))   # (saved tensors: rows of known elements)
     gx1, gvec1 = nodeops.node_update_bwd(c(gxo), c(gvo), vp, h2b, q23, nrm, wd, gd)
     gx1_r, gvec1_r = ref_ops.node_update_bwd(d64(gxo), d64(gvo), refs[2], refs[3], refs[4], refs[5], w, g)
     assert rel_err(gx1.cpu().double(), gx1_r) < 5e-6 and rel_err(gvec1.cpu().double(), gvec1_r) < 5e-6
     assert torch.isfinite(gx1).all() and torch.isfinite(gvec1).all()
+    padded_channels_are_zero(gx1, gvec1)
 
 
 # ---- parity MARGIN: the goldens assert < 1e-5; these fail at HALF of it, so a precision trade (a trimmed
@@ -586,18 +603,12 @@ def test_parity_margin_against_reference_goldens(name):
     assert fe < MARGIN_FORCES, (name, fe)
 
 
-def _row_err(a, b):
-    """Per-row relative error: max |a - b| over a row / max |b| over that row (rows at very different scales each count)."""
-    a, b = a.detach().cpu().double().reshape(a.shape[0], -1), b.detach().cpu().double().reshape(b.shape[0], -1)
-    return (a - b).abs().amax(1) / b.abs().amax(1).clamp(min=1e-300)
-
-
 @pytest.mark.parametrize("H,T,counts,tile16", [(128, 3, (70, 91, 45), False), (128, 3, (70, 91, 45), True), (256, 2, (60, 45), False),
                                                (512, 2, (40, 33), False)])
 def test_node_chain_kernels_on_adversarial_operands(H, T, counts, tile16, monkeypatch):
     """The node chain kernels run every product as a three-way bf16 split on the bf16 matrix pipe (csrc/node_chain_common.h:
     split8, mma_panel; node_chain16.hip: mma16_panel) and claim fp32-equivalent results.  Operands chosen to break a sloppier
-    scheme, every ROW judged on its own scale (`_row_err`) against the fp64 restatement:
+    scheme, every ROW judged on its own scale (`helpers.row_err`) against the fp64 restatement:
       * per-row scales from 1e-12 to 1e+12 (x: LayerNorm input; gradients) and 1e-6 ... 1e+6 (vec: its square enters vdot),
       * cancelling rows: a constant offset of 1e3 under unit noise (LayerNorm's mean removal), vec rows whose channels
         alternate in sign so that the vec_proj sums cancel,
@@ -638,11 +649,7 @@ def test_node_chain_kernels_on_adversarial_operands(H, T, counts, tile16, monkey
     d64 = lambda t: t.double()
     nk = g.type_rowptr_host[-1]
 
-    def judge(got, ref64, ref32, floor, what, rows=slice(None)):
-        assert bool(torch.isfinite(got).all()), what
-        err, base = _row_err(got[rows], ref64[rows]), _row_err(ref32[rows], ref64[rows])
-        bad = err > torch.maximum(torch.full_like(err, floor), 8.0 * base)
-        assert not bool(bad.any()), (what, int(bad.sum()), float(err[bad].max()), float(base[bad].max()))
+    judge = judge_rows          # (helpers.py: every row on its own scale, `row_err`)
 
     # the node projection: LayerNorm -> [H -> H] -> ScaledSiLU -> [H -> 3H]; rows of [T, N, .] arrays judged per (t, row)
     hb, xh, mean, rstd = nodeops.node_pre_fwd(c(x), wd, T)
