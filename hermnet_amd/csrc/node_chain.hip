@@ -798,15 +798,44 @@ static bool use_wide(int hidden) {
   if (hidden == 64) return false;
   return force != 0 || !(hidden == 128 || hidden == 256);
 }
-// rows per tile of the pre kernels (the row windows of the halo overlap are cut at these boundaries)
-static int pre_tile_rows(int hidden) { return use_wide(hidden) ? 32 : (hidden == 256 ? 32 : 64); }
+// Rows per tile of a width's base kernels (the update chain may take 16-row tiles instead: hermnet_node_update_tile_rows).
+// The pre kernels' row windows of the halo overlap are cut at these boundaries.
+static int base_tile_rows(int hidden, bool update) {
+  if (use_wide(hidden) || hidden == 256) return 32;
+  return hidden == 64 ? 64 : (update ? 32 : 64);
+}
+static int real_width(int hidden_real, int hidden) { return hidden_real > 0 ? hidden_real : hidden; }
+
+// What the two pre-chain entry points check alike in front of their pointers.
+static bool pre_shape_ok(int num_src, int num_rel, int hidden, int hidden_real, const int* windows, int nwin, int wmode) {
+  return num_src >= 0 && num_rel > 0 && hidden_real <= hidden && wmode >= 0 && wmode <= 2 && !(wmode && (!windows || nwin < 0)) &&
+         hermnet_node_chain_supported(hidden);
+}
+
+// The one check of the update chains' arguments, each way, behind all five entry points -> -1: launch; else what the entry
+// point returns (HN_OK: no rows, the pointers unchecked; HN_ERR_BAD_ARG).  `supported`: the form's kernels exist at this
+// width; `last`: the last-layer form, whose vec_out / gvec_out is null.
+static int upd_fwd_refused(const UpdFwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
+  if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
+  if (a.N == 0) return HN_OK;
+  const bool ok = a.x1 && a.vec1 && a.wvf && a.wx0f && a.bx0 && a.wx2f && a.bx2 && a.type_rowptr && a.vp && a.h2b && a.q23 &&
+                  a.nrm && a.x_out && (last || a.vec_out) && type_rowptr_host[a.T] <= a.N;
+  return ok ? -1 : HN_ERR_BAD_ARG;
+}
+static int upd_bwd_refused(const UpdBwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
+  if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
+  if (a.N == 0) return HN_OK;
+  const bool ok = a.gxo && (last || a.gvo) && a.vp && a.h2b && a.q23 && a.nrm && a.wx2tf && a.wx0tf && a.wvtf && a.type_rowptr &&
+                  a.gx1 && a.gvec1 && type_rowptr_host[a.T] <= a.N;
+  return ok ? -1 : HN_ERR_BAD_ARG;
+}
 
 // 16 or 32: the tile height the update kernels should run this grid at.  16-row tiles cost twice the weight bytes from L2,
 // so they are chosen only where they shorten the launch: the busiest CU's share (whole tiles) is at least ~15 % smaller.
 extern "C" int hermnet_node_update_tile_rows(const int* type_rowptr_host, int num_nodes, int num_rel, int hidden) {
   const int force = hn_option(HN_OPT_UPDATE_TILE16);      // 0 never, 1 always, 2 auto
   if (!type_rowptr_host || !hermnet_node_chain_supported(hidden)) return 0;
-  const int base = use_wide(hidden) ? 32 : (hidden == 64 ? 64 : 32);
+  const int base = base_tile_rows(hidden, true);
   if (!hn_update16_supported(hidden) || use_wide(hidden) || force == 0) return base;
   if (force == 1) return 16;
   int cus = 256, dev = 0, v = 0;
@@ -818,21 +847,17 @@ extern "C" int hermnet_node_update_tile_rows(const int* type_rowptr_host, int nu
 
 extern "C" int hermnet_node_chain_supported(int hidden) { return hidden >= 64 && hidden <= 512 && hidden % 64 == 0; }
 extern "C" int hermnet_node_chain_tile_rows(int hidden, int update) {
-  if (!hermnet_node_chain_supported(hidden)) return 0;
-  if (update) return use_wide(hidden) ? 32 : (hidden == 64 ? 64 : 32);
-  return pre_tile_rows(hidden);
+  return hermnet_node_chain_supported(hidden) ? base_tile_rows(hidden, update != 0) : 0;
 }
 
 extern "C" int hermnet_node_pre_fwd(const float* x, const float* w1_frag, const float* b1, const float* w2_frag,
                                     const float* b2, float* hb, float* xh, float* mean, float* rstd,
                                     const int* src_ranges, int num_src, int num_rel, int hidden, int hidden_real,
                                     float eps, const int* row_windows, int num_windows, int window_mode, void* stream) {
-  if (num_src < 0 || num_rel <= 0 || hidden_real > hidden) return HN_ERR_BAD_ARG;
-  if (window_mode < 0 || window_mode > 2 || (window_mode && (!row_windows || num_windows < 0))) return HN_ERR_BAD_ARG;
-  if (!hermnet_node_chain_supported(hidden)) return HN_ERR_BAD_ARG;
+  if (!pre_shape_ok(num_src, num_rel, hidden, hidden_real, row_windows, num_windows, window_mode)) return HN_ERR_BAD_ARG;
   if (num_src == 0) return HN_OK;
   if (!x || !w1_frag || !b1 || !w2_frag || !b2 || !hb || !xh || !mean || !rstd) return HN_ERR_BAD_ARG;
-  PreFwdArgs a = {x, w1_frag, b1, w2_frag, b2, hb, xh, mean, rstd, src_ranges, num_src, num_rel, hidden_real > 0 ? hidden_real : hidden, eps,
+  PreFwdArgs a = {x, w1_frag, b1, w2_frag, b2, hb, xh, mean, rstd, src_ranges, num_src, num_rel, real_width(hidden_real, hidden), eps,
                   row_windows, num_windows, window_mode};
   if (use_wide(hidden)) return hn_wide_pre_fwd(hidden, a, stream);
 #define HN_GRID(TR) dim3((unsigned)((num_src + TR - 1) / TR), (unsigned)num_rel)
@@ -844,9 +869,7 @@ extern "C" int hermnet_node_pre_bwd(const float* gxh, const float* hb, const flo
                                     const float* add, float* gx, const int* src_ranges, int num_src, int num_rel,
                                     int hidden, int hidden_real, const int* row_windows, int num_windows,
                                     int window_mode, void* stream) {
-  if (num_src < 0 || num_rel <= 0 || hidden_real > hidden) return HN_ERR_BAD_ARG;
-  if (window_mode < 0 || window_mode > 2 || (window_mode && (!row_windows || num_windows < 0))) return HN_ERR_BAD_ARG;
-  if (!hermnet_node_chain_supported(hidden)) return HN_ERR_BAD_ARG;
+  if (!pre_shape_ok(num_src, num_rel, hidden, hidden_real, row_windows, num_windows, window_mode)) return HN_ERR_BAD_ARG;
   if (num_src == 0) return HN_OK;
   if (!gxh || !hb || !w2t_frag || !w1t_frag || !gn_parts || (gx && (!x || !mean || !rstd))) return HN_ERR_BAD_ARG;
   if (!gx && window_mode) return HN_ERR_BAD_ARG;
@@ -863,7 +886,7 @@ extern "C" int hermnet_node_pre_bwd(const float* gxh, const float* hb, const flo
   if (rc != HN_OK || !gx) return rc;              // (gx == NULL: the consumer runs the LayerNorm backward over the parts)
   hipLaunchKernelGGL(layernorm_bwd_parts_kernel, dim3((unsigned)((num_src + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      gn_parts, num_rel, (long)num_src * hidden, x, mean, rstd, add, gx, num_src, hidden,
-                     hidden_real > 0 ? hidden_real : hidden, row_windows, num_windows, window_mode, pre_tile_rows(hidden));
+                     real_width(hidden_real, hidden), row_windows, num_windows, window_mode, base_tile_rows(hidden, false));
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }
 
@@ -872,14 +895,10 @@ extern "C" int hermnet_node_update_fwd(const float* x1, const float* vec1, const
                                        const float* row_active, const int* type_rowptr, const int* type_rowptr_host,
                                        float* vp, float* h2b, float* q23, float* nrm, float* x_out, float* vec_out,
                                        int num_nodes, int num_rel, int hidden, int tile_rows, void* stream) {
-  if (num_nodes < 0 || num_rel <= 0 || !type_rowptr_host) return HN_ERR_BAD_ARG;
-  if (!hermnet_node_chain_supported(hidden)) return HN_ERR_BAD_ARG;
-  if (num_nodes == 0) return HN_OK;
-  if (!x1 || !vec1 || !wv_frag || !wx0_frag || !bx0 || !wx2_frag || !bx2 || !type_rowptr || !vp || !h2b || !q23 || !nrm ||
-      !x_out || !vec_out || type_rowptr_host[num_rel] > num_nodes)
-    return HN_ERR_BAD_ARG;
-  UpdFwdArgs a = {x1, vec1, wv_frag, wx0_frag, bx0, wx2_frag, bx2, row_active, type_rowptr, vp, h2b, q23, nrm, x_out,
-                  vec_out, num_nodes, num_rel};
+  const UpdFwdArgs a = {x1, vec1, wv_frag, wx0_frag, bx0, wx2_frag, bx2, row_active, type_rowptr, vp, h2b, q23, nrm, x_out,
+                        vec_out, num_nodes, num_rel};
+  const int rc = upd_fwd_refused(a, type_rowptr_host, hermnet_node_chain_supported(hidden), false);
+  if (rc >= 0) return rc;
   if (tile_rows == 16) return hn_update16_supported(hidden) ? hn_update16_fwd(hidden, a, HN_TILES(16), stream) : HN_ERR_BAD_ARG;
   if (use_wide(hidden)) return hn_wide_update_fwd(hidden, a, HN_TILES(32), stream);
   HN_UPDATE_DISPATCH(node_update_fwd_kernel, a);
@@ -890,21 +909,17 @@ extern "C" int hermnet_node_update_bwd(const float* gx_out, const float* gvec_ou
                                        const float* wvt_frag, const float* row_active, const int* type_rowptr,
                                        const int* type_rowptr_host, float* gx1, float* gvec1, int num_nodes, int num_rel,
                                        int hidden, int tile_rows, const hn_pending_grads* pending, void* stream) {
-  if (num_nodes < 0 || num_rel <= 0 || !type_rowptr_host) return HN_ERR_BAD_ARG;
-  if (!hermnet_node_chain_supported(hidden)) return HN_ERR_BAD_ARG;
-  if (num_nodes == 0) return HN_OK;
-  if (!gx_out || !gvec_out || !vp || !h2b || !q23 || !nrm || !wx2t_frag || !wx0t_frag || !wvt_frag || !type_rowptr || !gx1 ||
-      !gvec1 || type_rowptr_host[num_rel] > num_nodes)
-    return HN_ERR_BAD_ARG;
   UpdBwdArgs a = {gx_out, gvec_out, vp, h2b, q23, nrm, wx2t_frag, wx0t_frag, wvt_frag, row_active, type_rowptr, gx1, gvec1,
                   num_nodes, num_rel, {}};
+  const int rc = upd_bwd_refused(a, type_rowptr_host, hermnet_node_chain_supported(hidden), false);
+  if (rc >= 0) return rc;
   if (pending) {
     const hn_pending_grads& p = *pending;
     if ((!p.gn_parts && !p.gxh) || !p.gvec_parts || !p.x || !p.mean || !p.rstd || !p.gx1 || !p.gvec1 || p.num_parts < 1 ||
         p.hidden_real > hidden)
       return HN_ERR_BAD_ARG;
     a.pend = {p.gn_parts, p.gvec_parts, p.x, p.mean, p.rstd, p.gx1, p.gvec1, p.num_parts,
-              p.hidden_real > 0 ? p.hidden_real : hidden, p.gxh, p.hb, p.w2t_frag16, p.w1t_frag16};
+              real_width(p.hidden_real, hidden), p.gxh, p.hb, p.w2t_frag16, p.w1t_frag16};
     // fused form: the projection's backward of the layer above runs inside this launch (16-row tiles only)
     if (p.gxh && (tile_rows != 16 || !p.hb || !p.w2t_frag16 || !p.w1t_frag16)) return HN_ERR_BAD_ARG;
   }
@@ -923,17 +938,14 @@ extern "C" int hermnet_node_update_pre_fwd(const float* x1, const float* vec1, c
                                            int num_nodes, int num_rel, int hidden, const float* w1_frag16, const float* b1,
                                            const float* w2_frag16, const float* b2, float* hb, float* xh, float* mean,
                                            float* rstd, int next_num_rel, int hidden_real, float eps, void* stream) {
-  if (num_nodes < 0 || num_rel <= 0 || next_num_rel <= 0 || !type_rowptr_host || hidden_real > hidden) return HN_ERR_BAD_ARG;
-  if (!hn_update16_supported(hidden)) return HN_ERR_BAD_ARG;
-  if (num_nodes == 0) return HN_OK;
-  if (!x1 || !vec1 || !wv_frag16 || !wx0_frag16 || !bx0 || !wx2_frag16 || !bx2 || !type_rowptr || !vp || !h2b || !q23 || !nrm ||
-      !x_out || !vec_out || !w1_frag16 || !b1 || !w2_frag16 || !b2 || !hb || !xh || !mean || !rstd ||
-      type_rowptr_host[num_rel] > num_nodes)
-    return HN_ERR_BAD_ARG;
-  UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q23, nrm, x_out,
-                  vec_out, num_nodes, num_rel};
+  if (next_num_rel <= 0 || hidden_real > hidden) return HN_ERR_BAD_ARG;
+  const UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q23, nrm, x_out,
+                        vec_out, num_nodes, num_rel};
+  const int rc = upd_fwd_refused(a, type_rowptr_host, hn_update16_supported(hidden), false);
+  if (rc >= 0) return rc;
+  if (!w1_frag16 || !b1 || !w2_frag16 || !b2 || !hb || !xh || !mean || !rstd) return HN_ERR_BAD_ARG;
   PreFwdArgs p = {x_out, w1_frag16, b1, w2_frag16, b2, hb, xh, mean, rstd, nullptr, num_nodes, next_num_rel,
-                  hidden_real > 0 ? hidden_real : hidden, eps, nullptr, 0, 0};
+                  real_width(hidden_real, hidden), eps, nullptr, 0, 0};
   return hn_update16_pre_fwd(hidden, a, p, HN_TILES(16), stream);
 }
 
@@ -944,7 +956,7 @@ extern "C" int hermnet_node_pre_fwd16(const float* x, const float* w1_frag16, co
   if (num_src == 0) return HN_OK;
   if (!x || !w1_frag16 || !b1 || !w2_frag16 || !b2 || !hb || !xh || !mean || !rstd) return HN_ERR_BAD_ARG;
   PreFwdArgs p = {x, w1_frag16, b1, w2_frag16, b2, hb, xh, mean, rstd, nullptr, num_src, num_rel,
-                  hidden_real > 0 ? hidden_real : hidden, eps, nullptr, 0, 0};
+                  real_width(hidden_real, hidden), eps, nullptr, 0, 0};
   return hn_pre16_fwd(hidden, p, stream);
 }
 
@@ -983,14 +995,10 @@ extern "C" int hermnet_node_update_fwd_last(const float* x1, const float* vec1, 
                                             const float* row_active, const int* type_rowptr, const int* type_rowptr_host,
                                             float* vp, float* h2b, float* q2, float* nrm, float* x_out, int num_nodes,
                                             int num_rel, int hidden, void* stream) {
-  if (num_nodes < 0 || num_rel <= 0 || !type_rowptr_host) return HN_ERR_BAD_ARG;
-  if (!hn_update16_supported(hidden) || use_wide(hidden)) return HN_ERR_BAD_ARG;
-  if (num_nodes == 0) return HN_OK;
-  if (!x1 || !vec1 || !wv_frag16 || !wx0_frag16 || !bx0 || !wx2_frag16 || !bx2 || !type_rowptr || !vp || !h2b || !q2 || !nrm ||
-      !x_out || type_rowptr_host[num_rel] > num_nodes)
-    return HN_ERR_BAD_ARG;
-  UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q2, nrm, x_out,
-                  nullptr, num_nodes, num_rel};
+  const UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q2, nrm, x_out,
+                        nullptr, num_nodes, num_rel};
+  const int rc = upd_fwd_refused(a, type_rowptr_host, hn_update16_supported(hidden) && !use_wide(hidden), true);
+  if (rc >= 0) return rc;
   return hn_update16_fwd(hidden, a, HN_TILES(16), stream);
 }
 
@@ -999,14 +1007,10 @@ extern "C" int hermnet_node_update_bwd_last(const float* gx_out, const float* vp
                                             const float* wvt_frag16, const float* row_active, const int* type_rowptr,
                                             const int* type_rowptr_host, float* gx1, float* gvec1, int num_nodes, int num_rel,
                                             int hidden, const hn_pending_grads* pending, void* stream) {
-  if (num_nodes < 0 || num_rel <= 0 || !type_rowptr_host) return HN_ERR_BAD_ARG;
-  if (!hn_update16_supported(hidden) || use_wide(hidden)) return HN_ERR_BAD_ARG;
   if (pending) return HN_ERR_BAD_ARG;             // no layer above the last one can have handed anything down
-  if (num_nodes == 0) return HN_OK;
-  if (!gx_out || !vp || !h2b || !q2 || !nrm || !wx2t_frag16 || !wx0t_frag16 || !wvt_frag16 || !type_rowptr || !gx1 || !gvec1 ||
-      type_rowptr_host[num_rel] > num_nodes)
-    return HN_ERR_BAD_ARG;
-  UpdBwdArgs a = {gx_out, nullptr, vp, h2b, q2, nrm, wx2t_frag16, wx0t_frag16, wvt_frag16, row_active, type_rowptr, gx1, gvec1,
-                  num_nodes, num_rel, {}};
+  const UpdBwdArgs a = {gx_out, nullptr, vp, h2b, q2, nrm, wx2t_frag16, wx0t_frag16, wvt_frag16, row_active, type_rowptr, gx1,
+                        gvec1, num_nodes, num_rel, {}};
+  const int rc = upd_bwd_refused(a, type_rowptr_host, hn_update16_supported(hidden) && !use_wide(hidden), true);
+  if (rc >= 0) return rc;
   return hn_update16_bwd(hidden, a, HN_TILES(16), stream);
 }

@@ -10,8 +10,8 @@ from .elements import atomic_numbers
 from .ops import EdgeGeometry, TrueEdgeGradient, edge_radial_tables
 from .relations import RelationalGraph
 from .sharding import HaloExchange, HaloExchangeFeatures, HaloGradReturn, SumAcrossRanks
-from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, GemmRelationalLayer, LayerWeights, Route,
-                    StepState)
+from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, GemmRelationalLayer, HeadWeights, LayerWeights,
+                    Route, StepState)
 from .rmnet import PaiNNModule, RadialBasis, ScaledSiLU, relational_layer
 
 
@@ -178,12 +178,10 @@ class HVNet(nn.Module):
         rebuilds them.  Runs by itself on `load_state_dict`, `.to()` / `.cuda()` / `.float()` (`_apply`) and `train()` /
         `eval()` transitions; call it after writing parameters through `.data` (a write the caches' keys cannot see --
         the device-side guard would otherwise answer the next step with NaN and repair on the one after)."""
-        from . import layer as _layer
         self.__dict__["_cache_epoch"] = self.__dict__.get("_cache_epoch", 0) + 1    # (captured steps compare it: graph.py)
-        for conv in self.hermconvs:
-            if getattr(conv, "_weights", None) is not None:
-                conv._weights.key = None
-        del _layer._T_CACHE[:]
+        for w in [getattr(conv, "_weights", None) for conv in self.hermconvs] + [self.__dict__.get("_head")]:
+            if w is not None:
+                w.key = None
         g = self.__dict__.get("_guard")
         if g is not None:
             g.armed_for, g._event = None, None
@@ -206,7 +204,8 @@ class HVNet(nn.Module):
         return super().train(mode)
 
     def _refresh_weights(self, dev):
-        """Every layer's kernel-ready copies, current; fingerprints recorded / checked on the device (one launch)."""
+        """Every layer's kernel-ready copies and the read-out's (layer.HeadWeights; None where EnergyHead has no kernels for
+        the width), current and owned by this model; fingerprints recorded / checked on the device (one launch)."""
         from .guard import ParamGuard
         guard_on = dev.type == "cuda" and switches.param_guard()
         for _ in range(2):
@@ -215,8 +214,13 @@ class HVNet(nn.Module):
                 if conv._weights is None:
                     conv._weights = LayerWeights(conv.mods.values())
                 ws.append(conv._weights.refresh())
+            hw = None
+            if (self.hidden_channels // 2) % 4 == 0:            # (the EnergyHead kernels)
+                if self.__dict__.get("_head") is None:
+                    self.__dict__["_head"] = HeadWeights(self.out_energy)
+                hw = self._head.refresh()
             if not guard_on or not ws:
-                return ws
+                return ws, hw
             g = self.__dict__.get("_guard")
             if g is None:
                 g = self.__dict__["_guard"] = ParamGuard(self)
@@ -224,10 +228,10 @@ class HVNet(nn.Module):
             extra = tuple((p_.data_ptr(), p_._version) for p_ in (self.embed.weight, self.out_energy[0].weight,
                                                                  self.out_energy[0].bias, self.out_energy[2].weight,
                                                                  self.out_energy[2].bias))
-            if not g.step(dev, tuple((id(w), w.builds) for w in ws) + extra, ws[0].b1cat):
-                return ws
+            if not g.step(dev, tuple((id(w), w.builds) for w in ws + [hw] if w is not None) + extra, ws[0].b1cat):
+                return ws, hw
             self.invalidate_caches()            # the previous step ran on stale copies (its result was NaN): rebuild
-        return ws
+        return ws, hw
 
     # eval() treats parameters as constants (energy / force evaluation).  Set True to take the differentiable
     # device-op path in eval() as well (fine-tuning or gradient diagnostics with dropout-free eval semantics).
@@ -364,7 +368,7 @@ class HVNet(nn.Module):
         if Hp != H:
             # widths that are not a multiple of 64 run on the same kernels with zero-padded channels (layer.LayerWeights)
             x = torch.nn.functional.pad(x, (0, Hp - H))
-        weights = self._refresh_weights(pos.device) if fused and switches.fused_layer else None
+        weights, head = self._refresh_weights(pos.device) if fused and switches.fused_layer else (None, None)
         if train:
             edge, edge_parts = self._edge_geometry_autograd(pos, data.get("cell"), graph)
         elif props is not None and (props.want_virials or props.want_graph_virial):
@@ -392,7 +396,7 @@ class HVNet(nn.Module):
             edge_embed = self.radial_basis(edge[:, 3])
         data.x, data.vec = x, None                                          # (vec: zeros, hermnet.py:124)
         data._hn_graph, data._hn_edge, data._hn_edge_embed = graph, edge, edge_embed
-        step = StepState(graph, edge, rbf, edge_embed, train=train, fused=fused, whole=whole, weights=weights)
+        step = StepState(graph, edge, rbf, edge_embed, train=train, fused=fused, whole=whole, weights=weights, head=head)
         if fused and edge.requires_grad and switches.fused_layer:
             # one reduction of the edge gradients per step instead of one per layer (layer.EdgeFanout)
             # (atoms of an unknown element own the rows past type_rowptr[T]; only edges INTO them go unwritten)
@@ -428,12 +432,12 @@ class HVNet(nn.Module):
         """`out_energy` on every row, then the per-graph sums (hermnet.py:129-130) -> energy [num_graphs]."""
         graph, shard, H = step.graph, data.get("_hn_shard"), self.hidden_channels
         x = data.x if data.x.size(1) == H else data.x[:, :H]               # the read-out sees the real channels
-        head = step.fused and not step.train and switches.fused_layer and (H // 2) % 4 == 0      # (the EnergyHead kernels)
+        head, step.head = step.head, None            # (EnergyHead's copies: fused eval() at a width that has its kernels)
         # Rows that do not count are masked where the energies are made and the sum runs over the rows: no gather back to atom
         # order (its backward is an index_put, ~50 us), no mask product, no count.  One graph: the padding rows.  One structure on
         # an atom shard (the sharded MD case): the halo atoms' rows too (round 6: ~10 small launches per step less, each way).
         mask = graph.row_real if shard is None and graph.num_graphs == 1 else None
-        if shard is not None and shard.num_graphs == 1 and head:
+        if shard is not None and shard.num_graphs == 1 and head is not None:
             mask = shard.owned_rows(graph, x.size(0))
         e_rows = self._row_energies(x, step.train, head, mask)
         props = data.get("_hn_atom_props")
@@ -442,10 +446,10 @@ class HVNet(nn.Module):
         return self._graph_energies(e_rows, graph, data.batch, shard, mask is not None)
 
     def _row_energies(self, x, train, head, mask):
-        """The read-out term of every row (hermnet.py:129), row order; `mask` [rows] (optional) multiplies it."""
-        if head:
-            return EnergyHead.apply(x.contiguous(), self.out_energy[0].weight.detach(), self.out_energy[0].bias.detach(),
-                                    self.out_energy[2].weight.detach(), self.out_energy[2].bias.detach(), mask)
+        """The read-out term of every row (hermnet.py:129), row order; `mask` [rows] (optional) multiplies it.  `head`: this
+        model's layer.HeadWeights where EnergyHead runs, else None."""
+        if head is not None:
+            return EnergyHead.apply(x.contiguous(), head.w0, head.b0, head.w2v, head.b2, mask, head)
         if train and x.is_cuda:
             # (the same nn.Sequential, its two Linears through trainops.TallBmm: weight gradients over ~2e4 rows)
             from .trainops import tall_linear

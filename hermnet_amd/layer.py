@@ -19,25 +19,32 @@ from .sharding import _all_to_all_rows_start, comm_wait
 
 
 class LayerWeights(object):
-    """Kernel-ready views of one HeteroVertexConv's parameters, rebuilt when they change."""
+    """Kernel-ready views of one HeteroVertexConv's parameters, rebuilt when they change.  Every copy is a declared field;
+    a group that a width does not get is None in every field."""
+
+    STATE = ("mods", "key", "builds", "_params", "h_real", "chain")
+    # dense copies (transposed `t`, per-relation lists, stacked `_s`): the GEMM layer, the message kernels, tests/ref_ops.py
+    DENSE = ("w1cat", "b1cat", "w1cat_t", "w2", "w2t", "b2", "wt", "brbf", "wv", "wvt", "wx0", "wx0t", "bx0", "wx2", "wx2t",
+             "bx2", "wv_s", "wvt_s", "wx0_s", "wx0t_s", "bx0_s", "wx2_s", "wx2t_s", "bx2_s")
+    # frag(W), frag(W^T) of the five weights (include/hermnet_hip.h): the 32/64-row and the wide chains (widths up to 512)
+    FRAG = ("w1f", "w1tf", "w2f", "w2tf", "wvf", "wvtf", "wx0f", "wx0tf", "wx2f", "wx2tf")
+    # frag16 of the same (width 128): the 16-row update, the last-layer forms, the boundary forms (the read-out: HeadWeights)
+    FRAG16 = tuple(n + "16" for n in FRAG)
+    __slots__ = STATE + DENSE + FRAG + FRAG16
 
     def __init__(self, mods):
+        for n in self.__slots__:
+            setattr(self, n, None)
         self.mods = list(mods)
-        self.key = None
         self.builds = 0               # how often the copies were (re)built (guard.ParamGuard stamps its fingerprints with it)
         # (owner module, name) of every parameter, collected once: walking `module.parameters()` on every
         # forward costs ~0.13 ms of host time per layer
-        self._slots = [(sub, name) for m in self.mods for sub in m.modules() for name in sub._parameters]
+        self._params = [(sub, name) for m in self.mods for sub in m.modules() for name in sub._parameters]
 
-    def _version_key(self):
-        # identity + version of the CURRENT parameter objects (a replaced Parameter or an in-place update both
-        # change the key); data_ptr covers `.to(device)` / `.data = ...`
-        key = []
-        for sub, name in self._slots:
-            p = sub._parameters[name]
-            if p is not None:               # e.g. vec_proj has bias=False
-                key.append((id(p), p._version, p.data_ptr()))
-        return tuple(key)
+    @property
+    def __dict__(self):
+        """`vars(w)`: the declared fields by name (tests and tools move them to a device one by one)."""
+        return {n: getattr(self, n) for n in self.__slots__}
 
     @staticmethod
     def _pad(w, dim, parts, H, Hp, scale=None):
@@ -65,7 +72,7 @@ class LayerWeights(object):
         `h_real`), and the kernels' 1/sqrt(Hp) factors are turned back into 1/sqrt(H) by scaling the weights that
         feed them linearly by s = sqrt(Hp/H): the `a` and `b` thirds of x_proj[2] (message, rmnet.py:63-66) and the
         middle third of xvec_proj[2] (the factor of `vdot`, rmnet.py:97,104)."""
-        key = self._version_key()
+        key = _version_key(self._params)
         if key == self.key:
             return self
         ml = [m.message_layer for m in self.mods]
@@ -75,53 +82,92 @@ class LayerWeights(object):
         s = (Hp / H) ** 0.5
         self.h_real = H if Hp != H else 0
         pad = lambda w, dim, parts, scale=None: self._pad(w, dim, parts, H, Hp, scale)
+        st = lambda lst: torch.stack(lst, 0).contiguous()
+        sab = None if Hp == H else (1.0, s, s)
+        sq = None if Hp == H else (1.0, s, 1.0)
         # LayerNorm affine folded into the first Linear: (n*g + b) W1^T + b1 = n (W1*g)^T + (W1 b + b1)
         w1 = [pad(pad(m.x_proj[0].weight * m.x_layernorm.weight[None, :], 0, 1), 1, 1) for m in ml]
         b1 = [pad(m.x_proj[0].weight @ m.x_layernorm.bias + m.x_proj[0].bias, 0, 1) for m in ml]
         self.w1cat = torch.cat(w1, 0).contiguous()                                  # [T*H, H]
         self.b1cat = torch.cat(b1, 0).contiguous()                                  # [T*H]
         self.w1cat_t = self.w1cat.t().contiguous()                                  # [H, T*H]
-        sab = None if Hp == H else (1.0, s, s)
-        self.w2 = torch.stack([pad(pad(m.x_proj[2].weight, 0, 3, sab), 1, 1) for m in ml], 0).contiguous()   # [T, 3H, H]
+        self.w2 = st([pad(pad(m.x_proj[2].weight, 0, 3, sab), 1, 1) for m in ml])   # [T, 3H, H]
         self.w2t = self.w2.transpose(1, 2).contiguous()                             # [T, H, 3H]
         self.b2 = torch.stack([pad(m.x_proj[2].bias, 0, 3, sab) for m in ml], 0)[:, None, :].contiguous()     # [T,1,3H]
-        self.wt = torch.stack([pad(m.rbf_proj.weight.t(), 1, 3) for m in ml], 0).contiguous()  # [T, R, 3H]
-        self.brbf = torch.stack([pad(m.rbf_proj.bias, 0, 3) for m in ml], 0).contiguous()      # [T, 3H]
-        self.wv = [pad(pad(u.vec_proj.weight, 0, 2), 1, 1).contiguous() for u in ul]           # [2H, H]
-        self.wvt = [w.t().contiguous() for w in self.wv]                            # [H, 2H]
-        self.wx0 = [pad(pad(u.xvec_proj[0].weight, 0, 1), 1, 2).contiguous() for u in ul]      # [H, 2H]
-        self.wx0t = [w.t().contiguous() for w in self.wx0]
+        self.wt = st([pad(m.rbf_proj.weight.t(), 1, 3) for m in ml])                # [T, R, 3H]
+        self.brbf = st([pad(m.rbf_proj.bias, 0, 3) for m in ml])                    # [T, 3H]
+        # the update's three weights: per relation, transposed, and stacked for the uniform-block layout (one batched GEMM
+        # per stage): wv [2H, H], wx0 [H, 2H], wx2 [3H, H]
+        for name, ws in (("wv", [pad(pad(u.vec_proj.weight, 0, 2), 1, 1) for u in ul]),
+                         ("wx0", [pad(pad(u.xvec_proj[0].weight, 0, 1), 1, 2) for u in ul]),
+                         ("wx2", [pad(pad(u.xvec_proj[2].weight, 0, 3, sq), 1, 1) for u in ul])):
+            ws = [w.contiguous() for w in ws]
+            wts = [w.t().contiguous() for w in ws]
+            for n, v in ((name, ws), (name + "t", wts), (name + "_s", st(ws)), (name + "t_s", st(wts))):
+                setattr(self, n, v)
         self.bx0 = [pad(u.xvec_proj[0].bias, 0, 1) for u in ul]
-        sq = None if Hp == H else (1.0, s, 1.0)
-        self.wx2 = [pad(pad(u.xvec_proj[2].weight, 0, 3, sq), 1, 1).contiguous() for u in ul]  # [3H, H]
-        self.wx2t = [w.t().contiguous() for w in self.wx2]
         self.bx2 = [pad(u.xvec_proj[2].bias, 0, 3, sq) for u in ul]
-        # stacked copies for the uniform-block layout (one batched GEMM per stage)
-        st = lambda lst: torch.stack(lst, 0).contiguous()
-        self.wv_s, self.wvt_s = st(self.wv), st(self.wvt)
-        self.wx0_s, self.wx0t_s, self.bx0_s = st(self.wx0), st(self.wx0t), st(self.bx0)[:, None, :].contiguous()
-        self.wx2_s, self.wx2t_s, self.bx2_s = st(self.wx2), st(self.wx2t), st(self.bx2)[:, None, :].contiguous()
-        # MFMA-operand-order copies for the chain kernels (include/hermnet_hip.h: frag(W))
+        self.bx0_s, self.bx2_s = st(self.bx0)[:, None, :].contiguous(), st(self.bx2)[:, None, :].contiguous()
+        # MFMA-operand-order copies of the five weights [T, out, in] and their transposes for the chain kernels
         self.chain = nodeops.chain_supported(Hp)
         if self.chain:
-            fr = nodeops.weight_fragments
             w1s = self.w1cat.view(len(ml), Hp, Hp)
-            self.w1f, self.w1tf = fr(w1s), fr(w1s.transpose(1, 2).contiguous())
-            self.w2f, self.w2tf = fr(self.w2), fr(self.w2t)
-            self.wvf, self.wvtf = fr(self.wv_s), fr(self.wvt_s)
-            self.wx0f, self.wx0tf = fr(self.wx0_s), fr(self.wx0t_s)
-            self.wx2f, self.wx2tf = fr(self.wx2_s), fr(self.wx2t_s)
-            self.wvf16 = self.w1f16 = None
-            if Hp == 128:        # the update chain's 16-row form (csrc/node_chain16.hip) reads frag16 copies
-                f16 = nodeops.weight_fragments16
-                self.wvf16, self.wvtf16 = f16(self.wv_s), f16(self.wvt_s)
-                self.wx0f16, self.wx0tf16 = f16(self.wx0_s), f16(self.wx0t_s)
-                self.wx2f16, self.wx2tf16 = f16(self.wx2_s), f16(self.wx2t_s)
-                # the node projection on 16-row tiles (the fused layer boundary, csrc/node_chain16.hip)
-                self.w1f16, self.w1tf16 = f16(w1s), f16(w1s.transpose(1, 2).contiguous())
-                self.w2f16, self.w2tf16 = f16(self.w2), f16(self.w2t)
+            five = (("w1", w1s, w1s.transpose(1, 2).contiguous()), ("w2", self.w2, self.w2t), ("wv", self.wv_s, self.wvt_s),
+                    ("wx0", self.wx0_s, self.wx0t_s), ("wx2", self.wx2_s, self.wx2t_s))
+            # (frag16: the 16-row kernels of csrc/node_chain16.hip exist at width 128 only)
+            for sfx, fr in (("", nodeops.weight_fragments), ("16", nodeops.weight_fragments16))[:2 if Hp == 128 else 1]:
+                for name, w, wt in five:
+                    setattr(self, name + "f" + sfx, fr(w))
+                    setattr(self, name + "tf" + sfx, fr(wt))
         self.key = key
         self.builds += 1
+        return self
+
+
+def _version_key(params):
+    """Identity + version of the CURRENT parameter objects behind `params` = [(owner module, name)] (a replaced Parameter or
+    an in-place update both change the key); data_ptr covers `.to(device)` / `.data = ...`."""
+    key = []
+    for sub, name in params:
+        p = sub._parameters[name]
+        if p is not None:               # e.g. vec_proj has bias=False
+            key.append((id(p), p._version, p.data_ptr()))
+    return tuple(key)
+
+
+class HeadWeights(object):
+    """The same for `out_energy` (EnergyHead): the copies the read-out kernels of this width read, owned by the model they
+    were built from -- no other model can drop or evict them."""
+
+    # w0 [C, H], b0 [C], w2v [C], b2 [1]: every form; w0t [H, C]: the fused form (nodeops.head_fused_supported);
+    # w0f16, w0tf16 = frag16(w0), frag16(w0^T): the matrix-pipe form (nodeops.head16_supported, csrc/node_chain16.hip)
+    __slots__ = ("lin0", "lin2", "key", "builds", "w0", "b0", "w2v", "b2", "w0t", "w0f16", "w0tf16")
+
+    def __init__(self, out_energy=None):
+        """`out_energy`: the model's nn.Sequential (`refresh`); None: copies of loose tensors, for one call (`build`)."""
+        for n in self.__slots__:
+            setattr(self, n, None)
+        if out_energy is not None:
+            self.lin0, self.lin2 = out_energy[0], out_energy[2]
+        self.builds = 0
+
+    @torch.no_grad()
+    def refresh(self):
+        key = _version_key([(m, n) for m in (self.lin0, self.lin2) for n in ("weight", "bias")])
+        if key != self.key:
+            self.build(self.lin0.weight.detach(), self.lin0.bias.detach(), self.lin2.weight.detach(), self.lin2.bias.detach())
+            self.key = key
+            self.builds += 1
+        return self
+
+    def build(self, w0, b0, w2, b2):
+        """The copies of these four tensors; of (w0t | w0f16, w0tf16) what the read-out kernel of this width takes."""
+        H, C = w0.size(1), w0.size(0)
+        self.w0, self.b0, self.w2v, self.b2 = w0.contiguous(), b0, w2.reshape(-1).contiguous(), b2
+        if nodeops.head16_supported(H, C):
+            self.w0f16, self.w0tf16 = nodeops.weight_fragments16(self.w0), nodeops.weight_fragments16(self.w0.t().contiguous())
+        elif nodeops.head_fused_supported(H, C):
+            self.w0t = self.w0.t().contiguous()
         return self
 
 
@@ -203,10 +249,11 @@ class StepState(object):
     """The context of ONE evaluation (`data._hn_step`): what `HVNet._prepare` leaves for the layers and what the layers hand to
     each other, indexed by layer.  Every forward creates its own, so no other step or model sees it; undeclared fields raise."""
 
-    __slots__ = ("graph", "edge", "rbf", "edge_embed", "train", "fused", "whole", "weights", "edge_sink", "edge_handles",
-                 "layer", "last", "halo", "chain_node", "pending", "pre_next")
+    __slots__ = ("graph", "edge", "rbf", "edge_embed", "train", "fused", "whole", "weights", "head", "edge_sink",
+                 "edge_handles", "layer", "last", "halo", "chain_node", "pending", "pre_next")
 
-    def __init__(self, graph=None, edge=None, rbf=None, edge_embed=None, train=False, fused=False, whole=True, weights=None):
+    def __init__(self, graph=None, edge=None, rbf=None, edge_embed=None, train=False, fused=False, whole=True, weights=None,
+                 head=None):
         self.graph = graph              # _prepare: relation-ordered graph of this neighbour list; every layer, the read-out
         self.edge = edge                # _prepare: edge geometry [E,4] = (rhat, d); layers that got no handle
         self.rbf = rbf                  # _prepare: the radial basis' descriptor for the kernels (None: materialised); layers
@@ -215,6 +262,7 @@ class StepState(object):
         self.fused = fused              # _prepare: the basis is evaluated inside the kernels; the loop's `last`, the read-out
         self.whole = whole              # _prepare: no shard, or a lone world-1 plan (the unsharded forms); the loop, Route
         self.weights = weights          # _prepare: the list from `_refresh_weights` or None; layers; dropped behind the loop
+        self.head = head                # _prepare: the model's HeadWeights, current, where EnergyHead runs; the read-out takes it
         self.edge_sink = None           # _prepare: EdgeGradSink of this step, where the edge gradients are wanted; backwards
         self.edge_handles = None        # _prepare: one handle per layer from `EdgeFanout`; layers; dropped behind the loop
         self.layer = 0                  # _run_layers: index of the layer that is running its forward; that layer
@@ -465,22 +513,20 @@ class FusedRelationalLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gxo, gvo):
         x, mean, rstd, hb, xh, vec, edge, vp, h2b, q23, nrm = ctx.saved_tensors
+        pend = ctx.step.pending.pop(ctx.li, None)
         if ctx.short:
-            if ctx.step.pending.pop(ctx.li, None) is not None:
+            if pend is not None:
                 raise RuntimeError("hermnet_amd: gradients handed down to the last layer")
             gx1, gvec1 = nodeops.node_update_bwd_last(gxo.contiguous(), vp, h2b, q23, nrm, ctx.w, ctx.graph)
-            gedge = _edge_grad_slot(edge, ctx.graph, ctx.step, ctx.li, x.size(1), gx1.device)
-            gx, gvec = _ROUTES[ctx.exchange][1](ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge)
-            return (gx, gvec, _edge_grad(edge, gedge)) + (None,) * 5
-        gxo, gvo = gxo.contiguous(), gvo.contiguous()
-        # (the layer above may have left its finishing launches to this one: the buffers arrive unfilled -- and they must be
-        # the very buffers it registered: a copy made on the way would hold garbage, so that is refused loudly)
-        pend = ctx.step.pending.pop(ctx.li, None)
-        if pend is not None and (pend.gx.data_ptr() != gxo.data_ptr() or pend.gvec.data_ptr() != gvo.data_ptr()):
-            raise RuntimeError("hermnet_amd: the gradients handed down as partial sums (layer %d) did not arrive in the "
-                               "buffers they were registered with; set the environment variable named in "
-                               "hermnet_amd/switches.py: defer_sums to 0" % (ctx.li + 1))
-        gx1, gvec1 = nodeops.node_update_bwd(gxo, gvo, vp, h2b, q23, nrm, ctx.w, ctx.graph, pending=pend)
+        else:
+            gxo, gvo = gxo.contiguous(), gvo.contiguous()
+            # (the layer above may have left its finishing launches to this one: the buffers arrive unfilled -- and they must
+            # be the very buffers it registered: a copy made on the way would hold garbage, so that is refused loudly)
+            if pend is not None and (pend.gx.data_ptr() != gxo.data_ptr() or pend.gvec.data_ptr() != gvo.data_ptr()):
+                raise RuntimeError("hermnet_amd: the gradients handed down as partial sums (layer %d) did not arrive in the "
+                                   "buffers they were registered with; set the environment variable named in "
+                                   "hermnet_amd/switches.py: defer_sums to 0" % (ctx.li + 1))
+            gx1, gvec1 = nodeops.node_update_bwd(gxo, gvo, vp, h2b, q23, nrm, ctx.w, ctx.graph, pending=pend)
         gedge = _edge_grad_slot(edge, ctx.graph, ctx.step, ctx.li, x.size(1), gx1.device)
         gx, gvec = _ROUTES[ctx.exchange][1](ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge)
         return (gx, gvec, _edge_grad(edge, gedge)) + (None,) * 5
@@ -578,63 +624,34 @@ class EnergyHead(torch.autograd.Function):
     Parameters are constants here (eval() mode; train() mode runs the nn.Sequential)."""
 
     @staticmethod
-    def forward(ctx, x, w0, b0, w2, b2, mask=None):
-        """`mask` [N] (optional) multiplies the per-row energies: padding rows of the relation order -> 0."""
-        w2v = w2.reshape(-1).contiguous()
+    def forward(ctx, x, w0, b0, w2, b2, mask=None, head=None):
+        """`mask` [N] (optional) multiplies the per-row energies: padding rows of the relation order -> 0.
+        `head`: the model's HeadWeights of these four tensors (HVNet); without it the copies are built for this call."""
+        hw = head if head is not None else HeadWeights().build(w0, b0, w2, b2)
         ctx.mask = mask
-        ctx.mfma = x.is_cuda and nodeops.head16_supported(x.size(1), w0.size(0))
+        ctx.mfma = x.is_cuda and hw.w0f16 is not None
+        ctx.fused = ctx.mfma or (x.is_cuda and hw.w0t is not None)
         if ctx.mfma:       # the H -> C product on the matrix pipe (csrc/node_chain16.hip), one launch each way
-            w0c = w0.contiguous()
-            wf, wtf = _head_fragments(w0c)
-            h, e = nodeops.energy_head16_fwd(x, wf, b0, w2v, b2, mask)
-            ctx.save_for_backward(h, wtf, w2v)
-            ctx.fused, ctx.H = True, x.size(1)
+            h, e = nodeops.energy_head16_fwd(x, hw.w0f16, hw.b0, hw.w2v, hw.b2, mask)
+            ctx.save_for_backward(h, hw.w0tf16, hw.w2v)
+            ctx.H = x.size(1)
             return e
-        ctx.fused = x.is_cuda and nodeops.head_fused_supported(x.size(1), w0.size(0))
         if ctx.fused:      # one launch each way, no library GEMM (csrc/node_kernels.hip: energy_head_fused_kernel)
-            w0c = w0.contiguous()
-            h, e = nodeops.energy_head_fused_fwd(x, _transposed_once(w0c), b0, w2v, b2, mask)
-            ctx.save_for_backward(h, w0c, w2v)
-            return e
-        h = _launch("gemm", lambda: torch.addmm(b0, x, w0.t()))                       # [N, H/2]
-        ctx.save_for_backward(h, w0, w2v)
-        return nodeops.energy_head_fwd(h, w2v, b2, mask)      # [N]
+            h, e = nodeops.energy_head_fused_fwd(x, hw.w0t, hw.b0, hw.w2v, hw.b2, mask)
+        else:
+            h = _launch("gemm", lambda: torch.addmm(hw.b0, x, hw.w0.t()))             # [N, H/2]
+            e = nodeops.energy_head_fwd(h, hw.w2v, hw.b2, mask)                       # [N]
+        ctx.save_for_backward(h, hw.w0, hw.w2v)
+        return e
 
     @staticmethod
     def backward(ctx, ge):
         h, w0, w2v = ctx.saved_tensors
         if ctx.mfma:
-            return nodeops.energy_head16_bwd(ge.contiguous(), h, w0, w2v, ctx.H, ctx.mask), None, None, None, None, None
-        if ctx.fused:
-            return nodeops.energy_head_fused_bwd(ge.contiguous(), h, w0, w2v, ctx.mask), None, None, None, None, None
-        gh = nodeops.energy_head_bwd(ge.contiguous(), h, w2v, ctx.mask)
-        return _launch("gemm", lambda: torch.mm(gh, w0)), None, None, None, None, None
-
-
-_T_CACHE = []
-
-
-def _head_fragments(w):
-    """(frag16(W0), frag16(W0^T)) of the read-out's first weight, rebuilt only when it changes (the cache of `_transposed_once`;
-    guard.ParamGuard covers writes through `.data`)."""
-    key = ("frag16", w.data_ptr(), w._version, tuple(w.shape))
-    for ent in _T_CACHE:
-        if ent[0] == key:
-            return ent[2]
-    fr = (nodeops.weight_fragments16(w), nodeops.weight_fragments16(w.t().contiguous()))
-    _T_CACHE.insert(0, (key, w, fr))
-    del _T_CACHE[4:]
-    return fr
-
-
-def _transposed_once(w):
-    """w^T (contiguous), rebuilt only when the parameter changes (storage address, version, shape; the cache holds the
-    source tensor, so its address cannot be reused while the entry lives)."""
-    key = (w.data_ptr(), w._version, tuple(w.shape))
-    for ent in _T_CACHE:
-        if ent[0] == key:
-            return ent[2]
-    wt = w.t().contiguous()
-    _T_CACHE.insert(0, (key, w, wt))
-    del _T_CACHE[4:]
-    return wt
+            gx = nodeops.energy_head16_bwd(ge.contiguous(), h, w0, w2v, ctx.H, ctx.mask)
+        elif ctx.fused:
+            gx = nodeops.energy_head_fused_bwd(ge.contiguous(), h, w0, w2v, ctx.mask)
+        else:
+            gh = nodeops.energy_head_bwd(ge.contiguous(), h, w2v, ctx.mask)
+            gx = _launch("gemm", lambda: torch.mm(gh, w0))
+        return (gx,) + (None,) * 6

@@ -11,15 +11,22 @@ from .ops import _launch, _stream
 P = _lib.ptr
 
 
+def _new(like, *shape):
+    return torch.empty(*shape, dtype=like.dtype, device=like.device)
+
+
+def _call(timer_name, c_name, *args):
+    """One launch: the library's `c_name(*args, current stream)` under the timer label `timer_name`; an error code raises."""
+    _lib.check(_launch(timer_name, lambda: getattr(_lib.load(), c_name)(*args, _stream())), c_name)
+
+
 def layernorm_fwd(x, eps=1e-5, h_real=0):
     """LayerNorm without affine over the last axis -> (n, mean [rows], rstd [rows]).  `h_real` (0 = all): width of
     the statistics when the rows are zero-padded (padded outputs are zero)."""
     rows, H = x.shape
     n = torch.empty_like(x)
-    mean = torch.empty(rows, dtype=x.dtype, device=x.device)
-    rstd = torch.empty(rows, dtype=x.dtype, device=x.device)
-    _lib.check(_launch("layernorm_fwd", lambda: _lib.load().hermnet_layernorm_fwd(
-        P(x), P(n), P(mean), P(rstd), rows, H, h_real, eps, _stream())), "hermnet_layernorm_fwd")
+    mean, rstd = _new(x, rows), _new(x, rows)
+    _call("layernorm_fwd", "hermnet_layernorm_fwd", P(x), P(n), P(mean), P(rstd), rows, H, h_real, eps)
     return n, mean, rstd
 
 
@@ -27,8 +34,7 @@ def layernorm_bwd(g, x, mean, rstd, add=None, h_real=0):
     """Gradient of layernorm_fwd w.r.t. x, plus `add`."""
     rows, H = x.shape
     gx = torch.empty_like(x)
-    _lib.check(_launch("layernorm_bwd", lambda: _lib.load().hermnet_layernorm_bwd(
-        P(g), P(x), P(mean), P(rstd), P(add), P(gx), rows, H, h_real, _stream())), "hermnet_layernorm_bwd")
+    _call("layernorm_bwd", "hermnet_layernorm_bwd", P(g), P(x), P(mean), P(rstd), P(add), P(gx), rows, H, h_real)
     return gx
 
 
@@ -36,68 +42,53 @@ def ssilu_fwd(h, bias=None, rows_per_bias=0):
     """a = ScaledSiLU(h + bias); h [rows, cols]; bias [groups, cols] (group = row // rows_per_bias) or None."""
     a = torch.empty_like(h)
     cols = h.size(-1)
-    _lib.check(_launch("ssilu_fwd", lambda: _lib.load().hermnet_ssilu_fwd(
-        P(h), P(bias), rows_per_bias, P(a), h.numel() // cols, cols, _stream())), "hermnet_ssilu_fwd")
+    _call("ssilu_fwd", "hermnet_ssilu_fwd", P(h), P(bias), rows_per_bias, P(a), h.numel() // cols, cols)
     return a
 
 
 def ssilu_bwd(g, h, N, T, C, gs_n, gs_t, bias=None, rows_per_bias=0):
-    gh = torch.empty(N, T * C, dtype=h.dtype, device=h.device)
-    _lib.check(_launch("ssilu_bwd", lambda: _lib.load().hermnet_ssilu_bwd(
-        P(g), P(h), P(bias), rows_per_bias, P(gh), N, T, C, gs_n, gs_t, _stream())), "hermnet_ssilu_bwd")
+    gh = _new(h, N, T * C)
+    _call("ssilu_bwd", "hermnet_ssilu_bwd", P(g), P(h), P(bias), rows_per_bias, P(gh), N, T, C, gs_n, gs_t)
     return gh
 
 
 def update_mid(vp, x1, rows, H):
-    vdot = torch.empty(x1.size(0), H, dtype=x1.dtype, device=x1.device)
-    xin = torch.empty(x1.size(0), 2 * H, dtype=x1.dtype, device=x1.device)
-    _lib.check(_launch("update_mid", lambda: _lib.load().hermnet_update_mid(P(vp), P(x1), P(vdot), P(xin), rows, H,
-                                                                            _stream())), "hermnet_update_mid")
+    vdot, xin = _new(x1, x1.size(0), H), _new(x1, x1.size(0), 2 * H)
+    _call("update_mid", "hermnet_update_mid", P(vp), P(x1), P(vdot), P(xin), rows, H)
     return vdot, xin
 
 
 def update_out(q, vdot, vp, x1, vec1, mask, N, nk, H, qbias=None, rows_per_bias=0):
-    xo = torch.empty(N, H, dtype=x1.dtype, device=x1.device)
-    vo = torch.empty(N, 3, H, dtype=x1.dtype, device=x1.device)
-    _lib.check(_launch("update_out", lambda: _lib.load().hermnet_update_out(
-        P(q), P(qbias), rows_per_bias, P(vdot), P(vp), P(x1), P(vec1), P(mask), P(xo), P(vo), N, nk, H, _stream())),
-        "hermnet_update_out")
+    xo, vo = _new(x1, N, H), _new(x1, N, 3, H)
+    _call("update_out", "hermnet_update_out", P(q), P(qbias), rows_per_bias, P(vdot), P(vp), P(x1), P(vec1), P(mask), P(xo),
+          P(vo), N, nk, H)
     return xo, vo
 
 
 def update_out_bwd(gxo, gvo, q, vdot, vp, mask, N, nk, H, qbias=None, rows_per_bias=0):
-    dev, dt = gxo.device, gxo.dtype
-    gq = torch.empty(N, 3 * H, dtype=dt, device=dev)
-    gvdot = torch.empty(N, H, dtype=dt, device=dev)
-    gvp = torch.empty(N, 3, 2 * H, dtype=dt, device=dev)
-    gx1 = torch.empty(N, H, dtype=dt, device=dev)
-    gvec1 = torch.empty(N, 3, H, dtype=dt, device=dev)
-    _lib.check(_launch("update_out_bwd", lambda: _lib.load().hermnet_update_out_bwd(
-        P(gxo), P(gvo), P(q), P(qbias), rows_per_bias, P(vdot), P(vp), P(mask), P(gq), P(gvdot), P(gvp), P(gx1), P(gvec1),
-        N, nk, H,
-        _stream())), "hermnet_update_out_bwd")
+    gq, gvdot, gvp = _new(gxo, N, 3 * H), _new(gxo, N, H), _new(gxo, N, 3, 2 * H)
+    gx1, gvec1 = _new(gxo, N, H), _new(gxo, N, 3, H)
+    _call("update_out_bwd", "hermnet_update_out_bwd", P(gxo), P(gvo), P(q), P(qbias), rows_per_bias, P(vdot), P(vp), P(mask),
+          P(gq), P(gvdot), P(gvp), P(gx1), P(gvec1), N, nk, H)
     return gq, gvdot, gvp, gx1, gvec1
 
 
 def update_mid_bwd(gvdot, gxin, vp, xin, gvp, gx1, rows, H):
-    _lib.check(_launch("update_mid_bwd", lambda: _lib.load().hermnet_update_mid_bwd(
-        P(gvdot), P(gxin), P(vp), P(xin), P(gvp), P(gx1), rows, H, _stream())), "hermnet_update_mid_bwd")
+    _call("update_mid_bwd", "hermnet_update_mid_bwd", P(gvdot), P(gxin), P(vp), P(xin), P(gvp), P(gx1), rows, H)
 
 
 def energy_head_fwd(h, w, b, mask=None):
     """e[n] = (sum_c ScaledSiLU(h[n,c]) w[c] + b[0]) * mask[n]  (b: 1-element device tensor or None)."""
     rows, C = h.shape
-    e = torch.empty(rows, dtype=h.dtype, device=h.device)
-    _lib.check(_launch("energy_head_fwd", lambda: _lib.load().hermnet_energy_head_fwd(
-        P(h), P(w), P(b), P(mask), P(e), rows, C, _stream())), "hermnet_energy_head_fwd")
+    e = _new(h, rows)
+    _call("energy_head_fwd", "hermnet_energy_head_fwd", P(h), P(w), P(b), P(mask), P(e), rows, C)
     return e
 
 
 def energy_head_bwd(ge, h, w, mask=None):
     rows, C = h.shape
     gh = torch.empty_like(h)
-    _lib.check(_launch("energy_head_bwd", lambda: _lib.load().hermnet_energy_head_bwd(
-        P(ge), P(h), P(w), P(mask), P(gh), rows, C, _stream())), "hermnet_energy_head_bwd")
+    _call("energy_head_bwd", "hermnet_energy_head_bwd", P(ge), P(h), P(w), P(mask), P(gh), rows, C)
     return gh
 
 
@@ -109,19 +100,17 @@ def energy_head_fused_fwd(x, w0t, b0, w2, b2, mask=None):
     """x [rows,H] -> (h [rows,C] pre-activation, e [rows]) in one launch (no library GEMM); w0t = out_energy[0].weight^T."""
     rows, H = x.shape
     C = w0t.size(1)
-    h = torch.empty(rows, C, dtype=x.dtype, device=x.device)
-    e = torch.empty(rows, dtype=x.dtype, device=x.device)
-    _lib.check(_launch("energy_head_fused_fwd", lambda: _lib.load().hermnet_energy_head_fused_fwd(
-        P(x), P(w0t), P(b0), P(w2), P(b2), P(mask), P(h), P(e), rows, H, C, _stream())), "hermnet_energy_head_fused_fwd")
+    h, e = _new(x, rows, C), _new(x, rows)
+    _call("energy_head_fused_fwd", "hermnet_energy_head_fused_fwd", P(x), P(w0t), P(b0), P(w2), P(b2), P(mask), P(h), P(e),
+          rows, H, C)
     return h, e
 
 
 def energy_head_fused_bwd(ge, h, w0, w2, mask=None):
     rows, C = h.shape
     H = w0.size(1)
-    gx = torch.empty(rows, H, dtype=h.dtype, device=h.device)
-    _lib.check(_launch("energy_head_fused_bwd", lambda: _lib.load().hermnet_energy_head_fused_bwd(
-        P(ge), P(h), P(w0), P(w2), P(mask), P(gx), rows, H, C, _stream())), "hermnet_energy_head_fused_bwd")
+    gx = _new(h, rows, H)
+    _call("energy_head_fused_bwd", "hermnet_energy_head_fused_bwd", P(ge), P(h), P(w0), P(w2), P(mask), P(gx), rows, H, C)
     return gx
 
 
@@ -133,18 +122,16 @@ def energy_head16_fwd(x, w0f16, b0, w2, b2, mask=None):
     """The read-out with its H -> C product on the matrix pipe (16-row tiles, H = 128, C = 64): (h [rows,C], e [rows])."""
     rows, H = x.shape
     C = b0.numel()
-    h = torch.empty(rows, C, dtype=x.dtype, device=x.device)
-    e = torch.empty(rows, dtype=x.dtype, device=x.device)
-    _lib.check(_launch("energy_head16_fwd", lambda: _lib.load().hermnet_energy_head16_fwd(
-        P(x), P(w0f16), P(b0), P(w2), P(b2), P(mask), P(h), P(e), rows, H, C, _stream())), "hermnet_energy_head16_fwd")
+    h, e = _new(x, rows, C), _new(x, rows)
+    _call("energy_head16_fwd", "hermnet_energy_head16_fwd", P(x), P(w0f16), P(b0), P(w2), P(b2), P(mask), P(h), P(e),
+          rows, H, C)
     return h, e
 
 
 def energy_head16_bwd(ge, h, w0tf16, w2, H, mask=None):
     rows, C = h.shape
-    gx = torch.empty(rows, H, dtype=h.dtype, device=h.device)
-    _lib.check(_launch("energy_head16_bwd", lambda: _lib.load().hermnet_energy_head16_bwd(
-        P(ge), P(h), P(w0tf16), P(w2), P(mask), P(gx), rows, H, C, _stream())), "hermnet_energy_head16_bwd")
+    gx = _new(h, rows, H)
+    _call("energy_head16_bwd", "hermnet_energy_head16_bwd", P(ge), P(h), P(w0tf16), P(w2), P(mask), P(gx), rows, H, C)
     return gx
 
 
@@ -153,11 +140,9 @@ def pair_mean(x, vec, Te, P_, B, rows_out, backward=False):
     rows behind Te*B) or its gradient (backward=True: [rows_out, ...] -> [Te*P*B, ...])."""
     H = x.size(1)
     rows = Te * P_ * B if backward else rows_out
-    xo = torch.empty(rows, H, dtype=x.dtype, device=x.device)
-    vo = torch.empty(rows, 3, H, dtype=x.dtype, device=x.device)
-    _lib.check(_launch("pair_mean", lambda: _lib.load().hermnet_pair_mean(
-        1 if backward else 0, P(x), P(vec), P(xo), P(vo), Te, P_, B, rows_out, H, 1.0 / P_, 1.0 / P_, None, 0, _stream())),
-        "hermnet_pair_mean")
+    xo, vo = _new(x, rows, H), _new(x, rows, 3, H)
+    _call("pair_mean", "hermnet_pair_mean", 1 if backward else 0, P(x), P(vec), P(xo), P(vo), Te, P_, B, rows_out, H,
+          1.0 / P_, 1.0 / P_, None, 0)
     return xo, vo
 
 
@@ -166,9 +151,8 @@ def pair_sum_accumulate(x, vec, x_acc, vec_acc, Te, P_, B, scale_x, scale_vec, r
     target rows, one launch.  `ranges` = (device [k,2] int32, host list): only these rows of x_acc / vec_acc."""
     H = x.size(1)
     rd, nr = (None, 0) if ranges is None else (ranges[0], len(ranges[1]))
-    _lib.check(_launch("pair_sum", lambda: _lib.load().hermnet_pair_mean(
-        2, P(x), P(vec), P(x_acc), P(vec_acc), Te, P_, B, x_acc.size(0), H, scale_x, scale_vec, P(rd), nr, _stream())),
-        "hermnet_pair_mean")
+    _call("pair_sum", "hermnet_pair_mean", 2, P(x), P(vec), P(x_acc), P(vec_acc), Te, P_, B, x_acc.size(0), H, scale_x,
+          scale_vec, P(rd), nr)
 
 
 def halo_rows(mode, x, vec, idx, buf=None):
@@ -176,9 +160,8 @@ def halo_rows(mode, x, vec, idx, buf=None):
     (see include/hermnet_hip.h).  Returns `buf` (allocated for the packing modes)."""
     n, H = int(idx.numel()), x.size(1)
     if buf is None:
-        buf = torch.empty(n, 4 * H, dtype=x.dtype, device=x.device)
-    _lib.check(_launch("halo_rows", lambda: _lib.load().hermnet_halo_rows(
-        mode, P(x), P(vec), P(idx), n, H, P(buf), _stream())), "hermnet_halo_rows")
+        buf = _new(x, n, 4 * H)
+    _call("halo_rows", "hermnet_halo_rows", mode, P(x), P(vec), P(idx), n, H, P(buf))
     return buf
 
 
@@ -186,8 +169,8 @@ def halo_accumulate(x, vec, plan, buf):
     """rows[plan.acc_rows[u]] += sum of the packed rows `buf[plan.acc_pos[q]]` of segment u, in list order
     (ordered sums: no float atomics anywhere on the path)."""
     rows, ptr, pos = plan.accumulate_lists()
-    _lib.check(_launch("halo_accumulate", lambda: _lib.load().hermnet_halo_accumulate(
-        P(x), P(vec), P(rows), P(ptr), P(pos), int(rows.numel()), x.size(1), P(buf), _stream())), "hermnet_halo_accumulate")
+    _call("halo_accumulate", "hermnet_halo_accumulate", P(x), P(vec), P(rows), P(ptr), P(pos), int(rows.numel()), x.size(1),
+          P(buf))
 
 
 def halo_proj_rows(mode, a, b, idx, buf=None):
@@ -200,9 +183,8 @@ def halo_proj_rows(mode, a, b, idx, buf=None):
     nsum = b.size(0) if sliced else 1
     n = int(idx.numel())
     if buf is None:
-        buf = torch.empty(n, (S + 1) * W, dtype=a.dtype, device=a.device)
-    _lib.check(_launch("halo_rows", lambda: _lib.load().hermnet_halo_proj_rows(
-        mode, P(a), N * W, S, P(b), N * W, nsum, P(idx), n, W, P(buf), _stream())), "hermnet_halo_proj_rows")
+        buf = _new(a, n, (S + 1) * W)
+    _call("halo_rows", "hermnet_halo_proj_rows", mode, P(a), N * W, S, P(b), N * W, nsum, P(idx), n, W, P(buf))
     return buf
 
 
@@ -211,8 +193,8 @@ def halo_proj_accumulate(a, b, plan, buf):
     last blocks, in list order (`plan.accumulate_lists()`): the owner's side of the gradient return, no atomics."""
     rows, ptr, pos = plan.accumulate_lists()
     S, N, W = a.shape
-    _lib.check(_launch("halo_accumulate", lambda: _lib.load().hermnet_halo_proj_accumulate(
-        P(a), N * W, S, P(b), P(rows), P(ptr), P(pos), int(rows.numel()), W, P(buf), _stream())), "hermnet_halo_proj_accumulate")
+    _call("halo_accumulate", "hermnet_halo_proj_accumulate", P(a), N * W, S, P(b), P(rows), P(ptr), P(pos), int(rows.numel()),
+          W, P(buf))
 
 
 # ---- node chain kernels (csrc/node_chain.hip): one launch per chain on the fp32 matrix pipe ---------------------------
@@ -246,12 +228,7 @@ def weight_fragments(w):
     smallest first, as v_mfma_f32_32x32x16_bf16 operands:
         frag(W)[((cb * K/16 + Q) * 3 + s) * 64 + l] = 8 bf16  W_(2-s)[32 cb + (l & 31)][16 Q + 8 (l >> 5) .. +7]
     out % 32 == 0, in % 16 == 0 -> float32 [..., out * in * 3 / 2] (6 bytes per weight, opaque)."""
-    lead = w.shape[:-2]
-    o, k = w.shape[-2:]
-    n = len(lead)
-    f = torch.stack(_bf16_planes(w), dim=n).reshape(*lead, 3, o // 32, 32, k // 16, 2, 8)     # [s, cb, m, Q, g, e]
-    f = f.permute(*range(n), n + 1, n + 3, n, n + 4, n + 2, n + 5).contiguous()                # [cb, Q, s, g, m, e]
-    return f.reshape(*lead, o * k * 3).view(torch.float32)
+    return _fragments(w, 32, 16)
 
 
 def weight_fragments16(w):
@@ -259,11 +236,16 @@ def weight_fragments16(w):
     and 32-deep k-group Q the three planes as v_mfma_f32_16x16x32_bf16 operands:
         frag16(W)[((b * K/32 + Q) * 3 + s) * 64 + l] = 8 bf16  W_(2-s)[16 b + (l & 15)][32 Q + 8 (l >> 4) .. +7]
     out % 16 == 0, in % 32 == 0 -> float32 [..., out * in * 3 / 2]."""
+    return _fragments(w, 16, 32)
+
+
+def _fragments(w, rows, depth):
+    """Blocks of `rows` rows of W by k-groups of `depth`, lane l of an operand holding 8 consecutive k of row l % rows."""
     lead = w.shape[:-2]
     o, k = w.shape[-2:]
     n = len(lead)
-    f = torch.stack(_bf16_planes(w), dim=n).reshape(*lead, 3, o // 16, 16, k // 32, 4, 8)     # [s, b, m, Q, g, e]
-    f = f.permute(*range(n), n + 1, n + 3, n, n + 4, n + 2, n + 5).contiguous()                # [b, Q, s, g, m, e]
+    f = torch.stack(_bf16_planes(w), dim=n).reshape(*lead, 3, o // rows, rows, k // depth, depth // 8, 8)   # [s, b, m, Q, g, e]
+    f = f.permute(*range(n), n + 1, n + 3, n, n + 4, n + 2, n + 5).contiguous()                             # [b, Q, s, g, m, e]
     return f.reshape(*lead, o * k * 3).view(torch.float32)
 
 
@@ -274,9 +256,30 @@ def update_tile_rows(graph, H):
         _rowptr_host(graph), graph.N, graph.T, H)), key=H)
 
 
+def update_stream(graph, H, w):
+    """Which weight stream the update launches of this row layout read -> (tile_rows, (wvf, wx0f, wx2f) of the forward,
+    (wx2tf, wx0tf, wvtf) of the backward): 16-row tiles on the frag16 copies where `update_tile_rows` picks them and the width
+    has them, else tile_rows = 0 (the width's base tiles) on the frag copies.  The forward and the backward of a layer ask
+    here, and so do `last_update_supported` and `fused_boundary_supported`, whose forms have 16-row kernels only."""
+    if update_tile_rows(graph, H) == 16 and w.wvf16 is not None:
+        return _stream16(w)
+    return 0, (w.wvf, w.wx0f, w.wx2f), (w.wx2tf, w.wx0tf, w.wvtf)
+
+
+def _stream16(w):
+    return 16, (w.wvf16, w.wx0f16, w.wx2f16), (w.wx2tf16, w.wx0tf16, w.wvtf16)
+
+
 def _rowptr_host(graph):
-    import ctypes
     return graph.derived("rowptr_c", lambda: (ctypes.c_int * len(graph.type_rowptr_host))(*graph.type_rowptr_host))
+
+
+def _pre_outputs(x, T, zero_stats=False):
+    """What a node projection of x [Ns,H] writes: (hb [T,Ns,H], xh [T,Ns,3H], mean [Ns], rstd [Ns])."""
+    Ns, H = x.shape
+    alloc = torch.zeros if zero_stats else torch.empty
+    hb, xh = _new(x, T, Ns, H), _new(x, T, Ns, 3 * H)
+    return hb, xh, alloc(Ns, dtype=x.dtype, device=x.device), alloc(Ns, dtype=x.dtype, device=x.device)
 
 
 def node_pre_fwd(x, w, T, src_ranges=None, windows=None, mode=0, out=None):
@@ -285,19 +288,11 @@ def node_pre_fwd(x, w, T, src_ranges=None, windows=None, mode=0, out=None):
     `windows` [W,2] int32 + `mode` (atom shards): 1 = only the row tiles that touch a window, 2 = only the others;
     the second of the two calls passes the first one's result as `out`."""
     Ns, H = x.shape
-    dev, dt = x.device, x.dtype
-    if out is None:
-        hb = torch.empty(T, Ns, H, dtype=dt, device=dev)
-        xh = torch.empty(T, Ns, 3 * H, dtype=dt, device=dev)
-        alloc = torch.empty if src_ranges is None else torch.zeros      # rows no relation wants keep (0, 0): finite
-        mean = alloc(Ns, dtype=dt, device=dev)
-        rstd = alloc(Ns, dtype=dt, device=dev)
-    else:
-        hb, xh, mean, rstd = out
+    # (rows no relation wants keep (0, 0) statistics: finite)
+    hb, xh, mean, rstd = out if out is not None else _pre_outputs(x, T, zero_stats=src_ranges is not None)
     nwin = 0 if windows is None else int(windows.size(0))
-    _lib.check(_launch("node_pre_fwd", lambda: _lib.load().hermnet_node_pre_fwd(
-        P(x), P(w.w1f), P(w.b1cat), P(w.w2f), P(w.b2), P(hb), P(xh), P(mean), P(rstd), P(src_ranges), Ns, T, H, w.h_real,
-        1e-5, P(windows), nwin, mode if windows is not None else 0, _stream())), "hermnet_node_pre_fwd")
+    _call("node_pre_fwd", "hermnet_node_pre_fwd", P(x), P(w.w1f), P(w.b1cat), P(w.w2f), P(w.b2), P(hb), P(xh), P(mean),
+          P(rstd), P(src_ranges), Ns, T, H, w.h_real, 1e-5, P(windows), nwin, mode if windows is not None else 0)
     return hb, xh, mean, rstd
 
 
@@ -306,77 +301,85 @@ def node_pre_bwd(gxh, hb, x, mean, rstd, w, add=None, src_ranges=None, windows=N
     the first call).  `parts_only`: no LayerNorm-backward launch -- returns the per-relation partial sums [T,Ns,H] for a
     consumer that runs it itself (node_update_bwd's `pending`)."""
     T, Ns, H = hb.shape
-    if parts_only:
-        parts = torch.empty(T, Ns, H, dtype=x.dtype, device=x.device)
-        _lib.check(_launch("node_pre_bwd", lambda: _lib.load().hermnet_node_pre_bwd(
-            P(gxh), P(hb), P(w.w2tf), P(w.w1tf), P(parts), None, None, None, None, None, P(src_ranges), Ns, T, H, w.h_real,
-            None, 0, 0, _stream())), "hermnet_node_pre_bwd")
-        return parts
-    if out is None:
-        parts = torch.empty(T, Ns, H, dtype=x.dtype, device=x.device)
-        gx = torch.empty_like(x)
-    else:
-        gx, parts = out
+    if parts_only:          # (the LayerNorm backward's operands stay away, and with them the windows)
+        x = mean = rstd = add = windows = out = None
+    parts, gx = (out[1], out[0]) if out is not None else (_new(hb, T, Ns, H), None if parts_only else torch.empty_like(x))
     nwin = 0 if windows is None else int(windows.size(0))
-    _lib.check(_launch("node_pre_bwd", lambda: _lib.load().hermnet_node_pre_bwd(
-        P(gxh), P(hb), P(w.w2tf), P(w.w1tf), P(parts), P(x), P(mean), P(rstd), P(add), P(gx), P(src_ranges), Ns, T, H, w.h_real,
-        P(windows), nwin, mode if windows is not None else 0, _stream())), "hermnet_node_pre_bwd")
+    _call("node_pre_bwd", "hermnet_node_pre_bwd", P(gxh), P(hb), P(w.w2tf), P(w.w1tf), P(parts), P(x), P(mean), P(rstd),
+          P(add), P(gx), P(src_ranges), Ns, T, H, w.h_real, P(windows), nwin, mode if windows is not None else 0)
+    if parts_only:
+        return parts
     return gx if out is None and windows is None else (gx, parts)
+
+
+def _update_outputs(x1, vec_out=True):
+    """What an update forward writes: the saved (vp [N,3,2H], h2b [N,H], q23 [N,2H], nrm [N,H]), x_out [N,H] and
+    vec_out [N,3,H] (None for the form that leaves it out)."""
+    N, H = x1.shape
+    return (_new(x1, N, 3, 2 * H), _new(x1, N, H), _new(x1, N, 2 * H), _new(x1, N, H), _new(x1, N, H),
+            _new(x1, N, 3, H) if vec_out else None)
+
+
+def _update_fwd(form, x1, vec1, w, graph, w_next=None):
+    """The update forward in one of its three forms -> (x_out, vec_out, vp, h2b, q23, nrm, pre_next):
+      "general"  node_update_fwd on the stream `update_stream` picks;
+      "last"     without vec_out (kernels of the 16-row tiles only; the layer asks `last_update_supported` first);
+      "next"     with the next layer's node projection of x_out behind it (likewise; `fused_boundary_supported`)."""
+    N, H = x1.shape
+    tile, (wvf, wx0f, wx2f), _ = update_stream(graph, H, w) if form == "general" else _stream16(w)
+    vp, h2b, q23, nrm, xo, vo = _update_outputs(x1, vec_out=form != "last")
+    args = (P(x1), P(vec1), P(wvf), P(wx0f), P(w.bx0_s), P(wx2f), P(w.bx2_s), P(graph.row_active), P(graph.type_rowptr),
+            _rowptr_host(graph), P(vp), P(h2b), P(q23), P(nrm), P(xo))
+    pre = None
+    if form == "general":
+        _call("node_update_fwd", "hermnet_node_update_fwd", *args, P(vo), N, graph.T, H, tile)
+    elif form == "last":
+        _call("node_update_fwd", "hermnet_node_update_fwd_last", *args, N, graph.T, H)
+    else:
+        pre = _pre_outputs(xo, graph.T)
+        _call("node_update_pre_fwd", "hermnet_node_update_pre_fwd", *args, P(vo), N, graph.T, H, P(w_next.w1f16),
+              P(w_next.b1cat), P(w_next.w2f16), P(w_next.b2), *[P(t) for t in pre], graph.T, w_next.h_real, 1e-5)
+    return xo, vo, vp, h2b, q23, nrm, pre
+
+
+def _update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending=None):
+    """The update backward -> (gx1, gvec1); gvo = None: the last-layer form (gvec_out = 0, 16-row tiles)."""
+    N, H = gxo.shape
+    tile, _, (wx2tf, wx0tf, wvtf) = update_stream(graph, H, w) if gvo is not None else _stream16(w)
+    gx1 = torch.empty_like(gxo)
+    gvec1 = _new(gxo, N, 3, H)
+    saved = (P(vp), P(h2b), P(q23), P(nrm), P(wx2tf), P(wx0tf), P(wvtf), P(graph.row_active), P(graph.type_rowptr),
+             _rowptr_host(graph), P(gx1), P(gvec1), N, graph.T, H)
+    pend = None if pending is None else ctypes.byref(pending.struct)
+    if gvo is not None:
+        _call("node_update_bwd", "hermnet_node_update_bwd", P(gxo), P(gvo), *saved, tile, pend)
+    else:
+        _call("node_update_bwd", "hermnet_node_update_bwd_last", P(gxo), *saved, pend)
+    return gx1, gvec1
 
 
 def node_update_fwd(x1, vec1, w, graph):
     """(x1, vec1) -> (x_out, vec_out) and the saved (vp [N,3,2H], h2b [N,H], q23 [N,2H], nrm [N,H])
     (rmnet.py:94-107, 29-31)."""
-    N, H = x1.shape
-    dev, dt = x1.device, x1.dtype
-    t16 = update_tile_rows(graph, H) == 16 and getattr(w, "wvf16", None) is not None
-    wvf, wx0f, wx2f = (w.wvf16, w.wx0f16, w.wx2f16) if t16 else (w.wvf, w.wx0f, w.wx2f)
-    vp = torch.empty(N, 3, 2 * H, dtype=dt, device=dev)
-    h2b = torch.empty(N, H, dtype=dt, device=dev)
-    q23 = torch.empty(N, 2 * H, dtype=dt, device=dev)
-    nrm = torch.empty(N, H, dtype=dt, device=dev)
-    xo = torch.empty(N, H, dtype=dt, device=dev)
-    vo = torch.empty(N, 3, H, dtype=dt, device=dev)
-    _lib.check(_launch("node_update_fwd", lambda: _lib.load().hermnet_node_update_fwd(
-        P(x1), P(vec1), P(wvf), P(wx0f), P(w.bx0_s), P(wx2f), P(w.bx2_s), P(graph.row_active), P(graph.type_rowptr),
-        _rowptr_host(graph), P(vp), P(h2b), P(q23), P(nrm), P(xo), P(vo), N, graph.T, H, 16 if t16 else 0, _stream())),
-        "hermnet_node_update_fwd")
-    return xo, vo, vp, h2b, q23, nrm
+    return _update_fwd("general", x1, vec1, w, graph)[:6]
 
 
 def last_update_supported(graph, H, w):
     """The update launches of the LAST layer without its vec output (csrc/node_chain16.hip: NOVEC / NOGV): width 128 on
     16-row update tiles."""
-    return H == 128 and getattr(w, "wvf16", None) is not None and update_tile_rows(graph, H) == 16
+    return H == 128 and update_stream(graph, H, w)[0] == 16
 
 
 def node_update_fwd_last(x1, vec1, w, graph):
     """node_update_fwd where nothing reads vec_out (the last layer in front of the read-out) -> (x_out, vp, h2b, q23, nrm);
     of q23 [N,2H] only the q half is written."""
-    N, H = x1.shape
-    dev, dt = x1.device, x1.dtype
-    vp = torch.empty(N, 3, 2 * H, dtype=dt, device=dev)
-    h2b = torch.empty(N, H, dtype=dt, device=dev)
-    q23 = torch.empty(N, 2 * H, dtype=dt, device=dev)
-    nrm = torch.empty(N, H, dtype=dt, device=dev)
-    xo = torch.empty(N, H, dtype=dt, device=dev)
-    _lib.check(_launch("node_update_fwd", lambda: _lib.load().hermnet_node_update_fwd_last(
-        P(x1), P(vec1), P(w.wvf16), P(w.wx0f16), P(w.bx0_s), P(w.wx2f16), P(w.bx2_s), P(graph.row_active), P(graph.type_rowptr),
-        _rowptr_host(graph), P(vp), P(h2b), P(q23), P(nrm), P(xo), N, graph.T, H, _stream())),
-        "hermnet_node_update_fwd_last")
+    xo, _, vp, h2b, q23, nrm, _ = _update_fwd("last", x1, vec1, w, graph)
     return xo, vp, h2b, q23, nrm
 
 
 def node_update_bwd_last(gxo, vp, h2b, q23, nrm, w, graph):
     """node_update_bwd for gvec_out = 0 (the saved tensors of node_update_fwd_last) -> (gx1, gvec1)."""
-    N, H = gxo.shape
-    gx1 = torch.empty_like(gxo)
-    gvec1 = torch.empty(N, 3, H, dtype=gxo.dtype, device=gxo.device)
-    _lib.check(_launch("node_update_bwd", lambda: _lib.load().hermnet_node_update_bwd_last(
-        P(gxo), P(vp), P(h2b), P(q23), P(nrm), P(w.wx2tf16), P(w.wx0tf16), P(w.wvtf16), P(graph.row_active),
-        P(graph.type_rowptr), _rowptr_host(graph), P(gx1), P(gvec1), N, graph.T, H, None, _stream())),
-        "hermnet_node_update_bwd_last")
-    return gx1, gvec1
+    return _update_bwd(gxo, None, vp, h2b, q23, nrm, w, graph)
 
 
 class PendingGrads(object):
@@ -398,71 +401,38 @@ def fused_boundary_supported(graph, H, w, w_next=None):
     """The layer boundary as one node launch each way (csrc/node_chain16.hip): width 128, HVNet rows, and a row layout whose
     update kernels run on 16-row tiles (small grids: nodeops.update_tile_rows).  `w_next`: the next layer's weights (forward
     fusion: same width and relation count)."""
-    if H != 128 or getattr(w, "w1f16", None) is None or graph.num_src or graph.res_row is not None:
+    if H != 128 or graph.num_src or graph.res_row is not None:
         return False
-    if w_next is not None and (getattr(w_next, "w1f16", None) is None or w_next.b1cat.numel() != graph.T * H):
+    if w_next is not None and (w_next.w1f16 is None or w_next.b1cat.numel() != graph.T * H):
         return False
-    return update_tile_rows(graph, H) == 16
+    return update_stream(graph, H, w)[0] == 16
 
 
 def node_update_pre_fwd(x1, vec1, w, graph, w_next):
     """node_update_fwd of this layer + node_pre_fwd of the NEXT layer (weights `w_next`) on the rows it produces, ONE launch:
     returns (x_out, vec_out, vp, h2b, q23, nrm, (hb, xh, mean, rstd))."""
-    N, H = x1.shape
-    T = graph.T
-    dev, dt = x1.device, x1.dtype
-    vp = torch.empty(N, 3, 2 * H, dtype=dt, device=dev)
-    h2b = torch.empty(N, H, dtype=dt, device=dev)
-    q23 = torch.empty(N, 2 * H, dtype=dt, device=dev)
-    nrm = torch.empty(N, H, dtype=dt, device=dev)
-    xo = torch.empty(N, H, dtype=dt, device=dev)
-    vo = torch.empty(N, 3, H, dtype=dt, device=dev)
-    hb = torch.empty(T, N, H, dtype=dt, device=dev)
-    xh = torch.empty(T, N, 3 * H, dtype=dt, device=dev)
-    mean = torch.empty(N, dtype=dt, device=dev)
-    rstd = torch.empty(N, dtype=dt, device=dev)
-    _lib.check(_launch("node_update_pre_fwd", lambda: _lib.load().hermnet_node_update_pre_fwd(
-        P(x1), P(vec1), P(w.wvf16), P(w.wx0f16), P(w.bx0_s), P(w.wx2f16), P(w.bx2_s), P(graph.row_active), P(graph.type_rowptr),
-        _rowptr_host(graph), P(vp), P(h2b), P(q23), P(nrm), P(xo), P(vo), N, T, H,
-        P(w_next.w1f16), P(w_next.b1cat), P(w_next.w2f16), P(w_next.b2), P(hb), P(xh), P(mean), P(rstd), T, w_next.h_real,
-        1e-5, _stream())), "hermnet_node_update_pre_fwd")
-    return xo, vo, vp, h2b, q23, nrm, (hb, xh, mean, rstd)
+    return _update_fwd("next", x1, vec1, w, graph, w_next)
 
 
 def node_pre_fwd16(x, w, T):
     """node_pre_fwd on 16-row tiles (the second half of node_update_pre_fwd as a launch of its own: A/B, bit-for-bit check)."""
     Ns, H = x.shape
-    dev, dt = x.device, x.dtype
-    hb = torch.empty(T, Ns, H, dtype=dt, device=dev)
-    xh = torch.empty(T, Ns, 3 * H, dtype=dt, device=dev)
-    mean = torch.empty(Ns, dtype=dt, device=dev)
-    rstd = torch.empty(Ns, dtype=dt, device=dev)
-    _lib.check(_launch("node_pre_fwd16", lambda: _lib.load().hermnet_node_pre_fwd16(
-        P(x), P(w.w1f16), P(w.b1cat), P(w.w2f16), P(w.b2), P(hb), P(xh), P(mean), P(rstd), Ns, T, H, w.h_real, 1e-5,
-        _stream())), "hermnet_node_pre_fwd16")
-    return hb, xh, mean, rstd
+    pre = _pre_outputs(x, T)
+    _call("node_pre_fwd16", "hermnet_node_pre_fwd16", P(x), P(w.w1f16), P(w.b1cat), P(w.w2f16), P(w.b2), *[P(t) for t in pre],
+          Ns, T, H, w.h_real, 1e-5)
+    return pre
 
 
 def node_pre_bwd16(gxh, hb, w):
     """Per-relation partial sums gn [T,Ns,H] of node_pre_bwd on 16-row tiles (the first half of the fused update backward as
     a launch of its own)."""
     T, Ns, H = hb.shape
-    parts = torch.empty(T, Ns, H, dtype=hb.dtype, device=hb.device)
-    _lib.check(_launch("node_pre_bwd16", lambda: _lib.load().hermnet_node_pre_bwd16(
-        P(gxh), P(hb), P(w.w2tf16), P(w.w1tf16), P(parts), Ns, T, H, _stream())), "hermnet_node_pre_bwd16")
+    parts = _new(hb, T, Ns, H)
+    _call("node_pre_bwd16", "hermnet_node_pre_bwd16", P(gxh), P(hb), P(w.w2tf16), P(w.w1tf16), P(parts), Ns, T, H)
     return parts
 
 
 def node_update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending=None):
     """Gradient of node_update_fwd w.r.t. (x1, vec1).  `pending` (PendingGrads whose gx / gvec ARE gxo / gvo): the kernel
     forms the incoming gradients from the partial sums of the layer above first."""
-    N, H = gxo.shape
-    t16 = update_tile_rows(graph, H) == 16 and getattr(w, "wvf16", None) is not None
-    wx2tf, wx0tf, wvtf = (w.wx2tf16, w.wx0tf16, w.wvtf16) if t16 else (w.wx2tf, w.wx0tf, w.wvtf)
-    gx1 = torch.empty_like(gxo)
-    gvec1 = torch.empty_like(gvo)
-    _lib.check(_launch("node_update_bwd", lambda: _lib.load().hermnet_node_update_bwd(
-        P(gxo), P(gvo), P(vp), P(h2b), P(q23), P(nrm), P(wx2tf), P(wx0tf), P(wvtf), P(graph.row_active), P(graph.type_rowptr),
-        _rowptr_host(graph), P(gx1), P(gvec1), N, graph.T, H, 16 if t16 else 0,
-        None if pending is None else ctypes.byref(pending.struct), _stream())), "hermnet_node_update_bwd")
-    return gx1, gvec1
+    return _update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending)

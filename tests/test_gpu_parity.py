@@ -2379,6 +2379,46 @@ def test_whole_step_graph_replay_100_steps_bit_identical_to_eager(name):
     assert rel_err(e.cpu(), g.energy) < 1e-5 and rel_err(f.cpu(), g.forces) < 1e-5
 
 
+def test_a_captured_step_keeps_its_read_out_copies_whatever_another_model_does():
+    """A capture bakes in the addresses of the model's kernel-ready copies; the read-out's (layer.HeadWeights) belong to the
+    model like the layers'.  A second model in the process -- evaluated, invalidated, switched train() / eval(), evaluated
+    again -- frees none of them: memory allocated and poisoned behind that cannot be theirs, the replay repeats bit for bit."""
+    from hermnet_amd.graph import GraphedStep
+    dev = _dev()
+    g = Golden("c1_si64")                       # 64 Si atoms, H = 128, two layers
+    model_a = g.model().to(dev)
+    for p in model_a.parameters():
+        p.requires_grad_(False)
+    step = GraphedStep(model_a, g.data().to(dev))
+    e0, f0 = (t.clone() for t in step())
+    assert rel_err(e0.cpu(), g.energy) < 1e-5 and rel_err(f0.cpu(), g.forces) < 1e-5
+    head = model_a._head
+    assert head.w0f16 is not None and head.builds == 1
+
+    model_b = hn.HVNet(g.elems, **g.model_kw)
+    model_b.load_state_dict(synth.synth_state_dict(model_b.state_dict(), g.meta["weight_seed"] + 1))
+    model_b = model_b.eval().to(dev)
+    for p in model_b.parameters():
+        p.requires_grad_(False)
+
+    def eager_b():
+        d = g.data().to(dev)
+        d.pos.requires_grad_(True)
+        e = model_b(d)
+        return e.detach(), -torch.autograd.grad(e.sum(), d.pos)[0]
+
+    eb = eager_b()[0]
+    model_b.invalidate_caches()
+    model_b.train()
+    model_b.eval()
+    assert torch.equal(eager_b()[0], eb) and not torch.equal(eb, e0)
+    poison = [torch.full_like(t, float("nan")) for _ in range(16) for t in (head.w0f16, head.w0tf16)]
+    assert len(poison) == 32
+    e1, f1 = step()
+    assert torch.equal(e1, e0) and torch.equal(f1, f0)
+    assert model_a._head is head and head.builds == 1
+
+
 def test_nve_energy_conservation_on_a_fixed_neighbour_list():
     """End to end, no oracle: velocity-Verlet on the device with the model's forces (tools/md_nve.py).  With the
     neighbour list held fixed the total energy must stay put while kinetic and potential energy trade ~10 eV -- and the
