@@ -63,13 +63,16 @@ class GraphedStep(object):
         self.virial = None
         self.pos = data.pos.detach().clone().requires_grad_(True)      # static input
         data.pos = self.pos
+        if data.get("batch") is None:      # (a single graph, as the forward fills it in)
+            data.batch = torch.zeros(self.pos.size(0), dtype=torch.long, device=self.pos.device)
+        # the capture reads the atom set's arrays: held here for as long as the capture may be replayed
+        self.atoms = data._hn_atoms = model.atom_set(data.atomic_number, data.batch)
         self.graph, out = _capture(self._eager, warmup)
         self.energy, self.forces = out[:2]
         if self.stress:
             self.virial = out[2]
         # the captured topology: the tensor OBJECTS (kept alive here, so their addresses cannot be handed to a rebuilt
-        # list of the same size) and their versions (in-place edits); taken after the first forward, which fills in a
-        # missing `batch`
+        # list of the same size) and their versions (in-place edits)
         self._topo = self._topology(data)
 
     def _eager(self):
@@ -123,24 +126,32 @@ class GraphedMDStep(object):
 
     def __init__(self, model, atomic_number, cell, pos, capacity=None, warmup=3, reference_compat=False, stress=False,
                  variable_cell=False, hooks=None):
-        from .neighbor import neighbor_search, padded_capacity
-        self.reference_compat = bool(reference_compat)      # edge conventions of the reference's own pipeline (neighbor.py)
-        self._hooks = hooks
         if not pos.is_cuda or cell is None:
             raise RuntimeError("GraphedMDStep needs GPU tensors and a periodic cell")
-        if model.training:
-            raise RuntimeError("GraphedMDStep captures the eval() path")
-        self.model, self.z, self.cell = model, atomic_number, cell
-        self.stress, self.variable_cell = bool(stress), bool(variable_cell)
-        self.virial, self.last_flags = None, 0
-        if self.variable_cell:
-            self.cell = cell.detach().float().reshape(3, 3).contiguous().clone()      # static input
+        self.variable_cell = bool(variable_cell)
+        self.cell = cell.detach().float().reshape(3, 3).contiguous().clone() if self.variable_cell else cell   # static input
         self.batch = torch.zeros(atomic_number.numel(), dtype=torch.long, device=pos.device)
+        self._start(model, atomic_number, pos, capacity, warmup, reference_compat, stress, hooks)
+
+    def _start(self, model, atomic_number, pos, capacity, warmup, reference_compat, stress, hooks, **search):
+        """The tail of both constructors, behind `self.cell / batch / variable_cell`: the refusals, the static inputs, the atom
+        set the capture reads, the first capacity (from an exact search with `search`) and the capture."""
+        from .neighbor import neighbor_search, padded_capacity
+        if not pos.is_cuda:
+            raise RuntimeError("%s needs GPU tensors" % type(self).__name__)
+        if model.training:
+            raise RuntimeError("%s captures the eval() path" % type(self).__name__)
+        self.reference_compat = bool(reference_compat)      # edge conventions of the reference's own pipeline (neighbor.py)
+        if self.cell is None and self.reference_compat:
+            raise NotImplementedError("the reference pipeline's 32-neighbour cap needs the exact list (neighbor_search)")
+        self.model, self.z, self._hooks, self._warmup = model, atomic_number, hooks, warmup
+        self.stress, self.virial, self.last_flags = bool(stress), None, 0
         self.pos = pos.detach().clone().float().requires_grad_(True)      # static input
-        self._warmup = warmup
+        # the capture reads the atom set's arrays: held here, handed to every `Data` of the step (`_eager`)
+        self.atoms = model.atom_set(self.z, self.batch)
         if capacity is None:
-            capacity = padded_capacity(int(neighbor_search(self.pos.detach(), model.rc, cell,
-                                                           reference_compat=self.reference_compat)[0].size(1)))
+            out = neighbor_search(self.pos.detach(), model.rc, self.cell, reference_compat=self.reference_compat, **search)
+            capacity = padded_capacity(int((out if self.cell is None else out[0]).size(1)))
         self._capture(int(capacity))
 
     def _data(self):
@@ -156,7 +167,7 @@ class GraphedMDStep(object):
         """search + step: (energy, forces, total), with `stress` (energy, forces, virial, total), and behind them everything
         a caller copies to the host per step as ONE array (`fetch`): energies | (edges, flags) | forces (| virial)."""
         d, total = self._data()
-        d._hn_edge_count = total
+        d._hn_edge_count, d._hn_atoms = total, self.atoms
         out = _energy_forces(self.model, d, self.pos, self.stress)
         parts = [out[0].double().reshape(-1), total.double(), out[1].double().reshape(-1)]
         parts += [w.double().reshape(-1) for w in out[2:]]
@@ -263,27 +274,11 @@ class GraphedBatchMDStep(GraphedMDStep):
 
     def __init__(self, model, atomic_number, cell, pos, batch, num_graphs, capacity=None, warmup=3, reference_compat=False,
                  stress=False, hooks=None):
-        from .neighbor import neighbor_search, padded_capacity
-        self._hooks = hooks
-        if not pos.is_cuda:
-            raise RuntimeError("GraphedBatchMDStep needs GPU tensors")
-        if model.training:
-            raise RuntimeError("GraphedBatchMDStep captures the eval() path")
-        self.reference_compat = bool(reference_compat)
-        if cell is None and self.reference_compat:
-            raise NotImplementedError("the reference pipeline's 32-neighbour cap needs the exact list (neighbor_search)")
-        self.model, self.z, self.num_graphs = model, atomic_number, int(num_graphs)
+        self.num_graphs, self.variable_cell = int(num_graphs), cell is not None
         self.batch = batch.detach().long().contiguous()
         self.cell = None if cell is None else cell.detach().float().reshape(self.num_graphs, 3, 3).contiguous().clone()
-        self.stress, self.variable_cell = bool(stress), cell is not None
-        self.virial, self.last_flags = None, 0
-        self.pos = pos.detach().clone().float().requires_grad_(True)      # static input
-        self._warmup = warmup
-        if capacity is None:
-            out = neighbor_search(self.pos.detach(), model.rc, self.cell, reference_compat=self.reference_compat,
-                                  batch=self.batch, num_graphs=self.num_graphs)
-            capacity = padded_capacity(int((out if cell is None else out[0]).size(1)))
-        self._capture(int(capacity))
+        self._start(model, atomic_number, pos, capacity, warmup, reference_compat, stress, hooks,
+                    batch=self.batch, num_graphs=self.num_graphs)
 
     def _data(self):
         from .data import Data

@@ -8,7 +8,7 @@ from torch import nn
 from . import nodeops, switches
 from .elements import atomic_numbers
 from .ops import EdgeGeometry, TrueEdgeGradient, edge_radial_tables
-from .relations import RelationalGraph
+from .relations import AtomSet, RelationalGraph
 from .sharding import HaloExchange, HaloExchangeFeatures, HaloGradReturn, SumAcrossRanks
 from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, GemmRelationalLayer, HeadWeights, LayerWeights,
                     Route, StepState)
@@ -251,12 +251,20 @@ class HVNet(nn.Module):
             raise TypeError("hermnet_amd.HVNet computes in float32: parameters are %s, data.pos is %s "
                             "(call model.float() / pos.float())" % (wd, pos.dtype))
 
-    def _build_graph(self, data, zl, shard):
+    def _z_list(self):
+        return [atomic_numbers[el] for el in self.elems]
+
+    def atom_set(self, atomic_number, batch):
+        """The `relations.AtomSet` of these atoms under this model's elements.  Who replays a captured step holds it and hands
+        it to every `Data` of that step as `data._hn_atoms`: the capture reads its arrays."""
+        return AtomSet.of(atomic_number, batch, self._z_list())
+
+    def _build_graph(self, data, zl, shard, atoms):
         """Relation-ordered graph of this neighbour list (the replacement of `in_subgraph`, utils.py:11-24)."""
         rel_active = None if shard is None else shard.rel_active(zl)
         return RelationalGraph.build(data.atomic_number, data.edge_index, zl,
                                      edge_shift=data.get("edge_shift") if data.get("cell") is not None else None,
-                                     batch=data.batch, rel_active=rel_active)
+                                     batch=data.batch, rel_active=rel_active, atoms=atoms)
 
     @staticmethod
     def _edge_geometry_autograd(pos, cell, graph):
@@ -316,9 +324,11 @@ class HVNet(nn.Module):
         if data.get("batch") is None:
             # the reference fails here (scatter(..., None), hermnet.py:130); a single graph is meant
             data.batch = torch.zeros(pos.size(0), dtype=torch.long, device=pos.device)
-        zl = [atomic_numbers[el] for el in self.elems]
+        zl = self._z_list()
         # atom-sharded evaluation (hermnet_amd/sharding.py): this rank's atoms + one-hop halo
         shard = data.get("_hn_shard")
+        # the owner's relations.AtomSet of (atomic_number, batch), where a captured step made this Data; else looked up
+        atoms = data.get("_hn_atoms")
         # a padded neighbour list (neighbor.neighbor_search_padded: NULL edges behind the real ones, the count on the device)
         if data.get("_hn_edge_count") is not None and train:
             raise NotImplementedError("a padded neighbour list runs through the fused eval() path")
@@ -337,7 +347,7 @@ class HVNet(nn.Module):
         if props is not None and shard is not None:
             raise NotImplementedError("per-atom outputs / virials of atom-sharded data: the ghost atoms' shares would have to "
                                       "be sent back to their owners, which is not implemented")
-        graph = self._build_graph(data, zl, shard)
+        graph = self._build_graph(data, zl, shard, atoms)
         if props is not None and graph.num_src:
             raise NotImplementedError("per-atom outputs: HTNet's triadic graphs are not supported")
         rbf = self.radial_basis.descriptor() if fused else None
@@ -576,12 +586,12 @@ class HTNet(HVNet):
             self.hermconvs.append(HeteroTriadicConv(
                 mods={k: PaiNNModule(hidden_channels=hidden_channels, num_rbf=num_rbf) for k in keys}))
 
-    def _build_graph(self, data, zl, shard):
+    def _build_graph(self, data, zl, shard, atoms):
         if data.get("_hn_edge_count") is not None:
             raise NotImplementedError("HTNet's triadic relation build takes exact neighbour lists")
         return RelationalGraph.build_triadic(data.atomic_number, data.edge_index, zl,
                                              edge_shift=data.get("edge_shift") if data.get("cell") is not None else None,
-                                             batch=data.batch,
+                                             batch=data.batch, atoms=atoms,
                                              rel_active=None if shard is None else shard.rel_active_triadic(zl))
 
     def forward(self, data):

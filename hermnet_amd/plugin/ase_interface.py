@@ -27,40 +27,40 @@ except Exception:  # pragma: no cover - exercised on the GPU image
             self.atoms = atoms
 
 
-_SPECIES = {}      # device -> (numpy Z, z tensor, batch tensor) of the last call
+class StructureTensors(object):
+    """The structure tensors of ONE caller (an `NNCalculator`, a serve loop), REUSED while their values are unchanged: along
+    a trajectory only the coordinates change, so the relation build is handed the same `z` / `batch` objects again and
+    skips its one host sync (`relations.AtomSet.of`), the neighbour search skips reading the cell back
+    (`neighbor._cell_on_host`), and a captured step keeps seeing the tensors it was captured for."""
+
+    __slots__ = ("device", "species", "z", "batch", "cell", "cell_t")
+
+    def __init__(self, device=None):
+        self.device = None if device is None else torch.device(device)      # the owner; where the tensors live (None: host)
+        self.species = self.z = self.batch = None       # `species_tensors`: numpy Z and its z / batch tensors; build_graph, the capture's key
+        self.cell = self.cell_t = None                  # `cell_tensor`: numpy cell and its [3,3] float32 tensor; build_graph, the capture's key
+
+    def species_tensors(self, elements):
+        """Atomic numbers and the (single-graph) batch vector as tensors on the device."""
+        elements = np.asarray(elements)
+        if self.species is None or self.species.shape != elements.shape or not np.array_equal(self.species, elements):
+            z = torch.from_numpy(elements.copy()).long()
+            batch = torch.zeros(elements.shape[0], dtype=torch.long)
+            if self.device is not None:
+                z, batch = z.to(self.device), batch.to(self.device)
+            self.species, self.z, self.batch = elements.copy(), z, batch
+        return self.z, self.batch
+
+    def cell_tensor(self, cell):
+        """The cell as a [3,3] float32 tensor on the device."""
+        c = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+        if self.cell is None or not np.array_equal(self.cell, c):
+            t = torch.from_numpy(c).float()
+            self.cell, self.cell_t = c.copy(), t if self.device is None else t.to(self.device)
+        return self.cell_t
 
 
-def _species_tensors(elements, device):
-    """Atomic numbers and the (single-graph) batch vector as device tensors, REUSED while the species list is
-    unchanged: along a trajectory only the coordinates change, and the relation build skips its one host sync
-    (element counts) when it is handed the same tensor objects again (`relations._COUNT_CACHE`)."""
-    elements = np.asarray(elements)
-    key = str(device)
-    hit = _SPECIES.get(key)
-    if hit is None or hit[0].shape != elements.shape or not np.array_equal(hit[0], elements):
-        z = torch.from_numpy(elements.copy()).long()
-        batch = torch.zeros(elements.shape[0], dtype=torch.long)
-        if device is not None:
-            z, batch = z.to(device), batch.to(device)
-        hit = _SPECIES[key] = (elements.copy(), z, batch)
-    return hit[1], hit[2]
-
-
-_CELLS = {}      # device -> (numpy cell, tensor) of the last call
-
-
-def _cell_tensor(cell, device):
-    """The cell as a [3,3] float32 tensor on `device`, REUSED while its values are unchanged (NVT / NVE: the neighbour
-    search then skips reading it back, `neighbor._cell_on_host`, and a captured step keeps seeing the same tensor)."""
-    c = np.asarray(cell, dtype=np.float64).reshape(3, 3)
-    key = str(device)
-    hit = _CELLS.get(key)
-    if hit is None or not np.array_equal(hit[0], c):
-        hit = _CELLS[key] = (c.copy(), torch.from_numpy(c).float().to(device))
-    return hit[1]
-
-
-def build_graph(cell, elements, pos, rc, device=None, reference_compat=False, capacity=None):
+def build_graph(cell, elements, pos, rc, device=None, reference_compat=False, capacity=None, structure=None):
     """`calculator.py:10-27`: numpy (cell [3,3] or None, Z [N], pos [N,3]) -> `Data` with the cutoff graph.
     `capacity` (periodic cells on the GPU): the neighbour list is built WITHOUT its host read, padded to that many columns
     (`neighbor.neighbor_search_padded`); `data._hn_edge_count` then holds (E, flags) on the device for a check behind
@@ -68,16 +68,21 @@ def build_graph(cell, elements, pos, rc, device=None, reference_compat=False, ca
     With `device` set to the GPU the coordinates are uploaded first and the neighbour search runs on the
     device (`csrc/neighbor_kernels.hip`) instead of the host -- the reference rebuilds the list every step.
     `reference_compat`: the edge conventions of the reference's own pipeline (`neighbor.neighbor_search`),
-    for checkpoints trained through it on periodic data."""
+    for checkpoints trained through it on periodic data.
+    `structure`: the caller's `StructureTensors` for `device` (calls along a trajectory); without one the tensors are new."""
+    if structure is None:
+        structure = StructureTensors(device)
+    elif structure.device != (None if device is None else torch.device(device)):
+        raise ValueError("build_graph: `structure` holds tensors for %s, not for %s" % (structure.device, device))
     pos_t = torch.from_numpy(np.asarray(pos)).float()
     if device is not None:
         pos_t = pos_t.to(device)
-    z, batch = _species_tensors(elements, device)
+    z, batch = structure.species_tensors(elements)
     data = Data(atomic_number=z, pos=pos_t, batch=batch)
     if cell is None or not np.any(np.asarray(cell)):
         data.edge_index = neighbor_search(pos=pos_t, rc=rc, reference_compat=reference_compat)
     else:
-        cell_t = _cell_tensor(cell, pos_t.device)
+        cell_t = structure.cell_tensor(cell)
         if capacity is not None and pos_t.is_cuda:
             from ..neighbor import neighbor_search_padded
             data.edge_index, data.edge_shift, data._hn_edge_count = neighbor_search_padded(
@@ -201,6 +206,8 @@ class NNCalculator(_Base):
         self.graph_replay = bool(graph_replay)
         self.replay_stress = bool(replay_stress)
         self._graphed = None              # ((z tensor, cell tensor, N), GraphedMDStep)
+        # this calculator's z / batch / cell tensors (build_graph, the capture's key): no other calculator replaces them
+        self._structure = StructureTensors(device_ if torch.device(device_).type == 'cuda' else None)
         self.graph_captures = 0           # how often a step was captured (diagnostics / tests)
         self.device_ = device_
         device = torch.device(device_)
@@ -218,14 +225,14 @@ class NNCalculator(_Base):
         eagerly.  With `replay_stress` the cell is an input of the capture (uploaded per call, never part of its key)."""
         from ..graph import GraphedMDStep
         dev = torch.device(self.device_)
-        z, _batch = _species_tensors(elems, dev)
+        z, _batch = self._structure.species_tensors(elems)
         var = self.replay_stress
         pos_t = torch.from_numpy(np.ascontiguousarray(positions, dtype=np.float32))     # host: copied into the captured input
         if var:
-            # (float32 values of the float64 cell: the numbers `_cell_tensor` hands the eager path)
+            # (float32 values of the float64 cell: the numbers `cell_tensor` hands the eager path)
             cell_t, cell_in = None, torch.from_numpy(np.asarray(cell, dtype=np.float64).reshape(3, 3)).float()
         else:
-            cell_t, cell_in = _cell_tensor(cell, dev), None
+            cell_t, cell_in = self._structure.cell_tensor(cell), None
         g = self._graphed
         if (g is None or g[0][0] is not z or g[0][1] is not cell_t or g[0][2] != pos_t.size(0) or g[1].stale()
                 or g[1].model is not self.model or g[1].variable_cell != var):
@@ -288,7 +295,7 @@ class NNCalculator(_Base):
         # copied to the host anyway (an overflow repeats the step on an exact list)
         cap = self._edge_capacity if (dev is not None and cell is not None) else None
         data = build_graph(cell=cell, elements=elems, pos=atoms.positions, rc=self.model.rc, device=dev,
-                           reference_compat=self.reference_compat, capacity=cap)
+                           reference_compat=self.reference_compat, capacity=cap, structure=self._structure)
         # stress whenever ASE asks for it (or the ensemble is NPT) on a periodic cell; an open system has none
         want = pbc and cell is not None and (self.ensemble.lower() == 'npt' or 'stress' in tuple(properties))
         sink = None

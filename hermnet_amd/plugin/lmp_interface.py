@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from ..elements import atomic_numbers
-from .ase_interface import build_graph, model_calc
+from .ase_interface import StructureTensors, build_graph, model_calc
 
 # lmp_calc.py:136-138
 SETUP, STEP = 1, 2
@@ -94,6 +94,7 @@ def serve(argv=None, model=None, cslib=None):
     types = coords = box = natoms = None
     pbc = a.periodic == 'True'             # (the reference: eval(args.periodic), lmp_calc.py:227)
     served = 0
+    structure = StructureTensors(a.device if device.type == 'cuda' else None)      # this loop's z / batch / cell tensors
     while True:
         msg_id, nfield, fieldid, fieldtype, fieldlen = cs.recv()
         if msg_id < 0:
@@ -130,7 +131,7 @@ def serve(argv=None, model=None, cslib=None):
         # on the host every step, lmp_calc.py:224)
         dev = a.device if device.type == 'cuda' else None
         data = build_graph(box_to_cell(box) if pbc else None, z, pos, a.radius, device=dev,
-                           reference_compat=a.reference_compat)
+                           reference_compat=a.reference_compat, structure=structure)
         e, f, v = calculator(data, model, a.stats, a.device, pbc, a.units, a.ensemble)
         pack_reply(cs, msg_id, f, e, v)
         served += 1

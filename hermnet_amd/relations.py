@@ -7,18 +7,24 @@ edge list is kept in two orders,
   CSR  (row(target), edge id)                      -> forward segmented sums,
   CSC  (relation(target), row(source), CSR pos)    -> backward segmented sums,
 plus (torch build only) the out-adjacency by source row.  All index arrays are
-int32 device tensors.  One small D2H copy (atoms per relation, number of graphs)
-tells the host where each relation's rows start.
+int32 device tensors.  One small D2H copy per atom set (atoms per relation,
+number of graphs) tells the host where each relation's rows start.
+
+What follows from (atomic_number, batch, z_list) alone is an `AtomSet`: that
+host read, the `RowArrays` of every row layout, the read-out order and the
+small constants the native kernels read.  Its owners keep it alive -- every
+graph built from it, every captured step that replays its addresses --;
+`AtomSet.of` finds the set of tensors passed again (8 most recent).
 
 Every piece is stated once and the four builds (HVNet / HTNet, torch / native)
-are assembled from them: `_classify` (relation of every atom, the host read),
+are assembled from them: `_classify` (relation of every atom),
 `RelationalGraph._layout` (where the relations' rows start), `_source_rows`
 (rows of the atoms), `_order_edges` (CSR + CSC, one key-width rule),
-`_active_relations`, `_graph_order`, `_src_ranges`; the native builds share
-`_atom_counts`, `_native_rows` / `_finish_native_rows` (row arrays, kept per
-atom set) and `_native_edges` (output arrays + `RelationsOut`).  The torch
-builds define the result bit for bit.  Other modules keep values derived from
-the immutable graph through `RelationalGraph.derived`.
+`_active_relations`, the set's `graph_order` / `triadic_src_ranges`; the
+native builds share the set's `new_rows` / `keep_rows` and `_native_edges`
+(output arrays + `RelationsOut`).  The torch builds define the result bit for
+bit.  Other modules keep values derived from the immutable graph through
+`RelationalGraph.derived`.
 """
 import ctypes
 
@@ -27,41 +33,145 @@ import torch
 from . import _lib, switches
 from .ops import _stream
 
-_COUNT_CACHE = []      # most recent first: (z tensor, version, batch tensor, version, z_list, result)
-_CONST_CACHE = {}
+_ATOM_SETS = []      # AtomSet.of: the lookup index, most recent first, at most 8 sets; dropping one frees nothing an owner reads
 
 
-def _cached_i32(values, dev):
-    """Small constant index tensors are uploaded once (a pageable H2D copy per step would also break
-    hipGraph capture of the step)."""
-    key = ("i32", values, str(dev))
-    t = _CONST_CACHE.get(key)
-    if t is None:
-        if len(_CONST_CACHE) > 64:
-            _CONST_CACHE.clear()
-        t = _CONST_CACHE[key] = torch.tensor(list(values), dtype=torch.int32, device=dev)
-    return t
-
-
-def _cached_u8(values, dev):
-    key = ("u8", values, str(dev))
-    t = _CONST_CACHE.get(key)
-    if t is None:
-        t = _CONST_CACHE[key] = torch.tensor(list(values), dtype=torch.uint8, device=dev)
-    return t
-
-
-def _classify(atomic_number, batch, z_list):
+def _classify(atomic_number, z_list):
     """The torch restatement of `hermnet_relation_counts`: (relation of every atom [NA] -- the first matching element, T
-    for "not in elems" (hermnet.py:53 finds none) --, atoms per relation + unknown [T+1] on the device, the same on the
-    host, number of graphs), with the one host sync of a torch build."""
+    for "not in elems" (hermnet.py:53 finds none) --, atoms per relation + unknown [T+1]), both on the atoms' device; the
+    host reads the counts once per atom set (`AtomSet`)."""
     dev, NA, T = atomic_number.device, int(atomic_number.numel()), len(z_list)
     eq = atomic_number.long()[:, None] == torch.tensor(list(z_list), dtype=torch.long, device=dev)[None, :]
     rel = torch.where(eq.any(1), eq.int().argmax(1), torch.full((NA,), T, dtype=torch.long, device=dev))
     counts = torch.zeros(T + 1, dtype=torch.long, device=dev).index_add_(0, rel, torch.ones_like(rel))
-    nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
-    host = torch.cat([counts, nb]).cpu().tolist()
-    return rel, counts, host[:T + 1], int(host[-1])
+    return rel, counts
+
+
+class RowArrays(object):
+    """The row arrays of ONE row layout of an atom set (`AtomSet.rows`), which a native build's kernel fills on the first
+    build and reads (`rows_ready`) on every later one."""
+
+    __slots__ = ("type_rowptr", "node_order", "row_of_node", "z_rows", "row_real", "node_order64", "row_of_node64",
+                 "z_rows64", "batch32")
+
+    def __init__(self, starts, num_atoms, n_rows, dev):
+        e32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        self.type_rowptr = torch.tensor(list(starts), dtype=torch.int32, device=dev)  # here (one upload); build kernels, graph
+        self.node_order = e32(num_atoms)        # the first build's kernel; later builds' kernels
+        self.row_of_node = e32(num_atoms)       # the first build's kernel; later builds' kernels
+        self.z_rows = e32(n_rows)               # the first build's kernel; later builds' kernels
+        self.row_real = torch.empty(n_rows, dtype=torch.float32, device=dev)    # the first build's kernel; graph.row_real
+        self.node_order64 = self.row_of_node64 = self.z_rows64 = None   # `finish`; the graphs' node_order / row_of_node / z_rows
+        self.batch32 = None                     # `finish`; graph.batch32
+
+    def finish(self, batch):
+        """After the kernel: int64 copies for the host code's gathers (embedding, index_select) and `batch32`."""
+        self.z_rows64, self.row_of_node64, self.node_order64 = self.z_rows.long(), self.row_of_node.long(), self.node_order.long()
+        self.batch32 = None if batch is None else batch.to(torch.int32).contiguous()
+
+
+class AtomSet(object):
+    """Everything that follows from (atomic_number, batch, z_list) alone: the atom counts of the one host sync and the
+    device arrays the builds make once and then READ -- a captured step bakes in their addresses.  Nothing in a set is
+    ever cleared or evicted; it lives as long as its owners: every `RelationalGraph` built from it (`graph.atoms`), every
+    object that replays a capture (graph.py: `step.atoms`, handed to each `Data` as `_hn_atoms`), and the lookup index
+    `AtomSet.of` while the set is among its 8 most recent.  Undeclared fields raise."""
+
+    __slots__ = ("atomic_number", "z_version", "batch", "batch_version", "z_list", "device", "zl", "z64", "counts_host",
+                 "num_graphs", "rows", "graph_perm", "graph_lengths", "active", "src_ranges", "triadic_counts")
+
+    def __init__(self, atomic_number, batch, z_list):
+        dev, NA, T = atomic_number.device, int(atomic_number.numel()), len(z_list)
+        # the key (written here, read by `matches`): the caller's tensor OBJECTS, kept alive here -- an address alone could be
+        # reused by a different tensor of the same size -- with their versions (in-place edits), and the model's elements
+        self.atomic_number, self.z_version = atomic_number, atomic_number._version
+        self.batch, self.batch_version = batch, None if batch is None else batch._version
+        self.z_list = tuple(z_list)
+        self.device = dev
+        self.zl = torch.tensor(list(z_list), dtype=torch.int32, device=dev)     # here; the native builds' kernels
+        self.z64 = atomic_number.to(torch.int64, copy=True).contiguous()        # here (the set's own copy); the native builds' kernels
+        if atomic_number.is_cuda and switches.native_relations:
+            counts = torch.empty(T + 1, dtype=torch.int32, device=dev)
+            _lib.check(_lib.load().hermnet_relation_counts(_lib.ptr(self.z64), NA, _lib.ptr(self.zl), T, _lib.ptr(counts),
+                                                           _stream()), "hermnet_relation_counts")
+        else:
+            counts = _classify(self.z64, z_list)[1]
+        nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
+        host = torch.cat([counts.long(), nb]).cpu().tolist()      # the ONE host sync of an atom set
+        self.counts_host = host[:T + 1]         # here; all four builds: atoms per relation + unknown [T+1]
+        self.num_graphs = int(host[-1])         # here; all four builds
+        self.rows = {}                          # `keep_rows`: layout key -> RowArrays; the native builds
+        self.graph_perm = self.graph_lengths = None     # `graph_order`; all four builds (the graphs' read-out order)
+        self.active = {}                        # `active_flags`: pattern -> uint8 [n_rel]; the native builds' kernels
+        self.src_ranges = None                  # `triadic_src_ranges`; both HTNet builds (graph.src_ranges)
+        self.triadic_counts = None              # `_build_triadic_native`: int32 [T] atoms per element; its kernel
+
+    def matches(self, atomic_number, batch, z_list):
+        return (self.atomic_number is atomic_number and self.z_version == atomic_number._version and self.batch is batch
+                and self.batch_version == (None if batch is None else batch._version) and self.z_list == tuple(z_list))
+
+    @staticmethod
+    def of(atomic_number, batch, z_list, given=None):
+        """The set of these atoms: `given` (an owner's, e.g. `data._hn_atoms`; one made for other tensors raises), else the
+        one the index holds for the same tensor objects, unmodified, and the same elements, else a new one (the host sync;
+        atom types and batch assignment do not change along an MD trajectory)."""
+        if given is not None:
+            if not given.matches(atomic_number, batch, z_list):
+                raise ValueError("this AtomSet was made for other atomic_number / batch tensors (or they were modified in "
+                                 "place since) or for other elements")
+            return given
+        for s in _ATOM_SETS:
+            if s.matches(atomic_number, batch, z_list):
+                return s
+        s = AtomSet(atomic_number, batch, z_list)
+        _ATOM_SETS.insert(0, s)
+        del _ATOM_SETS[8:]
+        return s
+
+    def new_rows(self, key, starts, n_rows):
+        """-> (the RowArrays of layout `key`, filled already?); new ones are for the kernel to fill, then `keep_rows`."""
+        rows = self.rows.get(key)
+        if rows is not None:
+            return rows, True
+        return RowArrays(starts, int(self.atomic_number.numel()), n_rows, self.device), False
+
+    def keep_rows(self, g, key, rows):
+        """After the kernel: the layout's arrays are kept (once) and go on the graph."""
+        if key not in self.rows:
+            rows.finish(self.batch)
+            self.rows[key] = rows
+        g.type_rowptr, g.row_real, g.batch32 = rows.type_rowptr, rows.row_real, rows.batch32
+        g.z_rows, g.row_of_node, g.node_order = rows.z_rows64, rows.row_of_node64, rows.node_order64
+
+    def graph_order(self):
+        """Deterministic per-graph read-out: (atoms grouped by graph, stable; segment lengths), or (None, None) for one graph."""
+        if self.batch is None or self.num_graphs <= 1:
+            return None, None
+        if self.graph_perm is None:
+            b64 = self.batch.long()
+            self.graph_lengths = torch.zeros(self.num_graphs, dtype=torch.long, device=self.device).index_add_(
+                0, b64, torch.ones_like(b64))
+            self.graph_perm = torch.argsort(b64, stable=True)
+        return self.graph_perm, self.graph_lengths
+
+    def active_flags(self, flags):
+        """uint8 device flags of a relation pattern (a tuple of bools), uploaded once: a pageable H2D copy per step would
+        also break hipGraph capture of the step."""
+        t = self.active.get(flags)
+        if t is None:
+            t = self.active[flags] = torch.tensor(list(flags), dtype=torch.uint8, device=self.device)
+        return t
+
+    def triadic_src_ranges(self):
+        """HTNet [T P, 4]: relation (c; p, q) gathers sources of elements p and q only (the x_proj chain skips the other
+        rows): rows [p B, p B + N_p) and, for q != p, [q B, q B + N_q); B = the largest element's atom count."""
+        if self.src_ranges is None:
+            T, cnt = len(self.z_list), self.counts_host
+            B = max(cnt[:T]) if T > 0 else 0
+            per_pair = [v for p in range(T) for q in range(p, T)
+                        for v in (p * B, p * B + cnt[p], (q * B if q != p else 0), (q * B + cnt[q] if q != p else 0))]
+            self.src_ranges = torch.tensor(per_pair * T, dtype=torch.int32, device=self.device).view(T * T * (T + 1) // 2, 4)
+        return self.src_ranges
 
 
 def _source_rows(rel, counts, starts, n_rows, z):
@@ -106,66 +216,17 @@ def _order_edges(target_row, source_row, rel_of_target, n_target_rows, n_source_
     return csr_perm, csr_src.to(i32), csr_rowptr.to(i32), csc_pos.to(i32), tgt_sorted[csc_pos].to(i32), csc_rowptr.to(i32)
 
 
-def _active_relations(rel_active, dev, edges_per_relation=None):
+def _active_relations(rel_active, atoms, edges_per_relation=None):
     """Which relations run.  Torch form (`edges_per_relation` given): bool [n_rel], by default "it receives an edge".
     Native form: uint8 device flags or None (the kernel decides by the edges).  `rel_active` (list, or device tensor:
     slab plans, no host read): the caller knows better, e.g. a shard whose relation has edges on other ranks only."""
-    native = edges_per_relation is None
+    native, dev = edges_per_relation is None, atoms.device
     if rel_active is None:
         return None if native else edges_per_relation > 0
     if torch.is_tensor(rel_active):
         return rel_active.to(device=dev, dtype=torch.uint8 if native else torch.bool).contiguous()
     flags = tuple(bool(a) for a in rel_active)
-    return _cached_u8(flags, dev) if native else torch.tensor(flags, dtype=torch.bool, device=dev)
-
-
-def _graph_order(batch, num_graphs, cache=None):
-    """Deterministic per-graph read-out: (atoms grouped by graph, stable; segment lengths), or (None, None) for one graph.
-    It depends on the batch vector only: the native builds keep it in `cache`, their row arrays of the atom set."""
-    if batch is None or num_graphs <= 1:
-        return None, None
-    if cache is None or "graph_perm" not in cache:
-        b64 = batch.long()
-        order = (torch.argsort(b64, stable=True),
-                 torch.zeros(num_graphs, dtype=torch.long, device=batch.device).index_add_(0, b64, torch.ones_like(b64)))
-        if cache is None:
-            return order
-        cache["graph_perm"], cache["graph_lengths"] = order
-    return cache["graph_perm"], cache["graph_lengths"]
-
-
-def _src_ranges(T, B, cnt_host, dev):
-    """HTNet [T P, 4]: relation (c; p, q) gathers sources of elements p and q only (the x_proj chain skips the other
-    rows): rows [p B, p B + N_p) and, for q != p, [q B, q B + N_q)."""
-    per_pair = tuple(v for p in range(T) for q in range(p, T)
-                     for v in (p * B, p * B + cnt_host[p], (q * B if q != p else 0), (q * B + cnt_host[q] if q != p else 0)))
-    return _cached_i32(per_pair * T, dev).view(T * T * (T + 1) // 2, 4)
-
-
-def _native_rows(rows_cache, key, NA, n_rows, dev):
-    """Row arrays of a native build, which depend on the atoms only: those of `rows_cache[key]`, or new ones for the
-    kernel to fill.  -> (rows, ready)"""
-    rows = rows_cache.get(key)
-    if rows is not None:
-        return rows, True
-    e32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
-    return dict(node_order=e32(NA), row_of_node=e32(NA), z_rows=e32(n_rows),
-                row_real=torch.empty(n_rows, dtype=torch.float32, device=dev)), False
-
-
-def _finish_native_rows(g, rows, rows_cache, key, batch):
-    """After the kernel: int64 copies for the host code's gathers (embedding, index_select) and `batch32`, made once per
-    atom set and kept in `rows_cache[key]`."""
-    if key not in rows_cache:
-        rows["z_rows64"] = rows["z_rows"].long()
-        rows["row_of_node64"] = rows["row_of_node"].long()
-        rows["node_order64"] = rows["node_order"].long()
-        rows["batch32"] = None if batch is None else batch.to(torch.int32).contiguous()
-        if len(rows_cache) > 4:
-            rows_cache.clear()
-        rows_cache[key] = rows
-    g.z_rows, g.row_of_node, g.node_order = rows["z_rows64"], rows["row_of_node64"], rows["node_order64"]
-    g.batch32 = rows["batch32"]
+    return atoms.active_flags(flags) if native else torch.tensor(flags, dtype=torch.bool, device=dev)
 
 
 def _native_edges(g, rows, n_target_rows, n_csc_rows, E, edge_shift, dev):
@@ -179,7 +240,7 @@ def _native_edges(g, rows, n_target_rows, n_csc_rows, E, edge_shift, dev):
     g.out_rowptr = g.out_edges = None
     shift = None if edge_shift is None else edge_shift.float().contiguous()
     g.shift = None if shift is None else torch.empty(E, 3, dtype=torch.float32, device=dev)
-    out = _lib.RelationsOut(P(rows["node_order"]), P(rows["row_of_node"]), P(rows["z_rows"]), P(rows["row_real"]),
+    out = _lib.RelationsOut(P(rows.node_order), P(rows.row_of_node), P(rows.z_rows), P(rows.row_real),
                             P(g.row_active), P(g.csr_rowptr), P(g.csr_src), P(g.csr_perm), P(g.src_id), P(g.tgt_id),
                             P(g.shift), P(g.csc_rowptr), P(g.csc_tgt), P(g.csc_pos), None, None)
     return out, shift
@@ -203,11 +264,12 @@ class RelationalGraph(object):
                  "csc_pos", "out_rowptr", "out_edges", "src_id", "tgt_id", "shift", "row_active", "row_real",
                  "batch32", "num_graphs", "graph_perm", "graph_lengths", "device", "_cstruct", "_rel_bounds",
                  "edge_table", "fwd_taps", "num_src", "res_row", "triadic_pairs", "src_real", "src_ranges",
-                 "_all_known") + _DERIVED
+                 "_all_known", "atoms") + _DERIVED
 
     def __init__(self):
         self._cstruct = None
         self._rel_bounds = None
+        self.atoms = None          # the AtomSet this graph was built from (every build): owns what the native build kernels read
         self._all_known = False    # every atom has an element of the model (host knowledge from the atom counts): Ek == E
         self.edge_table = None     # [E+1,32] per-edge radial records of the current step, CSC order (set by HVNet.forward)
         self.fwd_taps = None       # [E,16] per-edge tap records of the current step, CSR order (set with edge_table), or None
@@ -250,17 +312,19 @@ class RelationalGraph(object):
         return self.csr_rowptr[self.type_rowptr.long()]
 
     @staticmethod
-    def build(atomic_number, edge_index, z_list, edge_shift=None, batch=None, rel_active=None, uniform=None):
+    def build(atomic_number, edge_index, z_list, edge_shift=None, batch=None, rel_active=None, uniform=None, atoms=None):
         """atomic_number [N] int, edge_index [2,E] int (row 0 = source, row 1 = target,
         `hermnet.py:135`), z_list: atomic numbers of the model's elements in module order.
         `uniform`: None = automatic (padding overhead <= 15 %), True/False = forced.
 
         GPU tensors take the device-side build (`csrc/relation_kernels.hip`); host tensors (tests,
         planning) take the PyTorch restatement below, which defines the expected result bit for bit.
-        (`switches.native_relations = False`: the restatement for GPU tensors too -- tests.)"""
+        (`switches.native_relations = False`: the restatement for GPU tensors too -- tests.)
+        `atoms`: the caller's `AtomSet` of these tensors (an owner of a capture); default `AtomSet.of`."""
+        atoms = AtomSet.of(atomic_number, batch, z_list, atoms)
         if atomic_number.is_cuda and switches.native_relations:
-            return RelationalGraph._build_native(atomic_number, edge_index, z_list, edge_shift, batch, rel_active, uniform)
-        return RelationalGraph._build_torch(atomic_number, edge_index, z_list, edge_shift, batch, rel_active, uniform)
+            return RelationalGraph._build_native(atoms, edge_index, edge_shift, rel_active, uniform)
+        return RelationalGraph._build_torch(atomic_number, edge_index, z_list, edge_shift, batch, rel_active, uniform, atoms)
 
     @staticmethod
     def _layout(cnt_host, T, uniform):
@@ -278,64 +342,39 @@ class RelationalGraph(object):
         return uniform, block, starts, starts[T] + cnt_host[T]
 
     @staticmethod
-    def _atom_counts(atomic_number, batch, z_list):
-        """(z_list on the device, atoms per relation + unknown [T+1] on the host, number of graphs, atomic numbers as
-        int64, {row-layout cache}) of these atoms: a host sync, skipped while the same tensors are passed again (atom
-        types and batch assignment do not change along an MD trajectory).  Keyed on the identity of the caller's
-        tensor OBJECTS, which the cache keeps alive: an address alone could be reused by a different tensor of the
-        same size."""
-        dev, NA, T = atomic_number.device, int(atomic_number.numel()), len(z_list)
-        i32, P = torch.int32, _lib.ptr
-        for ent in _COUNT_CACHE:
-            if (ent[0] is atomic_number and ent[1] == atomic_number._version and ent[2] is batch
-                    and ent[3] == (None if batch is None else batch._version) and ent[4] == tuple(z_list)):
-                return ent[5]
-        z = atomic_number.long().contiguous()
-        zl = torch.tensor(list(z_list), dtype=i32, device=dev)
-        counts = torch.empty(T + 1, dtype=i32, device=dev)
-        _lib.check(_lib.load().hermnet_relation_counts(P(z), NA, P(zl), T, P(counts), _stream()), "hermnet_relation_counts")
-        nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
-        host = torch.cat([counts.long(), nb]).cpu().tolist()
-        hit = (zl, host[:T + 1], int(host[-1]), z, {})
-        _COUNT_CACHE.insert(0, (atomic_number, atomic_number._version, batch,
-                                None if batch is None else batch._version, tuple(z_list), hit))
-        del _COUNT_CACHE[8:]
-        return hit
-
-    @staticmethod
-    def _build_native(atomic_number, edge_index, z_list, edge_shift, batch, rel_active, uniform):
+    def _build_native(atoms, edge_index, edge_shift, rel_active, uniform):
         lib, P = _lib.load(), _lib.ptr
         g = RelationalGraph()
-        dev = atomic_number.device
-        NA, E, T = int(atomic_number.numel()), int(edge_index.size(1)), len(z_list)
-        g.num_atoms, g.E, g.T, g.device = NA, E, T, dev
+        dev, cnt_host = atoms.device, atoms.counts_host
+        NA, E, T = int(atoms.z64.numel()), int(edge_index.size(1)), len(atoms.z_list)
+        g.num_atoms, g.E, g.T, g.device, g.atoms, g.num_graphs = NA, E, T, dev, atoms, atoms.num_graphs
         ei = edge_index.long().contiguous()
-        zl, cnt_host, g.num_graphs, z, rows_cache = RelationalGraph._atom_counts(atomic_number, batch, z_list)
         g.uniform, g.block, starts, N = RelationalGraph._layout(cnt_host, T, uniform)
         g.N, g.type_rowptr_host = N, starts[:T + 1]
         g._all_known = int(cnt_host[T]) == 0
-        g.type_rowptr = _cached_i32(tuple(starts[:T + 1]), dev)
         key = (g.uniform, N)
-        rows, rows_ready = _native_rows(rows_cache, key, NA, N, dev)
-        g.row_real = rows["row_real"]
+        rows, rows_ready = atoms.new_rows(key, starts[:T + 1], N)
         out, shift = _native_edges(g, rows, N, T * N, E, edge_shift, dev)
-        act = _active_relations(rel_active, dev)
+        act = _active_relations(rel_active, atoms)
         wbytes = lib.hermnet_build_relations_workspace(NA, N, E, T)
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.hermnet_build_relations(P(z), P(ei), P(shift), NA, E, P(zl), T, P(g.type_rowptr), N, P(act), ctypes.byref(out),
-                                               1 if rows_ready else 0, P(work), wbytes, _stream()), "hermnet_build_relations")
-        _finish_native_rows(g, rows, rows_cache, key, batch)
-        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs, rows)
+        _lib.check(lib.hermnet_build_relations(P(atoms.z64), P(ei), P(shift), NA, E, P(atoms.zl), T, P(rows.type_rowptr), N, P(act),
+                                               ctypes.byref(out), 1 if rows_ready else 0, P(work), wbytes, _stream()),
+                   "hermnet_build_relations")
+        atoms.keep_rows(g, key, rows)
+        g.graph_perm, g.graph_lengths = atoms.graph_order()
         return g
 
     @staticmethod
-    def _build_torch(atomic_number, edge_index, z_list, edge_shift=None, batch=None, rel_active=None, uniform=None):
+    def _build_torch(atomic_number, edge_index, z_list, edge_shift=None, batch=None, rel_active=None, uniform=None, atoms=None):
         g = RelationalGraph()
+        g.atoms = atoms = AtomSet.of(atomic_number, batch, z_list, atoms)
         dev, i32 = atomic_number.device, torch.int32
         NA, E, T = int(atomic_number.numel()), int(edge_index.size(1)), len(z_list)
         g.num_atoms, g.E, g.T, g.device = NA, E, T, dev
         z = atomic_number.long()
-        rel, counts, cnt_host, g.num_graphs = _classify(z, batch, z_list)
+        rel, counts = _classify(z, z_list)
+        cnt_host, g.num_graphs = atoms.counts_host, atoms.num_graphs
         g.uniform, g.block, starts, N = RelationalGraph._layout(cnt_host, T, uniform)
         g.N, g.type_rowptr_host = N, starts[:T + 1]             # rows (>= atoms when padded)
         g.type_rowptr = torch.tensor(starts[:T + 1], dtype=i32, device=dev)
@@ -353,22 +392,21 @@ class RelationalGraph(object):
         # hermnet.py:56-57: a relation without edges is skipped -> its rows stay zero; rows of
         # unknown-type atoms (hermnet.py:51) and padding rows are zero as well.
         tn = torch.arange(T + 1, device=dev) * N
-        act = _active_relations(rel_active, dev, g.csc_rowptr[tn[1:]] - g.csc_rowptr[tn[:-1]])
+        act = _active_relations(rel_active, atoms, g.csc_rowptr[tn[1:]] - g.csc_rowptr[tn[:-1]])
         act = torch.cat([act, torch.zeros(1, dtype=torch.bool, device=dev)])
         g.row_active = torch.zeros(N, dtype=torch.float32, device=dev)
         g.row_active[g.row_of_node] = act[rel].float()          # a row runs iff it holds an atom whose relation runs
         g.batch32 = None if batch is None else batch.to(i32).contiguous()
-        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs)
+        g.graph_perm, g.graph_lengths = atoms.graph_order()
         return g
 
     @staticmethod
-    def _build_triadic_native(atomic_number, edge_index, z_list, edge_shift, batch, rel_active=None):
+    def _build_triadic_native(atoms, edge_index, edge_shift, rel_active=None):
         """`build_triadic` through `hermnet_build_triadic` (csrc/relation_kernels.hip); None when an atom is of an
         element outside `z_list` (the torch build handles those)."""
         lib, P = _lib.load(), _lib.ptr
-        dev = atomic_number.device
-        NA, E0, T = int(atomic_number.numel()), int(edge_index.size(1)), len(z_list)
-        zl, cnt_host, num_graphs, z, rows_cache = RelationalGraph._atom_counts(atomic_number, batch, z_list)
+        dev, cnt_host = atoms.device, atoms.counts_host
+        NA, E0, T = int(atoms.z64.numel()), int(edge_index.size(1)), len(atoms.z_list)
         if cnt_host[T] != 0:
             return None
         Pn = T * (T + 1) // 2
@@ -377,31 +415,31 @@ class RelationalGraph(object):
         if TR * Ns + Nt + 8 >= 2 ** 31 or E >= 2 ** 31:
             return None
         g = RelationalGraph()
-        g.num_atoms, g.T, g.device, g.uniform, g.block, g.num_graphs = NA, TR, dev, True, B, num_graphs
-        g.N, g.num_src, g.triadic_pairs, g.E = Nt, Ns, Pn, E
+        g.num_atoms, g.T, g.device, g.uniform, g.block, g.num_graphs = NA, TR, dev, True, B, atoms.num_graphs
+        g.N, g.num_src, g.triadic_pairs, g.E, g.atoms = Nt, Ns, Pn, E, atoms
         g.type_rowptr_host = [r * B for r in range(TR + 1)]
-        g.type_rowptr = _cached_i32(tuple(g.type_rowptr_host), dev)
         key = ("triadic", B)
-        rows, rows_ready = _native_rows(rows_cache, key, NA, Ns, dev)
-        g.src_real = g.row_real = rows["row_real"]                 # the energy read-out masks SOURCE rows
+        rows, rows_ready = atoms.new_rows(key, g.type_rowptr_host, Ns)
         ei = edge_index.long().contiguous()
         out, shift = _native_edges(g, rows, Nt, TR * Ns, E, edge_shift, dev)
         tgt_real = torch.empty(Nt, dtype=torch.float32, device=dev)
         g.res_row = torch.empty(Nt, dtype=torch.int32, device=dev)
-        counts_d = _cached_i32(tuple(cnt_host[:T]), dev)
+        if atoms.triadic_counts is None:
+            atoms.triadic_counts = torch.tensor(cnt_host[:T], dtype=torch.int32, device=dev)
         wbytes = lib.hermnet_build_triadic_workspace(NA, E0, T, B)
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-        act = _active_relations(rel_active, dev)
-        _lib.check(lib.hermnet_build_triadic(P(z), P(ei), P(shift), NA, E0, P(zl), T, B, P(counts_d), P(act), ctypes.byref(out),
-                                             P(tgt_real), P(g.res_row), 1 if rows_ready else 0, P(work), wbytes, _stream()),
-                   "hermnet_build_triadic")
-        _finish_native_rows(g, rows, rows_cache, key, batch)
-        g.src_ranges = _src_ranges(T, B, cnt_host, dev)
-        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs, rows)
+        act = _active_relations(rel_active, atoms)
+        _lib.check(lib.hermnet_build_triadic(P(atoms.z64), P(ei), P(shift), NA, E0, P(atoms.zl), T, B, P(atoms.triadic_counts),
+                                             P(act), ctypes.byref(out), P(tgt_real), P(g.res_row), 1 if rows_ready else 0,
+                                             P(work), wbytes, _stream()), "hermnet_build_triadic")
+        atoms.keep_rows(g, key, rows)
+        g.src_real = g.row_real                                    # the energy read-out masks SOURCE rows
+        g.src_ranges = atoms.triadic_src_ranges()
+        g.graph_perm, g.graph_lengths = atoms.graph_order()
         return g
 
     @staticmethod
-    def build_triadic(atomic_number, edge_index, z_list, edge_shift=None, batch=None, rel_active=None):
+    def build_triadic(atomic_number, edge_index, z_list, edge_shift=None, batch=None, rel_active=None, atoms=None):
         """HTNet's relation-ordered graph (DESIGN.md "HTNet"): relation rho = (centre element c, unordered pair
         {p, q} of neighbour elements), T * T(T+1)/2 of them.
 
@@ -417,19 +455,22 @@ class RelationalGraph(object):
         GPU tensors whose atoms are all of listed elements take the device-side build (`hermnet_build_triadic`, the
         HVNet build's counting sort over the expanded list); everything else the torch-op build below, which defines
         the result (tests/test_htnet.py compares the two)."""
+        atoms = AtomSet.of(atomic_number, batch, z_list, atoms)
         if (atomic_number.is_cuda and switches.native_relations and len(z_list) > 0
                 and atomic_number.numel() > 0):
-            g = RelationalGraph._build_triadic_native(atomic_number, edge_index, z_list, edge_shift, batch, rel_active)
+            g = RelationalGraph._build_triadic_native(atoms, edge_index, edge_shift, rel_active)
             if g is not None:
                 return g
         g = RelationalGraph()
+        g.atoms = atoms
         dev, i32 = atomic_number.device, torch.int32
         NA, T = int(atomic_number.numel()), len(z_list)
         pairs = [(p, q) for p in range(T) for q in range(p, T)]
         P = len(pairs)
         TR = T * P
         z = atomic_number.long()
-        rel, counts, cnt_host, g.num_graphs = _classify(z, batch, z_list)
+        rel, counts = _classify(z, z_list)
+        cnt_host, g.num_graphs = atoms.counts_host, atoms.num_graphs
         _, B, starts, Ns = RelationalGraph._layout(cnt_host, T, True)
         Nt = TR * B
         g.num_atoms, g.T, g.device, g.uniform, g.block = NA, TR, dev, True, B
@@ -463,12 +504,12 @@ class RelationalGraph(object):
         r_el = r_rel // P
         row_real = (r_loc < counts[:T][r_el.clamp(max=max(T - 1, 0))]).float() if Nt > 0 else torch.zeros(0, device=dev)
         tn = torch.arange(TR + 1, device=dev) * B
-        act = _active_relations(rel_active, dev, g.csr_rowptr[tn[1:]] - g.csr_rowptr[tn[:-1]])
+        act = _active_relations(rel_active, atoms, g.csr_rowptr[tn[1:]] - g.csr_rowptr[tn[:-1]])
         g.row_active = act[r_rel].float() * row_real if Nt > 0 else row_real
         g.res_row = (r_el * B + r_loc).to(i32)
-        g.src_ranges = _src_ranges(T, B, cnt_host, dev)
+        g.src_ranges = atoms.triadic_src_ranges()
         g.batch32 = None if batch is None else batch.to(i32).contiguous()
-        g.graph_perm, g.graph_lengths = _graph_order(batch, g.num_graphs)
+        g.graph_perm, g.graph_lengths = atoms.graph_order()
         return g
 
     def as_struct(self):

@@ -2419,6 +2419,128 @@ def test_a_captured_step_keeps_its_read_out_copies_whatever_another_model_does()
     assert model_a._head is head and head.builds == 1
 
 
+def test_a_captured_step_keeps_its_atom_set_whatever_else_is_built():
+    """A capture bakes in the addresses of the atom set's arrays (relations.AtomSet: row arrays, element list), which the
+    relation build kernels READ on every replay.  The step owns its set: twelve other structures evaluated in the process
+    push it out of the lookup index and free nothing -- memory allocated behind that cannot be the set's, and the replays
+    repeat bit for bit.  (Zeros behind it, not garbage: zero is a valid value of every row array.)"""
+    from hermnet_amd import relations
+    from hermnet_amd.graph import GraphedMDStep, GraphedStep
+    dev = _dev()
+    g = Golden("c1_si64")
+    model = g.model().to(dev)
+    for p in model.parameters():
+        p.requires_grad_(False)
+    d = g.data().to(dev)
+    steps = [GraphedMDStep(model, d.atomic_number, d.cell.reshape(3, 3), d.pos.detach()), GraphedStep(model, g.data().to(dev))]
+    first = [tuple(t.clone() for t in s()) for s in steps]
+    for e0, f0 in first:
+        assert rel_err(e0.cpu(), g.energy) < 1e-5 and rel_err(f0.cpu(), g.forces) < 1e-5
+    zl = [atomic_numbers[el] for el in g.elems]
+    sets = [relations.AtomSet.of(steps[0].z, steps[0].batch, zl),
+            relations.AtomSet.of(steps[1].data.atomic_number, steps[1].data.batch, zl)]
+    assert sets[0] is not sets[1]
+
+    def arrays(s):
+        assert len(s.rows) == 1 and s.graph_perm is None
+        (rows,) = s.rows.values()
+        return [s.zl, s.z64] + [getattr(rows, n) for n in relations.RowArrays.__slots__]
+
+    held = [arrays(s) for s in sets]
+    ptrs = [[t.data_ptr() for t in a] for a in held]
+    assert all(t is not None for a in held for t in a)
+
+    # twelve other structures of 2 to 8 atoms (H, C, O counts: every composition another row layout), open boundaries, fresh
+    # tensors each, evaluated eagerly by another model
+    gen = torch.Generator().manual_seed(11)
+    model_b = hn.HVNet(["H", "C", "O"], rc=5.0, num_layers=2, hidden_channels=128, num_rbf=128).eval()
+    model_b.load_state_dict(synth.synth_state_dict(model_b.state_dict(), 31))
+    model_b = model_b.to(dev)
+    for p in model_b.parameters():
+        p.requires_grad_(False)
+    counts = [(1, 1, 0), (2, 1, 0), (2, 0, 1), (2, 1, 1), (0, 2, 2), (3, 1, 1), (4, 2, 0), (2, 2, 2), (4, 2, 1), (1, 3, 3),
+              (4, 2, 2), (5, 0, 3)]
+    assert len(set(counts)) == 12 and all(2 <= sum(c) <= 8 for c in counts)
+    corners = 1.6 * torch.tensor([[i, j, k] for i in (0, 1) for j in (0, 1) for k in (0, 1)], dtype=torch.float32)
+    for c in counts:
+        z = torch.tensor([1] * c[0] + [6] * c[1] + [8] * c[2], device=dev)
+        n = int(z.numel())
+        pos = (corners[:n] + 0.2 * torch.rand(n, 3, generator=gen)).to(dev).requires_grad_(True)
+        ei = hn.neighbor_search(pos.detach(), 5.0)
+        assert ei.size(1) == n * (n - 1)
+        e = model_b(hn.Data(pos=pos, atomic_number=z, edge_index=ei))
+        (f,) = torch.autograd.grad(e.sum(), pos)
+        assert bool(torch.isfinite(e).all()) and bool(torch.isfinite(f).all())
+    assert len(relations._ATOM_SETS) == 8 and not any(s is kept for s in relations._ATOM_SETS for kept in sets)
+
+    # ownership first: the steps hold the sets of their captures, and every array is where it was
+    for step, kept, a, p in zip(steps, sets, held, ptrs):
+        assert step.atoms is kept
+        assert all(x is y for x, y in zip(arrays(kept), a))
+        assert [t.data_ptr() for t in arrays(kept)] == p
+    # only then: what a freed block would be handed to
+    fill = [torch.zeros_like(t) for _ in range(32) for t in held[0]]
+    assert len(fill) == 32 * len(held[0]) and {torch.int32, torch.float32} <= {t.dtype for t in fill}
+    for step, (e0, f0) in zip(steps, first):
+        e, f = step()
+        assert torch.equal(e, e0) and torch.equal(f, f0)
+
+
+def test_a_repeat_build_around_the_same_tensors_does_not_synchronise():
+    """An MD-style step makes a fresh `Data` around the same `atomic_number` / `batch` tensors every step: the relation build
+    finds their atom set again (`AtomSet.of`) and nothing in the evaluation reads the host."""
+    dev = _dev()
+    g = Golden("c1_si64")
+    model = g.model().to(dev)
+    for p in model.parameters():
+        p.requires_grad_(False)
+    data = g.data().to(dev)
+
+    def fresh():
+        return hn.Data(pos=data.pos.clone().requires_grad_(True), atomic_number=data.atomic_number, batch=data.batch,
+                       cell=data.cell, edge_index=data.edge_index, edge_shift=data.edge_shift)
+
+    e0 = model(fresh()).detach().clone()
+    model(fresh())                                  # (the parameter guard arms on the second forward)
+    torch.cuda.synchronize()
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        d = fresh()
+        e = model(d)
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
+    (f,) = torch.autograd.grad(e.sum(), d.pos)
+    assert torch.equal(e.detach(), e0) and rel_err(-f.cpu(), g.forces) < 1e-5
+
+
+def test_two_calculators_on_one_device_do_not_evict_each_other():
+    """Every `NNCalculator` owns its structure tensors (`StructureTensors`): a second calculator with other species, called in
+    turns with the first, replaces none of them -- the first one's capture stays the ONE capture and repeats bit for bit."""
+    from hermnet_amd.plugin import NNCalculator
+    _dev()
+    g = Golden("c1_si64")
+    d = g.data()
+    z, cell, pos = d.atomic_number.numpy(), d.cell[0].numpy().astype("float64"), d.pos.numpy().astype("float64")
+    first = NNCalculator(g.model(), None, trn_mean=0.0, device_="cuda:0", graph_replay=True)
+    pos2, cell2, z2 = synth.fcc_alloy_atoms(reps=(2, 2, 2))
+    model2 = hn.HVNet(["Al", "Ni", "Cu"], rc=5.0, num_layers=2, hidden_channels=128, num_rbf=64).eval()
+    model2.load_state_dict(synth.synth_state_dict(model2.state_dict(), 8))
+    second = NNCalculator(model2, None, trn_mean=0.0, device_="cuda:0")
+    seen = []
+    for _ in range(4):
+        first.calculate(_FakeAtoms(pos, z, cell), ["energy", "forces"])
+        seen.append((first.results["energy"], first.results["forces"].copy()))
+        second.calculate(_FakeAtoms(pos2.astype("float64"), z2, cell2.astype("float64")), ["energy", "forces"])
+        seen.append((second.results["energy"], second.results["forces"].copy()))
+        assert first.graph_captures == 1
+    assert abs(seen[0][0] - float(g.energy[0])) <= 1e-5 * abs(float(g.energy[0]))
+    assert first._structure is not second._structure and first._structure.z is not second._structure.z
+    for k in range(2, 8):
+        assert seen[k][0] == seen[k % 2][0] and np.array_equal(seen[k][1], seen[k % 2][1]), k
+    assert np.isfinite(seen[1][0]) and seen[1][1].shape == (len(z2), 3)
+
+
 def test_nve_energy_conservation_on_a_fixed_neighbour_list():
     """End to end, no oracle: velocity-Verlet on the device with the model's forces (tools/md_nve.py).  With the
     neighbour list held fixed the total energy must stay put while kinetic and potential energy trade ~10 eV -- and the

@@ -178,7 +178,7 @@ def test_edge_orders_do_not_depend_on_the_sort_key_width(case):
     from hermnet_amd import relations
     z, ei, zl = _small_relation_case(case)
     g = RelationalGraph._build_torch(z, ei, zl, uniform=True)
-    rel = relations._classify(z, None, zl)[0]
+    rel = relations._classify(z, zl)[0]
     args = (g.row_of_node[ei[1]], g.row_of_node[ei[0]], rel[ei[1]], g.N, g.N, len(zl))
     narrow, wide = relations._order_edges(*args, wide=False), relations._order_edges(*args, wide=True)
     mine = (g.csr_perm, g.csr_src, g.csr_rowptr, g.csc_pos, g.csc_tgt, g.csc_rowptr)
