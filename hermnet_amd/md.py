@@ -24,28 +24,19 @@ Out of scope: barostats / NPT (the cell is constant during `run`), constraints o
 atom), atom shards, HTNet, more than one time step per replay."""
 import math
 import types
-import warnings
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._resident import HALT_CAPACITY, HALT_NONFINITE, PARKED as _PARKED, after_halt, cell_args, f64 as _f64, fetch_packed  # noqa: F401
 
 AMU_A2_FS2_TO_EV = 103.642696562         # 1 amu A^2 / fs^2 in eV (tools/md_nve.py)
 KB = 8.617333262e-5                       # eV / K
 ASE_TIME_FS = math.sqrt(AMU_A2_FS2_TO_EV)   # ASE's time unit in fs: v [A/fs] = v_ase / 10.18051
 
 HN_MD_LANGEVIN, HN_MD_WRAP = 1, 2        # include/hermnet_hip.h
-HALT_NONFINITE = 256                      # halt code: an energy that is not finite
-HALT_CAPACITY = 4                         # ... list flag bit 2: more pairs than columns
-_PARKED = 1 << 20                         # host-side halt code while a capture is made: its replays must not integrate
-
-
-def _f64(a, dev, shape=None):
-    t = torch.as_tensor(np.asarray(a.detach().cpu()) if torch.is_tensor(a) else np.asarray(a), dtype=torch.float64)
-    if shape is not None:
-        t = t.reshape(shape)
-    return t.contiguous().to(dev)
+# HALT_NONFINITE, HALT_CAPACITY (halt codes) and _PARKED (the halt code while a capture is made): _resident.py
 
 
 class DeviceMD(object):
@@ -133,15 +124,8 @@ class DeviceMD(object):
     # ---- the two hooks of the capture ---------------------------------------------------------------------------------------
     def _cell_args(self, step):
         """(flags, cell pointer, inverse-cell pointer): the cell is the tensor the search reads; its inverse is made here."""
-        cell = step.cell
-        if cell is None or not self.wrap:
-            return self.flags & ~HN_MD_WRAP, None, None
-        if cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != 9 * self.num_graphs:
-            raise RuntimeError("DeviceMD: the step's cell must be a contiguous float32 [B,3,3]")
-        if self._inv_of is not cell:
-            inv = np.linalg.inv(cell.detach().double().cpu().numpy().reshape(-1, 3, 3))
-            self.inv_cell, self._inv_of = torch.from_numpy(np.ascontiguousarray(inv)).to(self.device), cell
-        return self.flags | HN_MD_WRAP, cell.data_ptr(), self.inv_cell.data_ptr()
+        wrap, cell, inv = cell_args(self, step)
+        return (self.flags | HN_MD_WRAP) if wrap else (self.flags & ~HN_MD_WRAP), cell, inv
 
     def _advance(self, step):
         P = _lib.ptr
@@ -206,12 +190,7 @@ class DeviceMD(object):
         idx = (torch.arange(rows, device=self.device) + self._logged) % self.log_steps
         packed = torch.cat([self.state.double(), self.x.reshape(-1), self.image.double().reshape(-1), self.v.reshape(-1),
                             self.f_prev.double().reshape(-1), self.log.index_select(0, idx).reshape(-1)])
-        if self._host is None or self._host.numel() < packed.numel():
-            self._host = torch.empty(4 + 12 * n + self.log_steps * B * 3, dtype=torch.float64).pin_memory()
-        host = self._host[:packed.numel()]
-        host.copy_(packed, non_blocking=True)
-        torch.cuda.current_stream(self.device).synchronize()
-        h = host.numpy()
+        h = fetch_packed(self, packed, 4 + 12 * n + self.log_steps * B * 3)
         step, code, halt_step = int(h[0]), int(h[1]), int(h[2])
         done = max(0, min(rows, step - self._logged))
         o = 4
@@ -222,18 +201,7 @@ class DeviceMD(object):
         s.forces = h[o + 9 * n:o + 12 * n].astype(np.float32).reshape(n, 3)
         s.log = h[o + 12 * n:].reshape(rows, B, 3)[:done].copy()
         self._logged, self._pending = step, 0
-        if code & 2:
-            from .neighbor import _stash_overflowed
-            _stash_overflowed(self.device)
-        if code & HALT_NONFINITE:
-            # the captured step holds the stale-cache guard's check-and-poison kernel: after a write through `.data` every
-            # replay answers NaN.  The halt kept the NaN forces out of the integrator; the caches are dropped here.
-            if not self.model.__dict__.get("_warned_nan_repair"):
-                self.model.__dict__["_warned_nan_repair"] = True
-                warnings.warn("hermnet_amd: DeviceMD halted at step %d on an energy that is not finite (weights written "
-                              "through `.data` behind the cached copies?); the caches were dropped -- call resume() to "
-                              "recapture and continue from the last completed step." % halt_step, RuntimeWarning, stacklevel=2)
-            self.model.invalidate_caches()
+        after_halt(self, code, halt_step)
         return s
 
     def resume(self):

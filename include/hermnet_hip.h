@@ -19,7 +19,7 @@
  * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -899,6 +899,62 @@ int hermnet_host_md_finish(int num_atoms, int num_graphs, const int* graph_ptr_h
                            float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
                            double* ke_atom_host, double* log_host, long log_steps, long* state_host);
 int hermnet_host_md_noise(unsigned long seed, unsigned long step, int n, unsigned* out_words_host, double* out_gauss_host);
+
+/* Device-resident FIRE relaxation of a batch of structures (added within ABI v13: new entry points only;
+ * hermnet_amd/relax.py: DeviceRelax; csrc/relax_kernels.hip, relax_step.h).  As for hermnet_md_*: hermnet_relax_advance is
+ * enqueued in FRONT of the captured neighbour search and hermnet_relax_finish BEHIND the force backward, so that one replay of
+ * the step's hipGraph is one force evaluation of the optimiser.  The optimiser is ASE's FIRE (dt, dtmax, maxstep, fmax are
+ * arguments; Nmin 5, finc 1.1, fdec 0.5, astart 0.1, fa 0.99), applied to every graph on its own: a graph whose largest
+ * force is below its threshold freezes while the others keep going.  Units: eV, Angstrom; FIRE's time is a parameter.
+ *
+ * Caller-owned state (all allocated outside the capture):
+ *   x, x0 [N,3] float64 coordinates and their start-of-step backup;   v [N,3] float64 FIRE's velocities;   image, image0
+ *   [N,3] int32 as for hermnet_md_*;   f_prev [N,3] float32 the forces of a graph's last evaluation while it was moving;
+ *   fixed [N] uint8 or NULL: an atom that is held counts as f = 0 everywhere, keeps v = 0 and is never moved;   batch,
+ *   graph_ptr, cell, inv_cell, pos32 as for hermnet_md_*;   fmax_graph [B] float64 or NULL (then `fmax` for all);
+ *   gf [B,5] float64 = (dt, a, scale, fnorm, energy) and gi [B,4] int64 = (nsteps, fresh, converged, conv_step) per graph --
+ *   scale is what the next advance multiplies v with; a run starts from scale 0, fresh 1, converged 0, v 0 --, gf_new / gi_new
+ *   their scratch copies;   log [log_steps,B,4] float64 ring of (E_pot, max |f_i|, dt, edges found) per evaluation and graph;
+ *   state [4] int64 = (step, halt code, step at which it halted, done).
+ *
+ * hermnet_relax_advance   halt code != 0: nothing.  For every atom of a graph that has not converged: x0, image0 = x, image,
+ *   and unless it is held x += scale_g v, then with HN_MD_WRAP (the only flag) the wrap of hermnet_md_advance.  All atoms:
+ *   pos32 = float(x).  scale starts at 0: the first replay evaluates the start coordinates.
+ * hermnet_relax_finish    halt code != 0 or done: nothing.  The step's code is hermnet_md_finish's.  Code != 0: the step is
+ *   void -- x, image = x0, image0 and pos32 = float(x) for the graphs that moved, v and the per-graph state untouched, state
+ *   = (step, code, step, 0), no log row.  Code 0, per graph that has not converged, with f = float64(forces) (0 where held):
+ *   P = sum f.v, ff = sum f.f, vv = sum v.v, fm2 = max |f_i|^2;  fm2 < fmax^2 (an empty graph too): converged, conv_step =
+ *   step, scale = 0, v = 0.  Otherwise: fresh: dt = `dt`, a = astart, nsteps = 0, fresh = 0;  else P > 0: v = (1 - a) v +
+ *   (ff > 0 ? (a / sqrt(ff)) sqrt(vv) : 0) f, then if nsteps > Nmin dt = min(dt finc, dtmax), a = a fa, then nsteps += 1;
+ *   else v = 0, a = astart, dt = dt fdec, nsteps = 0.  Then v += dt f;  s = sum v.v;  nd = dt sqrt(s);  scale = nd > maxstep ?
+ *   dt (maxstep / nd) : dt;  f_prev = forces;  fnorm = sqrt(fm2), energy = energy[g].  Every graph: log[step % log_steps][g]
+ *   = (energy, fnorm, dt, total[0]).  step += 1; done = 1 once every graph has converged.
+ *   Two launches: one 256-lane workgroup per graph, then one workgroup that alone writes state, gf and gi (from gf_new /
+ *   gi_new), so every workgroup of a step reads the state the step began with.
+ * A per-graph sum takes ONE order: lane l of 256 adds the terms of atoms lo+l, lo+l+256, ... ascending from 0.0, the
+ *   partials are folded part[l] += part[l+m], m = 128 ... 1; an atom's term is (t0 + t1) + t2; no atomics.  `/` and sqrt
+ *   appear in the per-graph scalars alone.  The hermnet_host_relax_* twins run the same text, in this order, on HOST
+ *   pointers (no stream): bit for bit what the device computes for the same forces.
+ * HN_ERR_BAD_ARG: a NULL state / gf / gi (or any array with num_atoms > 0), num_graphs < 1, log_steps < 1, a flag other
+ *   than HN_MD_WRAP, dt, dtmax, maxstep or fmax not positive.  num_atoms = 0 is served. */
+int hermnet_relax_advance(int num_atoms, int num_graphs, int flags, double* x, double* x0, const double* v, int* image, int* image0,
+                          const unsigned char* fixed, const long* batch, const float* cell, const double* inv_cell, float* pos32,
+                          const long* state, const double* gf, const long* gi, void* stream);
+int hermnet_relax_finish(int num_atoms, int num_graphs, const int* graph_ptr, const float* forces, const float* energy,
+                         const long* total, long capacity, double dt, double dtmax, double maxstep, double fmax,
+                         const double* fmax_graph, double* x, double* v, const double* x0, int* image, const int* image0,
+                         float* f_prev, const unsigned char* fixed, float* pos32, double* gf, long* gi, double* gf_new,
+                         long* gi_new, double* log, long log_steps, long* state, void* stream);
+int hermnet_host_relax_advance(int num_atoms, int num_graphs, int flags, double* x_host, double* x0_host, const double* v_host,
+                               int* image_host, int* image0_host, const unsigned char* fixed_host, const long* batch_host,
+                               const float* cell_host, const double* inv_cell_host, float* pos32_host, const long* state_host,
+                               const double* gf_host, const long* gi_host);
+int hermnet_host_relax_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const float* forces_host,
+                              const float* energy_host, const long* total_host, long capacity, double dt, double dtmax,
+                              double maxstep, double fmax, const double* fmax_graph_host, double* x_host, double* v_host,
+                              const double* x0_host, int* image_host, const int* image0_host, float* f_prev_host,
+                              const unsigned char* fixed_host, float* pos32_host, double* gf_host, long* gi_host,
+                              double* gf_new_host, long* gi_new_host, double* log_host, long log_steps, long* state_host);
 
 #ifdef __cplusplus
 }
