@@ -6,14 +6,10 @@
 // The arithmetic is md_step.h's, shared with the host twins at the end of this file; contraction is off for the whole
 // file, so device, host twin and a numpy float64 transcription agree bit for bit.
 //
-// state [4] int64 = (step, halt code, step at which it halted, mode).  Halted (code != 0): every kernel here returns at
-// once.  Mode 1 ("prime"): advance only rewrites the float32 input, finish only copies the forces to f_prev and clears the
-// mode -- the same capture serves the first force evaluation and the one behind a recapture.
-// Who writes `state`: the LAST kernel of hermnet_md_finish alone (one workgroup), so every other workgroup of a step reads
-// the words the step began with, whatever the order they are scheduled in.
+// The step protocol (state words, halt code, void step, single writer) is resident_step.h's.  What MD adds: velocities are
+// backed up and restored with the coordinates, and the fourth state word is a mode -- 1 ("prime"): advance only rewrites the
+// float32 input, finish only copies the forces to f_prev and clears the mode (the first evaluation, and a recapture's).
 #include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/hermnet_hip.h"
 #include "md_step.h"
 
 #pragma clang fp contract(off)
@@ -67,8 +63,7 @@ __host__ __device__ inline void md_advance_one(const MdAdvanceArgs& a, int i, lo
       a.v0[3 * (size_t)i + k] = v[k];
       a.image0[3 * (size_t)i + k] = image[k];
     }
-    long g = a.batch ? a.batch[i] : 0;
-    g = g < 0 ? 0 : (g >= a.num_graphs ? a.num_graphs - 1 : g);      // (a broken `batch` must not read out of bounds)
+    const long g = hn_graph_of(a.batch, i, a.num_graphs);
     const int langevin = a.flags & HN_MD_LANGEVIN;
     double xi[3] = {0.0, 0.0, 0.0};
     if (langevin) {
@@ -79,10 +74,7 @@ __host__ __device__ inline void md_advance_one(const MdAdvanceArgs& a, int i, lo
     md_advance_atom(x, v, f, a.kick[i], a.dt, langevin, langevin ? a.c1[g] : 0.0, langevin ? a.sigma[i] : 0.0, xi);
     if (a.flags & HN_MD_WRAP) {
       double cell[9], inv[9];
-      for (int k = 0; k < 9; ++k) {
-        cell[k] = (double)a.cell[9 * g + k];
-        inv[k] = a.inv_cell[9 * g + k];
-      }
+      hn_load_cell(a.cell, a.inv_cell, g, cell, inv);
       md_wrap_atom(x, image, cell, inv);
     }
     for (int k = 0; k < 3; ++k) {
@@ -101,13 +93,8 @@ __host__ __device__ inline void md_finish_one(const MdFinishArgs& a, int i, long
     return;
   }
   if (code != 0) {        // the step is void: back to the state it began with
-    for (int k = 0; k < 3; ++k) {
-      const double x = a.x0[3 * (size_t)i + k];
-      a.x[3 * (size_t)i + k] = x;
-      a.v[3 * (size_t)i + k] = a.v0[3 * (size_t)i + k];
-      a.image[3 * (size_t)i + k] = a.image0[3 * (size_t)i + k];
-      a.pos32[3 * (size_t)i + k] = (float)x;
-    }
+    hn_restore_atom(i, a.x, a.x0, a.image, a.image0, a.pos32);
+    for (int k = 0; k < 3; ++k) a.v[3 * (size_t)i + k] = a.v0[3 * (size_t)i + k];
     return;
   }
   double v[3];
@@ -123,72 +110,54 @@ __host__ __device__ inline void md_finish_one(const MdFinishArgs& a, int i, long
   }
 }
 
-__host__ __device__ inline int md_not_finite(float e) { return !(e - e == 0.0f); }
+__host__ __device__ inline void md_log_row(const MdFinishArgs& a, long step, int g, double e_kin) {
+  double* row = hn_log_row(a.log, step, a.log_steps, a.num_graphs, g, 3);
+  row[0] = (double)a.energy[g];
+  row[1] = e_kin;
+  row[2] = (double)a.total[0];
+}
+
+// The single writer of `state`: a void step records its halt, a completed one is counted; a prime clears its mode.
+__host__ __device__ inline void md_commit(long* state, long step, long code, long mode) {
+  if (!hn_commit_halt(state, step, code) && mode == 0) state[HN_STATE_STEP] = step + 1;
+  if (mode != 0) state[HN_STATE_MODE] = 0;
+}
 
 __global__ __launch_bounds__(256) void md_advance_kernel(MdAdvanceArgs a) {
-  const long step = a.state[0], code = a.state[1], mode = a.state[3];
+  const long step = a.state[HN_STATE_STEP], code = a.state[HN_STATE_CODE], mode = a.state[HN_STATE_MODE];
   if (code != 0) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < a.n) md_advance_one(a, i, step, mode);
 }
 
-// Every workgroup works the step's halt code out for itself (B energies from the cache: nothing to what a launch costs).
-__device__ inline long md_block_code(const MdFinishArgs& a) {
-  int bad = 0;
-  for (int g = threadIdx.x; g < a.num_graphs; g += blockDim.x) bad |= md_not_finite(a.energy[g]);
-  bad = __syncthreads_or(bad);
-  return md_step_code(a.total[0], a.total[1], a.capacity, bad);
-}
-
 __global__ __launch_bounds__(256) void md_finish_atoms_kernel(MdFinishArgs a) {
-  const long halted = a.state[1], mode = a.state[3];
+  const long halted = a.state[HN_STATE_CODE], mode = a.state[HN_STATE_MODE];
   if (halted != 0) return;
-  const long code = md_block_code(a);
+  const long code = hn_step_code(a.energy, a.num_graphs, a.total, a.capacity);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < a.n) md_finish_one(a, i, code, mode);
 }
 
-// One workgroup per graph: its atoms' kinetic energies in a fixed order (lane-strided partial sums, then a fixed tree),
-// and the graph's log row.
+// One workgroup per graph: its atoms' kinetic energies in the canonical order, and the graph's log row.
 __global__ __launch_bounds__(256) void md_log_kernel(MdFinishArgs a) {
-  __shared__ double part[256];
-  const long step = a.state[0], halted = a.state[1], mode = a.state[3];
+  __shared__ double part[1][256];
+  const long step = a.state[HN_STATE_STEP], halted = a.state[HN_STATE_CODE], mode = a.state[HN_STATE_MODE];
   if (halted != 0 || mode != 0) return;
-  if (md_block_code(a) != 0) return;
-  const int g = blockIdx.x, lo = max(a.graph_ptr[g], 0), hi = min(a.graph_ptr[g + 1], a.n);
-  double s = 0.0;
-  for (int i = lo + (int)threadIdx.x; i < hi; i += 256) s = s + a.ke_atom[i];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int m = 128; m >= 1; m >>= 1) {
-    if ((int)threadIdx.x < m) part[threadIdx.x] = part[threadIdx.x] + part[threadIdx.x + m];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    double* row = a.log + ((size_t)(step % a.log_steps) * a.num_graphs + g) * 3;
-    row[0] = (double)a.energy[g];
-    row[1] = part[0];
-    row[2] = (double)a.total[0];
-  }
+  if (hn_step_code(a.energy, a.num_graphs, a.total, a.capacity) != 0) return;
+  const int g = blockIdx.x, lo = hn_graph_lo(a.graph_ptr, g), hi = hn_graph_hi(a.graph_ptr, g, a.n);
+  hn_canonical_sums<1, -1>(lo, hi, part, [&](int i, double* s) { s[0] = s[0] + a.ke_atom[i]; });
+  if (threadIdx.x == 0) md_log_row(a, step, g, part[0][0]);
 }
 
 __global__ __launch_bounds__(64) void md_commit_kernel(MdFinishArgs a) {
-  const long step = a.state[0], halted = a.state[1], mode = a.state[3];
+  const long step = a.state[HN_STATE_STEP], halted = a.state[HN_STATE_CODE], mode = a.state[HN_STATE_MODE];
   if (halted != 0) return;
-  const long code = md_block_code(a);
-  if (threadIdx.x != 0) return;
-  if (code != 0) {
-    a.state[1] = code;
-    a.state[2] = step;
-  } else if (mode == 0) {
-    a.state[0] = step + 1;
-  }
-  if (mode != 0) a.state[3] = 0;
+  const long code = hn_step_code(a.energy, a.num_graphs, a.total, a.capacity);
+  if (threadIdx.x == 0) md_commit(a.state, step, code, mode);
 }
 
-__global__ __launch_bounds__(256) void md_noise_kernel(uint64_t seed, uint64_t step, int n, uint32_t* words, double* gauss) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
+// Atom i's eight words and three Gaussians of (seed, step) into the caller's arrays (either may be null).
+__host__ __device__ inline void md_noise_one(uint64_t seed, uint64_t step, int i, uint32_t* words, double* gauss) {
   uint32_t w[8];
   double xi[3];
   md_noise_words(seed, step, (uint32_t)i, w);
@@ -197,6 +166,11 @@ __global__ __launch_bounds__(256) void md_noise_kernel(uint64_t seed, uint64_t s
     for (int k = 0; k < 8; ++k) words[8 * (size_t)i + k] = w[k];
   if (gauss)
     for (int k = 0; k < 3; ++k) gauss[3 * (size_t)i + k] = xi[k];
+}
+
+__global__ __launch_bounds__(256) void md_noise_kernel(uint64_t seed, uint64_t step, int n, uint32_t* words, double* gauss) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) md_noise_one(seed, step, i, words, gauss);
 }
 
 bool md_advance_args_ok(const MdAdvanceArgs& a) {
@@ -258,16 +232,7 @@ extern "C" int hermnet_md_noise(unsigned long seed, unsigned long step, int n, u
 extern "C" int hermnet_host_md_noise(unsigned long seed, unsigned long step, int n, unsigned* out_words_host,
                                      double* out_gauss_host) {
   if (n < 0 || (!out_words_host && !out_gauss_host)) return HN_ERR_BAD_ARG;
-  for (int i = 0; i < n; ++i) {
-    uint32_t w[8];
-    double xi[3];
-    md_noise_words((uint64_t)seed, (uint64_t)step, (uint32_t)i, w);
-    md_gaussians(w, xi);
-    if (out_words_host)
-      for (int k = 0; k < 8; ++k) out_words_host[8 * (size_t)i + k] = w[k];
-    if (out_gauss_host)
-      for (int k = 0; k < 3; ++k) out_gauss_host[3 * (size_t)i + k] = xi[k];
-  }
+  for (int i = 0; i < n; ++i) md_noise_one((uint64_t)seed, (uint64_t)step, i, out_words_host, out_gauss_host);
   return HN_OK;
 }
 
@@ -279,8 +244,8 @@ extern "C" int hermnet_host_md_advance(int num_atoms, int num_graphs, int flags,
   const MdAdvanceArgs a = {num_atoms, num_graphs, flags, x_host, v_host, x0_host, v0_host, image_host, image0_host, f_prev_host, kick_host,
                            c1_host, sigma_host, batch_host, cell_host, inv_cell_host, pos32_host, state_host, dt, (uint64_t)seed};
   if (!md_advance_args_ok(a)) return HN_ERR_BAD_ARG;
-  if (num_atoms == 0 || state_host[1] != 0) return HN_OK;
-  for (int i = 0; i < num_atoms; ++i) md_advance_one(a, i, state_host[0], state_host[3]);
+  if (num_atoms == 0 || state_host[HN_STATE_CODE] != 0) return HN_OK;
+  for (int i = 0; i < num_atoms; ++i) md_advance_one(a, i, state_host[HN_STATE_STEP], state_host[HN_STATE_MODE]);
   return HN_OK;
 }
 
@@ -294,28 +259,17 @@ extern "C" int hermnet_host_md_finish(int num_atoms, int num_graphs, const int* 
                           forces_host, energy_host, total_host, capacity, kick_host, half_mass_host, graph_ptr_host, pos32_host,
                           ke_atom_host, log_host, log_steps, state_host};
   if (!md_finish_args_ok(a)) return HN_ERR_BAD_ARG;
-  const long step = state_host[0], mode = state_host[3];
-  if (state_host[1] != 0) return HN_OK;
-  int bad = 0;
-  for (int g = 0; g < num_graphs; ++g) bad |= md_not_finite(energy_host[g]);
-  const long code = md_step_code(total_host[0], total_host[1], capacity, bad);
+  const long step = state_host[HN_STATE_STEP], mode = state_host[HN_STATE_MODE];
+  if (state_host[HN_STATE_CODE] != 0) return HN_OK;
+  const long code = hn_step_code(energy_host, num_graphs, total_host, capacity);
   for (int i = 0; i < num_atoms; ++i) md_finish_one(a, i, code, mode);
-  if (code == 0 && mode == 0) {
+  if (code == 0 && mode == 0)
     for (int g = 0; g < num_graphs; ++g) {
-      double s = 0.0;
-      const int lo = graph_ptr_host[g] < 0 ? 0 : graph_ptr_host[g], hi = graph_ptr_host[g + 1] > num_atoms ? num_atoms : graph_ptr_host[g + 1];
+      const int lo = hn_graph_lo(graph_ptr_host, g), hi = hn_graph_hi(graph_ptr_host, g, num_atoms);
+      double s = 0.0;      // sequential, NOT the canonical order the device takes: frozen with ABI v13
       for (int i = lo; i < hi; ++i) s = s + ke_atom_host[i];
-      double* row = log_host + ((size_t)(step % log_steps) * num_graphs + g) * 3;
-      row[0] = (double)energy_host[g];
-      row[1] = s;
-      row[2] = (double)total_host[0];
+      md_log_row(a, step, g, s);
     }
-    state_host[0] = step + 1;
-  }
-  if (code != 0) {
-    state_host[1] = code;
-    state_host[2] = step;
-  }
-  if (mode != 0) state_host[3] = 0;
+  md_commit(state_host, step, code, mode);
   return HN_OK;
 }

@@ -6,14 +6,7 @@
 #ifndef HERMNET_MD_STEP_H
 #define HERMNET_MD_STEP_H
 
-#include <math.h>
-#include <stdint.h>
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define HN_HD __host__ __device__
-#else
-#define HN_HD
-#endif
+#include "resident_step.h"
 
 // ---- Philox4x32-10 (Salmon et al., SC'11; the Random123 known answers are checked in tests/test_md_host.py) --------------
 HN_HD inline void md_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
@@ -52,21 +45,7 @@ HN_HD inline void md_gaussians(const uint32_t w[8], double xi[3]) {
   xi[2] = rb * cos(tb);
 }
 
-// ---- the step -------------------------------------------------------------------------------------------------------------
-// Triclinic wrap: s = x cell^-1 (rows of `cell` are the lattice vectors), x -= floor(s) cell, image += floor(s).  A
-// coordinate that is not finite, or 2^30 cells away, is left alone (the cast below would be undefined).
-HN_HD inline void md_wrap_atom(double x[3], int image[3], const double cell[9], const double inv[9]) {
-#pragma clang fp contract(off)
-  double n[3];
-  for (int k = 0; k < 3; ++k) {
-    const double s = (x[0] * inv[k] + x[1] * inv[3 + k]) + x[2] * inv[6 + k];
-    const double fl = floor(s);
-    n[k] = (fl >= -1073741824.0 && fl <= 1073741824.0) ? fl : 0.0;
-  }
-  for (int j = 0; j < 3; ++j) x[j] = x[j] - ((n[0] * cell[j] + n[1] * cell[3 + j]) + n[2] * cell[6 + j]);
-  for (int k = 0; k < 3; ++k) image[k] += (int)n[k];
-}
-
+// ---- the step (its wrap and its halt code are the protocol's: resident_step.h) ---------------------------------------------
 // The first half of a step, up to the coordinates the forces are evaluated at.  NVE (velocity Verlet): v += kick f,
 // x += dt v.  Langevin (BAOAB): v += kick f, x += dt/2 v, v = c1 v + sigma xi, x += dt/2 v.  f: the last accepted forces.
 HN_HD inline void md_advance_atom(double x[3], double v[3], const float f[3], double kick, double dt, int langevin, double c1,
@@ -88,15 +67,6 @@ HN_HD inline double md_finish_atom(double v[3], const float f[3], double kick, d
 #pragma clang fp contract(off)
   for (int k = 0; k < 3; ++k) v[k] = v[k] + kick * (double)f[k];
   return half_mass * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
-}
-
-// Halt code of a step from what the force evaluation left behind: the list's flags (+ bit 2 where only the count says
-// so) in the low bits, HN_MD_HALT_NONFINITE for an energy that is not finite (the stale-weight guard answers with NaN).
-HN_HD inline long long md_step_code(long long found, long long flags, long long capacity, int nonfinite) {
-  long long code = flags & 255;
-  if (found > capacity) code |= 4;
-  if (nonfinite) code |= 256;
-  return code;
 }
 
 #endif  // HERMNET_MD_STEP_H

@@ -4,16 +4,13 @@
 // its own: a structure that has converged freezes while the others keep going.
 //
 // The arithmetic is relax_step.h's, shared with the host twins at the end of this file; contraction is off for the whole
-// file, and the per-graph sums take relax_step.h's canonical order, so device, host twin and a numpy float64 transcription
-// agree bit for bit.  No float atomics.
+// file, and the per-graph sums take resident_step.h's canonical order, so device, host twin and a numpy float64
+// transcription agree bit for bit.  No float atomics.
 //
-// state [4] int64 = (step, halt code, step at which it halted, done).  Halted (code != 0) or done: nothing changes.
-// Who writes the words the kernels branch on (`state`, gf, gi): the LAST kernel of hermnet_relax_finish alone (one
-// workgroup), from the scratch copy gf_new / gi_new the per-graph kernel filled -- so every workgroup of a step reads the
-// state the step began with, whatever the order they are scheduled in.
+// The step protocol (state words, halt code, void step, single writer) is resident_step.h's.  What the relaxation adds: the
+// fourth state word is `done` (every graph has converged), a void step leaves the velocities and a converged graph alone, and
+// the single writer also owns gf / gi: it copies them from the scratch gf_new / gi_new the per-graph kernel filled.
 #include <hip/hip_runtime.h>
-#include <stdint.h>
-#include "../../include/hermnet_hip.h"
 #include "relax_step.h"
 
 #pragma clang fp contract(off)
@@ -60,8 +57,7 @@ struct RelaxFinishArgs {
 };
 
 __host__ __device__ inline void relax_advance_one(const RelaxAdvanceArgs& a, int i) {
-  long g = a.batch ? a.batch[i] : 0;
-  g = g < 0 ? 0 : (g >= a.num_graphs ? a.num_graphs - 1 : g);      // (a broken `batch` must not read out of bounds)
+  const long g = hn_graph_of(a.batch, i, a.num_graphs);
   double x[3];
   for (int k = 0; k < 3; ++k) x[k] = a.x[3 * (size_t)i + k];
   if (!a.gi[4 * (size_t)g + 2]) {                                   // a converged graph is never touched again
@@ -75,11 +71,7 @@ __host__ __device__ inline void relax_advance_one(const RelaxAdvanceArgs& a, int
       double v[3], cell[9], inv[9];
       for (int k = 0; k < 3; ++k) v[k] = a.v[3 * (size_t)i + k];
       const int wrap = a.flags & HN_MD_WRAP;
-      if (wrap)
-        for (int k = 0; k < 9; ++k) {
-          cell[k] = (double)a.cell[9 * g + k];
-          inv[k] = a.inv_cell[9 * g + k];
-        }
+      if (wrap) hn_load_cell(a.cell, a.inv_cell, g, cell, inv);
       relax_advance_atom(x, image, v, a.gf[5 * (size_t)g + 2], wrap ? cell : nullptr, inv);
       for (int k = 0; k < 3; ++k) {
         a.x[3 * (size_t)i + k] = x[k];
@@ -88,16 +80,6 @@ __host__ __device__ inline void relax_advance_one(const RelaxAdvanceArgs& a, int
     }
   }
   for (int k = 0; k < 3; ++k) a.pos32[3 * (size_t)i + k] = (float)x[k];
-}
-
-// A void step: the atom returns to where the step began.
-__host__ __device__ inline void relax_restore_one(const RelaxFinishArgs& a, int i) {
-  for (int k = 0; k < 3; ++k) {
-    const double x = a.x0[3 * (size_t)i + k];
-    a.x[3 * (size_t)i + k] = x;
-    a.image[3 * (size_t)i + k] = a.image0[3 * (size_t)i + k];
-    a.pos32[3 * (size_t)i + k] = (float)x;
-  }
 }
 
 // An atom's terms of the four sums, added to the lane's partials.
@@ -126,27 +108,24 @@ __host__ __device__ inline double relax_velocity_one(const RelaxFinishArgs& a, i
 }
 
 __host__ __device__ inline void relax_log_row(const RelaxFinishArgs& a, long step, int g, const RelaxGraph& G) {
-  double* row = a.log + ((size_t)(step % a.log_steps) * a.num_graphs + g) * 4;
+  double* row = hn_log_row(a.log, step, a.log_steps, a.num_graphs, g, 4);
   row[0] = G.energy;
   row[1] = G.fnorm;
   row[2] = G.dt;
   row[3] = (double)a.total[0];
 }
 
-__host__ __device__ inline int relax_not_finite(float e) { return !(e - e == 0.0f); }
-
-__global__ __launch_bounds__(256) void relax_advance_kernel(RelaxAdvanceArgs a) {
-  if (a.state[1] != 0) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < a.n) relax_advance_one(a, i);
+// The single writer's last words: a void step records its halt, a completed one is counted and may be the last.
+__host__ __device__ inline void relax_commit(long* state, long step, long code, int all) {
+  if (hn_commit_halt(state, step, code)) return;
+  state[HN_STATE_STEP] = step + 1;
+  if (all) state[HN_STATE_DONE] = 1;
 }
 
-// Every workgroup works the step's halt code out for itself (B energies from the cache).
-__device__ inline long relax_block_code(const RelaxFinishArgs& a) {
-  int bad = 0;
-  for (int g = threadIdx.x; g < a.num_graphs; g += blockDim.x) bad |= relax_not_finite(a.energy[g]);
-  bad = __syncthreads_or(bad);
-  return md_step_code(a.total[0], a.total[1], a.capacity, bad);
+__global__ __launch_bounds__(256) void relax_advance_kernel(RelaxAdvanceArgs a) {
+  if (a.state[HN_STATE_CODE] != 0) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < a.n) relax_advance_one(a, i);
 }
 
 // One workgroup per graph: the four sums in the canonical order, the graph's decision, its atoms' new velocities, the
@@ -154,14 +133,14 @@ __device__ inline long relax_block_code(const RelaxFinishArgs& a) {
 __global__ __launch_bounds__(256) void relax_graph_kernel(RelaxFinishArgs a) {
   __shared__ double part[4][256];
   __shared__ RelaxCoef coef;
-  const long step = a.state[0];
-  if (a.state[1] != 0 || a.state[3] != 0) return;
-  const long code = relax_block_code(a);
-  const int g = blockIdx.x, t = threadIdx.x, lo = max(a.graph_ptr[g], 0), hi = min(a.graph_ptr[g + 1], a.n);
+  const long step = a.state[HN_STATE_STEP];
+  if (a.state[HN_STATE_CODE] != 0 || a.state[HN_STATE_DONE] != 0) return;
+  const long code = hn_step_code(a.energy, a.num_graphs, a.total, a.capacity);
+  const int g = blockIdx.x, t = threadIdx.x, lo = hn_graph_lo(a.graph_ptr, g), hi = hn_graph_hi(a.graph_ptr, g, a.n);
   RelaxGraph G = relax_graph_load(a.gf, a.gi, g);
   if (code != 0) {
     if (!G.converged)
-      for (int i = lo + t; i < hi; i += 256) relax_restore_one(a, i);
+      for (int i = lo + t; i < hi; i += 256) hn_restore_atom(i, a.x, a.x0, a.image, a.image0, a.pos32);
     return;
   }
   if (G.converged) {
@@ -171,17 +150,7 @@ __global__ __launch_bounds__(256) void relax_graph_kernel(RelaxFinishArgs a) {
     }
     return;
   }
-  double s[4] = {0.0, 0.0, 0.0, 0.0};
-  for (int i = lo + t; i < hi; i += 256) relax_sums_one(a, i, s);
-  for (int k = 0; k < 4; ++k) part[k][t] = s[k];
-  __syncthreads();
-  for (int m = 128; m >= 1; m >>= 1) {
-    if (t < m) {
-      for (int k = 0; k < 3; ++k) part[k][t] = part[k][t] + part[k][t + m];
-      part[3][t] = part[3][t + m] > part[3][t] ? part[3][t + m] : part[3][t];
-    }
-    __syncthreads();
-  }
+  hn_canonical_sums<4, 3>(lo, hi, part, [&](int i, double* s) { relax_sums_one(a, i, s); });
   if (t == 0) {
     G.energy = (double)a.energy[g];
     coef = relax_graph_update(part[0][0], part[1][0], part[2][0], part[3][0], a.fmax_graph ? a.fmax_graph[g] : a.fmax, a.dt,
@@ -189,14 +158,7 @@ __global__ __launch_bounds__(256) void relax_graph_kernel(RelaxFinishArgs a) {
   }
   __syncthreads();
   const RelaxCoef c = coef;
-  double w = 0.0;
-  for (int i = lo + t; i < hi; i += 256) w = w + relax_velocity_one(a, i, c);
-  part[0][t] = w;
-  __syncthreads();
-  for (int m = 128; m >= 1; m >>= 1) {
-    if (t < m) part[0][t] = part[0][t] + part[0][t + m];
-    __syncthreads();
-  }
+  hn_canonical_sums<1, -1>(lo, hi, part, [&](int i, double* s) { s[0] = s[0] + relax_velocity_one(a, i, c); });
   if (t == 0) {
     if (!G.converged) G.scale = relax_graph_scale(part[0][0], G.dt, a.maxstep);
     relax_graph_store(G, a.gf_new, a.gi_new, g);
@@ -206,9 +168,9 @@ __global__ __launch_bounds__(256) void relax_graph_kernel(RelaxFinishArgs a) {
 
 // One workgroup: the scratch copy becomes the state, the step is counted, `done` is set once every graph has converged.
 __global__ __launch_bounds__(256) void relax_commit_kernel(RelaxFinishArgs a) {
-  const long step = a.state[0];
-  if (a.state[1] != 0 || a.state[3] != 0) return;
-  const long code = relax_block_code(a);
+  const long step = a.state[HN_STATE_STEP];
+  if (a.state[HN_STATE_CODE] != 0 || a.state[HN_STATE_DONE] != 0) return;
+  const long code = hn_step_code(a.energy, a.num_graphs, a.total, a.capacity);
   int all = 1;
   if (code == 0)
     for (int g = threadIdx.x; g < a.num_graphs; g += blockDim.x) {
@@ -217,14 +179,7 @@ __global__ __launch_bounds__(256) void relax_commit_kernel(RelaxFinishArgs a) {
       all &= a.gi_new[4 * (size_t)g + 2] != 0;
     }
   all = __syncthreads_and(all);
-  if (threadIdx.x != 0) return;
-  if (code != 0) {
-    a.state[1] = code;
-    a.state[2] = step;
-  } else {
-    a.state[0] = step + 1;
-    if (all) a.state[3] = 1;
-  }
+  if (threadIdx.x == 0) relax_commit(a.state, step, code, all);
 }
 
 bool relax_advance_args_ok(const RelaxAdvanceArgs& a) {
@@ -242,22 +197,6 @@ bool relax_finish_args_ok(const RelaxFinishArgs& a) {
   if (!a.state || !a.gf || !a.gi || !a.gf_new || !a.gi_new || !a.energy || !a.total || !a.graph_ptr || !a.log) return false;
   if (a.n == 0) return true;
   return a.x && a.v && a.x0 && a.image && a.image0 && a.f_prev && a.forces && a.pos32;
-}
-
-// The canonical order on the host: lane partials, then the fold.  term(i, s) adds atom i's terms to s[0..count).
-template <class Term>
-void relax_host_sums(int lo, int hi, int count, int max_at, double out[4], Term term) {
-  static thread_local double part[4][256];
-  for (int l = 0; l < 256; ++l) {
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int i = lo + l; i < hi; i += 256) term(i, s);
-    for (int k = 0; k < count; ++k) part[k][l] = s[k];
-  }
-  for (int m = 128; m >= 1; m >>= 1)
-    for (int l = 0; l < m; ++l)
-      for (int k = 0; k < count; ++k)
-        part[k][l] = k == max_at ? (part[k][l + m] > part[k][l] ? part[k][l + m] : part[k][l]) : part[k][l] + part[k][l + m];
-  for (int k = 0; k < count; ++k) out[k] = part[k][0];
 }
 
 }  // namespace
@@ -297,7 +236,7 @@ extern "C" int hermnet_host_relax_advance(int num_atoms, int num_graphs, int fla
   const RelaxAdvanceArgs a = {num_atoms, num_graphs, flags, x_host, x0_host, v_host, image_host, image0_host, fixed_host, batch_host,
                               cell_host, inv_cell_host, pos32_host, state_host, gf_host, gi_host};
   if (!relax_advance_args_ok(a)) return HN_ERR_BAD_ARG;
-  if (num_atoms == 0 || state_host[1] != 0) return HN_OK;
+  if (num_atoms == 0 || state_host[HN_STATE_CODE] != 0) return HN_OK;
   for (int i = 0; i < num_atoms; ++i) relax_advance_one(a, i);
   return HN_OK;
 }
@@ -313,43 +252,34 @@ extern "C" int hermnet_host_relax_finish(int num_atoms, int num_graphs, const in
                              fmax, fmax_graph_host, x_host, v_host, x0_host, image_host, image0_host, f_prev_host, fixed_host,
                              pos32_host, gf_host, gi_host, gf_new_host, gi_new_host, log_host, log_steps, state_host};
   if (!relax_finish_args_ok(a)) return HN_ERR_BAD_ARG;
-  const long step = state_host[0];
-  if (state_host[1] != 0 || state_host[3] != 0) return HN_OK;
-  int bad = 0;
-  for (int g = 0; g < num_graphs; ++g) bad |= relax_not_finite(energy_host[g]);
-  const long code = md_step_code(total_host[0], total_host[1], capacity, bad);
+  const long step = state_host[HN_STATE_STEP];
+  if (state_host[HN_STATE_CODE] != 0 || state_host[HN_STATE_DONE] != 0) return HN_OK;
+  const long code = hn_step_code(energy_host, num_graphs, total_host, capacity);
   int all = 1;
+  double part[4][256];
   for (int g = 0; g < num_graphs; ++g) {
-    const int lo = graph_ptr_host[g] < 0 ? 0 : graph_ptr_host[g];
-    const int hi = graph_ptr_host[g + 1] > num_atoms ? num_atoms : graph_ptr_host[g + 1];
+    const int lo = hn_graph_lo(graph_ptr_host, g), hi = hn_graph_hi(graph_ptr_host, g, num_atoms);
     RelaxGraph G = relax_graph_load(gf_host, gi_host, g);
     if (code != 0) {
       if (!G.converged)
-        for (int i = lo; i < hi; ++i) relax_restore_one(a, i);
+        for (int i = lo; i < hi; ++i) hn_restore_atom(i, x_host, x0_host, image_host, image0_host, pos32_host);
       continue;
     }
     if (!G.converged) {
-      double s[4];
-      relax_host_sums(lo, hi, 4, 3, s, [&](int i, double* p) { relax_sums_one(a, i, p); });
+      hn_canonical_sums<4, 3>(lo, hi, part, [&](int i, double* s) { relax_sums_one(a, i, s); });
       G.energy = (double)energy_host[g];
-      const RelaxCoef c = relax_graph_update(s[0], s[1], s[2], s[3], fmax_graph_host ? fmax_graph_host[g] : fmax, dt, dtmax, step, G);
-      relax_host_sums(lo, hi, 1, -1, s, [&](int i, double* p) { p[0] = p[0] + relax_velocity_one(a, i, c); });
-      if (!G.converged) G.scale = relax_graph_scale(s[0], G.dt, maxstep);
+      const RelaxCoef c = relax_graph_update(part[0][0], part[1][0], part[2][0], part[3][0], fmax_graph_host ? fmax_graph_host[g] : fmax, dt, dtmax, step, G);
+      hn_canonical_sums<1, -1>(lo, hi, part, [&](int i, double* s) { s[0] = s[0] + relax_velocity_one(a, i, c); });
+      if (!G.converged) G.scale = relax_graph_scale(part[0][0], G.dt, maxstep);
     }
     relax_graph_store(G, gf_new_host, gi_new_host, g);
     relax_log_row(a, step, g, G);
     all &= G.converged != 0;
   }
-  if (code != 0) {
-    state_host[1] = code;
-    state_host[2] = step;
-    return HN_OK;
-  }
-  for (int g = 0; g < num_graphs; ++g) {
+  for (int g = 0; g < num_graphs && code == 0; ++g) {
     for (int k = 0; k < 5; ++k) gf_host[5 * (size_t)g + k] = gf_new_host[5 * (size_t)g + k];
     for (int k = 0; k < 4; ++k) gi_host[4 * (size_t)g + k] = gi_new_host[4 * (size_t)g + k];
   }
-  state_host[0] = step + 1;
-  if (all) state_host[3] = 1;
+  relax_commit(state_host, step, code, all);
   return HN_OK;
 }

@@ -5,13 +5,11 @@
 // appear in the two per-graph scalar functions alone (relax_graph_update, relax_graph_scale), where they are the correctly
 // rounded IEEE operations on the device as on the host (no fast-math).
 //
-// The canonical order of a per-graph sum over the atoms lo..hi-1 (it steers the trajectory, so it is part of the contract):
-// lane l of 256 adds the terms of atoms lo+l, lo+l+256, ... in ascending order starting from 0.0; the 256 partials are then
-// folded part[l] += part[l+m] for m = 128, 64, ..., 1.  An atom's term is (t0 + t1) + t2.  The maximum takes the same tree.
+// The per-graph sums that steer the trajectory take the canonical order of resident_step.h; an atom's term is (t0 + t1) + t2.
 #ifndef HERMNET_RELAX_STEP_H
 #define HERMNET_RELAX_STEP_H
 
-#include "md_step.h"
+#include "resident_step.h"
 
 // ASE's defaults; the time step, its ceiling, the longest step and the force threshold are arguments.
 #define HN_RELAX_NMIN 5

@@ -219,17 +219,12 @@ class GraphedMDStep(object):
         cell): (energy [graphs] float32 array, forces [N,3] float32 array, list complete?, edges found), with `stress` also
         the virial [graphs,3,3] float32 array as a fifth result.  `last_flags` keeps the list's flags."""
         import numpy as np
-        from .neighbor import _stash_overflowed
-        if self._host is None:
-            self._host = torch.empty(self.packed.shape, dtype=torch.float64).pin_memory()
-        self._host.copy_(self.packed, non_blocking=True)
-        torch.cuda.current_stream(self.packed.device).synchronize()
-        h = self._host.numpy()
+        from ._resident import fetch_packed, list_flags_seen
+        h, self._host = fetch_packed(self.packed, self._host)
         ng = self.energy.numel()
         n_edges, flags = int(h[ng]), int(h[ng + 1])
         self.last_flags = flags
-        if flags & 2:
-            _stash_overflowed(self.packed.device)        # (the repeat gets a larger stash slot per atom)
+        list_flags_seen(flags, self.packed.device)       # (a stash overflow: the repeat gets a larger stash slot per atom)
         if self.stress:
             nf = self.forces.numel()
             return (h[:ng].astype(np.float32), h[ng + 2:ng + 2 + nf].astype(np.float32).reshape(-1, 3), flags == 0, n_edges,

@@ -137,12 +137,9 @@ def _evaluate_finite(model, data, device, pbc, want_virial, trn_mean=0.0, atom_p
 
 
 def _warn_repaired(model):
-    if not model.__dict__.get("_warned_nan_repair"):
-        model.__dict__["_warned_nan_repair"] = True
-        import warnings
-        warnings.warn("hermnet_amd: a step came back NaN (weights written through `.data` behind the cached copies?); the "
-                      "caches were rebuilt and the step re-evaluated.  Call model.invalidate_caches() after such writes.",
-                      RuntimeWarning, stacklevel=3)
+    from .._resident import warn_nan_once
+    warn_nan_once(model, "hermnet_amd: a step came back NaN (weights written through `.data` behind the cached copies?); the "
+                  "caches were rebuilt and the step re-evaluated.  Call model.invalidate_caches() after such writes.", 3)
 
 
 def model_calc(model, data, device, pbc, ensemble='NVT', trn_mean=0.0, units='metal'):

@@ -42,7 +42,7 @@ def host_noise(seed, step, n):
     return words, gauss
 
 
-def coefficients(masses, dt, batch, friction=None, temperature=None):
+def coefficients(masses, dt, batch, friction=None, temperature=None, num_graphs=None):
     """(kick, half_mass, c1 [B] or None, sigma [N] or None) exactly as hermnet_amd/md.py makes them."""
     m = np.asarray(masses, dtype=np.float64) * AMU
     kick = 0.5 * dt / m
@@ -50,7 +50,7 @@ def coefficients(masses, dt, batch, friction=None, temperature=None):
     if friction is None:
         return kick, half_mass, None, None
     t = np.asarray(temperature, dtype=np.float64)
-    B = int(batch[-1]) + 1
+    B = int(num_graphs) if num_graphs is not None else int(batch[-1]) + 1
     t = np.broadcast_to(t.reshape(-1) if t.ndim else t, (B,)).astype(np.float64)
     c1 = math.exp(-float(friction) * dt)
     return kick, half_mass, np.full(B, c1), np.sqrt(KB * t[batch] * (1.0 - c1 * c1) / m)
@@ -87,13 +87,13 @@ def finish_np(v, f32, kick, half_mass):
 class NumpyMD(object):
     """The reference trajectory: numpy float64 velocity Verlet / BAOAB with the noise of the library's host form."""
 
-    def __init__(self, x, v, masses, dt, cell=None, batch=None, friction=None, temperature=None, seed=0):
+    def __init__(self, x, v, masses, dt, cell=None, batch=None, friction=None, temperature=None, seed=0, num_graphs=None):
         n = len(x)
         self.x, self.v = np.array(x, dtype=np.float64), np.array(v, dtype=np.float64)
         self.image = np.zeros((n, 3), dtype=np.int32)
         self.batch = np.zeros(n, dtype=np.int64) if batch is None else np.asarray(batch, dtype=np.int64)
         self.dt, self.seed, self.step = float(dt), seed, 0
-        self.kick, self.half_mass, c1, self.sigma = coefficients(masses, dt, self.batch, friction, temperature)
+        self.kick, self.half_mass, c1, self.sigma = coefficients(masses, dt, self.batch, friction, temperature, num_graphs)
         self.c1_atom = None if c1 is None else c1[self.batch]
         self.cell = self.inv = None
         if cell is not None:
@@ -116,7 +116,8 @@ class NumpyMD(object):
 class HostMD(object):
     """The library's host twins on numpy arrays (the state layout of include/hermnet_hip.h)."""
 
-    def __init__(self, x, v, masses, dt, cell=None, batch=None, friction=None, temperature=None, seed=0, log_steps=64):
+    def __init__(self, x, v, masses, dt, cell=None, batch=None, friction=None, temperature=None, seed=0, log_steps=64,
+                 num_graphs=None):
         n = self.n = len(x)
         self.lib = _lib.load()
         self.x, self.v = np.array(x, dtype=np.float64), np.array(v, dtype=np.float64)
@@ -124,10 +125,10 @@ class HostMD(object):
         self.image, self.image0 = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 3), dtype=np.int32)
         self.f_prev = np.zeros((n, 3), dtype=np.float32)
         self.batch = np.zeros(n, dtype=np.int64) if batch is None else np.ascontiguousarray(batch, dtype=np.int64)
-        self.B = int(self.batch[-1]) + 1
+        self.B = int(num_graphs) if num_graphs is not None else int(self.batch[-1]) + 1
         self.graph_ptr = np.searchsorted(self.batch, np.arange(self.B + 1)).astype(np.int32)
         self.dt, self.seed = float(dt), seed
-        self.kick, self.half_mass, self.c1, self.sigma = coefficients(masses, dt, self.batch, friction, temperature)
+        self.kick, self.half_mass, self.c1, self.sigma = coefficients(masses, dt, self.batch, friction, temperature, self.B)
         self.flags = LANGEVIN if friction is not None else 0
         self.cell = self.inv = None
         if cell is not None:

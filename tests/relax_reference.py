@@ -1,8 +1,8 @@
 """Shared by tests/test_relax_host.py and tests/test_relax_device.py: the numpy float64 transcription of the relaxation's
-arithmetic (hermnet_amd/csrc/relax_step.h, operation by operation, the per-graph sums in the canonical order: lane partials
-as an explicit loop over the rows of a zero-padded [-1,256] reshape, then the explicit fold), a thin wrapper that runs the
-library's host twins (hermnet_host_relax_advance / _finish) on numpy arrays, a plain vectorised FIRE that follows ASE's
-published `FIRE.step`, and two analytic force fields x -> float32 forces."""
+arithmetic (hermnet_amd/csrc/relax_step.h, operation by operation, the per-graph sums in resident_step.h's canonical order:
+lane partials as an explicit loop over the rows of a zero-padded [-1,256] reshape, then the explicit fold), a thin wrapper
+that runs the library's host twins (hermnet_host_relax_advance / _finish) on numpy arrays, a plain vectorised FIRE that
+follows ASE's published `FIRE.step`, and two analytic force fields x -> float32 forces."""
 import ctypes
 
 import numpy as np

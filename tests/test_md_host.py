@@ -223,6 +223,110 @@ def test_prime_mode_changes_neither_step_nor_velocities():
     assert host.state.tolist() == [0, NONFINITE, 0, 0] and np.array_equal(host.f_prev, f)
 
 
+def _sequential(terms):
+    """hermnet_host_md_finish's kinetic-energy sum: one accumulator from 0.0, atoms in ascending order."""
+    s = 0.0
+    for t in terms:
+        s = s + float(t)
+    return s
+
+
+@pytest.mark.parametrize("wrap", [True, False], ids=["wrap", "nowrap"])
+@pytest.mark.parametrize("n", [0, 1, 256, 257, 513])
+def test_one_graph_on_both_sides_of_the_lane_boundary(n, wrap):
+    """No atom, one, a full row of 256 lanes, one over, two rows and one: four BAOAB steps bit-equal to the numpy
+    transcription, the log row's kinetic energy bit-equal to the host twin's own (sequential) order."""
+    x, v, m = _system(n, TRICLINIC, seed=100 + n)
+    kw = dict(cell=TRICLINIC if wrap else None, friction=0.02, temperature=400.0, seed=5, num_graphs=1)
+    host, ref = HostMD(x, v, m, 0.5, log_steps=3, **kw), NumpyMD(x, v, m, 0.5, **kw)
+    centre = np.array([0.5, 0.5, 0.5]) @ TRICLINIC
+    for step in range(4):
+        p_host, p_ref = host.advance().copy(), ref.advance()
+        assert np.array_equal(p_host.view(np.uint32), p_ref.view(np.uint32))
+        host.finish(_well(p_host, centre), energy=[0.5 * step], total=(7 * step, 0))
+        ref.finish(_well(p_ref, centre))
+        _same_state(host, ref)
+        assert host.state.tolist() == [step + 1, 0, 0, 0]
+        assert bits(host.log[step % 3, 0]).tolist() == bits([0.5 * step, _sequential(ref.ke), 7.0 * step]).tolist()
+    assert bool(host.image.any()) == (wrap and n > 0)
+
+
+_HOSTILE = dict(sizes=(130, 0, 70), temperature=[300.0, 500.0, 700.0])
+
+
+def _hostile_batch(broken, friction=0.02):
+    """Three graphs, the middle one empty, a triclinic and an orthogonal cell; `broken`: the first and the last `batch` entry
+    out of range on either side (the library clamps them to the graphs they belong to: the numpy twin keeps the sound batch)."""
+    n = sum(_HOSTILE["sizes"])
+    x, v, m = _system(n, CUBIC, seed=21)
+    batch = np.repeat([0, 1, 2], _HOSTILE["sizes"])
+    kw = dict(cell=np.stack([TRICLINIC, CUBIC, CUBIC]), batch=batch, friction=friction,
+              temperature=None if friction is None else _HOSTILE["temperature"], seed=8, num_graphs=3)
+    host, ref = HostMD(x, v, m, 0.5, log_steps=8, **kw), NumpyMD(x, v, m, 0.5, **kw)
+    if broken:
+        host.batch[0], host.batch[-1] = -7, 99
+    return host, ref, np.array([5.0, 5.5, 6.0])
+
+
+@pytest.mark.parametrize("friction", [None, 0.02], ids=["nve", "baoab"])
+@pytest.mark.parametrize("broken", [False, True], ids=["sound", "broken"])
+def test_batch_with_an_empty_graph_and_a_batch_out_of_range(broken, friction):
+    host, ref, centre = _hostile_batch(broken, friction)
+    ptr = host.graph_ptr
+    assert ptr.tolist() == [0, 130, 130, 200]
+    for step in range(4):
+        p_host, p_ref = host.advance().copy(), ref.advance()
+        assert np.array_equal(p_host.view(np.uint32), p_ref.view(np.uint32))
+        host.finish(_well(p_host, centre), energy=[-1.0, -2.0, -3.0], total=(40 + step, 0))
+        ref.finish(_well(p_ref, centre))
+        _same_state(host, ref)
+        want = [[-1.0 - g, _sequential(ref.ke[ptr[g]:ptr[g + 1]]), 40.0 + step] for g in range(3)]
+        assert np.array_equal(bits(host.log[step]), bits(want))
+    assert host.state.tolist() == [4, 0, 0, 0] and np.all(host.log[4:] == -7.0) and host.image.any()
+
+
+@pytest.mark.parametrize("why", ["flags", "count", "nan", "inf"])
+def test_void_step_in_the_hostile_batch(why):
+    """Each halt cause on its own, at step 3 of the batch above with its broken `batch`: x, v, image, f_prev and the log
+    bit-equal to the end of step 2, pos32 the rounding of x, state = (3, code, 3, 0), and a second call changes nothing."""
+    host, _, centre = _hostile_batch(True)
+    good = dict(energy=[-1.0, -2.0, -3.0], total=(500, 0), capacity=512)
+    for _ in range(3):
+        host.finish(_well(host.advance(), centre), **good)
+    names = ("x", "v", "image", "f_prev", "log", "ke_atom")
+    keep = [getattr(host, k).copy() for k in names]
+    bad, code = {"flags": (dict(good, total=(500, 16)), 16), "count": (dict(good, total=(513, 0)), 4),
+                 "nan": (dict(good, energy=[-1.0, np.nan, -3.0]), NONFINITE),
+                 "inf": (dict(good, energy=[-1.0, -2.0, -np.inf]), NONFINITE)}[why]
+    moved = host.advance().copy()
+    assert not np.array_equal(bits(host.x), bits(keep[0]))
+    host.finish(_well(moved, centre), **bad)
+    for again in range(2):
+        assert host.state.tolist() == [3, code, 3, 0]
+        assert all(np.array_equal(getattr(host, k).view(np.uint8), b.view(np.uint8)) for k, b in zip(names, keep))
+        assert np.array_equal(host.pos32, keep[0].astype(np.float32))
+        host.finish(_well(host.advance(), centre), **good)
+
+
+@pytest.mark.parametrize("code", [0, 4], ids=["clean", "halting"])
+def test_prime_in_the_hostile_batch(code):
+    """Mode 1 with and without a halt code: nothing moves and no row is written; a clean prime takes the forces and clears
+    the mode, a failing one records the halt (at the step it stands at) and leaves f_prev alone."""
+    host, _, centre = _hostile_batch(True)
+    host.finish(_well(host.advance(), centre), energy=[0.0, 0.0, 0.0])
+    names = ("x", "v", "image", "log", "ke_atom")
+    keep = [getattr(host, k).copy() for k in names]
+    f_before = host.f_prev.copy()
+    host.state[3] = 1
+    p = host.advance().copy()
+    assert np.array_equal(p, keep[0].astype(np.float32))
+    f = _well(p, centre) + np.float32(1.0)
+    host.finish(f, energy=[0.0, 0.0, 0.0], total=(11 if code else 10, 0), capacity=10)
+    assert host.state.tolist() == [1, code, 1 if code else 0, 0]
+    assert all(np.array_equal(getattr(host, k).view(np.uint8), b.view(np.uint8)) for k, b in zip(names, keep))
+    assert np.array_equal(host.f_prev, f_before if code else f)
+
+
 def test_argument_checks_of_the_md_entry_points_need_no_gpu():
     host = HostMD(*_system(4, CUBIC, seed=1), 1.0, cell=CUBIC)
     lib, P = host.lib, lambda a: a.ctypes.data

@@ -203,6 +203,98 @@ def test_void_step(what):
     assert np.array_equal(bits(host.x), bits(straight.x)) and np.array_equal(bits(host.gf), bits(straight.gf))
 
 
+@pytest.mark.parametrize("wrap", [True, False], ids=["wrap", "nowrap"])
+@pytest.mark.parametrize("n", [0, 1, 256, 257, 513])
+def test_one_graph_on_both_sides_of_the_lane_boundary(n, wrap):
+    """No atom, one, a full row of 256 lanes, one over, two rows and one: twelve evaluations bit-equal to the numpy
+    transcription (state, log rows, accepted forces), with the wrap and without."""
+    x, force = wells(n, 40 + n, 0.3, cell=TRICLINIC, outside=True)
+    host, ref = HostRelax(x, cell=TRICLINIC, wrap=wrap), NumpyRelax(x, cell=TRICLINIC, wrap=wrap)
+    for k in range(12):
+        host.finish(force(host.advance()), energy=[0.25 * k], total=(3 * k, 0))
+        ref.finish(force(ref.advance()), energy=[0.25 * k], total=(3 * k, 0))
+        same_state(host, ref)
+        if k < len(ref.log):
+            assert np.array_equal(bits(host.log[k]), bits(ref.log[k])) and np.array_equal(host.f_prev, ref.f)
+    assert np.all(host.log[len(ref.log):] == -7.0)
+    assert bool(host.image.any()) == (wrap and n > 0)
+    assert host.state[0] == len(ref.log) and (n > 0 or host.state.tolist() == [1, 0, 0, 1])
+
+
+ORTHO = np.diag([18.0, 19.0, 20.0])
+HOSTILE_SIZES = (40, 0, 70)
+HELD = 45
+
+
+def _hostile_batch(broken=True, wrap=True):
+    """Three graphs, the middle one empty, a triclinic and an orthogonal cell, one held atom under a large force; graph 0
+    starts so close to its minimum that it converges at the first evaluation.  `broken`: the first and the last `batch`
+    entry out of range on either side (the library clamps them to the graphs they belong to)."""
+    cells = np.stack([TRICLINIC, ORTHO, ORTHO])
+    near, f_near = wells(HOSTILE_SIZES[0], 31, 0.002, cell=cells[0], outside=True)
+    far, f_far = wells(HOSTILE_SIZES[2], 32, 0.3, cell=cells[2], outside=True)
+    x, batch = np.concatenate([near, far]), np.repeat([0, 1, 2], HOSTILE_SIZES)
+    fixed = np.zeros(len(x), dtype=bool)
+    fixed[HELD] = True
+
+    def force(pos32):
+        f = np.concatenate([f_near(pos32[:HOSTILE_SIZES[0]]), f_far(pos32[HOSTILE_SIZES[0]:])]).astype(np.float32)
+        f[HELD] = 50.0
+        return f
+
+    kw = dict(cell=cells, batch=batch, num_graphs=3, fixed=fixed, wrap=wrap)
+    host, ref = HostRelax(x, log_steps=16, **kw), NumpyRelax(x, **kw)
+    if broken:
+        host.batch[0], host.batch[-1] = -7, 99
+    return host, ref, force, x
+
+
+@pytest.mark.parametrize("wrap", [True, False], ids=["wrap", "nowrap"])
+@pytest.mark.parametrize("broken", [False, True], ids=["sound", "broken"])
+def test_batch_with_an_empty_graph_and_a_batch_out_of_range(broken, wrap):
+    host, ref, force, x = _hostile_batch(broken, wrap)
+    assert host.graph_ptr.tolist() == [0, 40, 40, 110]
+    for k in range(10):
+        host.finish(force(host.advance()), total=(90 + k, 0))
+        ref.finish(force(ref.advance()), total=(90 + k, 0))
+        same_state(host, ref)
+        assert np.array_equal(bits(host.log[k]), bits(ref.log[k])) and np.array_equal(host.f_prev, ref.f)
+    assert host.gi[:, 2].tolist() == [1, 1, 0] and host.gi[:, 3].tolist() == [0, 0, -1]
+    assert np.array_equal(bits(host.x[HELD]), bits(x[HELD])) and not host.v[HELD].any()
+    assert bool(host.image.any()) == wrap
+
+
+@pytest.mark.parametrize("why", ["flags", "count", "nan", "inf"])
+def test_void_step_beside_a_converged_graph(why):
+    """Each halt cause on its own, at evaluation 4 of the batch above (broken `batch`, graphs 0 and 1 converged, graph 2 with
+    its held atom moving): every array bit-equal to the end of evaluation 3 -- the converged graph's atoms and its gf / gi
+    rows among them --, pos32 the rounding of x, state = (4, code, 4, 0), no log row, and a second call changes nothing."""
+    host, ref, force, _ = _hostile_batch()
+    good = dict(energy=[-1.0, -2.0, -3.0], total=(500, 0), capacity=512)
+    for _ in range(4):
+        host.finish(force(host.advance()), **good)
+        ref.finish(force(ref.advance()), **good)
+    assert host.gi[:, 2].tolist() == [1, 1, 0]
+    names = ("x", "v", "image", "pos32", "gf", "gi", "log", "f_prev")
+    keep = [getattr(host, k).copy() for k in names]
+    x0_converged = host.x0[:40].copy()
+    bad, code = {"flags": (dict(good, total=(500, 16)), 16), "count": (dict(good, total=(513, 0)), 4),
+                 "nan": (dict(good, energy=[-1.0, np.nan, -3.0]), 256),
+                 "inf": (dict(good, energy=[np.inf, -2.0, -3.0]), 256)}[why]
+    moved = host.advance().copy()
+    assert not np.array_equal(moved[40:], keep[3][40:]) and np.array_equal(moved[:40], keep[3][:40])
+    ref.advance()
+    host.finish(force(moved) + np.float32(2.0), **bad)
+    ref.finish(force(moved) + np.float32(2.0), **bad)
+    for again in range(2):
+        assert host.state.tolist() == [4, code, 4, 0]
+        assert all(np.array_equal(getattr(host, k).view(np.uint8), b.view(np.uint8)) for k, b in zip(names, keep))
+        assert np.array_equal(host.pos32, host.x.astype(np.float32)) and np.array_equal(bits(host.x0[:40]), bits(x0_converged))
+        assert np.all(host.log[4:] == -7.0)
+        same_state(host, ref)
+        host.finish(force(host.advance()), **good)
+
+
 def test_argument_refusals():
     """HN_ERR_BAD_ARG for a null state, num_graphs < 1, dt / dtmax / maxstep / fmax not positive, a flag other than the
     wrap; n = 0 is served."""
