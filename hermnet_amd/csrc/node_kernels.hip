@@ -244,22 +244,32 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
     v[k] = make_float4(v[k].x * m.x, v[k].y * m.y, v[k].z * m.z, v[k].w * m.w);
     s += (v[k].x + v[k].y) + (v[k].z + v[k].w);
   }
-  const float mu = wave_sum(s) / (float)Hr;
-  float q = 0.f;
+  // The mean in two steps: mu0 from the plain sum, then the sum of the shifted row, which an exact mu0 would leave at zero.
+  // A row of 1e3 + unit noise over 1024 channels puts mu0 off by ~1e-4 (the partial sums reach 1e6, half an ulp of which is
+  // 0.03), 3e-5 of the row's largest output; the shifted entries are O(1), so their sum gives that error back to an ulp.
+  const float mu0 = wave_sum(s) / (float)Hr;
+  float q = 0.f, d = 0.f;
 #pragma unroll
   for (int k = 0; k < kLnMaxPerLane; ++k) {
     const int c = (k * 64 + lane) * 4;
     if (c < H) {
       const float4 m = chan_mask4(c, Hr);
-      v[k] = make_float4((v[k].x - mu) * m.x, (v[k].y - mu) * m.y, (v[k].z - mu) * m.z, (v[k].w - mu) * m.w);
+      v[k] = make_float4((v[k].x - mu0) * m.x, (v[k].y - mu0) * m.y, (v[k].z - mu0) * m.z, (v[k].w - mu0) * m.w);
+      d += (v[k].x + v[k].y) + (v[k].z + v[k].w);
       q += (v[k].x * v[k].x + v[k].y * v[k].y) + (v[k].z * v[k].z + v[k].w * v[k].w);
     }
   }
-  const float rs = rsqrtf(wave_sum(q) / (float)Hr + eps);
+  const float dm = wave_sum(d) / (float)Hr;
+  const float mu = mu0 + dm;
+  const float rs = rsqrtf(fmaxf(wave_sum(q) / (float)Hr - dm * dm, 0.f) + eps);
 #pragma unroll
   for (int k = 0; k < kLnMaxPerLane; ++k) {
     const int c = (k * 64 + lane) * 4;
-    if (c < H) st4(n + (size_t)r * H + c, make_float4(v[k].x * rs, v[k].y * rs, v[k].z * rs, v[k].w * rs));
+    if (c < H) {
+      const float4 m = chan_mask4(c, Hr);
+      st4(n + (size_t)r * H + c, make_float4((v[k].x - dm) * m.x * rs, (v[k].y - dm) * m.y * rs, (v[k].z - dm) * m.z * rs,
+                                             (v[k].w - dm) * m.w * rs));
+    }
   }
   if (lane == 0) { mean[r] = mu; rstd[r] = rs; }
 }

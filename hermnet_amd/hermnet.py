@@ -139,6 +139,11 @@ class _GraphSpread(torch.autograd.Function):
         return GraphEnergies.apply(c_rows.contiguous(), ctx.graph, ctx.batch), None, None, None
 
 
+# Every channel axis is padded to a multiple of 64 (layer.LayerWeights.refresh); hermnet_layernorm_fwd / _bwd take rows of at
+# most this many channels (HN_ERR_BAD_ARG beyond), and every layer path past the chain kernels' 512 runs through them
+MAX_PADDED_WIDTH = 1024
+
+
 class HVNet(nn.Module):
     """Heterogeneous Vertex Network (`hermnet.py:68-152`).
 
@@ -155,6 +160,10 @@ class HVNet(nn.Module):
         if isinstance(elems, str):
             elems = [elems]
         self.elems = list(elems)
+        if (hidden_channels + 63) // 64 * 64 > MAX_PADDED_WIDTH:
+            raise ValueError("hermnet_amd: hidden_channels = %d pads to %d channels; the LayerNorm kernels hold a row of at "
+                             "most %d (csrc/node_kernels.hip: kLnMaxPerLane), so the widest model has hidden_channels = %d"
+                             % (hidden_channels, (hidden_channels + 63) // 64 * 64, MAX_PADDED_WIDTH, MAX_PADDED_WIDTH))
         self.rc = rc   # read by the calculators (plugin/ase_interface/calculator.py:49)
         self.num_layers = num_layers
         self.hidden_channels = hidden_channels

@@ -24,8 +24,7 @@ def layernorm_fwd(x, eps=1e-5, h_real=0):
     """LayerNorm without affine over the last axis -> (n, mean [rows], rstd [rows]).  `h_real` (0 = all): width of
     the statistics when the rows are zero-padded (padded outputs are zero)."""
     rows, H = x.shape
-    n = torch.empty_like(x)
-    mean, rstd = _new(x, rows), _new(x, rows)
+    n, mean, rstd = _new(x, rows, H), _new(x, rows), _new(x, rows)
     _call("layernorm_fwd", "hermnet_layernorm_fwd", P(x), P(n), P(mean), P(rstd), rows, H, h_real, eps)
     return n, mean, rstd
 
@@ -33,14 +32,14 @@ def layernorm_fwd(x, eps=1e-5, h_real=0):
 def layernorm_bwd(g, x, mean, rstd, add=None, h_real=0):
     """Gradient of layernorm_fwd w.r.t. x, plus `add`."""
     rows, H = x.shape
-    gx = torch.empty_like(x)
+    gx = _new(x, rows, H)
     _call("layernorm_bwd", "hermnet_layernorm_bwd", P(g), P(x), P(mean), P(rstd), P(add), P(gx), rows, H, h_real)
     return gx
 
 
 def ssilu_fwd(h, bias=None, rows_per_bias=0):
     """a = ScaledSiLU(h + bias); h [rows, cols]; bias [groups, cols] (group = row // rows_per_bias) or None."""
-    a = torch.empty_like(h)
+    a = _new(h, *h.shape)
     cols = h.size(-1)
     _call("ssilu_fwd", "hermnet_ssilu_fwd", P(h), P(bias), rows_per_bias, P(a), h.numel() // cols, cols)
     return a
@@ -87,7 +86,7 @@ def energy_head_fwd(h, w, b, mask=None):
 
 def energy_head_bwd(ge, h, w, mask=None):
     rows, C = h.shape
-    gh = torch.empty_like(h)
+    gh = _new(h, rows, C)
     _call("energy_head_bwd", "hermnet_energy_head_bwd", P(ge), P(h), P(w), P(mask), P(gh), rows, C)
     return gh
 

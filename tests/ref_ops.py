@@ -269,6 +269,34 @@ def node_pre_bwd(gxh, hb, x, mean, rstd, w, add=None, src_ranges=None, windows=N
     return out
 
 
+def pair_mean(x, vec, Te, P, B, rows_out, backward=False):
+    """csrc/node_kernels.hip: hermnet_pair_mean, modes 0 and 1.  Target rows are [Te][P][B] blocks of B rows.
+    forward: [Te*P*B, ...] -> [rows_out, ...], row c*B + i = the mean over k of row (c*P + k)*B + i, zero rows behind Te*B;
+    backward: [rows_out, ...] -> [Te*P*B, ...], row (c*P + k)*B + i = row c*B + i / P."""
+    outs = []
+    for t in (x, vec):
+        tail = tuple(t.shape[1:])
+        if backward:
+            g = t[:Te * B].reshape((Te, 1, B) + tail).expand((Te, P, B) + tail)
+            outs.append((g * (1.0 / P)).reshape((Te * P * B,) + tail))
+        else:
+            out = torch.zeros((rows_out,) + tail, dtype=t.dtype)
+            out[:Te * B] = (t.view((Te, P, B) + tail).sum(1) * (1.0 / P)).reshape((Te * B,) + tail)
+            outs.append(out)
+    return tuple(outs)
+
+
+def pair_sum_accumulate(x, vec, x_acc, vec_acc, Te, P, B, scale_x, scale_vec, ranges=None):
+    """hermnet_pair_mean, mode 2 (in place): x_acc[c*B + i] += scale_x * sum_k x[(c*P + k)*B + i], vec likewise with
+    scale_vec.  `ranges` = (tensor [k,2], host list of (lo, hi)): only the rows of x_acc / vec_acc inside one of them."""
+    sel = torch.ones(Te * B, dtype=torch.bool) if ranges is None else _rows_of_ranges(
+        [(lo, min(hi, Te * B)) for lo, hi in ranges[1]], Te * B)
+    for t, acc, s in ((x, x_acc, scale_x), (vec, vec_acc, scale_vec)):
+        tail = tuple(t.shape[1:])
+        add = (t.view((Te, P, B) + tail).sum(1) * s).reshape((Te * B,) + tail)
+        acc[:Te * B][sel] += add[sel]
+
+
 def halo_rows(mode, x, vec, idx, buf=None):
     """csrc/node_kernels.hip: hermnet_halo_rows -- 0 pack, 1 pack-and-clear, 2 unpack (in place)."""
     H = x.size(1)

@@ -17,7 +17,7 @@ from hermnet_amd import synth
 from hermnet_amd.ops import EdgeGeometry, MessageScatter
 from hermnet_amd.relations import RelationalGraph
 from hermnet_amd.elements import atomic_numbers
-from helpers import Golden, SMALL_CASES, NONGAUSS_CASES, rel_err, judge_rows
+from helpers import Golden, SMALL_CASES, NONGAUSS_CASES, rel_err, judge_rows, row_err, FLT_MIN
 import ref_ops
 
 pytestmark = pytest.mark.gpu
@@ -616,7 +616,9 @@ def test_node_chain_kernels_on_adversarial_operands(H, T, counts, tile16, monkey
         denormals: below ~1e-33 the residual planes flush and a row keeps >= 8 significant bits -- documented, not tested).
     Bound per row: the kernels' usual 5e-6 (2e-6 forward), or 8 x the error a plain fp32 evaluation of the same chain makes on
     that row, whichever is larger -- cancellation costs fp32 itself digits (and how many depends on the order of a sum: the
-    kernels' LayerNorm and torch's reduce a row in different trees); the split products must not cost more."""
+    kernels' LayerNorm and torch's reduce a row in different trees); the split products must not cost more.
+    Behind them, as further rows of the update chain: the tail of ScaledSiLU (`_chain_tail_rows`; measured on the MI355X:
+    worst row 6.3e-7 at H = 128, 6.4e-7 at 256, 9.4e-7 at 512, against a derived bound of 1.25e-5)."""
     from test_host_logic import _layer_weights_and_graph
     from hermnet_amd import nodeops
     import copy
@@ -672,6 +674,65 @@ def test_node_chain_kernels_on_adversarial_operands(H, T, counts, tile16, monkey
     b32 = ref_ops.node_update_bwd(gxo.clone(), gvo.clone(), u32[2], u32[3], u32[4], u32[5], w, g)
     judge(gx1, b64[0], b32[0], 5e-6, "update_bwd gx1", known)
     judge(gvec1, b64[1], b32[1], 5e-6, "update_bwd gvec1", known)
+    _chain_tail_rows(w, wd, g, gd, H, gen)
+
+
+def _chain_tail_rows(w, wd, g, gd, H, gen):
+    """The tail rows of tests/test_stage_reference.py as further rows of x1 for the update chain (sigmoid_ of
+    csrc/node_chain_common.h: the fast exponential and the hardware reciprocal), on a copy of the weights in which the x half
+    of Wx0 is the identity and bx0 = bx2 = 0: with vec1 = 0 the pre-activations are then h2b = x1 itself -- rows whose every
+    entry lies in [-80, -20], and rows at +-100 and +-1e6, in turn -- and q23 = ScaledSiLU(h2b) Wx2[H:] shows the tail: such a
+    row within floor + 2 |h|max 2^-24 of float64 (or 8 x the fp32 restatement's error), the rows at -100 and -1e6 below
+    FLT_MIN x H, those at +100 and +1e6 by the row rule; everything finite, backward included."""
+    import copy
+    from hermnet_amd import nodeops
+    from test_stage_reference import TAIL_SATURATED
+    dev = _dev()
+    N, T, nk = g.N, g.T, g.type_rowptr_host[-1]
+    eye = torch.cat([torch.eye(H), torch.zeros(H, H)], 1)                  # [H, 2H]: h2 = x1 (the |v2| half unread)
+    eye_s = eye.expand(T, H, 2 * H).contiguous().to(dev)
+    w0, wd0 = copy.copy(w), copy.copy(wd)
+    w0.wx0, w0.bx0, w0.bx2 = [eye] * T, [torch.zeros(H)] * T, [torch.zeros_like(b) for b in w.bx2]
+    wd0.bx0_s, wd0.bx2_s = torch.zeros_like(wd.bx0_s), torch.zeros_like(wd.bx2_s)
+    wd0.wx0f, wd0.wx0tf = nodeops.weight_fragments(eye_s), nodeops.weight_fragments(eye_s.transpose(1, 2).contiguous())
+    if wd.wx0f16 is not None:
+        wd0.wx0f16 = nodeops.weight_fragments16(eye_s)
+        wd0.wx0tf16 = nodeops.weight_fragments16(eye_s.transpose(1, 2).contiguous())
+    kind = torch.arange(N) % (1 + len(TAIL_SATURATED))              # 0: a row in the tail; k: TAIL_SATURATED[k - 1]
+    x1 = -20.0 - 60.0 * torch.rand(N, H, generator=gen)
+    x1[:, 0], x1[:, 1] = -20.0, -80.0
+    for k, v in enumerate(TAIL_SATURATED):
+        x1[kind == k + 1] = v
+    vec1 = torch.zeros(N, 3, H)
+    outs = nodeops.node_update_fwd(x1.to(dev), vec1.to(dev), wd0, gd)
+    u64, u32 = ref_ops.node_update_fwd(x1.double(), vec1.double(), w0, g), ref_ops.node_update_fwd(x1, vec1, w0, g)
+    rows = torch.arange(N) < nk
+    if g.row_real is not None:
+        rows &= g.row_real.cpu() != 0
+    if g.row_active is not None:
+        rows &= g.row_active.cpu() != 0
+    h2b = u64[3]
+    tail = rows & (kind == 0)
+    assert int(tail.sum()) >= 5 and float(h2b[tail].max()) == -20.0 and float(h2b[tail].min()) == -80.0
+    for t_ in outs:
+        assert bool(torch.isfinite(t_[:nk][rows[:nk].to(dev)]).all())
+    judge_rows(outs[0], u64[0], u32[0], 3e-6, "tail rows update_fwd x", slice(0, nk))
+    q, q64, q32 = outs[4].cpu().double(), u64[4], u32[4]
+    err, base = row_err(q[tail], q64[tail]), row_err(q32[tail], q64[tail])
+    bound = torch.maximum(3e-6 + 2.0 * h2b[tail].abs().amax(1) * 2.0 ** -24, 8.0 * base)
+    print("chain tail rows H=%d: worst q23 row err %.2e, its bound %.2e" % (H, float(err.max()), float(bound[err.argmax()])))
+    assert bool((err <= bound).all()), float((err / bound).max())
+    for k, v in enumerate(TAIL_SATURATED):
+        sel = rows & (kind == k + 1)
+        assert bool(sel.any())
+        if v > 0:
+            judge_rows(q[sel], q64[sel], q32[sel], 3e-6, "tail rows q23 at %g" % v)
+        else:
+            assert float(q[sel].abs().max()) < FLT_MIN * H, v
+    gen2 = torch.Generator().manual_seed(13)
+    gx1, gvec1 = nodeops.node_update_bwd(torch.randn(N, H, generator=gen2).to(dev), torch.randn(N, 3, H, generator=gen2).to(dev),
+                                         outs[2], outs[3], outs[4], outs[5], wd0, gd)
+    assert bool(torch.isfinite(gx1).all()) and bool(torch.isfinite(gvec1).all())
 
 
 @pytest.mark.parametrize("E,H,has_v", [(1000, 128, True), (777, 128, False), (301, 100, True), (50, 512, True), (5, 4, True),
@@ -2246,11 +2307,14 @@ def test_skewed_composition_uses_tight_layout_and_matches_oracle():
 
 
 @pytest.mark.parametrize("H,R,layers", [(512, 128, 2), (64, 20, 3), (192, 50, 2), (96, 16, 2), (100, 32, 3), (50, 20, 2),
-                                        (320, 40, 2), (384, 64, 2), (448, 30, 2), (300, 24, 2), (500, 32, 2)])
+                                        (320, 40, 2), (384, 64, 2), (448, 30, 2), (300, 24, 2), (500, 32, 2),
+                                        # beyond the chain kernels' 512: layer.GemmRelationalLayer, 9 and 16 column blocks
+                                        (576, 24, 2), (520, 16, 2), (1024, 16, 2)])
 def test_other_widths_vs_oracle(H, R, layers):
     """hidden_channels = 512 is the reference default (hermnet.py:86): 8 column blocks; odd num_rbf; and widths that
     are NOT a multiple of 64 (the reference accepts any, hermnet.py:84-88): 96, 100 and 50 run on the same kernels with
-    zero-padded channels (layer.LayerWeights.refresh)."""
+    zero-padded channels (layer.LayerWeights.refresh).  576, 520 (padded to 576) and 1024 (the widest: hermnet.MAX_PADDED_WIDTH)
+    take library GEMMs joined by the stage kernels, and the read-out's stage form."""
     data = synth.fcc_alloy(reps=(2, 2, 3))
     _oracle_vs_hip(data, ["Al", "Ni", "Cu"], dict(rc=5.0, num_layers=layers, hidden_channels=H, num_rbf=R), 40 + H)
 
