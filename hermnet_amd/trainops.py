@@ -19,6 +19,12 @@ import torch.nn.functional as F
 from . import _lib
 
 
+def _new(like, *shape):
+    """Every buffer a kernel of the training path writes in full is allocated here (the row-rule tests replace it with a
+    NaN fill: tests/test_train_rows.py); buffers whose contract needs zeros stay `zeros` (`_rows_buffer`)."""
+    return torch.empty(shape, dtype=like.dtype, device=like.device)
+
+
 class _RowKey(object):
     """One edge -> row assignment `idx` [K] (values < n_rows) in both forms the pair below needs: the index vector for
     the gather, and (perm, lengths) -- the edges sorted by row and the run lengths of all n_rows rows -- for a sum
@@ -128,7 +134,7 @@ class _EdgeUnitGrad(torch.autograd.Function):
 def _edge_unit(order, D, gU, gd, C):
     from .ops import _stream
     E = D.size(0)
-    new = lambda *shape: torch.empty(*shape, dtype=D.dtype, device=D.device)
+    new = lambda *shape: _new(D, *shape)
     o0, o1, o2 = new(E, 3), (new(E) if order != 1 else None), (new(E, 3) if order == 2 else None)
     P = _lib.ptr
     _lib.check(_lib.load().hermnet_edge_unit(order, P(D), P(gU), P(gd), P(C), E, P(o0), P(o1), P(o2), _stream()),
@@ -351,7 +357,7 @@ class BandP(torch.autograd.Function):
         ctx.set_materialize_grads(False)
         nc, C, N = A.size(0), A.size(1), B.size(2)
         if _band_kernels(A, N):
-            out = torch.empty(nc, C, N, dtype=A.dtype, device=A.device)
+            out = _new(A, nc, C, N)
             P = _lib.ptr
             _lib.check(_lib.load().hermnet_band_product(P(A), P(B), P(bias), nc, C, N, P(out), _stream()), "hermnet_band_product")
         else:
@@ -371,9 +377,7 @@ class BandP(torch.autograd.Function):
             from .ops import _stream
             A, g1, g2 = ctx.held.t, _c(g1), _c(g2)
             nc, C, N = g1.shape
-            gA = torch.empty(nc, C, 32, dtype=A.dtype, device=A.device)
-            gB = torch.empty(nc, 32, N, dtype=A.dtype, device=A.device)
-            gb = torch.empty(nc, N, dtype=A.dtype, device=A.device)
+            gA, gB, gb = _new(A, nc, C, 32), _new(A, nc, 32, N), _new(A, nc, N)
             P = _lib.ptr
             _lib.check(_lib.load().hermnet_band_product_grads(P(A), P(B), P(g1), P(g2), nc, C, N, P(gA), P(gB), P(gb), _stream()),
                        "hermnet_band_product_grads")
@@ -428,7 +432,7 @@ class BandQ(torch.autograd.Function):
         ctx.save_for_backward(g1, g2, B)
         nc, C, N = g1.shape
         if _band_kernels(B.new_empty(0, C, 32), N):
-            gA = torch.empty(nc, C, 32, dtype=g1.dtype, device=g1.device)
+            gA = _new(g1, nc, C, 32)
             P = _lib.ptr
             _lib.check(_lib.load().hermnet_band_product_grad_a(P(g1), P(g2), P(B), nc, C, N, P(gA), _stream()),
                        "hermnet_band_product_grad_a")
@@ -454,8 +458,7 @@ class BandS(torch.autograd.Function):
         ctx.save_for_backward(A, g1, g2)
         nc, C, N = g1.shape
         if _band_kernels(A, N):
-            gB = torch.empty(nc, 32, N, dtype=A.dtype, device=A.device)
-            gb = torch.empty(nc, N, dtype=A.dtype, device=A.device)
+            gB, gb = _new(A, nc, 32, N), _new(A, nc, N)
             P = _lib.ptr
             _lib.check(_lib.load().hermnet_band_product_grad_b(P(A), P(g1), P(g2), nc, C, N, P(gB), P(gb), _stream()),
                        "hermnet_band_product_grad_b")
@@ -537,7 +540,7 @@ class _ColSum(torch.autograd.Function):
         T, K, O = g.shape
         ctx.K = K
         nb = (K + _ColSum.ROWS - 1) // _ColSum.ROWS
-        part = torch.empty(T, nb, O, dtype=g.dtype, device=g.device)
+        part = _new(g, T, nb, O)
         _lib.check(_lib.load().hermnet_col_sum(_lib.ptr(g), T, K, O, _ColSum.ROWS, _lib.ptr(part), _stream()), "hermnet_col_sum")
         return part.sum(1)
 
@@ -681,7 +684,7 @@ class _SiLUBwd(torch.autograd.Function):
     def forward(ctx, gy, x):
         gy, x = _c(gy), _c(x)
         ctx.save_for_backward(gy, x)
-        gx = torch.empty_like(x)
+        gx = _new(x, *x.shape)
         _node_op(1, [gy, x], [gx], x.numel() // 4, 4)
         return gx
 
@@ -689,7 +692,7 @@ class _SiLUBwd(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, u):
         gy, x = ctx.saved_tensors
-        cg, cx = torch.empty_like(x), torch.empty_like(x)
+        cg, cx = _new(x, *x.shape), _new(x, *x.shape)
         _node_op(2, [_c(u), gy, x], [cg, cx], x.numel() // 4, 4)
         return cg, cx
 
@@ -715,7 +718,7 @@ class _LayerNormBwd(torch.autograd.Function):
         gy, x = _c(gy), _c(x)
         ctx.save_for_backward(gy, x)
         ctx.eps = eps
-        gx = torch.empty_like(x)
+        gx = _new(x, *x.shape)
         _node_op(9, [gy, x], [gx], x.numel() // x.size(-1), x.size(-1), eps)
         return gx
 
@@ -723,7 +726,7 @@ class _LayerNormBwd(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, v):
         gy, x = ctx.saved_tensors
-        cg, cx = torch.empty_like(x), torch.empty_like(x)
+        cg, cx = _new(x, *x.shape), _new(x, *x.shape)
         _node_op(10, [_c(v), gy, x], [cg, cx], x.numel() // x.size(-1), x.size(-1), ctx.eps)
         return cg, cx, None
 
@@ -740,7 +743,7 @@ class Residual(torch.autograd.Function):
         ctx.save_for_backward(mask)
         ctx.c, ctx.has_vec = c, vec is not None
         ctx.set_materialize_grads(False)
-        x1, v1 = torch.empty_like(x), torch.empty_like(dv)
+        x1, v1 = _new(x, *x.shape), _new(dv, *dv.shape)
         _node_op(11, [x, dx, vec, dv, mask], [x1, v1], R, H, c)
         return x1, v1
 
@@ -759,8 +762,8 @@ class _MaskScale(torch.autograd.Function):
         ctx.save_for_backward(mask)
         ctx.c = c
         ctx.set_materialize_grads(False)
-        o1 = torch.empty(R, H, dtype=ref.dtype, device=ref.device)
-        o2 = torch.empty(R, 3, H, dtype=ref.dtype, device=ref.device)
+        o1 = _new(ref, R, H)
+        o2 = _new(ref, R, 3, H)
         _node_op(12, [_c(g1), _c(gv1), mask], [o1, o2], R, H, c)
         return o1, o2
 
@@ -782,7 +785,7 @@ class UpdateMid(torch.autograd.Function):
         R, H = xt.shape
         ctx.save_for_backward(vp)
         ctx.c, ctx.eps = c, eps
-        vdot, xin = torch.empty_like(xt), torch.empty(R, 2 * H, dtype=xt.dtype, device=xt.device)
+        vdot, xin = _new(xt, *xt.shape), _new(xt, R, 2 * H)
         _node_op(3, [vp, xt], [vdot, xin], R, H, c, eps)
         return vdot, xin
 
@@ -801,7 +804,7 @@ class _UpdateMidBwd(torch.autograd.Function):
         ctx.save_for_backward(g_vdot, g_xin, vp)
         ctx.c, ctx.eps = c, eps
         ctx.set_materialize_grads(False)
-        g_vp, g_xt = torch.empty_like(vp), torch.empty_like(g_vdot)
+        g_vp, g_xt = _new(vp, *vp.shape), _new(g_vdot, *g_vdot.shape)
         _node_op(4, [g_vdot, g_xin, vp], [g_vp, g_xt], R, H, c, eps)
         return g_vp, g_xt
 
@@ -810,7 +813,7 @@ class _UpdateMidBwd(torch.autograd.Function):
     def backward(ctx, u_vp, u_xt):
         g_vdot, g_xin, vp = ctx.saved_tensors
         R, H = g_vdot.shape
-        c_a, c_b, c_vp = torch.empty_like(g_vdot), torch.empty_like(g_xin), torch.empty_like(vp)
+        c_a, c_b, c_vp = _new(g_vdot, *g_vdot.shape), _new(g_xin, *g_xin.shape), _new(vp, *vp.shape)
         _node_op(5, [_c(u_vp), _c(u_xt), g_vdot, g_xin, vp], [c_a, c_b, c_vp], R, H, ctx.c, ctx.eps)
         return c_a, c_b, c_vp, None, None
 
@@ -826,7 +829,7 @@ class UpdateOut(torch.autograd.Function):
         ctx.save_for_backward(q, vdot, vp, mask)
         ctx.s = s
         ctx.set_materialize_grads(False)
-        xo, vo = torch.empty_like(xt), torch.empty_like(vt)
+        xo, vo = _new(xt, *xt.shape), _new(vt, *vt.shape)
         _node_op(6, [q, vdot, vp, xt, vt, mask], [xo, vo], R, H, s)
         return xo, vo
 
@@ -847,9 +850,9 @@ class _UpdateOutBwd(torch.autograd.Function):
         ctx.save_for_backward(gx, gv, q, vdot, vp, mask)
         ctx.s = s
         ctx.set_materialize_grads(False)
-        g_q, g_vdot, g_vp = torch.empty_like(q), torch.empty_like(vdot), torch.empty_like(vp)
-        g_xt = torch.empty_like(gx)
-        g_vt = torch.empty(R, 3, H, dtype=gx.dtype, device=gx.device)
+        g_q, g_vdot, g_vp = _new(q, *q.shape), _new(vdot, *vdot.shape), _new(vp, *vp.shape)
+        g_xt = _new(gx, *gx.shape)
+        g_vt = _new(gx, R, 3, H)
         _node_op(7, [gx, gv, q, vdot, vp, mask], [g_q, g_vdot, g_vp, g_xt, g_vt], R, H, s)
         return g_q, g_vdot, g_vp, g_xt, g_vt
 
@@ -858,8 +861,8 @@ class _UpdateOutBwd(torch.autograd.Function):
     def backward(ctx, c_q, c_vdot, c_vp, c_xt, c_vt):
         gx, gv, q, vdot, vp, mask = ctx.saved_tensors
         R, H = gx.shape
-        d_gx, d_q, d_vdot, d_vp = torch.empty_like(gx), torch.empty_like(q), torch.empty_like(vdot), torch.empty_like(vp)
-        d_gv = torch.empty(R, 3, H, dtype=gx.dtype, device=gx.device)
+        d_gx, d_q, d_vdot, d_vp = _new(gx, *gx.shape), _new(q, *q.shape), _new(vdot, *vdot.shape), _new(vp, *vp.shape)
+        d_gv = _new(gx, R, 3, H)
         _node_op(8, [_c(c_q), _c(c_vdot), _c(c_vp), _c(c_xt), _c(c_vt), gx, gv, q, vdot, vp, mask],
                  [d_gx, d_gv, d_q, d_vdot, d_vp], R, H, ctx.s)
         return d_gx, (d_gv if gv is not None else None), d_q, d_vdot, d_vp, None, None
@@ -894,8 +897,8 @@ class EdgeMessage(torch.autograd.Function):
         from .ops import _stream
         X, R, V, U = _c(X), _c(R), _c(V), _c(U)
         E, H = X.size(0), X.size(1) // 3
-        S = torch.empty(E, H, dtype=X.dtype, device=X.device)
-        M = torch.empty(E, 3, H, dtype=X.dtype, device=X.device)
+        S = _new(X, E, H)
+        M = _new(X, E, 3, H)
         P = _lib.ptr
         _lib.check(_lib.load().hermnet_edge_message_fwd(P(X), P(R), P(V), P(U), E, H, None, None, None, P(S), P(M), _stream()),
                    "hermnet_edge_message_fwd")
@@ -920,9 +923,9 @@ class EdgeMessageGrad(torch.autograd.Function):
         E, H = X.size(0), X.size(1) // 3
         GS = torch.zeros(E, H, dtype=X.dtype, device=X.device) if GS is None else _c(GS)
         GM = torch.zeros(E, 3, H, dtype=X.dtype, device=X.device) if GM is None else _c(GM)
-        gX, gR = torch.empty_like(X), torch.empty_like(R)
-        gV = None if V is None else torch.empty_like(V)
-        gU = torch.empty_like(U)
+        gX, gR = _new(X, *X.shape), _new(R, *R.shape)
+        gV = None if V is None else _new(V, *V.shape)
+        gU = _new(U, *U.shape)
         P = _lib.ptr
         _lib.check(_lib.load().hermnet_edge_message_bwd(P(GS), P(GM), P(X), P(R), P(V), P(U), E, H, None, None, None, None,
                                                         P(gX), P(gR), P(gV), P(gU), _stream()), "hermnet_edge_message_bwd")
@@ -936,10 +939,10 @@ class EdgeMessageGrad(torch.autograd.Function):
         GS, GM, X, R, V, U = ctx.saved_tensors
         E, H = X.size(0), X.size(1) // 3
         cX, cR, cV, cU = _c(cX), _c(cR), _c(cV), _c(cU)
-        dGS, dGM = torch.empty_like(GS), torch.empty_like(GM)
-        dX, dR = torch.empty_like(X), torch.empty_like(R)
-        dV = None if V is None else torch.empty_like(V)
-        dU = torch.empty_like(U)
+        dGS, dGM = _new(GS, *GS.shape), _new(GM, *GM.shape)
+        dX, dR = _new(X, *X.shape), _new(R, *R.shape)
+        dV = None if V is None else _new(V, *V.shape)
+        dU = _new(U, *U.shape)
         P = _lib.ptr
         _lib.check(_lib.load().hermnet_edge_message_bwd2(P(cX), P(cR), P(cV), P(cU), P(GS), P(GM), P(X), P(R), P(V), P(U),
                                                          E, H, None, None, None, None, P(dGS), P(dGM), P(dX), P(dR), P(dV), P(dU),
@@ -951,7 +954,7 @@ def _segsum(x, key):
     """out[r] = sum of x[k] over the edges k of row r (`hermnet_segment_sum`: rows gathered inside the sum, list order)."""
     from .ops import _stream
     x = x.contiguous()
-    out = torch.empty((key.n_rows,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+    out = _new(x, key.n_rows, *x.shape[1:])
     P = _lib.ptr
     _lib.check(_lib.load().hermnet_segment_sum(P(x), P(key.perm), P(key.rowptr), key.n_rows, x[0].numel(), P(out), _stream()),
                "hermnet_segment_sum")
@@ -962,11 +965,11 @@ def _rows_buffer(R, r_rows, keys):
     """Buffer for a gradient of R that the edge kernels write row by row (at r_rows): rows no edge points to must read
     zero -- all of them zeroed, or only the listed padding rows (keys[4])."""
     if r_rows is None:
-        return torch.empty_like(R)
+        return _new(R, *R.shape)
     pad = keys[4] if len(keys) > 4 else None
     if pad is None:
         return torch.zeros_like(R)
-    out = torch.empty_like(R)
+    out = _new(R, *R.shape)
     if pad.numel() > 0:
         out.index_fill_(0, pad, 0.0)
     return out
@@ -994,14 +997,14 @@ class MessageAlgebra(torch.autograd.Function):
         ctx.keys = keys
         if _row_sums_inside():
             # (the sums over a target's edges stay in registers: no [E,4H] round trip through HBM)
-            dx = torch.empty(k_tgt.n_rows, H, dtype=R.dtype, device=R.device)
-            dv = torch.empty(k_tgt.n_rows, 3, H, dtype=R.dtype, device=R.device)
+            dx = _new(R, k_tgt.n_rows, H)
+            dv = _new(R, k_tgt.n_rows, 3, H)
             _lib.check(_lib.load().hermnet_edge_message_fwd_rows(
                 P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx), P(k_all.idx), P(r_rows), P(k_tgt.rowptr), P(k_tgt.perm),
                 k_tgt.n_rows, P(dx), P(dv), _stream()), "hermnet_edge_message_fwd_rows")
             return dx, dv
-        S = torch.empty(E, H, dtype=R.dtype, device=R.device)
-        M = torch.empty(E, 3, H, dtype=R.dtype, device=R.device)
+        S = _new(R, E, H)
+        M = _new(R, E, 3, H)
         _lib.check(_lib.load().hermnet_edge_message_fwd(P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx), P(k_all.idx), P(r_rows),
                                                         P(S), P(M), _stream()), "hermnet_edge_message_fwd")
         return _segsum(S, k_tgt), _segsum(M, k_tgt)
@@ -1023,21 +1026,21 @@ class MessageAlgebraGrad(torch.autograd.Function):
         g_dv = torch.zeros(k_tgt.n_rows, 3, H, dtype=R.dtype, device=R.device) if g_dv is None else _c(g_dv)
         # (R kept in another edge order with padding rows: rows no edge points to get no gradient)
         gR = _rows_buffer(R, r_rows, keys)
-        gU = torch.empty_like(U)
+        gU = _new(U, *U.shape)
         P = _lib.ptr
         ctx.save_for_backward(g_dx, g_dv, xh, vec, R, U)
         ctx.keys = keys
         if _row_sums_inside() and _groups_of_sources(k_xh, k_all):
             # groups = the (relation, source) rows of xh: gX arrives summed, gV as one partial sum per relation
             G, Ns = k_xh.n_rows, k_all.n_rows
-            gX = torch.empty(G, 3 * H, dtype=R.dtype, device=R.device)
-            gVp = None if vec is None else torch.empty(G, 3, H, dtype=R.dtype, device=R.device)
+            gX = _new(R, G, 3 * H)
+            gVp = None if vec is None else _new(R, G, 3, H)
             _lib.check(_lib.load().hermnet_edge_message_bwd_rows(
                 P(g_dx), P(g_dv), P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx), P(k_all.idx), P(k_tgt.idx), P(r_rows),
                 P(k_xh.rowptr), P(k_xh.perm), G, P(gX), P(gR), P(gVp), P(gU), _stream()), "hermnet_edge_message_bwd_rows")
             return gX, (None if vec is None else gVp.view(G // Ns, Ns, 3, H).sum(0)), gR, gU
-        gX = torch.empty(E, 3 * H, dtype=R.dtype, device=R.device)
-        gV = None if vec is None else torch.empty(E, 3, H, dtype=R.dtype, device=R.device)
+        gX = _new(R, E, 3 * H)
+        gV = None if vec is None else _new(R, E, 3, H)
         _lib.check(_lib.load().hermnet_edge_message_bwd(P(g_dx), P(g_dv), P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx),
                                                         P(k_all.idx), P(k_tgt.idx), P(r_rows), P(gX), P(gR), P(gV), P(gU),
                                                         _stream()), "hermnet_edge_message_bwd")
@@ -1050,7 +1053,7 @@ class MessageAlgebraGrad(torch.autograd.Function):
         k_tgt, k_all, k_xh, r_rows = ctx.keys[:4]
         E, H = U.size(0), R.size(1) // 3
         c_xh, c_vec, cR, cU = _c(c_xh), _c(c_vec), _c(cR), _c(cU)
-        new = lambda *shape: torch.empty(*shape, dtype=R.dtype, device=R.device)
+        new = lambda *shape: _new(R, *shape)
         dR = _rows_buffer(R, r_rows, ctx.keys)
         P = _lib.ptr
         if _row_sums_inside() and _groups_of_sources(k_xh, k_all):

@@ -590,3 +590,299 @@ class RefEdgeGeometry(torch.autograd.Function):
             b = g.batch32.long()[g.src_id.long()]
             gcell = torch.zeros(nb, 3, 3, dtype=gedge.dtype).index_add_(0, b, outer).reshape(ctx.cell_shape)
         return gp, gcell, None
+
+
+# ---------------------------------------------------------------------------------------------
+# The kernels of the TRAINING step (csrc/train_kernels.hip, train_node_kernels.hip, band_product.hip): the formulas of the
+# kernels' header comments and of include/hermnet_hip.h, written out -- no autograd inside.  tests/test_train_reference.py
+# checks each against float64 autograd of the torch expression to second order.  A cotangent that is None is zero.
+# ---------------------------------------------------------------------------------------------
+def _thirds(X):
+    H = X.shape[-1] // 3
+    return X[..., :H], X[..., H:2 * H], X[..., 2 * H:]
+
+
+def _dot3(G, W):
+    """sum_d G_d W_d over the Cartesian axis, in the kernels' order: G [E,3,H]; W [E,3] or [E,3,H]."""
+    w = (lambda d: W[:, d, None]) if W.dim() == 2 else (lambda d: W[:, d])
+    return G[:, 0] * w(0) + G[:, 1] * w(1) + G[:, 2] * w(2)
+
+
+def _z(t, like):
+    return torch.zeros_like(like) if t is None else t
+
+
+def edge_message_fwd(X, R, V, U):
+    """S = Xs Rs, M_d = (Xb Rb) U_d + V_d (Xa Ra)."""
+    (xs, xa, xb), (rs, ra, rb) = _thirds(X), _thirds(R)
+    M = (xb * rb)[:, None, :] * U[:, :, None]
+    if V is not None:
+        M = M + V * (xa * ra)[:, None, :]
+    return xs * rs, M
+
+
+def edge_message_bwd(GS, GM, X, R, V, U):
+    """(GS, GM) -> gX, gR, gV (None with V), gU."""
+    (xs, xa, xb), (rs, ra, rb) = _thirds(X), _thirds(R)
+    gB = _dot3(GM, U)
+    gXa = gRa = torch.zeros_like(xs)
+    gV = None
+    if V is not None:
+        gA, A = _dot3(GM, V), xa * ra
+        gXa, gRa, gV = gA * ra, gA * xa, GM * A[:, None, :]
+    gX = torch.cat([GS * rs, gXa, gB * rb], 1)
+    gR = torch.cat([GS * xs, gRa, gB * xb], 1)
+    return gX, gR, gV, (GM * (xb * rb)[:, None, :]).sum(2)
+
+
+def edge_message_bwd2(cX, cR, cV, cU, GS, GM, X, R, V, U):
+    """Cotangents (cX, cR, cV, cU) of edge_message_bwd's outputs -> dGS, dGM, dX, dR, dV (None with V), dU."""
+    (xs, xa, xb), (rs, ra, rb) = _thirds(X), _thirds(R)
+    (cXs, cXa, cXb), (cRs, cRa, cRb) = _thirds(_z(cX, X)), _thirds(_z(cR, R))
+    cU = _z(cU, U)
+    tB, B = cXb * rb + cRb * xb, xb * rb
+    gB, sU = _dot3(GM, U), _dot3(GM, cU)
+    dGM = tB[:, None, :] * U[:, :, None] + B[:, None, :] * cU[:, :, None]
+    dXa = dRa = torch.zeros_like(xs)
+    dV = None
+    if V is not None:
+        cV = _z(cV, V)
+        tA, A = cXa * ra + cRa * xa, xa * ra
+        gA, sV = _dot3(GM, V), _dot3(GM, cV)
+        dGM = dGM + (tA[:, None, :] * V + cV * A[:, None, :])
+        dXa, dRa, dV = cRa * gA + ra * sV, cXa * gA + xa * sV, tA[:, None, :] * GM
+    dX = torch.cat([cRs * GS, dXa, cRb * gB + rb * sU], 1)
+    dR = torch.cat([cXs * GS, dRa, cXb * gB + xb * sU], 1)
+    return cXs * rs + cRs * xs, dGM, dX, dR, dV, (GM * tB[:, None, :]).sum(2)
+
+
+def _sum_rows(x, idx, n):
+    return torch.zeros((n,) + tuple(x.shape[1:]), dtype=x.dtype).index_add_(0, idx, x)
+
+
+def _r_of_edges(R, k):
+    return R if k.r_rows is None else R.index_select(0, k.r_rows)
+
+
+def _r_rows_out(gRe, R, k):
+    """A per-edge gradient of R at the rows the edges read; rows no edge points to (padding) are zero."""
+    if k.r_rows is None:
+        return gRe
+    return torch.zeros_like(R).index_copy_(0, k.r_rows, gRe)
+
+
+def message_algebra_fwd(xh, vec, R, U, k):
+    """trainops.MessageAlgebra: x_j = xh[k.xrow], vec_j = vec[k.src], R of edge e at row k.r_rows[e]; sums per target row."""
+    V = None if vec is None else vec.index_select(0, k.src)
+    S, M = edge_message_fwd(xh.index_select(0, k.xrow), _r_of_edges(R, k), V, U)
+    return _sum_rows(S, k.tgt, k.n_tgt), _sum_rows(M, k.tgt, k.n_tgt)
+
+
+def message_algebra_bwd(g_dx, g_dv, xh, vec, R, U, k):
+    V = None if vec is None else vec.index_select(0, k.src)
+    gX, gRe, gV, gU = edge_message_bwd(g_dx.index_select(0, k.tgt), g_dv.index_select(0, k.tgt), xh.index_select(0, k.xrow),
+                                       _r_of_edges(R, k), V, U)
+    return (_sum_rows(gX, k.xrow, xh.shape[0]), None if vec is None else _sum_rows(gV, k.src, vec.shape[0]),
+            _r_rows_out(gRe, R, k), gU)
+
+
+def message_algebra_bwd2(c_xh, cR, c_vec, cU, g_dx, g_dv, xh, vec, R, U, k):
+    """-> (d g_dx, d g_dv, d xh, d vec (None with vec), dR, dU)."""
+    sel = lambda t, i: None if t is None else t.index_select(0, i)
+    V = sel(vec, k.src)
+    dGS, dGM, dX, dRe, dV, dU = edge_message_bwd2(
+        sel(c_xh, k.xrow), None if cR is None else _r_of_edges(cR, k), None if vec is None else sel(c_vec, k.src), cU,
+        g_dx.index_select(0, k.tgt), g_dv.index_select(0, k.tgt), xh.index_select(0, k.xrow), _r_of_edges(R, k), V, U)
+    return (_sum_rows(dGS, k.tgt, k.n_tgt), _sum_rows(dGM, k.tgt, k.n_tgt), _sum_rows(dX, k.xrow, xh.shape[0]),
+            None if vec is None else _sum_rows(dV, k.src, vec.shape[0]), _r_rows_out(dRe, R, k), dU)
+
+
+def segment_sum(x, idx, n_rows):
+    """hermnet_segment_sum behind trainops.SumRows: out[r] = the sum of the rows k of x with idx[k] == r."""
+    return _sum_rows(x, idx, n_rows)
+
+
+def col_sum(g):
+    """hermnet_col_sum behind trainops._col_sum_over_rows: [T,K,O] -> [T,O]."""
+    return g.sum(1)
+
+
+def edge_unit(order, D, gU=None, gd=None, C=None):
+    """hermnet_edge_unit: U = D / d, d = max(|D|, 1e-6) and its two derivatives (csrc/train_kernels.hip's header):
+    order 0 -> (U, d);  1 -> gD = (gU - U (U.gU)) / d + U gd;  2 -> (c_gU, c_gd, c_D) for the cotangent C of gD.
+    On the floor d is a constant: no projection and no distance term."""
+    n = torch.sqrt((D * D).sum(1))
+    on = n <= 1.0e-6
+    d = torch.where(on, torch.full_like(n, 1.0e-6), n)
+    U = D / d[:, None]
+    if order == 0:
+        return U, d
+    dot = lambda a, b: (a * b).sum(1)
+    gU = _z(gU, D)
+    gd = torch.where(on, torch.zeros_like(d), _z(gd, d))
+    zero = torch.zeros_like(d)
+    ug = torch.where(on, zero, dot(U, gU))
+    if order == 1:
+        return (gU - U * ug[:, None]) / d[:, None] + U * gd[:, None]
+    uc = torch.where(on, zero, dot(U, C))
+    pc, pg = C - U * uc[:, None], gU - U * ug[:, None]
+    k = dot(gU, C) - uc * ug
+    c_D = (gd[:, None] * pc - (k[:, None] * U + ug[:, None] * pc + uc[:, None] * pg) / d[:, None]) / d[:, None]
+    return pc / d[:, None], uc, torch.where(on[:, None], torch.zeros_like(c_D), c_D)
+
+
+def edge_unit_scale(order, D, gU=None, gd=None, C=None):
+    """The same expressions with every term taken in magnitude (float64): the scale a cancelling gD / c_D is judged on."""
+    D = D.double()
+    U, d = edge_unit(0, D)
+    a = lambda t: torch.zeros_like(D) if t is None else t.double().abs()
+    one = lambda t: torch.zeros_like(d) if t is None else t.double().abs()
+    Ua, inv = U.abs(), 1.0 / d
+    dot = lambda p, q: (p * q).sum(1)
+    off = (torch.sqrt((D * D).sum(1)) > 1.0e-6).double()          # on the floor c_gd and c_D are zero by definition
+    if order == 1:
+        return ((a(gU) + Ua * (off * dot(Ua, a(gU)))[:, None]) * inv[:, None] + Ua * (off * one(gd))[:, None]).amax(1)
+    ug, uc = off * dot(Ua, a(gU)), off * dot(Ua, a(C))
+    pc, pg = a(C) + Ua * uc[:, None], a(gU) + Ua * ug[:, None]
+    k = dot(a(gU), a(C)) + uc * ug
+    c_D = (one(gd)[:, None] * pc + (k[:, None] * Ua + ug[:, None] * pc + uc[:, None] * pg) * inv[:, None]) * inv[:, None]
+    return (pc * inv[:, None]).amax(1), uc, c_D.amax(1) * off
+
+
+def _sig(x):
+    return 1.0 / (1.0 + torch.exp(-x))
+
+
+def silu_bwd(gy, x):
+    s = _sig(x)
+    return gy * (s * (1.0 + x * (1.0 - s)))
+
+
+def silu_bwd2(u, gy, x):
+    """-> c_gy = u f'(x), c_x = u gy f''(x), f'' = s (1 - s) (2 + x (1 - 2 s))."""
+    s = _sig(x)
+    return u * (s * (1.0 + x * (1.0 - s))), u * gy * (s * (1.0 - s) * (2.0 + x * (1.0 - 2.0 * s)))
+
+
+def _ln_row(x, eps):
+    mu = x.mean(1, keepdim=True)
+    y = x - mu
+    r = 1.0 / torch.sqrt((y * y).mean(1, keepdim=True) + eps)
+    return y * r, r
+
+
+def ln_bwd(gy, x, eps):
+    """gx = r (gy - mean(gy) - y mean(gy y))."""
+    y, r = _ln_row(x, eps)
+    m = lambda t: t.mean(1, keepdim=True)
+    return (gy - m(gy) - y * m(gy * y)) * r
+
+
+def ln_bwd2(v, gy, x, eps):
+    """Cotangent v of gx -> c_gy = r (v - Vm - y Vy),  c_x = -r^2 [y P + b (v - Vm - y Vy) + Vy (gy - a - y b)]."""
+    y, r = _ln_row(x, eps)
+    m = lambda t: t.mean(1, keepdim=True)
+    a, b, Vm, Vy = m(gy), m(gy * y), m(v), m(v * y)
+    P = m(v * gy) - a * Vm - b * Vy
+    t = v - Vm - y * Vy
+    return t * r, (y * P + t * b + (gy - a - y * b) * Vy) * (-(r * r))
+
+
+def mid_fwd(vp, xt, c0, c1):
+    H = xt.shape[1]
+    v1, v2 = vp[..., :H], vp[..., H:]
+    return (v1 * v2).sum(1) * c0, torch.cat([xt, torch.sqrt((v2 * v2).sum(1) + c1)], 1)
+
+
+def mid_bwd(g_vdot, g_xin, vp, c0, c1):
+    H = g_vdot.shape[1]
+    v1, v2 = vp[..., :H], vp[..., H:]
+    ga, bn = (g_vdot * c0)[:, None, :], (g_xin[:, H:] / torch.sqrt((v2 * v2).sum(1) + c1))[:, None, :]
+    return torch.cat([ga * v2, ga * v1 + bn * v2], 2), g_xin[:, :H].clone()
+
+
+def mid_bwd2(u_vp, u_xt, g_vdot, g_xin, vp, c0, c1):
+    """-> c_gvdot, c_gxin = (u_xt | S / n), c_vp = (c0 a u2 | c0 a u1 + b (u2 / n - v2 S / n^3))."""
+    H = g_vdot.shape[1]
+    v1, v2 = vp[..., :H], vp[..., H:]
+    u_vp = _z(u_vp, vp)
+    u1, u2 = u_vp[..., :H], u_vp[..., H:]
+    ga, gb = (g_vdot * c0)[:, None, :], g_xin[:, H:]
+    S = (u2 * v2).sum(1)
+    rn = 1.0 / torch.sqrt((v2 * v2).sum(1) + c1)
+    bn, bs = (gb * rn)[:, None, :], (gb * S * rn * rn * rn)[:, None, :]
+    return ((u1 * v2 + u2 * v1).sum(1) * c0, torch.cat([_z(u_xt, g_vdot), S * rn], 1),
+            torch.cat([ga * u2, ga * u1 + bn * u2 - bs * v2], 2))
+
+
+def _m1(m, like):
+    return torch.ones(like.shape[0], dtype=like.dtype) if m is None else m
+
+
+def out_fwd(q, vdot, vp, xt, vt, m, c0):
+    H = xt.shape[1]
+    q1, q2, q3 = _thirds(q)
+    mm = _m1(m, xt)
+    return (xt + (q1 + q2 * vdot) * c0) * mm[:, None], (vt + q3[:, None, :] * vp[..., :H]) * mm[:, None, None]
+
+
+def out_bwd(gx, gv, q, vdot, vp, m, c0, want_xt_vt=True):
+    """-> g_q, g_vdot, g_vp = (m gv q3 | 0), g_xt = m gx, g_vt = m gv (the last two only on request: outputs nobody reads)."""
+    H = gx.shape[1]
+    q1, q2, q3 = _thirds(q)
+    mm = _m1(m, gx)
+    gx = gx * mm[:, None]
+    gv = torch.zeros(gx.shape[0], 3, H, dtype=gx.dtype) if gv is None else gv * mm[:, None, None]
+    g_q = torch.cat([gx * c0, gx * vdot * c0, (gv * vp[..., :H]).sum(1)], 1)
+    first = (g_q, gx * q2 * c0, torch.cat([gv * q3[:, None, :], torch.zeros_like(gv)], 2))
+    return first + (gx, gv) if want_xt_vt else first
+
+
+def out_bwd2(c_gq, c_gvdot, c_gvp, c_gxt, c_gvt, gx, gv, q, vdot, vp, m, c0):
+    """-> d_gx, d_gv, d_q = (0 | m gx c0 c_gvdot | m sum_d w1_d gv_d), d_vdot = m gx c0 k2, d_vp = (m gv k3 | 0)."""
+    H = gx.shape[1]
+    q1, q2, q3 = _thirds(q)
+    mm = _m1(m, gx)
+    k1, k2, k3 = _thirds(_z(c_gq, q))
+    cvd, cxt = _z(c_gvdot, gx), _z(c_gxt, gx)
+    z3 = torch.zeros(gx.shape[0], 3, H, dtype=gx.dtype)
+    w1 = z3 if c_gvp is None else c_gvp[..., :H]
+    cvt = z3 if c_gvt is None else c_gvt
+    gx = gx * mm[:, None]
+    gv = z3 if gv is None else gv * mm[:, None, None]
+    v1 = vp[..., :H]
+    d_gx = ((k1 + k2 * vdot + cvd * q2) * c0 + cxt) * mm[:, None]
+    d_gv = (k3[:, None, :] * v1 + w1 * q3[:, None, :] + cvt) * mm[:, None, None]
+    d_q = torch.cat([torch.zeros_like(gx), gx * cvd * c0, (w1 * gv).sum(1)], 1)
+    return d_gx, d_gv, d_q, gx * k2 * c0, torch.cat([gv * k3[:, None, :], z3], 2)
+
+
+def res_fwd(x, dx, v, dv, m, c0):
+    mm = _m1(m, x)
+    return (x + dx) * (mm * c0)[:, None], (dv if v is None else v + dv) * mm[:, None, None]
+
+
+def mask_scale(g1, gv1, m, c0, rows, H):
+    ref = g1 if g1 is not None else gv1
+    mm = torch.ones(rows, dtype=ref.dtype) if m is None else m
+    z1, z3 = torch.zeros(rows, H, dtype=ref.dtype), torch.zeros(rows, 3, H, dtype=ref.dtype)
+    return _z(g1, z1) * (mm * c0)[:, None], _z(gv1, z3) * mm[:, None, None]
+
+
+def band_product(A, B, bias):
+    out = torch.bmm(A, B)
+    return out if bias is None else out + bias[:, None, :]
+
+
+def band_grad_a(g1, g2, B):
+    return torch.bmm(g1 if g2 is None else g1 + g2, B.transpose(1, 2))
+
+
+def band_grad_b(A, g1, g2):
+    g = g1 if g2 is None else g1 + g2
+    return torch.bmm(A.transpose(1, 2), g), g.sum(1)
+
+
+def band_grads(A, B, g1, g2):
+    """hermnet_band_product_grads: the three gradients from one pass over g1 (+ g2)."""
+    return (band_grad_a(g1, g2, B),) + band_grad_b(A, g1, g2)
