@@ -13,6 +13,7 @@ from .sharding import HaloExchange, HaloExchangeFeatures, HaloGradReturn, SumAcr
 from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, GemmRelationalLayer, HeadWeights, LayerWeights,
                     Route, StepState)
 from .rmnet import PaiNNModule, RadialBasis, ScaledSiLU, relational_layer
+from .trainops import EdgeDiff, EdgeUnit, embedding_rows, tall_linear
 
 
 class HeteroVertexConv(nn.Module):
@@ -283,7 +284,6 @@ class HVNet(nn.Module):
         geometry kernel's hand-written backward does not provide."""
         src = graph.src_id.long()
         if pos.is_cuda and not graph.num_src and graph.csc_pos is not None:
-            from .trainops import EdgeDiff
             D = EdgeDiff.apply(pos, graph)          # (gather and its adjoint as a closed pair: no index sort, no atomics)
         else:
             D = pos[src] - pos[graph.tgt_id.long()]
@@ -291,7 +291,6 @@ class HVNet(nn.Module):
             c = cell.reshape(-1, 3, 3)
             D = D + torch.einsum("ni,nij->nj", graph.shift.to(D.dtype), c[graph.batch32.long()[src]])
         if D.is_cuda and D.dtype == torch.float32:
-            from .trainops import EdgeUnit
             U, d = EdgeUnit.apply(D)                # (one launch per order of differentiation)
             return torch.cat([U, d[:, None]], dim=1), (U, d)
         d = D.norm(dim=-1)
@@ -378,7 +377,6 @@ class HVNet(nn.Module):
         # hermnet.py:123, row order (pads: Z=0).  eval(): every parameter is a constant, the embedding included
         # (the fused layers produce no parameter gradients; a partial set would be worse than none)
         if train and pos.is_cuda:
-            from .trainops import embedding_rows
             x = embedding_rows(self.embed.weight, graph.z_rows.long())
         else:
             x = self.embed(graph.z_rows) if train else torch.nn.functional.embedding(graph.z_rows, self.embed.weight.detach())
@@ -471,7 +469,6 @@ class HVNet(nn.Module):
             return EnergyHead.apply(x.contiguous(), head.w0, head.b0, head.w2v, head.b2, mask, head)
         if train and x.is_cuda:
             # (the same nn.Sequential, its two Linears through trainops.TallBmm: weight gradients over ~2e4 rows)
-            from .trainops import tall_linear
             h_ = tall_linear(x, self.out_energy[0].weight, self.out_energy[0].bias)
             e_rows = tall_linear(self.out_energy[1](h_), self.out_energy[2].weight, self.out_energy[2].bias).squeeze(1)
         else:

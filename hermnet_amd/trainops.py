@@ -7,16 +7,20 @@ the parameters, so every op here is differentiable TWICE): the autograd function
   MessageAlgebra(Grad)        the same with node-level inputs and outputs (gathers and row sums inside)
   BucketedBasis / TallLinear  rbf_proj (rmnet.py:55) on the distance-bucketed basis / on a dense basis
   message_scatter_generic     rbf_proj + gather + message + aggregation + residual of ALL relations of a layer
-"""
-import math
-import os
 
+Every launch goes through `nodeops._call` under a timer label (the C name without `hermnet_`; for hermnet_train_node_op the
+name of the op in `NODE_OPS`), every kernel-written buffer comes from `_new`.
+"""
 import ctypes
+import math
 
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, switches
+from .nodeops import _call
+
+P = _lib.ptr
 
 
 def _new(like, *shape):
@@ -132,13 +136,10 @@ class _EdgeUnitGrad(torch.autograd.Function):
 
 
 def _edge_unit(order, D, gU, gd, C):
-    from .ops import _stream
     E = D.size(0)
     new = lambda *shape: _new(D, *shape)
     o0, o1, o2 = new(E, 3), (new(E) if order != 1 else None), (new(E, 3) if order == 2 else None)
-    P = _lib.ptr
-    _lib.check(_lib.load().hermnet_edge_unit(order, P(D), P(gU), P(gd), P(C), E, P(o0), P(o1), P(o2), _stream()),
-               "hermnet_edge_unit")
+    _call("edge_unit", "hermnet_edge_unit", order, P(D), P(gU), P(gd), P(C), E, P(o0), P(o1), P(o2))
     return o0, o1, o2
 
 
@@ -177,15 +178,12 @@ class _BasisWindowGrad(torch.autograd.Function):
 
 
 def _basis_window(order, u, src, mu, w, consts, g, cu):
-    from .ops import _stream
     num_edges, C, coeff, p = consts
     nc = mu.size(0)
-    new = lambda *shape: torch.empty(*shape, dtype=u.dtype, device=u.device)
-    out0 = new(nc * C) if order == 1 else new(nc, C, 32)
-    out1 = new(nc * C) if order == 2 else None
-    P = _lib.ptr
-    _lib.check(_lib.load().hermnet_basis_window(order, P(u), P(src), num_edges, P(mu), P(w), nc, C, coeff, p, P(g), P(cu), P(out0),
-                                                P(out1), _stream()), "hermnet_basis_window")
+    out0 = _new(u, nc * C) if order == 1 else _new(u, nc, C, 32)
+    out1 = _new(u, nc * C) if order == 2 else None
+    _call("basis_window", "hermnet_basis_window", order, P(u), P(src), num_edges, P(mu), P(w), nc, C, coeff, p, P(g), P(cu),
+          P(out0), P(out1))
     return out0, out1
 
 
@@ -350,7 +348,6 @@ class BandP(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, B, bias, side1, side2, held):
-        from .ops import _stream
         ctx.save_for_backward(B)
         ctx.side = side1 is not None
         ctx.held = held
@@ -358,8 +355,7 @@ class BandP(torch.autograd.Function):
         nc, C, N = A.size(0), A.size(1), B.size(2)
         if _band_kernels(A, N):
             out = _new(A, nc, C, N)
-            P = _lib.ptr
-            _lib.check(_lib.load().hermnet_band_product(P(A), P(B), P(bias), nc, C, N, P(out), _stream()), "hermnet_band_product")
+            _call("band_product", "hermnet_band_product", P(A), P(B), P(bias), nc, C, N, P(out))
         else:
             out = torch.bmm(A, B) if bias is None else torch.baddbmm(bias[:, None, :], A, B)
         return out, out.view_as(out)
@@ -374,13 +370,8 @@ class BandP(torch.autograd.Function):
         if ctx.side and ctx.needs_input_grad[0] and not torch.is_grad_enabled() and _band_kernels(ctx.held.t, B.size(2)):
             # the pass that differentiates the parameters (no graph is being recorded): gA and the parameter side's (gB, gbias)
             # from ONE pass over g1 (+ g2); `_BandParams.backward` picks its share up from the box it shares with this node
-            from .ops import _stream
             A, g1, g2 = ctx.held.t, _c(g1), _c(g2)
-            nc, C, N = g1.shape
-            gA, gB, gb = _new(A, nc, C, 32), _new(A, nc, 32, N), _new(A, nc, N)
-            P = _lib.ptr
-            _lib.check(_lib.load().hermnet_band_product_grads(P(A), P(B), P(g1), P(g2), nc, C, N, P(gA), P(gB), P(gb), _stream()),
-                       "hermnet_band_product_grads")
+            gA, gB, gb = _band_grads(A, B, g1, g2)
             ctx.held.ready = (g1, g2, gB, gb)
             return gA, None, None, g1, g2, None
         gA = BandQ.apply(g1, g2, B) if ctx.needs_input_grad[0] else None
@@ -422,20 +413,25 @@ def band_product(A, B, bias):
     return BandP.apply(A, B, bias, s1, s2, held)
 
 
+def _band_grads(A, B, g1, g2):
+    """(gA, gB, gbias) of `BandP` from one pass over g1 (+ g2): `hermnet_band_product_grads`."""
+    nc, C, N = g1.shape
+    gA, gB, gb = _new(A, nc, C, 32), _new(A, nc, 32, N), _new(A, nc, N)
+    _call("band_product_grads", "hermnet_band_product_grads", P(A), P(B), P(g1), P(g2), nc, C, N, P(gA), P(gB), P(gb))
+    return gA, gB, gb
+
+
 class BandQ(torch.autograd.Function):
     """(g1, g2 | None [nc,C,N], B [nc,32,N]) -> gA [nc,C,32] = (g1 + g2) B^T: `hermnet_band_product_grad_a`."""
 
     @staticmethod
     def forward(ctx, g1, g2, B):
-        from .ops import _stream
         g1, g2, B = _c(g1), _c(g2), _c(B)
         ctx.save_for_backward(g1, g2, B)
         nc, C, N = g1.shape
         if _band_kernels(B.new_empty(0, C, 32), N):
             gA = _new(g1, nc, C, 32)
-            P = _lib.ptr
-            _lib.check(_lib.load().hermnet_band_product_grad_a(P(g1), P(g2), P(B), nc, C, N, P(gA), _stream()),
-                       "hermnet_band_product_grad_a")
+            _call("band_product_grad_a", "hermnet_band_product_grad_a", P(g1), P(g2), P(B), nc, C, N, P(gA))
             return gA
         return torch.bmm(_sum2(g1, g2), B.transpose(1, 2))
 
@@ -453,15 +449,12 @@ class BandS(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, A, g1, g2):
-        from .ops import _stream
         A, g1, g2 = _c(A), _c(g1), _c(g2)
         ctx.save_for_backward(A, g1, g2)
         nc, C, N = g1.shape
         if _band_kernels(A, N):
             gB, gb = _new(A, nc, 32, N), _new(A, nc, N)
-            P = _lib.ptr
-            _lib.check(_lib.load().hermnet_band_product_grad_b(P(A), P(g1), P(g2), nc, C, N, P(gB), P(gb), _stream()),
-                       "hermnet_band_product_grad_b")
+            _call("band_product_grad_b", "hermnet_band_product_grad_b", P(A), P(g1), P(g2), nc, C, N, P(gB), P(gb))
             return gB, gb
         g = _sum2(g1, g2)
         return torch.bmm(A.transpose(1, 2), g), g.sum(1)
@@ -536,12 +529,11 @@ class _ColSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, g):
-        from .ops import _stream
         T, K, O = g.shape
         ctx.K = K
         nb = (K + _ColSum.ROWS - 1) // _ColSum.ROWS
         part = _new(g, T, nb, O)
-        _lib.check(_lib.load().hermnet_col_sum(_lib.ptr(g), T, K, O, _ColSum.ROWS, _lib.ptr(part), _stream()), "hermnet_col_sum")
+        _call("col_sum", "hermnet_col_sum", P(g), T, K, O, _ColSum.ROWS, P(part))
         return part.sum(1)
 
     @staticmethod
@@ -651,13 +643,24 @@ def tall_linear(a, weight, bias=None):
 
 
 # ---- node-level stages of the training step as one launch per order of differentiation (csrc/train_node_kernels.hip) ----
-def _node_op(op, ins, outs, rows, H, c0=0.0, c1=0.0):
-    from . import _lib
-    from .ops import _stream
-    ai = (ctypes.c_void_p * len(ins))(*[None if t is None else t.data_ptr() for t in ins])
-    ao = (ctypes.c_void_p * len(outs))(*[None if t is None else t.data_ptr() for t in outs])
-    _lib.check(_lib.load().hermnet_train_node_op(op, ai, len(ins), ao, len(outs), rows, H, c0, c1, _stream()),
-               "hermnet_train_node_op")
+# name (the kernel's, and the timer label) -> (op code, inputs, outputs) of hermnet_train_node_op
+NODE_OPS = {"silu_bwd": (1, 2, 1), "silu_bwd2": (2, 3, 2), "mid_fwd": (3, 2, 2), "mid_bwd": (4, 3, 2), "mid_bwd2": (5, 5, 3),
+            "out_fwd": (6, 6, 2), "out_bwd": (7, 6, 5), "out_bwd2": (8, 11, 5), "ln_bwd": (9, 2, 1), "ln_bwd2": (10, 3, 2),
+            "res_fwd": (11, 5, 2), "mask_scale": (12, 3, 2)}
+
+
+def _node_op(name, ins, out_shapes, rows, H, c0=0.0, c1=0.0):
+    """One node-stage launch: `ins` (None = an absent operand) -> one new buffer per shape of `out_shapes` (None = an output
+    nobody wants: the kernel gets NULL and None comes back in its place)."""
+    code, n_in, n_out = NODE_OPS[name]
+    if len(ins) != n_in or len(out_shapes) != n_out:
+        raise ValueError("%s takes %d inputs and %d outputs" % (name, n_in, n_out))
+    like = next(t for t in ins if t is not None)
+    outs = tuple(None if s is None else _new(like, *s) for s in out_shapes)
+    ai = (ctypes.c_void_p * n_in)(*[P(t) for t in ins])
+    ao = (ctypes.c_void_p * n_out)(*[P(t) for t in outs])
+    _call(name, "hermnet_train_node_op", code, ai, n_in, ao, n_out, rows, H, c0, c1)
+    return outs
 
 
 def node_kernels_ok(x):
@@ -684,17 +687,13 @@ class _SiLUBwd(torch.autograd.Function):
     def forward(ctx, gy, x):
         gy, x = _c(gy), _c(x)
         ctx.save_for_backward(gy, x)
-        gx = _new(x, *x.shape)
-        _node_op(1, [gy, x], [gx], x.numel() // 4, 4)
-        return gx
+        return _node_op("silu_bwd", [gy, x], [x.shape], x.numel() // 4, 4)[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, u):
         gy, x = ctx.saved_tensors
-        cg, cx = _new(x, *x.shape), _new(x, *x.shape)
-        _node_op(2, [_c(u), gy, x], [cg, cx], x.numel() // 4, 4)
-        return cg, cx
+        return _node_op("silu_bwd2", [_c(u), gy, x], [x.shape, x.shape], x.numel() // 4, 4)
 
 
 class LayerNorm2(torch.autograd.Function):
@@ -718,17 +717,13 @@ class _LayerNormBwd(torch.autograd.Function):
         gy, x = _c(gy), _c(x)
         ctx.save_for_backward(gy, x)
         ctx.eps = eps
-        gx = _new(x, *x.shape)
-        _node_op(9, [gy, x], [gx], x.numel() // x.size(-1), x.size(-1), eps)
-        return gx
+        return _node_op("ln_bwd", [gy, x], [x.shape], x.numel() // x.size(-1), x.size(-1), eps)[0]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, v):
         gy, x = ctx.saved_tensors
-        cg, cx = _new(x, *x.shape), _new(x, *x.shape)
-        _node_op(10, [_c(v), gy, x], [cg, cx], x.numel() // x.size(-1), x.size(-1), ctx.eps)
-        return cg, cx, None
+        return _node_op("ln_bwd2", [_c(v), gy, x], [x.shape, x.shape], x.numel() // x.size(-1), x.size(-1), ctx.eps) + (None,)
 
 
 class Residual(torch.autograd.Function):
@@ -743,9 +738,7 @@ class Residual(torch.autograd.Function):
         ctx.save_for_backward(mask)
         ctx.c, ctx.has_vec = c, vec is not None
         ctx.set_materialize_grads(False)
-        x1, v1 = _new(x, *x.shape), _new(dv, *dv.shape)
-        _node_op(11, [x, dx, vec, dv, mask], [x1, v1], R, H, c)
-        return x1, v1
+        return _node_op("res_fwd", [x, dx, vec, dv, mask], [x.shape, dv.shape], R, H, c)
 
     @staticmethod
     def backward(ctx, g1, gv1):
@@ -762,10 +755,7 @@ class _MaskScale(torch.autograd.Function):
         ctx.save_for_backward(mask)
         ctx.c = c
         ctx.set_materialize_grads(False)
-        o1 = _new(ref, R, H)
-        o2 = _new(ref, R, 3, H)
-        _node_op(12, [_c(g1), _c(gv1), mask], [o1, o2], R, H, c)
-        return o1, o2
+        return _node_op("mask_scale", [_c(g1), _c(gv1), mask], [(R, H), (R, 3, H)], R, H, c)
 
     @staticmethod
     def backward(ctx, u1, uv):
@@ -785,9 +775,7 @@ class UpdateMid(torch.autograd.Function):
         R, H = xt.shape
         ctx.save_for_backward(vp)
         ctx.c, ctx.eps = c, eps
-        vdot, xin = _new(xt, *xt.shape), _new(xt, R, 2 * H)
-        _node_op(3, [vp, xt], [vdot, xin], R, H, c, eps)
-        return vdot, xin
+        return _node_op("mid_fwd", [vp, xt], [xt.shape, (R, 2 * H)], R, H, c, eps)
 
     @staticmethod
     def backward(ctx, g_vdot, g_xin):
@@ -804,18 +792,15 @@ class _UpdateMidBwd(torch.autograd.Function):
         ctx.save_for_backward(g_vdot, g_xin, vp)
         ctx.c, ctx.eps = c, eps
         ctx.set_materialize_grads(False)
-        g_vp, g_xt = _new(vp, *vp.shape), _new(g_vdot, *g_vdot.shape)
-        _node_op(4, [g_vdot, g_xin, vp], [g_vp, g_xt], R, H, c, eps)
-        return g_vp, g_xt
+        return _node_op("mid_bwd", [g_vdot, g_xin, vp], [vp.shape, g_vdot.shape], R, H, c, eps)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, u_vp, u_xt):
         g_vdot, g_xin, vp = ctx.saved_tensors
         R, H = g_vdot.shape
-        c_a, c_b, c_vp = _new(g_vdot, *g_vdot.shape), _new(g_xin, *g_xin.shape), _new(vp, *vp.shape)
-        _node_op(5, [_c(u_vp), _c(u_xt), g_vdot, g_xin, vp], [c_a, c_b, c_vp], R, H, ctx.c, ctx.eps)
-        return c_a, c_b, c_vp, None, None
+        return _node_op("mid_bwd2", [_c(u_vp), _c(u_xt), g_vdot, g_xin, vp], [g_vdot.shape, g_xin.shape, vp.shape], R, H, ctx.c,
+                        ctx.eps) + (None, None)
 
 
 class UpdateOut(torch.autograd.Function):
@@ -829,9 +814,7 @@ class UpdateOut(torch.autograd.Function):
         ctx.save_for_backward(q, vdot, vp, mask)
         ctx.s = s
         ctx.set_materialize_grads(False)
-        xo, vo = _new(xt, *xt.shape), _new(vt, *vt.shape)
-        _node_op(6, [q, vdot, vp, xt, vt, mask], [xo, vo], R, H, s)
-        return xo, vo
+        return _node_op("out_fwd", [q, vdot, vp, xt, vt, mask], [xt.shape, vt.shape], R, H, s)
 
     @staticmethod
     def backward(ctx, gx, gv):
@@ -850,21 +833,16 @@ class _UpdateOutBwd(torch.autograd.Function):
         ctx.save_for_backward(gx, gv, q, vdot, vp, mask)
         ctx.s = s
         ctx.set_materialize_grads(False)
-        g_q, g_vdot, g_vp = _new(q, *q.shape), _new(vdot, *vdot.shape), _new(vp, *vp.shape)
-        g_xt = _new(gx, *gx.shape)
-        g_vt = _new(gx, R, 3, H)
-        _node_op(7, [gx, gv, q, vdot, vp, mask], [g_q, g_vdot, g_vp, g_xt, g_vt], R, H, s)
-        return g_q, g_vdot, g_vp, g_xt, g_vt
+        return _node_op("out_bwd", [gx, gv, q, vdot, vp, mask], [q.shape, vdot.shape, vp.shape, gx.shape, (R, 3, H)], R, H, s)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, c_q, c_vdot, c_vp, c_xt, c_vt):
         gx, gv, q, vdot, vp, mask = ctx.saved_tensors
         R, H = gx.shape
-        d_gx, d_q, d_vdot, d_vp = _new(gx, *gx.shape), _new(q, *q.shape), _new(vdot, *vdot.shape), _new(vp, *vp.shape)
-        d_gv = _new(gx, R, 3, H)
-        _node_op(8, [_c(c_q), _c(c_vdot), _c(c_vp), _c(c_xt), _c(c_vt), gx, gv, q, vdot, vp, mask],
-                 [d_gx, d_gv, d_q, d_vdot, d_vp], R, H, ctx.s)
+        d_gx, d_gv, d_q, d_vdot, d_vp = _node_op(
+            "out_bwd2", [_c(c_q), _c(c_vdot), _c(c_vp), _c(c_xt), _c(c_vt), gx, gv, q, vdot, vp, mask],
+            [gx.shape, (R, 3, H), q.shape, vdot.shape, vp.shape], R, H, ctx.s)
         return d_gx, (d_gv if gv is not None else None), d_q, d_vdot, d_vp, None, None
 
 
@@ -885,6 +863,37 @@ def _c(t):
     return None if t is None else t.contiguous()
 
 
+class EdgeKeys(object):
+    """The index side of one message-algebra call: which rows of the node-level operands each edge reads and writes.  Built
+    by `RowKeys.edge_keys` (message_scatter_generic, once per call); read by `_message_fwd / _bwd / _bwd2`."""
+
+    __slots__ = ("tgt",      # _RowKey: target row of every edge (edges sorted by it); the row sums of S, M, dGS, dGM
+                 "src",      # _RowKey: source row of every edge; gathers vec, sums gV / dV
+                 "xrow",     # _RowKey: (relation, source) row of xh.view(T Ns, 3H) of every edge; gathers xh, sums gX / dX
+                 "r_rows",   # [E] row of R of every edge (BucketedBasis.slot), or None: R in the edge order
+                 "pad")      # [n_pad] rows of R no edge points to (BucketedBasis.pad), zeroed in gR / dR; None: zero them all
+
+    def __init__(self, tgt, src, xrow, r_rows=None, pad=None):
+        self.tgt, self.src, self.xrow, self.r_rows, self.pad = tgt, src, xrow, r_rows, pad
+
+
+class RowKeys(object):
+    """The row keys of one graph for `message_scatter_generic`.  Written once per graph by `_make_row_keys` (kept in the
+    graph's `_row_keys` slot); read by message_scatter_generic alone."""
+
+    __slots__ = ("tgt",      # _RowKey: targets of the first Ek CSR edges [Nt target rows] -> EdgeKeys.tgt
+                 "src",      # _RowKey: their sources [Ns source rows] -> EdgeKeys.src
+                 "xrow",     # _RowKey: their (relation, source) rows of xh.view(T Ns, 3H) -> EdgeKeys.xrow
+                 "res",      # _RowKey: the source row each target row takes its residual from (HTNet), or None: its own
+                 "known")    # [Nt] float32 row mask: 1 on rows of a known element (hermnet.py:51)
+
+    def __init__(self, tgt, src, xrow, res, known):
+        self.tgt, self.src, self.xrow, self.res, self.known = tgt, src, xrow, res, known
+
+    def edge_keys(self, r_rows=None, pad=None):
+        return EdgeKeys(self.tgt, self.src, self.xrow, r_rows, pad)
+
+
 class EdgeMessage(torch.autograd.Function):
     """(X [E,3H], R [E,3H], V [E,3,H] | None, U [E,3]) -> (S [E,H], M [E,3,H]) on the GPU: `hermnet_edge_message_fwd`.
     The map is multilinear, so its backward (`EdgeMessageGrad`) and the backward of that are per-edge products and
@@ -893,23 +902,13 @@ class EdgeMessage(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, R, V, U):
-        from . import _lib
-        from .ops import _stream
         X, R, V, U = _c(X), _c(R), _c(V), _c(U)
-        E, H = X.size(0), X.size(1) // 3
-        S = _new(X, E, H)
-        M = _new(X, E, 3, H)
-        P = _lib.ptr
-        _lib.check(_lib.load().hermnet_edge_message_fwd(P(X), P(R), P(V), P(U), E, H, None, None, None, P(S), P(M), _stream()),
-                   "hermnet_edge_message_fwd")
         ctx.save_for_backward(X, R, V, U)
-        return S, M
+        return _message_fwd(X, R, V, U)
 
     @staticmethod
     def backward(ctx, GS, GM):
-        X, R, V, U = ctx.saved_tensors
-        gX, gR, gV, gU = EdgeMessageGrad.apply(GS, GM, X, R, V, U)
-        return gX, gR, gV, gU
+        return EdgeMessageGrad.apply(GS, GM, *ctx.saved_tensors)
 
 
 class EdgeMessageGrad(torch.autograd.Function):
@@ -918,60 +917,104 @@ class EdgeMessageGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, GS, GM, X, R, V, U):
-        from . import _lib
-        from .ops import _stream
-        E, H = X.size(0), X.size(1) // 3
-        GS = torch.zeros(E, H, dtype=X.dtype, device=X.device) if GS is None else _c(GS)
-        GM = torch.zeros(E, 3, H, dtype=X.dtype, device=X.device) if GM is None else _c(GM)
-        gX, gR = _new(X, *X.shape), _new(R, *R.shape)
-        gV = None if V is None else _new(V, *V.shape)
-        gU = _new(U, *U.shape)
-        P = _lib.ptr
-        _lib.check(_lib.load().hermnet_edge_message_bwd(P(GS), P(GM), P(X), P(R), P(V), P(U), E, H, None, None, None, None,
-                                                        P(gX), P(gR), P(gV), P(gU), _stream()), "hermnet_edge_message_bwd")
+        (GS, GM), grads = _message_bwd(GS, GM, X, R, V, U)
         ctx.save_for_backward(GS, GM, X, R, V, U)
-        return gX, gR, gV, gU
+        return grads
 
     @staticmethod
     def backward(ctx, cX, cR, cV, cU):
-        from . import _lib
-        from .ops import _stream
-        GS, GM, X, R, V, U = ctx.saved_tensors
-        E, H = X.size(0), X.size(1) // 3
-        cX, cR, cV, cU = _c(cX), _c(cR), _c(cV), _c(cU)
-        dGS, dGM = _new(GS, *GS.shape), _new(GM, *GM.shape)
-        dX, dR = _new(X, *X.shape), _new(R, *R.shape)
-        dV = None if V is None else _new(V, *V.shape)
-        dU = _new(U, *U.shape)
-        P = _lib.ptr
-        _lib.check(_lib.load().hermnet_edge_message_bwd2(P(cX), P(cR), P(cV), P(cU), P(GS), P(GM), P(X), P(R), P(V), P(U),
-                                                         E, H, None, None, None, None, P(dGS), P(dGM), P(dX), P(dR), P(dV), P(dU),
-                                                         _stream()), "hermnet_edge_message_bwd2")
-        return dGS, dGM, dX, dR, dV, dU
+        return _message_bwd2(cX, cR, cV, cU, *ctx.saved_tensors)
+
+
+# ---- the three orders of the message algebra: one launch function each ----------------------------------------------------------
+# Operands in the order (X, R, V, U) of the kernels.  keys = None: per-edge operands, NULL index arrays, per-edge results
+# (EdgeMessage).  keys = an EdgeKeys: node-level operands read through the keys, node-level results -- summed inside the
+# `_rows` kernels (switches.train_row_sums) or by `_segsum` behind the per-edge ones (MessageAlgebra).
+def _message_fwd(X, R, V, U, keys=None):
+    """-> (S, M) per edge | (dx [Nt,H], dv [Nt,3,H])."""
+    E, H = U.size(0), R.size(1) // 3
+    ix = (None,) * 3 if keys is None else (P(keys.xrow.idx), P(keys.src.idx), P(keys.r_rows))
+    if keys is not None and switches.train_row_sums:
+        # (the sums over a target's edges stay in registers: no [E,4H] round trip through HBM)
+        tgt = keys.tgt
+        dx, dv = _new(R, tgt.n_rows, H), _new(R, tgt.n_rows, 3, H)
+        _call("edge_message_fwd_rows", "hermnet_edge_message_fwd_rows", P(X), P(R), P(V), P(U), E, H, *ix, P(tgt.rowptr),
+              P(tgt.perm), tgt.n_rows, P(dx), P(dv))
+        return dx, dv
+    S, M = _new(R, E, H), _new(R, E, 3, H)
+    _call("edge_message_fwd", "hermnet_edge_message_fwd", P(X), P(R), P(V), P(U), E, H, *ix, P(S), P(M))
+    return (S, M) if keys is None else (_segsum(S, keys.tgt), _segsum(M, keys.tgt))
+
+
+def _message_bwd(GS, GM, X, R, V, U, keys=None):
+    """-> ((GS, GM) as the kernel read them: contiguous, an absent one as zeros), (gX, gR, gV | None, gU)."""
+    E, H = U.size(0), R.size(1) // 3
+    n = E if keys is None else keys.tgt.n_rows
+    GS = torch.zeros(n, H, dtype=R.dtype, device=R.device) if GS is None else _c(GS)
+    GM = torch.zeros(n, 3, H, dtype=R.dtype, device=R.device) if GM is None else _c(GM)
+    gR, gU = _rows_buffer(R, keys), _new(U, *U.shape)
+    ix = (None,) * 4 if keys is None else (P(keys.xrow.idx), P(keys.src.idx), P(keys.tgt.idx), P(keys.r_rows))
+    if keys is not None and switches.train_row_sums and _groups_of_sources(keys.xrow, keys.src):
+        # groups = the (relation, source) rows of xh: gX arrives summed, gV as one partial sum per relation
+        G, Ns = keys.xrow.n_rows, keys.src.n_rows
+        gX = _new(R, G, 3 * H)
+        gVp = None if V is None else _new(R, G, 3, H)
+        _call("edge_message_bwd_rows", "hermnet_edge_message_bwd_rows", P(GS), P(GM), P(X), P(R), P(V), P(U), E, H, *ix,
+              P(keys.xrow.rowptr), P(keys.xrow.perm), G, P(gX), P(gR), P(gVp), P(gU))
+        return (GS, GM), (gX, gR, (None if V is None else gVp.view(G // Ns, Ns, 3, H).sum(0)), gU)
+    gX = _new(R, E, 3 * H)
+    gV = None if V is None else _new(R, E, 3, H)
+    _call("edge_message_bwd", "hermnet_edge_message_bwd", P(GS), P(GM), P(X), P(R), P(V), P(U), E, H, *ix, P(gX), P(gR),
+          P(gV), P(gU))
+    if keys is not None:
+        gX, gV = _segsum(gX, keys.xrow), (None if V is None else _segsum(gV, keys.src))
+    return (GS, GM), (gX, gR, gV, gU)
+
+
+def _message_bwd2(cX, cR, cV, cU, GS, GM, X, R, V, U, keys=None):
+    """-> (dGS, dGM, dX, dR, dV | None, dU): the cotangents of `_message_bwd`'s inputs from those of its outputs."""
+    E, H = U.size(0), R.size(1) // 3
+    cX, cR, cV, cU = _c(cX), _c(cR), _c(cV), _c(cU)
+    new = lambda *shape: _new(R, *shape)
+    dR = _rows_buffer(R, keys)
+    dGS, dGM, dU = new(E, H), new(E, 3, H), new(E, 3)
+    ix = (None,) * 4 if keys is None else (P(keys.xrow.idx), P(keys.src.idx), P(keys.tgt.idx), P(keys.r_rows))
+    ops = (P(cX), P(cR), P(cV), P(cU), P(GS), P(GM), P(X), P(R), P(V), P(U), E, H) + ix
+    if keys is not None and switches.train_row_sums and _groups_of_sources(keys.xrow, keys.src):
+        G, Ns = keys.xrow.n_rows, keys.src.n_rows
+        dX = new(G, 3 * H)
+        dVp = None if V is None else new(G, 3, H)
+        _call("edge_message_bwd2_rows", "hermnet_edge_message_bwd2_rows", *ops, P(keys.xrow.rowptr), P(keys.xrow.perm), G,
+              P(dGS), P(dGM), P(dX), P(dR), P(dVp), P(dU))
+        return (_segsum(dGS, keys.tgt), _segsum(dGM, keys.tgt), dX, dR,
+                (None if V is None else dVp.view(G // Ns, Ns, 3, H).sum(0)), dU)
+    dX = new(E, 3 * H)
+    dV = None if V is None else new(E, 3, H)
+    _call("edge_message_bwd2", "hermnet_edge_message_bwd2", *ops, P(dGS), P(dGM), P(dX), P(dR), P(dV), P(dU))
+    if keys is not None:
+        dGS, dGM, dX = _segsum(dGS, keys.tgt), _segsum(dGM, keys.tgt), _segsum(dX, keys.xrow)
+        dV = None if V is None else _segsum(dV, keys.src)
+    return dGS, dGM, dX, dR, dV, dU
 
 
 def _segsum(x, key):
     """out[r] = sum of x[k] over the edges k of row r (`hermnet_segment_sum`: rows gathered inside the sum, list order)."""
-    from .ops import _stream
     x = x.contiguous()
     out = _new(x, key.n_rows, *x.shape[1:])
-    P = _lib.ptr
-    _lib.check(_lib.load().hermnet_segment_sum(P(x), P(key.perm), P(key.rowptr), key.n_rows, x[0].numel(), P(out), _stream()),
-               "hermnet_segment_sum")
+    _call("segment_sum", "hermnet_segment_sum", P(x), P(key.perm), P(key.rowptr), key.n_rows, x[0].numel(), P(out))
     return out
 
 
-def _rows_buffer(R, r_rows, keys):
-    """Buffer for a gradient of R that the edge kernels write row by row (at r_rows): rows no edge points to must read
-    zero -- all of them zeroed, or only the listed padding rows (keys[4])."""
-    if r_rows is None:
+def _rows_buffer(R, keys):
+    """Buffer for a gradient of R that the edge kernels write row by row (at keys.r_rows): rows no edge points to must read
+    zero -- all of them zeroed, or only the listed padding rows (keys.pad)."""
+    if keys is None or keys.r_rows is None:
         return _new(R, *R.shape)
-    pad = keys[4] if len(keys) > 4 else None
-    if pad is None:
+    if keys.pad is None:
         return torch.zeros_like(R)
     out = _new(R, *R.shape)
-    if pad.numel() > 0:
-        out.index_fill_(0, pad, 0.0)
+    if keys.pad.numel() > 0:
+        out.index_fill_(0, keys.pad, 0.0)
     return out
 
 
@@ -981,33 +1024,16 @@ class MessageAlgebra(torch.autograd.Function):
     `EdgeMessage` read their gathered operands through row indices (x_j = xh[(relation, source)], vec_j = vec[source],
     cotangents = g[target]) and the row sums follow inside the function, so no [E, 3H] copy of a gathered operand and
     no per-edge gradient ever enters the autograd graph: what two graph nodes share and the engine has to add up is
-    node-sized.  Twice differentiable through `MessageAlgebraGrad`.  keys = (targets, sources, (relation, source), rows
-    of R or None, padding rows of R or None)."""
+    node-sized.  Twice differentiable through `MessageAlgebraGrad`.  keys: an `EdgeKeys`."""
 
     @staticmethod
     def forward(ctx, xh, vec, R, U, keys, R2=None):
-        from .ops import _stream
-        k_tgt, k_all, k_xh, r_rows = keys[:4]
         xh, vec, R, U = _c(xh), _c(vec), _c(R), _c(U)
-        E, H = U.size(0), R.size(1) // 3
-        P = _lib.ptr
         # R2: the same values as R under a second autograd identity (BandP's second output) -- the backward below is R's
         # second consumer in the graph and differentiates through R2, so that R's two gradients are not summed by the engine
         ctx.save_for_backward(xh, vec, R if R2 is None else R2, U)
         ctx.keys = keys
-        if _row_sums_inside():
-            # (the sums over a target's edges stay in registers: no [E,4H] round trip through HBM)
-            dx = _new(R, k_tgt.n_rows, H)
-            dv = _new(R, k_tgt.n_rows, 3, H)
-            _lib.check(_lib.load().hermnet_edge_message_fwd_rows(
-                P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx), P(k_all.idx), P(r_rows), P(k_tgt.rowptr), P(k_tgt.perm),
-                k_tgt.n_rows, P(dx), P(dv), _stream()), "hermnet_edge_message_fwd_rows")
-            return dx, dv
-        S = _new(R, E, H)
-        M = _new(R, E, 3, H)
-        _lib.check(_lib.load().hermnet_edge_message_fwd(P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx), P(k_all.idx), P(r_rows),
-                                                        P(S), P(M), _stream()), "hermnet_edge_message_fwd")
-        return _segsum(S, k_tgt), _segsum(M, k_tgt)
+        return _message_fwd(xh, R, vec, U, keys)
 
     @staticmethod
     def backward(ctx, g_dx, g_dv):
@@ -1019,66 +1045,16 @@ class MessageAlgebra(torch.autograd.Function):
 class MessageAlgebraGrad(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g_dx, g_dv, xh, vec, R, U, keys):
-        from .ops import _stream
-        k_tgt, k_all, k_xh, r_rows = keys[:4]
-        E, H = U.size(0), R.size(1) // 3
-        g_dx = torch.zeros(k_tgt.n_rows, H, dtype=R.dtype, device=R.device) if g_dx is None else _c(g_dx)
-        g_dv = torch.zeros(k_tgt.n_rows, 3, H, dtype=R.dtype, device=R.device) if g_dv is None else _c(g_dv)
-        # (R kept in another edge order with padding rows: rows no edge points to get no gradient)
-        gR = _rows_buffer(R, r_rows, keys)
-        gU = _new(U, *U.shape)
-        P = _lib.ptr
+        (g_dx, g_dv), (g_xh, gR, g_vec, gU) = _message_bwd(g_dx, g_dv, xh, R, vec, U, keys)
         ctx.save_for_backward(g_dx, g_dv, xh, vec, R, U)
         ctx.keys = keys
-        if _row_sums_inside() and _groups_of_sources(k_xh, k_all):
-            # groups = the (relation, source) rows of xh: gX arrives summed, gV as one partial sum per relation
-            G, Ns = k_xh.n_rows, k_all.n_rows
-            gX = _new(R, G, 3 * H)
-            gVp = None if vec is None else _new(R, G, 3, H)
-            _lib.check(_lib.load().hermnet_edge_message_bwd_rows(
-                P(g_dx), P(g_dv), P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx), P(k_all.idx), P(k_tgt.idx), P(r_rows),
-                P(k_xh.rowptr), P(k_xh.perm), G, P(gX), P(gR), P(gVp), P(gU), _stream()), "hermnet_edge_message_bwd_rows")
-            return gX, (None if vec is None else gVp.view(G // Ns, Ns, 3, H).sum(0)), gR, gU
-        gX = _new(R, E, 3 * H)
-        gV = None if vec is None else _new(R, E, 3, H)
-        _lib.check(_lib.load().hermnet_edge_message_bwd(P(g_dx), P(g_dv), P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx),
-                                                        P(k_all.idx), P(k_tgt.idx), P(r_rows), P(gX), P(gR), P(gV), P(gU),
-                                                        _stream()), "hermnet_edge_message_bwd")
-        return _segsum(gX, k_xh), (None if vec is None else _segsum(gV, k_all)), gR, gU
+        return g_xh, g_vec, gR, gU
 
     @staticmethod
     def backward(ctx, c_xh, c_vec, cR, cU):
-        from .ops import _stream
         g_dx, g_dv, xh, vec, R, U = ctx.saved_tensors
-        k_tgt, k_all, k_xh, r_rows = ctx.keys[:4]
-        E, H = U.size(0), R.size(1) // 3
-        c_xh, c_vec, cR, cU = _c(c_xh), _c(c_vec), _c(cR), _c(cU)
-        new = lambda *shape: _new(R, *shape)
-        dR = _rows_buffer(R, r_rows, ctx.keys)
-        P = _lib.ptr
-        if _row_sums_inside() and _groups_of_sources(k_xh, k_all):
-            G, Ns = k_xh.n_rows, k_all.n_rows
-            dGS, dGM, dX, dU = new(E, H), new(E, 3, H), new(G, 3 * H), new(E, 3)
-            dVp = None if vec is None else new(G, 3, H)
-            _lib.check(_lib.load().hermnet_edge_message_bwd2_rows(
-                P(c_xh), P(cR), P(c_vec), P(cU), P(g_dx), P(g_dv), P(xh), P(R), P(vec), P(U), E, H, P(k_xh.idx), P(k_all.idx),
-                P(k_tgt.idx), P(r_rows), P(k_xh.rowptr), P(k_xh.perm), G, P(dGS), P(dGM), P(dX), P(dR), P(dVp), P(dU),
-                _stream()), "hermnet_edge_message_bwd2_rows")
-            return (_segsum(dGS, k_tgt), _segsum(dGM, k_tgt), dX, (None if vec is None else dVp.view(G // Ns, Ns, 3, H).sum(0)),
-                    dR, dU, None)
-        dGS, dGM, dX, dU = new(E, H), new(E, 3, H), new(E, 3 * H), new(E, 3)
-        dV = None if vec is None else new(E, 3, H)
-        _lib.check(_lib.load().hermnet_edge_message_bwd2(P(c_xh), P(cR), P(c_vec), P(cU), P(g_dx), P(g_dv), P(xh), P(R), P(vec),
-                                                         P(U), E, H, P(k_xh.idx), P(k_all.idx), P(k_tgt.idx), P(r_rows), P(dGS),
-                                                         P(dGM), P(dX), P(dR), P(dV), P(dU), _stream()),
-                   "hermnet_edge_message_bwd2")
-        return (_segsum(dGS, k_tgt), _segsum(dGM, k_tgt), _segsum(dX, k_xh), (None if vec is None else _segsum(dV, k_all)),
-                dR, dU, None)
-
-
-def _row_sums_inside():
-    from . import switches
-    return switches.train_row_sums
+        d_gdx, d_gdv, d_xh, dR, d_vec, dU = _message_bwd2(c_xh, cR, c_vec, cU, g_dx, g_dv, xh, R, vec, U, ctx.keys)
+        return d_gdx, d_gdv, d_xh, d_vec, dR, dU, None
 
 
 def _groups_of_sources(k_xh, k_all):
@@ -1104,10 +1080,9 @@ def _run_lengths(sorted_keys, n):
 
 
 def _row_keys(graph, T, Nt, Ns, Ek):
-    """(key of the targets of the first Ek CSR edges [Nt target rows], key of their sources [Ns source rows], key of
-    their (relation, source) rows of xh.view(T Ns, 3H), key of the residual rows or None) for `message_scatter_generic`,
-    from the graph's CSR / CSC orders; built once per graph.  Nt = Ns for HVNet; HTNet has one target row per atom and
-    pair relation and reads the residual from the atom's own source row (`graph.res_row`)."""
+    """The `RowKeys` of `message_scatter_generic` from the graph's CSR / CSC orders; built once per graph.  Nt = Ns for
+    HVNet; HTNet has one target row per atom and pair relation and reads the residual from the atom's own source row
+    (`graph.res_row`)."""
     return graph.derived("row_keys", lambda: _make_row_keys(graph, T, Nt, Ns, Ek))
 
 
@@ -1136,7 +1111,7 @@ def _make_row_keys(graph, T, Nt, Ns, Ek):
         k_res = _RowKey(res, order_r, _run_lengths(res.index_select(0, order_r), Ns), Ns)
     # rows of a known element (the others stay zero, hermnet.py:51): once per graph, not once per layer
     known = torch.arange(Nt, device=dev) < graph.type_rowptr[T:T + 1].long()
-    return k_tgt, k_all, k_xh, k_res, known.to(torch.float32)
+    return RowKeys(k_tgt, k_all, k_xh, k_res, known.to(torch.float32))
 
 
 _SCALE = {}
@@ -1167,8 +1142,8 @@ def message_scatter_generic(xh, vec, x, edge, edge_embed, w_rbf, b_rbf, graph):
     bucketed = isinstance(edge_embed, BucketedBasis)
     bounds = None if bucketed else graph.rel_edge_bounds()     # (per relation: the materialised-basis route only)
     Ek = graph.rel_edge_total()                                # edges whose target has a known element
-    k_tgt, k_all, k_xh, k_res, known = _row_keys(graph, T, N, Ns, Ek)
-    known = known.to(x.dtype)
+    rk = _row_keys(graph, T, N, Ns, Ek)
+    k_res, known = rk.res, rk.known.to(x.dtype)
     # the constant factors of the vector message (1/sqrt(3H) on the `a` part, 1/sqrt(H) on `b`, rmnet.py:64-66) ride on
     # the [3H, R] projection weights, not on per-edge tensors
     sc = _message_scale(H, x)
@@ -1178,7 +1153,7 @@ def message_scatter_generic(xh, vec, x, edge, edge_embed, w_rbf, b_rbf, graph):
         if Ek > 0:     # rbf_proj (rmnet.py:55) as one batched product on the bucketed basis; R stays in its sorted order
             R, R2 = edge_embed.project(w_rbf, b_rbf, sc)
             dx, dv = MessageAlgebra.apply(xh.reshape(T * Ns, 3 * H), vec, R, edge_embed.unit_vectors(edge, Ek),
-                                          (k_tgt, k_all, k_xh, edge_embed.slot, edge_embed.pad), R2)
+                                          rk.edge_keys(edge_embed.slot, edge_embed.pad), R2)
     else:
         # (split, not slices: the backward of a split is ONE cat, a slice's zero-fills the whole [E,R] gradient)
         emb = edge_embed.split([bounds[t + 1] - bounds[t] for t in range(T)] + [edge_embed.size(0) - Ek])
@@ -1191,13 +1166,13 @@ def message_scatter_generic(xh, vec, x, edge, edge_embed, w_rbf, b_rbf, graph):
         if _train_kernels(R):
             # gather x_j / vec_j (rmnet.py:58), x_j * rbfh and the vector message (:61-66), aggregation (:69-73): one
             # twice-differentiable function with node-level inputs and outputs (csrc/train_kernels.hip)
-            dx, dv = MessageAlgebra.apply(xh.reshape(T * Ns, 3 * H), vec, R, edge[:Ek, :3], (k_tgt, k_all, k_xh, None, None))
+            dx, dv = MessageAlgebra.apply(xh.reshape(T * Ns, 3 * H), vec, R, edge[:Ek, :3], rk.edge_keys())
         else:
-            X = GatherRows.apply(xh.reshape(T * Ns, 3 * H), k_xh)                  # x_j of every edge, rmnet.py:58
-            V = None if vec is None else GatherRows.apply(vec, k_all)
+            X = GatherRows.apply(xh.reshape(T * Ns, 3 * H), rk.xrow)               # x_j of every edge, rmnet.py:58
+            V = None if vec is None else GatherRows.apply(vec, rk.src)
             S, M = edge_message(X, R, V, edge[:Ek, :3])
-            dx = SumRows.apply(S, k_tgt)
-            dv = SumRows.apply(M, k_tgt)
+            dx = SumRows.apply(S, rk.tgt)
+            dv = SumRows.apply(M, rk.tgt)
     if dx is None:                                             # no edge into a known element
         dx, dv = x.new_zeros(N, H), x.new_zeros(N, 3, H)
     # the residual (rmnet.py:24-26) reads the target atom's own row: the same row for HVNet, `res_row` for HTNet

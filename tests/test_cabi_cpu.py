@@ -273,6 +273,27 @@ def test_argument_checks_of_the_round_4_entry_points_need_no_gpu():
                                        None, None) == HN_OK                                                 # no rows
 
 
+def test_node_op_table_of_the_package_equals_the_operand_counts_the_library_checks():
+    """trainops.NODE_OPS (name -> code, inputs, outputs) against hermnet_train_node_op itself, which checks the counts before
+    any launch: with no rows the table's counts are accepted for every op, one input more or one output more is refused.
+    Exactly the codes 1 .. 12, under the kernel names of csrc/train_node_kernels.hip."""
+    from hermnet_amd import trainops
+    lib = _lib.load()
+    HN_OK, HN_ERR_BAD_ARG = 0, 1
+    ptr = np.zeros(64, dtype=np.float32).ctypes.data
+    arr = lambda n: (ctypes.c_void_p * n)(*([ptr] * n))
+    table = trainops.NODE_OPS
+    assert sorted(code for code, _, _ in table.values()) == list(range(1, 13))
+    assert list(table) == ["silu_bwd", "silu_bwd2", "mid_fwd", "mid_bwd", "mid_bwd2", "out_fwd", "out_bwd", "out_bwd2", "ln_bwd",
+                           "ln_bwd2", "res_fwd", "mask_scale"]
+    src = open(os.path.join(ROOT, "hermnet_amd", "csrc", "train_node_kernels.hip")).read()
+    for name, (code, ni, no) in table.items():
+        assert re.search(r"case %d: hipLaunchKernelGGL\(%s_kernel," % (code, name), src) or (code == 10 and "default: hipLaunchKernelGGL(ln_bwd2_kernel," in src), name
+        call = lambda n_in, n_out: lib.hermnet_train_node_op(code, arr(n_in + 1), n_in, arr(n_out + 1), n_out, 0, 128, 0.0, 0.0, None)
+        assert call(ni, no) == HN_OK, name
+        assert call(ni + 1, no) == HN_ERR_BAD_ARG and call(ni, no + 1) == HN_ERR_BAD_ARG, name
+
+
 def test_argument_checks_of_the_projected_halo_entry_points_need_no_gpu():
     """hermnet_halo_proj_rows / hermnet_halo_proj_accumulate (ABI v12): malformed calls are refused before a launch, an empty
     row list is done."""

@@ -1057,8 +1057,8 @@ def test_message_algebra_node_level_matches_autograd_to_second_order(E, N, T, H,
     def keys(device):
         mk = lambda idx, perm, n: trainops._RowKey(idx.to(device), None if perm is None else perm.to(device),
                                                 torch.bincount(idx, minlength=n).to(device), n)
-        return (mk(tgt, None, N), mk(src, torch.argsort(src, stable=True), N), mk(xrow, torch.argsort(xrow, stable=True), T * N),
-                None)
+        return trainops.EdgeKeys(mk(tgt, None, N), mk(src, torch.argsort(src, stable=True), N),
+                                 mk(xrow, torch.argsort(xrow, stable=True), T * N))
 
     base = dict(xh=rnd(T * N, 3 * H), vec=rnd(N, 3, H) if has_v else None, R=rnd(E, 3 * H), U=rnd(E, 3),
                 wx=rnd(N, H), wv=rnd(N, 3, H))

@@ -414,6 +414,37 @@ def test_width_not_multiple_of_64_runs_on_zero_padded_channels(H, monkeypatch):
     assert rel_err(e.detach(), e_ref) < 5e-6 and rel_err(f, f_ref) < 1e-5
 
 
+def test_message_scatter_on_host_tensors_equals_its_recorded_results_and_keys_are_declared():
+    """trainops.message_scatter_generic on host tensors (the torch route, reading the graph's `RowKeys` by name) gives, to the
+    last bit, what it gave before the keys were declared objects (tests/golden/message_scatter_host.npz: 12 atoms, three
+    elements, one without atoms, H = 8, float64; recorded by tests/golden/gen_message_scatter_host.py), with and without vec.
+    `RowKeys` / `EdgeKeys` are read by field name only: no positional index, no stray attribute."""
+    import os
+    from hermnet_amd import trainops
+    ref = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "message_scatter_host.npz"))
+    t = {k: torch.from_numpy(ref[k]) for k in ("z", "edge_index", "xh", "vec", "x", "edge", "edge_embed", "w_rbf", "b_rbf")}
+    assert t["z"].numel() == 12 and t["x"].dtype == torch.float64 and t["x"].size(1) == 8
+    g = RelationalGraph.build(t["z"], t["edge_index"], [13, 28, 29])
+    assert g.T == 3 and not bool((t["z"] == 28).any())
+    for with_vec in (0, 1):
+        x1, vec1 = trainops.message_scatter_generic(t["xh"], t["vec"] if with_vec else None, t["x"], t["edge"], t["edge_embed"],
+                                                    list(t["w_rbf"]), list(t["b_rbf"]), g)
+        assert np.array_equal(x1.numpy(), ref["x1_vec%d" % with_vec]) and np.array_equal(vec1.numpy(), ref["vec1_vec%d" % with_vec])
+        assert float(x1.abs().sum()) > 0 and float(vec1.abs().sum()) > 0
+    rk = g._row_keys[1]                                    # (the graph's declared slot: relations.RelationalGraph._DERIVED)
+    assert isinstance(rk, trainops.RowKeys) and rk.res is None and rk.known.dtype == torch.float32
+    slot, pad = torch.arange(g.rel_edge_total()), torch.zeros(0, dtype=torch.long)
+    ek = rk.edge_keys(slot, pad)
+    assert isinstance(ek, trainops.EdgeKeys) and ek.tgt is rk.tgt and ek.src is rk.src and ek.xrow is rk.xrow
+    assert ek.r_rows is slot and ek.pad is pad and rk.edge_keys().r_rows is None and rk.edge_keys().pad is None
+    for keys in (rk, ek):
+        assert not hasattr(type(keys), "__getitem__") and not hasattr(type(keys), "__len__") and not hasattr(type(keys), "__iter__")
+        with pytest.raises(TypeError):
+            keys[0]
+        with pytest.raises(AttributeError):
+            keys.rows = None
+
+
 def _layer_weights_and_graph(H, T, counts, seed=0, unknown=3, uniform=None):
     """LayerWeights of T randomly initialised PaiNNModules + a relation-ordered graph with `counts[t]` atoms per element."""
     import hermnet_amd as hn

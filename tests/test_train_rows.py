@@ -8,14 +8,16 @@ defines as zero exactly zero.  Every buffer a kernel writes is NaN-filled before
 hermnet_amd.trainops allocate through `trainops._new`, which is replaced here (`kernels`); the same replacement records the
 shapes, which is how the routes are asserted (kernel taken, row sums inside or behind the kernel).
 
-The kernels are reached through the static forward / backward of trainops' autograd functions, run as plain functions on a
-stand-in ctx: that hands a kernel the NULL operands the autograd engine would materialise as zeros.
+The kernels are reached through trainops' plain launch functions where one exists (the three orders of the message algebra,
+`_node_op` by name, `_edge_unit`, `_basis_window`, `_band_grads`), else through the static forward / backward of its autograd
+functions, run as plain functions on a stand-in ctx: both hand a kernel the NULL operands the autograd engine would
+materialise as zeros.
 
 Measured on the MI355X: see each test's docstring and profiles/train_row_margin.md."""
 import pytest
 import torch
 
-from hermnet_amd import _lib, switches, trainops
+from hermnet_amd import switches, trainops
 import test_train_reference as tr
 from test_train_reference import CAP, OPERAND_SETS
 
@@ -53,13 +55,13 @@ class KernelOps(object):
 
     # ---- the message algebra
     def edge_message_fwd(self, X, R, V, U):
-        return trainops.EdgeMessage.forward(_Ctx(), X, R, V, U)
+        return trainops._message_fwd(X, R, V, U)
 
     def edge_message_bwd(self, GS, GM, X, R, V, U):
-        return trainops.EdgeMessageGrad.forward(_Ctx(), GS, GM, X, R, V, U)
+        return trainops._message_bwd(GS, GM, X, R, V, U)[1]
 
     def edge_message_bwd2(self, cX, cR, cV, cU, GS, GM, X, R, V, U):
-        return trainops.EdgeMessageGrad.backward(_Ctx((GS, GM, X, R, V, U)), cX, cR, cV, cU)
+        return trainops._message_bwd2(cX, cR, cV, cU, GS, GM, X, R, V, U)
 
     def keys(self, k):
         if id(k) not in self._keys:
@@ -70,27 +72,27 @@ class KernelOps(object):
                 return trainops._RowKey(d(idx), d(perm), d(torch.bincount(idx, minlength=n)), n)
 
             assert bool((k.tgt[1:] >= k.tgt[:-1]).all())
-            self._keys[id(k)] = (k, (key(k.tgt, k.n_tgt, False), key(k.src, k.n_src, True), key(k.xrow, k.T * k.n_src, True),
-                                     d(k.r_rows), d(k.pad)))
+            self._keys[id(k)] = (k, trainops.EdgeKeys(key(k.tgt, k.n_tgt, False), key(k.src, k.n_src, True),
+                                                      key(k.xrow, k.T * k.n_src, True), d(k.r_rows), d(k.pad)))
         return self._keys[id(k)][1]
 
     def message_algebra_fwd(self, xh, vec, R, U, k):
         assert switches.train_row_sums == self.row_sums
         mark = len(self.log)
-        out = trainops.MessageAlgebra.forward(_Ctx(), xh, vec, R, U, self.keys(k))
+        out = trainops._message_fwd(xh, R, vec, U, self.keys(k))
         assert len(self._since(mark)) == (2 if self.row_sums else 4), self._since(mark)      # (dx, dv) | (S, M) + two row sums
         return out
 
     def message_algebra_bwd(self, g_dx, g_dv, xh, vec, R, U, k):
         mark = len(self.log)
-        out = trainops.MessageAlgebraGrad.forward(_Ctx(), g_dx, g_dv, xh, vec, R, U, self.keys(k))
+        g_xh, gR, g_vec, gU = trainops._message_bwd(g_dx, g_dv, xh, R, vec, U, self.keys(k))[1]
         extra = 0 if vec is None else 1
         assert len(self._since(mark)) == (3 + extra if self.row_sums else 4 + 2 * extra), self._since(mark)
-        return out
+        return g_xh, g_vec, gR, gU
 
     def message_algebra_bwd2(self, c_xh, cR, c_vec, cU, g_dx, g_dv, xh, vec, R, U, k):
-        ctx = _Ctx((g_dx, g_dv, xh, vec, R, U), keys=self.keys(k))
-        return trainops.MessageAlgebraGrad.backward(ctx, c_xh, c_vec, cR, cU)[:6]
+        d_gdx, d_gdv, d_xh, dR, d_vec, dU = trainops._message_bwd2(c_xh, cR, c_vec, cU, g_dx, g_dv, xh, R, vec, U, self.keys(k))
+        return d_gdx, d_gdv, d_xh, d_vec, dR, dU
 
     # ---- sums
     def segment_sum(self, x, idx, n_rows):
@@ -141,9 +143,8 @@ class KernelOps(object):
     def out_bwd(self, gx, gv, q, vdot, vp, m, c0, want_xt_vt=True):
         if want_xt_vt:
             return trainops._UpdateOutBwd.forward(_Ctx(), gx, gv, q, vdot, vp, m, c0)
-        outs = [trainops._new(q, *q.shape), trainops._new(vdot, *vdot.shape), trainops._new(vp, *vp.shape)]
-        trainops._node_op(7, [gx, gv, q, vdot, vp, m], outs + [None, None], gx.size(0), gx.size(1), c0)
-        return tuple(outs)
+        return trainops._node_op("out_bwd", [gx, gv, q, vdot, vp, m], [q.shape, vdot.shape, vp.shape, None, None], gx.size(0),
+                                 gx.size(1), c0)[:3]
 
     def out_bwd2(self, c_gq, c_gvdot, c_gvp, c_gxt, c_gvt, gx, gv, q, vdot, vp, m, c0):
         return trainops._UpdateOutBwd.backward(_Ctx((gx, gv, q, vdot, vp, m), s=c0), c_gq, c_gvdot, c_gvp, c_gxt, c_gvt)[:5]
@@ -172,13 +173,7 @@ class KernelOps(object):
         return out
 
     def band_grads(self, A, B, g1, g2):
-        from hermnet_amd.ops import _stream
-        nc, C, N = g1.shape
-        gA, gB, gb = trainops._new(A, nc, C, 32), trainops._new(A, nc, 32, N), trainops._new(A, nc, N)
-        P = _lib.ptr
-        _lib.check(_lib.load().hermnet_band_product_grads(P(A), P(B), P(g1), P(g2), nc, C, N, P(gA), P(gB), P(gb), _stream()),
-                   "hermnet_band_product_grads")
-        return gA, gB, gb
+        return trainops._band_grads(A, B, g1, g2)
 
 
 @pytest.fixture
@@ -277,6 +272,38 @@ def test_edge_unit_kernel_edge_by_edge(E, kernels):
     lengths 1e-3 .. 1e4, gU nearly parallel to U; gD, c_gU, c_gd and c_D on the scale of their terms' magnitudes.
     Measured on the MI355X, worst err / bound: 0.07 (plain), 0.05 (adversarial)."""
     _run_case(("unit", E), kernels)
+
+
+def test_basis_window_writes_every_row_of_its_outputs(kernels):
+    """hermnet_basis_window, orders 0, 1, 2, on NaN-filled outputs (tests/ref_ops.py has no restatement of it, so no row rule):
+    two chunks of 16 rows, one padding row (src == num_edges) and one distance beyond the cutoff -- rows the kernel must
+    write as zeros, not skip.  Every output comes from `trainops._new` (the shapes in the log) and holds no NaN afterwards;
+    the two dead rows are exactly zero in all of them."""
+    dev, nc, C = kernels.dev, 2, 16
+    gen = torch.Generator().manual_seed(11)
+    rows = nc * C
+    u = torch.sort(0.05 + 0.9 * torch.rand(rows, generator=gen)).values
+    u[-1] = 1.25                                            # beyond the cutoff
+    src = torch.arange(rows)
+    src[5] = rows                                           # row 5 holds no edge (num_edges = rows)
+    dead = torch.tensor([5, rows - 1])
+    mu = (torch.linspace(0.0, 1.0, 32)[None, :] + torch.tensor([0.0, 0.02])[:, None]).contiguous()
+    w = torch.ones(nc, 32)
+    w[1, :3] = 0.0                                          # centres outside the basis
+    g, cu = torch.randn(nc, C, 32, generator=gen), torch.randn(rows, generator=gen)
+    u, src, mu, w, g, cu = (t.to(dev) for t in (u, src, mu, w, g, cu))
+    consts = (rows, C, -50.0, 5)
+    mark = len(kernels.log)
+    phi = trainops._basis_window(0, u, src, mu, w, consts, None, None)[0]
+    g_u = trainops._basis_window(1, u, src, mu, w, consts, g, None)[0]
+    d_g, d_u = trainops._basis_window(2, u, src, mu, w, consts, g, cu)
+    torch.cuda.synchronize()
+    assert kernels.log[mark:] == [(nc, C, 32), (rows,), (nc, C, 32), (rows,)]
+    for nm, out in (("phi", phi), ("g_u", g_u), ("d_g", d_g), ("d_u", d_u)):
+        out = out.reshape(rows, -1).cpu()
+        assert not bool(torch.isnan(out).any()), nm
+        assert not bool(out[dead].any()), nm
+    assert bool((phi.reshape(rows, 32).cpu()[4] > 0).all()) and not bool(phi.cpu()[1, :, :3].any())
 
 
 @pytest.mark.parametrize("case", [("band",) + s for s in tr.BAND_CASES], ids=tr.case_id)

@@ -280,3 +280,74 @@ def test_training_step_matches_fp64_oracle(name, loss, routes):
     tol = max(GRAD_TOL, 2 * d32)
     worst = assert_grads_close({k: v for k, v in grads.items() if k not in absent}, ref, tol=tol)
     print("%-22s %-6s worst %.2e  d32 %.2e  tol %.2e  worst/tol %.2f" % (name, loss, worst, d32, tol, worst / tol))
+
+
+class _Labels(object):
+    """ops.set_kernel_timer hook that records the label of every library launch."""
+
+    def __init__(self):
+        self.names = []
+
+    def launch(self, name, fn):
+        self.names.append(name)
+        return fn()
+
+
+def test_training_step_launches_through_the_one_labelled_path(monkeypatch):
+    """Every launch of hermnet_amd.trainops goes through `nodeops._call` under a timer label: the C name without `hermnet_`,
+    for hermnet_train_node_op the op's name in `trainops.NODE_OPS`.  One full step (forward, autograd.grad(E, pos,
+    create_graph=True), loss.backward()) on 256 atoms of three elements in the uniform row layout, Gaussian basis, two layers
+    (vec is None in layer 0 and present in layer 1), H the smallest multiple of 4 whose band product the library supports --
+    asked of hermnet_band_product_supported at the chunk length the step uses (BucketedBasis.CHUNK; at 16 rows per chunk
+    it supports no width: chunks are multiples of 32 rows).  256 atoms: the column-sum kernel takes 256 rows or more.
+    The step reaches all twelve node-stage ops (SiLU2, LayerNorm2, UpdateMid, UpdateOut each to second order, Residual and its
+    backward), so none is exempt.  With switches.train_row_sums off the same step records the per-edge message kernels in
+    place of the `_rows` ones and gives the same energy, forces and parameter gradients within the training tolerance."""
+    from hermnet_amd import _lib, ops, switches
+    dev = torch.device("cuda:0")
+    C = trainops.BucketedBasis.CHUNK
+    H = next(h for h in range(4, 1025, 4) if _lib.load().hermnet_band_product_supported(C, 3 * h))
+    kw = dict(rc=4.0, hidden_channels=H, num_rbf=32, num_layers=2)
+    d0 = _alloy((4, 4, 4), rc=4.0)
+    sd = synth_state_dict(hn.HVNet(ALNICU, **kw).state_dict(), 47)
+    gen = torch.Generator().manual_seed(47)
+    y, ftgt = torch.randn(1, generator=gen).to(dev), (0.5 * torch.randn(d0.pos.shape, generator=gen)).to(dev)
+    runs = []
+    for row_sums in (True, False):
+        monkeypatch.setattr(switches, "train_row_sums", row_sums)
+        model = hn.HVNet(ALNICU, **kw)
+        model.load_state_dict(sd)
+        model = model.to(dev).train()
+        d = copy.copy(d0).to(dev)
+        rec = _Labels()
+        ops.set_kernel_timer(rec)
+        try:
+            d.pos.requires_grad_(True)
+            e = model(d)
+            f = -torch.autograd.grad(e.sum(), d.pos, create_graph=True)[0]
+            loss = 0.2 * torch.nn.functional.mse_loss(e, y) + 0.8 * torch.nn.functional.mse_loss(f, ftgt)
+            loss.backward()
+        finally:
+            ops.set_kernel_timer(None)
+        torch.cuda.synchronize()
+        g = d._hn_graph
+        assert g.T == 3 and g.uniform and g.N >= 256
+        _bucketed(d)
+        out = {k: p.grad.detach().cpu() for k, p in model.named_parameters() if p.grad is not None}
+        out["forces"] = f.detach().cpu()
+        runs.append((e.detach().cpu(), out, set(rec.names)))
+    names = runs[0][2]
+    print("labels of one training step:", sorted(names))
+    want = {"edge_unit", "basis_window", "band_product", "band_product_grad_a", "edge_message_fwd_rows", "edge_message_bwd_rows",
+            "edge_message_bwd2_rows", "segment_sum", "col_sum"} | set(trainops.NODE_OPS)
+    assert want <= names, sorted(want - names)
+    assert names & {"band_product_grad_b", "band_product_grads"}
+    assert not names & {"edge_message_fwd", "edge_message_bwd", "edge_message_bwd2", "train_node_op"}
+    behind = runs[1][2]
+    assert {"edge_message_fwd", "edge_message_bwd", "edge_message_bwd2"} <= behind
+    assert not behind & {"edge_message_fwd_rows", "edge_message_bwd_rows", "edge_message_bwd2_rows"}
+    assert behind - {"edge_message_fwd", "edge_message_bwd", "edge_message_bwd2"} == \
+        names - {"edge_message_fwd_rows", "edge_message_bwd_rows", "edge_message_bwd2_rows"}
+    (e0, out0, _), (e1, out1, _) = runs
+    assert float((e1 - e0).abs().max()) < 2e-5 * max(1.0, float(e0.abs().max()))
+    assert_grads_close(out1, out0)
