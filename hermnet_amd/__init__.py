@@ -5,7 +5,7 @@ from .hermnet import HVNet, HeteroVertexConv, HTNet, HeteroTriadicConv  # noqa: 
 from .atomic import atom_properties  # noqa: F401
 from .stress import energy_forces_stress  # noqa: F401
 from .graph import GraphedStep, GraphedMDStep, GraphedBatchMDStep  # noqa: F401
-from .md import DeviceMD  # noqa: F401
+from .md import DeviceMD, DeviceNPT  # noqa: F401
 from .relax import DeviceRelax  # noqa: F401
 from .rmnet import PaiNNModule, PaiNNMessage, PaiNNUpdate, ScaledSiLU, RadialBasis  # noqa: F401
 

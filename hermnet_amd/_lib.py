@@ -180,6 +180,12 @@ SIGNATURES = {
     "hermnet_host_md_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] + [c_fp] * 12 +
                                [ctypes.c_long, c_fp]),
     "hermnet_host_md_noise": (ctypes.c_int, [ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int, c_fp, c_fp]),
+    "hermnet_md_finish_npt": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 6 + [ctypes.c_long, ctypes.c_int, ctypes.c_int,
+                                                                                      ctypes.c_double] + [c_fp] * 19 +
+                              [ctypes.c_long, c_fp, c_fp]),
+    "hermnet_host_md_finish_npt": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 6 +
+                                   [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [c_fp] * 19 +
+                                   [ctypes.c_long, c_fp]),
     "hermnet_relax_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_fp] * 14),
     "hermnet_relax_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] + [ctypes.c_double] * 4 +
                              [c_fp] * 14 + [ctypes.c_long, c_fp, c_fp]),

@@ -102,13 +102,14 @@ class ResidentDriver(object):
         self.log_steps = int(log_steps)   # rows of the ring
         self.log = torch.zeros(self.log_steps, B, self.LOG_WIDTH, dtype=torch.float64, device=dev)    # finish: row step % log_steps
         self.wrap = bool(wrap)            # wrap coordinates into the cell where the step has one
-        self.inv_cell = self._inv_of = None     # `_cell_args`: the float64 inverse [B,3,3] and the cell tensor it was made of
+        self.inv_cell = self._inv_of = None     # `_inverse_of`: the float64 inverse [B,3,3] and the cell tensor it was made of
         self._logged = self._pending = 0  # `fetch`: the step its last snapshot stood at; `run`, `fetch`: replays enqueued since
         self._host = None                 # `fetch`: the pinned buffer
         self._own_state(**own)
         # the captured step: advance -> the graphed step's own _eager() -> finish
         cell_t = None if cell is None else torch.as_tensor(cell).detach().float().to(dev).contiguous()
         kw = dict(capacity=capacity, reference_compat=reference_compat, hooks=(self._advance, self._finish))
+        kw.update(self._step_options(batch is None))
         if batch is None:
             if cell_t is None:
                 raise RuntimeError("%s: one structure needs a periodic cell (open structures: batch=, cell=None)" % name)
@@ -139,10 +140,20 @@ class ResidentDriver(object):
             return False, None, None
         if cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != 9 * self.num_graphs:
             raise RuntimeError("%s: the step's cell must be a contiguous float32 [B,3,3]" % type(self).__name__)
+        return True, cell.data_ptr(), self._inverse_of(cell).data_ptr()
+
+    def _inverse_of(self, cell):
+        """The float64 inverse [B,3,3] of the step's cell tensor: made on the host, once per tensor.  A subclass whose
+        kernels move the cell keeps `inv_cell` as device state of its own and answers with that."""
         if self._inv_of is not cell:
             inv = np.linalg.inv(cell.detach().double().cpu().numpy().reshape(-1, 3, 3))
             self.inv_cell, self._inv_of = torch.from_numpy(np.ascontiguousarray(inv)).to(self.device), cell
-        return True, cell.data_ptr(), self.inv_cell.data_ptr()
+        return self.inv_cell
+
+    def _step_options(self, single):
+        """Further keyword arguments of the graphed step (`single`: one structure, a `GraphedMDStep`): none.  A subclass
+        that needs the virial or a cell it can move asks for `stress=` / `variable_cell=` here."""
+        return {}
 
     # ---- running --------------------------------------------------------------------------------------------------------------
     @property

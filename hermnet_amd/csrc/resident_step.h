@@ -112,7 +112,7 @@ HN_HD inline double* hn_log_row(double* log, long step, long log_steps, int num_
   return log + ((size_t)(step % log_steps) * num_graphs + g) * width;
 }
 
-// COUNT (1..4) per-graph sums over the atoms lo..hi-1 in the CANONICAL ORDER (the sums steer a trajectory, so their order is
+// COUNT (1..6) per-graph sums over the atoms lo..hi-1 in the CANONICAL ORDER (the sums steer a trajectory, so their order is
 // part of the contract): lane l of 256 adds the terms of atoms lo+l, lo+l+256, ... in ascending order starting from 0.0 --
 // term(i, s) adds atom i's to the lane's partials s[0..COUNT) --; the 256 partials are then folded part[l] += part[l+m] for
 // m = 128, 64, ..., 1; the sum at MAX_AT (-1: none) is a maximum and takes the same tree.  No atomics.  Results: part[k][0].

@@ -14,6 +14,8 @@ What made replay work (ROCm 7.2, bisected with tools/graph_probe.py): captured `
 eager memsets issued between two replays (the second replay skips / mis-addresses the fill), so nothing on the step
 path uses hipMemsetAsync / hipMemcpyAsync any more (csrc/relation_kernels.hip: zero / copy / scan kernels).
 """
+import gc
+
 import torch
 
 
@@ -38,8 +40,19 @@ def _capture(step, warmup):
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        out = step()
+    # No garbage collection inside the capture: a resident driver and its step refer to each other through the hooks, so a
+    # dead driver's capture is freed by the collector alone, and destroying a CUDAGraph synchronises the device on ROCm --
+    # inside a capture in progress that call is refused and the refusal, raised in a destructor, ends the process.  Dead
+    # captures are collected here instead, and the collector stays out until this capture has ended.
+    collecting = gc.isenabled()
+    gc.collect()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            out = step()
+    finally:
+        if collecting:
+            gc.enable()
     torch.cuda.synchronize()
     return graph, out
 

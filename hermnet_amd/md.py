@@ -21,8 +21,11 @@ is VOID -- coordinates, velocities and images return to the start of the
 step, the halt code and step are recorded, no log row is written, and every later replay changes nothing.  `fetch()` reports
 it; `resume()` recaptures (with a larger capacity where the list overflowed), re-evaluates the forces and clears the halt.
 
-Out of scope: barostats / NPT (the cell is constant during `run`), constraints other than an infinite mass (= a fixed
-atom), atom shards, HTNet, more than one time step per replay."""
+`DeviceNPT` is `DeviceMD` with a Berendsen barostat inside the replay (its class docstring): the captured step carries the
+virial kernels, and `hermnet_md_finish_npt` scales the cell and the coordinates at the end of every committed step.
+
+Out of scope: for `DeviceMD` the cell is constant during `run` (barostat: `DeviceNPT`); for both, constraints other than an
+infinite mass (= a fixed atom), atom shards, HTNet, more than one time step per replay."""
 import math
 
 import numpy as np
@@ -34,6 +37,8 @@ from ._resident import HALT_CAPACITY, HALT_NONFINITE, HN_MD_LANGEVIN, HN_MD_WRAP
 AMU_A2_FS2_TO_EV = 103.642696562         # 1 amu A^2 / fs^2 in eV (tools/md_nve.py)
 KB = 8.617333262e-5                       # eV / K
 ASE_TIME_FS = math.sqrt(AMU_A2_FS2_TO_EV)   # ASE's time unit in fs: v [A/fs] = v_ase / 10.18051
+GPA = 1.0 / 160.2176634                   # 1 GPa in eV / A^3
+HN_MD_BARO = {"isotropic": 0, "axes": 1, "full": 2}     # include/hermnet_hip.h: HN_MD_BARO_*
 
 
 class DeviceMD(ResidentDriver):
@@ -162,3 +167,150 @@ class DeviceMD(ResidentDriver):
         atoms.positions = s.positions.copy()
         atoms.set_velocities(s.velocities * ASE_TIME_FS)
         return s
+
+
+def _det3(c):
+    """csrc/npt_step.h: npt_det3 on [B,3,3] float64, operation by operation."""
+    c = c.reshape(-1, 9)
+    return ((c[:, 0] * (c[:, 4] * c[:, 8] - c[:, 5] * c[:, 7]) + c[:, 1] * (c[:, 5] * c[:, 6] - c[:, 3] * c[:, 8]))
+            + c[:, 2] * (c[:, 3] * c[:, 7] - c[:, 4] * c[:, 6]))
+
+
+def _inverse3(c):
+    """csrc/npt_step.h: npt_inverse3 (adjugate over determinant) on [B,3,3] float64: the inverse the kernels themselves
+    make after every scaling, so a run's first wrap and its later ones use one definition."""
+    c = c.reshape(-1, 9)
+    det = _det3(c)
+    a = [c[:, k] for k in range(9)]
+    adj = [a[4] * a[8] - a[5] * a[7], a[2] * a[7] - a[1] * a[8], a[1] * a[5] - a[2] * a[4],
+           a[5] * a[6] - a[3] * a[8], a[0] * a[8] - a[2] * a[6], a[2] * a[3] - a[0] * a[5],
+           a[3] * a[7] - a[4] * a[6], a[1] * a[6] - a[0] * a[7], a[0] * a[4] - a[1] * a[3]]
+    return np.stack([t / det for t in adj], axis=1).reshape(-1, 3, 3)
+
+
+class DeviceNPT(DeviceMD):
+    """`DeviceMD` at constant pressure: a Berendsen barostat INSIDE the replayed step, for one structure or a batch
+    (replicas at different pressures and temperatures in one capture).  Everything `DeviceMD` takes, and `pressure` (the
+    target, eV/A^3; `GPA` converts), `compressibility` (A^3/eV), `taup` (fs) -- scalars or [B] --, `coupling`:
+
+        "isotropic"  mu = (1 - c (P0 - P)) I                            (ASE's NPTBerendsen)
+        "axes"       mu = diag(1 - c (P0 - P_kk)) where `mask[k]`, 1 elsewhere      (ASE's Inhomogeneous_NPTBerendsen,
+                     applied to Cartesian components, so it is valid for triclinic cells too)
+        "full"       mu_ab = delta_ab - c (P0 delta_ab - P_ab)
+
+    with c = (dt / taup) compressibility / 3 and P_ab = (sum m v_a v_b + sym(W)_ab) / V from the step's own virial W (stress
+    = -sym(W) / V) and the kinetic tensor.  With `friction=None` it is velocity Verlet plus barostat, with `friction` the
+    usual Langevin NPT.  One force evaluation per step: the scaling ends a committed step (cell <- cell mu, x <- x mu for
+    every atom, held ones too; images and velocities stay) and the next replay's search reads the new cell.  The float64
+    cell is the truth; the step's float32 cell is its rounding, as the float32 coordinates are of x.  Two safety conditions
+    that are not physics: every entry of mu - I is clamped to +-`max_strain`, and a pressure that is not finite gives mu = I
+    -- a scaled cell cannot be taken back by a later void step.  `cell` may be given in float64.
+
+    `fetch()`: `DeviceMD`'s, `log` [rows,B,5] = (E_pot, E_kin, edges found, pressure, volume) per time step -- the pressure
+    that step's scaling was made from, the volume before it --, `cell` [B,3,3] float64, `volume` [B], `mu` [B,3,3] (the last
+    scaling) and `clamped` [B] (how often a safety condition acted).  A void step, a prime and the parked replays of a capture
+    never scale, so halt and `resume()` are `DeviceMD`'s.
+
+    Out of scope: stochastic cell rescaling and MTK (barostats that sample the correct ensemble), velocity scaling, atom
+    shards, HTNet, NPT in `DeviceRelax`, open structures (they have no volume)."""
+
+    __slots__ = ("pressure", "compressibility", "taup", "coupling", "mask", "max_strain", "cell64", "mu", "clamped", "p0",
+                 "coupling_c", "_cell_given")
+    LOG_WIDTH = 5
+
+    def __init__(self, model, atomic_number, cell, pos, masses, dt, pressure=0.0, compressibility=None, taup=1000.0,
+                 coupling="isotropic", mask=(1, 1, 1), max_strain=1e-2, **kw):
+        if cell is None:
+            raise RuntimeError("DeviceNPT: a barostat needs periodic cells (cell=None, open structures, have no volume)")
+        if compressibility is None:
+            raise ValueError("DeviceNPT: compressibility= (A^3/eV) is required")
+        if coupling not in HN_MD_BARO:
+            raise ValueError("DeviceNPT: coupling is one of %s" % sorted(HN_MD_BARO))
+        self.pressure, self.compressibility, self.taup = pressure, compressibility, taup     # as given
+        self.coupling = coupling                          # "isotropic", "axes" or "full"
+        self.mask = sum(1 << k for k, on in enumerate(tuple(mask)) if on)      # "axes": bit k = direction k is coupled
+        self.max_strain = float(max_strain)               # the largest |mu - I| entry of one step
+        if len(tuple(mask)) != 3 or not (self.max_strain > 0.0):
+            raise ValueError("DeviceNPT: mask has three entries and max_strain > 0")
+        self._cell_given = cell                           # `_own_state` makes cell64 of it
+        super().__init__(model, atomic_number, cell, pos, masses, dt, **kw)
+
+    def _own_state(self, masses):
+        super()._own_state(masses)
+        B, dev = self.num_graphs, self.device
+        taup, comp = per_graph(self.taup, B), per_graph(self.compressibility, B)
+        if not (np.all(taup > 0.0) and np.all(comp >= 0.0)):
+            raise ValueError("DeviceNPT: taup > 0 and compressibility >= 0")
+        cell = host_f64(self._cell_given).reshape(B, 3, 3).copy()
+        self._cell_given = None
+        self.cell64 = torch.from_numpy(cell).to(dev)      # the cell [B,3,3] f64: the truth; finish
+        self.inv_cell = torch.from_numpy(_inverse3(cell.astype(np.float32).astype(np.float64))).to(dev)   # of the f32 cell; finish
+        self.mu = torch.eye(3, dtype=torch.float64, device=dev).repeat(B, 1, 1).contiguous()   # the last scaling; finish
+        self.clamped = torch.zeros(B, dtype=torch.int64, device=dev)      # safety conditions that acted; finish
+        self.p0 = torch.from_numpy(per_graph(self.pressure, B)).to(dev)   # the targets [B]
+        self.coupling_c = torch.from_numpy((self.dt / taup) * comp / 3.0).to(dev)     # (dt / taup) compressibility / 3 [B]
+
+    def _step_options(self, single):
+        return dict(stress=True, variable_cell=True) if single else dict(stress=True)
+
+    def _inverse_of(self, cell):
+        return self.inv_cell              # device state: finish rewrites it with the cell
+
+    def _finish(self, step, out):
+        P = _lib.ptr
+        energy, forces, total = self._step_outputs(out)
+        virial, cell, B = out[2], step.cell, self.num_graphs
+        if virial.dtype != torch.float32 or not virial.is_contiguous() or virial.numel() != 9 * B:
+            raise RuntimeError("DeviceNPT: the captured step must return a contiguous float32 virial [B,3,3]")
+        if cell is None or cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != 9 * B:
+            raise RuntimeError("DeviceNPT: the step's cell must be a contiguous float32 [B,3,3]")
+        _lib.check(self.lib.hermnet_md_finish_npt(
+            self.n, B, P(self.graph_ptr), P(self.batch), P(forces), P(energy), P(virial), P(total), int(step.capacity),
+            HN_MD_BARO[self.coupling], self.mask, self.max_strain, P(self.p0), P(self.coupling_c), P(self.x), P(self.v),
+            P(self.x0), P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos),
+            P(self.ke_atom), P(self.cell64), P(cell), P(self.inv_cell), P(self.mu), P(self.clamped), P(self.log), self.log_steps,
+            P(self.state), torch.cuda.current_stream(self.device).cuda_stream), "hermnet_md_finish_npt")
+
+    def resume(self):
+        """`DeviceMD.resume`, and the last accepted forces stay: they are those of the configuration BEFORE the last scaling
+        (one force evaluation per step), which the recapture's evaluation of the scaled configuration must not replace --
+        the next step's first kick is the one an uninterrupted run makes.  (After a change of weights that one half kick
+        still uses the old weights' forces.)"""
+        f = self.f_prev.clone()
+        super().resume()
+        self.f_prev.copy_(f)
+
+    # ---- the packed fetch's own part ------------------------------------------------------------------------------------------
+    def _fetch_extras(self):
+        return [self.cell64, self.mu, self.clamped]
+
+    def _read_extras(self, s, word, h):
+        B = self.num_graphs
+        s.cell, s.mu = h[:9 * B].reshape(B, 3, 3).copy(), h[9 * B:18 * B].reshape(B, 3, 3).copy()
+        s.clamped = h[18 * B:19 * B].astype(np.int64)
+        s.volume = np.abs(_det3(s.cell))
+
+    # ---- ASE hand-off ---------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_atoms(cls, atoms, model, dt, device="cuda:0", **kw):
+        """As `DeviceMD.from_atoms`; the cell is taken in float64."""
+        if not np.all(np.asarray(atoms.pbc)):
+            raise RuntimeError("DeviceNPT.from_atoms: a periodic structure (pbc in all three directions)")
+        dev = torch.device(device)
+        v = atoms.get_velocities()
+        return cls(model, torch.as_tensor(np.asarray(atoms.numbers)).to(dev),
+                   np.asarray(atoms.cell, dtype=np.float64).reshape(3, 3), np.asarray(atoms.positions, dtype=np.float64),
+                   np.asarray(atoms.get_masses(), dtype=np.float64), dt,
+                   velocities=None if v is None else np.asarray(v, dtype=np.float64) / ASE_TIME_FS, device=dev, **kw)
+
+    def to_atoms(self, atoms, snapshot=None):
+        """`DeviceMD.to_atoms`, and the cell (one structure) -- written first and without moving the atoms: the positions
+        are already those of the scaled cell."""
+        s = snapshot if snapshot is not None else self.fetch()
+        if self.num_graphs != 1:
+            raise ValueError("DeviceNPT.to_atoms: one structure (a batch: take `cell` and `positions` of the snapshot)")
+        if hasattr(atoms, "set_cell"):
+            atoms.set_cell(s.cell[0].copy(), scale_atoms=False)
+        else:
+            atoms.cell = s.cell[0].copy()
+        return super().to_atoms(atoms, s)

@@ -19,7 +19,7 @@
  * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -899,6 +899,57 @@ int hermnet_host_md_finish(int num_atoms, int num_graphs, const int* graph_ptr_h
                            float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
                            double* ke_atom_host, double* log_host, long log_steps, long* state_host);
 int hermnet_host_md_noise(unsigned long seed, unsigned long step, int n, unsigned* out_words_host, double* out_gauss_host);
+
+/* Device-resident NPT: a Berendsen barostat inside the replayed MD step (added within ABI v13: new entry points only;
+ * hermnet_amd/md.py: DeviceNPT; csrc/md_kernels.hip, npt_step.h).  hermnet_md_finish_npt takes the place of hermnet_md_finish
+ * behind the force backward of a step captured WITH the virial kernels and with the cell as a device-side input; the advance
+ * is hermnet_md_advance.  One force evaluation per step; the scaling ends a committed step (as GROMACS orders it) and is
+ * ASE's NPTBerendsen formula.  Units: eV, Angstrom, fs; pressures in eV / A^3.
+ *
+ * Caller-owned state beside hermnet_md_finish's:   virial [B,9] float32 the step's virial output (stress = -sym(W) / V);
+ *   cell64 [B,9] float64 the cell -- the truth --, cell32 [B,9] float32 its rounding: the tensor search, edge geometry and
+ *   virial kernels read, inv_cell [B,9] float64 the inverse of the WIDENED cell32 (adjugate over determinant), the one
+ *   hermnet_md_advance wraps with;   mu [B,9] float64 the last scaling matrix;   clamped [B] int64 how often the safety
+ *   conditions acted;   pressure [B] the targets P0, coupling_c [B] = (dt / taup) compressibility / 3;   batch [N] int64 or
+ *   NULL (one graph);   log [log_steps,B,5] = (E_pot, E_kin, edges found, pressure, volume).
+ *
+ * hermnet_md_finish_npt   halt code != 0: nothing.  Mode 1, and a step whose code is not 0: as hermnet_md_finish -- cell64,
+ *   cell32, inv_cell, mu are NOT touched (a void step restores x, v, image alone: the cell needs no backup because only
+ *   committed steps scale).  Code 0: v += kick forces, f_prev = forces; then per graph g:
+ *     K_ab = sum m_i v_ia v_ib over xx, yy, zz, xy, xz, yz (m = 2 half_mass; a term is (m v_a) v_b), six sums in the
+ *       canonical order of hermnet_relax_finish;  E_kin = ((K_xx + K_yy) + K_zz) / 2;
+ *     V = |det cell64|, det = (c0 (c4 c8 - c5 c7) + c1 (c5 c6 - c3 c8)) + c2 (c3 c7 - c4 c6);
+ *     P_ab = (K_ab + (W_ab + W_ba) / 2) / V with W widened to float64;  P = ((P_xx + P_yy) + P_zz) / 3;
+ *     e_ab: HN_MD_BARO_ISOTROPIC c (P0 - P) on the diagonal;  HN_MD_BARO_AXES c (P0 - P_kk) on the diagonal entries k with
+ *       bit k of `mask` set, 0 elsewhere;  HN_MD_BARO_FULL c (P0 delta_ab - P_ab);  every e_ab is clamped to +-max_strain;
+ *       an entry of P that is not finite: e = 0 (these two are safety conditions: a scaled cell cannot be taken back);
+ *     mu = I - e;  cell64 <- cell64 mu (rows are lattice vectors; an entry is (c_i0 mu_0j + c_i1 mu_1j) + c_i2 mu_2j);
+ *     cell32 = float(cell64);  inv_cell = adj(double(cell32)) / det(double(cell32));  clamped += 1 where a condition acted;
+ *     log[step % log_steps][g] = (energy[g], E_kin, total[0], P, V) -- the pressure mu was made from, the volume before it;
+ *   then every atom (held ones too) x <- x mu of its graph, pos32 = float(x); images and velocities stay;  step += 1.
+ *   Four launches: hermnet_md_finish's per-atom kernel, one 256-lane workgroup per graph, the per-atom scaling, and the
+ *   single workgroup that alone writes `state`.
+ * hermnet_host_md_finish_npt runs the same text on HOST pointers (no stream), the sums in the canonical order: bit for bit
+ *   what the device computes for the same forces and virial.
+ * HN_ERR_BAD_ARG: hermnet_md_finish's, a NULL virial / pressure / coupling_c / cell64 / cell32 / inv_cell / mu / clamped,
+ *   an unknown coupling, mask bits above 7, max_strain <= 0 (or NaN). */
+#define HN_MD_BARO_ISOTROPIC 0
+#define HN_MD_BARO_AXES 1
+#define HN_MD_BARO_FULL 2
+int hermnet_md_finish_npt(int num_atoms, int num_graphs, const int* graph_ptr, const long* batch, const float* forces,
+                          const float* energy, const float* virial, const long* total, long capacity, int coupling, int mask,
+                          double max_strain, const double* pressure, const double* coupling_c, double* x, double* v,
+                          const double* x0, const double* v0, int* image, const int* image0, float* f_prev, const double* kick,
+                          const double* half_mass, float* pos32, double* ke_atom, double* cell64, float* cell32,
+                          double* inv_cell, double* mu, long* clamped, double* log, long log_steps, long* state, void* stream);
+int hermnet_host_md_finish_npt(int num_atoms, int num_graphs, const int* graph_ptr_host, const long* batch_host,
+                               const float* forces_host, const float* energy_host, const float* virial_host,
+                               const long* total_host, long capacity, int coupling, int mask, double max_strain,
+                               const double* pressure_host, const double* coupling_c_host, double* x_host, double* v_host,
+                               const double* x0_host, const double* v0_host, int* image_host, const int* image0_host,
+                               float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
+                               double* ke_atom_host, double* cell64_host, float* cell32_host, double* inv_cell_host,
+                               double* mu_host, long* clamped_host, double* log_host, long log_steps, long* state_host);
 
 /* Device-resident FIRE relaxation of a batch of structures (added within ABI v13: new entry points only;
  * hermnet_amd/relax.py: DeviceRelax; csrc/relax_kernels.hip, relax_step.h).  As for hermnet_md_*: hermnet_relax_advance is
