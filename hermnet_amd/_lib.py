@@ -1,198 +1,103 @@
-"""ctypes binding of `libhermnet_hip.so` (C ABI in `include/hermnet_hip.h`).
+"""ctypes binding of `libhermnet_hip.so`, READ from its contract `include/hermnet_hip.h`.
+
+Nothing of the C ABI is retyped here: `read_header` turns the header's `#define HN_*`, its four `typedef struct hn_*` and every
+`hermnet_*` declaration into the constants, the `ctypes.Structure` classes (`Graph`, `RbfDesc`, `PendingGrads`, `RelationsOut`)
+and `SIGNATURES` (name -> (restype, argtypes)) of this module, on the first use of any of them.  The reader is strict: a type it
+does not know or a declaration it cannot read raises, naming it.
+`call(c_name, *args)` is THE way to call an entry point that returns an HN_* code; launches that carry a timer label take
+`ops._call`, which appends the stream.  Size queries (`*_workspace*`, `*_supported`, `*_tile_rows`) are plain calls on `load()`.
 
 The library is built in-tree by `__graft_entry__.build()` / `make -C hermnet_amd/csrc`.
 There is NO fallback: if it is missing the product path raises.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HERMNET_LIB_PATH") or os.path.join(_HERE, "csrc", "libhermnet_hip.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "hermnet_hip.h")
 
-HN_ENV = {"polynomial": 0, "exponential": 1}
-_ERR = {1: "HN_ERR_BAD_ARG (unsupported shape or null pointer)",
-        2: "HN_ERR_LDS (weight tile does not fit the 160 KiB LDS)",
-        3: "HN_ERR_LAUNCH (kernel launch failed)"}
-
-c_fp = ctypes.c_void_p  # device pointers travel as integers
-ABI_VERSION = 13         # must equal hermnet_abi_version() of the loaded library (include/hermnet_hip.h)
+_SCALARS = {"int": ctypes.c_int, "long": ctypes.c_long, "float": ctypes.c_float, "double": ctypes.c_double,
+            "size_t": ctypes.c_size_t, "unsigned long": ctypes.c_ulong}
 
 
-class RbfDesc(ctypes.Structure):
-    _fields_ = [("offset", c_fp), ("num_rbf", ctypes.c_int), ("inv_rc", ctypes.c_float),
-                ("coeff", ctypes.c_float), ("env_kind", ctypes.c_int), ("env_p", ctypes.c_int)]
+def _ctype(ctext, structs, where, named=True):
+    """ctypes type of the C parameter, field (`named`) or return type `ctext`.  Device and host pointers travel as integers
+    (c_void_p), except a pointer to one of the header's structs and the `const char*` a function returns."""
+    words = [w for w in ctext.replace("*", " * ").split() if w != "const"]
+    if "*" in words:
+        base = " ".join(words[:words.index("*")])
+        if words.count("*") == 1 and base in structs:
+            return ctypes.POINTER(structs[base])
+        return ctypes.c_char_p if base == "char" and not named else ctypes.c_void_p
+    base = " ".join(words[:-1] if named else words)
+    if base not in _SCALARS:
+        raise ValueError("include/hermnet_hip.h: unknown type `%s` in %s" % (ctext.strip(), where))
+    return _SCALARS[base]
 
 
-class Graph(ctypes.Structure):
-    _fields_ = [("num_nodes", ctypes.c_int), ("num_edges", ctypes.c_int), ("num_rel", ctypes.c_int),
-                ("type_rowptr", c_fp), ("csr_rowptr", c_fp), ("csr_src", c_fp),
-                ("csc_rowptr", c_fp), ("csc_tgt", c_fp), ("csc_pos", c_fp),
-                ("num_src", ctypes.c_int), ("res_row", c_fp)]
+def read_header(text):
+    """(defines, structs, signatures, notes) of the header `text`: every `#define HN_* <int>` by name, every `typedef struct
+    hn_x` as a ctypes.Structure class by its C name, every `hermnet_*` declaration as name -> (restype, argtypes), and the
+    comment behind each HN_ERR_* define."""
+    raw = text
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {n: int(v) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(HN_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
+    # (an error code's message: the comment behind its define)
+    notes = dict(re.findall(r"#[ \t]*define[ \t]+(HN_ERR_\w+)[ \t]+\d+[ \t]*/\*\s*(.*?)\s*\*/", raw))
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+    structs = {}
+    for name, body, alias in re.findall(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", text):
+        if alias != name or not name.startswith("hn_"):
+            raise ValueError("include/hermnet_hip.h: struct %s is typedef'd as %s" % (name, alias))
+        fields = [f for f in body.split(";") if f.strip()]
+        cls = "".join(p.capitalize() for p in name[3:].split("_"))
+        structs[name] = type(cls, (ctypes.Structure,), {
+            "__doc__": "%s of include/hermnet_hip.h" % name,
+            "_fields_": [(f.split()[-1].lstrip("*"), _ctype(f, structs, "struct " + name)) for f in fields]})
+    signatures = {}
+    for res, name, params in re.findall(r"([\w\s\*]+?)\b(hermnet_\w+)\s*\(([^()]*)\)\s*;", text):
+        params = [] if params.strip() == "void" else params.split(",")
+        signatures[name] = (_ctype(res, structs, name + "'s return type", named=False), [_ctype(p, structs, name) for p in params])
+    seen = re.findall(r"\b(hermnet_\w+)\s*\(", text)
+    if len(seen) != len(signatures):
+        raise ValueError("include/hermnet_hip.h: %d declarations read, %d `hermnet_*(` present -- not read: %s"
+                         % (len(signatures), len(seen), sorted(set(seen) - set(signatures)) or "a name declared twice"))
+    return defines, structs, signatures, notes
 
 
-class PendingGrads(ctypes.Structure):
-    """hn_pending_grads (include/hermnet_hip.h): the incoming gradients of an update backward, still in partial sums."""
-    _fields_ = [(n, c_fp) for n in ("gn_parts", "gvec_parts", "x", "mean", "rstd", "gx1", "gvec1")] + \
-               [("num_parts", ctypes.c_int), ("hidden_real", ctypes.c_int)] + \
-               [(n, c_fp) for n in ("gxh", "hb", "w2t_frag16", "w1t_frag16")]
+def _bind():
+    """Read the header (once) and publish what it declares as attributes of this module: every HN_* define, the struct
+    classes, SIGNATURES, OPTIONS / HN_ENV (the HN_OPT_* / HN_ENV_* defines, lower-cased), ABI_VERSION, the error texts."""
+    g = globals()
+    if "SIGNATURES" in g:
+        return
+    try:
+        with open(HEADER_PATH) as fh:
+            text = fh.read()
+    except OSError:
+        raise RuntimeError("hermnet_amd: the C ABI's header %s not found -- the binding is read from it (it ships with the "
+                           "sources, beside hermnet_amd/)" % HEADER_PATH)
+    defines, structs, signatures, notes = read_header(text)
+    g.update(defines)
+    g.update({cls.__name__: cls for cls in structs.values()})
+    prefixed = lambda p: {n[len(p):].lower(): v for n, v in defines.items() if n.startswith(p)}
+    g.update(OPTIONS=prefixed("HN_OPT_"), HN_ENV=prefixed("HN_ENV_"), ABI_VERSION=defines["HN_ABI_VERSION"],
+             _ERR={v: "%s (%s)" % (n, notes[n]) if n in notes else n for n, v in defines.items() if n.startswith("HN_ERR_")},
+             SIGNATURES=signatures)
 
 
-class RelationsOut(ctypes.Structure):
-    _fields_ = [(n, c_fp) for n in ("node_order", "row_of_node", "z_rows", "row_real", "row_active", "csr_rowptr",
-                                    "csr_src", "csr_perm", "src_id", "tgt_id", "shift_csr", "csc_rowptr", "csc_tgt",
-                                    "csc_pos", "out_rowptr", "out_edges")]
+def __getattr__(name):
+    """The names `_bind` derives from the header, on their first use (a missing header raises there, not at import)."""
+    if name.startswith("__") or "SIGNATURES" in globals():
+        raise AttributeError("module %r has no attribute %r" % (__name__, name))
+    _bind()
+    try:
+        return globals()[name]
+    except KeyError:
+        raise AttributeError("module %r has no attribute %r" % (__name__, name))
 
-
-# name -> (restype, argtypes); mirrors include/hermnet_hip.h one to one
-SIGNATURES = {
-    "hermnet_abi_version": (ctypes.c_int, []),
-    "hermnet_build_info": (ctypes.c_char_p, []),
-    "hermnet_edge_geometry_fwd": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_edge_geometry_bwd": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_edge_geometry_bwd_csc": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_edge_geometry_bwd_virial": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                                        c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "hermnet_graph_virial_workspace": (ctypes.c_size_t, [ctypes.c_int]),
-    "hermnet_graph_virial": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_size_t, c_fp, c_fp]),
-    "hermnet_message_scatter_fwd": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int,
-                                                   c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_message_scatter_bwd": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int,
-                                                   c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                                   c_fp, c_fp, c_fp, c_fp, ctypes.c_int, c_fp, c_fp,
-                                                   c_fp, c_fp, ctypes.c_int, c_fp]),
-    "hermnet_message_scatter_bwd_gedge": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int] +
-                                          [c_fp] * 9),
-    "hermnet_edge_radial_table": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), c_fp, c_fp, c_fp]),
-    "hermnet_edge_radial_tables": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), c_fp, c_fp, c_fp, c_fp]),
-    "hermnet_message_scatter_fwd_taps": (ctypes.c_int, [ctypes.POINTER(Graph), ctypes.POINTER(RbfDesc), ctypes.c_int,
-                                                        c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
-                                                        ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_neighbor_workspace": (ctypes.c_size_t, [ctypes.c_int]),
-    "hermnet_neighbor_workspace_for": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]),
-    "hermnet_neighbor_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_double, c_fp,
-                                              ctypes.c_size_t, c_fp, c_fp, c_fp]),
-    "hermnet_neighbor_count_devcell": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_double, c_fp, ctypes.c_size_t,
-                                                      c_fp, c_fp, c_fp]),
-    "hermnet_neighbor_fill": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_double, c_fp, ctypes.c_size_t,
-                                             ctypes.c_long, ctypes.c_float, ctypes.c_int, ctypes.c_int,
-                                             c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "hermnet_neighbor_fill_padded": (ctypes.c_int, [ctypes.c_int, c_fp, ctypes.c_size_t, ctypes.c_long, ctypes.c_float,
-                                                    ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "hermnet_neighbor_batch_workspace": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "hermnet_neighbor_batch_count": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_double, c_fp,
-                                                    ctypes.c_size_t, c_fp, c_fp]),
-    "hermnet_neighbor_batch_fill": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_size_t, ctypes.c_long,
-                                                   ctypes.c_float, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "hermnet_neighbor_batch_fill_padded": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_size_t, ctypes.c_long,
-                                                          ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp]),
-    "hermnet_relation_counts": (ctypes.c_int, [c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_build_relations_workspace": (ctypes.c_size_t, [ctypes.c_int] * 4),
-    "hermnet_build_relations": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int,
-                                               c_fp, ctypes.c_int, c_fp, ctypes.POINTER(RelationsOut), ctypes.c_int, c_fp,
-                                               ctypes.c_size_t, c_fp]),
-    "hermnet_build_triadic_workspace": (ctypes.c_size_t, [ctypes.c_int] * 4),
-    "hermnet_build_triadic": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int,
-                                             c_fp, c_fp, ctypes.POINTER(RelationsOut), c_fp, c_fp, ctypes.c_int, c_fp,
-                                             ctypes.c_size_t, c_fp]),
-    "hermnet_train_node_op": (ctypes.c_int, [ctypes.c_int, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_long, ctypes.c_int,
-                                             ctypes.c_float, ctypes.c_float, c_fp]),
-    "hermnet_edge_message_fwd_rows": (ctypes.c_int, [c_fp] * 4 + [ctypes.c_long, ctypes.c_int] + [c_fp] * 5 + [ctypes.c_long] +
-                                      [c_fp] * 3),
-    "hermnet_edge_message_bwd_rows": (ctypes.c_int, [c_fp] * 6 + [ctypes.c_long, ctypes.c_int] + [c_fp] * 6 + [ctypes.c_long] +
-                                      [c_fp] * 5),
-    "hermnet_edge_message_bwd2_rows": (ctypes.c_int, [c_fp] * 10 + [ctypes.c_long, ctypes.c_int] + [c_fp] * 6 + [ctypes.c_long] +
-                                       [c_fp] * 7),
-    "hermnet_segment_sum": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_long, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_edge_message_fwd": (ctypes.c_int, [c_fp] * 4 + [ctypes.c_long, ctypes.c_int] + [c_fp] * 6),
-    "hermnet_edge_message_bwd": (ctypes.c_int, [c_fp] * 6 + [ctypes.c_long, ctypes.c_int] + [c_fp] * 9),
-    "hermnet_edge_message_bwd2": (ctypes.c_int, [c_fp] * 10 + [ctypes.c_long, ctypes.c_int] + [c_fp] * 11),
-    "hermnet_ssilu_fwd": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_long, ctypes.c_int, c_fp]),
-    "hermnet_ssilu_bwd": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_long, ctypes.c_long, c_fp]),
-    "hermnet_layernorm_fwd": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_float, c_fp]),
-    "hermnet_layernorm_bwd": (ctypes.c_int, [c_fp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_update_mid": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_update_out": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int] + [c_fp] * 7 +
-                           [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_update_out_bwd": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_int] + [c_fp] * 8 +
-                               [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_update_mid_bwd": (ctypes.c_int, [c_fp] * 6 + [ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_energy_head_fwd": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_energy_head_bwd": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_energy_head_fused_fwd": (ctypes.c_int, [c_fp] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_energy_head_fused_bwd": (ctypes.c_int, [c_fp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_energy_head16_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "hermnet_energy_head16_fwd": (ctypes.c_int, [c_fp] * 8 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_energy_head16_bwd": (ctypes.c_int, [c_fp] * 6 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_node_chain_supported": (ctypes.c_int, [ctypes.c_int]),
-    "hermnet_node_chain_tile_rows": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "hermnet_node_pre_fwd": (ctypes.c_int, [c_fp] * 10 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                        ctypes.c_float, c_fp, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_node_pre_bwd": (ctypes.c_int, [c_fp] * 11 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp,
-                                                        ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_node_update_tile_rows": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "hermnet_node_update_fwd": (ctypes.c_int, [c_fp] * 16 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_node_update_bwd": (ctypes.c_int, [c_fp] * 14 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp,
-                                                           c_fp]),
-    "hermnet_node_update_fwd_last": (ctypes.c_int, [c_fp] * 15 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_node_update_bwd_last": (ctypes.c_int, [c_fp] * 13 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_node_fused_supported": (ctypes.c_int, [ctypes.c_int]),
-    "hermnet_node_update_pre_fwd": (ctypes.c_int, [c_fp] * 16 + [ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_fp] * 8 +
-                                    [ctypes.c_int, ctypes.c_int, ctypes.c_float, c_fp]),
-    "hermnet_node_pre_fwd16": (ctypes.c_int, [c_fp] * 9 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                          ctypes.c_float, c_fp]),
-    "hermnet_node_pre_bwd16": (ctypes.c_int, [c_fp] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_pair_mean": (ctypes.c_int, [ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                         ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, c_fp, ctypes.c_int, c_fp]),
-    "hermnet_halo_rows": (ctypes.c_int, [ctypes.c_int, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_halo_accumulate": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_halo_proj_rows": (ctypes.c_int, [ctypes.c_int, c_fp, ctypes.c_long, ctypes.c_int, c_fp, ctypes.c_long, ctypes.c_int,
-                                              c_fp, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_halo_proj_accumulate": (ctypes.c_int, [c_fp, ctypes.c_long, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_int,
-                                                    ctypes.c_int, c_fp, c_fp]),
-    "hermnet_stream_copy": (ctypes.c_int, [c_fp, c_fp, ctypes.c_size_t, ctypes.c_int, c_fp]),
-    "hermnet_set_option": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "hermnet_get_option": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
-    "hermnet_weight_fragments": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_fp]),
-    "hermnet_band_product_supported": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
-    "hermnet_band_product": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_band_product_grad_a": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_band_product_grad_b": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "hermnet_col_sum": (ctypes.c_int, [c_fp, ctypes.c_long, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_edge_unit": (ctypes.c_int, [ctypes.c_int, c_fp, c_fp, c_fp, c_fp, ctypes.c_long, c_fp, c_fp, c_fp, c_fp]),
-    "hermnet_basis_window": (ctypes.c_int, [ctypes.c_int, c_fp, c_fp, ctypes.c_long, c_fp, c_fp, ctypes.c_long, ctypes.c_int,
-                                            ctypes.c_float, ctypes.c_int, c_fp, c_fp, c_fp, c_fp, c_fp]),
-    "hermnet_band_product_grads": (ctypes.c_int, [c_fp, c_fp, c_fp, c_fp, ctypes.c_long, ctypes.c_int, ctypes.c_int, c_fp, c_fp, c_fp,
-                                                  c_fp]),
-    "hermnet_param_guard": (ctypes.c_int, [c_fp, c_fp, ctypes.c_int, c_fp, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "hermnet_shard_step_flags": (ctypes.c_int, [c_fp, ctypes.c_long, c_fp, ctypes.c_int, c_fp, ctypes.c_long, c_fp, c_fp, c_fp,
-                                                ctypes.c_long, ctypes.c_float, c_fp]),
-    "hermnet_host_rbf_row": (ctypes.c_int, [c_fp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
-                                            ctypes.c_int, c_fp, c_fp, ctypes.c_int, ctypes.c_float, c_fp, c_fp]),
-    "hermnet_host_neighbor_geometry": (ctypes.c_int, [c_fp, c_fp, c_fp, ctypes.c_double, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_md_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_ulong] + [c_fp] * 16),
-    "hermnet_md_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] + [c_fp] * 12 +
-                          [ctypes.c_long, c_fp, c_fp]),
-    "hermnet_md_noise": (ctypes.c_int, [ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int, c_fp, c_fp, c_fp]),
-    "hermnet_host_md_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_ulong] +
-                                [c_fp] * 15),
-    "hermnet_host_md_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] + [c_fp] * 12 +
-                               [ctypes.c_long, c_fp]),
-    "hermnet_host_md_noise": (ctypes.c_int, [ctypes.c_ulong, ctypes.c_ulong, ctypes.c_int, c_fp, c_fp]),
-    "hermnet_md_finish_npt": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 6 + [ctypes.c_long, ctypes.c_int, ctypes.c_int,
-                                                                                      ctypes.c_double] + [c_fp] * 19 +
-                              [ctypes.c_long, c_fp, c_fp]),
-    "hermnet_host_md_finish_npt": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 6 +
-                                   [ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [c_fp] * 19 +
-                                   [ctypes.c_long, c_fp]),
-    "hermnet_relax_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_fp] * 14),
-    "hermnet_relax_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] + [ctypes.c_double] * 4 +
-                             [c_fp] * 14 + [ctypes.c_long, c_fp, c_fp]),
-    "hermnet_host_relax_advance": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int] + [c_fp] * 13),
-    "hermnet_host_relax_finish": (ctypes.c_int, [ctypes.c_int, ctypes.c_int] + [c_fp] * 4 + [ctypes.c_long] +
-                                  [ctypes.c_double] * 4 + [c_fp] * 14 + [ctypes.c_long, c_fp]),
-}
 
 _lib = None
 
@@ -204,7 +109,7 @@ def source_hash():
     import hashlib
     csrc = os.path.join(_HERE, "csrc")
     files = sorted(os.path.basename(f) for pat in ("*.hip", "*.cpp", "*.h") for f in glob.glob(os.path.join(csrc, pat)))
-    paths = [os.path.join(csrc, f) for f in files] + [os.path.join(_HERE, "..", "include", "hermnet_hip.h")]
+    paths = [os.path.join(csrc, f) for f in files] + [HEADER_PATH]
     h = hashlib.sha256()
     for p in paths:
         with open(p, "rb") as fh:
@@ -218,10 +123,11 @@ def build_info():
 
 
 def load():
-    """Load the native library (once).  Raises RuntimeError if it has not been built."""
+    """Load the native library (once).  Raises RuntimeError if it has not been built, or if the header is missing."""
     global _lib
     if _lib is not None:
         return _lib
+    _bind()
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             "hermnet_amd: native library %s not found -- run `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -249,22 +155,31 @@ def load():
     return lib
 
 
+def check(rc, what):
+    if rc != 0:
+        raise RuntimeError("%s failed: %s" % (what, _ERR.get(rc, "error %d" % rc)))
+
+
+def call(c_name, *args):
+    """The library's `c_name(*args)`; a return code other than HN_OK raises RuntimeError under the entry point's own name."""
+    rc = getattr(load(), c_name)(*args)
+    if rc != 0:
+        check(rc, c_name)
+
+
 # hermnet_set_option / hermnet_get_option (include/hermnet_hip.h: HN_OPT_*): tuning knobs and the alternative kernel forms
 # that tests and A/Bs compare against -- process-wide, read by the launchers at every call (ids 0-3: retired)
-OPTIONS = {"fwd_rows": 4, "bwd_rows": 5, "bwd_cl_rows": 6, "bwd_lanes16": 7, "node_chain_wide": 8, "update_tile16": 9,
-           "update_tile64_max": 10}
-
-
 def get_option(name):
     v = ctypes.c_int(0)
-    check(load().hermnet_get_option(OPTIONS[name], ctypes.byref(v)), "hermnet_get_option")
+    load()
+    call("hermnet_get_option", OPTIONS[name], ctypes.byref(v))
     return int(v.value)
 
 
 def set_option(name, value):
     """Set a library option; returns the previous value."""
     old = get_option(name)
-    check(load().hermnet_set_option(OPTIONS[name], int(value)), "hermnet_set_option")
+    call("hermnet_set_option", OPTIONS[name], int(value))
     return old
 
 
@@ -282,11 +197,6 @@ class options(object):
     def __exit__(self, *exc):
         for k, v in self.old.items():
             set_option(k, v)
-
-
-def check(rc, what):
-    if rc != 0:
-        raise RuntimeError("%s failed: %s" % (what, _ERR.get(rc, "error %d" % rc)))
 
 
 def ptr(t):

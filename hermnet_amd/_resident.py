@@ -13,12 +13,11 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib
+from ._lib import HN_MD_LANGEVIN, HN_MD_WRAP  # noqa: F401  (md.py, relax.py: the advance flags)
+from ._lib import HN_MD_HALT_NONFINITE as HALT_NONFINITE  # halt code: an energy that is not finite
 
-HALT_NONFINITE = 256                      # halt code: an energy that is not finite
 HALT_CAPACITY = 4                         # ... list flag bit 2: more pairs than columns
 PARKED = 1 << 20                          # host-side halt code while a capture is made: its replays must not move anything
-HN_MD_LANGEVIN, HN_MD_WRAP = 1, 2        # include/hermnet_hip.h
 
 
 def host_f64(a):
@@ -65,7 +64,7 @@ class ResidentDriver(object):
     `_advance(step)` in front of the search and `_finish(step, out)` behind the force backward, and `_unpark()` (what follows
     a capture: the halt words cleared, the state ready for `run`)."""
 
-    __slots__ = ("device", "model", "lib", "z", "n", "num_graphs", "_batch_h", "batch", "graph_ptr", "x", "x0", "v", "image",
+    __slots__ = ("device", "model", "z", "n", "num_graphs", "_batch_h", "batch", "graph_ptr", "x", "x0", "v", "image",
                  "image0", "f_prev", "state", "log", "log_steps", "wrap", "inv_cell", "_inv_of", "step", "_logged", "_pending",
                  "_host")
     LOG_WIDTH = None                      # columns of a log row: the subclass's
@@ -81,7 +80,6 @@ class ResidentDriver(object):
             raise RuntimeError("%s needs GPU tensors" % name)
         self.device = dev                 # the GPU everything lives on
         self.model = model                # the HVNet of the captured step; `_after_halt` drops its caches
-        self.lib = _lib.load()            # the native library
         self.z = torch.as_tensor(atomic_number).long().to(dev)    # atomic numbers [N]
         n = self.n = int(self.z.numel())  # atoms
         self.num_graphs = 1 if batch is None else int(num_graphs if num_graphs is not None else int(torch.as_tensor(batch)[-1]) + 1)

@@ -77,10 +77,9 @@ class ParamGuard(object):
 
     def _launch(self, check, poison):
         stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(_lib.load().hermnet_param_guard(self.ptrs.data_ptr(), self.counts.data_ptr(), int(self.counts.numel()),
-                                                   self.fp.data_ptr(), 1 if check else 0,
-                                                   None if poison is None else poison.data_ptr(), self.flag.data_ptr(), stream),
-                   "hermnet_param_guard")
+        _lib.call("hermnet_param_guard", self.ptrs.data_ptr(), self.counts.data_ptr(), int(self.counts.numel()),
+                  self.fp.data_ptr(), 1 if check else 0, None if poison is None else poison.data_ptr(), self.flag.data_ptr(),
+                  stream)
 
     def tripped(self, wait=False):
         """Has a check found the parameters changed behind the cached copies?  Non-blocking unless `wait` (False also while

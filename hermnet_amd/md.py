@@ -38,7 +38,7 @@ AMU_A2_FS2_TO_EV = 103.642696562         # 1 amu A^2 / fs^2 in eV (tools/md_nve.
 KB = 8.617333262e-5                       # eV / K
 ASE_TIME_FS = math.sqrt(AMU_A2_FS2_TO_EV)   # ASE's time unit in fs: v [A/fs] = v_ase / 10.18051
 GPA = 1.0 / 160.2176634                   # 1 GPa in eV / A^3
-HN_MD_BARO = {"isotropic": 0, "axes": 1, "full": 2}     # include/hermnet_hip.h: HN_MD_BARO_*
+HN_MD_BARO = {"isotropic": _lib.HN_MD_BARO_ISOTROPIC, "axes": _lib.HN_MD_BARO_AXES, "full": _lib.HN_MD_BARO_FULL}
 
 
 class DeviceMD(ResidentDriver):
@@ -101,19 +101,18 @@ class DeviceMD(ResidentDriver):
         P = _lib.ptr
         wrap, cell, inv = self._cell_args(step)
         flags = (self.flags | HN_MD_WRAP) if wrap else (self.flags & ~HN_MD_WRAP)
-        _lib.check(self.lib.hermnet_md_advance(
-            self.n, self.num_graphs, flags, self.dt, self.seed, P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image),
-            P(self.image0), P(self.f_prev), P(self.kick), P(self.c1), P(self.sigma), P(self.batch), cell, inv,
-            P(self._pos_input(step)), P(self.state), torch.cuda.current_stream(self.device).cuda_stream), "hermnet_md_advance")
+        _lib.call("hermnet_md_advance", self.n, self.num_graphs, flags, self.dt, self.seed, P(self.x), P(self.v), P(self.x0),
+                  P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick), P(self.c1), P(self.sigma),
+                  P(self.batch), cell, inv, P(self._pos_input(step)), P(self.state),
+                  torch.cuda.current_stream(self.device).cuda_stream)
 
     def _finish(self, step, out):
         P = _lib.ptr
         energy, forces, total = self._step_outputs(out)
-        _lib.check(self.lib.hermnet_md_finish(
-            self.n, self.num_graphs, P(self.graph_ptr), P(forces), P(energy), P(total), int(step.capacity), P(self.x), P(self.v),
-            P(self.x0), P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos),
-            P(self.ke_atom), P(self.log), self.log_steps, P(self.state),
-            torch.cuda.current_stream(self.device).cuda_stream), "hermnet_md_finish")
+        _lib.call("hermnet_md_finish", self.n, self.num_graphs, P(self.graph_ptr), P(forces), P(energy), P(total),
+                  int(step.capacity), P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image), P(self.image0),
+                  P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos), P(self.ke_atom), P(self.log), self.log_steps,
+                  P(self.state), torch.cuda.current_stream(self.device).cuda_stream)
 
     def _unpark(self):
         """Clear the halt and evaluate the forces of the current coordinates with the captured graph (mode word 1: no kick,
@@ -264,12 +263,12 @@ class DeviceNPT(DeviceMD):
             raise RuntimeError("DeviceNPT: the captured step must return a contiguous float32 virial [B,3,3]")
         if cell is None or cell.dtype != torch.float32 or not cell.is_contiguous() or cell.numel() != 9 * B:
             raise RuntimeError("DeviceNPT: the step's cell must be a contiguous float32 [B,3,3]")
-        _lib.check(self.lib.hermnet_md_finish_npt(
-            self.n, B, P(self.graph_ptr), P(self.batch), P(forces), P(energy), P(virial), P(total), int(step.capacity),
-            HN_MD_BARO[self.coupling], self.mask, self.max_strain, P(self.p0), P(self.coupling_c), P(self.x), P(self.v),
-            P(self.x0), P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos),
-            P(self.ke_atom), P(self.cell64), P(cell), P(self.inv_cell), P(self.mu), P(self.clamped), P(self.log), self.log_steps,
-            P(self.state), torch.cuda.current_stream(self.device).cuda_stream), "hermnet_md_finish_npt")
+        _lib.call("hermnet_md_finish_npt", self.n, B, P(self.graph_ptr), P(self.batch), P(forces), P(energy), P(virial),
+                  P(total), int(step.capacity), HN_MD_BARO[self.coupling], self.mask, self.max_strain, P(self.p0),
+                  P(self.coupling_c), P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image), P(self.image0),
+                  P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos), P(self.ke_atom), P(self.cell64), P(cell),
+                  P(self.inv_cell), P(self.mu), P(self.clamped), P(self.log), self.log_steps, P(self.state),
+                  torch.cuda.current_stream(self.device).cuda_stream)
 
     def resume(self):
         """`DeviceMD.resume`, and the last accepted forces stay: they are those of the configuration BEFORE the last scaling

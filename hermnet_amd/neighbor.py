@@ -224,7 +224,7 @@ def _device_search(pos, rc, cell, reference_compat, target_mask=None, device_cel
         ws_bytes = lib.hermnet_neighbor_batch_workspace(N, B, hint)
         if ws_bytes == 0:
             raise RuntimeError("batched neighbour search: %d atoms in %d graphs are beyond the search's index range" % (N, B))
-        count, head = lib.hermnet_neighbor_batch_count, (P(p32), N, P(b64), B, P(cells), float(rc))
+        count, head = "hermnet_neighbor_batch_count", (P(p32), N, P(b64), B, P(cells), float(rc))
     else:
         ws_bytes = lib.hermnet_neighbor_workspace_for(N, hint)
         if device_cell:
@@ -232,7 +232,7 @@ def _device_search(pos, rc, cell, reference_compat, target_mask=None, device_cel
                 raise ValueError("device_cell=True needs a contiguous float32 [3,3] cell on the GPU")
             if N == 0:
                 raise ValueError("device_cell=True needs at least one atom")
-            count, head = lib.hermnet_neighbor_count_devcell, (P(p32), N, P(cell), float(rc))
+            count, head = "hermnet_neighbor_count_devcell", (P(p32), N, P(cell), float(rc))
         else:
             dbl3 = ctypes.c_double * 3
             cell_h, lo_h, hi_h = None, dbl3(0, 0, 0), dbl3(1, 1, 1)
@@ -241,7 +241,7 @@ def _device_search(pos, rc, cell, reference_compat, target_mask=None, device_cel
             elif N > 0:       # (an open structure's bounding box is a host read of its own: periodic cells are the MD case)
                 mm = torch.stack([p32.min(0).values, p32.max(0).values]).double().cpu().tolist()
                 lo_h, hi_h = dbl3(*mm[0]), dbl3(*mm[1])
-            count, head = lib.hermnet_neighbor_count, (P(p32), N, cell_h, lo_h, hi_h, float(rc))
+            count, head = "hermnet_neighbor_count", (P(p32), N, cell_h, lo_h, hi_h, float(rc))
         if target_mask is not None:
             mask = (target_mask if target_mask.dtype == torch.uint8 else target_mask.to(torch.uint8)).contiguous()
             if mask.numel() != N or mask.device != dev:
@@ -249,7 +249,7 @@ def _device_search(pos, rc, cell, reference_compat, target_mask=None, device_cel
     work = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     total = torch.empty(2, dtype=torch.long, device=dev) if padded else torch.zeros(2, dtype=torch.long, device=dev)
     masks = () if batched else (P(mask),)             # (target masks are not part of the batched entry points)
-    _lib.check(count(*head, P(work), ws_bytes, *masks, P(total), stream), count.__name__)
+    _lib.call(count, *head, P(work), ws_bytes, *masks, P(total), stream)
     source_first = 0 if periodic else 1
     sign = 1.0 if reference_compat else -1.0
     if padded:
@@ -261,9 +261,8 @@ def _device_search(pos, rc, cell, reference_compat, target_mask=None, device_cel
             edge_index.fill_(0x3f3f3f3f3f3f3f3f)
             if shift is not None:
                 shift.fill_(float("nan"))
-        fill, shape = (lib.hermnet_neighbor_batch_fill_padded, (N, B)) if batched else (lib.hermnet_neighbor_fill_padded, (N,))
-        _lib.check(fill(*shape, P(work), ws_bytes, cap, sign, source_first, P(edge_index), P(shift), P(total), stream),
-                   fill.__name__)
+        fill, shape = ("hermnet_neighbor_batch_fill_padded", (N, B)) if batched else ("hermnet_neighbor_fill_padded", (N,))
+        _lib.call(fill, *shape, P(work), ws_bytes, cap, sign, source_first, P(edge_index), P(shift), P(total), stream)
         return edge_index, shift, total
     E, flags = total.tolist()                                # the one host read of the search
     if batched:
@@ -277,9 +276,9 @@ def _device_search(pos, rc, cell, reference_compat, target_mask=None, device_cel
     if E > 0:
         stash_ok = 0 if (flags & 2) else 1
         keys = None if stash_ok else torch.empty(E, dtype=torch.long, device=dev)
-        fill, shape = (lib.hermnet_neighbor_batch_fill, (N, B)) if batched else (lib.hermnet_neighbor_fill, head)
-        _lib.check(fill(*shape, P(work), ws_bytes, E, sign, source_first, stash_ok, P(keys), *masks, P(edge_index), P(shift),
-                        stream), fill.__name__)
+        fill, shape = ("hermnet_neighbor_batch_fill", (N, B)) if batched else ("hermnet_neighbor_fill", head)
+        _lib.call(fill, *shape, P(work), ws_bytes, E, sign, source_first, stash_ok, P(keys), *masks, P(edge_index), P(shift),
+                  stream)
     return (edge_index, shift) if periodic else edge_index
 
 

@@ -1,30 +1,19 @@
 """Thin Python wrappers (allocate outputs, pass pointers) around the node-level fused
-kernels of `csrc/node_kernels.hip`.  One call = one kernel launch on the current stream."""
+kernels of `csrc/node_kernels.hip`.  One call = one kernel launch on the current stream, through `ops._call` under its
+timer label."""
 
 import ctypes
 
 import torch
 
-from . import _lib, ops
-from .ops import _launch, _stream
+from . import _lib
+from .ops import _call
 
 P = _lib.ptr
 
 
 def _new(like, *shape):
     return torch.empty(*shape, dtype=like.dtype, device=like.device)
-
-
-def _call(timer_name, c_name, *args):
-    """One launch: the library's `c_name(*args, current stream)` under the timer label `timer_name`; an error code raises.
-    Without a timer installed the entry point is called directly: no closure per launch on the training step's ~400 calls."""
-    fn = getattr(_lib.load(), c_name)
-    if ops._TIMER is None:
-        rc = fn(*args, _stream())
-    else:
-        rc = _launch(timer_name, lambda: fn(*args, _stream()))
-    if rc != 0:
-        _lib.check(rc, c_name)
 
 
 def layernorm_fwd(x, eps=1e-5, h_real=0):

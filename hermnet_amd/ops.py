@@ -1,6 +1,9 @@
 """Autograd wrappers around the C-ABI kernels (host side of the operator boundary,
 SURVEY.md section 8(b)).  Tensors are allocated by PyTorch; the library only enqueues
-kernels on the current stream.  CUDA(HIP) tensors only -- there is no CPU path."""
+kernels on the current stream.  CUDA(HIP) tensors only -- there is no CPU path.
+
+The launch helper of the whole package lives here, beside the timer it serves: `_call(label, c_name, *args)` (this module,
+`nodeops`, `trainops`); calls without a label take `_lib.call`."""
 import ctypes
 from types import SimpleNamespace
 
@@ -51,6 +54,18 @@ def _launch(name, fn):
 def _stream():
     """hipStream_t of PyTorch's current stream as an integer (the raw getter: no Stream object per launch)."""
     return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
+
+
+def _call(label, c_name, *args):
+    """One launch: the library's `c_name(*args, current stream)` under the timer label `label`; an error code raises.
+    Without a timer installed the entry point is called directly: no closure per launch (profiles/train_refactor_ab.md)."""
+    fn = getattr(_lib.load(), c_name)
+    if _TIMER is None:
+        rc = fn(*args, _stream())
+    else:
+        rc = _launch(label, lambda: fn(*args, _stream()))
+    if rc != 0:
+        _lib.check(rc, c_name)
 
 
 def _require_gpu(t, what):
@@ -109,8 +124,8 @@ def graph_virial(vrows, graph):
     out = torch.empty(B, 9, dtype=torch.float32, device=vrows.device)
     wbytes = lib.hermnet_graph_virial_workspace(n)
     work = torch.empty(wbytes, dtype=torch.uint8, device=vrows.device)
-    _lib.check(lib.hermnet_graph_virial(P(vrows), P(graph.row_of_node), P(graph.graph_perm), P(graph.batch32), n, B, P(work), wbytes,
-                                        P(out), _stream()), "hermnet_graph_virial")
+    _lib.call("hermnet_graph_virial", P(vrows), P(graph.row_of_node), P(graph.graph_perm), P(graph.batch32), n, B, P(work), wbytes,
+              P(out), _stream())
     return out.view(B, 3, 3)
 
 
@@ -121,17 +136,14 @@ class EdgeGeometry(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, cell, graph, sink=None):
         _require_gpu(pos, "EdgeGeometry")
-        lib = _lib.load()
         pos_c = pos.detach().float().contiguous()
         edge = torch.empty(graph.E, 4, dtype=torch.float32, device=pos.device)
         cell_c = None
         if graph.shift is not None and cell is not None:
             cell_c = cell.detach().float().reshape(-1, 3, 3).contiguous()
         batch32 = graph.batch32
-        _lib.check(lib.hermnet_edge_geometry_fwd(
-            _lib.ptr(pos_c), _lib.ptr(graph.src_id), _lib.ptr(graph.tgt_id),
-            _lib.ptr(graph.shift if cell_c is not None else None), _lib.ptr(cell_c), _lib.ptr(batch32),
-            graph.E, _lib.ptr(edge), _stream()), "hermnet_edge_geometry_fwd")
+        _lib.call("hermnet_edge_geometry_fwd", P(pos_c), P(graph.src_id), P(graph.tgt_id),
+                  P(graph.shift if cell_c is not None else None), P(cell_c), P(batch32), graph.E, P(edge), _stream())
         ctx.graph, ctx.sink = graph, sink
         ctx.keep = (pos_c, cell_c)
         ctx.cell_shape = None if cell is None else tuple(cell.shape)
@@ -140,7 +152,6 @@ class EdgeGeometry(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gedge):
         graph = ctx.graph
-        lib = _lib.load()
         gD = gedge.float().contiguous()
         gpos_rows = torch.empty(graph.num_src or graph.N, 3, dtype=torch.float32, device=gD.device)
         if graph.num_src:
@@ -159,25 +170,21 @@ class EdgeGeometry(torch.autograd.Function):
             pos_c, cell_c = ctx.keep
             csc = graph.out_rowptr is None
             vrows = torch.empty(graph.N, 9, dtype=torch.float32, device=gD.device)
-            _lib.check(lib.hermnet_edge_geometry_bwd_virial(
-                _lib.ptr(gD), _lib.ptr(graph.csr_rowptr), _lib.ptr(graph.csc_rowptr if csc else None),
-                _lib.ptr(graph.csc_pos if csc else None), graph.T if csc else 0,
-                _lib.ptr(None if csc else graph.out_rowptr), _lib.ptr(None if csc else graph.out_edges), _lib.ptr(pos_c),
-                _lib.ptr(graph.src_id), _lib.ptr(graph.tgt_id), _lib.ptr(graph.shift if cell_c is not None else None),
-                _lib.ptr(cell_c), _lib.ptr(graph.batch32), graph.N, _lib.ptr(gpos_rows), _lib.ptr(vrows), _stream()),
-                "hermnet_edge_geometry_bwd_virial")
+            _lib.call("hermnet_edge_geometry_bwd_virial", P(gD), P(graph.csr_rowptr), P(graph.csc_rowptr if csc else None),
+                      P(graph.csc_pos if csc else None), graph.T if csc else 0, P(None if csc else graph.out_rowptr),
+                      P(None if csc else graph.out_edges), P(pos_c), P(graph.src_id), P(graph.tgt_id),
+                      P(graph.shift if cell_c is not None else None), P(cell_c), P(graph.batch32), graph.N, P(gpos_rows),
+                      P(vrows), _stream())
             if ctx.sink.want_virials:
                 ctx.sink.virials = vrows.index_select(0, graph.row_of_node).view(-1, 3, 3)
             if ctx.sink.want_graph_virial:
                 ctx.sink.graph_virial = graph_virial(vrows, graph)
         elif graph.out_rowptr is None:      # device-built graphs: out-edges from the CSC order (one sort fewer)
-            _lib.check(lib.hermnet_edge_geometry_bwd_csc(
-                _lib.ptr(gD), _lib.ptr(graph.csr_rowptr), _lib.ptr(graph.csc_rowptr), _lib.ptr(graph.csc_pos),
-                graph.T, graph.N, _lib.ptr(gpos_rows), _stream()), "hermnet_edge_geometry_bwd_csc")
+            _lib.call("hermnet_edge_geometry_bwd_csc", P(gD), P(graph.csr_rowptr), P(graph.csc_rowptr), P(graph.csc_pos),
+                      graph.T, graph.N, P(gpos_rows), _stream())
         else:
-            _lib.check(lib.hermnet_edge_geometry_bwd(
-                _lib.ptr(gD), _lib.ptr(graph.csr_rowptr), None, _lib.ptr(graph.out_rowptr),
-                _lib.ptr(graph.out_edges), graph.N, _lib.ptr(gpos_rows), _stream()), "hermnet_edge_geometry_bwd")
+            _lib.call("hermnet_edge_geometry_bwd", P(gD), P(graph.csr_rowptr), None, P(graph.out_rowptr), P(graph.out_edges),
+                      graph.N, P(gpos_rows), _stream())
         gcell = None
         if ctx.needs_input_grad[1] and ctx.keep[1] is not None:
             # D = ... + shift @ cell[batch[src]]  =>  dE/dcell[b] = sum_{e in b} shift_e (x) gD_e
@@ -216,7 +223,6 @@ def _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=True, ranges=None, zero
     """`xh_bias=False`: xh already includes x_proj's bias (chain kernels).  `ranges` [T,2] int32 (device): only these
     target rows of every relation (atom shards: two launches over complementary ranges around the halo exchange;
     the second passes the first one's result as `out`); `range_rows`: how many rows they cover (host int)."""
-    lib = _lib.load()
     b2 = w.b2 if xh_bias else None
     if out is None:
         x1 = torch.empty(graph.N, H, dtype=x.dtype, device=x.device)          # target rows (= source rows unless HTNet)
@@ -225,11 +231,9 @@ def _msg_fwd(graph, rbf, H, xh, vec, x, w, edge, xh_bias=True, ranges=None, zero
         x1, vec1 = out
     gs, rs = graph.as_struct(), rbf.struct()
     # (graph.fwd_taps: the step's per-edge tap records, or None -- the kernel then evaluates them itself; same bits)
-    _lib.check(_launch("message_scatter_fwd" + ("" if vec is not None else "_l0"),
-                       lambda: lib.hermnet_message_scatter_fwd_taps(
-                           ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(b2), P(vec), P(x), P(w.wt), P(w.brbf), P(edge),
-                           P(graph.fwd_taps), P(x1), P(vec1), P(ranges), 1 if zero_unknown else 0, int(range_rows), _stream())),
-               "hermnet_message_scatter_fwd_taps")
+    _call("message_scatter_fwd" + ("" if vec is not None else "_l0"), "hermnet_message_scatter_fwd_taps",
+          ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(b2), P(vec), P(x), P(w.wt), P(w.brbf), P(edge),
+          P(graph.fwd_taps), P(x1), P(vec1), P(ranges), 1 if zero_unknown else 0, int(range_rows))
     return x1, vec1
 
 
@@ -237,51 +241,34 @@ def _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=True, r
     """`gedge` [H/64, E, 4] (zero-filled by the caller) receives the per-column-block Cartesian edge gradients.
     `ranges` = (device [k,2] int32, host list of (lo, hi)): only these SOURCE rows (atom shards: the halo rows first,
     the others while their gradients travel; the second call passes the first one's buffers as `out`).
+    -> (gxh, gvec, gx), with `ranges` (gxh, gvec, gx, part): the buffers a second call takes as `out`.
     `finish=False` (only where `_bwd_sums_deferrable`): no finishing launch -- returns (gxh, per-relation partial sums of
     gvec [T,N,3,H] or None); the sums over the relations and the residual's identity terms are the consumer's."""
-    lib = _lib.load()
     b2 = w.b2 if xh_bias else None
-    if not finish:
-        if out is None:
-            gxh = torch.empty_like(xh)
-            part = None if vec is None else torch.empty((graph.T,) + tuple(vec.shape), dtype=vec.dtype, device=vec.device)
-        else:
-            gxh, part = out
-        rd, rh, nr = None, None, 0
-        if ranges is not None:         # (the "proj" halo exchange: the halo source rows first, the others while they travel)
-            rd, host = ranges
-            nr = len(host)
-            rh = (ctypes.c_int * (2 * nr))(*[v for lo_hi in host for v in lo_hi])
-        gs, rs = graph.as_struct(), rbf.struct()
-        _lib.check(_launch("message_scatter_bwd" + ("" if vec is not None else "_l0"),
-                           lambda: lib.hermnet_message_scatter_bwd(
-                               ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(b2), P(vec), P(w.wt), P(w.brbf), P(edge),
-                               P(gx1), P(gvec1), P(gxh), None, None, P(gedge), 0, P(graph.edge_table), P(part),
-                               P(rd), rh, nr, _stream())),
-                   "hermnet_message_scatter_bwd")
-        return gxh, part
-    if out is None:
-        gxh = torch.empty_like(xh)
-        gvec = None if vec is None else torch.empty_like(vec)
-        gx = torch.empty(xh.size(1), H, dtype=gx1.dtype, device=gx1.device)   # source rows
-        # workspace of the channel-per-lane form: per-relation partial sums of gvec
-        part = None
-        if graph.edge_table is not None and vec is not None and graph.T > 1:
-            part = torch.empty((graph.T,) + tuple(vec.shape), dtype=vec.dtype, device=vec.device)
+    gvec = gx = None                   # (finish=False: the library leaves the finishing launch out when gx is NULL)
+    if out is not None:
+        gxh, gvec, gx, part = out if finish else (out[0], None, None, out[1])
     else:
-        gxh, gvec, gx, part = out
+        gxh = torch.empty_like(xh)
+        if finish:
+            gvec = None if vec is None else torch.empty_like(vec)
+            gx = torch.empty(xh.size(1), H, dtype=gx1.dtype, device=gx1.device)   # source rows
+        # per-relation partial sums of gvec: the result itself without the finishing launch, with it the workspace of the
+        # channel-per-lane form
+        part = None
+        if vec is not None and (not finish or (graph.edge_table is not None and graph.T > 1)):
+            part = torch.empty((graph.T,) + tuple(vec.shape), dtype=vec.dtype, device=vec.device)
     rd, rh, nr = None, None, 0
     if ranges is not None:
         rd, host = ranges
         nr = len(host)
         rh = (ctypes.c_int * (2 * nr))(*[v for lo_hi in host for v in lo_hi])
     gs, rs = graph.as_struct(), rbf.struct()
-    _lib.check(_launch("message_scatter_bwd" + ("" if vec is not None else "_l0"),
-                       lambda: lib.hermnet_message_scatter_bwd(
-                           ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(b2), P(vec), P(w.wt), P(w.brbf), P(edge),
-                           P(gx1), P(gvec1), P(gxh), P(gvec), P(gx), P(gedge), 0, P(graph.edge_table), P(part),
-                           P(rd), rh, nr, _stream())),
-               "hermnet_message_scatter_bwd")
+    _call("message_scatter_bwd" + ("" if vec is not None else "_l0"), "hermnet_message_scatter_bwd",
+          ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(b2), P(vec), P(w.wt), P(w.brbf), P(edge), P(gx1), P(gvec1),
+          P(gxh), P(gvec), P(gx), P(gedge), 0, P(graph.edge_table), P(part), P(rd), rh, nr)
+    if not finish:
+        return gxh, part
     if ranges is not None:
         return gxh, gvec, gx, part
     return gxh, gvec, gx
@@ -290,13 +277,9 @@ def _msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=True, r
 def _msg_bwd_gedge(graph, rbf, H, xh, w, edge, gx1, gvec1, gedge):
     """The message backward of a FIRST layer whose inputs carry no gradient (no vec rows; `_bwd_sums_deferrable`): only
     `gedge` is written -- no source-row sums, no gxh buffer."""
-    lib = _lib.load()
     gs, rs = graph.as_struct(), rbf.struct()
-    _lib.check(_launch("message_scatter_bwd_l0",
-                       lambda: lib.hermnet_message_scatter_bwd_gedge(
-                           ctypes.byref(gs), ctypes.byref(rs), H, P(xh), P(w.wt), P(w.brbf), P(edge),
-                           P(gx1), P(gvec1), P(gedge), P(graph.edge_table), _stream())),
-               "hermnet_message_scatter_bwd_gedge")
+    _call("message_scatter_bwd_l0", "hermnet_message_scatter_bwd_gedge", ctypes.byref(gs), ctypes.byref(rs), H, P(xh),
+          P(w.wt), P(w.brbf), P(edge), P(gx1), P(gvec1), P(gedge), P(graph.edge_table))
 
 
 class MessageScatter(torch.autograd.Function):
@@ -336,8 +319,7 @@ def edge_radial_table(graph, rbf, edge):
     E = edge.size(0)
     table = torch.empty(E + 1, 32, dtype=torch.float32, device=edge.device)      # (+1: the stream reads one record ahead)
     gs, rs = graph.as_struct(), rbf.struct()
-    _lib.check(_launch("edge_radial_table", lambda: _lib.load().hermnet_edge_radial_table(
-        ctypes.byref(gs), ctypes.byref(rs), _lib.ptr(edge), _lib.ptr(table), _stream())), "hermnet_edge_radial_table")
+    _call("edge_radial_table", "hermnet_edge_radial_table", ctypes.byref(gs), ctypes.byref(rs), P(edge), P(table))
     return table
 
 
@@ -349,7 +331,5 @@ def edge_radial_tables(graph, rbf, edge):
     table = torch.empty(E + 1, 32, dtype=torch.float32, device=edge.device)
     taps = torch.empty(E, 16, dtype=torch.float32, device=edge.device)
     gs, rs = graph.as_struct(), rbf.struct()
-    _lib.check(_launch("edge_radial_table", lambda: _lib.load().hermnet_edge_radial_tables(
-        ctypes.byref(gs), ctypes.byref(rs), _lib.ptr(edge), _lib.ptr(table), _lib.ptr(taps), _stream())),
-        "hermnet_edge_radial_tables")
+    _call("edge_radial_table", "hermnet_edge_radial_tables", ctypes.byref(gs), ctypes.byref(rs), P(edge), P(table), P(taps))
     return table, taps

@@ -92,8 +92,7 @@ class AtomSet(object):
         self.z64 = atomic_number.to(torch.int64, copy=True).contiguous()        # here (the set's own copy); the native builds' kernels
         if atomic_number.is_cuda and switches.native_relations:
             counts = torch.empty(T + 1, dtype=torch.int32, device=dev)
-            _lib.check(_lib.load().hermnet_relation_counts(_lib.ptr(self.z64), NA, _lib.ptr(self.zl), T, _lib.ptr(counts),
-                                                           _stream()), "hermnet_relation_counts")
+            _lib.call("hermnet_relation_counts", _lib.ptr(self.z64), NA, _lib.ptr(self.zl), T, _lib.ptr(counts), _stream())
         else:
             counts = _classify(self.z64, z_list)[1]
         nb = batch.long().max().reshape(1) + 1 if (batch is not None and NA > 0) else torch.ones(1, dtype=torch.long, device=dev)
@@ -358,9 +357,8 @@ class RelationalGraph(object):
         act = _active_relations(rel_active, atoms)
         wbytes = lib.hermnet_build_relations_workspace(NA, N, E, T)
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.hermnet_build_relations(P(atoms.z64), P(ei), P(shift), NA, E, P(atoms.zl), T, P(rows.type_rowptr), N, P(act),
-                                               ctypes.byref(out), 1 if rows_ready else 0, P(work), wbytes, _stream()),
-                   "hermnet_build_relations")
+        _lib.call("hermnet_build_relations", P(atoms.z64), P(ei), P(shift), NA, E, P(atoms.zl), T, P(rows.type_rowptr), N, P(act),
+                  ctypes.byref(out), 1 if rows_ready else 0, P(work), wbytes, _stream())
         atoms.keep_rows(g, key, rows)
         g.graph_perm, g.graph_lengths = atoms.graph_order()
         return g
@@ -429,9 +427,8 @@ class RelationalGraph(object):
         wbytes = lib.hermnet_build_triadic_workspace(NA, E0, T, B)
         work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
         act = _active_relations(rel_active, atoms)
-        _lib.check(lib.hermnet_build_triadic(P(atoms.z64), P(ei), P(shift), NA, E0, P(atoms.zl), T, B, P(atoms.triadic_counts),
-                                             P(act), ctypes.byref(out), P(tgt_real), P(g.res_row), 1 if rows_ready else 0,
-                                             P(work), wbytes, _stream()), "hermnet_build_triadic")
+        _lib.call("hermnet_build_triadic", P(atoms.z64), P(ei), P(shift), NA, E0, P(atoms.zl), T, B, P(atoms.triadic_counts),
+                  P(act), ctypes.byref(out), P(tgt_real), P(g.res_row), 1 if rows_ready else 0, P(work), wbytes, _stream())
         atoms.keep_rows(g, key, rows)
         g.src_real = g.row_real                                    # the energy read-out masks SOURCE rows
         g.src_ranges = atoms.triadic_src_ranges()

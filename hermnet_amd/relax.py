@@ -89,19 +89,18 @@ class DeviceRelax(ResidentDriver):
     def _advance(self, step):
         P = _lib.ptr
         wrap, cell, inv = self._cell_args(step)
-        _lib.check(self.lib.hermnet_relax_advance(
-            self.n, self.num_graphs, HN_MD_WRAP if wrap else 0, P(self.x), P(self.x0), P(self.v), P(self.image), P(self.image0),
-            P(self.fixed), P(self.batch), cell, inv, P(self._pos_input(step)), P(self.state), P(self.gf), P(self.gi),
-            torch.cuda.current_stream(self.device).cuda_stream), "hermnet_relax_advance")
+        _lib.call("hermnet_relax_advance", self.n, self.num_graphs, HN_MD_WRAP if wrap else 0, P(self.x), P(self.x0), P(self.v),
+                  P(self.image), P(self.image0), P(self.fixed), P(self.batch), cell, inv, P(self._pos_input(step)),
+                  P(self.state), P(self.gf), P(self.gi), torch.cuda.current_stream(self.device).cuda_stream)
 
     def _finish(self, step, out):
         P = _lib.ptr
         energy, forces, total = self._step_outputs(out)
-        _lib.check(self.lib.hermnet_relax_finish(
-            self.n, self.num_graphs, P(self.graph_ptr), P(forces), P(energy), P(total), int(step.capacity), self.dt, self.dtmax,
-            self.maxstep, self._fmax0, P(self.fmax), P(self.x), P(self.v), P(self.x0), P(self.image), P(self.image0), P(self.f_prev),
-            P(self.fixed), P(step.pos), P(self.gf), P(self.gi), P(self.gf_new), P(self.gi_new), P(self.log), self.log_steps,
-            P(self.state), torch.cuda.current_stream(self.device).cuda_stream), "hermnet_relax_finish")
+        _lib.call("hermnet_relax_finish", self.n, self.num_graphs, P(self.graph_ptr), P(forces), P(energy), P(total),
+                  int(step.capacity), self.dt, self.dtmax, self.maxstep, self._fmax0, P(self.fmax), P(self.x), P(self.v),
+                  P(self.x0), P(self.image), P(self.image0), P(self.f_prev), P(self.fixed), P(step.pos), P(self.gf), P(self.gi),
+                  P(self.gf_new), P(self.gi_new), P(self.log), self.log_steps, P(self.state),
+                  torch.cuda.current_stream(self.device).cuda_stream)
 
     def _unpark(self):
         """Parked while the capture was made: nothing has moved, so the halt words are cleared and that is all."""

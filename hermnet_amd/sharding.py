@@ -964,11 +964,9 @@ def _slab_step(plan, pos, reference_compat=False, capacity=None, want_moved=Fals
         ask = bool(want_moved) and plan.pos_ref.shape == pos.shape
         if ask:
             cur, ref = pos.detach().contiguous(), plan.pos_ref.contiguous()
-        _lib.check(_lib.load().hermnet_shard_step_flags(
-            P(ei), int(ei.size(1)), P(z), int(z.numel()), None if total is None else P(total),
-            0 if capacity is None else int(capacity), P(flags), P(cur) if ask else None, P(ref) if ask else None,
-            int(pos.size(0)) if ask else 0, float((0.5 * plan.skin) ** 2),
-            torch.cuda.current_stream(dev).cuda_stream), "hermnet_shard_step_flags")
+        _lib.call("hermnet_shard_step_flags", P(ei), int(ei.size(1)), P(z), int(z.numel()), None if total is None else P(total),
+                  0 if capacity is None else int(capacity), P(flags), P(cur) if ask else None, P(ref) if ask else None,
+                  int(pos.size(0)) if ask else 0, float((0.5 * plan.skin) ** 2), torch.cuda.current_stream(dev).cuda_stream)
         has_in = flags[:128 * 128 + 2]
         if ask:
             moved = flags[128 * 128 + 2]

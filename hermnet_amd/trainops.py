@@ -8,7 +8,7 @@ the parameters, so every op here is differentiable TWICE): the autograd function
   BucketedBasis / TallLinear  rbf_proj (rmnet.py:55) on the distance-bucketed basis / on a dense basis
   message_scatter_generic     rbf_proj + gather + message + aggregation + residual of ALL relations of a layer
 
-Every launch goes through `nodeops._call` under a timer label (the C name without `hermnet_`; for hermnet_train_node_op the
+Every launch goes through `ops._call` under a timer label (the C name without `hermnet_`; for hermnet_train_node_op the
 name of the op in `NODE_OPS`), every kernel-written buffer comes from `_new`.
 """
 import ctypes
@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, switches
-from .nodeops import _call
+from .ops import _call
 
 P = _lib.ptr
 

@@ -16,7 +16,7 @@
  *   - float = IEEE fp32 (the reference is fp32-only), indices = int32 (int64 where a parameter says so:
  *     the caller's edge_index / atomic_number / halo index lists arrive as torch LongTensors).
  *
- * ABI version 13 (`hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
+ * ABI version 13 (`HN_ABI_VERSION` below, returned by `hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
  * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator) were added within v13 (new entry points only, nothing
@@ -62,7 +62,9 @@ extern "C" {
 #define HN_ENV_POLYNOMIAL 0   /* rmnet.py:175-193 */
 #define HN_ENV_EXPONENTIAL 1  /* rmnet.py:196-208 */
 
-/* Library / build identification (also used as the "is the native path loaded" probe). */
+/* Library / build identification (also used as the "is the native path loaded" probe).  HN_ABI_VERSION is what
+ * hermnet_abi_version() of a library built from this header returns; a binder compares the two. */
+#define HN_ABI_VERSION 13
 int hermnet_abi_version(void);
 const char* hermnet_build_info(void);
 

@@ -565,6 +565,22 @@ def msg_bwd(graph, rbf, H, xh, vec, w, edge, gx1, gvec1, gedge, xh_bias=True, ra
     return out
 
 
+# every kernel wrapper of hermnet_amd.nodeops that the fused layer calls on one device and has a restatement of its name here
+NODEOPS = ("energy_head_fwd", "energy_head_bwd", "layernorm_fwd", "layernorm_bwd", "ssilu_fwd", "ssilu_bwd", "update_mid",
+           "update_out", "update_out_bwd", "update_mid_bwd", "node_pre_fwd", "node_pre_bwd", "node_update_fwd", "node_update_bwd",
+           "node_update_pre_fwd", "node_pre_fwd16", "node_pre_bwd16")
+
+
+def install(put, extra=()):
+    """Kernel wrappers -> their restatements: `put(object, name, value)` (monkeypatch.setattr, or setattr in a worker process)
+    for NODEOPS and `extra` on hermnet_amd.nodeops, and for layer._msg_fwd / _msg_bwd."""
+    import hermnet_amd.layer as lmod
+    for fn in NODEOPS + tuple(extra):
+        put(lmod.nodeops, fn, globals()[fn])
+    put(lmod, "_msg_fwd", msg_fwd)
+    put(lmod, "_msg_bwd", msg_bwd)
+
+
 class RefEdgeGeometry(torch.autograd.Function):
     """Same contract as hermnet_amd.ops.EdgeGeometry: the incoming gradient is Cartesian (dE/dD)."""
 

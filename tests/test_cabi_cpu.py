@@ -1,7 +1,9 @@
 """CPU: the C-ABI library loads without a GPU, exports every symbol include/hermnet_hip.h
-declares, and its banded radial contraction (the formulation the kernels use) agrees with the
+declares, the binding `hermnet_amd._lib` reads from that header equals the recorded ABI v13, and its
+banded radial contraction (the formulation the kernels use) agrees with the
 dense reference formula (rmnet.py:55,168-172) and with finite differences."""
 import ctypes
+import json
 import os
 import re
 
@@ -14,8 +16,21 @@ from hermnet_amd import _lib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _header():
+    with open(os.path.join(ROOT, "include", "hermnet_hip.h")) as fh:
+        return fh.read()
+
+
+def _declared_parameters(hdr):
+    """name -> number of parameters of every hermnet_* declaration, counted on the header text by itself (commas between the
+    parentheses; `(void)` is none) -- not through `_lib.read_header`."""
+    text = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    return {name: 0 if params.strip() == "void" else params.count(",") + 1
+            for name, params in re.findall(r"\b(hermnet_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)}
+
+
 def test_library_exports_every_declared_symbol():
-    hdr = open(os.path.join(ROOT, "include", "hermnet_hip.h")).read()
+    hdr = _header()
     declared = set(re.findall(r"\b(hermnet_[a-z0-9_]+)\s*\(", hdr))
     assert declared == set(_lib.SIGNATURES.keys()), declared ^ set(_lib.SIGNATURES.keys())
     lib = _lib.load()
@@ -23,6 +38,108 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
     assert lib.hermnet_abi_version() == _lib.ABI_VERSION == 13
     assert b"gfx950" in lib.hermnet_build_info()
+    # every bound function takes as many arguments as the header's parameter list has
+    counts = _declared_parameters(hdr)
+    assert set(counts) == declared
+    for name in declared:
+        assert len(getattr(lib, name).argtypes) == counts[name], (name, len(getattr(lib, name).argtypes), counts[name])
+
+
+def test_binding_read_from_the_header_equals_the_recorded_abi_v13():
+    """tests/golden/cabi_v13.json (gen_cabi_fixture.py) is the binding as `_lib` held it in hand-written tables; what `_lib` now
+    reads from include/hermnet_hip.h must equal it entry for entry: restype and every argtype of every recorded entry point, every
+    struct's fields in order with their types and its size, the option ids, the envelope kinds, the version and the error
+    codes.  The header may declare MORE entry points (the ABI is additive), never other ones: "STABLE from v11 on" as a test.
+    Where the derived type may differ, and only there: the tables wrote three pointers otherwise than the header does --
+    hermnet_get_option's `int* value` as POINTER(c_int), which the reader's uniform rule makes c_void_p, and the `const
+    hn_pending_grads* pending` of hermnet_node_update_bwd / _bwd_last as c_void_p, which the rule for pointers to the
+    header's structs makes POINTER(PendingGrads).  All are pointers; `ctypes.byref`, which every caller uses, serves both."""
+    with open(os.path.join(ROOT, "tests", "golden", "cabi_v13.json")) as fh:
+        want = json.load(fh)
+    allowed = {("hermnet_get_option", 1): ("LP_c_int", "c_void_p"),
+               ("hermnet_node_update_bwd", 18): ("c_void_p", "LP_PendingGrads"),
+               ("hermnet_node_update_bwd_last", 16): ("c_void_p", "LP_PendingGrads")}
+    assert len(want["functions"]) == 98 and set(want["functions"]) <= set(_lib.SIGNATURES)
+    used = set()
+    for name, rec in want["functions"].items():
+        res, args = _lib.SIGNATURES[name]
+        assert res.__name__ == rec["restype"], name
+        assert len(args) == len(rec["argtypes"]), name
+        for i, (got, old) in enumerate(zip((a.__name__ for a in args), rec["argtypes"])):
+            if got != old:
+                assert allowed.get((name, i)) == (old, got), (name, i, old, got)
+                used.add((name, i))
+    assert used == set(allowed)
+    assert sorted(want["structs"]) == ["Graph", "PendingGrads", "RbfDesc", "RelationsOut"]
+    for name, rec in want["structs"].items():
+        cls = getattr(_lib, name)
+        assert issubclass(cls, ctypes.Structure)
+        assert [[n, t.__name__] for n, t in cls._fields_] == rec["fields"], name
+        assert ctypes.sizeof(cls) == rec["sizeof"], name
+    assert _lib.OPTIONS == want["options"] and _lib.HN_ENV == want["env"]
+    assert _lib.ABI_VERSION == want["abi_version"] == 13 and sorted(_lib._ERR) == want["error_codes"] == [1, 2, 3]
+    # the loaded library carries exactly these types
+    lib = _lib.load()
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert getattr(lib, name).restype is res and list(getattr(lib, name).argtypes) == list(args), name
+
+
+_MINI = """
+#define HN_OK 0
+#define HN_ERR_BAD_ARG 1  /* bad */
+#define HN_ABI_VERSION 13
+typedef struct hn_box { const float* p; int n; } hn_box;
+/* a comment that mentions hermnet_foo( and hermnet_bar (int) must not count */
+int hermnet_a(void);
+const char* hermnet_b(const hn_box* box, unsigned long seed, const float* const* in, size_t bytes, void* stream);
+"""
+
+
+def test_header_reader_is_strict():
+    """`_lib.read_header` on small header strings: what it reads, and that it raises -- naming the culprit -- on a scalar type
+    it does not know, on a declaration its pattern cannot read (through the count of `hermnet_*(` occurrences), and on a
+    struct field of unknown type; a comment that contains `hermnet_foo(` is not a declaration."""
+    defines, structs, sigs, notes = _lib.read_header(_MINI)
+    assert defines == {"HN_OK": 0, "HN_ERR_BAD_ARG": 1, "HN_ABI_VERSION": 13} and notes == {"HN_ERR_BAD_ARG": "bad"}
+    box = structs["hn_box"]
+    assert box.__name__ == "Box" and [(n, t) for n, t in box._fields_] == [("p", ctypes.c_void_p), ("n", ctypes.c_int)]
+    assert sorted(sigs) == ["hermnet_a", "hermnet_b"] and sigs["hermnet_a"] == (ctypes.c_int, [])
+    res, args = sigs["hermnet_b"]
+    assert res is ctypes.c_char_p
+    assert args == [ctypes.POINTER(box), ctypes.c_ulong, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    with pytest.raises(ValueError, match=r"unknown type `short flag` in hermnet_c"):
+        _lib.read_header(_MINI + "int hermnet_c(int n, short flag);\n")
+    with pytest.raises(ValueError, match=r"unknown type `bool` in hermnet_c's return type"):
+        _lib.read_header(_MINI + "bool hermnet_c(int n);\n")
+    with pytest.raises(ValueError, match=r"2 declarations read, 3 .* not read: \['hermnet_c'\]"):
+        _lib.read_header(_MINI + "int hermnet_c(int (*callback)(int), void* stream);\n")
+    with pytest.raises(ValueError, match=r"unknown type `uint8_t kind` in struct hn_box"):
+        _lib.read_header(_MINI.replace("int n; }", "int n; uint8_t kind; }"))
+    with pytest.raises(ValueError, match=r"2 declarations read, 3"):           # one name declared twice
+        _lib.read_header(_MINI + "int hermnet_a(int n);\n")
+
+
+def test_missing_header_is_named_by_load(monkeypatch, tmp_path):
+    """The binding is read from the header on first use: without it `load()` raises a RuntimeError that names the path, as it
+    does for a missing library.  (A fresh copy of the module: the test process has long read the header.)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("hermnet_amd._lib_without_header", _lib.__file__)
+    fresh = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(fresh)
+    fresh.HEADER_PATH = str(tmp_path / "hermnet_hip.h")
+    with pytest.raises(RuntimeError, match="hermnet_hip.h not found"):
+        fresh.load()
+    with pytest.raises(RuntimeError, match=re.escape(fresh.HEADER_PATH)):
+        fresh.ABI_VERSION
+
+
+def test_call_raises_under_the_entry_points_name():
+    """`_lib.call`: HN_OK returns None, any other code raises RuntimeError with the entry point's name and the HN_ERR_* text."""
+    assert _lib.call("hermnet_set_option", _lib.OPTIONS["fwd_rows"], _lib.get_option("fwd_rows")) is None
+    with pytest.raises(RuntimeError, match=r"hermnet_set_option failed: HN_ERR_BAD_ARG \(unsupported shape / null pointer\)"):
+        _lib.call("hermnet_set_option", 99, 1)
+    with pytest.raises(AttributeError):
+        _lib.call("hermnet_no_such_entry_point")
 
 
 def _dense(offset, inv_rc, coeff, env_kind, p, wt, b, d):

@@ -245,11 +245,7 @@ def test_fused_layer_orchestration_matches_golden(name, monkeypatch):
     monkeypatch.setattr(switches, "fused_layer", True)
     monkeypatch.setattr(hmod.HVNet, "_require_device", staticmethod(lambda pos: None))
     monkeypatch.setattr(hmod, "EdgeGeometry", ref_ops.RefEdgeGeometry)
-    for fn in ["energy_head_fwd", "energy_head_bwd", "layernorm_fwd", "layernorm_bwd", "ssilu_fwd", "ssilu_bwd", "update_mid", "update_out", "update_out_bwd",
-               "update_mid_bwd", "node_pre_fwd", "node_pre_bwd", "node_update_fwd", "node_update_bwd", "node_update_pre_fwd", "node_pre_fwd16", "node_pre_bwd16"]:
-        monkeypatch.setattr(lmod.nodeops, fn, getattr(ref_ops, fn))
-    monkeypatch.setattr(lmod, "_msg_fwd", ref_ops.msg_fwd)
-    monkeypatch.setattr(lmod, "_msg_bwd", ref_ops.msg_bwd)
+    ref_ops.install(monkeypatch.setattr)
     # both forms of the backward hand-over between layers: finished gradients, and partial sums the update backward of the
     # layer below finishes (hn_pending_grads; on the GPU the form is picked by `_bwd_sums_deferrable`)
     # ... and the three forms of the layer boundary (round 5): one node launch each way (switches.boundary_mode = 1: the next
@@ -353,15 +349,10 @@ def test_eval_mode_parameters_are_constants_unless_asked(monkeypatch):
     """eval(): no parameter receives a gradient (not even the embedding: a partial set would mislead);
     `eval_param_grads = True` routes eval() through the differentiable path, which gives all of them."""
     import hermnet_amd.hermnet as hmod
-    import hermnet_amd.layer as lmod
     import hermnet_amd.rmnet as rmod
     monkeypatch.setattr(hmod.HVNet, "_require_device", staticmethod(lambda pos: None))
     monkeypatch.setattr(hmod, "EdgeGeometry", ref_ops.RefEdgeGeometry)
-    for fn in ["energy_head_fwd", "energy_head_bwd", "layernorm_fwd", "layernorm_bwd", "ssilu_fwd", "ssilu_bwd", "update_mid",
-               "update_out", "update_out_bwd", "update_mid_bwd", "node_pre_fwd", "node_pre_bwd", "node_update_fwd", "node_update_bwd", "node_update_pre_fwd", "node_pre_fwd16", "node_pre_bwd16"]:
-        monkeypatch.setattr(lmod.nodeops, fn, getattr(ref_ops, fn))
-    monkeypatch.setattr(lmod, "_msg_fwd", ref_ops.msg_fwd)
-    monkeypatch.setattr(lmod, "_msg_bwd", ref_ops.msg_bwd)
+    ref_ops.install(monkeypatch.setattr)
     g = Golden("alloy108")
     model = g.model()                      # eval(), parameters require grad (the nn.Module default)
     d = g.data()
@@ -389,16 +380,11 @@ def test_width_not_multiple_of_64_runs_on_zero_padded_channels(H, monkeypatch):
     replaced by their PyTorch restatements (which, like the kernels, only see the padded width) the result must equal
     the oracle at the real width."""
     import hermnet_amd.hermnet as hmod
-    import hermnet_amd.layer as lmod
     from hermnet_amd import synth
     from oracle import hermnet_oracle as orc
     monkeypatch.setattr(hmod.HVNet, "_require_device", staticmethod(lambda pos: None))
     monkeypatch.setattr(hmod, "EdgeGeometry", ref_ops.RefEdgeGeometry)
-    for fn in ["energy_head_fwd", "energy_head_bwd", "layernorm_fwd", "layernorm_bwd", "ssilu_fwd", "ssilu_bwd", "update_mid",
-               "update_out", "update_out_bwd", "update_mid_bwd", "node_pre_fwd", "node_pre_bwd", "node_update_fwd", "node_update_bwd", "node_update_pre_fwd", "node_pre_fwd16", "node_pre_bwd16"]:
-        monkeypatch.setattr(lmod.nodeops, fn, getattr(ref_ops, fn))
-    monkeypatch.setattr(lmod, "_msg_fwd", ref_ops.msg_fwd)
-    monkeypatch.setattr(lmod, "_msg_bwd", ref_ops.msg_bwd)
+    ref_ops.install(monkeypatch.setattr)
     g = Golden("alloy108")
     kw = dict(rc=5.0, num_layers=2, hidden_channels=H, num_rbf=16)
     model = hn.HVNet(g.elems, **kw).eval()
@@ -606,9 +592,6 @@ def test_parameter_gradients_are_not_formed_in_a_pass_that_does_not_ask_for_them
         assert torch.allclose(got.grad, ref.grad, rtol=1e-10, atol=1e-10)
 
 
-_REF_NODEOPS = ["energy_head_fwd", "energy_head_bwd", "layernorm_fwd", "layernorm_bwd", "ssilu_fwd", "ssilu_bwd", "update_mid",
-                "update_out", "update_out_bwd", "update_mid_bwd", "node_pre_fwd", "node_pre_bwd", "node_update_fwd",
-                "node_update_bwd", "node_update_pre_fwd", "node_pre_fwd16", "node_pre_bwd16"]
 _STEP_OUTPUTS = {"_hn_step", "_hn_graph", "_hn_edge", "_hn_edge_embed"}
 
 
@@ -616,7 +599,6 @@ def _reference_ops(monkeypatch, fused_layer=True):
     """The monkeypatched reference ops of `test_fused_layer_orchestration_matches_golden` (fused_layer False: of
     `test_host_pipeline_with_reference_ops_matches_golden`)."""
     import hermnet_amd.hermnet as hmod
-    import hermnet_amd.layer as lmod
     import hermnet_amd.rmnet as rmod
     from hermnet_amd import switches
     monkeypatch.setattr(switches, "fused_layer", fused_layer)
@@ -626,10 +608,7 @@ def _reference_ops(monkeypatch, fused_layer=True):
         monkeypatch.setattr(rmod, "MessageScatter", _FakeFn(ref_ops.message_scatter_ref))
         return
     monkeypatch.setattr(hmod, "EdgeGeometry", ref_ops.RefEdgeGeometry)
-    for fn in _REF_NODEOPS:
-        monkeypatch.setattr(lmod.nodeops, fn, getattr(ref_ops, fn))
-    monkeypatch.setattr(lmod, "_msg_fwd", ref_ops.msg_fwd)
-    monkeypatch.setattr(lmod, "_msg_bwd", ref_ops.msg_bwd)
+    ref_ops.install(monkeypatch.setattr)
 
 
 def _frozen_model(g):

@@ -30,12 +30,7 @@ def _patch_cpu_ops(monkeypatch=None):
     put = (lambda o, n, v: setattr(o, n, v)) if monkeypatch is None else monkeypatch.setattr
     put(hmod.HVNet, "_require_device", staticmethod(lambda pos: None))
     put(hmod, "EdgeGeometry", ref_ops.RefEdgeGeometry)
-    for fn in ["energy_head_fwd", "energy_head_bwd", "layernorm_fwd", "layernorm_bwd", "ssilu_fwd", "ssilu_bwd", "update_mid", "update_out", "update_out_bwd",
-               "update_mid_bwd", "node_pre_fwd", "node_pre_bwd", "node_update_fwd", "node_update_bwd", "node_update_pre_fwd", "node_pre_fwd16", "node_pre_bwd16", "halo_rows",
-               "halo_accumulate", "halo_proj_rows", "halo_proj_accumulate"]:
-        put(lmod.nodeops, fn, getattr(ref_ops, fn))
-    put(lmod, "_msg_fwd", ref_ops.msg_fwd)
-    put(lmod, "_msg_bwd", ref_ops.msg_bwd)
+    ref_ops.install(put, extra=("halo_rows", "halo_accumulate", "halo_proj_rows", "halo_proj_accumulate"))
     # (on the GPU `_bwd_sums_deferrable` wants the radial table and width 128; the restatements hand partial sums down at any
     # width -- which is also what lets the "proj" form of the halo exchange run here)
     put(lmod, "_bwd_sums_deferrable", lambda graph, H: True)

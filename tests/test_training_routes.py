@@ -294,7 +294,7 @@ class _Labels(object):
 
 
 def test_training_step_launches_through_the_one_labelled_path(monkeypatch):
-    """Every launch of hermnet_amd.trainops goes through `nodeops._call` under a timer label: the C name without `hermnet_`,
+    """Every launch of hermnet_amd.trainops goes through `ops._call` under a timer label: the C name without `hermnet_`,
     for hermnet_train_node_op the op's name in `trainops.NODE_OPS`.  One full step (forward, autograd.grad(E, pos,
     create_graph=True), loss.backward()) on 256 atoms of three elements in the uniform row layout, Gaussian basis, two layers
     (vec is None in layer 0 and present in layer 1), H the smallest multiple of 4 whose band product the library supports --
