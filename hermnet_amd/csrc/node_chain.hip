@@ -1,6 +1,7 @@
-// gfx950: the node-level dense algebra of one HeteroVertexConv layer as FOUR chain kernels on the fp32 matrix pipe.
+// gfx950: the node-level dense algebra of one HeteroVertexConv layer as FOUR chain kernels on the matrix pipe, for the widths
+// 64 / 128 / 256 (tuned instances; node_chain_wide.hip: every multiple of 64 up to 512, node_chain16.hip: 16-row tiles).
 //
-//   node_pre_fwd     x -> LayerNorm -> [H -> H] -> ScaledSiLU -> [H -> 3H]  = xh[t]        /root/reference/HermNet/rmnet.py:52
+//   node_pre_fwd     x -> LayerNorm -> [H -> H] -> ScaledSiLU -> [H -> 3H]  = xh[t]        rmnet.py:52
 //   node_pre_bwd     gxh[t] -> [3H -> H] -> * ScaledSiLU' -> [H -> H]       = gn[t]        (its input gradient)
 //   node_update_fwd  (x1, vec1) -> vec_proj, vec_dot, |v2|, xvec_proj MLP, dx / dvec, residual   rmnet.py:94-107, 29-31
 //   node_update_bwd  (gx_out, gvec_out) -> (gx1, gvec1)                                         (its input gradient)
@@ -11,13 +12,15 @@
 // owns a tile of TR rows for the WHOLE chain: hidden activations live in an LDS tile (the A operand of the next product),
 // elementwise stages run on the accumulators, and only what the backward needs is stored.
 //
-// Data flow of one product  C[TR, Nout] = A[TR, K] . W[Nout, K]^T :
-//   * A: an LDS tile, rows padded by 4 floats; lane l reads row (l & 31), k = 8q + 4 (l >> 5) .. +3 with one conflict-free
-//     ds_read_b128 and feeds four v_mfma_f32_32x32x2_f32 with it;
-//   * W: never staged in LDS.  The host keeps every weight in FRAGMENT ORDER, wf[(cb * K/8 + q) * 64 + l] = the float4
-//     W[32 cb + (l & 31)][8q + 4 (l >> 5) .. +3], i.e. exactly the B operand registers of lane l: one coalesced 1 KiB
-//     global_load_dwordx4 per wave, straight from L2 (a layer's weights are < 1 MB) into the MFMA operand, two k-groups
-//     ahead of use.  Waves of a workgroup split the OUTPUT COLUMNS, so no weight byte is loaded twice per workgroup;
+// Data flow of one product  C[TR, Nout] = A[TR, K] . W[Nout, K]^T  (node_chain_common.h: mma_panel), fp32 in and out, both
+// operands as three bf16 planes each (x = x0 + x1 + x2 exactly), the six largest partial products on v_mfma_f32_32x32x16_bf16:
+//   * A: an fp32 LDS tile, rows padded by 4 floats; per 16-deep k-group lane l reads row (l & 31), k = 16 Q + 8 (l >> 5) .. +7
+//     with two conflict-free ds_read_b128 and splits the eight values into planes in registers (split8);
+//   * W: never staged in LDS.  The host keeps every weight split and in FRAGMENT ORDER, frag(W)[((cb * K/16 + Q) * 3 + s) * 64
+//     + l] = 8 bf16 of plane 2 - s, W[32 cb + (l & 31)][16 Q + 8 (l >> 5) .. +7], i.e. exactly the operand registers of lane l:
+//     one coalesced 1 KiB load per wave and STEP (a plane of a k-group), straight from L2 (a layer's weights are < 1.5 MB) into
+//     the MFMA operand, through a ring of kRS slots two steps ahead of use.  Step s runs s + 1 MFMAs per accumulator block
+//     (activation planes s .. 0).  Waves of a workgroup split the OUTPUT COLUMNS, so no weight byte is loaded twice per workgroup;
 //   * C: 32 x 32 accumulator blocks, TRANSPOSED (the weight fragment is the MFMA's row operand, the activation its column
 //     operand): a lane holds ONE tile row and 16 channels as four runs of 4 consecutive channels, so every epilogue
 //     access to a row-major [rows][channels] array is a 16-byte load / store at `row offset + constant` (4 per block
@@ -25,21 +28,20 @@
 //     quantities (row flags) are per-lane.  A wave owns the same 32-channel slices of every part of an output
 //     (s|a|b, v1|v2, p|q|r), so products of parts (vec_dot, q * vdot, r * v1) are lane-local.
 // Two workgroups per CU (<= 68 KB of LDS, <= 256 VGPRs): one's elementwise / staging phases run beside the other's
-// matrix phases.  fp32 MFMA is exact fp32 (a k-ordered fmaf chain): results equal a library GEMM's to rounding.
+// matrix phases.  The dropped partial products are each <= 2^-24 of a product: results equal a library fp32 GEMM's to rounding.
 #include "node_chain_common.h"
-int hn_option(int option);      // host_api.cpp: process-wide options (hermnet_set_option)
 
 namespace {
 // =====================================================================================================================
 // node_pre_fwd: one workgroup = (TR source rows, relation t)
 // =====================================================================================================================
+constexpr size_t pre_fwd_lds_bytes(int H, int TR) { return chain_lds_bytes(1, TR, H); }     // one [TR][LD] tile, then the scratch
 
 template <int H, int TR>
 __global__ __launch_bounds__(256, 2) void node_pre_fwd_kernel(PreFwdArgs a) {
   using C = Cfg<H, TR>;
   constexpr int LD = C::LD, RB = C::RB, CPW = C::CPW, CB = C::CB;
   extern __shared__ __align__(16) float tile[];           // [TR][LD], then 4 x [32][36] store scratch
-  stagger_start();
   const int t = blockIdx.y, row0 = blockIdx.x * TR;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wc = wave % C::WC, wr = wave / C::WC;
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void node_pre_fwd_kernel(PreFwdArgs a) {
   for (int p = 0; p < 3; ++p)
 #pragma unroll
     for (int j = 0; j < CPW; ++j) bp2[p * CPW + j] = w2 + (size_t)(p * CB + wc * CPW + j) * frag_f4(H);
-  BRing<CPW, ring_size(RB * CPW, false)> r1;
+  BRing<CPW, kRS> r1;
   b_preload(r1, bp1);
   const int ch = 4 * (lane >> 5);
   f32x4 bias1[CPW][4];                                // b1 of this wave's channels: the first product starts from it
@@ -93,7 +95,7 @@ __global__ __launch_bounds__(256, 2) void node_pre_fwd_kernel(PreFwdArgs a) {
 #pragma unroll
     for (int m = 1; m < TPR; m <<= 1) s += __shfl_xor(s, m, 64);
     float mu = s / (float)a.Hr;
-    // corrected two-pass statistics (round 6): a lane sums NF * 4 values in sequence, so on a row whose mean dwarfs its spread
+    // corrected two-pass statistics: a lane sums NF * 4 values in sequence, so on a row whose mean dwarfs its spread
     // (1e3 under unit noise) `mu` carries an error of ~1e-4 of the spread -- 20 x what torch's pairwise sum leaves
     // (tests/test_gpu_parity.py::test_node_chain_kernels_on_adversarial_operands).  The mean of the DEVIATIONS is that error,
     // measured at the deviations' own scale: it is taken out of the deviations, the mean and the variance.
@@ -135,9 +137,9 @@ __global__ __launch_bounds__(256, 2) void node_pre_fwd_kernel(PreFwdArgs a) {
   const float* As = tile + mrow * LD + ch;
   f32x16 acc1[RB][CPW];
   bias_acc(acc1, bias1);
-  mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, false), false, HN_PIN_PRE>(acc1, As, bp1, r1);
+  mma_panel<H, LD, RB, CPW, kRS, false, kPinPre>(acc1, As, bp1, r1);
   STAMP(3);
-  BRing<3 * CPW, ring_size(RB * 3 * CPW, false)> r2;
+  BRing<3 * CPW, kRS> r2;
   b_preload(r2, bp2);
   f32x4 bias2[3 * CPW][4];                           // b2, requested in front of the epilogue's stores
 #pragma unroll
@@ -167,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void node_pre_fwd_kernel(PreFwdArgs a) {
   // ---- xh = a W2^T + b2
   f32x16 acc2[RB][3 * CPW];
   bias_acc(acc2, bias2);
-  mma_panel<H, LD, RB, 3 * CPW, ring_size(RB * 3 * CPW, false), false, HN_PIN_PRE>(acc2, As, bp2, r2);
+  mma_panel<H, LD, RB, 3 * CPW, kRS, false, kPinPre>(acc2, As, bp2, r2);
   STAMP(7);
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
@@ -186,10 +188,10 @@ __global__ __launch_bounds__(256, 2) void node_pre_fwd_kernel(PreFwdArgs a) {
 // node_pre_bwd: one workgroup = (TR source rows, relation t) -> gn[t] (the sum over t and the LayerNorm backward follow
 // in layernorm_bwd_parts_kernel)
 // =====================================================================================================================
-// LDS floats of node_pre_bwd: two K-chunk buffers, later the gh tile + the store scratch in the same space
-constexpr int pre_bwd_lds_floats(int H, int TR) {
+// LDS of node_pre_bwd: two K-chunk buffers [TR][min(H, 128) + 4], later the gh tile + the store scratch in the same space
+constexpr size_t pre_bwd_lds_bytes(int H, int TR) {
   const int kc = H < 128 ? H : 128, chunks = 2 * TR * (kc + 4), tail = TR * (H + 4) + 4 * kScrFloats;
-  return chunks > tail ? chunks : tail;
+  return (size_t)(chunks > tail ? chunks : tail) * sizeof(float);
 }
 
 
@@ -199,9 +201,8 @@ __global__ __launch_bounds__(256, 2) void node_pre_bwd_kernel(PreBwdArgs a) {
   constexpr int LD = C::LD, RB = C::RB, CPW = C::CPW;
   constexpr int KC = H < 128 ? H : 128;            // K chunk of the first product (K = 3H)
   constexpr int NCH = 3 * H / KC, LDC = KC + 4;
-  static_assert(2 * TR * LDC >= TR * LD, "the gh tile must fit the two chunk buffers");   // (+ scratch: pre_bwd_lds_floats)
+  static_assert(2 * TR * LDC >= TR * LD, "the gh tile must fit the two chunk buffers");   // (+ scratch: pre_bwd_lds_bytes)
   extern __shared__ __align__(16) float lds[];            // 2 x [TR][LDC], then 4 x [32][36] store scratch
-  stagger_start();
   const int t = blockIdx.y, row0 = blockIdx.x * TR;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wc = wave % C::WC, wr = wave / C::WC;
@@ -224,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void node_pre_bwd_kernel(PreBwdArgs a) {
     bpa[j] = w2t + (size_t)(wc * CPW + j) * frag_f4(3 * H);
     bpb[j] = w1t + (size_t)(wc * CPW + j) * frag_f4(H);
   }
-  BRing<CPW, ring_size(RB * CPW, true)> ra;
+  BRing<CPW, kRS> ra;
   b_preload(ra, bpa);
   const rsrc_t gxh_r = tile_rsrc(a.gxh + ((size_t)t * a.Ns + row0) * 3 * H, nrows * 3 * H);
   const rsrc_t hb_r = tile_rsrc(a.hb + ((size_t)t * a.Ns + row0) * H, nrows * H);
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(256, 2) void node_pre_bwd_kernel(PreBwdArgs a) {
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
-    for (int j = 0; j < CPW; ++j) issue_block<H, true>(lhb[rb][j], lane, hb_r, (wr * RB + rb) * 32 * H + (wc * CPW + j) * 32);
+    for (int j = 0; j < CPW; ++j) issue_block<H>(lhb[rb][j], lane, hb_r, (wr * RB + rb) * 32 * H + (wc * CPW + j) * 32);
 
   // ---- ga = gxh W2   (K = 3H in chunks, double-buffered through registers)
   f32x16 acc[RB][CPW];
@@ -251,10 +252,10 @@ __global__ __launch_bounds__(256, 2) void node_pre_bwd_kernel(PreBwdArgs a) {
     const f32x4* bpk[CPW];
 #pragma unroll
     for (int j = 0; j < CPW; ++j) bpk[j] = bpa[j] + (size_t)kc * frag_f4(KC);
-    if (kc + 1 < NCH) mma_panel<KC, LDC, RB, CPW, ring_size(RB * CPW, true), true>(acc, As, bpk, ra);
-    else mma_panel<KC, LDC, RB, CPW, ring_size(RB * CPW, true), false>(acc, As, bpk, ra);
+    if (kc + 1 < NCH) mma_panel<KC, LDC, RB, CPW, kRS, true>(acc, As, bpk, ra);
+    else mma_panel<KC, LDC, RB, CPW, kRS, false>(acc, As, bpk, ra);
   }
-  BRing<CPW, ring_size(RB * CPW, false)> rb_;
+  BRing<CPW, kRS> rb_;
   b_preload(rb_, bpb);
   __syncthreads();                                   // the chunk buffers are free
   // ---- gh = ga * ScaledSiLU'(hb) -> tile
@@ -274,7 +275,7 @@ __global__ __launch_bounds__(256, 2) void node_pre_bwd_kernel(PreBwdArgs a) {
   // ---- gn_t = gh W1
   f32x16 acc2[RB][CPW];
   zero_acc(acc2);
-  mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, false), false>(acc2, tile + mrow * LD + ch, bpb, rb_);
+  mma_panel<H, LD, RB, CPW, kRS, false>(acc2, tile + mrow * LD + ch, bpb, rb_);
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -284,17 +285,30 @@ __global__ __launch_bounds__(256, 2) void node_pre_bwd_kernel(PreBwdArgs a) {
     }
 }
 
+// gx = LayerNorm'(x)^T (sum_p g[p]) + add : the backward of the LayerNorm in front of the T relations' projections
+__global__ __launch_bounds__(256) void layernorm_bwd_parts_kernel(const float* __restrict__ g, int nparts, long part_stride,
+                                                                  const float* __restrict__ x, const float* __restrict__ mean,
+                                                                  const float* __restrict__ rstd, const float* __restrict__ add,
+                                                                  float* __restrict__ gx, int rows, int H, int Hr,
+                                                                  const int* __restrict__ windows, int nwin, int wmode,
+                                                                  int TR) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  if (!tile_selected(windows, nwin, wmode, r / TR * TR, TR)) return;     // the rows of the pre kernel's tiles
+  layernorm_bwd_row(g, nparts, part_stride, x, mean[r], rstd[r], add, 1.f, gx, (size_t)r, H, Hr, threadIdx.x & 63);
+}
 
 // =====================================================================================================================
 // node_update_fwd (rmnet.py:94-107 + the residual of rmnet.py:29-31 + the zero rows of hermnet.py:51,56-57)
 // =====================================================================================================================
+// both update kernels: two [TR][LD] tiles, then the scratch
+constexpr size_t update_lds_bytes(int H, int TR) { return chain_lds_bytes(2, TR, H); }
 
 template <int H, int TR, int MINW>
 __global__ __launch_bounds__(256, MINW) void node_update_fwd_kernel(UpdFwdArgs a) {
   using C = Cfg<H, TR>;
   constexpr int LD = C::LD, RB = C::RB, CPW = C::CPW, CB = C::CB;
   extern __shared__ __align__(16) float lds[];            // 2 x [TR][LD], then 4 x [32][36] store scratch
-  stagger_start();
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wc = wave % C::WC, wr = wave / C::WC;
   float* scr = lds + 2 * TR * LD + wave * kScrFloats;
@@ -354,8 +368,8 @@ __global__ __launch_bounds__(256, MINW) void node_update_fwd_kernel(UpdFwdArgs a
   STAMP_HWID();
   TileRegs<TR, H> regs;
   tile_load<TR, H>(regs, vec1_r, 3 * H, 0, tid);
-  BRing<2 * CPW, ring_size(RB * 2 * CPW, false)> rv;
-  BRing<CPW, ring_size(RB * CPW, true)> rx;
+  BRing<2 * CPW, kRS> rv;
+  BRing<CPW, kRS> rx;
   b_preload(rv, bpv);
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
@@ -367,7 +381,7 @@ __global__ __launch_bounds__(256, MINW) void node_update_fwd_kernel(UpdFwdArgs a
     else tile_load<TR, H>(regs, x1_r, H, 0, tid);
     f32x16 accv[RB][2 * CPW];
     zero_acc(accv);
-    mma_panel<H, LD, RB, 2 * CPW, ring_size(RB * 2 * CPW, false), false, true, false>(accv, buf + mrow * LD + ch, bpv, rv);
+    mma_panel<H, LD, RB, 2 * CPW, kRS, false, true, false>(accv, buf + mrow * LD + ch, bpv, rv);
     STAMP(2 + 3 * d);
     if (d < 2) b_preload(rv, bpv);
     else b_preload(rx, bpx);
@@ -420,11 +434,11 @@ __global__ __launch_bounds__(256, MINW) void node_update_fwd_kernel(UpdFwdArgs a
     const f32x4* bpx1[CPW];
 #pragma unroll
     for (int j = 0; j < CPW; ++j) bpx1[j] = bpx[j] + (size_t)frag_f4(H);
-    mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, true), true, true, false>(acch, bufx + mrow * LD + ch, bpx, rx);
-    mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, true), false, true, false>(acch, bufn + mrow * LD + ch, bpx1, rx);
+    mma_panel<H, LD, RB, CPW, kRS, true, true, false>(acch, bufx + mrow * LD + ch, bpx, rx);
+    mma_panel<H, LD, RB, CPW, kRS, false, true, false>(acch, bufn + mrow * LD + ch, bpx1, rx);
   }
   STAMP(11);
-  BRing<3 * CPW, ring_size(RB * 3 * CPW, false)> rq;
+  BRing<3 * CPW, kRS> rq;
   b_preload(rq, bpq);
   __syncthreads();                                   // both buffers are free (x1 is re-read from memory below)
 #pragma unroll
@@ -458,7 +472,7 @@ __global__ __launch_bounds__(256, MINW) void node_update_fwd_kernel(UpdFwdArgs a
   STAMP(12);
   f32x16 accq[RB][3 * CPW];
   zero_acc(accq);
-  mma_panel<H, LD, RB, 3 * CPW, ring_size(RB * 3 * CPW, false), false, true, false>(accq, lds + mrow * LD + ch, bpq, rq);
+  mma_panel<H, LD, RB, 3 * CPW, kRS, false, true, false>(accq, lds + mrow * LD + ch, bpq, rq);
   STAMP(13);
   fence_sched();
   const float inv_sqrt_h = rsqrtf((float)H);
@@ -504,7 +518,6 @@ __global__ __launch_bounds__(256, MINW) void node_update_bwd_kernel(UpdBwdArgs a
   using C = Cfg<H, TR>;
   constexpr int LD = C::LD, RB = C::RB, CPW = C::CPW, CB = C::CB, F4 = C::F4, V = H / 4;
   extern __shared__ __align__(16) float lds[];            // 2 x [TR][LD], then 4 x [32][36] store scratch
-  stagger_start();
   float* buf0 = lds;
   float* buf1 = lds + TR * LD;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -538,7 +551,7 @@ __global__ __launch_bounds__(256, MINW) void node_update_bwd_kernel(UpdBwdArgs a
   for (int p = 0; p < 2; ++p)
 #pragma unroll
     for (int j = 0; j < CPW; ++j) bpx[p * CPW + j] = wx0t + (size_t)(p * CB + wc * CPW + j) * frag_f4(H);
-  BRing<CPW, ring_size(RB * CPW, true)> ra;
+  BRing<CPW, kRS> ra;
   b_preload(ra, bpa);
   const int mrow = wr * RB * 32 + (lane & 31), ch = 4 * (lane >> 5);
   const float inv_sqrt_h = rsqrtf((float)H);
@@ -595,14 +608,14 @@ __global__ __launch_bounds__(256, MINW) void node_update_bwd_kernel(UpdBwdArgs a
     const f32x4* bp2[CPW];
 #pragma unroll
     for (int j = 0; j < CPW; ++j) { bp1[j] = bpa[j] + (size_t)frag_f4(H); bp2[j] = bpa[j] + (size_t)frag_f4(2 * H); }
-    mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, true), true, true, false>(acc, buf0 + mrow * LD + ch, bpa, ra);
+    mma_panel<H, LD, RB, CPW, kRS, true, true, false>(acc, buf0 + mrow * LD + ch, bpa, ra);
     __syncthreads();                                 // buffer 0 is free
     tile_store<TR, H, LD>(buf0, g3, tid);
-    mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, true), true, true, false>(acc, buf1 + mrow * LD + ch, bp1, ra);
+    mma_panel<H, LD, RB, CPW, kRS, true, true, false>(acc, buf1 + mrow * LD + ch, bp1, ra);
     __syncthreads();                                 // third part in place, buffer 1 free
-    mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, true), false, true, false>(acc, buf0 + mrow * LD + ch, bp2, ra);
+    mma_panel<H, LD, RB, CPW, kRS, false, true, false>(acc, buf0 + mrow * LD + ch, bp2, ra);
   }
-  BRing<2 * CPW, ring_size(RB * 2 * CPW, false)> rx;
+  BRing<2 * CPW, kRS> rx;
   b_preload(rx, bpx);
   fence_sched();
   // ---- gh2 = ga2 * ScaledSiLU'(h2b) -> buffer 1
@@ -663,9 +676,9 @@ __global__ __launch_bounds__(256, MINW) void node_update_bwd_kernel(UpdBwdArgs a
   HN_REQUEST(0)
   fence_sched();
   __syncthreads();
-  mma_panel<H, LD, RB, 2 * CPW, ring_size(RB * 2 * CPW, false), false, true, false>(accx, buf1 + mrow * LD + ch, bpx, rx);
+  mma_panel<H, LD, RB, 2 * CPW, kRS, false, true, false>(accx, buf1 + mrow * LD + ch, bpx, rx);
   // (weight rings are requested BEFORE the stores of the epilogue in front of their product: vmcnt retires in order)
-  BRing<CPW, ring_size(RB * CPW, true)> rg;
+  BRing<CPW, kRS> rg;
   b_preload(rg, bpg);
   fence_sched();
   f32x4 pnrm[RB][CPW][4];
@@ -721,8 +734,8 @@ __global__ __launch_bounds__(256, MINW) void node_update_bwd_kernel(UpdBwdArgs a
     const f32x4* bpg1[CPW];
 #pragma unroll
     for (int j = 0; j < CPW; ++j) bpg1[j] = bpg[j] + (size_t)frag_f4(H);
-    mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, true), true, true, false>(accg, buf0 + mrow * LD + ch, bpg, rg);
-    mma_panel<H, LD, RB, CPW, ring_size(RB * CPW, true), false, true, false>(accg, buf1 + mrow * LD + ch, bpg1, rg);
+    mma_panel<H, LD, RB, CPW, kRS, true, true, false>(accg, buf0 + mrow * LD + ch, bpg, rg);
+    mma_panel<H, LD, RB, CPW, kRS, false, true, false>(accg, buf1 + mrow * LD + ch, bpg1, rg);
     if (d < 2) b_preload(rg, bpg);
     fence_sched();
     if (d < 2) { HN_ARRIVE(d + 1) }
@@ -736,32 +749,43 @@ __global__ __launch_bounds__(256, MINW) void node_update_bwd_kernel(UpdBwdArgs a
   }
 }
 
-// LDS floats of a kernel family for tile (H, TR): NB buffers of [TR][H + 4]
-#define HN_CHAIN_DISPATCH(KERNEL, GRID, NB, ARGS)                                                          \
-  switch (hidden) {                                                                                        \
-    case 64: return launch_chain(KERNEL<64, 64>, GRID(64), (size_t)(NB * 64 * 68 + 4 * kScrFloats) * 4, stream, ARGS);        \
-    case 128: return launch_chain(KERNEL<128, 64>, GRID(64), (size_t)(NB * 64 * 132 + 4 * kScrFloats) * 4, stream, ARGS);     \
-    case 256: return launch_chain(KERNEL<256, 32>, GRID(32), (size_t)(NB * 32 * 260 + 4 * kScrFloats) * 4, stream, ARGS);     \
-    default: return HN_ERR_BAD_ARG;                                                                        \
+// The width dispatch of this unit: CALL(H, rows per tile of the pre kernels, of the update kernels, the update kernels'
+// workgroups per CU) for the tuned instance at `hidden`.
+#define HN_TUNED_WIDTHS(CALL)                \
+  switch (hidden) {                          \
+    case 64: CALL(64, 64, 64, 2);            \
+    case 128: CALL(128, 64, 32, 2);          \
+    case 256: CALL(256, 32, 32, 1);          \
+    default: return HN_ERR_BAD_ARG;          \
   }
+#define HN_PRE_GRID(TR) dim3((unsigned)((num_src + TR - 1) / TR), (unsigned)num_rel)
+#define HN_PRE_FWD(H, TRP, TRU, MINW) \
+  return launch_chain<node_pre_fwd_kernel<H, TRP>>(HN_PRE_GRID(TRP), pre_fwd_lds_bytes(H, TRP), stream, a)
+#define HN_PRE_BWD(H, TRP, TRU, MINW) \
+  return launch_chain<node_pre_bwd_kernel<H, TRP>>(HN_PRE_GRID(TRP), pre_bwd_lds_bytes(H, TRP), stream, a)
+#define HN_UPDATE_FWD(H, TRP, TRU, MINW) \
+  return launch_chain<node_update_fwd_kernel<H, TRU, MINW>>(dim3((unsigned)HN_TILES(TRU)), update_lds_bytes(H, TRU), stream, a)
+#define HN_UPDATE_BWD(H, TRP, TRU, MINW) \
+  return launch_chain<node_update_bwd_kernel<H, TRU, MINW>>(dim3((unsigned)HN_TILES(TRU)), update_lds_bytes(H, TRU), stream, a)
 
-// Update kernels: tile (H, TR) and register budget.  H = 128 has two instances: 32-row tiles fit 256 registers, so two
-// workgroups share a CU and one's elementwise phases run beside the other's matrix phases (the default: measured
-// 64 / 77 us against 75 / 99 us per launch at 10,000 rows); 64-row tiles keep ~400 values per lane live (one wave per SIMD,
-// 512 registers) and load every weight fragment once per 64 rows (option HN_OPT_UPDATE_TILE64_MAX = largest grid, in 64-row
-// tiles, that takes them).
-inline int tile64_max() { return hn_option(HN_OPT_UPDATE_TILE64_MAX); }
-#define HN_TILES(TR) tiles_of(type_rowptr_host, num_rel, num_nodes, TR)
-#define HN_UPDATE_DISPATCH(KERNEL, ARGS)                                                                              \
-  switch (hidden) {                                                                                                   \
-    case 64: return launch_chain(KERNEL<64, 64, 2>, dim3((unsigned)HN_TILES(64)), (size_t)(2 * 64 * 68 + 4 * kScrFloats) * 4, stream, ARGS); \
-    case 128:                                                                                                         \
-      if (HN_TILES(64) <= tile64_max())                                                                               \
-        return launch_chain(KERNEL<128, 64, 1>, dim3((unsigned)HN_TILES(64)), (size_t)(2 * 64 * 132 + 4 * kScrFloats) * 4, stream, ARGS); \
-      return launch_chain(KERNEL<128, 32, 2>, dim3((unsigned)HN_TILES(32)), (size_t)(2 * 32 * 132 + 4 * kScrFloats) * 4, stream, ARGS);  \
-    case 256: return launch_chain(KERNEL<256, 32, 1>, dim3((unsigned)HN_TILES(32)), (size_t)(2 * 32 * 260 + 4 * kScrFloats) * 4, stream, ARGS); \
-    default: return HN_ERR_BAD_ARG;                                                                                   \
-  }
+// The update kernels at H = 128 have a second instance: 32-row tiles fit 256 registers, so two workgroups share a CU and one's
+// elementwise phases run beside the other's matrix phases (the default: measured 64 / 77 us against 75 / 99 us per launch at
+// 10,000 rows); 64-row tiles keep ~400 values per lane live (one wave per SIMD, 512 registers) and load every weight fragment
+// once per 64 rows (option HN_OPT_UPDATE_TILE64_MAX = largest grid, in 64-row tiles, that takes them).
+inline bool take_tile64(int hidden, int tiles64) { return hidden == 128 && tiles64 <= hn_option(HN_OPT_UPDATE_TILE64_MAX); }
+
+// Rows per tile of a width's base kernels (the update chain may take 16-row tiles instead: hermnet_node_update_tile_rows).
+// The pre kernels' row windows of the halo overlap are cut at these boundaries.
+int base_tile_rows(int hidden, bool update) {
+  if (use_wide(hidden) || hidden == 256) return 32;
+  return hidden == 64 ? 64 : (update ? 32 : 64);
+}
+
+// What the two pre-chain entry points check alike in front of their pointers.
+bool pre_shape_ok(int num_src, int num_rel, int hidden, int hidden_real, const int* windows, int nwin, int wmode) {
+  return num_src >= 0 && num_rel > 0 && hidden_real <= hidden && wmode >= 0 && wmode <= 2 && !(wmode && (!windows || nwin < 0)) &&
+         hermnet_node_chain_supported(hidden);
+}
 
 }  // namespace
 
@@ -770,65 +794,6 @@ extern "C" int hermnet_debug_stamps(unsigned long long* out_host, int count) {
   return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(hn_stamps), (size_t)count * sizeof(unsigned long long)) == hipSuccess ? 0 : 3;
 }
 #endif
-
-// node_chain_wide.hip: the same four chains for every multiple of 64 from 128 to 512
-int hn_wide_pre_fwd(int hidden, const PreFwdArgs& a, void* stream);
-int hn_wide_pre_bwd(int hidden, const PreBwdArgs& a, void* stream);
-int hn_wide_update_fwd(int hidden, const UpdFwdArgs& a, int tiles, void* stream);
-int hn_wide_update_bwd(int hidden, const UpdBwdArgs& a, int tiles, void* stream);
-
-// node_chain16.hip: the update chain on 16-row tiles (v_mfma_f32_16x16x4_f32, frag16 weight copies)
-int hn_update16_supported(int hidden);
-int hn_update16_fwd(int hidden, const UpdFwdArgs& a, int tiles, void* stream);
-int hn_update16_bwd(int hidden, const UpdBwdArgs& a, int tiles, void* stream);
-int hn_update16_pre_fwd(int hidden, const UpdFwdArgs& a, const PreFwdArgs& p, int tiles, void* stream);
-int hn_pre16_fwd(int hidden, const PreFwdArgs& p, void* stream);
-int hn_pre16_bwd(int hidden, const PreBwdArgs& a, void* stream);
-int hn_head16_supported(int hidden, int cols);
-int hn_head16_fwd(const float* x, const float* w0_frag16, const float* b0, const float* w2, const float* b2, const float* mask,
-                  float* h, float* e, int rows, void* stream);
-int hn_head16_bwd(const float* ge, const float* h, const float* w0t_frag16, const float* w2, const float* mask, float* gx,
-                  int rows, void* stream);
-
-// Widths 64 / 128 / 256 have tuned instances in this file; every other multiple of 64 up to 512 -- the reference's default
-// hidden_channels = 512 among them (hermnet.py:86) -- takes the panelled kernels.  Option HN_OPT_NODE_CHAIN_WIDE = 1 sends 128
-// and 256 there too (tests, comparisons).
-static bool use_wide(int hidden) {
-  const int force = hn_option(HN_OPT_NODE_CHAIN_WIDE);
-  if (hidden == 64) return false;
-  return force != 0 || !(hidden == 128 || hidden == 256);
-}
-// Rows per tile of a width's base kernels (the update chain may take 16-row tiles instead: hermnet_node_update_tile_rows).
-// The pre kernels' row windows of the halo overlap are cut at these boundaries.
-static int base_tile_rows(int hidden, bool update) {
-  if (use_wide(hidden) || hidden == 256) return 32;
-  return hidden == 64 ? 64 : (update ? 32 : 64);
-}
-static int real_width(int hidden_real, int hidden) { return hidden_real > 0 ? hidden_real : hidden; }
-
-// What the two pre-chain entry points check alike in front of their pointers.
-static bool pre_shape_ok(int num_src, int num_rel, int hidden, int hidden_real, const int* windows, int nwin, int wmode) {
-  return num_src >= 0 && num_rel > 0 && hidden_real <= hidden && wmode >= 0 && wmode <= 2 && !(wmode && (!windows || nwin < 0)) &&
-         hermnet_node_chain_supported(hidden);
-}
-
-// The one check of the update chains' arguments, each way, behind all five entry points -> -1: launch; else what the entry
-// point returns (HN_OK: no rows, the pointers unchecked; HN_ERR_BAD_ARG).  `supported`: the form's kernels exist at this
-// width; `last`: the last-layer form, whose vec_out / gvec_out is null.
-static int upd_fwd_refused(const UpdFwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
-  if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
-  if (a.N == 0) return HN_OK;
-  const bool ok = a.x1 && a.vec1 && a.wvf && a.wx0f && a.bx0 && a.wx2f && a.bx2 && a.type_rowptr && a.vp && a.h2b && a.q23 &&
-                  a.nrm && a.x_out && (last || a.vec_out) && type_rowptr_host[a.T] <= a.N;
-  return ok ? -1 : HN_ERR_BAD_ARG;
-}
-static int upd_bwd_refused(const UpdBwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
-  if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
-  if (a.N == 0) return HN_OK;
-  const bool ok = a.gxo && (last || a.gvo) && a.vp && a.h2b && a.q23 && a.nrm && a.wx2tf && a.wx0tf && a.wvtf && a.type_rowptr &&
-                  a.gx1 && a.gvec1 && type_rowptr_host[a.T] <= a.N;
-  return ok ? -1 : HN_ERR_BAD_ARG;
-}
 
 // 16 or 32: the tile height the update kernels should run this grid at.  16-row tiles cost twice the weight bytes from L2,
 // so they are chosen only where they shorten the launch: the busiest CU's share (whole tiles) is at least ~15 % smaller.
@@ -840,7 +805,7 @@ extern "C" int hermnet_node_update_tile_rows(const int* type_rowptr_host, int nu
   if (force == 1) return 16;
   int cus = 256, dev = 0, v = 0;
   if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-  const long t32 = tiles_of(type_rowptr_host, num_rel, num_nodes, 32), t16 = tiles_of(type_rowptr_host, num_rel, num_nodes, 16);
+  const long t32 = HN_TILES(32), t16 = HN_TILES(16);
   const long m32 = 2 * ((t32 + cus - 1) / cus), m16 = (t16 + cus - 1) / cus;      // busiest CU, in 16-row units
   return (m16 * 100 <= m32 * 85) ? 16 : base;
 }
@@ -850,6 +815,7 @@ extern "C" int hermnet_node_chain_tile_rows(int hidden, int update) {
   return hermnet_node_chain_supported(hidden) ? base_tile_rows(hidden, update != 0) : 0;
 }
 
+// ---- the four entry points that choose among the kernel families -----------------------------------------------------------
 extern "C" int hermnet_node_pre_fwd(const float* x, const float* w1_frag, const float* b1, const float* w2_frag,
                                     const float* b2, float* hb, float* xh, float* mean, float* rstd,
                                     const int* src_ranges, int num_src, int num_rel, int hidden, int hidden_real,
@@ -860,8 +826,13 @@ extern "C" int hermnet_node_pre_fwd(const float* x, const float* w1_frag, const 
   PreFwdArgs a = {x, w1_frag, b1, w2_frag, b2, hb, xh, mean, rstd, src_ranges, num_src, num_rel, real_width(hidden_real, hidden), eps,
                   row_windows, num_windows, window_mode};
   if (use_wide(hidden)) return hn_wide_pre_fwd(hidden, a, stream);
-#define HN_GRID(TR) dim3((unsigned)((num_src + TR - 1) / TR), (unsigned)num_rel)
-  HN_CHAIN_DISPATCH(node_pre_fwd_kernel, HN_GRID, 1, a);
+  HN_TUNED_WIDTHS(HN_PRE_FWD)
+}
+
+static int pre_bwd_parts(int hidden, const PreBwdArgs& a, void* stream) {
+  const int num_src = a.Ns, num_rel = a.T;
+  if (use_wide(hidden)) return hn_wide_pre_bwd(hidden, a, stream);
+  HN_TUNED_WIDTHS(HN_PRE_BWD)
 }
 
 extern "C" int hermnet_node_pre_bwd(const float* gxh, const float* hb, const float* w2t_frag, const float* w1t_frag,
@@ -874,15 +845,7 @@ extern "C" int hermnet_node_pre_bwd(const float* gxh, const float* hb, const flo
   if (!gxh || !hb || !w2t_frag || !w1t_frag || !gn_parts || (gx && (!x || !mean || !rstd))) return HN_ERR_BAD_ARG;
   if (!gx && window_mode) return HN_ERR_BAD_ARG;
   PreBwdArgs a = {gxh, hb, w2t_frag, w1t_frag, gn_parts, src_ranges, num_src, num_rel, row_windows, num_windows, window_mode};
-  // chunk buffers: 2 x [TR][min(H,128) + 4]
-  int rc;
-  if (use_wide(hidden)) rc = hn_wide_pre_bwd(hidden, a, stream);
-  else switch (hidden) {
-    case 64: rc = launch_chain(node_pre_bwd_kernel<64, 64>, HN_GRID(64), (size_t)pre_bwd_lds_floats(64, 64) * 4, stream, a); break;
-    case 128: rc = launch_chain(node_pre_bwd_kernel<128, 64>, HN_GRID(64), (size_t)pre_bwd_lds_floats(128, 64) * 4, stream, a); break;
-    default: rc = launch_chain(node_pre_bwd_kernel<256, 32>, HN_GRID(32), (size_t)pre_bwd_lds_floats(256, 32) * 4, stream, a); break;
-  }
-#undef HN_GRID
+  const int rc = pre_bwd_parts(hidden, a, stream);
   if (rc != HN_OK || !gx) return rc;              // (gx == NULL: the consumer runs the LayerNorm backward over the parts)
   hipLaunchKernelGGL(layernorm_bwd_parts_kernel, dim3((unsigned)((num_src + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                      gn_parts, num_rel, (long)num_src * hidden, x, mean, rstd, add, gx, num_src, hidden,
@@ -899,9 +862,10 @@ extern "C" int hermnet_node_update_fwd(const float* x1, const float* vec1, const
                         vec_out, num_nodes, num_rel};
   const int rc = upd_fwd_refused(a, type_rowptr_host, hermnet_node_chain_supported(hidden), false);
   if (rc >= 0) return rc;
-  if (tile_rows == 16) return hn_update16_supported(hidden) ? hn_update16_fwd(hidden, a, HN_TILES(16), stream) : HN_ERR_BAD_ARG;
+  if (tile_rows == 16) return hn_update16_supported(hidden) ? hn_update16_fwd(a, HN_TILES(16), stream) : HN_ERR_BAD_ARG;
   if (use_wide(hidden)) return hn_wide_update_fwd(hidden, a, HN_TILES(32), stream);
-  HN_UPDATE_DISPATCH(node_update_fwd_kernel, a);
+  if (take_tile64(hidden, HN_TILES(64))) HN_UPDATE_FWD(128, 64, 64, 1);
+  HN_TUNED_WIDTHS(HN_UPDATE_FWD)
 }
 
 extern "C" int hermnet_node_update_bwd(const float* gx_out, const float* gvec_out, const float* vp, const float* h2b,
@@ -923,94 +887,8 @@ extern "C" int hermnet_node_update_bwd(const float* gx_out, const float* gvec_ou
     // fused form: the projection's backward of the layer above runs inside this launch (16-row tiles only)
     if (p.gxh && (tile_rows != 16 || !p.hb || !p.w2t_frag16 || !p.w1t_frag16)) return HN_ERR_BAD_ARG;
   }
-  if (tile_rows == 16) return hn_update16_supported(hidden) ? hn_update16_bwd(hidden, a, HN_TILES(16), stream) : HN_ERR_BAD_ARG;
+  if (tile_rows == 16) return hn_update16_supported(hidden) ? hn_update16_bwd(a, HN_TILES(16), stream) : HN_ERR_BAD_ARG;
   if (use_wide(hidden)) return hn_wide_update_bwd(hidden, a, HN_TILES(32), stream);
-  HN_UPDATE_DISPATCH(node_update_bwd_kernel, a);
-}
-
-// ---- round 5: the layer boundary as ONE node launch each way (csrc/node_chain16.hip) ------------------------------------------
-extern "C" int hermnet_node_fused_supported(int hidden) { return hn_update16_supported(hidden); }
-
-extern "C" int hermnet_node_update_pre_fwd(const float* x1, const float* vec1, const float* wv_frag16, const float* wx0_frag16,
-                                           const float* bx0, const float* wx2_frag16, const float* bx2,
-                                           const float* row_active, const int* type_rowptr, const int* type_rowptr_host,
-                                           float* vp, float* h2b, float* q23, float* nrm, float* x_out, float* vec_out,
-                                           int num_nodes, int num_rel, int hidden, const float* w1_frag16, const float* b1,
-                                           const float* w2_frag16, const float* b2, float* hb, float* xh, float* mean,
-                                           float* rstd, int next_num_rel, int hidden_real, float eps, void* stream) {
-  if (next_num_rel <= 0 || hidden_real > hidden) return HN_ERR_BAD_ARG;
-  const UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q23, nrm, x_out,
-                        vec_out, num_nodes, num_rel};
-  const int rc = upd_fwd_refused(a, type_rowptr_host, hn_update16_supported(hidden), false);
-  if (rc >= 0) return rc;
-  if (!w1_frag16 || !b1 || !w2_frag16 || !b2 || !hb || !xh || !mean || !rstd) return HN_ERR_BAD_ARG;
-  PreFwdArgs p = {x_out, w1_frag16, b1, w2_frag16, b2, hb, xh, mean, rstd, nullptr, num_nodes, next_num_rel,
-                  real_width(hidden_real, hidden), eps, nullptr, 0, 0};
-  return hn_update16_pre_fwd(hidden, a, p, HN_TILES(16), stream);
-}
-
-extern "C" int hermnet_node_pre_fwd16(const float* x, const float* w1_frag16, const float* b1, const float* w2_frag16,
-                                      const float* b2, float* hb, float* xh, float* mean, float* rstd, int num_src,
-                                      int num_rel, int hidden, int hidden_real, float eps, void* stream) {
-  if (num_src < 0 || num_rel <= 0 || hidden_real > hidden || !hn_update16_supported(hidden)) return HN_ERR_BAD_ARG;
-  if (num_src == 0) return HN_OK;
-  if (!x || !w1_frag16 || !b1 || !w2_frag16 || !b2 || !hb || !xh || !mean || !rstd) return HN_ERR_BAD_ARG;
-  PreFwdArgs p = {x, w1_frag16, b1, w2_frag16, b2, hb, xh, mean, rstd, nullptr, num_src, num_rel,
-                  real_width(hidden_real, hidden), eps, nullptr, 0, 0};
-  return hn_pre16_fwd(hidden, p, stream);
-}
-
-extern "C" int hermnet_node_pre_bwd16(const float* gxh, const float* hb, const float* w2t_frag16, const float* w1t_frag16,
-                                      float* gn_parts, int num_src, int num_rel, int hidden, void* stream) {
-  if (num_src < 0 || num_rel <= 0 || !hn_update16_supported(hidden)) return HN_ERR_BAD_ARG;
-  if (num_src == 0) return HN_OK;
-  if (!gxh || !hb || !w2t_frag16 || !w1t_frag16 || !gn_parts) return HN_ERR_BAD_ARG;
-  PreBwdArgs a = {gxh, hb, w2t_frag16, w1t_frag16, gn_parts, nullptr, num_src, num_rel, nullptr, 0, 0};
-  return hn_pre16_bwd(hidden, a, stream);
-}
-
-// ---- the read-out on the matrix pipe (csrc/node_chain16.hip: 16-row tiles, hidden 128 -> 64) --------------------------------------
-extern "C" int hermnet_energy_head16_supported(int hidden, int cols) { return hn_head16_supported(hidden, cols); }
-
-extern "C" int hermnet_energy_head16_fwd(const float* x, const float* w0_frag16, const float* b0, const float* w2, const float* b2,
-                                         const float* row_mask, float* h, float* e, int rows, int hidden, int cols, void* stream) {
-  if (rows < 0 || !hn_head16_supported(hidden, cols)) return HN_ERR_BAD_ARG;
-  if (rows == 0) return HN_OK;
-  if (!x || !w0_frag16 || !b0 || !w2 || !h || !e) return HN_ERR_BAD_ARG;
-  return hn_head16_fwd(x, w0_frag16, b0, w2, b2, row_mask, h, e, rows, stream);
-}
-
-extern "C" int hermnet_energy_head16_bwd(const float* ge, const float* h, const float* w0t_frag16, const float* w2,
-                                         const float* row_mask, float* gx, int rows, int hidden, int cols, void* stream) {
-  if (rows < 0 || !hn_head16_supported(hidden, cols)) return HN_ERR_BAD_ARG;
-  if (rows == 0) return HN_OK;
-  if (!ge || !h || !w0t_frag16 || !w2 || !gx) return HN_ERR_BAD_ARG;
-  return hn_head16_bwd(ge, h, w0t_frag16, w2, row_mask, gx, rows, stream);
-}
-
-// ---- the LAST layer of an energy / force evaluation (csrc/node_chain16.hip: NOVEC / NOGV) -------------------------------------
-// The read-out takes x only: vec_out feeds nothing, its gradient is identically zero.  16-row tiles, width 128.
-extern "C" int hermnet_node_update_fwd_last(const float* x1, const float* vec1, const float* wv_frag16, const float* wx0_frag16,
-                                            const float* bx0, const float* wx2_frag16, const float* bx2,
-                                            const float* row_active, const int* type_rowptr, const int* type_rowptr_host,
-                                            float* vp, float* h2b, float* q2, float* nrm, float* x_out, int num_nodes,
-                                            int num_rel, int hidden, void* stream) {
-  const UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q2, nrm, x_out,
-                        nullptr, num_nodes, num_rel};
-  const int rc = upd_fwd_refused(a, type_rowptr_host, hn_update16_supported(hidden) && !use_wide(hidden), true);
-  if (rc >= 0) return rc;
-  return hn_update16_fwd(hidden, a, HN_TILES(16), stream);
-}
-
-extern "C" int hermnet_node_update_bwd_last(const float* gx_out, const float* vp, const float* h2b, const float* q2,
-                                            const float* nrm, const float* wx2t_frag16, const float* wx0t_frag16,
-                                            const float* wvt_frag16, const float* row_active, const int* type_rowptr,
-                                            const int* type_rowptr_host, float* gx1, float* gvec1, int num_nodes, int num_rel,
-                                            int hidden, const hn_pending_grads* pending, void* stream) {
-  if (pending) return HN_ERR_BAD_ARG;             // no layer above the last one can have handed anything down
-  const UpdBwdArgs a = {gx_out, nullptr, vp, h2b, q2, nrm, wx2t_frag16, wx0t_frag16, wvt_frag16, row_active, type_rowptr, gx1,
-                        gvec1, num_nodes, num_rel, {}};
-  const int rc = upd_bwd_refused(a, type_rowptr_host, hn_update16_supported(hidden) && !use_wide(hidden), true);
-  if (rc >= 0) return rc;
-  return hn_update16_bwd(hidden, a, HN_TILES(16), stream);
+  if (take_tile64(hidden, HN_TILES(64))) HN_UPDATE_BWD(128, 64, 64, 1);
+  HN_TUNED_WIDTHS(HN_UPDATE_BWD)
 }

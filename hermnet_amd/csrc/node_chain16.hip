@@ -1,49 +1,47 @@
-// gfx950: the PaiNNUpdate chain (node_update_fwd / node_update_bwd of node_chain.hip; rmnet.py:94-107, 29-31) on 16-ROW
-// tiles -- for grids that 32-row tiles quantise badly.  (Written for v_mfma_f32_16x16x4_f32; since the second half of round 5
-// the products run as three-way bf16 splits on v_mfma_f32_16x16x32_bf16 at fp32 accuracy: see mma16_panel.)
+// gfx950: the PaiNNUpdate chain (node_update_fwd / node_update_bwd of node_chain.hip; rmnet.py:94-107, 29-31), the node
+// projection and the read-out on 16-ROW tiles, width 128 -- for grids that 32-row tiles quantise badly.
 //
 // Why: BASELINE configs[1] has 10,041 target rows = 314 tiles of 32 rows on 256 CUs: 58 CUs get two workgroups, 198 get
 // one, the launch lasts as long as the CUs with two (a makespan of 64 rows against 39 rows per CU on average: 0.61).  In
 // 16-row tiles the same rows are 628 workgroups, three or two per CU: 48 rows against 39 (0.82), and a CU's two or three
-// co-resident workgroups fill each other's epilogue phases.  The 16 x 16 x 4 form has the same FLOP rate as 32 x 32 x 2
-// (64 FLOP/clk/SIMD); what it costs is weight traffic (every fragment serves 16 rows instead of 32: twice the bytes
-// from L2), which is why the 32-row kernels stay in charge of large grids (node_chain.hip picks per launch).
+// co-resident workgroups fill each other's epilogue phases.  What 16-row tiles cost is weight traffic (every fragment serves
+// 16 rows instead of 32: twice the requests and bytes from L2), which is why the 32-row kernels stay in charge of large grids
+// (hermnet_node_update_tile_rows picks per launch).
 //
-// Data flow as in node_chain.hip: weights streamed from L2 in MFMA operand order -- here frag16(W)[(b * K/16 + Q) * 64 + l]
-// = float4 W[16 b + (l & 15)][16 Q + 4 (l >> 4) .. +3], one coalesced 1 KiB load per 16-channel block and 16-deep k-group --,
-// activations in [16][H + 8] LDS tiles (ds_read_b128 at row l & 15, k = 16 Q + 4 (l >> 4): conflict-free with the +8 pad),
-// accumulators transposed: lane l holds tile row l & 15 and the channels 16 b + 4 (l >> 4) .. +3 of block b as ONE float4.
-// A wave owns 32 channels (two blocks) of every output part, so vec_dot, q * vdot and r * v1 stay lane-local.
+// Data flow as in node_chain.hip -- fp32 in and out, both operands of a product as three bf16 planes, the six largest partial
+// products on v_mfma_f32_16x16x32_bf16 (mma16_panel_rb) --: weights streamed from L2 in MFMA operand order, here
+// frag16(W)[((b * K/32 + Q) * 3 + s) * 64 + l] = 8 bf16 of plane 2 - s, W[16 b + (l & 15)][32 Q + 8 (l >> 4) .. +7], one
+// coalesced 1 KiB load per 16-channel block and STEP (a plane of a 32-deep k-group); fp32 activations in [16][H + 8] LDS tiles
+// (two ds_read_b128 per k-group at row l & 15, k = 32 Q + 8 (l >> 4): conflict-free with the +8 pad), split into planes by the
+// consuming wave (split8); accumulators transposed: lane l holds tile row l & 15 and the channels 16 b + 4 (l >> 4) .. +3 of
+// block b as ONE float4.  A wave owns 32 channels (two blocks) of every output part, so vec_dot, q * vdot and r * v1 stay
+// lane-local.
 //
-// Round 5: ONE node launch per layer boundary, each way.  A tile's update (layer l) and the node projection of the rows it has
+// ONE node launch per layer boundary, each way.  A tile's update (layer l) and the node projection of the rows it has
 // just produced (layer l + 1: LayerNorm -> [H -> H] -> ScaledSiLU -> [H -> 3H] for every relation; rmnet.py:52 behind
-// rmnet.py:29-31, 94-107) are row-local, so `node_update_pre_fwd16_kernel` runs both: x_out never leaves the chip between
-// them.  The mirror `node_pre_update_bwd16_kernel` runs the projection's backward of layer l + 1 in front of the update
+// rmnet.py:29-31, 94-107) are row-local, so `node_update_fwd16_kernel<FUSE>` runs both: x_out never leaves the chip between
+// them.  The mirror `node_update_bwd16_kernel<FUSE>` runs the projection's backward of layer l + 1 in front of the update
 // backward of layer l: the per-relation sums stay in registers (no [T, N, H] partial sums in memory), the LayerNorm backward
 // runs on the tile.  The same phases also exist as kernels of their own (`node_pre_fwd16_kernel`, `node_pre_bwd16_kernel`):
 // the unfused form is the A/B and the bit-for-bit check of the fused one.
 #include "node_chain_common.h"
 
-// Workgroups per CU the register budget is cut for (launch bounds).  Round 5: every kernel here FITS three (<= 168 registers,
-// no spills) -- what it took: the vec_dot sums pinned where they are formed (hipcc had sunk them behind the last product and
-// kept v1 / v2 of all three components alive, spilled), v1 re-read from vp instead of held in registers, a weight ring of two
+namespace {
+
+// Workgroups per CU the register budget is cut for (launch bounds).  Every kernel here fits three workgroups (<= 168
+// registers) -- what it takes: the vec_dot sums pinned where they are formed (hipcc sinks them behind the last product and
+// keeps v1 / v2 of all three components alive, spilled), v1 re-read from vp instead of held in registers, a weight ring of two
 // for four-block products.  Measured (tools/chain_bench.py, 10,041 rows, same box, alternating builds, profiles/r05_chain_bench1.log):
 // the backward kernels gain a little from the third workgroup (fused 100.0 vs 101.8 us), the forward kernels LOSE (fused 102.0
 // vs 97.2 us) -- with three resident the products of each run slower and the launch ends no earlier: the matrix pipe is not
 // what a third workgroup's waves were waiting for.  So: forward 2, backward 3.
-#ifndef HN_U16_MINW_FWD
-#define HN_U16_MINW_FWD 2
-#endif
-#ifndef HN_U16_MINW_BWD
-#define HN_U16_MINW_BWD 3
-#endif
-
-namespace {
+constexpr int kMinWFwd16 = 2, kMinWBwd16 = 3;
 
 constexpr int kTR16 = 16;
 constexpr int kScr16Ld = 36, kScr16Floats = 16 * kScr16Ld;     // per-wave transpose scratch [16][36]
 
-// k-groups of weight fragments in flight per block: a group is 4 NB MFMAs of 32 cycles, an L2 hit 500-800 cycles
+// steps of weight fragments in flight per block (a step: one weight plane of a k-group, 1 .. 3 MFMAs per block; an L2 hit
+// 500-800 cycles)
 constexpr int ring16(int nb) { return nb >= 4 ? 2 : 4; }     // (64 registers for a ring of four at NB = 4 kept a third workgroup off the CU)
 
 template <int NB>
@@ -51,7 +49,7 @@ struct Ring16 { f32x4 v[ring16(NB)][NB]; };
 
 // Diagnostic builds (results wrong, time meaningful): -DHN_KO_BSTREAM=1 every weight request reads the stream's FIRST fragment
 // (same instructions, every request an L1 hit: what the weight stream's bytes cost), =2 no weight request at all (what its
-// instructions cost).  Round 5, 10,041 rows (profiles/r05_chain_ko.log): fused forward 98.4 / 96.2 / 75.2 us, fused backward
+// instructions cost).  10,041 rows (profiles/r05_chain_ko.log): fused forward 98.4 / 96.2 / 75.2 us, fused backward
 // 99.9 / 94.8 / 74.3 us for 0 / 1 / 2 -- the REQUESTS (one 1-KiB load per four MFMAs at 16 rows), not their bytes or their
 // latency, are a quarter of these kernels' time.  Halving them with two row blocks per fragment (mixed 32- / 16-row tiles so
 // that the busiest CU still holds three blocks) was prototyped on the projection kernel: bit-identical, 64.0 -> 59.6 us -- the
@@ -78,14 +76,14 @@ __device__ __forceinline__ void b16_preload(Ring16<NB>& r, const f32x4* const (&
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// Round 5 (second half): the products run on the BF16 matrix pipe at fp32 accuracy -- three-way bf16 splits, six partial
-// products per k-group on v_mfma_f32_16x16x32_bf16 (node_chain_common.h: split8, "fp32 products on the BF16 matrix pipe").
-// Measured before it was built, with the instruction mix alone (a diagnostic build, results wrong, time meaningful:
-// profiles/r05_split_timing.log): update_fwd 55 -> 32 us, pre_fwd16 64 -> 30, fused forward 98 -> 61.
+// The products run on the BF16 matrix pipe at fp32 accuracy -- three-way bf16 splits, six partial products per k-group on
+// v_mfma_f32_16x16x32_bf16 (node_chain_common.h: split8, "fp32 products on the BF16 matrix pipe").  Against the fp32 MFMAs,
+// measured with the instruction mix alone (a diagnostic build, results wrong, time meaningful: profiles/r05_split_timing.log):
+// update_fwd 55 -> 32 us, pre_fwd16 64 -> 30, fused forward 98 -> 61.
 //
 // Stream: a block's fragments are consumed as STEPS of one 1-KiB load each (lane l: 16 bytes = 8 bf16 of one weight plane,
-// W_p[16 b + (l & 15)][32 Q + 8 (l >> 4) .. +7]), in the order [k-group Q of 32][plane 2, 1, 0]: three steps per 32 k where
-// the fp32 form took two 16-deep groups -- 1.5 x the requests and bytes.  frag16(W)[((b * K/32 + Q) * 3 + s) * 64 + l].
+// W_p[16 b + (l & 15)][32 Q + 8 (l >> 4) .. +7]), in the order [k-group Q of 32][plane 2, 1, 0]: three steps per 32 k.
+// frag16(W)[((b * K/32 + Q) * 3 + s) * 64 + l].
 // ---------------------------------------------------------------------------------------------------------------------
 // float4s of one 16-channel block's fragment stream over K inputs (3 K / 32 steps of 64 lanes), floats of an [O, K] weight
 constexpr int frag16_f4(int K) { return K * 6; }
@@ -132,7 +130,7 @@ __device__ __forceinline__ void mma16_panel_rb(f32x4 (&acc)[RB][NB], const float
 #pragma unroll
         for (int j = 0; j < NB; ++j) ring.v[(n + PF) % RS][j] = wfrag(bp[j], (n + PF) * 64);
       }
-      if (HN_PIN_LOADS) fence_sched();               // (the requests stay in front of the step's MFMAs: node_chain_common.h)
+      fence_sched();                                 // (the requests stay in front of the step's MFMAs: node_chain_common.h)
 #pragma unroll
       for (int m = ps; m >= 0; --m)                  // activation planes ps .. 0: the smaller partial products first
 #pragma unroll
@@ -170,12 +168,10 @@ __device__ __forceinline__ void store16(float* scr, int lane, const f32x4 (&v)[2
   }
 }
 struct Load16 { f32x4 v[2]; };
-template <int LDG, bool NT = false>
+template <int LDG>
 __device__ __forceinline__ void issue16(Load16& b, int lane, rsrc_t r, int off) {
 #pragma unroll
-  for (int it = 0; it < 2; ++it)
-    b.v[it] = NT ? bld4_nt(r, off + (it * 8 + (lane >> 3)) * LDG + (lane & 7) * 4)
-                 : bld4(r, off + (it * 8 + (lane >> 3)) * LDG + (lane & 7) * 4);
+  for (int it = 0; it < 2; ++it) b.v[it] = bld4(r, off + (it * 8 + (lane >> 3)) * LDG + (lane & 7) * 4);
 }
 __device__ __forceinline__ void finish16(float* scr, int lane, const Load16& b, f32x4 (&out)[2]) {
 #pragma unroll
@@ -241,7 +237,7 @@ __device__ __forceinline__ void layernorm_tile16(float* tile, int tid, int nrows
   for (int m = 1; m < TPR; m <<= 1) s += __shfl_xor(s, m, 64);
   const float inv_h = 1.0f / (float)Hr;
   float mu = s * inv_h;
-  // corrected two-pass statistics (round 6; see node_chain.hip): the mean of the deviations is the rounding error of `mu`
+  // corrected two-pass statistics (see node_chain.hip): the mean of the deviations is the rounding error of `mu`
   float qq = 0.f, dd = 0.f;
 #pragma unroll
   for (int k = 0; k < NF; ++k)
@@ -343,9 +339,14 @@ __device__ __forceinline__ void pre_fwd16_phase(const PreFwdArgs& p, float* bufN
   }
 }
 
+// Dynamic LDS of this unit's kernels: the tiles they carve, then (unless said otherwise) the four waves' [16][36] scratch
+constexpr size_t lds16_bytes(int tile_floats, int behind = 4 * kScr16Floats) { return (size_t)(tile_floats + behind) * sizeof(float); }
+// the forward kernels, fused or not: three [16][H + 8] tiles
+constexpr size_t fwd16_lds_bytes(int H) { return lds16_bytes(3 * kTR16 * (H + 8)); }
+
 // The projection as a kernel of its own (the unfused form: A/B and bit-for-bit check of the fused kernel's second half)
 template <int H>
-__global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_pre_fwd16_kernel(PreFwdArgs p) {
+__global__ __launch_bounds__(256, kMinWFwd16) void node_pre_fwd16_kernel(PreFwdArgs p) {
   constexpr int TR = kTR16, LD = H + 8;
   extern __shared__ __align__(16) float lds[];               // 3 x [TR][LD], then 4 x [16][36] scratch
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -366,7 +367,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_pre_fwd16_kernel(Pr
 // (its r half stays unwritten: the matching backward, NOGV below, does not read it).  Every accumulator block of p and q sees
 // the MFMAs it sees in the general form, in the same order: x_out, vp, h2b, nrm and q are the same bits.
 template <int H, bool FUSE, bool NOVEC = false>
-__global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel(UpdFwdArgs a, PreFwdArgs p) {
+__global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdFwdArgs a, PreFwdArgs p) {
   static_assert(H == 128, "four waves x 32 channels");
   static_assert(!(FUSE && NOVEC), "the last layer has no layer above");
   constexpr int TR = kTR16, LD = H + 8, NB16 = H / 16;       // NB16: 16-channel blocks per part
@@ -423,12 +424,12 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
   const rsrc_t nrm_r = tile_rsrc(a.nrm + (size_t)row0 * H, nrows * H);
   f32x4 dot[2] = {zero4(), zero4()}, sq[2] = {zero4(), zero4()};
 
-  // ---- vp[d] = vec1[d] Wv^T; vec_dot and |v2|^2 accumulate in registers (v1 is re-read from vp for dvec = r v1: round 5 --
-  // 24 registers held across the whole kernel were what kept a third workgroup off the CU)
+  // ---- vp[d] = vec1[d] Wv^T; vec_dot and |v2|^2 accumulate in registers (v1 is re-read from vp for dvec = r v1:
+  // 24 registers held across the whole kernel keep a third workgroup off the CU)
   STAMP(0);
   STAMP_HWID();
-  // Round 5, second half: the three components in ONE product (three activation tiles per weight fragment): Wv was streamed
-  // once per component -- 144 of the kernel's 264 fragment requests per wave, and the requests are what a tile's time is made of.
+  // The three components in ONE product (three activation tiles per weight fragment): streamed once per component, Wv is
+  // 144 of the kernel's 264 fragment requests per wave, and the requests are what a tile's time is made of.
   Tile16Regs<H> regs;
   Ring16<4> rv;
   b16_preload(rv, bpv);
@@ -573,6 +574,10 @@ __global__ __launch_bounds__(256, HN_U16_MINW_FWD) void node_update_fwd16_kernel
 // LDS floats of the phase: the gxh tile [16][3H + 8] (3H + 8 = 8 mod 64 like H + 8: the same conflict-free ds_read_b128 pattern),
 // then the gh tile [16][H + 8]
 constexpr int pre_bwd16_tile_floats(int H) { return kTR16 * (3 * H + 8); }
+// (node_pre_bwd16_kernel and the fused update backward, which turns the gxh tile's space into its two [16][H + 8] tiles)
+constexpr size_t pre_bwd16_lds_bytes(int H) { return lds16_bytes(pre_bwd16_tile_floats(H) + kTR16 * (H + 8)); }
+// the update backward without the projection's: two [16][H + 8] tiles
+constexpr size_t upd_bwd16_lds_bytes(int H) { return lds16_bytes(2 * kTR16 * (H + 8)); }
 
 template <int H>
 struct Tile16Regs3 { f32x4 v[kTR16 * 3 * H / 4 / 256]; };
@@ -655,7 +660,7 @@ __device__ __forceinline__ void pre_bwd16_phase(const float* gxh, const float* h
 }
 
 template <int H>
-__global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_pre_bwd16_kernel(PreBwdArgs a) {
+__global__ __launch_bounds__(256, kMinWBwd16) void node_pre_bwd16_kernel(PreBwdArgs a) {
   constexpr int TR = kTR16, LD = H + 8;
   extern __shared__ __align__(16) float lds[];               // [TR][3H + 8], [TR][LD], then 4 x [16][36] scratch
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -680,7 +685,7 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_pre_bwd16_kernel(Pr
 //   * gv q3 + s v2 may differ from s v2 in the SIGN of a zero (-0 + +0 = +0), but only as an MFMA operand whose accumulator
 //     started at +0: a +-0 product changes neither a non-zero sum nor a +0 one.
 template <int H, bool FUSE, bool NOGV = false>
-__global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel(UpdBwdArgs a) {
+__global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdBwdArgs a) {
   static_assert(H == 128, "four waves x 32 channels");
   static_assert(!(FUSE && NOGV), "the last layer has no layer above");
   constexpr int TR = kTR16, LD = H + 8, NB16 = H / 16, V = H / 4, F4 = TR * H / 4 / 256;
@@ -773,9 +778,9 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
   }
   // h2b, gx and q of this wave's accumulator positions: requested now, transposed behind the first product
   Load16 lh2, lgx, lq2;
-  issue16<H, true>(lh2, lane, h2b_r, cw);
+  issue16<H>(lh2, lane, h2b_r, cw);
   issue16<H>(lgx, lane, gxo_r, cw);
-  issue16<2 * H, true>(lq2, lane, q23_r, cw);
+  issue16<2 * H>(lq2, lane, q23_r, cw);
   __syncthreads();
   STAMP(7);
   // ---- ga2 = gq Wx2  (K = 3H: three panels)
@@ -818,10 +823,10 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
   }
   // inputs of the later epilogues, requested one product ahead
   Load16 lnr, lgv, lq3, lw1, lw2;
-  issue16<H, true>(lnr, lane, nrm_r, cw);
+  issue16<H>(lnr, lane, nrm_r, cw);
   if constexpr (!NOGV) {
     issue16<3 * H>(lgv, lane, gvo_r, cw);
-    issue16<2 * H, true>(lq3, lane, q23_r, H + cw);
+    issue16<2 * H>(lq3, lane, q23_r, H + cw);
   }
   issue16<6 * H>(lw1, lane, vp_r, cw);
   issue16<6 * H>(lw2, lane, vp_r, H + cw);
@@ -895,8 +900,8 @@ __global__ __launch_bounds__(256, HN_U16_MINW_BWD) void node_update_bwd16_kernel
 
 // =====================================================================================================================
 // The read-out (hermnet.py:112-116, 129) on 16-row tiles: Linear(H -> C) on the matrix pipe, ScaledSiLU and the C -> 1 Linear in
-// the epilogue; H = 128, C = 64.  Round 5: the VALU form of csrc/node_kernels.hip (every workgroup stages the whole weight in LDS)
-// took 24 us forward + 16 us backward at 10k rows for 0.3 GFLOP.
+// the epilogue; H = 128, C = 64.  The VALU form of csrc/node_kernels.hip (every workgroup stages the whole weight in LDS)
+// takes 24 us forward + 16 us backward at 10k rows for 0.3 GFLOP.
 // =====================================================================================================================
 struct HeadArgs {
   const float* x;        // fwd: x [N, H];  bwd: h [N, C] (saved pre-activations)
@@ -910,6 +915,9 @@ struct HeadArgs {
   float* out;            // fwd: e [N];  bwd: gx [N, H]
   int N;
 };
+// forward: the [16][H + 8] tile, then [4][16] partial row sums; backward: the [16][C + 8] tile, then the scratch
+constexpr size_t head16_fwd_lds_bytes(int H) { return lds16_bytes(kTR16 * (H + 8), 4 * 16); }
+constexpr size_t head16_bwd_lds_bytes(int C) { return lds16_bytes(kTR16 * (C + 8)); }
 
 template <int H, int C>
 __global__ __launch_bounds__(256) void energy_head16_fwd_kernel(HeadArgs a) {
@@ -976,79 +984,120 @@ __global__ __launch_bounds__(256) void energy_head16_bwd_kernel(HeadArgs a) {
   store16<H>(scr, lane, acc, tile_rsrc(a.out + (size_t)row0 * H, nrows * H), 32 * wave);
 }
 
+constexpr int kH16 = 128, kC16 = 64;      // the width this unit's kernels are instantiated at; the read-out's columns
+inline dim3 grid16(int rows) { return dim3((unsigned)((rows + kTR16 - 1) / kTR16)); }
+bool head16_supported(int hidden, int cols) { return hidden == kH16 && cols == kC16; }
+
 }  // namespace
-
-int hn_head16_supported(int hidden, int cols) { return hidden == 128 && cols == 64; }
-
-int hn_head16_fwd(const float* x, const float* w0_frag16, const float* b0, const float* w2, const float* b2, const float* mask,
-                  float* h, float* e, int rows, void* stream) {
-  HeadArgs a = {x, w0_frag16, b0, w2, b2, nullptr, mask, h, e, rows};
-  return launch_chain(energy_head16_fwd_kernel<128, 64>, dim3((unsigned)((rows + 15) / 16)), (size_t)(16 * 136 + 64) * 4, stream, a);
-}
-
-int hn_head16_bwd(const float* ge, const float* h, const float* w0t_frag16, const float* w2, const float* mask, float* gx,
-                  int rows, void* stream) {
-  HeadArgs a = {h, w0t_frag16, nullptr, w2, nullptr, ge, mask, nullptr, gx, rows};
-  return launch_chain(energy_head16_bwd_kernel<128, 64>, dim3((unsigned)((rows + 15) / 16)), (size_t)(16 * 72 + 4 * kScr16Floats) * 4,
-                      stream, a);
-}
-
-namespace {
-}  // namespace
-
-// Entry points of this translation unit (called by node_chain.hip's dispatch).  The weight pointers of the argument blocks
-// must hold frag16 copies (include/hermnet_hip.h: hermnet_node_update_fwd, "16-row form").
-int hn_update16_supported(int hidden) { return hidden == 128; }
-
-namespace {
-constexpr size_t kLdsUpd16 = (size_t)(2 * 16 * 136 + 4 * kScr16Floats) * 4;
-constexpr size_t kLdsFwdFused16 = (size_t)(3 * 16 * 136 + 4 * kScr16Floats) * 4;
-constexpr size_t kLdsBwdFused16 = (size_t)(pre_bwd16_tile_floats(128) + 16 * 136 + 4 * kScr16Floats) * 4;
-
-int launch_fwd16(bool fuse, int tiles, size_t lds_bytes, void* stream, const UpdFwdArgs& a, const PreFwdArgs& p) {
-  if (a.vec_out == nullptr) {                     // the last layer's form (see the kernel: NOVEC)
-    if (fuse) return HN_ERR_BAD_ARG;
-    hipLaunchKernelGGL((node_update_fwd16_kernel<128, false, true>), dim3((unsigned)tiles), dim3(256), lds_bytes, (hipStream_t)stream, a, p);
-  } else if (fuse) hipLaunchKernelGGL((node_update_fwd16_kernel<128, true>), dim3((unsigned)tiles), dim3(256), lds_bytes, (hipStream_t)stream, a, p);
-  else hipLaunchKernelGGL((node_update_fwd16_kernel<128, false>), dim3((unsigned)tiles), dim3(256), lds_bytes, (hipStream_t)stream, a, p);
-  return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
-}
-}  // namespace
-
-int hn_update16_fwd(int hidden, const UpdFwdArgs& a, int tiles, void* stream) {
-  if (hidden != 128) return HN_ERR_BAD_ARG;
-  return launch_fwd16(false, tiles, kLdsFwdFused16, stream, a, PreFwdArgs{});
-}
-
-// update of layer l + node projection of layer l + 1 on the same 16-row tiles (p.x is unused: the rows come from the update)
-int hn_update16_pre_fwd(int hidden, const UpdFwdArgs& a, const PreFwdArgs& p, int tiles, void* stream) {
-  if (hidden != 128 || p.Ns != a.N || p.src_ranges != nullptr || p.wmode != 0) return HN_ERR_BAD_ARG;
-  return launch_fwd16(true, tiles, kLdsFwdFused16, stream, a, p);
-}
-
-int hn_update16_bwd(int hidden, const UpdBwdArgs& a, int tiles, void* stream) {
-  if (hidden != 128) return HN_ERR_BAD_ARG;
-  if (a.gvo == nullptr) {                         // the last layer's form (see the kernel: NOGV); nothing is ever pending above it
-    if (a.pend.gxh != nullptr || a.pend.gn != nullptr) return HN_ERR_BAD_ARG;
-    return launch_chain(node_update_bwd16_kernel<128, false, true>, dim3((unsigned)tiles), kLdsUpd16, stream, a);
-  }
-  if (a.pend.gxh != nullptr)
-    return launch_chain(node_update_bwd16_kernel<128, true>, dim3((unsigned)tiles), kLdsBwdFused16, stream, a);
-  return launch_chain(node_update_bwd16_kernel<128, false>, dim3((unsigned)tiles), kLdsUpd16, stream, a);
-}
-
-int hn_pre16_fwd(int hidden, const PreFwdArgs& p, void* stream) {
-  if (hidden != 128 || p.src_ranges != nullptr || p.wmode != 0) return HN_ERR_BAD_ARG;
-  return launch_chain(node_pre_fwd16_kernel<128>, dim3((unsigned)((p.Ns + 15) / 16)), kLdsFwdFused16, stream, p);
-}
-
-int hn_pre16_bwd(int hidden, const PreBwdArgs& a, void* stream) {
-  if (hidden != 128 || a.src_ranges != nullptr || a.wmode != 0) return HN_ERR_BAD_ARG;
-  return launch_chain(node_pre_bwd16_kernel<128>, dim3((unsigned)((a.Ns + 15) / 16)), kLdsBwdFused16, stream, a);
-}
 
 #ifdef HN_STAMPS
 extern "C" int hermnet_debug_stamps16(unsigned long long* out_host, int count) {
   return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(hn_stamps), (size_t)count * sizeof(unsigned long long)) == hipSuccess ? 0 : 3;
 }
 #endif
+
+// ---- what node_chain.hip's hermnet_node_update_fwd / _bwd reach with tile_rows = 16 (node_chain_common.h declares them; the
+// caller has checked the argument blocks and hn_update16_supported).  The weight pointers of the argument blocks must hold frag16
+// copies (include/hermnet_hip.h: hermnet_node_update_fwd, "16-row form").
+int hn_update16_supported(int hidden) { return hidden == kH16; }
+
+int hn_update16_fwd(const UpdFwdArgs& a, int tiles, void* stream) {
+  return launch_chain<node_update_fwd16_kernel<kH16, false>>(dim3((unsigned)tiles), fwd16_lds_bytes(kH16), stream, a, PreFwdArgs{});
+}
+
+int hn_update16_bwd(const UpdBwdArgs& a, int tiles, void* stream) {
+  if (a.pend.gxh != nullptr)        // fused: the projection's backward of the layer above in front
+    return launch_chain<node_update_bwd16_kernel<kH16, true>>(dim3((unsigned)tiles), pre_bwd16_lds_bytes(kH16), stream, a);
+  return launch_chain<node_update_bwd16_kernel<kH16, false>>(dim3((unsigned)tiles), upd_bwd16_lds_bytes(kH16), stream, a);
+}
+
+// ---- the layer boundary as ONE node launch each way ---------------------------------------------------------------------------
+extern "C" int hermnet_node_fused_supported(int hidden) { return hn_update16_supported(hidden); }
+
+// update of layer l + node projection of layer l + 1 on the same 16-row tiles (p.x is unused: the rows come from the update)
+extern "C" int hermnet_node_update_pre_fwd(const float* x1, const float* vec1, const float* wv_frag16, const float* wx0_frag16,
+                                           const float* bx0, const float* wx2_frag16, const float* bx2,
+                                           const float* row_active, const int* type_rowptr, const int* type_rowptr_host,
+                                           float* vp, float* h2b, float* q23, float* nrm, float* x_out, float* vec_out,
+                                           int num_nodes, int num_rel, int hidden, const float* w1_frag16, const float* b1,
+                                           const float* w2_frag16, const float* b2, float* hb, float* xh, float* mean,
+                                           float* rstd, int next_num_rel, int hidden_real, float eps, void* stream) {
+  if (next_num_rel <= 0 || hidden_real > hidden) return HN_ERR_BAD_ARG;
+  const UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q23, nrm, x_out,
+                        vec_out, num_nodes, num_rel};
+  const int rc = upd_fwd_refused(a, type_rowptr_host, hn_update16_supported(hidden), false);
+  if (rc >= 0) return rc;
+  if (!w1_frag16 || !b1 || !w2_frag16 || !b2 || !hb || !xh || !mean || !rstd) return HN_ERR_BAD_ARG;
+  const PreFwdArgs p = {x_out, w1_frag16, b1, w2_frag16, b2, hb, xh, mean, rstd, nullptr, num_nodes, next_num_rel,
+                        real_width(hidden_real, hidden), eps, nullptr, 0, 0};
+  return launch_chain<node_update_fwd16_kernel<kH16, true>>(dim3((unsigned)HN_TILES(16)), fwd16_lds_bytes(kH16), stream, a, p);
+}
+
+extern "C" int hermnet_node_pre_fwd16(const float* x, const float* w1_frag16, const float* b1, const float* w2_frag16,
+                                      const float* b2, float* hb, float* xh, float* mean, float* rstd, int num_src,
+                                      int num_rel, int hidden, int hidden_real, float eps, void* stream) {
+  if (num_src < 0 || num_rel <= 0 || hidden_real > hidden || !hn_update16_supported(hidden)) return HN_ERR_BAD_ARG;
+  if (num_src == 0) return HN_OK;
+  if (!x || !w1_frag16 || !b1 || !w2_frag16 || !b2 || !hb || !xh || !mean || !rstd) return HN_ERR_BAD_ARG;
+  const PreFwdArgs p = {x, w1_frag16, b1, w2_frag16, b2, hb, xh, mean, rstd, nullptr, num_src, num_rel,
+                        real_width(hidden_real, hidden), eps, nullptr, 0, 0};
+  return launch_chain<node_pre_fwd16_kernel<kH16>>(grid16(num_src), fwd16_lds_bytes(kH16), stream, p);
+}
+
+extern "C" int hermnet_node_pre_bwd16(const float* gxh, const float* hb, const float* w2t_frag16, const float* w1t_frag16,
+                                      float* gn_parts, int num_src, int num_rel, int hidden, void* stream) {
+  if (num_src < 0 || num_rel <= 0 || !hn_update16_supported(hidden)) return HN_ERR_BAD_ARG;
+  if (num_src == 0) return HN_OK;
+  if (!gxh || !hb || !w2t_frag16 || !w1t_frag16 || !gn_parts) return HN_ERR_BAD_ARG;
+  const PreBwdArgs a = {gxh, hb, w2t_frag16, w1t_frag16, gn_parts, nullptr, num_src, num_rel, nullptr, 0, 0};
+  return launch_chain<node_pre_bwd16_kernel<kH16>>(grid16(num_src), pre_bwd16_lds_bytes(kH16), stream, a);
+}
+
+// ---- the read-out on the matrix pipe (hidden 128 -> 64) ---------------------------------------------------------------------------
+extern "C" int hermnet_energy_head16_supported(int hidden, int cols) { return head16_supported(hidden, cols); }
+
+extern "C" int hermnet_energy_head16_fwd(const float* x, const float* w0_frag16, const float* b0, const float* w2, const float* b2,
+                                         const float* row_mask, float* h, float* e, int rows, int hidden, int cols, void* stream) {
+  if (rows < 0 || !head16_supported(hidden, cols)) return HN_ERR_BAD_ARG;
+  if (rows == 0) return HN_OK;
+  if (!x || !w0_frag16 || !b0 || !w2 || !h || !e) return HN_ERR_BAD_ARG;
+  const HeadArgs a = {x, w0_frag16, b0, w2, b2, nullptr, row_mask, h, e, rows};
+  return launch_chain<energy_head16_fwd_kernel<kH16, kC16>>(grid16(rows), head16_fwd_lds_bytes(kH16), stream, a);
+}
+
+extern "C" int hermnet_energy_head16_bwd(const float* ge, const float* h, const float* w0t_frag16, const float* w2,
+                                         const float* row_mask, float* gx, int rows, int hidden, int cols, void* stream) {
+  if (rows < 0 || !head16_supported(hidden, cols)) return HN_ERR_BAD_ARG;
+  if (rows == 0) return HN_OK;
+  if (!ge || !h || !w0t_frag16 || !w2 || !gx) return HN_ERR_BAD_ARG;
+  const HeadArgs a = {h, w0t_frag16, nullptr, w2, nullptr, ge, row_mask, nullptr, gx, rows};
+  return launch_chain<energy_head16_bwd_kernel<kH16, kC16>>(grid16(rows), head16_bwd_lds_bytes(kC16), stream, a);
+}
+
+// ---- the LAST layer of an energy / force evaluation (NOVEC / NOGV) --------------------------------------------------------------
+// The read-out takes x only: vec_out feeds nothing, its gradient is identically zero.  16-row tiles, width 128.
+extern "C" int hermnet_node_update_fwd_last(const float* x1, const float* vec1, const float* wv_frag16, const float* wx0_frag16,
+                                            const float* bx0, const float* wx2_frag16, const float* bx2,
+                                            const float* row_active, const int* type_rowptr, const int* type_rowptr_host,
+                                            float* vp, float* h2b, float* q2, float* nrm, float* x_out, int num_nodes,
+                                            int num_rel, int hidden, void* stream) {
+  const UpdFwdArgs a = {x1, vec1, wv_frag16, wx0_frag16, bx0, wx2_frag16, bx2, row_active, type_rowptr, vp, h2b, q2, nrm, x_out,
+                        nullptr, num_nodes, num_rel};
+  const int rc = upd_fwd_refused(a, type_rowptr_host, hn_update16_supported(hidden) && !use_wide(hidden), true);
+  if (rc >= 0) return rc;
+  return launch_chain<node_update_fwd16_kernel<kH16, false, true>>(dim3((unsigned)HN_TILES(16)), fwd16_lds_bytes(kH16), stream, a,
+                                                                  PreFwdArgs{});
+}
+
+extern "C" int hermnet_node_update_bwd_last(const float* gx_out, const float* vp, const float* h2b, const float* q2,
+                                            const float* nrm, const float* wx2t_frag16, const float* wx0t_frag16,
+                                            const float* wvt_frag16, const float* row_active, const int* type_rowptr,
+                                            const int* type_rowptr_host, float* gx1, float* gvec1, int num_nodes, int num_rel,
+                                            int hidden, const hn_pending_grads* pending, void* stream) {
+  if (pending) return HN_ERR_BAD_ARG;             // no layer above the last one can have handed anything down
+  const UpdBwdArgs a = {gx_out, nullptr, vp, h2b, q2, nrm, wx2t_frag16, wx0t_frag16, wvt_frag16, row_active, type_rowptr, gx1,
+                        gvec1, num_nodes, num_rel, {}};
+  const int rc = upd_bwd_refused(a, type_rowptr_host, hn_update16_supported(hidden) && !use_wide(hidden), true);
+  if (rc >= 0) return rc;
+  return launch_chain<node_update_bwd16_kernel<kH16, false, true>>(dim3((unsigned)HN_TILES(16)), upd_bwd16_lds_bytes(kH16), stream, a);
+}

@@ -1,17 +1,18 @@
-// Shared pieces of the node chain kernels (node_chain.hip: widths 64 / 128 / 256; node_chain_wide.hip: every
-// multiple of 64 up to 512): MFMA panel loop with streamed weight fragments, buffer-descriptor tile I/O, the
-// wave-private LDS transposes of the epilogues, tile bookkeeping and the launcher.  Included inside each
-// translation unit's anonymous namespace user: everything here is `static`/inline by construction.
+// Shared pieces of the node chain kernels' three translation units (node_chain.hip: widths 64 / 128 / 256 on 64- / 32-row
+// tiles; node_chain_wide.hip: every multiple of 64 up to 512; node_chain16.hip: width 128 on 16-row tiles).
+//   * the argument blocks, the functions that cross the units (declared once, below) and the host-side checks the entry
+//     points of more than one unit make;
+//   * the product: fp32 operands as three bf16 planes each (split8), v_mfma_f32_32x32x16_bf16 over weight fragments streamed
+//     from L2 in steps of one plane (frag(W): mma_panel; the 16-row form, frag16(W) on 16x16x32_bf16, is node_chain16.hip's);
+//   * buffer-descriptor tile I/O, the wave-private LDS transposes of the epilogues, tile bookkeeping, the launcher.
+// Everything from `namespace {` on is internal to the unit that includes it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/hermnet_hip.h"
 
-#ifndef HN_NT_SAVED_LOADS
-#define HN_NT_SAVED_LOADS 0      // (the read-once side of the same tensors: measured, no gain -- profiles/r06_nt_saved_ab.log)
-#endif
-// Argument blocks of the four chain kernels (plain structs shared by both translation units)
+// Argument blocks of the four chain kernels (plain structs shared by the three translation units)
 namespace hn_chain {
 struct PreFwdArgs {
   const float* x;      // [Ns, H]
@@ -99,7 +100,56 @@ struct UpdBwdArgs {
 }  // namespace hn_chain
 using namespace hn_chain;
 
+// ---- what crosses the translation units (each defined once; the argument blocks are checked by the caller) ----------------
+int hn_option(int option);      // host_api.cpp: process-wide options (hermnet_set_option)
+// node_chain_wide.hip: the four chains for every multiple of 64 from 128 to 512
+int hn_wide_pre_fwd(int hidden, const PreFwdArgs& a, void* stream);
+int hn_wide_pre_bwd(int hidden, const PreBwdArgs& a, void* stream);
+int hn_wide_update_fwd(int hidden, const UpdFwdArgs& a, int tiles, void* stream);
+int hn_wide_update_bwd(int hidden, const UpdBwdArgs& a, int tiles, void* stream);
+// node_chain16.hip: the update chain on 16-row tiles (frag16 weight copies); the width it exists at
+int hn_update16_supported(int hidden);
+int hn_update16_fwd(const UpdFwdArgs& a, int tiles, void* stream);
+int hn_update16_bwd(const UpdBwdArgs& a, int tiles, void* stream);
+
 namespace {
+
+// ---- host side: what the entry points of more than one unit check and count alike --------------------------------------------
+// Widths 64 / 128 / 256 have tuned instances in node_chain.hip; every other multiple of 64 up to 512 -- the reference's default
+// hidden_channels = 512 among them (hermnet.py:86) -- takes the panelled kernels of node_chain_wide.hip.  Option
+// HN_OPT_NODE_CHAIN_WIDE = 1 sends 128 and 256 there too (tests, comparisons).
+inline bool use_wide(int hidden) {
+  const int force = hn_option(HN_OPT_NODE_CHAIN_WIDE);
+  if (hidden == 64) return false;
+  return force != 0 || !(hidden == 128 || hidden == 256);
+}
+inline int real_width(int hidden_real, int hidden) { return hidden_real > 0 ? hidden_real : hidden; }
+
+// TR-row tiles of the target rows (find_tile below: every relation's row block is cut on its own, then the unknown elements')
+inline int tiles_of(const int* rp_host, int T, int N, int TR) {
+  int n = 0;
+  for (int t = 0; t < T; ++t) n += (rp_host[t + 1] - rp_host[t] + TR - 1) / TR;
+  return n + (N - rp_host[T] + TR - 1) / TR;
+}
+#define HN_TILES(TR) tiles_of(type_rowptr_host, num_rel, num_nodes, TR)
+
+// The one check of the update chains' arguments, each way, behind all five entry points -> -1: launch; else what the entry
+// point returns (HN_OK: no rows, the pointers unchecked; HN_ERR_BAD_ARG).  `supported`: the form's kernels exist at this
+// width; `last`: the last-layer form, whose vec_out / gvec_out is null.
+inline int upd_fwd_refused(const UpdFwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
+  if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
+  if (a.N == 0) return HN_OK;
+  const bool ok = a.x1 && a.vec1 && a.wvf && a.wx0f && a.bx0 && a.wx2f && a.bx2 && a.type_rowptr && a.vp && a.h2b && a.q23 &&
+                  a.nrm && a.x_out && (last || a.vec_out) && type_rowptr_host[a.T] <= a.N;
+  return ok ? -1 : HN_ERR_BAD_ARG;
+}
+inline int upd_bwd_refused(const UpdBwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
+  if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
+  if (a.N == 0) return HN_OK;
+  const bool ok = a.gxo && (last || a.gvo) && a.vp && a.h2b && a.q23 && a.nrm && a.wx2tf && a.wx0tf && a.wvtf && a.type_rowptr &&
+                  a.gx1 && a.gvec1 && type_rowptr_host[a.T] <= a.N;
+  return ok ? -1 : HN_ERR_BAD_ARG;
+}
 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -167,34 +217,18 @@ struct Cfg {
   static_assert(CB % WC == 0 && (TR / 32) % WR == 0 && RB >= 1 && F4 >= 1, "unsupported tile");
 };
 
-// ---- B operand: a ring of RS weight fragments per column block, RS - 1 steps ahead of use ----------------------------
-// (written for the fp32 MFMAs: a k-group was RB * NJ * 4 MFMAs = RB * NJ * 256 cycles, an L2 hit under load 500-800: three
-// groups ahead.  Since the products run as bf16 splits a slot holds one STEP: see mma_panel)
+// ---- B operand: a ring of RS weight fragments per column block, RS - 1 STEPS ahead of use (a slot holds one step of one
+// weight plane: see mma_panel) --------------------------------------------------------------------------------------------
 template <int NJ, int RS>
 struct BRing { f32x4 v[RS][NJ]; };
 
-// ring slots of a product with RB x NJ accumulator blocks per wave
-// (three slots: a k-group is three steps, so the slots of a group's steps are compile-time constants in a loop rolled per GROUP --
-// with four the loop body had to be four groups, twelve steps, and the update kernels spilled)
-#ifndef HN_RS
-#define HN_RS 3
-#endif
-constexpr int kRS = HN_RS;
-constexpr int ring_size(int rb_nj, bool more) { return kRS; }
-
-// Experiment knob (-DHN_STAGGER=n): the workgroup that lands in an ODD wave slot of its SIMD (the second of two
-// co-resident ones) starts n x 8128 cycles late, so that the two do not walk through their matrix phases in lockstep.
-__device__ __forceinline__ void stagger_start() {
-#ifdef HN_STAGGER
-  unsigned hw;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-  if (hw & 1)
-    for (int i = 0; i < HN_STAGGER; ++i) __builtin_amdgcn_s_sleep(127);
-#endif
-}
+// Ring slots of the products of node_chain.hip.  Three: a k-group is three steps, so the slots of a group's steps are
+// compile-time constants in a loop rolled per GROUP -- with four the loop body has to be four groups, twelve steps, and the
+// update kernels spill (depths 2 .. 12 measured: profiles/r04_chain_variants.log, r05_ring_ab.log).
+constexpr int kRS = 3;
 
 // ---------------------------------------------------------------------------------------------------------------------
-// fp32 products on the BF16 matrix pipe (round 5).  The fp32 MFMAs (v_mfma_f32_32x32x2_f32 / 16x16x4) deliver 64 FLOP/clk/SIMD,
+// fp32 products on the BF16 matrix pipe.  The fp32 MFMAs (v_mfma_f32_32x32x2_f32 / 16x16x4) deliver 64 FLOP/clk/SIMD,
 // the bf16 ones (32x32x16 / 16x16x32) 1024.  An fp32 value split THREE ways into bf16 planes, x = x0 + x1 + x2 EXACTLY (3 x 8
 // significant bits; each plane the round-to-nearest-even of what the planes before it leave), and the six largest of the nine
 // partial products -- w2 x0, w1 x1, w1 x0, w0 x2, w0 x1, w0 x0, smallest first, accumulated in fp32 by the MFMA; the three dropped
@@ -206,9 +240,6 @@ __device__ __forceinline__ void stagger_start() {
 typedef __bf16 hn_bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 hn_bf16x2 __attribute__((ext_vector_type(2)));
 typedef float hn_f32x2 __attribute__((ext_vector_type(2)));
-#ifndef HN_SPLIT_SCALAR
-#define HN_SPLIT_SCALAR 0
-#endif
 struct Split8 { hn_bf16x8 p[3]; };          // p[0] + p[1] + p[2] == the eight fp32 values (exactly, barring under/overflow)
 
 __device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, Split8& o) {
@@ -222,15 +253,9 @@ __device__ __forceinline__ void split8(const f32x4& lo, const f32x4& hi, Split8&
       o.p[p][e] = h[0]; o.p[p][e + 1] = h[1];
       if (p < 2) {
         const hn_f32x2 back = __builtin_convertvector(h, hn_f32x2);
-#if HN_SPLIT_SCALAR
-        // (A/B, VERDICT r5 item 3: MI355X_MICROARCH.md prices a packed fp32 op beside MFMAs at +22-26 cycles per gap; the
-        // residuals as two v_sub_f32 -- the pins keep the SLP vectoriser from re-packing them)
-        float r0 = x[e] - back[0], r1 = x[e + 1] - back[1];
-        pin(r0); pin(r1);
-        x[e] = r0; x[e + 1] = r1;
-#else
+        // (packed, v_pk_add_f32: the residuals as two pinned scalar subtractions measured no faster, 2.875 vs 2.865 ms/step --
+        // profiles/r06_split_scalar_ab.log)
         x[e] -= back[0]; x[e + 1] -= back[1];                             // exact: the residual fits fp32
-#endif
       }
     }
   }
@@ -253,27 +278,19 @@ __device__ __forceinline__ void b_preload(BRing<NJ, RS>& r, const f32x4* const (
 // A block's fragments are consumed as STEPS of one 1-KiB load each (lane l: 16 bytes = 8 bf16 of one weight plane,
 // W_p[32 cb + (l & 31)][16 Q + 8 (l >> 5) .. +7]) in the order [k-group Q of 16][plane 2, 1, 0]:
 //     frag(W)[((cb * K/16 + Q) * 3 + s) * 64 + l],   step s of a group runs s + 1 MFMAs per accumulator block
-// (activation planes s .. 0) -- three steps per 16 k where the fp32 form took two 8-deep groups: 1.5 x the requests and bytes.
+// (activation planes s .. 0).
 // `As`: this lane's LDS read pointer, &tile[(first row of the wave + (l & 31)) * LD + 4 (l >> 5)] (the tile is fp32).
 // The ring holds steps 0 .. RS-2 on entry.  MORE: the stream continues behind this panel (next panel of the same
 // product): its first RS - 1 steps are requested too and sit in slots 0 .. RS-2 on exit.
-// PIN: a step's requests stay in front of its MFMAs (see below); the pre-forward kernels, whose loops hipcc leaves alone
-// anyway, ran 5x slower with the fence in place (found by measurement, not understood) and pass false.
-#ifndef HN_PIN_LOADS
-#define HN_PIN_LOADS 1
-#endif
-#ifndef HN_PIN_PRE
-#define HN_PIN_PRE false     // the pre-forward kernels' products
-#endif
+// PIN: a step's requests stay in front of its MFMAs (see below; measured: profiles/r04_pin_loads.log); the pre-forward
+// kernels, whose loops hipcc leaves alone anyway, ran 5x slower with the fence in place (found by measurement, not understood)
+// and pass kPinPre.
+constexpr bool kPinPre = false;
 // DB: the activation planes of the NEXT k-group are split beside this group's MFMAs (a second set of planes: 12 RB more
 // registers -- the projection kernels have them, the update kernels, at their 256-register budgets, do not and pass false).
-#ifndef HN_SPLIT_DB
-#define HN_SPLIT_DB 1
-#endif
-template <int KP, int LD, int RB, int NJ, int RS, bool MORE, bool PIN = true, bool DBT = true>
+template <int KP, int LD, int RB, int NJ, int RS, bool MORE, bool PIN = true, bool DB = true>
 __device__ __forceinline__ void mma_panel(f32x16 (&acc)[RB][NJ], const float* As, const f32x4* const (&bp)[NJ],
                                           BRing<NJ, RS>& ring) {
-  constexpr bool DB = DBT && HN_SPLIT_DB;
   // k-groups; groups / steps of one pass of the rolled loop: the fewest groups whose steps fill whole turns of the ring -- an
   // EVEN number of them when the planes are double-buffered (a group's buffer is then a compile-time constant too)
   constexpr int CH0 = RS % 3 == 0 ? RS / 3 : RS;
@@ -318,8 +335,8 @@ __device__ __forceinline__ void mma_panel(f32x16 (&acc)[RB][NJ], const float* As
           for (int j = 0; j < NJ; ++j) ring.v[(sl + PF) % RS][j] = bp[j][(3 * g0 + sl + PF) * 64];
         }
         // the requests stay HERE, in front of the step's MFMAs: left alone, hipcc's scheduler sinks a weight request towards
-        // its use (fewer live registers) and the product waits for L2 every few steps (round 4: read off the ISA)
-        if (PIN && HN_PIN_LOADS) fence_sched();
+        // its use (fewer live registers) and the product waits for L2 every few steps (read off the ISA)
+        if (PIN) fence_sched();
 #pragma unroll
         for (int m = ps; m >= 0; --m)                               // activation planes ps .. 0
 #pragma unroll
@@ -396,29 +413,19 @@ __device__ __forceinline__ f32x4 bld4(rsrc_t r, int off) {
   const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, off * 4, 0, 0);
   return __builtin_bit_cast(f32x4, u);
 }
-// non-temporal load: saved tensors a backward kernel reads exactly once
-__device__ __forceinline__ f32x4 bld4_nt(rsrc_t r, int off) {
-#ifdef HN_KO_LOADS
-  return (f32x4){1.f, 0.5f, 0.25f, 2.f};
-#endif
-  const u32x4 u = __builtin_amdgcn_raw_buffer_load_b128(r, off * 4, 0, HN_NT_SAVED_LOADS ? 2 : 0);
-  return __builtin_bit_cast(f32x4, u);
-}
 __device__ __forceinline__ void bst4(rsrc_t r, int off, f32x4 v) {
   HN_STORE_IF(v)
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off * 4, 0, 0);
 }
 // non-temporal store (aux bit 1 = nt on gfx940+): for the tensors a forward kernel only SAVES for the backward (nobody reads
 // them for several milliseconds: keeping their lines would evict what the next kernels do read)
-// Round 6, measured (profiles/r06_nt_saved_ab.log, interleaved in one job): configs[1] 2.819 -> 2.808 ms/step with the update
+// Measured (profiles/r06_nt_saved_ab.log, interleaved in one job): configs[1] 2.819 -> 2.808 ms/step with the update
 // forward's save-only stores non-temporal; inside a step these kernels run like after a 512 MB cache flush (update forward 37 us
-// on hot buffers, 50 in the step and behind a flush: profiles/r06_chain_thrash.log), i.e. their inputs come from HBM.
-#ifndef HN_NT_SAVED
-#define HN_NT_SAVED 1
-#endif
+// on hot buffers, 50 in the step and behind a flush: profiles/r06_chain_thrash.log), i.e. their inputs come from HBM.  (The
+// read-once side, non-temporal LOADS of the same tensors in the backward: same log, no gain, not kept.)
 __device__ __forceinline__ void bst4_nt(rsrc_t r, int off, f32x4 v) {
   HN_STORE_IF(v)
-  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off * 4, 0, HN_NT_SAVED ? 2 : 0);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off * 4, 0, 2);
 }
 
 // Coalesced store of one 32 x 32 accumulator block through a wave-private LDS transpose.  A lane owns a ROW of the
@@ -429,6 +436,9 @@ __device__ __forceinline__ void bst4_nt(rsrc_t r, int off, f32x4 v) {
 // in order, so no barrier or wait is needed between the two halves.  `off_block`: float offset of the block's first
 // row / first channel in the destination, LDG its row stride.
 constexpr int kScrLd = 36, kScrFloats = 32 * kScrLd;
+// Dynamic LDS of a kernel of node_chain.hip / node_chain_wide.hip that carves `ntiles` tiles of [TR][H + 4] floats (Cfg::LD,
+// WCfg::LD) and, behind them, the four waves' scratch
+constexpr size_t chain_lds_bytes(int ntiles, int TR, int H) { return (size_t)(ntiles * TR * (H + 4) + 4 * kScrFloats) * sizeof(float); }
 template <int LDG, bool NT = false>
 __device__ __forceinline__ void store_block(float* scr, int lane, const f32x4 (&v)[4], rsrc_t r, int off_block) {
   const int m = lane & 31, h = lane >> 5;
@@ -446,12 +456,10 @@ __device__ __forceinline__ void store_block(float* scr, int lane, const f32x4 (&
 // 4 x (8 rows x 128 contiguous bytes) into registers, `finish` (any time later) passes it through the scratch and
 // returns the four runs of this lane's row.
 struct BlockLoad { f32x4 v[4]; };
-template <int LDG, bool NT = false>
+template <int LDG>
 __device__ __forceinline__ void issue_block(BlockLoad& b, int lane, rsrc_t r, int off_block) {
 #pragma unroll
-  for (int it = 0; it < 4; ++it)
-    b.v[it] = NT ? bld4_nt(r, off_block + (it * 8 + (lane >> 3)) * LDG + (lane & 7) * 4)
-                 : bld4(r, off_block + (it * 8 + (lane >> 3)) * LDG + (lane & 7) * 4);
+  for (int it = 0; it < 4; ++it) b.v[it] = bld4(r, off_block + (it * 8 + (lane >> 3)) * LDG + (lane & 7) * 4);
 }
 __device__ __forceinline__ void finish_block(float* scr, int lane, const BlockLoad& b, f32x4 (&out)[4]) {
 #pragma unroll
@@ -544,26 +552,14 @@ __device__ __forceinline__ TileInfo find_tile(const int* __restrict__ type_rowpt
 }
 
 
-int tiles_of(const int* rp_host, int T, int N, int TR) {
-  int n = 0;
-  for (int t = 0; t < T; ++t) n += (rp_host[t + 1] - rp_host[t] + TR - 1) / TR;
-  return n + (N - rp_host[T] + TR - 1) / TR;
-}
-
-// Launch with `lds_bytes` of dynamic LDS (> 64 KB needs the opt-in, once per kernel).
-template <typename Args>
-int launch_chain(void (*kernel)(Args), dim3 grid, size_t lds_bytes, void* stream, const Args& args) {
-  static void (*done[8])(Args);
-  static int ndone = 0;
-  bool seen = false;
-  for (int i = 0; i < ndone; ++i) seen |= done[i] == kernel;
-  if (!seen) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds_bytes) != hipSuccess)
-      return HN_ERR_LDS;
-    if (ndone < 8) done[ndone++] = kernel;
-  }
-  hipLaunchKernelGGL(kernel, grid, dim3(256), lds_bytes, (hipStream_t)stream, args);
+// Launch KERNEL (256 threads) with `lds_bytes` of dynamic LDS, always the same for one kernel.  More than 64 KB needs an opt-in:
+// it runs once per kernel, when the function-local static of the kernel's instance of this template is initialised (thread-safe).
+template <auto KERNEL, typename... Args>
+int launch_chain(dim3 grid, size_t lds_bytes, void* stream, const Args&... args) {
+  static const bool opted_in = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) == hipSuccess;
+  if (!opted_in) return HN_ERR_LDS;
+  hipLaunchKernelGGL(KERNEL, grid, dim3(256), lds_bytes, (hipStream_t)stream, args...);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }
 
@@ -630,21 +626,8 @@ __device__ __forceinline__ void layernorm_bwd_row(const float* __restrict__ g, i
   }
 }
 
-// gx = LayerNorm'(x)^T (sum_p g[p]) + add : the backward of the LayerNorm in front of the T relations' projections
-__global__ __launch_bounds__(256) void layernorm_bwd_parts_kernel(const float* __restrict__ g, int nparts, long part_stride,
-                                                                  const float* __restrict__ x, const float* __restrict__ mean,
-                                                                  const float* __restrict__ rstd, const float* __restrict__ add,
-                                                                  float* __restrict__ gx, int rows, int H, int Hr,
-                                                                  const int* __restrict__ windows, int nwin, int wmode,
-                                                                  int TR) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  if (!tile_selected(windows, nwin, wmode, r / TR * TR, TR)) return;     // the rows of the pre kernel's tiles
-  layernorm_bwd_row(g, nparts, part_stride, x, mean[r], rstd[r], add, 1.f, gx, (size_t)r, H, Hr, threadIdx.x & 63);
-}
-
 // The prologue of the update backward when its incoming gradients are still `pending` (UpdBwdArgs::pend): what
-// message_bwd_finish_kernel and layernorm_bwd_parts_kernel would have written for the rows [row0, row0 + nrows) of this
+// message_bwd_finish_kernel and layernorm_bwd_parts_kernel (node_chain.hip) would have written for the rows [row0, row0 + nrows) of this
 // workgroup's tile, in the same order of operations (bit-identical), into gxo / gvo; the barrier at the end makes the rows
 // visible to the whole workgroup, which then reads them like any other input.  Rows >= identity_rows (atoms of an unknown
 // element) have no residual term.

@@ -1,12 +1,13 @@
 // gfx950: the four node chain kernels (node_chain.hip) for EVERY hidden width that is a multiple of 64 up to 512 -- the
-// reference's default is hidden_channels = 512 (/root/reference/HermNet/hermnet.py:84-88), its examples use it.
+// reference's default is hidden_channels = 512 (hermnet.py:84-88), its examples use it.
 //
 //   node_pre_fwd     x -> LayerNorm -> [H -> H] -> ScaledSiLU -> [H -> 3H]  = xh[t]        rmnet.py:52
 //   node_pre_bwd     gxh[t] -> [3H -> H] -> * ScaledSiLU' -> [H -> H]       = gn[t]
 //   node_update_fwd  (x1, vec1) -> vec_proj, vec_dot, |v2|, xvec_proj MLP, dx / dvec, residual   rmnet.py:94-107, 29-31
 //   node_update_bwd  (gx_out, gvec_out) -> (gx1, gvec1)
 //
-// Same data flow as node_chain.hip (weights streamed from L2 in MFMA fragment order, activations in LDS tiles, transposed
+// Same data flow as node_chain.hip (weights streamed from L2 as bf16 planes in v_mfma_f32_32x32x16_bf16 operand order --
+// frag(W), a step of one plane per load --, fp32 activations in LDS tiles split into planes by the consuming wave, transposed
 // 32 x 32 accumulators, coalesced epilogue I/O through wave-private LDS transposes); what differs is how a 256-thread
 // workgroup covers a wide row:
 //   * a tile is 32 rows; wave w owns the 32-channel blocks {w, w + 4, w + 8, ...} (NP = ceil(H / 128) of them; the last
@@ -18,16 +19,14 @@
 //   * nothing is carried in registers between products except NP accumulator blocks (|v2|^2, s, g|v2| / |v2|): v1, v2,
 //     vec_dot, x1 ... are re-read (L2-hot, coalesced) where the narrow kernels keep them -- at these widths a product is
 //     tens of thousands of cycles, a block load a few hundred.
-// LDS: one or two [32][H + 4] tiles + 18 KB of transpose scratch: 150 KB at H = 512 (one workgroup per CU).
+// LDS: one or two [32][H + 4] tiles + 18 KB of transpose scratch (chain_lds_bytes): 150 KB at H = 512 (one workgroup per CU).
 #include <type_traits>
 #include "node_chain_common.h"
 
 // ring slots of the wide family's products: one workgroup per CU, so a wave has nobody to hide a late weight fragment behind --
-// five steps ahead (the 32/64-row kernels of node_chain.hip, two or more workgroups per CU, take two: node_chain_common.h)
-#ifndef HN_RS_WIDE
-#define HN_RS_WIDE 6
-#endif
-constexpr int kRSW = HN_RS_WIDE;
+// five steps ahead (the 32/64-row kernels of node_chain.hip, two or more workgroups per CU, take two: kRS of node_chain_common.h;
+// measured: profiles/r04_chain_variants.log)
+constexpr int kRSW = 6;
 
 namespace {
 
@@ -63,6 +62,8 @@ __device__ __forceinline__ void mma_all(f32x16 (&acc)[1][NP], const float* As, c
 }
 
 // =====================================================================================================================
+constexpr size_t pre_fwd_wide_lds_bytes(int H) { return chain_lds_bytes(1, 32, H); }      // one [32][LD] tile, then the scratch
+
 template <int H>
 __global__ __launch_bounds__(256, 1) void node_pre_fwd_wide_kernel(PreFwdArgs a) {
   using C = WCfg<H>;
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(256, 1) void node_pre_fwd_wide_kernel(PreFwdArgs a)
 #pragma unroll
     for (int m = 1; m < TPR; m <<= 1) s += __shfl_xor(s, m, 64);
     float mu = s / (float)a.Hr;
-    // corrected two-pass statistics (round 6): a lane sums NF * 4 values in sequence, so on a row whose mean dwarfs its spread
+    // corrected two-pass statistics: a lane sums NF * 4 values in sequence, so on a row whose mean dwarfs its spread
     // (1e3 under unit noise) `mu` carries an error of ~1e-4 of the spread -- 20 x what torch's pairwise sum leaves
     // (tests/test_gpu_parity.py::test_node_chain_kernels_on_adversarial_operands).  The mean of the DEVIATIONS is that error,
     // measured at the deviations' own scale: it is taken out of the deviations, the mean and the variance.
@@ -143,7 +144,7 @@ __global__ __launch_bounds__(256, 1) void node_pre_fwd_wide_kernel(PreFwdArgs a)
   const float* As = tile + mrow * LD + ch;
   f32x16 acc1[1][NP];
   zero_acc(acc1);
-  mma_all<H, LD, NP, false, HN_PIN_PRE>(acc1, As, bp1, r1);
+  mma_all<H, LD, NP, false, kPinPre>(acc1, As, bp1, r1);
   __syncthreads();                                   // every wave has read n
   // ---- + b1, save, ScaledSiLU -> the tile becomes the A operand of the second product
 #pragma unroll
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void node_pre_fwd_wide_kernel(PreFwdArgs a)
       b_preload(r2, bp2);
       f32x16 acc2[1][3];
       zero_acc(acc2);
-      mma_panel<H, LD, 1, 3, kRSW, false, HN_PIN_PRE>(acc2, As, bp2, r2);
+      mma_panel<H, LD, 1, 3, kRSW, false, kPinPre>(acc2, As, bp2, r2);
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
         const int cblk = p * H + B.cb[j] * 32;
@@ -184,9 +185,10 @@ __global__ __launch_bounds__(256, 1) void node_pre_fwd_wide_kernel(PreFwdArgs a)
 
 // =====================================================================================================================
 constexpr int pre_bwd_wide_kc(int H) { return H % 128 == 0 ? 128 : 64; }
-constexpr int pre_bwd_wide_lds_floats(int H) {
+// two [32][KC + 4] chunk buffers, later the gh tile [32][LD] in the same space (BODY below), then the scratch
+constexpr size_t pre_bwd_wide_lds_bytes(int H) {
   const int chunks = 2 * 32 * (pre_bwd_wide_kc(H) + 4), tile = 32 * (H + 4);
-  return (chunks > tile ? chunks : tile) + 4 * kScrFloats;
+  return (size_t)((chunks > tile ? chunks : tile) + 4 * kScrFloats) * sizeof(float);
 }
 
 template <int H>
@@ -272,6 +274,8 @@ __global__ __launch_bounds__(256, 1) void node_pre_bwd_wide_kernel(PreBwdArgs a)
 }
 
 // =====================================================================================================================
+constexpr size_t update_wide_lds_bytes(int H) { return chain_lds_bytes(2, 32, H); }       // both update kernels: two [32][LD] tiles, then the scratch
+
 template <int H>
 __global__ __launch_bounds__(256, 1) void node_update_fwd_wide_kernel(UpdFwdArgs a) {
   using C = WCfg<H>;
@@ -648,53 +652,38 @@ __global__ __launch_bounds__(256, 1) void node_update_bwd_wide_kernel(UpdBwdArgs
   }
 }
 
-#define HN_WIDE_SWITCH(CALL)          \
-  switch (hidden) {                   \
-    case 128: CALL(128); break;       \
-    case 192: CALL(192); break;       \
-    case 256: CALL(256); break;       \
-    case 320: CALL(320); break;       \
-    case 384: CALL(384); break;       \
-    case 448: CALL(448); break;       \
-    case 512: CALL(512); break;       \
-    default: return HN_ERR_BAD_ARG;   \
+// The width dispatch of this unit: KERNEL's instance at `hidden`, with LDS(width) bytes of dynamic LDS.
+#define HN_WIDE_LAUNCH(KERNEL, LDS)                                                               \
+  switch (hidden) {                                                                               \
+    case 128: return launch_chain<KERNEL<128>>(grid, LDS(128), stream, a);                        \
+    case 192: return launch_chain<KERNEL<192>>(grid, LDS(192), stream, a);                        \
+    case 256: return launch_chain<KERNEL<256>>(grid, LDS(256), stream, a);                        \
+    case 320: return launch_chain<KERNEL<320>>(grid, LDS(320), stream, a);                        \
+    case 384: return launch_chain<KERNEL<384>>(grid, LDS(384), stream, a);                        \
+    case 448: return launch_chain<KERNEL<448>>(grid, LDS(448), stream, a);                        \
+    case 512: return launch_chain<KERNEL<512>>(grid, LDS(512), stream, a);                        \
+    default: return HN_ERR_BAD_ARG;                                                               \
   }
 
 }  // namespace
 
-// Entry points of this translation unit (called by the extern "C" functions of node_chain.hip)
+// Entry points of this translation unit (node_chain_common.h declares them; called by the extern "C" functions of node_chain.hip)
 int hn_wide_pre_fwd(int hidden, const PreFwdArgs& a, void* stream) {
   const dim3 grid((unsigned)((a.Ns + 31) / 32), (unsigned)a.T);
-  int rc = HN_ERR_BAD_ARG;
-#define HN_CALL(HH) rc = launch_chain(node_pre_fwd_wide_kernel<HH>, grid, (size_t)(32 * (HH + 4) + 4 * kScrFloats) * 4, stream, a)
-  HN_WIDE_SWITCH(HN_CALL)
-#undef HN_CALL
-  return rc;
+  HN_WIDE_LAUNCH(node_pre_fwd_wide_kernel, pre_fwd_wide_lds_bytes)
 }
 
 int hn_wide_pre_bwd(int hidden, const PreBwdArgs& a, void* stream) {
   const dim3 grid((unsigned)((a.Ns + 31) / 32), (unsigned)a.T);
-  int rc = HN_ERR_BAD_ARG;
-#define HN_CALL(HH) rc = launch_chain(node_pre_bwd_wide_kernel<HH>, grid, (size_t)pre_bwd_wide_lds_floats(HH) * 4, stream, a)
-  HN_WIDE_SWITCH(HN_CALL)
-#undef HN_CALL
-  return rc;
+  HN_WIDE_LAUNCH(node_pre_bwd_wide_kernel, pre_bwd_wide_lds_bytes)
 }
 
 int hn_wide_update_fwd(int hidden, const UpdFwdArgs& a, int tiles, void* stream) {
   const dim3 grid((unsigned)tiles);
-  int rc = HN_ERR_BAD_ARG;
-#define HN_CALL(HH) rc = launch_chain(node_update_fwd_wide_kernel<HH>, grid, (size_t)(2 * 32 * (HH + 4) + 4 * kScrFloats) * 4, stream, a)
-  HN_WIDE_SWITCH(HN_CALL)
-#undef HN_CALL
-  return rc;
+  HN_WIDE_LAUNCH(node_update_fwd_wide_kernel, update_wide_lds_bytes)
 }
 
 int hn_wide_update_bwd(int hidden, const UpdBwdArgs& a, int tiles, void* stream) {
   const dim3 grid((unsigned)tiles);
-  int rc = HN_ERR_BAD_ARG;
-#define HN_CALL(HH) rc = launch_chain(node_update_bwd_wide_kernel<HH>, grid, (size_t)(2 * 32 * (HH + 4) + 4 * kScrFloats) * 4, stream, a)
-  HN_WIDE_SWITCH(HN_CALL)
-#undef HN_CALL
-  return rc;
+  HN_WIDE_LAUNCH(node_update_bwd_wide_kernel, update_wide_lds_bytes)
 }

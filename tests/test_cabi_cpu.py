@@ -359,6 +359,130 @@ def test_default_message_kernels_fit_their_register_budget(tmp_path):
             assert get("sgpr_spill_count") == 0 and get("private_segment_fixed_size") == 0, name
 
 
+# The node chain kernels as hipcc compiled them for gfx950 before the knobs of their experiments were taken out of the sources:
+# (registers, VGPR spills, SGPR spills, scratch bytes) per kernel, by template arguments (b0 / b1: bool).  The same commit compiled
+# layernorm_bwd_parts_kernel into all three units, out of the shared header; only node_chain.hip launches it and now holds it.
+CHAIN_KERNEL_BUDGETS = {
+    "node_chain.hip": {
+        "node_pre_bwd_kernel128,64": (206, 0, 0, 0),
+        "node_pre_bwd_kernel256,32": (172, 0, 0, 0),
+        "node_pre_bwd_kernel64,64": (118, 0, 0, 0),
+        "node_pre_fwd_kernel128,64": (174, 0, 0, 0),
+        "node_pre_fwd_kernel256,32": (204, 0, 0, 0),
+        "node_pre_fwd_kernel64,64": (114, 0, 0, 0),
+        "node_update_bwd_kernel128,32,2": (246, 0, 0, 0),
+        "node_update_bwd_kernel128,64,1": (450, 0, 20, 0),
+        "node_update_bwd_kernel256,32,1": (456, 0, 14, 0),
+        "node_update_bwd_kernel64,64,2": (246, 0, 0, 0),
+        "node_update_fwd_kernel128,32,2": (249, 0, 0, 0),
+        "node_update_fwd_kernel128,64,1": (506, 0, 0, 0),
+        "node_update_fwd_kernel256,32,1": (512, 28, 0, 116),
+        "node_update_fwd_kernel64,64,2": (249, 0, 0, 0),
+        "layernorm_bwd_parts_kernel": (56, 0, 0, 0),
+    },
+    "node_chain16.hip": {
+        "node_pre_bwd16_kernel128": (164, 0, 0, 0),
+        "node_pre_fwd16_kernel128": (212, 0, 0, 0),
+        "energy_head16_bwd_kernel128,64": (84, 0, 0, 0),
+        "energy_head16_fwd_kernel128,64": (76, 0, 0, 0),
+        "node_update_bwd16_kernel128,b0,b0": (168, 1, 0, 8),
+        "node_update_bwd16_kernel128,b0,b1": (166, 0, 0, 0),
+        "node_update_bwd16_kernel128,b1,b0": (168, 6, 0, 20),
+        "node_update_fwd16_kernel128,b0,b0": (200, 0, 0, 0),
+        "node_update_fwd16_kernel128,b0,b1": (196, 0, 0, 0),
+        "node_update_fwd16_kernel128,b1,b0": (215, 0, 1, 0),
+    },
+    "node_chain_wide.hip": {
+        "node_pre_bwd_wide_kernel128": (136, 0, 0, 0),
+        "node_pre_bwd_wide_kernel192": (176, 0, 0, 0),
+        "node_pre_bwd_wide_kernel256": (180, 0, 0, 0),
+        "node_pre_bwd_wide_kernel320": (244, 0, 0, 0),
+        "node_pre_bwd_wide_kernel384": (240, 0, 0, 0),
+        "node_pre_bwd_wide_kernel448": (296, 0, 0, 0),
+        "node_pre_bwd_wide_kernel512": (288, 0, 0, 0),
+        "node_pre_fwd_wide_kernel128": (192, 0, 0, 0),
+        "node_pre_fwd_wide_kernel192": (200, 0, 0, 0),
+        "node_pre_fwd_wide_kernel256": (200, 0, 3, 0),
+        "node_pre_fwd_wide_kernel320": (208, 0, 24, 0),
+        "node_pre_fwd_wide_kernel384": (204, 0, 45, 0),
+        "node_pre_fwd_wide_kernel448": (308, 0, 93, 0),
+        "node_pre_fwd_wide_kernel512": (324, 0, 113, 0),
+        "node_update_bwd_wide_kernel128": (232, 0, 0, 0),
+        "node_update_bwd_wide_kernel192": (307, 0, 11, 0),
+        "node_update_bwd_wide_kernel256": (304, 0, 15, 0),
+        "node_update_bwd_wide_kernel320": (407, 0, 44, 0),
+        "node_update_bwd_wide_kernel384": (407, 0, 56, 0),
+        "node_update_bwd_wide_kernel448": (504, 0, 68, 0),
+        "node_update_bwd_wide_kernel512": (492, 0, 74, 0),
+        "node_update_fwd_wide_kernel128": (348, 0, 0, 0),
+        "node_update_fwd_wide_kernel192": (371, 0, 0, 0),
+        "node_update_fwd_wide_kernel256": (370, 0, 0, 0),
+        "node_update_fwd_wide_kernel320": (371, 0, 0, 0),
+        "node_update_fwd_wide_kernel384": (386, 0, 0, 0),
+        "node_update_fwd_wide_kernel448": (442, 0, 0, 0),
+        "node_update_fwd_wide_kernel512": (396, 0, 0, 0),
+    },
+}
+
+
+def _chain_kernel_key(mangled):
+    """`node_update_fwd16_kernel128,b0,b1` for `_ZN12_GLOBAL__N_124node_update_fwd16_kernelILi128ELb0ELb1EEEvN8hn_chain...`"""
+    name, targs = re.match(r"_ZN12_GLOBAL__N_1\d+(\w+?_kernel)(?:I((?:L[ib]\d+E)+)E)?", mangled).groups()
+    return name + ",".join(("b" if kind == "b" else "") + value for kind, value in re.findall(r"L([ib])(\d+)", targs or ""))
+
+
+def test_node_chain_kernels_keep_their_register_budgets(tmp_path):
+    """Per chain kernel, as hipcc compiles the three units for gfx950 (no GPU): no more spilled registers and no more scratch
+    than CHAIN_KERNEL_BUDGETS records, and no fewer waves per SIMD than its registers allowed there (512 registers per lane and
+    SIMD, allocated in eights, at most 8 waves).  The kernels are exactly the recorded ones: 53, none compiled twice."""
+    import shutil
+    import subprocess
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("hipcc not found")
+    waves = lambda regs: min(8, 512 // (-(-regs // 8) * 8))
+    jobs = {unit: subprocess.Popen([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-S", "--cuda-device-only",
+                                    os.path.join(ROOT, "hermnet_amd", "csrc", unit), "-o", str(tmp_path / (unit + ".s"))],
+                                   stdout=subprocess.DEVNULL, stderr=subprocess.PIPE) for unit in CHAIN_KERNEL_BUDGETS}
+    for unit, job in jobs.items():
+        _, err = job.communicate(timeout=900)
+        assert job.returncode == 0, (unit, err.decode()[-2000:])
+    assert sum(len(t) for t in CHAIN_KERNEL_BUDGETS.values()) == 53
+    for unit, table in CHAIN_KERNEL_BUDGETS.items():
+        text = open(str(tmp_path / (unit + ".s"))).read()
+        found = {_chain_kernel_key(name): meta for name, meta in
+                 re.findall(r"^    \.name:\s+(\S+)\n(.*?)\.wavefront_size", text, flags=re.S | re.M)}
+        assert sorted(found) == sorted(table), (unit, sorted(set(found) ^ set(table)))
+        for key, (regs, vspill, sspill, scratch) in table.items():
+            get = lambda field: int(re.search(r"\.%s:\s+(\d+)" % field, found[key]).group(1))
+            print(unit, key, get("vgpr_count"), get("vgpr_spill_count"), get("sgpr_spill_count"), get("private_segment_fixed_size"))
+            assert get("vgpr_spill_count") <= vspill and get("sgpr_spill_count") <= sspill, (unit, key)
+            assert get("private_segment_fixed_size") <= scratch, (unit, key, get("private_segment_fixed_size"))
+            assert waves(get("vgpr_count")) >= waves(regs), (unit, key, get("vgpr_count"), regs)
+
+
+def test_node_chain_entry_points_refuse_and_choose_as_recorded():
+    """tests/golden/chain_dispatch.json (gen_chain_dispatch.py, recorded before the chain kernels' host dispatch was rearranged):
+    every refusal in front of a launch, the supported widths and the tile heights, entry for entry.  `table` asserts by itself
+    that no call with rows came back as anything but HN_ERR_BAD_ARG, i.e. that none reached a launch."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("gen_chain_dispatch", os.path.join(ROOT, "tests", "golden", "gen_chain_dispatch.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(ROOT, "tests", "golden", "chain_dispatch.json")) as fh:
+        want = json.load(fh)
+    got = json.loads(json.dumps(gen.table(_lib.load())))
+    assert sorted(got["entry_points"]) == sorted(want["entry_points"]) and len(want["entry_points"]) == 11
+    for name, widths in want["entry_points"].items():
+        assert sorted(widths) == sorted(str(h) for h in gen.WIDTHS), name
+        for h, cases in widths.items():
+            assert got["entry_points"][name][h] == cases, (name, h, {k: (v, got["entry_points"][name][h].get(k))
+                                                                     for k, v in cases.items() if got["entry_points"][name][h].get(k) != v})
+    assert got["supported"] == want["supported"]
+    assert got["update_tile_rows"] == want["update_tile_rows"]
+    assert len(want["update_tile_rows"]) == 6 and want["update_tile_rows"]["update_tile16=2,node_chain_wide=0"]["configs[1]"]["128"] == 16
+
+
 def test_argument_checks_of_the_round_4_entry_points_need_no_gpu():
     """The entry points added with ABI v8 refuse malformed calls before anything is launched (and treat empty inputs as
     done), so their argument contracts can be checked here: hermnet_train_node_op (operand counts per op), the *_rows edge

@@ -1,18 +1,11 @@
 #!/bin/bash
-# Diagnostic / experiment builds of the node chain kernels:
-#   bash tools/build_chain_variant.sh rs8 -DHN_RS_SMALL=8   ->  hermnet_amd/csrc/variants/libhermnet_rs8.so
-# then:  HERMNET_LIB_PATH=hermnet_amd/csrc/variants/libhermnet_rs8.so python tools/chain_bench.py
+# Diagnostic builds of the node chain kernels -- the knobs their sources keep are HN_STAMPS (tools/chain_stamps.py,
+# tools/fused_stamps.py), HN_KO_LOADS, HN_KO_STORES and HN_KO_BSTREAM=1|2 (results wrong, time meaningful):
+#   bash tools/build_chain_variant.sh kob1 -DHN_KO_BSTREAM=1   ->  hermnet_amd/csrc/variants/libhermnet_kob1.so
+# then:  HERMNET_LIB_PATH=hermnet_amd/csrc/variants/libhermnet_kob1.so python tools/chain_bench.py
+# The three chain units are compiled with the flags; every other object is the product library's (csrc/Makefile: variant).
 set -e
-cd "$(dirname "$0")/../hermnet_amd/csrc"
 NAME=$1; shift
-mkdir -p variants
-F="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function"
-/opt/rocm/bin/hipcc $F "$@" -c node_chain.hip -o variants/node_chain_$NAME.o &
-/opt/rocm/bin/hipcc $F "$@" -c node_chain_wide.hip -o variants/node_chain_wide_$NAME.o &
-/opt/rocm/bin/hipcc $F "$@" -c node_chain16.hip -o variants/node_chain16_$NAME.o &
-wait
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 message_kernels.o message_bwd_cl.o geometry_kernels.o node_kernels.o \
-  variants/node_chain_$NAME.o variants/node_chain_wide_$NAME.o variants/node_chain16_$NAME.o relation_kernels.o neighbor_kernels.o train_kernels.o train_node_kernels.o stream_kernels.o host_api.o \
-  -o variants/libhermnet_$NAME.so
-rm -f variants/node_chain_$NAME.o variants/node_chain_wide_$NAME.o variants/node_chain16_$NAME.o
+make -s -C "$(dirname "$0")/../hermnet_amd/csrc" -j4 variant NAME="$NAME" VARIANT_FLAGS="$*" \
+  VARIANT_SRCS="node_chain.hip node_chain_wide.hip node_chain16.hip"
 echo built variants/libhermnet_$NAME.so
