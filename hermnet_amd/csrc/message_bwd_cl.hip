@@ -278,8 +278,8 @@ struct EdgeIn {          // what one edge needs from memory (vector part)
 //
 // NEED_GXH = false (layer 0 of an energy / force evaluation, HAS_VEC = false only): x of the first layer is the species
 // embedding, which does not depend on the positions, so nothing below wants the source rows' gradients -- no gs / gb sums,
-// an empty row epilogue, no gxh array (a.gxh may be null).  What gedge depends on is instruction for instruction the
-// general form's: the same bits.
+// an empty row epilogue, no gxh array (a.gxh may be null), and of part s only the derivative sum (a scalar FMA per tap: the
+// value half fed gs alone).  What gedge depends on is operation for operation the general form's: the same bits.
 template <bool HAS_VEC, bool WIN, bool NEED_GXH>
 __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a) {
   static_assert(NEED_GXH || !HAS_VEC, "rows with a vec part always hand gradients down");
@@ -513,12 +513,16 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
         const EdgeIn& cur = (j & 1) ? in1 : in0;
         float (&tl)[5] = (j & 1) ? tl1 : tl0;
         // ---- (S0, S1) of the three parts: 12 taps, one LDS read each, requested during the previous edge
+        // (NEED_GXH = false: the value half of part s fed gs only -- its derivative half alone, as a scalar sum `sy`: the
+        // .y lane of the packed FMA, tap for tap, so the bits stay; a v_pk_fma_f32 takes ~1.7 issue slots, a v_fma_f32 one)
         hn_f2 Ss = {0.f, 0.f}, Sa = {0.f, 0.f}, Sb = {0.f, 0.f};
+        float sy = 0.f;
         auto taps4 = [&](int m0, const hn_f4 (&w)[4]) {
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const hn_f2 g = {rec[2 * (m0 + q)], rec[2 * (m0 + q) + 1]};
-            Ss = __builtin_elementwise_fma(g, hn_f2{w[q].x, w[q].x}, Ss);
+            if constexpr (NEED_GXH) Ss = __builtin_elementwise_fma(g, hn_f2{w[q].x, w[q].x}, Ss);
+            else sy = __builtin_fmaf(g.y, w[q].x, sy);
             if (HAS_VEC) Sa = __builtin_elementwise_fma(g, hn_f2{w[q].y, w[q].y}, Sa);
             Sb = __builtin_elementwise_fma(g, hn_f2{w[q].z, w[q].z}, Sb);
           }
@@ -528,6 +532,7 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
         // diagnostic build (results wrong, time meaningful): the twelve-tap contraction replaced by three moves -- the weight
         // rows are still read and waited for, every other instruction of the edge is in place
         Ss = hn_f2{rec[0] * wA[0].x, rec[1]}; Sa = hn_f2{rec[2] * wB[0].y, rec[3]}; Sb = hn_f2{rec[4] * wC[0].z, rec[5]};
+        sy = Ss.y;
 #else
         taps4(0, wA);
         taps4(4, wB);
@@ -547,7 +552,8 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
         // the taps are consumed: request the NEXT edge's record (taps into the same scalar registers, tail into the other
         // set) and its weight rows into the same vector registers; their latency hides behind the rest of this edge
         __builtin_amdgcn_sched_barrier(0);
-        asm volatile("" : "+v"(Ss), "+v"(Sa), "+v"(Sb));      // (every tap of this edge has been issued)
+        if constexpr (NEED_GXH) asm volatile("" : "+v"(Ss), "+v"(Sa), "+v"(Sb));      // (every tap of this edge has been issued)
+        else asm volatile("" : "+v"(sy), "+v"(Sb));
         rp += kRec;
         if (j & 1) load_record(tl0); else load_record(tl1);
         issue_weights(waddr_next);
@@ -557,7 +563,7 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
         // diagnostic build: the channel algebra replaced by the fewest operations that keep the contraction's results and the
         // gathered rows alive (results wrong): what the contraction, the loads and the reduction cost without it
         {
-          gs += Ss.x + Ss.y + cur.gx1; ga += Sa.x + Sa.y + cur.g0; gb += Sb.x + Sb.y + cur.g1 + cur.g2;
+          gs += Ss.x + Ss.y + sy + cur.gx1; ga += Sa.x + Sa.y + cur.g0; gb += Sb.x + Sb.y + cur.g1 + cur.g2;
           px[j & 1] = gs; py[j & 1] = ga; pz[j & 1] = gb;
           return;
         }
@@ -567,9 +573,8 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
         const float g1 = WIN ? cur.g1 * own : cur.g1, g2 = WIN ? cur.g2 * own : cur.g2;
         // (the .x sums are rbfh - bias, the .y sums d rbfh / d d: see the record layout)
         // ---- part s: dx = sum xs * rs
-        const float rs = Ss.x + bs;
-        if (NEED_GXH) gs = fmaf(gx1, rs, gs);
-        float pdv = gx1 * xs * Ss.y;
+        if constexpr (NEED_GXH) gs = fmaf(gx1, Ss.x + bs, gs);
+        float pdv = gx1 * xs * (NEED_GXH ? Ss.y : sy);
         // ---- part a: dvec += vec_j * (xa * ra) / sqrt(3H)
         if (HAS_VEC) {
           const float ra_ = Sa.x + ba;

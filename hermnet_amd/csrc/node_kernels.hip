@@ -579,6 +579,32 @@ __global__ __launch_bounds__(256) void pair_mean_kernel(const float* __restrict_
   }
 }
 
+// ---- layer 0 of an energy / force evaluation: x is the species embedding, so a row's node projection depends on its species only.
+// xh[t][r][:] = table[t][z_rows[r]][:]  (table [T, V, W]: hermnet_node_pre_fwd of the V embedding rows, made once per weight
+// refresh; W = 3H floats).  blockIdx.y = relation; one float4 per thread, consecutive threads consecutive float4 of xh[t]: whole
+// rows leave as coalesced lines; the table (T V W floats, 1.5 KB per species and relation at H = 128) stays in L2.  Every row is
+// written, pad rows (Z = 0) and rows of atoms of an unknown element like any other; a species outside [0, V) -- the embedding
+// gather in front has refused it -- is clamped, so that no read leaves the table.
+// I: the index type within a relation's slice (unsigned where rows * W / 4 < 2^32: a 64-bit division per thread costs more than
+// the copy).
+// Plain stores: xh is read by the message kernel right behind; non-temporal ones measured the same step time
+// (profiles/layer0_species_ab.md).
+template <typename I>
+__global__ __launch_bounds__(256) void species_expand_kernel(const float* __restrict__ table, const long* __restrict__ z_rows,
+                                                             float* __restrict__ xh, long rows, int V, int q4) {
+  const I n = (I)rows * (I)q4;                           // float4 of one relation's slice
+  const I j = (I)blockIdx.x * 256u + threadIdx.x;
+  if (j >= n) return;
+  const I r = j / (I)q4;
+  const int c = (int)(j - r * (I)q4);
+  const long t = blockIdx.y;
+  long z = z_rows[r];
+  z = z < 0 ? 0 : (z >= V ? V - 1 : z);
+  const float4 v = reinterpret_cast<const float4*>(table)[(t * V + z) * q4 + c];
+  float4* dst = reinterpret_cast<float4*>(xh) + ((size_t)t * (size_t)rows * (size_t)q4 + (size_t)j);
+  *dst = v;
+}
+
 inline dim3 grid_for(long n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
 #define HN_LAUNCH_END return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH
 
@@ -751,6 +777,25 @@ extern "C" int hermnet_energy_head_fused_bwd(const float* ge, const float* h, co
   if (hidden == 64) return go(energy_head_fused_kernel<false, 1>);
   if (hidden == 128) return go(energy_head_fused_kernel<false, 2>);
   return go(energy_head_fused_kernel<false, 4>);
+}
+
+extern "C" int hermnet_species_expand(const float* table, const long* z_rows, float* xh, int num_rows, int num_rel,
+                                      int num_species, int width, void* stream) {
+  if (num_rows < 0 || num_rel <= 0 || num_species <= 0 || width <= 0 || (width & 3)) return HN_ERR_BAD_ARG;
+  if (num_rows == 0) return HN_OK;
+  if (!table || !z_rows || !xh) return HN_ERR_BAD_ARG;
+  // (arrays of 4 GiB and more are handled: 64-bit addresses in the kernel, and 64-bit indices where a relation's slice needs them)
+  const long per_rel = (long)num_rows * (width / 4);
+  const long blocks = (per_rel + 255) / 256;
+  if (blocks > 0x7fffffffL || num_rel > 65535) return HN_ERR_BAD_ARG;
+  const dim3 grid((unsigned)blocks, (unsigned)num_rel);
+  if (per_rel < (1L << 32) - 256)
+    hipLaunchKernelGGL(species_expand_kernel<unsigned>, grid, dim3(256), 0, (hipStream_t)stream, table, z_rows, xh,
+                       (long)num_rows, num_species, width / 4);
+  else
+    hipLaunchKernelGGL(species_expand_kernel<unsigned long>, grid, dim3(256), 0, (hipStream_t)stream, table, z_rows, xh,
+                       (long)num_rows, num_species, width / 4);
+  HN_LAUNCH_END;
 }
 
 extern "C" int hermnet_pair_mean(int mode, const float* x_in, const float* vec_in, float* x_out, float* vec_out,

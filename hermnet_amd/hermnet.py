@@ -11,7 +11,7 @@ from .ops import EdgeGeometry, TrueEdgeGradient, edge_radial_tables
 from .relations import AtomSet, RelationalGraph
 from .sharding import HaloExchange, HaloExchangeFeatures, HaloGradReturn, SumAcrossRanks
 from .layer import (EdgeFanout, EdgeGradSink, EnergyHead, FusedRelationalLayer, GemmRelationalLayer, HeadWeights, LayerWeights,
-                    Route, StepState)
+                    Route, SpeciesTable, StepState)
 from .rmnet import PaiNNModule, RadialBasis, ScaledSiLU, relational_layer
 from .trainops import EdgeDiff, EdgeUnit, embedding_rows, tall_linear
 
@@ -61,7 +61,10 @@ class HeteroVertexConv(nn.Module):
                 raise RuntimeError("the in-layer halo exchange belongs to the chain path")
             data.x, data.vec = GemmRelationalLayer.apply(data.x, data.vec, edge, g, step.rbf, w, step)
             return data
-        route = _chain_route(data, step, node, halo)
+        # (a hook on the layer, or HTNet's layer, is somebody who may read or replace what the layer works on: the general form)
+        plain = (type(self) is HeteroVertexConv and not self._forward_hooks and not self._forward_pre_hooks
+                 and not torch.nn.modules.module._global_forward_hooks and not torch.nn.modules.module._global_forward_pre_hooks)
+        route = _chain_route(data, step, node, halo, plain)
         data.x, data.vec = FusedRelationalLayer.apply(data.x, data.vec, edge, g, step.rbf, w, step, route)
         step.chain_node = None if g.num_src else data.x.grad_fn
         return data
@@ -78,8 +81,9 @@ def _exchange_first(halo, w, g, x):
                 and switches.halo_overlap() != "0")
 
 
-def _chain_route(data, step, node, halo):
-    """The `layer.Route` of chain layer `step.layer`; `node`: the autograd node the chain layer below left, `halo`: still due."""
+def _chain_route(data, step, node, halo, plain=False):
+    """The `layer.Route` of chain layer `step.layer`; `node`: the autograd node the chain layer below left, `halo`: still due;
+    `plain`: HVNet's own layer without hooks."""
     g, li, ready = step.graph, step.layer, step.weights
     # (x, vec) straight from the chain layer below -- both still carry THAT autograd node (an in-place exchange of halo
     # rows or any other op in between replaces it) -- and this layer is their only reader: its backward may hand its
@@ -100,7 +104,13 @@ def _chain_route(data, step, node, halo):
     w_next = ready[li + 1] if (ready is not None and li + 1 < len(ready) and step.whole) else None
     # (HVNet._run_layers: this is the last layer and the read-out takes its x only)
     last = step.last and not g.num_src and w_next is None
-    return Route(defer=straight and step.whole, pre=None if pre is None else pre[1], w_next=w_next, last=last)
+    # the first layer of an evaluation, whose x is still the very embedding gather `_prepare` made: its node projection comes
+    # from the model's per-species table (layer.SpeciesTable)
+    species = None
+    if (li == 0 and plain and step.species is not None and data.x is step.species[1] and data.vec is None and step.whole
+            and not step.train and not g.num_src and switches.species_table):
+        species = (step.species[0], g.z_rows)
+    return Route(defer=straight and step.whole, pre=None if pre is None else pre[1], w_next=w_next, last=last, species=species)
 
 
 class GraphEnergies(torch.autograd.Function):
@@ -189,7 +199,8 @@ class HVNet(nn.Module):
         `eval()` transitions; call it after writing parameters through `.data` (a write the caches' keys cannot see --
         the device-side guard would otherwise answer the next step with NaN and repair on the one after)."""
         self.__dict__["_cache_epoch"] = self.__dict__.get("_cache_epoch", 0) + 1    # (captured steps compare it: graph.py)
-        for w in [getattr(conv, "_weights", None) for conv in self.hermconvs] + [self.__dict__.get("_head")]:
+        for w in [getattr(conv, "_weights", None) for conv in self.hermconvs] + [self.__dict__.get("_head"),
+                                                                                 self.__dict__.get("_species")]:
             if w is not None:
                 w.key = None
         g = self.__dict__.get("_guard")
@@ -229,16 +240,24 @@ class HVNet(nn.Module):
                 if self.__dict__.get("_head") is None:
                     self.__dict__["_head"] = HeadWeights(self.out_energy)
                 hw = self._head.refresh()
+            # layer 0's projection of every species (layer.SpeciesTable), where its chain kernels run: eval() on the device
+            sp = None
+            if ws and dev.type == "cuda" and not self.training and ws[0].chain and switches.node_chain:
+                if self.__dict__.get("_species") is None:
+                    self.__dict__["_species"] = SpeciesTable(self.embed)
+                sp = self._species.refresh(ws[0])
             if not guard_on or not ws:
                 return ws, hw
             g = self.__dict__.get("_guard")
             if g is None:
                 g = self.__dict__["_guard"] = ParamGuard(self)
+            # (poisoned on a difference: layer 0's rbf bias, which its message kernel reads in every step -- the biases of its
+            # node projection are baked into the species table)
             # (the stamp: which builds of the layers' copies + which tensors the embedding and the read-out are right now)
             extra = tuple((p_.data_ptr(), p_._version) for p_ in (self.embed.weight, self.out_energy[0].weight,
                                                                  self.out_energy[0].bias, self.out_energy[2].weight,
                                                                  self.out_energy[2].bias))
-            if not g.step(dev, tuple((id(w), w.builds) for w in ws + [hw] if w is not None) + extra, ws[0].b1cat):
+            if not g.step(dev, tuple((id(w), w.builds) for w in ws + [hw, sp] if w is not None) + extra, ws[0].brbf):
                 return ws, hw
             self.invalidate_caches()            # the previous step ran on stale copies (its result was NaN): rebuild
         return ws, hw
@@ -414,6 +433,9 @@ class HVNet(nn.Module):
         data.x, data.vec = x, None                                          # (vec: zeros, hermnet.py:124)
         data._hn_graph, data._hn_edge, data._hn_edge_embed = graph, edge, edge_embed
         step = StepState(graph, edge, rbf, edge_embed, train=train, fused=fused, whole=whole, weights=weights, head=head)
+        sp = self.__dict__.get("_species")
+        if weights is not None and sp is not None and sp.table is not None and sp.key is not None and not train:
+            step.species = (sp.table, x)
         if fused and edge.requires_grad and switches.fused_layer:
             # one reduction of the edge gradients per step instead of one per layer (layer.EdgeFanout)
             # (atoms of an unknown element own the rows past type_rowptr[T]; only edges INTO them go unwritten)

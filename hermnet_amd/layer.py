@@ -171,6 +171,38 @@ class HeadWeights(object):
         return self
 
 
+class SpeciesTable(object):
+    """Layer 0's node projection of every species, owned by the model beside its LayerWeights.  In an energy / force
+    evaluation x of the first layer is the embedding gather (hermnet.py:123), so xh of a row depends on its species only:
+    `table` [T, V, 3H] = xh of the V embedding rows, made by the `hermnet_node_pre_fwd` instance the per-atom launch of this
+    width takes (same kernel family, tile height and width: a row's result does not depend on its tile's other rows, so the
+    bits are the per-atom launch's), and `nodeops.species_expand` writes xh [T, N, 3H] from it.  Rebuilt when the embedding or
+    layer 0's copies were; never inside a captured graph (`refresh` leaves `table` None there: the per-atom launch runs)."""
+
+    __slots__ = ("embed", "key", "builds", "table")
+
+    def __init__(self, embed):
+        self.embed, self.key, self.builds, self.table = embed, None, 0, None
+
+    @torch.no_grad()
+    def refresh(self, w0):
+        """Current for the embedding's weight and the build `w0.builds` of layer 0's LayerWeights -> self."""
+        key = _version_key([(self.embed, "weight")]) + ((id(w0), w0.builds),)
+        if key == self.key:
+            return self
+        emb = self.embed.weight.detach()
+        self.table = None
+        if not (w0.chain and emb.is_cuda and emb.dtype == torch.float32) or torch.cuda.is_current_stream_capturing():
+            return self                 # (no key: a later refresh outside the capture builds it)
+        Hp = w0.b2.size(-1) // 3
+        if Hp != emb.size(1):           # (padded widths: the channels _prepare pads x with)
+            emb = torch.nn.functional.pad(emb, (0, Hp - emb.size(1)))
+        self.table = nodeops.species_table(emb.contiguous(), w0, len(w0.mods))
+        self.key = key
+        self.builds += 1
+        return self
+
+
 def _bwd_sums_deferrable(graph, H):
     """The message backward can leave its finishing launch to the consumer (hermnet_message_scatter_bwd with gx = NULL):
     channel-per-lane form, targets = sources (HVNet rows), 32-bit offsets.  Width 128 only: there the update backward
@@ -250,7 +282,7 @@ class StepState(object):
     each other, indexed by layer.  Every forward creates its own, so no other step or model sees it; undeclared fields raise."""
 
     __slots__ = ("graph", "edge", "rbf", "edge_embed", "train", "fused", "whole", "weights", "head", "edge_sink",
-                 "edge_handles", "layer", "last", "halo", "chain_node", "pending", "pre_next")
+                 "edge_handles", "layer", "last", "halo", "chain_node", "pending", "pre_next", "species")
 
     def __init__(self, graph=None, edge=None, rbf=None, edge_embed=None, train=False, fused=False, whole=True, weights=None,
                  head=None):
@@ -271,6 +303,7 @@ class StepState(object):
         self.chain_node = None          # a chain layer: the autograd node of its outputs; the layer above takes it
         self.pending = {}               # consuming layer -> nodeops.PendingGrads, from one layer's backward to the next one's
         self.pre_next = {}              # layer -> (x, its node projection), left by the fused update launch of the layer below
+        self.species = None             # _prepare: (the model's SpeciesTable.table, the x it gathered from the embedding); layer 0's Route
 
 
 class Route(object):
@@ -285,17 +318,26 @@ class Route(object):
     `last`: the caller reads x_out only (HVNet's last layer in front of the read-out, energy / force evaluation): the layer
     returns (x_out, None) and its update launches leave out everything that only vec_out and its zero gradient need, where
     `nodeops.last_update_supported`; `first`: the first layer's message backward may skip the source rows' sums
-    (switches.dead_ends, read once)."""
+    (switches.dead_ends, read once).
+    `species`: (table [T, V, 3H], z_rows) where x is the embedding gather of an evaluation (the first layer, unsharded): the node
+    projection is `nodeops.species_expand` of the model's `SpeciesTable` -- no hb / mean / rstd, nothing below takes a gradient;
+    the layer drops it where somebody does want x's gradient."""
 
-    def __init__(self, exchange=None, halo=None, defer=False, pre=None, w_next=None, last=False):
+    def __init__(self, exchange=None, halo=None, defer=False, pre=None, w_next=None, last=False, species=None):
         self.exchange, self.halo, self.defer, self.pre, self.w_next = exchange, halo, defer, pre, w_next
+        self.species = species if exchange is None and pre is None else None
         self.boundary = int(switches.boundary_mode)
         self.first = bool(switches.dead_ends)
         self.last = bool(last and switches.dead_ends and exchange is None and w_next is None)
 
 
 def _local_fwd(x, vec, edge, graph, rbf, w, route):
-    pre = route.pre if route.pre is not None else nodeops.node_pre_fwd(x, w, graph.T, src_ranges=graph.src_ranges)
+    if route.pre is not None:
+        pre = route.pre
+    elif route.species is not None:     # xh from the per-species table; the saved tensors of a backward nobody runs: none
+        pre = (None, nodeops.species_expand(route.species[0], route.species[1], x.size(0)), None, None)
+    else:
+        pre = nodeops.node_pre_fwd(x, w, graph.T, src_ranges=graph.src_ranges)
     x1, vec1 = _msg_fwd(graph, rbf, x.size(1), pre[1], vec, x, w, edge, xh_bias=False)
     return pre, x1, vec1
 
@@ -497,6 +539,8 @@ class FusedRelationalLayer(torch.autograd.Function):
         # wants them -- known only here --, the exchange takes the rows form)
         ctx.exchange = "rows" if (route.exchange == "proj" and not _bwd_sums_deferrable(graph, x.size(1))
                                   and (ctx.needs_input_grad[0] or ctx.needs_input_grad[2])) else route.exchange
+        if route.species is not None and (ctx.needs_input_grad[0] or vec is not None or not x.is_cuda):
+            route.species = None        # (x's gradient wanted -- known only here: the per-atom launch, which saves hb / mean / rstd)
         (hb, xh, mean, rstd), x1, vec1 = _ROUTES[ctx.exchange][0](x, vec, edge, graph, rbf, w, route)
         # (the last layer in front of a read-out of x: no vec output, and no zero gradient for it on the way back)
         # (the short forms are kernels of the device library only)

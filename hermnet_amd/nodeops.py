@@ -291,6 +291,26 @@ def node_pre_fwd(x, w, T, src_ranges=None, windows=None, mode=0, out=None):
     return hb, xh, mean, rstd
 
 
+def species_table(emb, w, T):
+    """The per-species table of `layer.SpeciesTable`: xh [T, V, 3H] of node_pre_fwd on the V embedding rows `emb` [V, H], by the
+    same entry point and so the same kernel instance as the per-atom launch of this width.  A build, not a step's launch: no
+    timer label (`_lib.call`)."""
+    from .ops import _stream
+    hb, xh, mean, rstd = _pre_outputs(emb, T)
+    _lib.call("hermnet_node_pre_fwd", P(emb), P(w.w1f), P(w.b1cat), P(w.w2f), P(w.b2), P(hb), P(xh), P(mean), P(rstd), None,
+              emb.size(0), T, emb.size(1), w.h_real, 1e-5, None, 0, 0, _stream())
+    return xh
+
+
+def species_expand(table, z_rows, Ns):
+    """xh [T, Ns, 3H] = table[:, z_rows]: node_pre_fwd's xh for x = embedding[z_rows] (`z_rows` [Ns] int64), bit for bit, as one
+    copy launch under node_pre_fwd's label (the layer's node projection, in its place among the launches)."""
+    T, V, W = table.shape
+    xh = _new(table, T, Ns, W)
+    _call("node_pre_fwd", "hermnet_species_expand", P(table), P(z_rows), P(xh), Ns, T, V, W)
+    return xh
+
+
 def node_pre_bwd(gxh, hb, x, mean, rstd, w, add=None, src_ranges=None, windows=None, mode=0, out=None, parts_only=False):
     """Gradient of node_pre_fwd w.r.t. x (+ add).  `windows` / `mode` / `out` as in node_pre_fwd (`out` = (gx, parts) of
     the first call).  `parts_only`: no LayerNorm-backward launch -- returns the per-relation partial sums [T,Ns,H] for a

@@ -21,6 +21,7 @@ node_chain = True           # False: library GEMMs + stage kernels instead of th
 boundary_mode = 0           # layer.FusedRelationalLayer: 0 every phase a launch of its own; 4 / 1 / 3 / 2: the fused 16-row forms
 native_relations = True     # False: the relation build as torch ops (its definition: relations.py) instead of the HIP kernels
 dead_ends = True            # False: the general kernel forms at both ends of the layer stack too (layer.Route: `first`, `last`)
+species_table = True        # False: layer 0's node projection per atom in an evaluation too, not from the model's per-species table
 train_row_sums = True       # False: train(): per-edge message kernels + segmented sums instead of row sums inside the kernels
 
 

@@ -19,7 +19,7 @@
  * ABI version 13 (`HN_ABI_VERSION` below, returned by `hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -533,6 +533,15 @@ int hermnet_node_pre_bwd(const float* gxh, const float* hb, const float* w2t_fra
                          float* gn_parts, const float* x, const float* mean, const float* rstd, const float* add,
                          float* gx, const int* src_ranges, int num_src, int num_rel, int hidden, int hidden_real,
                          const int* row_windows, int num_windows, int window_mode, void* stream);
+/* The node projection of layer 0 in an energy / force evaluation (additive in ABI v13): there x is the species embedding, so
+ * xh of a row depends on its species only.  table [num_rel, num_species, width] = xh of hermnet_node_pre_fwd run on the
+ * num_species embedding rows (made once per weight refresh by the caller), width = 3 hidden, a multiple of 4;
+ *     xh[t][r][:] = table[t][z_rows[r]][:]      for every relation t and all num_rows rows (z_rows int64; a value outside
+ *                                               [0, num_species) is clamped into it),
+ * the bits hermnet_node_pre_fwd writes for x[r] = embedding[z_rows[r]].  No hb / mean / rstd: nothing below layer 0 takes a
+ * gradient.  Arrays of 4 GiB and more are handled (64-bit indices). */
+int hermnet_species_expand(const float* table, const long* z_rows, float* xh, int num_rows, int num_rel, int num_species,
+                           int width, void* stream);
 /* hermnet_node_update_fwd (rmnet.py:94-107, 29-31; hermnet.py:51,56-61), target rows in relation order:
  *     vp = vec1 Wv^T  [N,3,2H] = (v1 | v2), saved;   vdot = sum_d v1 v2 / sqrt(H);   n = sqrt(sum_d v2^2 + 1e-8) -> nrm
  *                                                                                    [N,H], saved
