@@ -343,6 +343,11 @@ __device__ __forceinline__ void pre_fwd16_phase(const PreFwdArgs& p, float* bufN
 constexpr size_t lds16_bytes(int tile_floats, int behind = 4 * kScr16Floats) { return (size_t)(tile_floats + behind) * sizeof(float); }
 // the forward kernels, fused or not: three [16][H + 8] tiles
 constexpr size_t fwd16_lds_bytes(int H) { return lds16_bytes(3 * kTR16 * (H + 8)); }
+// node_update_fwd16_kernel<H, false, false> keeps vec1 and v1 on chip: five tiles (vec1[0 .. 2], the norm / a2, x1), the four
+// waves' v1 park [3][2][64] float4 each (= three tiles' rows of H floats), then the scratch.  Two workgroups per CU (kMinWFwd16).
+constexpr int kPark16Floats = 3 * 2 * 64 * 4;
+constexpr size_t upd_fwd16_lds_bytes(int H) { return lds16_bytes(5 * kTR16 * (H + 8) + 4 * kPark16Floats); }
+static_assert(2 * upd_fwd16_lds_bytes(128) <= 160 * 1024, "node_update_fwd16_kernel<128, false, false>: two workgroups per CU");
 
 // The projection as a kernel of its own (the unfused form: A/B and bit-for-bit check of the fused kernel's second half)
 template <int H>
@@ -366,15 +371,25 @@ __global__ __launch_bounds__(256, kMinWFwd16) void node_pre_fwd16_kernel(PreFwdA
 // the last product -- its weight fragments and MFMAs --, dvec = r v1 and the vec_out store are left out; q23 receives q only
 // (its r half stays unwritten: the matching backward, NOGV below, does not read it).  Every accumulator block of p and q sees
 // the MFMAs it sees in the general form, in the same order: x_out, vp, h2b, nrm and q are the same bits.
+//
+// Tile rows on chip (the general form, !FUSE && !NOVEC: `KEEP`).  The residual vec_out = vec1 + r v1 needs vec1 and v1 once more
+// behind the last product.  vec1's three tiles stay alive to the end (the norm / a2 and x1 take two further tiles) and are read in
+// accumulator layout; v1 of the Wv epilogue is parked in a wave-private region, written and read back by the same lane (no
+// barrier, no wait for the vp stores).  Per row 6 H floats fewer through the CU's vector-memory path (vec1 3 H and v1 3 H were
+// read a second time from global memory), and no s_waitcnt vmcnt(0) in front of the last product.  FUSE and NOVEC keep three
+// tiles: FUSE re-reads both from memory as before, NOVEC has no dvec.
 template <int H, bool FUSE, bool NOVEC = false>
 __global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdFwdArgs a, PreFwdArgs p) {
   static_assert(H == 128, "four waves x 32 channels");
   static_assert(!(FUSE && NOVEC), "the last layer has no layer above");
   constexpr int TR = kTR16, LD = H + 8, NB16 = H / 16;       // NB16: 16-channel blocks per part
   constexpr int NQ = NOVEC ? 2 : 3;                          // parts of the last product: (p | q) or (p | q | r)
-  extern __shared__ __align__(16) float lds[];               // 3 x [TR][LD], then 4 x [16][36] scratch
+  constexpr bool KEEP = !FUSE && !NOVEC;                     // vec1 and v1 stay on chip for the residual
+  // 3 x [TR][LD], then 4 x [16][36] scratch; KEEP: 5 x [TR][LD], 4 x the v1 park, then the scratch
+  extern __shared__ __align__(16) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* scr = lds + 3 * TR * LD + wave * kScr16Floats;
+  float* park = lds + 5 * TR * LD + wave * kPark16Floats + lane * 4;          // (KEEP) this lane's float4 (d, s): + (2 d + s) * 256
+  float* scr = lds + (KEEP ? 5 * TR * LD + 4 * kPark16Floats : 3 * TR * LD) + wave * kScr16Floats;
   const TileInfo ti = find_tile(a.type_rowptr, a.T, a.N, TR, blockIdx.x);
   const int row0 = ti.row0, nrows = ti.nrows, t = ti.t;
   if (t >= a.T) {                                 // rows of unknown elements: zero
@@ -424,8 +439,8 @@ __global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdF
   const rsrc_t nrm_r = tile_rsrc(a.nrm + (size_t)row0 * H, nrows * H);
   f32x4 dot[2] = {zero4(), zero4()}, sq[2] = {zero4(), zero4()};
 
-  // ---- vp[d] = vec1[d] Wv^T; vec_dot and |v2|^2 accumulate in registers (v1 is re-read from vp for dvec = r v1:
-  // 24 registers held across the whole kernel keep a third workgroup off the CU)
+  // ---- vp[d] = vec1[d] Wv^T; vec_dot and |v2|^2 accumulate in registers (v1 for dvec = r v1 is parked in LDS -- KEEP -- or
+  // re-read from vp: 24 registers held across the whole kernel keep a third workgroup off the CU)
   STAMP(0);
   STAMP_HWID();
   // The three components in ONE product (three activation tiles per weight fragment): streamed once per component, Wv is
@@ -464,17 +479,21 @@ __global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdF
         pin4(dot[s]);
         pin4(sq[s]);
       }
+      if constexpr (KEEP) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) *reinterpret_cast<f32x4*>(park + (2 * d + s) * 256) = v1[s];
+      }
       store16<6 * H>(scr, lane, v1, vp_r, d * 2 * H + cw);
       store16<6 * H, true>(scr, lane, v2, vp_r, d * 2 * H + H + cw);
     }
     STAMP(3);
   }
-  // ---- xin = [x1 | sqrt(|v2|^2 + 1e-8)]: x1 -> buffer 1, the norm -> buffer 0
-  float* bufx = lds + TR * LD;
-  float* bufn = lds;
+  // ---- xin = [x1 | sqrt(|v2|^2 + 1e-8)]: x1 -> buffer 1, the norm -> buffer 0 (KEEP: tiles 4 and 3, behind the vec1 tiles)
+  float* bufx = lds + (KEEP ? 4 : 1) * TR * LD;
+  float* bufn = lds + (KEEP ? 3 : 0) * TR * LD;
   Ring16<2> rx;
   b16_preload(rx, bpx);
-  __syncthreads();                                   // every wave has finished the product over the three vec tiles
+  if constexpr (!KEEP) __syncthreads();              // every wave has finished the product over the three vec tiles
   tile16_store<H, LD>(bufx, regs, tid);
   {
     f32x4 nv[2];
@@ -507,16 +526,16 @@ __global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdF
     for (int s = 0; s < 2; ++s) {
       const int c0 = cw + 16 * s + ch;
       hv[s] = acch[s];                               // (incl. bx0)
-      *reinterpret_cast<f32x4*>(lds + mrow * LD + c0) = ssilu4(hv[s]);
+      *reinterpret_cast<f32x4*>(bufn + mrow * LD + c0) = ssilu4(hv[s]);
     }
     store16<H, true>(scr, lane, hv, h2b_r, cw);
   }
   __syncthreads();
-  // ---- (p | q | r) = a2 Wx2^T + bx2, then the update and the residual; vec1 is requested before the product
-  // vec1 and v1 of component 0, requested before the product; the components behind it one epilogue step ahead.  (v1 was
+  // ---- (p | q | r) = a2 Wx2^T + bx2, then the update and the residual
+  // FUSE: vec1 and v1 of component 0, requested before the product; the components behind it one epilogue step ahead.  (v1 was
   // stored by this wave's own lanes: the wait makes the stores of the three vp epilogues final before it is read back.)
   Load16 lvv, lv1;
-  if constexpr (!NOVEC) {
+  if constexpr (FUSE) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     issue16<3 * H>(lvv, lane, vec1_r, cw);
     issue16<6 * H>(lv1, lane, vp_r, cw);
@@ -524,7 +543,7 @@ __global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdF
   const float on = (all_on | (bld(act_r, mrow) != 0.f)) ? 1.f : 0.f;
   fence_sched();
   STAMP(6);
-  mma16_panel<H, 2 * NQ, false>(accq, lds + mrow * LD + ch, bpq, rq);
+  mma16_panel<H, 2 * NQ, false>(accq, bufn + mrow * LD + ch, bpq, rq);
   fence_sched();
   STAMP(7);
   const float inv_sqrt_h = rsqrtf((float)H);
@@ -550,11 +569,19 @@ __global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdF
 #pragma unroll
   for (int d = 0; d < (NOVEC ? 0 : 3); ++d) {
     f32x4 vo[2], v1[2];
-    finish16(scr, lane, lvv, vo);
-    finish16(scr, lane, lv1, v1);
-    if (d < 2) {
-      issue16<3 * H>(lvv, lane, vec1_r, (d + 1) * H + cw);
-      issue16<6 * H>(lv1, lane, vp_r, (d + 1) * 2 * H + cw);
+    if constexpr (KEEP) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        vo[s] = *reinterpret_cast<const f32x4*>(lds + d * TR * LD + mrow * LD + cw + 16 * s + ch);
+        v1[s] = *reinterpret_cast<const f32x4*>(park + (2 * d + s) * 256);
+      }
+    } else {
+      finish16(scr, lane, lvv, vo);
+      finish16(scr, lane, lv1, v1);
+      if (d < 2) {
+        issue16<3 * H>(lvv, lane, vec1_r, (d + 1) * H + cw);
+        issue16<6 * H>(lv1, lane, vp_r, (d + 1) * 2 * H + cw);
+      }
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s) vo[s] = (vo[s] + r[s] * v1[s]) * on;
@@ -576,11 +603,93 @@ __global__ __launch_bounds__(256, kMinWFwd16) void node_update_fwd16_kernel(UpdF
 constexpr int pre_bwd16_tile_floats(int H) { return kTR16 * (3 * H + 8); }
 // (node_pre_bwd16_kernel and the fused update backward, which turns the gxh tile's space into its two [16][H + 8] tiles)
 constexpr size_t pre_bwd16_lds_bytes(int H) { return lds16_bytes(pre_bwd16_tile_floats(H) + kTR16 * (H + 8)); }
-// the update backward without the projection's: two [16][H + 8] tiles
-constexpr size_t upd_bwd16_lds_bytes(int H) { return lds16_bytes(2 * kTR16 * (H + 8)); }
+// the update backward without the projection's: two [16][H + 8] tiles and the three that hold gv[d] (below); the last layer's
+// (NOGV) has the two only
+constexpr size_t upd_bwd16_lds_bytes(int H) { return lds16_bytes(5 * kTR16 * (H + 8)); }
+constexpr size_t upd_bwd16_last_lds_bytes(int H) { return lds16_bytes(2 * kTR16 * (H + 8)); }
+// (the grid of configs[1] is 628 tiles on 256 CUs: it needs the third resident workgroup, kMinWBwd16.  A sixth tile for gx
+// would be 61,440 bytes a workgroup: two per CU.)
+static_assert(3 * upd_bwd16_lds_bytes(128) <= 160 * 1024, "node_update_bwd16_kernel<128, false, false>: three workgroups per CU");
 
 template <int H>
 struct Tile16Regs3 { f32x4 v[kTR16 * 3 * H / 4 / 256]; };
+
+// The 16-row form of materialise_pending (node_chain_common.h) for node_update_bwd16_kernel<128, false, false>: the same sums in
+// the same order of operations -- gx_out through ln_prep / ln_out, gvec_out = ((p0 + p1) + p2 ...) + gvec1 --, but indexed like
+// the kernel's elementwise pass (pass it: row it * 8 + tid / 32, channels 4 (tid & 31) .. + 3; gvec component d: the float4 at
+// (row * 3 + d) * H + c, still 512 contiguous bytes per row and component), which takes them from these registers.  gx_out is
+// stored as well (the kernel reloads it once, in accumulator layout, behind its next barrier); gvec_out is stored for the
+// caller only, and not at all with a.hold_gvo.  Rows past the tile's end come out as zero, like an out-of-range tile load.
+template <int H>
+struct Pend16 { f32x4 gx[kTR16 / 8], gv[kTR16 / 8][3]; };
+
+template <int H>
+__device__ __forceinline__ void pending16(const UpdBwdArgs& a, int row0, int nrows, int tid, Pend16<H>& o) {
+  static_assert(H == 128, "half a wave per row");
+  constexpr int RP = kTR16 / 8;
+  const PendingGrads& p = a.pend;
+  const int identity_rows = a.type_rowptr[a.T];
+  const int lane = tid & 63, wave = tid >> 6, c = (lane & 31) * 4;
+  const long ps = (long)a.N * H;
+  int rr[RP];
+  size_t r[RP];
+  // ---- gvec_out: every load of a relation's slice is issued before the first one is used
+#pragma unroll
+  for (int it = 0; it < RP; ++it) {
+    const int lr = it * 8 + wave * 2 + (lane >> 5);
+    rr[it] = lr < nrows ? row0 + lr : -1;
+    r[it] = (size_t)(rr[it] >= 0 ? rr[it] : row0);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) o.gv[it][d] = ld4g(p.gv + (r[it] * 3 + d) * H + c);
+  }
+  // ---- gx_out (requested behind the first slice of gvec, finished while the others arrive)
+  f32x4 gg[RP], xv[RP], av[RP];
+  float mu[RP], rs[RP];
+#pragma unroll
+  for (int it = 0; it < RP; ++it) {
+    gg[it] = ld4g(p.gn + r[it] * H + c);
+    xv[it] = ld4g(p.x + r[it] * H + c);
+    av[it] = ld4g(p.gx1 + r[it] * H + c);
+    mu[it] = p.mean[r[it]];
+    rs[it] = p.rstd[r[it]];
+  }
+  for (int t = 1; t < p.nparts; ++t) {
+#pragma unroll
+    for (int it = 0; it < RP; ++it) gg[it] += ld4g(p.gn + t * ps + r[it] * H + c);
+  }
+#pragma unroll
+  for (int it = 0; it < RP; ++it) {
+    f32x4 gv, nh;
+    float s1 = 0.f, s2 = 0.f;
+    ln_prep(gg[it], xv[it], mu[it], rs[it], c, p.Hr, gv, nh, s1, s2);
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) {
+      s1 += __shfl_xor(s1, m, 64);
+      s2 += __shfl_xor(s2, m, 64);
+    }
+    const float m1 = s1 / (float)p.Hr, m2 = s2 / (float)p.Hr;
+    o.gx[it] = ln_out(gv, nh, m1, m2, rs[it], c, p.Hr, rr[it] >= 0 && rr[it] < identity_rows, av[it], kInvSqrt2);
+    if (rr[it] >= 0) *reinterpret_cast<f32x4*>(const_cast<float*>(a.gxo) + r[it] * H + c) = o.gx[it];
+    else o.gx[it] = zero4();
+  }
+  for (int t = 1; t < p.nparts; ++t) {
+#pragma unroll
+    for (int it = 0; it < RP; ++it)
+#pragma unroll
+      for (int d = 0; d < 3; ++d) o.gv[it][d] += ld4g(p.gv + t * 3 * ps + (r[it] * 3 + d) * H + c);
+  }
+#pragma unroll
+  for (int it = 0; it < RP; ++it)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      if (rr[it] >= 0) {
+        if (rr[it] < identity_rows) o.gv[it][d] += ld4g(p.gvec1 + (r[it] * 3 + d) * H + c);
+        if (!a.hold_gvo) *reinterpret_cast<f32x4*>(const_cast<float*>(a.gvo) + (r[it] * 3 + d) * H + c) = o.gv[it][d];
+      } else {
+        o.gv[it][d] = zero4();
+      }
+    }
+}
 
 // `parts` != null: gn_t goes to parts[t] (the unfused form: the consumer sums the relations and runs the LayerNorm backward);
 // null: gsum = (gn_0 + gn_1) + gn_2 ... in this lane's accumulator positions (the same additions in the same order as the
@@ -684,17 +793,29 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_pre_bwd16_kernel(PreBwdA
 //   * gvec1's accumulator starts at gv = +0 either way;
 //   * gv q3 + s v2 may differ from s v2 in the SIGN of a zero (-0 + +0 = +0), but only as an MFMA operand whose accumulator
 //     started at +0: a +-0 product changes neither a non-zero sum nor a +0 one.
+//
+// Tile rows on chip (the general form, !FUSE && !NOGV: `KEEP`).  Gradients that arrive as partial sums (a.pend.gn) are summed
+// by pending16 straight into the registers of the elementwise pass, which has the same row / channel mapping: no store ->
+// barrier -> load of gx_out and gvec_out at the head of the workgroup.  gv[d], from those registers or loaded from gvo when
+// nothing is pending, is parked in three further LDS tiles (before the `on` factor) and read from there in accumulator layout
+// by the last three products: gvo crosses the CU boundary once instead of twice, or -- pending -- not at all as a load.  Per
+// row and H floats: 49 -> 42 (pending; 39 with a.hold_gvo, which also drops the gvec_out store nobody reads: 15 MB per launch
+// at 10,041 rows), 28 -> 25 without pending.  gx_out keeps its store and ONE reload in accumulator layout (lgx): a sixth tile
+// would cost the third workgroup per CU (upd_bwd16_lds_bytes).  FUSE and NOGV keep their data flow and their LDS layout.
 template <int H, bool FUSE, bool NOGV = false>
 __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdBwdArgs a) {
   static_assert(H == 128, "four waves x 32 channels");
   static_assert(!(FUSE && NOGV), "the last layer has no layer above");
   constexpr int TR = kTR16, LD = H + 8, NB16 = H / 16, V = H / 4, F4 = TR * H / 4 / 256;
-  // 2 x [TR][LD], then 4 x [16][36] scratch; FUSE: [TR][3H + 8] (later the two tiles), [TR][LD], then the scratch
+  constexpr bool KEEP = !FUSE && !NOGV;                      // pending sums handed over in registers, gv[d] in LDS tiles
+  // 2 x [TR][LD] (KEEP: + 3 x [TR][LD] for gv[d]), then 4 x [16][36] scratch; FUSE: [TR][3H + 8] (later the two tiles),
+  // [TR][LD], then the scratch
   extern __shared__ __align__(16) float lds[];
   float* buf0 = lds;
   float* buf1 = lds + TR * LD;
+  float* bufgv = lds + 2 * TR * LD;                          // (KEEP) gv[d]: + d * TR * LD
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  float* scr = lds + (FUSE ? pre_bwd16_tile_floats(H) + TR * LD : 2 * TR * LD) + wave * kScr16Floats;
+  float* scr = lds + (FUSE ? pre_bwd16_tile_floats(H) + TR * LD : (KEEP ? 5 : 2) * TR * LD) + wave * kScr16Floats;
   const TileInfo ti = find_tile(a.type_rowptr, a.T, a.N, TR, blockIdx.x);
   const int row0 = ti.row0, nrows = ti.nrows, t = ti.t;
   if (t >= a.T) {
@@ -721,8 +842,14 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
     __syncthreads();
     materialise_pending<H, TR, true>(a, row0, nrows, tid, lds, LD);
     STAMP(6);
-  } else {
+  } else if constexpr (!KEEP) {
     if (a.pend.gn != nullptr) materialise_pending<H, TR>(a, row0, nrows, tid);   // (incoming gradients still in partial sums)
+  }
+  // KEEP: incoming gradients that still sit in partial sums are formed in the registers the elementwise pass below takes them from
+  const bool pending = KEEP && a.pend.gn != nullptr;         // (wave-uniform: a kernel argument)
+  Pend16<H> pg;
+  if constexpr (KEEP) {
+    if (pending) pending16<H>(a, row0, nrows, tid, pg);
   }
   const f32x4* wx2t = reinterpret_cast<const f32x4*>(a.wx2tf + (size_t)t * frag16_floats(H, 3 * H)) + lane;   // [H, 3H]
   const f32x4* wx0t = reinterpret_cast<const f32x4*>(a.wx0tf + (size_t)t * frag16_floats(2 * H, H)) + lane;   // [2H, H]
@@ -744,7 +871,8 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
   const int mrow = lane & 15, ch = 4 * (lane >> 4), cw = 32 * wave;
   const float inv_sqrt_h = rsqrtf((float)H);
   const rsrc_t gxo_r = tile_rsrc(a.gxo + (size_t)row0 * H, nrows * H);
-  const rsrc_t gvo_r = tile_rsrc(NOGV ? a.gxo : a.gvo + (size_t)row0 * 3 * H, NOGV ? 0 : nrows * 3 * H);
+  const bool no_gvo = NOGV || a.hold_gvo != 0;               // (held: gvo may be null, gv[d] comes from the pending sums)
+  const rsrc_t gvo_r = tile_rsrc(no_gvo ? a.gxo : a.gvo + (size_t)row0 * 3 * H, no_gvo ? 0 : nrows * 3 * H);
   const rsrc_t vp_r = tile_rsrc(a.vp + (size_t)row0 * 6 * H, nrows * 6 * H);
   const rsrc_t h2b_r = tile_rsrc(a.h2b + (size_t)row0 * H, nrows * H);
   const rsrc_t q23_r = tile_rsrc(a.q23 + (size_t)row0 * 2 * H, nrows * 2 * H);
@@ -760,7 +888,19 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
   for (int it = 0; it < F4; ++it) {
     const int idx = tid + it * 256, lr = idx / V, c = (idx % V) * 4;
     const float on = (all_on | (bld(act_r, lr) != 0.f)) ? 1.f : 0.f;
-    const f32x4 gx = bld4(gxo_r, lr * H + c) * on;
+    f32x4 gxr, gvr[3];                                       // gx_out, gvec_out[d] of this position, before the `on` factor
+    if (pending) {
+      gxr = pg.gx[it];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) gvr[d] = pg.gv[it][d];
+    } else {
+      gxr = bld4(gxo_r, lr * H + c);
+      if constexpr (!NOGV) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) gvr[d] = bld4(gvo_r, (lr * 3 + d) * H + c);
+      }
+    }
+    const f32x4 gx = gxr * on;
     f32x4 vd = zero4(), gq3 = zero4();
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
@@ -768,7 +908,10 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
       const f32x4 v2 = bld4(vp_r, (lr * 3 + d) * 2 * H + H + c);
       vd += v1 * v2;
       if constexpr (!NOGV) {
-        const f32x4 gv = bld4(gvo_r, (lr * 3 + d) * H + c) * on;
+        // (KEEP: parked for the accumulator-layout reads of the last three products; the barrier in front of the first
+        // product publishes the tiles, nobody writes them again)
+        if constexpr (KEEP) *reinterpret_cast<f32x4*>(bufgv + d * TR * LD + lr * LD + c) = gvr[d];
+        const f32x4 gv = gvr[d] * on;
         gq3 += gv * v1;
       }
     }
@@ -776,12 +919,14 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
     *reinterpret_cast<f32x4*>(buf1 + lr * LD + c) = gx * vd * (inv_sqrt_h * kInvSqrt2);
     g3.v[it] = gq3;
   }
-  // h2b, gx and q of this wave's accumulator positions: requested now, transposed behind the first product
+  // h2b, gx and q of this wave's accumulator positions: requested now, transposed behind the first product.  (KEEP: gx behind
+  // the barrier -- with pending sums its rows were stored by other waves of this workgroup, in pending16.)
   Load16 lh2, lgx, lq2;
   issue16<H>(lh2, lane, h2b_r, cw);
-  issue16<H>(lgx, lane, gxo_r, cw);
+  if constexpr (!KEEP) issue16<H>(lgx, lane, gxo_r, cw);
   issue16<2 * H>(lq2, lane, q23_r, cw);
   __syncthreads();
+  if constexpr (KEEP) issue16<H>(lgx, lane, gxo_r, cw);
   STAMP(7);
   // ---- ga2 = gq Wx2  (K = 3H: three panels)
   f32x4 acc[2] = {zero4(), zero4()};
@@ -825,7 +970,7 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
   Load16 lnr, lgv, lq3, lw1, lw2;
   issue16<H>(lnr, lane, nrm_r, cw);
   if constexpr (!NOGV) {
-    issue16<3 * H>(lgv, lane, gvo_r, cw);
+    if constexpr (!KEEP) issue16<3 * H>(lgv, lane, gvo_r, cw);
     issue16<2 * H>(lq3, lane, q23_r, H + cw);
   }
   issue16<6 * H>(lw1, lane, vp_r, cw);
@@ -851,7 +996,7 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
     store16<H>(scr, lane, gx1v, gx1_r, cw);
   }
   if constexpr (!NOGV) {
-    finish16(scr, lane, lgv, pgv);
+    if constexpr (!KEEP) finish16(scr, lane, lgv, pgv);
     finish16(scr, lane, lq3, pq3);
   }
   finish16(scr, lane, lw1, pw1);
@@ -860,6 +1005,10 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
     f32x4 accg[2];
+    if constexpr (KEEP) {
+#pragma unroll
+      for (int s = 0; s < 2; ++s) pgv[s] = *reinterpret_cast<const f32x4*>(bufgv + d * TR * LD + mrow * LD + cw + 16 * s + ch);
+    }
     __syncthreads();                                 // the previous product has read both buffers
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -877,7 +1026,7 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
     fence_sched();
     Load16 ngv, nw1, nw2;
     if (d < 2) {                                     // in flight during the product below
-      if constexpr (!NOGV) issue16<3 * H>(ngv, lane, gvo_r, (d + 1) * H + cw);
+      if constexpr (FUSE) issue16<3 * H>(ngv, lane, gvo_r, (d + 1) * H + cw);
       issue16<6 * H>(nw1, lane, vp_r, (d + 1) * 2 * H + cw);
       issue16<6 * H>(nw2, lane, vp_r, (d + 1) * 2 * H + H + cw);
     }
@@ -889,7 +1038,7 @@ __global__ __launch_bounds__(256, kMinWBwd16) void node_update_bwd16_kernel(UpdB
     if (d < 2) b16_preload(rg, bpg);
     fence_sched();
     if (d < 2) {
-      if constexpr (!NOGV) finish16(scr, lane, ngv, pgv);
+      if constexpr (FUSE) finish16(scr, lane, ngv, pgv);
       finish16(scr, lane, nw1, pw1);
       finish16(scr, lane, nw2, pw2);
     }
@@ -1002,13 +1151,36 @@ extern "C" int hermnet_debug_stamps16(unsigned long long* out_host, int count) {
 int hn_update16_supported(int hidden) { return hidden == kH16; }
 
 int hn_update16_fwd(const UpdFwdArgs& a, int tiles, void* stream) {
-  return launch_chain<node_update_fwd16_kernel<kH16, false>>(dim3((unsigned)tiles), fwd16_lds_bytes(kH16), stream, a, PreFwdArgs{});
+  return launch_chain<node_update_fwd16_kernel<kH16, false>>(dim3((unsigned)tiles), upd_fwd16_lds_bytes(kH16), stream, a, PreFwdArgs{});
 }
 
 int hn_update16_bwd(const UpdBwdArgs& a, int tiles, void* stream) {
   if (a.pend.gxh != nullptr)        // fused: the projection's backward of the layer above in front
     return launch_chain<node_update_bwd16_kernel<kH16, true>>(dim3((unsigned)tiles), pre_bwd16_lds_bytes(kH16), stream, a);
   return launch_chain<node_update_bwd16_kernel<kH16, false>>(dim3((unsigned)tiles), upd_bwd16_lds_bytes(kH16), stream, a);
+}
+
+// hermnet_node_update_bwd (16-row form, `pending` in its gn_parts form) whose gvec_out never leaves the chip: the kernel takes
+// gv[d] from the pending sums in registers and LDS, the store nobody reads is skipped (UpdBwdArgs::hold_gvo).
+extern "C" int hermnet_node_update_bwd_held(const float* gx_out, const float* gvec_out, const float* vp, const float* h2b,
+                                            const float* q23, const float* nrm, const float* wx2t_frag16,
+                                            const float* wx0t_frag16, const float* wvt_frag16, const float* row_active,
+                                            const int* type_rowptr, const int* type_rowptr_host, float* gx1, float* gvec1,
+                                            int num_nodes, int num_rel, int hidden, int tile_rows,
+                                            const hn_pending_grads* pending, void* stream) {
+  (void)gvec_out;                                  // neither read nor written
+  UpdBwdArgs a = {gx_out, nullptr, vp, h2b, q23, nrm, wx2t_frag16, wx0t_frag16, wvt_frag16, row_active, type_rowptr, gx1, gvec1,
+                  num_nodes, num_rel, {}, 1};
+  if (!pending || tile_rows != 16) return HN_ERR_BAD_ARG;
+  const int rc = upd_bwd_refused(a, type_rowptr_host, hn_update16_supported(hidden), false);
+  if (rc >= 0) return rc;
+  const hn_pending_grads& p = *pending;
+  if (!p.gn_parts || p.gxh || !p.gvec_parts || !p.x || !p.mean || !p.rstd || !p.gx1 || !p.gvec1 || p.num_parts < 1 ||
+      p.hidden_real > hidden)
+    return HN_ERR_BAD_ARG;
+  a.pend = {p.gn_parts, p.gvec_parts, p.x, p.mean, p.rstd, p.gx1, p.gvec1, p.num_parts, real_width(p.hidden_real, hidden),
+            nullptr, nullptr, nullptr, nullptr};
+  return hn_update16_bwd(a, HN_TILES(16), stream);
 }
 
 // ---- the layer boundary as ONE node launch each way ---------------------------------------------------------------------------
@@ -1099,5 +1271,5 @@ extern "C" int hermnet_node_update_bwd_last(const float* gx_out, const float* vp
                         gvec1, num_nodes, num_rel, {}};
   const int rc = upd_bwd_refused(a, type_rowptr_host, hn_update16_supported(hidden) && !use_wide(hidden), true);
   if (rc >= 0) return rc;
-  return launch_chain<node_update_bwd16_kernel<kH16, false, true>>(dim3((unsigned)HN_TILES(16)), upd_bwd16_lds_bytes(kH16), stream, a);
+  return launch_chain<node_update_bwd16_kernel<kH16, false, true>>(dim3((unsigned)HN_TILES(16)), upd_bwd16_last_lds_bytes(kH16), stream, a);
 }

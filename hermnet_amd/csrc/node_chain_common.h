@@ -96,6 +96,8 @@ struct UpdBwdArgs {
   float* gvec1;             // [N, 3, H]
   int N, T;
   PendingGrads pend;
+  int hold_gvo;             // node_chain16.hip, hermnet_node_update_bwd_held: the pending sums of gvec_out stay on chip, gvo is
+                            // neither read nor written (may be null); 0 everywhere else
 };
 }  // namespace hn_chain
 using namespace hn_chain;
@@ -135,7 +137,7 @@ inline int tiles_of(const int* rp_host, int T, int N, int TR) {
 
 // The one check of the update chains' arguments, each way, behind all five entry points -> -1: launch; else what the entry
 // point returns (HN_OK: no rows, the pointers unchecked; HN_ERR_BAD_ARG).  `supported`: the form's kernels exist at this
-// width; `last`: the last-layer form, whose vec_out / gvec_out is null.
+// width; `last`: the last-layer form, whose vec_out / gvec_out is null (as it may be with UpdBwdArgs::hold_gvo).
 inline int upd_fwd_refused(const UpdFwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
   if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
   if (a.N == 0) return HN_OK;
@@ -146,7 +148,7 @@ inline int upd_fwd_refused(const UpdFwdArgs& a, const int* type_rowptr_host, boo
 inline int upd_bwd_refused(const UpdBwdArgs& a, const int* type_rowptr_host, bool supported, bool last) {
   if (a.N < 0 || a.T <= 0 || !type_rowptr_host || !supported) return HN_ERR_BAD_ARG;
   if (a.N == 0) return HN_OK;
-  const bool ok = a.gxo && (last || a.gvo) && a.vp && a.h2b && a.q23 && a.nrm && a.wx2tf && a.wx0tf && a.wvtf && a.type_rowptr &&
+  const bool ok = a.gxo && (last || a.hold_gvo || a.gvo) && a.vp && a.h2b && a.q23 && a.nrm && a.wx2tf && a.wx0tf && a.wvtf && a.type_rowptr &&
                   a.gx1 && a.gvec1 && type_rowptr_host[a.T] <= a.N;
   return ok ? -1 : HN_ERR_BAD_ARG;
 }

@@ -570,7 +570,12 @@ class FusedRelationalLayer(torch.autograd.Function):
                 raise RuntimeError("hermnet_amd: the gradients handed down as partial sums (layer %d) did not arrive in the "
                                    "buffers they were registered with; set the environment variable named in "
                                    "hermnet_amd/switches.py: defer_sums to 0" % (ctx.li + 1))
-            gx1, gvec1 = nodeops.node_update_bwd(gxo, gvo, vp, h2b, q23, nrm, ctx.w, ctx.graph, pending=pend)
+            # (partial sums, 16-row tiles at width 128: gvo stays unwritten -- the kernel keeps what it forms of it on chip; a
+            # form of the device library only)
+            held = (pend is not None and pend.chain is None and switches.pending_on_chip and gxo.is_cuda
+                    and nodeops.held_update_supported(ctx.graph, gxo.size(1), ctx.w))
+            update_bwd = nodeops.node_update_bwd_held if held else nodeops.node_update_bwd
+            gx1, gvec1 = update_bwd(gxo, gvo, vp, h2b, q23, nrm, ctx.w, ctx.graph, pending=pend)
         gedge = _edge_grad_slot(edge, ctx.graph, ctx.step, ctx.li, x.size(1), gx1.device)
         gx, gvec = _ROUTES[ctx.exchange][1](ctx, x, mean, rstd, hb, xh, vec, edge, gx1, gvec1, gedge)
         return (gx, gvec, _edge_grad(edge, gedge)) + (None,) * 5

@@ -357,8 +357,9 @@ def _update_fwd(form, x1, vec1, w, graph, w_next=None):
     return xo, vo, vp, h2b, q23, nrm, pre
 
 
-def _update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending=None):
-    """The update backward -> (gx1, gvec1); gvo = None: the last-layer form (gvec_out = 0, 16-row tiles)."""
+def _update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending=None, held=False):
+    """The update backward -> (gx1, gvec1); gvo = None: the last-layer form (gvec_out = 0, 16-row tiles); `held`: the form that
+    leaves gvo unwritten (`node_update_bwd_held`)."""
     N, H = gxo.shape
     tile, _, (wx2tf, wx0tf, wvtf) = update_stream(graph, H, w) if gvo is not None else _stream16(w)
     gx1 = torch.empty_like(gxo)
@@ -366,7 +367,9 @@ def _update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending=None):
     saved = (P(vp), P(h2b), P(q23), P(nrm), P(wx2tf), P(wx0tf), P(wvtf), P(graph.row_active), P(graph.type_rowptr),
              _rowptr_host(graph), P(gx1), P(gvec1), N, graph.T, H)
     pend = None if pending is None else ctypes.byref(pending.struct)
-    if gvo is not None:
+    if held:
+        _call("node_update_bwd", "hermnet_node_update_bwd_held", P(gxo), P(gvo), *saved, tile, pend)
+    elif gvo is not None:
         _call("node_update_bwd", "hermnet_node_update_bwd", P(gxo), P(gvo), *saved, tile, pend)
     else:
         _call("node_update_bwd", "hermnet_node_update_bwd_last", P(gxo), *saved, pend)
@@ -445,6 +448,17 @@ def node_pre_bwd16(gxh, hb, w):
     parts = _new(hb, T, Ns, H)
     _call("node_pre_bwd16", "hermnet_node_pre_bwd16", P(gxh), P(hb), P(w.w2tf16), P(w.w1tf16), P(parts), Ns, T, H)
     return parts
+
+
+def held_update_supported(graph, H, w):
+    """`node_update_bwd_held` exists where the update launches of this row layout run 16-row tiles at width 128."""
+    return H == 128 and update_stream(graph, H, w)[0] == 16
+
+
+def node_update_bwd_held(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending):
+    """node_update_bwd with `pending` in its partial-sums form (`pending.chain is None`; `held_update_supported`) that keeps the
+    gvec gradients it forms on chip: `gvo` is neither read nor written (same gx1 / gvec1 bits), `gxo` is workspace of the launch."""
+    return _update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending, held=True)
 
 
 def node_update_bwd(gxo, gvo, vp, h2b, q23, nrm, w, graph, pending=None):

@@ -22,6 +22,7 @@ boundary_mode = 0           # layer.FusedRelationalLayer: 0 every phase a launch
 native_relations = True     # False: the relation build as torch ops (its definition: relations.py) instead of the HIP kernels
 dead_ends = True            # False: the general kernel forms at both ends of the layer stack too (layer.Route: `first`, `last`)
 species_table = True        # False: layer 0's node projection per atom in an evaluation too, not from the model's per-species table
+pending_on_chip = True      # False: the update backward writes the gvec gradients it forms from partial sums back to memory (nobody reads them)
 train_row_sums = True       # False: train(): per-edge message kernels + segmented sums instead of row sums inside the kernels
 
 

@@ -597,6 +597,17 @@ int hermnet_node_update_bwd(const float* gx_out, const float* gvec_out, const fl
                             const float* row_active, const int* type_rowptr, const int* type_rowptr_host, float* gx1,
                             float* gvec1, int num_nodes, int num_rel, int hidden, int tile_rows,
                             const hn_pending_grads* pending, void* stream);
+/* hermnet_node_update_bwd_held (ABI 13, additive): hermnet_node_update_bwd for a caller that never reads gvec_out.  Requires
+ * `pending` in its gn_parts form (pending->gxh == NULL), tile_rows == 16 and hidden 128 (frag16 weights): HN_ERR_BAD_ARG before
+ * any launch otherwise.  The gvec sums the launch forms from the partial sums go from registers and LDS straight into the
+ * products: gvec_out is neither read nor written and may be NULL; gx_out is workspace of the launch (written, then read back by
+ * it).  gx1, gvec1: bit for bit what hermnet_node_update_bwd returns for the same arguments. */
+int hermnet_node_update_bwd_held(const float* gx_out, const float* gvec_out, const float* vp, const float* h2b,
+                                 const float* q23, const float* nrm, const float* wx2t_frag16, const float* wx0t_frag16,
+                                 const float* wvt_frag16,
+                                 const float* row_active, const int* type_rowptr, const int* type_rowptr_host, float* gx1,
+                                 float* gvec1, int num_nodes, int num_rel, int hidden, int tile_rows,
+                                 const hn_pending_grads* pending, void* stream);
 
 /* The LAST layer of an energy / force evaluation (ABI 13, additive; hidden 128, 16-row tiles, frag16 weights): the read-out
  * takes x only, so vec_out feeds nothing and its gradient is identically zero.

@@ -56,6 +56,9 @@ def main():
             "update_pre_fwd": (lambda: nodeops.node_update_pre_fwd(x1, vec1, w, g, w), 2 * N * (11 + 4 * T) * H * H),
             "pre_update_bwd": (lambda: nodeops.node_update_bwd(bx, bv, vp, h2b, q23, nrm, w, g, pending=pend_chain), 2 * N * (11 + 4 * T) * H * H),
         })
+        if nodeops.held_update_supported(g, H, w):          # the form the layer's backward takes: gvec_out never leaves the chip
+            cases["update_bwd(held)"] = (lambda: nodeops.node_update_bwd_held(bx, bv, vp, h2b, q23, nrm, w, g, pend_parts),
+                                         2 * N * 11 * H * H)
     # CHAIN_BENCH_THRASH=MB: between two timed launches a copy of that many MB runs (every launch then meets the caches the way
     # it does inside a step -- weights and inputs evicted from L2 by the message kernels' traffic -- instead of 200 back-to-back
     # launches on hot buffers); launches are timed one by one
