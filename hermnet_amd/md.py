@@ -211,7 +211,7 @@ class DeviceNPT(DeviceMD):
     never scale, so halt and `resume()` are `DeviceMD`'s.
 
     Out of scope: stochastic cell rescaling and MTK (barostats that sample the correct ensemble), velocity scaling, atom
-    shards, HTNet, NPT in `DeviceRelax`, open structures (they have no volume)."""
+    shards, HTNet, open structures (they have no volume).  (Relaxing a cell, under pressure too: `relax.DeviceCellRelax`.)"""
 
     __slots__ = ("pressure", "compressibility", "taup", "coupling", "mask", "max_strain", "cell64", "mu", "clamped", "p0",
                  "coupling_c", "_cell_given")

@@ -1029,6 +1029,76 @@ int hermnet_host_relax_finish(int num_atoms, int num_graphs, const int* graph_pt
                               const unsigned char* fixed_host, float* pos32_host, double* gf_host, long* gi_host,
                               double* gf_new_host, long* gi_new_host, double* log_host, long log_steps, long* state_host);
 
+/* Device-resident CELL relaxation: FIRE on atoms and cell together (added within ABI v13: new entry points only;
+ * hermnet_amd/relax.py: DeviceCellRelax; csrc/cellrelax_kernels.hip, cellrelax_step.h).  The model is ASE's UnitCellFilter
+ * under ASE's FIRE, every graph on its own.  hermnet_cellrelax_advance is enqueued in FRONT of the neighbour search of a step
+ * captured WITH the virial kernels and with the cell as a device-side input, hermnet_cellrelax_finish BEHIND the force
+ * backward: one replay is one force-and-stress evaluation.  Units: eV, Angstrom; pressures in eV / A^3.
+ *
+ * Per graph, C0 = cell0 (float64, constant) and cf = cell_factor:  F (deform) starts as I, C = C0 F^T (cell64);  the
+ *   generalised coordinates are q_i = x_i F^-T (the state; x is derived) and the rows G = cf F (rows);  the generalised forces
+ *   fq_i = f_i F (0 where held) and fG = proj(S F^-T) / cf, S = sym(W) - p V I, W = float64(virial), V = |det C|, p =
+ *   pressure[g];  proj in this order: HN_CELLRELAX_HYDROSTATIC replaces by (tr / 3) I, then x mask [9] entry-wise, then
+ *   HN_CELLRELAX_CONSTANT_VOLUME subtracts tr / 3 from the diagonal.  The objective is the enthalpy E + p V.
+ * Caller-owned state beside hermnet_relax_*'s (x0, image0, f_prev, fixed, batch, graph_ptr, fmax_graph, gf, gi, gf_new,
+ *   gi_new, state as there; v [N,3] the velocities of q):   q, q0 [N,3] float64 and x [N,3] = q F^T;   cell0, inv_cell0 [B,9]
+ *   float64 (the inverse by adjugate over determinant), cell_factor [B] > 0;   rows, rows0, rows_v [B,9] G, its start-of-step
+ *   backup and its velocities;   deform, deform_inv, cell64 [B,9], det_f [B] (det F of the last advance; 1 at the start);
+ *   cell32 [B,9] float32 = float(C): the tensor search, edge geometry and virial kernels read;   obs [B,11] = (V, tr W / 3V,
+ *   stress [9] = -sym(W) / V) of a graph's last evaluation while it moved;   mask_host [9]: a HOST array, read at the call;
+ *   log [log_steps,B,6] = (enthalpy, max generalised force, dt, edges found, V, tr W / 3V);   gf's energy is the enthalpy,
+ *   its fnorm the largest generalised force.
+ *
+ * hermnet_cellrelax_advance   halt code != 0: nothing.  First kernel, per graph that has not converged: rows0 = rows, rows +=
+ *   scale rows_v, F = rows / cf, C_ij = (C0_i0 F_j0 + C0_i1 F_j1) + C0_i2 F_j2, cell32 = float(C), det_f = det F, F^-1 =
+ *   adj(F) / det F.  Second kernel, per atom of such a graph: q0, x0, image0 = q, x, image; unless held q += scale v, then with
+ *   HN_MD_WRAP (the only flag) the wrap of hermnet_md_advance on q against cell0 / inv_cell0;  x_j = (q_0 F_j0 + q_1 F_j1) +
+ *   q_2 F_j2.  All atoms: pos32 = float(x).  A converged graph is not written, its cell included.
+ * hermnet_cellrelax_finish    halt code != 0 or done: nothing.  The step's code is hermnet_md_finish's, with
+ *   HN_MD_HALT_NONFINITE also for a virial entry that is not finite or a det_f that is not > 0.  Code != 0: void -- for the
+ *   graphs that moved q, x, image = q0, x0, image0, pos32 = float(x), rows = rows0 and deform, deform_inv, cell64, cell32 made
+ *   of it again; velocities, rows_v and the per-graph state untouched; state = (step, code, step, 0); no log row.  Code 0:
+ *   hermnet_relax_finish's text on the n + 3 rows (fq_i, vq_i; fG_r, rows_v_r): P, ff, vv and the clamp's s are the atoms'
+ *   canonical sums, THEN the three cell rows' terms added in row order 0, 1, 2; fm2 is the maximum over atoms and rows.
+ *   Launches: one 256-lane workgroup per graph, then the workgroup that alone writes state, gf and gi.
+ * The hermnet_host_cellrelax_* twins run the same text on HOST pointers (no stream), bit for bit.
+ * HN_ERR_BAD_ARG: hermnet_relax_*'s, a NULL cell array / virial / pressure / obs / mask_host, a mask entry that is not finite,
+ *   unknown flag bits; the host twins also refuse cell_factor <= 0 (the device entry points cannot read it). */
+#define HN_CELLRELAX_HYDROSTATIC 1
+#define HN_CELLRELAX_CONSTANT_VOLUME 2
+int hermnet_cellrelax_advance(int num_atoms, int num_graphs, int flags, double* q, double* q0, double* x, double* x0,
+                              const double* v, int* image, int* image0, const unsigned char* fixed, const long* batch,
+                              const double* cell0, const double* inv_cell0, const double* cell_factor, double* rows, double* rows0,
+                              const double* rows_v, double* deform, double* deform_inv, double* det_f, double* cell64,
+                              float* cell32, float* pos32, const long* state, const double* gf, const long* gi, void* stream);
+int hermnet_cellrelax_finish(int num_atoms, int num_graphs, int flags, const int* graph_ptr, const float* forces,
+                             const float* energy, const float* virial, const long* total, long capacity, double dt, double dtmax,
+                             double maxstep, double fmax, const double* fmax_graph, const double* pressure,
+                             const double* mask_host, const double* cell0, const double* inv_cell0, const double* cell_factor,
+                             double* q, const double* q0, double* x, const double* x0, double* v, int* image, const int* image0,
+                             float* f_prev, const unsigned char* fixed, float* pos32, double* rows, const double* rows0,
+                             double* rows_v, double* deform, double* deform_inv, double* det_f, double* cell64, float* cell32,
+                             double* obs, double* gf, long* gi, double* gf_new, long* gi_new, double* log, long log_steps,
+                             long* state, void* stream);
+int hermnet_host_cellrelax_advance(int num_atoms, int num_graphs, int flags, double* q_host, double* q0_host, double* x_host,
+                                   double* x0_host, const double* v_host, int* image_host, int* image0_host,
+                                   const unsigned char* fixed_host, const long* batch_host, const double* cell0_host,
+                                   const double* inv_cell0_host, const double* cell_factor_host, double* rows_host,
+                                   double* rows0_host, const double* rows_v_host, double* deform_host, double* deform_inv_host,
+                                   double* det_f_host, double* cell64_host, float* cell32_host, float* pos32_host,
+                                   const long* state_host, const double* gf_host, const long* gi_host);
+int hermnet_host_cellrelax_finish(int num_atoms, int num_graphs, int flags, const int* graph_ptr_host, const float* forces_host,
+                                  const float* energy_host, const float* virial_host, const long* total_host, long capacity,
+                                  double dt, double dtmax, double maxstep, double fmax, const double* fmax_graph_host,
+                                  const double* pressure_host, const double* mask_host, const double* cell0_host,
+                                  const double* inv_cell0_host, const double* cell_factor_host, double* q_host,
+                                  const double* q0_host, double* x_host, const double* x0_host, double* v_host, int* image_host,
+                                  const int* image0_host, float* f_prev_host, const unsigned char* fixed_host, float* pos32_host,
+                                  double* rows_host, const double* rows0_host, double* rows_v_host, double* deform_host,
+                                  double* deform_inv_host, double* det_f_host, double* cell64_host, float* cell32_host,
+                                  double* obs_host, double* gf_host, long* gi_host, double* gf_new_host, long* gi_new_host,
+                                  double* log_host, long log_steps, long* state_host);
+
 #ifdef __cplusplus
 }
 #endif
