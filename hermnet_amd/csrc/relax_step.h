@@ -1,9 +1,10 @@
-// The arithmetic of the device-resident FIRE relaxation (relax_kernels.hip): ONE text for the device kernels, their host
-// twins (hermnet_host_relax_advance / _finish) and -- transcribed operation by operation -- the numpy float64 reference of
-// tests/relax_reference.py.  FIRE as ASE's optimize/fire.py steps it (Bitzek et al., PRL 97, 170201), independently per
-// graph.  Per-atom work is IEEE + and x on doubles, one rounding each (contraction off), in the order written; `/` and sqrt
-// appear in the two per-graph scalar functions alone (relax_graph_update, relax_graph_scale), where they are the correctly
-// rounded IEEE operations on the device as on the host (no fast-math).
+// The arithmetic of the device-resident FIRE relaxation (relax_kernels.hip; the finish that strings it together, for the
+// cell relaxation too: relax_driver.h): ONE text for the device kernels, their host twins (hermnet_host_relax_advance /
+// _finish) and -- transcribed operation by operation -- the numpy float64 reference of tests/relax_reference.py.  FIRE as
+// ASE's optimize/fire.py steps it (Bitzek et al., PRL 97, 170201), independently per graph.  Per-atom work is IEEE + and x
+// on doubles, one rounding each (contraction off), in the order written; `/` and sqrt appear in the two per-graph scalar
+// functions alone (relax_graph_update, relax_graph_scale), where they are the correctly rounded IEEE operations on the
+// device as on the host (no fast-math).
 //
 // The per-graph sums that steer the trajectory take the canonical order of resident_step.h; an atom's term is (t0 + t1) + t2.
 #ifndef HERMNET_RELAX_STEP_H

@@ -1,6 +1,8 @@
-// The step protocol of the device-resident drivers (md_kernels.hip, relax_kernels.hip), stated once: ONE text for the device
-// kernels and their host twins, transcribed operation by operation in tests/md_reference.py and tests/relax_reference.py.
-// Contraction is off inside every function, so device, host and numpy agree bit for bit.
+// The step protocol of the device-resident drivers (md_kernels.hip, relax_kernels.hip, cellrelax_kernels.hip), stated once:
+// ONE text for the device kernels and their host twins, transcribed operation by operation in tests/md_reference.py,
+// tests/relax_reference.py and tests/cellrelax_reference.py.  Contraction is off inside every function, so device, host and
+// numpy agree bit for bit.  hn_lead_lane and hn_barrier let a driver write a workgroup's body and its host loop as one text
+// too (relax_driver.h: the FIRE finish of both relaxations).
 //
 // A driver brackets the captured step with an advance in front of the neighbour search and a finish behind the force
 // backward.  Finish derives the step's halt code from what the evaluation left behind (hn_step_code); every workgroup derives
@@ -55,6 +57,22 @@ HN_HD inline long hn_step_code(const float* energy, int num_graphs, const long* 
   for (int g = 0; g < num_graphs; ++g) bad |= hn_not_finite(energy[g]);
 #endif
   return md_step_code(total[0], total[1], capacity, bad);
+}
+
+// For a text that a workgroup and a host loop both run (relax_driver.h): the lane that does a graph's scalar work, and the
+// workgroup's barrier.  The host is that lane, and has nobody to wait for.
+HN_HD inline bool hn_lead_lane() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return threadIdx.x == 0;
+#else
+  return true;
+#endif
+}
+
+HN_HD inline void hn_barrier() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  __syncthreads();
+#endif
 }
 
 // The halt half of the commit (the single writer of `state`): true where the step was void.

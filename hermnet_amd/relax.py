@@ -134,25 +134,32 @@ class DeviceRelax(ResidentDriver):
         return s
 
     # ---- ASE hand-off (duck-typed: ASE itself is not needed) --------------------------------------------------------------------
+    OPEN_REFUSED = None       # from_atoms: the message that refuses a structure not periodic in all three directions, if any
+    CELLS_FLOAT64 = False     # from_atoms: the cells go on as float64 on the host; else as the step's float32, on the device
+
     @classmethod
     def from_atoms(cls, atoms, model, device="cuda:0", **kw):
         """`atoms`: one structure or a list of them (one batch), anything with `positions`, `numbers`, `cell`, `pbc`.  The
-        members of a list are all periodic (pbc in all three directions) or all open."""
+        members of a list are all periodic (pbc in all three directions) or all open (`DeviceCellRelax`: all periodic, and
+        their cells are kept in float64)."""
         dev = torch.device(device)
         ms = _members(atoms)
         periodic = [bool(np.all(np.asarray(m.pbc))) for m in ms]
+        if cls.OPEN_REFUSED and not all(periodic):
+            raise RuntimeError(cls.OPEN_REFUSED)
         if len(set(periodic)) != 1 or (not periodic[0] and any(np.any(np.asarray(m.pbc)) for m in ms)):
             raise RuntimeError("DeviceRelax.from_atoms: structures that are all periodic in three directions, or all open")
         pos = np.concatenate([np.asarray(m.positions, dtype=np.float64).reshape(-1, 3) for m in ms])
         z = torch.as_tensor(np.concatenate([np.asarray(m.numbers).reshape(-1) for m in ms])).to(dev)
         cells = np.stack([np.asarray(m.cell, dtype=np.float64).reshape(3, 3) for m in ms]) if periodic[0] else None
+        if cells is not None and not cls.CELLS_FLOAT64:
+            cells = torch.from_numpy(cells).float().to(dev)
         if not isinstance(atoms, (list, tuple)):
             if cells is None:
                 raise RuntimeError("DeviceRelax.from_atoms: one structure must be periodic (open structures: a list)")
-            return cls(model, z, torch.from_numpy(cells[0]).float().to(dev), pos, device=dev, **kw)
+            return cls(model, z, cells[0], pos, device=dev, **kw)
         batch = torch.from_numpy(np.repeat(np.arange(len(ms)), [len(m.positions) for m in ms])).to(dev)
-        cell = None if cells is None else torch.from_numpy(cells).float().to(dev)
-        return cls(model, z, cell, pos, batch=batch, num_graphs=len(ms), device=dev, **kw)
+        return cls(model, z, cells, pos, batch=batch, num_graphs=len(ms), device=dev, **kw)
 
     def to_atoms(self, atoms, snapshot=None):
         """Write the positions (wrapped) of `snapshot` (default: a fetch()) into `atoms` (one structure, or the list the
@@ -291,22 +298,10 @@ class DeviceCellRelax(DeviceRelax):
         s.stress = obs[:, 2:].reshape(B, 3, 3).copy()
         s.volume = np.abs(_det3(s.cell))
 
-    # ---- ASE hand-off ---------------------------------------------------------------------------------------------------------
-    @classmethod
-    def from_atoms(cls, atoms, model, device="cuda:0", **kw):
-        """As `DeviceRelax.from_atoms`; the cells are taken in float64 and open structures are refused."""
-        dev = torch.device(device)
-        ms = _members(atoms)
-        if not all(bool(np.all(np.asarray(m.pbc))) for m in ms):
-            raise RuntimeError("DeviceCellRelax.from_atoms: periodic structures (pbc in all three directions): an open "
-                               "structure has no cell to relax")
-        pos = np.concatenate([np.asarray(m.positions, dtype=np.float64).reshape(-1, 3) for m in ms])
-        z = torch.as_tensor(np.concatenate([np.asarray(m.numbers).reshape(-1) for m in ms])).to(dev)
-        cells = np.stack([np.asarray(m.cell, dtype=np.float64).reshape(3, 3) for m in ms])
-        if not isinstance(atoms, (list, tuple)):
-            return cls(model, z, cells[0], pos, device=dev, **kw)
-        batch = torch.from_numpy(np.repeat(np.arange(len(ms)), [len(m.positions) for m in ms])).to(dev)
-        return cls(model, z, cells, pos, batch=batch, num_graphs=len(ms), device=dev, **kw)
+    # ---- ASE hand-off: DeviceRelax.from_atoms, with these two rules ------------------------------------------------------------
+    OPEN_REFUSED = ("DeviceCellRelax.from_atoms: periodic structures (pbc in all three directions): an open structure has no "
+                    "cell to relax")
+    CELLS_FLOAT64 = True                  # `_own_state` makes cell0 of them
 
     def to_atoms(self, atoms, snapshot=None):
         """`DeviceRelax.to_atoms`, and each member's cell -- written first and without moving the atoms: the positions are

@@ -974,11 +974,12 @@ int hermnet_host_md_finish_npt(int num_atoms, int num_graphs, const int* graph_p
                                double* mu_host, long* clamped_host, double* log_host, long log_steps, long* state_host);
 
 /* Device-resident FIRE relaxation of a batch of structures (added within ABI v13: new entry points only;
- * hermnet_amd/relax.py: DeviceRelax; csrc/relax_kernels.hip, relax_step.h).  As for hermnet_md_*: hermnet_relax_advance is
- * enqueued in FRONT of the captured neighbour search and hermnet_relax_finish BEHIND the force backward, so that one replay of
- * the step's hipGraph is one force evaluation of the optimiser.  The optimiser is ASE's FIRE (dt, dtmax, maxstep, fmax are
- * arguments; Nmin 5, finc 1.1, fdec 0.5, astart 0.1, fa 0.99), applied to every graph on its own: a graph whose largest
- * force is below its threshold freezes while the others keep going.  Units: eV, Angstrom; FIRE's time is a parameter.
+ * hermnet_amd/relax.py: DeviceRelax; csrc/relax_kernels.hip, relax_driver.h, relax_step.h).  As for hermnet_md_*:
+ * hermnet_relax_advance is enqueued in FRONT of the captured neighbour search and hermnet_relax_finish BEHIND the force
+ * backward, so that one replay of the step's hipGraph is one force evaluation of the optimiser.  The optimiser is ASE's
+ * FIRE (dt, dtmax, maxstep, fmax are arguments; Nmin 5, finc 1.1, fdec 0.5, astart 0.1, fa 0.99), applied to every graph on
+ * its own: a graph whose largest force is below its threshold freezes while the others keep going.  Units: eV, Angstrom;
+ * FIRE's time is a parameter.
  *
  * Caller-owned state (all allocated outside the capture):
  *   x, x0 [N,3] float64 coordinates and their start-of-step backup;   v [N,3] float64 FIRE's velocities;   image, image0
@@ -1030,8 +1031,8 @@ int hermnet_host_relax_finish(int num_atoms, int num_graphs, const int* graph_pt
                               double* gf_new_host, long* gi_new_host, double* log_host, long log_steps, long* state_host);
 
 /* Device-resident CELL relaxation: FIRE on atoms and cell together (added within ABI v13: new entry points only;
- * hermnet_amd/relax.py: DeviceCellRelax; csrc/cellrelax_kernels.hip, cellrelax_step.h).  The model is ASE's UnitCellFilter
- * under ASE's FIRE, every graph on its own.  hermnet_cellrelax_advance is enqueued in FRONT of the neighbour search of a step
+ * hermnet_amd/relax.py: DeviceCellRelax; csrc/cellrelax_kernels.hip, relax_driver.h, cellrelax_step.h).  The model is ASE's
+ * UnitCellFilter under ASE's FIRE, every graph on its own.  hermnet_cellrelax_advance is enqueued in FRONT of the neighbour search of a step
  * captured WITH the virial kernels and with the cell as a device-side input, hermnet_cellrelax_finish BEHIND the force
  * backward: one replay is one force-and-stress evaluation.  Units: eV, Angstrom; pressures in eV / A^3.
  *

@@ -383,3 +383,94 @@ def test_ase_hand_off():
     lone = _FakeAtoms(s["pos"][ptr[2]:], s["z"][ptr[2]:], s["cell"][2])
     got = one.to_atoms(lone)
     assert np.array_equal(lone.cell, got.cell[0]) and np.array_equal(lone.positions, got.positions)
+
+
+def _many_on_the_device(host):
+    """Device copies of a HostCellRelax's arrays and (advance, finish) closures over hermnet_cellrelax_advance / _finish."""
+    dev, lib, P = rdt._dev(), _lib.load(), _lib.ptr
+    names = ["q", "q0", "x", "x0", "v", "image", "image0", "f_prev", "batch", "cell0", "inv0", "cf", "p", "rows", "rows0", "rows_v",
+             "deform", "deform_inv", "det_f", "cell64", "cell32", "obs", "pos32", "state", "gf", "gi", "gf_new", "gi_new", "log",
+             "graph_ptr", "fmax"]
+    d = {k: torch.from_numpy(getattr(host, k).copy()).to(dev) for k in names}
+    stream = torch.cuda.current_stream().cuda_stream
+    n, B = host.n, host.B
+
+    def advance():
+        _lib.check(lib.hermnet_cellrelax_advance(n, B, host.flags, P(d["q"]), P(d["q0"]), P(d["x"]), P(d["x0"]), P(d["v"]),
+                                                 P(d["image"]), P(d["image0"]), None, P(d["batch"]), P(d["cell0"]), P(d["inv0"]),
+                                                 P(d["cf"]), P(d["rows"]), P(d["rows0"]), P(d["rows_v"]), P(d["deform"]),
+                                                 P(d["deform_inv"]), P(d["det_f"]), P(d["cell64"]), P(d["cell32"]), P(d["pos32"]),
+                                                 P(d["state"]), P(d["gf"]), P(d["gi"]), stream), "advance")
+
+    def finish(f, w, e, tot):
+        f_d, e_d, w_d, t_d = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (f, e, w.reshape(B, 9), tot))
+        _lib.check(lib.hermnet_cellrelax_finish(n, B, host.cell_flags, P(d["graph_ptr"]), P(f_d), P(e_d), P(w_d), P(t_d), 5000,
+                                                host.dt, host.dtmax, host.maxstep, float(host.fmax[0]), P(d["fmax"]), P(d["p"]),
+                                                host.mask.ctypes.data, P(d["cell0"]), P(d["inv0"]), P(d["cf"]), P(d["q"]),
+                                                P(d["q0"]), P(d["x"]), P(d["x0"]), P(d["v"]), P(d["image"]), P(d["image0"]),
+                                                P(d["f_prev"]), None, P(d["pos32"]), P(d["rows"]), P(d["rows0"]), P(d["rows_v"]),
+                                                P(d["deform"]), P(d["deform_inv"]), P(d["det_f"]), P(d["cell64"]), P(d["cell32"]),
+                                                P(d["obs"]), P(d["gf"]), P(d["gi"]), P(d["gf_new"]), P(d["gi_new"]), P(d["log"]),
+                                                host.log_steps, P(d["state"]), stream), "finish")
+        torch.cuda.synchronize()
+
+    return d, advance, finish
+
+
+_MANY_F64 = ("q", "q0", "x", "x0", "v", "rows", "rows0", "rows_v", "deform", "deform_inv", "det_f", "cell64", "obs", "gf",
+             "gf_new", "log")
+_MANY_EXACT = ("image", "image0", "f_prev", "gi", "gi_new", "pos32", "cell32", "state")
+
+
+def _many_equal(d, host):
+    for key in _MANY_F64:
+        assert np.array_equal(bits(d[key].cpu().numpy()), bits(getattr(host, key))), key
+    for key in _MANY_EXACT:
+        assert np.array_equal(d[key].cpu().numpy(), getattr(host, key)), key
+
+
+def test_more_graphs_than_lanes():
+    """tests/test_cellrelax_host.py's B = 257 (graph 256 moving beside 256 converged graphs, graph 3 empty), kernel-direct: two
+    advance + finish through hermnet_cellrelax_advance / _finish against their host twins, bit for bit -- graph 256 (the second
+    block of the advance's lane-per-graph kernel) is moved, committed and counted in `all` (done stays 0), and done is 1 once
+    the second evaluation puts it under fmax."""
+    import test_cellrelax_host as cht
+    host, _, first, second = cht.many_graphs()
+    d, advance, finish = _many_on_the_device(host)
+    start = {k: getattr(host, k).copy() for k in ("x", "cell32")}
+    for k, (f, w) in enumerate((first, second)):
+        e, tot = np.zeros(host.B, dtype=np.float32), np.array([11 + k, 0], dtype=np.int64)
+        advance()
+        finish(f, w, e, tot)
+        host.advance()
+        host.finish(f, w, energy=e, total=tot, capacity=5000)
+        _many_equal(d, host)
+        assert host.state.tolist() == [k + 1, 0, 0, k]
+        assert host.gi[256, 1:].tolist() == [[0, 0, -1], [0, 1, 1]][k] and (host.gf[256, 2] > 0.0) == (k == 0)
+    x, cell32 = d["x"].cpu().numpy(), d["cell32"].cpu().numpy()
+    assert np.array_equal(bits(x[:-2]), bits(start["x"][:-2])) and not np.array_equal(x[-2:], start["x"][-2:])
+    assert np.array_equal(cell32[:256], start["cell32"][:256]) and not np.array_equal(cell32[256], start["cell32"][256])
+    assert np.all(host.log[2:] == -7.0)
+
+
+def test_more_graphs_than_lanes_void_on_the_last_virial():
+    """The virial of graph 256 alone is NaN (an input the kernels answer with a halt code): code 256, graph 256's atoms and
+    cell back to the start of the step, graphs 0..255 untouched, no log row -- every array bit-equal to the host twins'."""
+    import test_cellrelax_host as cht
+    host, _, (f, w), _ = cht.many_graphs()
+    d, advance, finish = _many_on_the_device(host)
+    names = ("q", "x", "image", "pos32", "rows", "deform", "cell64", "cell32", "gf", "gi", "log")
+    keep = {k: getattr(host, k).copy() for k in names}
+    w = w.copy()
+    w[256, 1, 2] = np.nan
+    e, tot = np.zeros(host.B, dtype=np.float32), np.array([11, 0], dtype=np.int64)
+    advance()
+    moved = d["cell32"].cpu().numpy()
+    assert not np.array_equal(moved[256], keep["cell32"][256]) and np.array_equal(moved[:256], keep["cell32"][:256])
+    finish(f, w, e, tot)
+    host.advance()
+    host.finish(f, w, energy=e, total=tot, capacity=5000)
+    _many_equal(d, host)
+    assert d["state"].cpu().numpy().tolist() == [0, 256, 0, 0]
+    for key, want in keep.items():
+        assert np.array_equal(d[key].cpu().numpy().view(np.uint8), want.view(np.uint8)), key

@@ -371,3 +371,77 @@ def test_argument_refusals():
     assert lib.hermnet_cellrelax_finish(*(dev_f[:15] + [_p(mask)] + dev_f[16:])) == bad
     assert lib.hermnet_cellrelax_finish(*(dev_f[:15] + [None] + dev_f[16:])) == bad
     assert lib.hermnet_cellrelax_finish(*(dev_f[:6] + [None] + dev_f[7:])) == bad
+
+
+MANY = 257      # one graph more than the 256 lanes that stride over the GRAPHS: in the commit's copy and its `all`, in the halt
+#                 code, in the advance's lane-per-graph kernel (a second block)
+
+
+def many_graphs():
+    """B = 257 with 257 atoms: graph 3 is empty, graph 256 has two atoms, every other graph one.  Graphs 0..255 converged at
+    evaluation 0 beforehand; graph 256 is moving (past its first step; velocities of atoms and cell rows and a scale set).
+    (host twin, numpy transcription, (forces, virial) of two evaluations: the second puts graph 256 under fmax)."""
+    sizes = np.ones(MANY, dtype=np.int64)
+    sizes[3], sizes[256] = 0, 2
+    n = int(sizes.sum())
+    rs = np.random.RandomState(MANY)
+    cells = TRICLINIC[None] * rs.uniform(0.4, 0.6, (MANY, 1, 1))
+    batch = np.repeat(np.arange(MANY), sizes)
+    x = np.einsum("nk,nkj->nj", rs.uniform(-0.5, 1.5, (n, 3)), cells[batch])
+    host = HostCellRelax(x, cells, batch=batch, num_graphs=MANY, log_steps=4)
+    ref = NumpyCellRelax(x, cells, batch=batch, num_graphs=MANY)
+    host.v[-2:] = ref.v[-2:] = rs.normal(scale=0.3, size=(2, 3))
+    host.rows_v[256] = ref.rows_v[256] = rs.normal(scale=0.1, size=9)
+    host.gi[:, 1], host.gi[:256, 2], host.gi[:256, 3], host.gi[256, 0], host.gf[256, 2] = 0, 1, 0, 2, 0.1
+    host.gf_new[:], host.gi_new[:] = host.gf, host.gi
+    ref.fresh[:], ref.converged[:256], ref.conv_step[:256], ref.nsteps[256], ref.scale[256] = 0, 1, 0, 2, 0.1
+    f, w = rs.normal(size=(n, 3)).astype(np.float32), rs.normal(scale=5.0, size=(MANY, 3, 3)).astype(np.float32)
+    return host, ref, (f, w), (f * np.float32(1e-3), w * np.float32(1e-4))
+
+
+MANY_NAMES = ("q", "x", "v", "image", "pos32", "rows", "rows_v", "deform", "deform_inv", "cell64", "cell32", "obs", "gf", "gi",
+              "log", "f_prev")
+
+
+def test_more_graphs_than_lanes():
+    """Graph 256 -- the second trip of lane 0 through every loop that strides over the graphs, and the second block of the
+    advance's lane-per-graph kernel -- beside 256 converged graphs: after one advance + finish its atoms and cell have moved,
+    it is committed (gf / gi, its log row) and is counted in `all` (done stays 0); after a second evaluation that puts it
+    under fmax, done is 1.  Bit-equal to the numpy transcription throughout; graphs 0..255 are never written."""
+    host, ref, first, second = many_graphs()
+    start = {k: getattr(host, k).copy() for k in ("x", "cell32", "rows", "gi")}
+    for k, (f, w) in enumerate((first, second)):
+        (pos32, cell32), (rp, rc) = host.advance(), ref.advance()
+        assert np.array_equal(pos32, rp) and np.array_equal(cell32, rc)
+        host.finish(f, w, total=(11 + k, 0))
+        ref.finish(f, w, total=(11 + k, 0))
+        same_state(host, ref)
+        assert np.array_equal(bits(host.log[k]), bits(ref.log[k])) and np.array_equal(host.f_prev, ref.f)
+        assert host.state.tolist() == [k + 1, 0, 0, k]
+        assert host.gi[256, 1:].tolist() == [[0, 0, -1], [0, 1, 1]][k] and (host.gf[256, 2] > 0.0) == (k == 0)
+    for name in ("x", "cell32", "rows"):
+        a, b = getattr(host, name), start[name]
+        rows = slice(-2, None) if name == "x" else slice(256, None)
+        keep = slice(None, -2) if name == "x" else slice(None, 256)
+        assert np.array_equal(a[keep].view(np.uint8), b[keep].view(np.uint8)) and not np.array_equal(a[rows], b[rows]), name
+    assert np.array_equal(host.gi[:256], start["gi"][:256]) and np.all(host.log[2:] == -7.0)
+
+
+def test_more_graphs_than_lanes_void_on_the_last_virial():
+    """The virial of graph 256 alone is NaN: halt code 256 at evaluation 0, graph 256's atoms and cell back to the start of
+    the step bit for bit, graphs 0..255 untouched, no log row; equal to the numpy transcription."""
+    host, ref, (f, w), _ = many_graphs()
+    keep = [getattr(host, k).copy() for k in MANY_NAMES]
+    (pos32, cell32), _ = host.advance(), ref.advance()
+    moved = (pos32.copy(), cell32.reshape(MANY, 9).copy())
+    old_pos, old_cell = keep[MANY_NAMES.index("pos32")], keep[MANY_NAMES.index("cell32")]
+    assert not np.array_equal(moved[0][-2:], old_pos[-2:]) and not np.array_equal(moved[1][256], old_cell[256])
+    assert np.array_equal(moved[0][:-2], old_pos[:-2]) and np.array_equal(moved[1][:256], old_cell[:256])
+    w = w.copy()
+    w[256, 1, 2] = np.nan
+    host.finish(f, w, total=(11, 0))
+    ref.finish(f, w, total=(11, 0))
+    assert host.state.tolist() == [0, 256, 0, 0]
+    for k, want in zip(MANY_NAMES, keep):
+        assert np.array_equal(getattr(host, k).view(np.uint8), want.view(np.uint8)), k
+    same_state(host, ref)

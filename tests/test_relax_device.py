@@ -383,3 +383,41 @@ def test_ase_hand_off():
         DeviceRelax.from_atoms(mixed, _shared_model())
     one = DeviceRelax.from_atoms(atoms[2], _shared_model(), fmax=1e-6)
     assert one.num_graphs == 1 and one.batch is None and one.n == 144
+
+
+def test_more_graphs_than_lanes():
+    """tests/test_relax_host.py's B = 257 (graph 256 moving beside 256 converged graphs, graph 3 empty), kernel-direct: two
+    advance + finish through hermnet_relax_advance / _finish against their host twins, bit for bit -- graph 256 is moved,
+    committed and counted in `all` (done stays 0), and done is 1 once the second evaluation puts it under fmax."""
+    import test_relax_host as rht
+    dev, lib, P = _dev(), _lib.load(), _lib.ptr
+    host, _, f1, f2 = rht.many_graphs()
+    n, B = host.n, host.B
+    names = ["x", "x0", "v", "image", "image0", "f_prev", "batch", "pos32", "state", "gf", "gi", "gf_new", "gi_new", "log",
+             "graph_ptr", "fmax"]
+    d = {k: torch.from_numpy(getattr(host, k).copy()).to(dev) for k in names}
+    stream = torch.cuda.current_stream().cuda_stream
+    start = host.x.copy()
+    for k, f in enumerate((f1, f2)):
+        e, tot = np.zeros(B, dtype=np.float32), np.array([11 + k, 0], dtype=np.int64)
+        f_d, e_d, t_d = (torch.from_numpy(a).to(dev) for a in (f, e, tot))
+        _lib.check(lib.hermnet_relax_advance(n, B, host.flags, P(d["x"]), P(d["x0"]), P(d["v"]), P(d["image"]), P(d["image0"]),
+                                             None, P(d["batch"]), None, None, P(d["pos32"]), P(d["state"]), P(d["gf"]), P(d["gi"]),
+                                             stream), "advance")
+        _lib.check(lib.hermnet_relax_finish(n, B, P(d["graph_ptr"]), P(f_d), P(e_d), P(t_d), 5000, host.dt, host.dtmax,
+                                            host.maxstep, float(host.fmax[0]), P(d["fmax"]), P(d["x"]), P(d["v"]), P(d["x0"]),
+                                            P(d["image"]), P(d["image0"]), P(d["f_prev"]), None, P(d["pos32"]), P(d["gf"]),
+                                            P(d["gi"]), P(d["gf_new"]), P(d["gi_new"]), P(d["log"]), host.log_steps,
+                                            P(d["state"]), stream), "finish")
+        torch.cuda.synchronize()
+        host.advance()
+        host.finish(f, energy=e, total=tot, capacity=5000)
+        got = {k: d[k].cpu().numpy() for k in names}
+        assert got["state"].tolist() == host.state.tolist() == [k + 1, 0, 0, k]
+        for key in ("x", "x0", "v", "gf", "gf_new", "log"):
+            assert np.array_equal(bits(got[key]), bits(getattr(host, key))), key
+        for key in ("image", "image0", "f_prev", "gi", "gi_new", "pos32"):
+            assert np.array_equal(got[key], getattr(host, key)), key
+        assert got["gi"][256, 1:].tolist() == [[0, 0, -1], [0, 1, 1]][k] and (got["gf"][256, 2] > 0.0) == (k == 0)
+    assert np.array_equal(bits(got["x"][:-2]), bits(start[:-2])) and np.abs(got["x"][-2:] - start[-2:]).min() > 1e-4
+    assert np.all(got["log"][2:] == -7.0) and np.all(got["log"][:2, :, 3] == [[11], [12]])

@@ -322,3 +322,44 @@ def test_argument_refusals():
     # the same checks in front of the device entry points (they return before anything is launched)
     assert lib.hermnet_relax_advance(3, 0, 0, *([None] * 14)) == bad
     assert lib.hermnet_relax_finish(3, 1, None, None, None, None, 10, 0.0, 1.0, 0.2, 0.05, *([None] * 14), 4, None, None) == bad
+
+
+MANY = 257      # one graph more than the 256 lanes that stride over the GRAPHS: the commit's copy and its `all`, the halt code
+
+
+def many_graphs():
+    """B = 257 with 257 atoms: graph 3 is empty, graph 256 has two atoms, every other graph one.  Graphs 0..255 converged at
+    evaluation 0 beforehand; graph 256 is moving (past its first step, velocities and a scale set).  (host twin, numpy
+    transcription, the forces of two evaluations: the second puts graph 256 under fmax)."""
+    sizes = np.ones(MANY, dtype=np.int64)
+    sizes[3], sizes[256] = 0, 2
+    n = int(sizes.sum())
+    rs = np.random.RandomState(MANY)
+    x, batch = rs.uniform(1.0, 9.0, (n, 3)), np.repeat(np.arange(MANY), sizes)
+    host = HostRelax(x, batch=batch, num_graphs=MANY, log_steps=4)
+    ref = NumpyRelax(x, batch=batch, num_graphs=MANY)
+    host.v[-2:] = ref.v[-2:] = rs.normal(scale=0.3, size=(2, 3))
+    host.gi[:, 1], host.gi[:256, 2], host.gi[:256, 3], host.gi[256, 0], host.gf[256, 2] = 0, 1, 0, 2, 0.1
+    host.gf_new[:], host.gi_new[:] = host.gf, host.gi
+    ref.fresh[:], ref.converged[:256], ref.conv_step[:256], ref.nsteps[256], ref.scale[256] = 0, 1, 0, 2, 0.1
+    f = rs.normal(size=(n, 3)).astype(np.float32)
+    assert (f[-2:].astype(np.float64) ** 2).sum(1).max() > 0.05 ** 2
+    return host, ref, f, f * np.float32(1e-3)
+
+
+def test_more_graphs_than_lanes():
+    """Graph 256 -- the second trip of lane 0 through every loop that strides over the graphs -- beside 256 converged graphs:
+    after one advance + finish it has moved, is committed (gf / gi, its log row) and is counted in `all` (done stays 0);
+    after a second evaluation that puts it under fmax, done is 1.  Bit-equal to the numpy transcription throughout."""
+    host, ref, f1, f2 = many_graphs()
+    start = host.x.copy()
+    for k, f in enumerate((f1, f2)):
+        assert np.array_equal(host.advance(), ref.advance())
+        host.finish(f, total=(11 + k, 0))
+        ref.finish(f, total=(11 + k, 0))
+        same_state(host, ref)
+        assert np.array_equal(bits(host.log[k]), bits(ref.log[k])) and np.array_equal(host.f_prev, ref.f)
+        assert host.state.tolist() == [k + 1, 0, 0, k]
+        assert host.gi[256, 1:].tolist() == [[0, 0, -1], [0, 1, 1]][k] and (host.gf[256, 2] > 0.0) == (k == 0)
+    assert np.array_equal(bits(host.x[:-2]), bits(start[:-2])) and np.abs(host.x[-2:] - start[-2:]).min() > 1e-4
+    assert np.all(host.gi[:256] == [0, 0, 1, 0]) and np.all(host.log[2:] == -7.0)
