@@ -19,7 +19,7 @@
  * ABI version 13 (`HN_ABI_VERSION` below, returned by `hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table), then hermnet_neb_finish with its hermnet_host_neb_finish twin (the device-resident nudged elastic band) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -1099,6 +1099,57 @@ int hermnet_host_cellrelax_finish(int num_atoms, int num_graphs, int flags, cons
                                   double* deform_inv_host, double* det_f_host, double* cell64_host, float* cell32_host,
                                   double* obs_host, double* gf_host, long* gi_host, double* gf_new_host, long* gi_new_host,
                                   double* log_host, long log_steps, long* state_host);
+
+/* Device-resident nudged elastic band: climbing-image NEB with improved tangents under FIRE on the whole band (added within
+ * ABI v13: new entry points only; hermnet_amd/neb.py: DeviceNEB; csrc/neb_kernels.hip, neb_step.h).  The captured step is
+ * bracketed by hermnet_relax_advance -- unchanged, WITHOUT HN_MD_WRAP, so displacements between images are plain differences
+ * -- and hermnet_neb_finish behind the force backward: one replay is one force evaluation of every image.
+ *
+ * The B graphs are the images; band_ptr [K+1] int32 splits them into K bands of >= 3 images of one atom count, band_of [B]
+ * int32 names each image's band.  A band's first and last image are end points: evaluated, never moved -- their gf / gi rows
+ * are converged = 1, scale = 0 from the start and are never written.  Caller-owned state as for hermnet_relax_* (x, x0, v,
+ * image, image0, f_prev, fixed, pos32, graph_ptr, log [log_steps,B,4], state), and: gf [B,5] / gi [B,4] hermnet_relax_*'s rows
+ * per image -- an interior image's row is its band's FIRE state (dt, a, scale, max |g_a| over the band; nsteps, fresh,
+ * converged, conv_step) with the image's own energy --, k_band, fmax_band [K] float64 (spring constant eV/A^2, threshold
+ * eV/A), obs [B,4] = (energy, max |g_a|, |t2|, ft) per image (end points: the energy, 0, 0, 0), climber [K] int64 the
+ * climbing image's index within its band (-1: none);  scratch: g [N,3], isum [B,4], csum [B], bf_new [K,5], bi_new [K,4],
+ * climber_new [K].
+ *
+ * hermnet_neb_finish    halt code != 0 or done: nothing.  The step's code is hermnet_md_finish's.  Code != 0: void -- x, image
+ *   = x0, image0 and pos32 = float(x) for the interior images of the bands that moved; velocities and all state untouched;
+ *   state = (step, code, step, 0); no log row.  Code 0, per band that has not converged, per interior image i with energies
+ *   Em, E0, Ep = float64(energy[i-1], [i], [i+1]), F = float64(forces) (0 where held), t1 = x_i - x_(i-1), t2 = x_(i+1) - x_i
+ *   (0 where held):  (c1, c2) = (0, 1) if Ep > E0 > Em;  (1, 0) if Ep < E0 < Em;  else with hi / lo = max / min(|Ep - E0|,
+ *   |Em - E0|): (lo, hi) if Ep > Em else (hi, lo);  T = c2 t2 + c1 t1;  canonical sums over the image's atoms t1.t1, t2.t2,
+ *   T.T, F.T;  inv = T.T == 0 ? 0 : 1 / sqrt(T.T);  ft = (F.T) inv;  spring = k (sqrt(t2.t2) - sqrt(t1.t1));  par = spring - ft,
+ *   or -2 ft on the climbing image (climb = 1: the band's interior image of largest energy, ties to the lowest index);  g_a =
+ *   F_a + par (T_a inv);  canonical sums g.v, g.g, v.v, max |g_a|^2 per image, folded over the band's interior images in
+ *   ascending order from 0.0;  then hermnet_relax_finish's FIRE on those sums with g for f, the clamp's sum v.v per image and
+ *   then over the images in the same order;  f_prev = forces.  A band whose max |g_a| < fmax_band[k] converges: conv_step =
+ *   step, scale = 0, v = 0, and it is never written again.  Every image: log[step % log_steps][i] = (obs energy, obs max |g_a|,
+ *   the band's dt, total[0]).  step += 1; done = 1 once every band has converged.
+ *   Three launches: one 256-lane workgroup per image (tangent, scalars, g, partials), one per image (the band's sums, FIRE,
+ *   velocities, the clamp's partial), then the one workgroup that alone writes state, gf, gi and climber.  No atomics; no
+ *   workgroup reads what another of the same launch writes.
+ * hermnet_host_neb_finish runs the same text on HOST pointers (no stream), bit for bit.
+ * HN_ERR_BAD_ARG: a NULL pointer (fixed may be NULL; the per-atom arrays with num_atoms > 0), num_graphs < 3, num_bands < 1
+ *   or > num_graphs / 3, log_steps < 1, capacity < 0, climb not 0 or 1, dt, dtmax or maxstep not positive; the host twin also
+ *   refuses bands that do not tile the graphs, a band shorter than 3, images of unequal atom count, a band_of that disagrees,
+ *   k < 0 and fmax <= 0 (the device entry point cannot read them). */
+int hermnet_neb_finish(int num_atoms, int num_graphs, int num_bands, int climb, const int* graph_ptr, const int* band_ptr,
+                       const int* band_of, const float* forces, const float* energy, const long* total, long capacity, double dt,
+                       double dtmax, double maxstep, const double* k_band, const double* fmax_band, double* x, double* v,
+                       const double* x0, int* image, const int* image0, float* f_prev, const unsigned char* fixed, float* pos32,
+                       double* gf, long* gi, double* obs, long* climber, double* g, double* isum, double* csum, double* bf_new,
+                       long* bi_new, long* climber_new, double* log, long log_steps, long* state, void* stream);
+int hermnet_host_neb_finish(int num_atoms, int num_graphs, int num_bands, int climb, const int* graph_ptr_host,
+                            const int* band_ptr_host, const int* band_of_host, const float* forces_host, const float* energy_host,
+                            const long* total_host, long capacity, double dt, double dtmax, double maxstep,
+                            const double* k_band_host, const double* fmax_band_host, double* x_host, double* v_host,
+                            const double* x0_host, int* image_host, const int* image0_host, float* f_prev_host,
+                            const unsigned char* fixed_host, float* pos32_host, double* gf_host, long* gi_host, double* obs_host,
+                            long* climber_host, double* g_host, double* isum_host, double* csum_host, double* bf_new_host,
+                            long* bi_new_host, long* climber_new_host, double* log_host, long log_steps, long* state_host);
 
 #ifdef __cplusplus
 }
