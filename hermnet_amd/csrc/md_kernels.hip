@@ -15,6 +15,7 @@
 // virial and the kinetic tensor, and writes the float32 cell the NEXT replay's search reads.  A void step, a prime and a
 // parked replay never scale, so the cell needs no backup.
 #include <hip/hip_runtime.h>
+#include "md_finish.h"
 #include "npt_step.h"
 
 #pragma clang fp contract(off)
@@ -34,24 +35,6 @@ struct MdAdvanceArgs {
   const long* state;
   double dt;
   uint64_t seed;
-};
-
-struct MdFinishArgs {
-  int n, num_graphs;
-  double *x, *v;
-  const double *x0, *v0;
-  int* image;
-  const int* image0;
-  float* f_prev;
-  const float *forces, *energy;
-  const long* total;
-  long capacity;
-  const double *kick, *half_mass;
-  const int* graph_ptr;
-  float* pos32;
-  double *ke_atom, *log;
-  long log_steps;
-  long* state;
 };
 
 __host__ __device__ inline void md_advance_one(const MdAdvanceArgs& a, int i, long step, long mode) {
@@ -91,41 +74,11 @@ __host__ __device__ inline void md_advance_one(const MdAdvanceArgs& a, int i, lo
   for (int k = 0; k < 3; ++k) a.pos32[3 * (size_t)i + k] = (float)x[k];
 }
 
-__host__ __device__ inline void md_finish_one(const MdFinishArgs& a, int i, long code, long mode) {
-  if (mode != 0) {
-    if (code == 0)
-      for (int k = 0; k < 3; ++k) a.f_prev[3 * (size_t)i + k] = a.forces[3 * (size_t)i + k];
-    return;
-  }
-  if (code != 0) {        // the step is void: back to the state it began with
-    hn_restore_atom(i, a.x, a.x0, a.image, a.image0, a.pos32);
-    for (int k = 0; k < 3; ++k) a.v[3 * (size_t)i + k] = a.v0[3 * (size_t)i + k];
-    return;
-  }
-  double v[3];
-  float f[3];
-  for (int k = 0; k < 3; ++k) {
-    v[k] = a.v[3 * (size_t)i + k];
-    f[k] = a.forces[3 * (size_t)i + k];
-  }
-  a.ke_atom[i] = md_finish_atom(v, f, a.kick[i], a.half_mass[i]);
-  for (int k = 0; k < 3; ++k) {
-    a.v[3 * (size_t)i + k] = v[k];
-    a.f_prev[3 * (size_t)i + k] = f[k];
-  }
-}
-
 __host__ __device__ inline void md_log_row(const MdFinishArgs& a, long step, int g, double e_kin) {
   double* row = hn_log_row(a.log, step, a.log_steps, a.num_graphs, g, 3);
   row[0] = (double)a.energy[g];
   row[1] = e_kin;
   row[2] = (double)a.total[0];
-}
-
-// The single writer of `state`: a void step records its halt, a completed one is counted; a prime clears its mode.
-__host__ __device__ inline void md_commit(long* state, long step, long code, long mode) {
-  if (!hn_commit_halt(state, step, code) && mode == 0) state[HN_STATE_STEP] = step + 1;
-  if (mode != 0) state[HN_STATE_MODE] = 0;
 }
 
 __global__ __launch_bounds__(256) void md_advance_kernel(MdAdvanceArgs a) {
@@ -267,14 +220,6 @@ bool md_advance_args_ok(const MdAdvanceArgs& a) {
   if ((a.flags & HN_MD_LANGEVIN) && (!a.c1 || !a.sigma)) return false;
   if ((a.flags & HN_MD_WRAP) && (!a.cell || !a.inv_cell)) return false;
   return true;
-}
-
-bool md_finish_args_ok(const MdFinishArgs& a) {
-  if (a.n < 0 || a.num_graphs < 1 || a.log_steps < 1 || a.capacity < 0) return false;
-  if (!a.state || !a.energy || !a.total || !a.graph_ptr || !a.log) return false;
-  if (a.n == 0) return true;
-  return a.x && a.v && a.x0 && a.v0 && a.image && a.image0 && a.f_prev && a.forces && a.kick && a.half_mass && a.pos32 &&
-         a.ke_atom;
 }
 
 bool npt_args_ok(const NptArgs& a) {

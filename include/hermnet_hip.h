@@ -1151,6 +1151,51 @@ int hermnet_host_neb_finish(int num_atoms, int num_graphs, int num_bands, int cl
                             long* climber_host, double* g_host, double* isum_host, double* csum_host, double* bf_new_host,
                             long* bi_new_host, long* climber_new_host, double* log_host, long log_steps, long* state_host);
 
+/* Device-resident temperature replica exchange (added within ABI v13: new entry points only; hermnet_amd/remd.py: DeviceREMD;
+ * csrc/remd_kernels.hip, remd_step.h).  The captured step is a Langevin step of B replicas of ONE system: hermnet_md_advance,
+ * unchanged, in front of the search, and hermnet_remd_finish in the place of hermnet_md_finish behind the force backward.
+ *
+ * One ladder of R = B rungs.  Caller-owned state beside hermnet_md_finish's (log is [log_steps,B,5] here):  beta [R] float64
+ * = 1 / (kB T_r);  up, down [R-1] float64 = sqrt(T_(r+1) / T_r), sqrt(T_r / T_(r+1));  sigma_table [R, N/B] float64, row r
+ * = hermnet_md_advance's sigma of one replica at T_r;  sigma [N] float64, the array hermnet_md_advance reads;  rung [B] int64
+ * the rung replica g holds and replica_at [R] int64 its inverse (both start as the identity: replicas stay where they are
+ * in the batch, temperatures travel);  attempts, accepts [R-1] int64 counters per pair (r, r+1);  scratch: rung_new [B] int64,
+ * vscale [B] float64, outcome [R-1] int64 (0 not tried, 1 rejected, 2 accepted).  `seed` is hermnet_md_advance's.
+ *
+ * hermnet_remd_finish    halt code != 0: nothing.  Mode 1, and a step whose code is not 0: as hermnet_md_finish -- rung,
+ *   replica_at, sigma and the counters untouched, no attempt.  Code 0: hermnet_md_finish's second kick, f_prev and ke_atom;
+ *   then, where (step + 1) % exchange_interval == 0, attempt a = (step + 1) / exchange_interval - 1 tries the pairs (r, r+1)
+ *   with r % 2 == a % 2, r + 1 < R:  with ga = replica_at[r], gb = replica_at[r+1],  delta = (beta[r] - beta[r+1]) *
+ *   ((double)energy[ga] - (double)energy[gb]);  accepted iff delta >= 0 or log(u) < delta,  u = (u(w0,w1) + 1) 2^-53 with
+ *   hermnet_md_advance's u(,) and w = Philox4x32-10 of key (seed low, seed high), counter (r, step low, step high, 2) --
+ *   streams 0 and 1 are the atoms' noise.  An accepted pair swaps rungs; every velocity of ga is multiplied by up[r], of gb by
+ *   down[r]; sigma[i] = sigma_table[new rung][i - first atom of the replica];  attempts[r] counts tried, accepts[r] accepted
+ *   pairs.  log[step % log_steps][g] = (energy[g], the canonical sum of ke_atom over replica g -- taken before any rescaling
+ *   --, total[0], rung[g] during the step, rung[g] behind the step's exchange);  step += 1.
+ *   Four launches: hermnet_md_finish's per-atom kernel; one workgroup with a lane per pair that writes the scratch alone; one
+ *   256-lane workgroup per replica (E_kin, the log row, v and sigma where its rung changed); and the one workgroup that alone
+ *   writes rung, replica_at, the counters and state.  No atomics; no workgroup reads what another of the same launch writes.
+ * hermnet_host_remd_finish runs the same text on HOST pointers (no stream), bit for bit but for the last digits of log(u).
+ * HN_ERR_BAD_ARG: hermnet_md_finish's, a NULL pointer, num_graphs < 2, num_atoms no multiple of num_graphs,
+ *   exchange_interval < 1; the host twin also refuses replicas that do not tile the atoms in equal ranges and a rung /
+ *   replica_at that is no permutation with its inverse (the device entry point cannot read them). */
+int hermnet_remd_finish(int num_atoms, int num_graphs, const int* graph_ptr, const float* forces, const float* energy,
+                        const long* total, long capacity, long exchange_interval, unsigned long seed, double* x, double* v,
+                        const double* x0, const double* v0, int* image, const int* image0, float* f_prev, const double* kick,
+                        const double* half_mass, float* pos32, double* ke_atom, const double* beta, const double* up,
+                        const double* down, const double* sigma_table, double* sigma, long* rung, long* replica_at,
+                        long* rung_new, double* vscale, long* outcome, long* attempts, long* accepts, double* log,
+                        long log_steps, long* state, void* stream);
+int hermnet_host_remd_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const float* forces_host,
+                             const float* energy_host, const long* total_host, long capacity, long exchange_interval,
+                             unsigned long seed, double* x_host, double* v_host, const double* x0_host, const double* v0_host,
+                             int* image_host, const int* image0_host, float* f_prev_host, const double* kick_host,
+                             const double* half_mass_host, float* pos32_host, double* ke_atom_host, const double* beta_host,
+                             const double* up_host, const double* down_host, const double* sigma_table_host,
+                             double* sigma_host, long* rung_host, long* replica_at_host, long* rung_new_host,
+                             double* vscale_host, long* outcome_host, long* attempts_host, long* accepts_host, double* log_host,
+                             long log_steps, long* state_host);
+
 #ifdef __cplusplus
 }
 #endif
