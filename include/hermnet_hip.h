@@ -19,7 +19,7 @@
  * ABI version 13 (`HN_ABI_VERSION` below, returned by `hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table), then hermnet_neb_finish with its hermnet_host_neb_finish twin (the device-resident nudged elastic band) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table), then hermnet_neb_finish with its hermnet_host_neb_finish twin (the device-resident nudged elastic band), then hermnet_remd_finish with its hermnet_host_remd_finish twin (replica exchange), then hermnet_pimd_advance / _finish with their hermnet_host_pimd_* twins (ring-polymer path-integral MD) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -1194,6 +1194,58 @@ int hermnet_host_remd_finish(int num_atoms, int num_graphs, const int* graph_ptr
                              const double* up_host, const double* down_host, const double* sigma_table_host,
                              double* sigma_host, long* rung_host, long* replica_at_host, long* rung_new_host,
                              double* vscale_host, long* outcome_host, long* attempts_host, long* accepts_host, double* log_host,
+                             long log_steps, long* state_host);
+
+/* Device-resident ring-polymer path-integral MD (added within ABI v13: new entry points only; hermnet_amd/pimd.py: DevicePIMD;
+ * csrc/pimd_kernels.hip, pimd_step.h).  The captured step is one BAOAB step of a ring polymer whose P = B beads are the graphs
+ * of the batch, all ONE system of n_rep = N / B atoms (atom a of bead j is row j n_rep + a): hermnet_pimd_advance in the place
+ * of hermnet_md_advance in front of the search, hermnet_pimd_finish in the place of hermnet_md_finish behind the force
+ * backward.  Convention: Ceriotti et al., J. Chem. Phys. 133, 124104 (2010) -- every bead feels the full potential, the
+ * extended system is sampled at P T, omega_P = P kB T / hbar, omega_k = 2 omega_P sin(k pi / P).
+ *
+ * Caller-owned state beside hermnet_md_advance's / _finish's (log is [log_steps,B,5] here), every table made on the host in
+ * float64:  cmat [P,P] the real orthogonal normal-mode matrix C[j][k] at j P + k (k = 0: sqrt(1/P); 0 < 2k < P: sqrt(2/P)
+ * cos(2 pi j k / P); 2k = P: sqrt(1/P) (-1)^j; 2k > P: sqrt(2/P) sin(2 pi j k / P));  cs, sw, ws [P] = cos(omega_k t),
+ * sin(omega_k t) / omega_k (t for k = 0), omega_k sin(omega_k t), with t = dt / 2 under HN_MD_LANGEVIN and t = dt without;
+ * c1 [P] = exp(-dt gamma_k) and sigma [P, n_rep] = sqrt(kB P T (1 - c1_k^2) / m_a) (both read under HN_MD_LANGEVIN alone);
+ * inv_beads = 1 / P;  spring_c [n_rep] = m_a omega_P^2 / 2 (0 for an atom that is held);  centroid [n_rep,3] float64 scratch.
+ *
+ * hermnet_pimd_advance   halt code != 0: nothing.  mode 1: pos32 = float(x), nothing else.  Otherwise x0, v0, image0 = x, v,
+ *   image, then per atom whose kick is not 0:  v_j += kick f_prev_j on every bead;  per component q~_k = sum_j C[j][k] q_j and
+ *   v~_k likewise (from 0.0, ascending j);  the free flight q~' = cs_k q~ + sw_k v~, v~' = cs_k v~ - ws_k q~ (the old q~);
+ *   under HN_MD_LANGEVIN v~ = c1_k v~ + sigma[k][a] xi with hermnet_md_advance's xi of (seed, step, k n_rep + a), and the
+ *   free flight again;  q_j = sum_k C[j][k] q~_k (from 0.0, ascending k), v likewise;  with HN_MD_WRAP the centroid
+ *   c = (ascending sum of the q_j) inv_beads takes hermnet_md_advance's wrap against cell / inv_cell of graph 0, and EVERY
+ *   bead of the atom loses the same floor(s) cell and gains the same floor(s) in its image.  An atom whose kick is 0 (an
+ *   infinite mass) keeps x, v and image.  All atoms: pos32 = float(x); centroid[a] = c (wrapped where the atom was).
+ *   One launch: a 256-lane workgroup per tile of 256 / P atoms x P lanes, the transform through LDS; no atomics.
+ * hermnet_pimd_finish    hermnet_md_finish, but for the log row:  log[step % log_steps][j] = (energy[j], E_kin_j, total[0],
+ *   spring_j = sum_a spring_c[a] |x_(j,a) - x_(j+1,a)|^2 (cyclic in j), vir_j = sum_a (x_(j,a) - centroid[a]) . forces_(j,a)),
+ *   the three sums over the atoms that are not held, float64 in hermnet_md_finish's fixed order.  Three launches.
+ * The hermnet_host_pimd_* twins run the same text on HOST pointers (no stream), bit for bit what the device computes for the
+ * same forces and xi.  HN_ERR_BAD_ARG: hermnet_md_advance's / _finish's, a NULL table, num_graphs > 128, num_atoms no multiple
+ * of num_graphs; the host finish also refuses beads that do not tile the atoms in equal ranges. */
+int hermnet_pimd_advance(int num_atoms, int num_graphs, int flags, unsigned long seed, double inv_beads, double* x, double* v,
+                         double* x0, double* v0, int* image, int* image0, const float* f_prev, const double* kick,
+                         const double* cmat, const double* cs, const double* sw, const double* ws, const double* c1,
+                         const double* sigma, const float* cell, const double* inv_cell, float* pos32, double* centroid,
+                         const long* state, void* stream);
+int hermnet_pimd_finish(int num_atoms, int num_graphs, const int* graph_ptr, const float* forces, const float* energy,
+                        const long* total, long capacity, double* x, double* v, const double* x0, const double* v0, int* image,
+                        const int* image0, float* f_prev, const double* kick, const double* half_mass, float* pos32,
+                        double* ke_atom, const double* spring_c, const double* centroid, double* log, long log_steps,
+                        long* state, void* stream);
+int hermnet_host_pimd_advance(int num_atoms, int num_graphs, int flags, unsigned long seed, double inv_beads, double* x_host,
+                              double* v_host, double* x0_host, double* v0_host, int* image_host, int* image0_host,
+                              const float* f_prev_host, const double* kick_host, const double* cmat_host, const double* cs_host,
+                              const double* sw_host, const double* ws_host, const double* c1_host, const double* sigma_host,
+                              const float* cell_host, const double* inv_cell_host, float* pos32_host, double* centroid_host,
+                              const long* state_host);
+int hermnet_host_pimd_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const float* forces_host,
+                             const float* energy_host, const long* total_host, long capacity, double* x_host, double* v_host,
+                             const double* x0_host, const double* v0_host, int* image_host, const int* image0_host,
+                             float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
+                             double* ke_atom_host, const double* spring_c_host, const double* centroid_host, double* log_host,
                              long log_steps, long* state_host);
 
 #ifdef __cplusplus
