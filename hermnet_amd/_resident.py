@@ -2,7 +2,8 @@
 a driver resident -- the float64 state on the device, the parked `state` words, the log ring, the graphed step captured
 between the driver's two hooks, `run` / `fetch` / `resume` and the reaction to a fetched halt code.  A subclass adds its own
 arrays, its two hooks (`_advance`, `_finish`: the launches of its kernels), what follows a capture (`_unpark`) and the extra
-tensors of its packed `fetch()`.  The step protocol the kernels keep is stated in csrc/resident_step.h.
+tensors of its packed `fetch()`.  The step protocol the kernels keep is stated in csrc/resident_step.h.  The MD drivers also
+take observers (observe.py: frames, g(r), MSD): launched behind the finish, checked by `run`, carried by the same `fetch()`.
 
 Also here, for `graph.GraphedMDStep.fetch` and `plugin/ase_interface` too: the one packed device-to-host copy with its one
 synchronisation (`fetch_packed`), the reaction to a list's flags (`list_flags_seen`) and the once-per-model NaN warning
@@ -66,13 +67,13 @@ class ResidentDriver(object):
 
     __slots__ = ("device", "model", "z", "n", "num_graphs", "_batch_h", "batch", "graph_ptr", "x", "x0", "v", "image",
                  "image0", "f_prev", "state", "log", "log_steps", "wrap", "inv_cell", "_inv_of", "step", "_logged", "_pending",
-                 "_host")
+                 "_host", "_observers")
     LOG_WIDTH = None                      # columns of a log row: the subclass's
 
     def _start(self, model, atomic_number, cell, pos, batch, num_graphs, capacity, log_steps, wrap, reference_compat, device,
-               **own):
-        """The constructor: the common state, the subclass's (`_own_state(**own)`), then the capture between its hooks.  The
-        state stays parked; the subclass unparks it."""
+               observers=None, **own):
+        """The constructor: the common state, the subclass's (`_own_state(**own)`), the observers' (`observers`: the MD
+        drivers'), then the capture between its hooks.  The state stays parked; the subclass unparks it."""
         from .graph import GraphedBatchMDStep, GraphedMDStep
         name = type(self).__name__
         dev = torch.device(device) if device is not None else (pos.device if torch.is_tensor(pos) else torch.device("cuda:0"))
@@ -104,9 +105,13 @@ class ResidentDriver(object):
         self._logged = self._pending = 0  # `fetch`: the step its last snapshot stood at; `run`, `fetch`: replays enqueued since
         self._host = None                 # `fetch`: the pinned buffer
         self._own_state(**own)
-        # the captured step: advance -> the graphed step's own _eager() -> finish
+        self._observers = tuple(observers or ())    # observe.py's Frames / RDF / MSD behind the finish (md.DeviceMD: observers=)
+        for ob in self._observers:
+            ob._bind(self, cell)
+        # the captured step: advance -> the graphed step's own _eager() -> finish (-> the observers, where there are any)
         cell_t = None if cell is None else torch.as_tensor(cell).detach().float().to(dev).contiguous()
-        kw = dict(capacity=capacity, reference_compat=reference_compat, hooks=(self._advance, self._finish))
+        kw = dict(capacity=capacity, reference_compat=reference_compat,
+                  hooks=(self._advance, self._finish_observed if self._observers else self._finish))
         kw.update(self._step_options(batch is None))
         if batch is None:
             if cell_t is None:
@@ -114,6 +119,13 @@ class ResidentDriver(object):
             self.step = GraphedMDStep(model, self.z, cell_t.reshape(3, 3), self.x.float(), **kw)
         else:
             self.step = GraphedBatchMDStep(model, self.z, cell_t, self.x.float(), self.batch, B, **kw)
+
+    def _finish_observed(self, step, out):
+        """The capture's second hook where there are observers: the finish, then each observer's launches (they read the
+        state the finish's commit kernel left)."""
+        self._finish(step, out)
+        for ob in self._observers:
+            ob._launch(self, step)
 
     # ---- what the two hooks of the capture check and pass on ----------------------------------------------------------------
     def _pos_input(self, step):
@@ -172,6 +184,8 @@ class ResidentDriver(object):
         if self._pending + n > self.log_steps:
             raise RuntimeError("%s.run(%d) would overwrite log rows not fetched yet (%d pending, log_steps=%d): fetch() "
                                "first" % (name, n, self._pending, self.log_steps))
+        for ob in self._observers:
+            ob._check_run(self, n)
         replay = self.step.graph.replay
         for _ in range(n):
             replay()
@@ -193,8 +207,22 @@ class ResidentDriver(object):
         rows = self._pending
         extras = [t.double().reshape(-1) for t in self._fetch_extras()]
         o = 4 + sum(t.numel() for t in extras)
-        h, self._host = fetch_packed(self._pack(extras, rows), self._host, o + 12 * self.n + self.log.numel())
-        return self._unpack(h, o, rows)
+        packed, room = self._pack(extras, rows), o + 12 * self.n + self.log.numel()
+        if not self._observers:
+            h, self._host = fetch_packed(packed, self._host, room)
+            return self._unpack(h, o, rows)
+        # the observers' parts ride behind the driver's own in the same copy: their words, counts and the ring entries not
+        # fetched yet
+        own = packed.numel()
+        packed = torch.cat([packed] + [t for ob in self._observers for t in ob._parts(self)])
+        h, self._host = fetch_packed(packed, self._host, max(room, packed.numel()))
+        s = self._unpack(h[:own], o, rows)
+        s.observers = []
+        for ob in self._observers:
+            entry, used = ob._read(self, h[own:])
+            s.observers.append(entry)
+            own += used
+        return s
 
     def _pack(self, extras, rows):
         """state | the subclass's extras | x | image | v | f_prev | the `rows` log rows not fetched yet, as one float64 array."""

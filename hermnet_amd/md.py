@@ -53,7 +53,9 @@ class DeviceMD(ResidentDriver):
     evaluation.
 
     `fetch()`: the base's snapshot, `velocities` in A/fs, `log` [rows,B,3] = (E_pot, E_kin, edges found) per time step.
-    `resume()`: the noise of a step depends on (seed, step, atom) alone, so a resumed run equals an uninterrupted one."""
+    `resume()`: the noise of a step depends on (seed, step, atom) alone, so a resumed run equals an uninterrupted one.
+    `observers`: a list of `observe.Frames` / `RDF` / `MSD` -- what they record arrives as `observers` [list] of the snapshot,
+    in the same packed copy (hermnet_amd/observe.py)."""
 
     __slots__ = ("dt", "seed", "temperature", "friction", "flags", "_m", "_free", "v0", "ke_atom", "kick", "half_mass", "c1",
                  "sigma")
@@ -61,14 +63,14 @@ class DeviceMD(ResidentDriver):
 
     def __init__(self, model, atomic_number, cell, pos, masses, dt, velocities=None, temperature=None, friction=None, seed=0,
                  batch=None, num_graphs=None, capacity=None, log_steps=4096, wrap=True, reference_compat=False,
-                 device=None):
+                 device=None, observers=None):
         self.dt = float(dt)                               # the time step in fs
         self.seed = int(seed) & (2 ** 64 - 1)             # the noise's key
         if not (self.dt > 0.0) or int(log_steps) < 1:
             raise ValueError("DeviceMD: dt > 0 and log_steps >= 1")
         self.temperature, self.friction = temperature, friction       # as given
         self._start(model, atomic_number, cell, pos, batch, num_graphs, capacity, log_steps, wrap, reference_compat, device,
-                    masses=masses)
+                    observers=observers, masses=masses)
         if velocities is not None:
             self.set_velocities(velocities)
         self._unpark()

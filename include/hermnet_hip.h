@@ -19,7 +19,7 @@
  * ABI version 13 (`HN_ABI_VERSION` below, returned by `hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table), then hermnet_neb_finish with its hermnet_host_neb_finish twin (the device-resident nudged elastic band), then hermnet_remd_finish with its hermnet_host_remd_finish twin (replica exchange), then hermnet_pimd_advance / _finish with their hermnet_host_pimd_* twins (ring-polymer path-integral MD) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table), then hermnet_neb_finish with its hermnet_host_neb_finish twin (the device-resident nudged elastic band), then hermnet_remd_finish with its hermnet_host_remd_finish twin (replica exchange), then hermnet_pimd_advance / _finish with their hermnet_host_pimd_* twins (ring-polymer path-integral MD), then hermnet_observe_frames / _msd / _rdf with their hermnet_host_observe_* twins (MD observers behind a driver's finish) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -1247,6 +1247,58 @@ int hermnet_host_pimd_finish(int num_atoms, int num_graphs, const int* graph_ptr
                              float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
                              double* ke_atom_host, const double* spring_c_host, const double* centroid_host, double* log_host,
                              long log_steps, long* state_host);
+
+/* MD observers behind a resident MD driver's finish (added within ABI v13: new entry points only; hermnet_amd/observe.py:
+ * Frames, MSD, RDF; csrc/observe_kernels.hip, observe_step.h).  Launched behind the driver's commit kernel, so they read the
+ * NEW state.  Each observer owns obs [4] int64 = (last sampled step, samples taken, reserved, reserved), obs[0] = -1 at the
+ * start.  A sample is DUE iff state[1] == 0 and state[0] % stride == 0 and state[0] > obs[0]: the prime of a construction
+ * samples the start configuration as step 0; void steps, halted and parked replays and the prime behind a resume sample
+ * nothing.  Not due: nothing is written.  Each call is its worker launch and one single-workgroup launch that alone writes obs
+ * (obs[0] = step, obs[1] += 1) and the ring's steps[slot].  No float atomics; the counts and sums are reproducible bit for bit.
+ *
+ * hermnet_observe_frames  slot = obs[1] % frames:  positions[slot,i,:] = float(x[i,:]);  velocities[slot] = float(v) and
+ *   images[slot] = image where given (v / velocities and image / images are NULL together);  cells[slot] = cell [B,3,3], the
+ *   step's float32 cell (NULL: open structures);  steps[slot] = step.
+ * hermnet_observe_msd     species [N] int32 in [0, num_species).  The first sample stores x_origin, image_origin = x, image.
+ *   d = (x - x_origin) + (image - image_origin) cell, with the current float32 cell widened (cell NULL: d = x - x_origin);
+ *   sums[slot,g,s,:] = (sum d_x, sum d_y, sum d_z, sum |d|^2) over the atoms of species s of graph g in float64 in
+ *   hermnet_md_finish's fixed order, atoms of other species skipped in place;  slot = obs[1] % rows;  steps[slot] = step.
+ * hermnet_observe_rdf     per atom s_k = (x0 inv[k] + x1 inv[3+k]) + x2 inv[6+k];  per pair i < j of one graph ds = s_i - s_j,
+ *   ds -= floor(ds + 0.5), d = ds cell as (a + b) + c, r2 = (d0^2 + d1^2) + d2^2, all float64 (cell and inv_cell NULL: s = x,
+ *   d = ds).  The pair counts in bin b iff edge2[b] <= r2 < edge2[b+1] (edge2 [bins+1] ascending from 0, made by the caller),
+ *   once, in counts[slot, p, b] with p = a S - a (a - 1) / 2 + (b' - a) for its species a <= b' of S = num_species, and
+ *   slot = slot_of[g] (clamped to [0, slots)) or g where slot_of is NULL.  A graph with r_max2 |column k of inv_cell|^2 > 1/4
+ *   for some k -- the rounding is the minimum image only below half the smallest cell height -- is not counted in that
+ *   sample: skipped[slot] += 1; otherwise samples[slot] += 1 and volume_sum[slot] += |det cell|, in the order of the graphs.
+ *   work [num_work,3] int32 = (graph, tile_i, tile_j >= tile_i) over 256-atom tiles of every graph, made by the caller; one
+ *   256-lane workgroup per entry, a uint32 histogram in LDS, integer atomic adds of its nonzero bins to counts.
+ * The hermnet_host_observe_* twins run the same text on HOST pointers (no stream): the same integers and the same bits.
+ * HN_ERR_BAD_ARG: a NULL pointer that is needed, num_graphs < 1, stride < 1, frames / rows / slots < 1, num_species < 1,
+ *   bins < 1 or > 1024, num_species (num_species + 1) / 2 x bins > 8192, r_max2 <= 0, slots < num_graphs without slot_of; the
+ *   host twin also refuses a work list that names a graph that does not exist or tile_j < tile_i. */
+int hermnet_observe_frames(int num_atoms, int num_graphs, long stride, long frames, const double* x, const double* v,
+                           const int* image, const float* cell, const long* state, long* obs, long* steps, float* positions,
+                           float* velocities, int* images, float* cells, void* stream);
+int hermnet_observe_msd(int num_atoms, int num_graphs, int num_species, long stride, long rows, const int* graph_ptr,
+                        const int* species, const double* x, const int* image, const float* cell, const long* state, long* obs,
+                        long* steps, double* x_origin, int* image_origin, double* sums, void* stream);
+int hermnet_observe_rdf(int num_atoms, int num_graphs, int num_species, int bins, long slots, long stride, double r_max2,
+                        const int* graph_ptr, const int* species, const double* x, const float* cell, const double* inv_cell,
+                        const long* slot_of, const double* edge2, const int* work, int num_work, const long* state, long* obs,
+                        long* counts, long* samples, long* skipped, double* volume_sum, void* stream);
+int hermnet_host_observe_frames(int num_atoms, int num_graphs, long stride, long frames, const double* x_host,
+                                const double* v_host, const int* image_host, const float* cell_host, const long* state_host,
+                                long* obs_host, long* steps_host, float* positions_host, float* velocities_host,
+                                int* images_host, float* cells_host);
+int hermnet_host_observe_msd(int num_atoms, int num_graphs, int num_species, long stride, long rows, const int* graph_ptr_host,
+                             const int* species_host, const double* x_host, const int* image_host, const float* cell_host,
+                             const long* state_host, long* obs_host, long* steps_host, double* x_origin_host,
+                             int* image_origin_host, double* sums_host);
+int hermnet_host_observe_rdf(int num_atoms, int num_graphs, int num_species, int bins, long slots, long stride, double r_max2,
+                             const int* graph_ptr_host, const int* species_host, const double* x_host, const float* cell_host,
+                             const double* inv_cell_host, const long* slot_of_host, const double* edge2_host,
+                             const int* work_host, int num_work, const long* state_host, long* obs_host, long* counts_host,
+                             long* samples_host, long* skipped_host, double* volume_sum_host);
 
 #ifdef __cplusplus
 }
