@@ -2,7 +2,8 @@
 // twins (hermnet_host_md_advance / _finish) and -- transcribed operation by operation -- the numpy float64 references of
 // tests/test_md_host.py.  Only IEEE +, x and floor on doubles, one rounding each (contraction off), in the order written:
 // device, host and numpy agree bit for bit.  Everything that needs exp / sqrt / a division (kick, c1, sigma, the inverse
-// cell) is made once on the host in float64; log / cos / sqrt appear in the Gaussian noise alone (md_gaussians).
+// cell) is made once on the host in float64; log / cos / sqrt appear in the Gaussian noise alone (md_gaussians).  Behind
+// the arithmetic: the advance's arguments, their check, and what one atom's advance and one atom's noise are.
 #ifndef HERMNET_MD_STEP_H
 #define HERMNET_MD_STEP_H
 
@@ -68,5 +69,84 @@ HN_HD inline double md_finish_atom(double v[3], const float f[3], double kick, d
   for (int k = 0; k < 3; ++k) v[k] = v[k] + kick * (double)f[k];
   return half_mass * ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
 }
+
+// ---- the advance of hermnet_md_advance and the noise of hermnet_md_noise, per atom (the kernels and the host twins loop) ----
+// In the unnamed namespace of the including source, as everything that names a kernel's argument type.
+namespace {
+
+struct MdAdvanceArgs {
+  int n, num_graphs, flags;
+  double *x, *v, *x0, *v0;
+  int *image, *image0;
+  const float* f_prev;
+  const double *kick, *c1, *sigma;
+  const long* batch;
+  const float* cell;
+  const double* inv_cell;
+  float* pos32;
+  const long* state;
+  double dt;
+  uint64_t seed;
+};
+
+inline bool md_advance_args_ok(const MdAdvanceArgs& a) {
+  if (a.n < 0 || a.num_graphs < 1 || (a.flags & ~(HN_MD_LANGEVIN | HN_MD_WRAP))) return false;
+  if (a.n == 0) return true;
+  if (!a.x || !a.v || !a.x0 || !a.v0 || !a.image || !a.image0 || !a.f_prev || !a.kick || !a.pos32 || !a.state) return false;
+  if ((a.flags & HN_MD_LANGEVIN) && (!a.c1 || !a.sigma)) return false;
+  if ((a.flags & HN_MD_WRAP) && (!a.cell || !a.inv_cell)) return false;
+  return true;
+}
+
+HN_HD inline void md_advance_one(const MdAdvanceArgs& a, int i, long step, long mode) {
+  double x[3], v[3];
+  for (int k = 0; k < 3; ++k) x[k] = a.x[3 * (size_t)i + k];
+  if (mode == 0) {
+    int image[3];
+    float f[3];
+    for (int k = 0; k < 3; ++k) {
+      v[k] = a.v[3 * (size_t)i + k];
+      image[k] = a.image[3 * (size_t)i + k];
+      f[k] = a.f_prev[3 * (size_t)i + k];
+      a.x0[3 * (size_t)i + k] = x[k];
+      a.v0[3 * (size_t)i + k] = v[k];
+      a.image0[3 * (size_t)i + k] = image[k];
+    }
+    const long g = hn_graph_of(a.batch, i, a.num_graphs);
+    const int langevin = a.flags & HN_MD_LANGEVIN;
+    double xi[3] = {0.0, 0.0, 0.0};
+    if (langevin) {
+      uint32_t w[8];
+      md_noise_words(a.seed, (uint64_t)step, (uint32_t)i, w);
+      md_gaussians(w, xi);
+    }
+    md_advance_atom(x, v, f, a.kick[i], a.dt, langevin, langevin ? a.c1[g] : 0.0, langevin ? a.sigma[i] : 0.0, xi);
+    if (a.flags & HN_MD_WRAP) {
+      double cell[9], inv[9];
+      hn_load_cell(a.cell, a.inv_cell, g, cell, inv);
+      md_wrap_atom(x, image, cell, inv);
+    }
+    for (int k = 0; k < 3; ++k) {
+      a.x[3 * (size_t)i + k] = x[k];
+      a.v[3 * (size_t)i + k] = v[k];
+      a.image[3 * (size_t)i + k] = image[k];
+    }
+  }
+  for (int k = 0; k < 3; ++k) a.pos32[3 * (size_t)i + k] = (float)x[k];
+}
+
+// Atom i's eight words and three Gaussians of (seed, step) into the caller's arrays (either may be null).
+HN_HD inline void md_noise_one(uint64_t seed, uint64_t step, int i, uint32_t* words, double* gauss) {
+  uint32_t w[8];
+  double xi[3];
+  md_noise_words(seed, step, (uint32_t)i, w);
+  md_gaussians(w, xi);
+  if (words)
+    for (int k = 0; k < 8; ++k) words[8 * (size_t)i + k] = w[k];
+  if (gauss)
+    for (int k = 0; k < 3; ++k) gauss[3 * (size_t)i + k] = xi[k];
+}
+
+}  // namespace
 
 #endif  // HERMNET_MD_STEP_H

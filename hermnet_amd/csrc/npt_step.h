@@ -2,11 +2,13 @@
 // the device kernels, their host twin (hermnet_host_md_finish_npt) and -- transcribed operation by operation -- the numpy
 // float64 reference of tests/npt_reference.py.  Only IEEE +, -, x, / and comparisons on doubles, one rounding each
 // (contraction off), in the order written: device, host and numpy agree bit for bit.  3x3 matrices are row-major [9]; the
-// rows of a cell are the lattice vectors, so a coordinate scales as the row vector x mu.
+// rows of a cell are the lattice vectors, so a coordinate scales as the row vector x mu.  Behind the arithmetic: the
+// barostat's argument struct, its check and what one graph and one atom of a committed step do (md_finish.h's skeleton
+// around them is the finish).
 #ifndef HERMNET_NPT_STEP_H
 #define HERMNET_NPT_STEP_H
 
-#include "md_step.h"
+#include "md_finish.h"
 
 // The six entries of a symmetric 3x3 tensor, in the order the kinetic sums are taken.
 #define HN_NPT_XX 0
@@ -125,5 +127,75 @@ HN_HD inline void npt_scale_atom(double x[3], const double mu[9]) {
   const double x0 = x[0], x1 = x[1], x2 = x[2];
   for (int j = 0; j < 3; ++j) x[j] = (x0 * mu[j] + x1 * mu[3 + j]) + x2 * mu[6 + j];
 }
+
+// ---- the barostat's part of hermnet_md_finish_npt: its arguments, and what one graph and one atom do -------------------------
+namespace {
+
+struct NptArgs {
+  MdFinishArgs m;
+  const long* batch;
+  const float* virial;
+  const double *pressure, *coupling_c;
+  double* cell64;
+  float* cell32;
+  double *inv_cell, *mu;
+  long* clamped;
+  int coupling, mask;
+  double max_strain;
+};
+
+inline bool npt_args_ok(const NptArgs& a) {
+  if (!md_finish_args_ok(a.m)) return false;
+  if (a.coupling != HN_MD_BARO_ISOTROPIC && a.coupling != HN_MD_BARO_AXES && a.coupling != HN_MD_BARO_FULL) return false;
+  if ((a.mask & ~7) || !(a.max_strain > 0.0)) return false;
+  return a.virial && a.pressure && a.coupling_c && a.cell64 && a.cell32 && a.inv_cell && a.mu && a.clamped;
+}
+
+// Graph g of a committed step, from its six kinetic sums: mu, the new cell in its three forms and the log row of width 5
+// (E_pot, E_kin, edges found, the pressure mu was made from, the volume before the scaling).
+HN_HD inline void npt_graph_one(const NptArgs& a, long step, int g, const double kin[6]) {
+  float w[9], cell32[9];
+  double cell[9], mu[9], inv[9], e_kin, pressure, volume;
+  for (int k = 0; k < 9; ++k) {
+    w[k] = a.virial[9 * (size_t)g + k];
+    cell[k] = a.cell64[9 * (size_t)g + k];
+  }
+  const int acted = npt_graph(kin, w, a.coupling_c[g], a.pressure[g], a.coupling, a.mask, a.max_strain, cell, mu, cell32, inv,
+                              &e_kin, &pressure, &volume);
+  for (int k = 0; k < 9; ++k) {
+    a.cell64[9 * (size_t)g + k] = cell[k];
+    a.cell32[9 * (size_t)g + k] = cell32[k];
+    a.inv_cell[9 * (size_t)g + k] = inv[k];
+    a.mu[9 * (size_t)g + k] = mu[k];
+  }
+  if (acted) a.clamped[g] = a.clamped[g] + 1;
+  double* row = hn_log_row(a.m.log, step, a.m.log_steps, a.m.num_graphs, g, 5);
+  row[0] = (double)a.m.energy[g];
+  row[1] = e_kin;
+  row[2] = (double)a.m.total[0];
+  row[3] = pressure;
+  row[4] = volume;
+}
+
+HN_HD inline void npt_kinetic_of(const NptArgs& a, int i, double* s) {
+  double v[3];
+  for (int k = 0; k < 3; ++k) v[k] = a.m.v[3 * (size_t)i + k];
+  npt_kinetic_terms(v, a.m.half_mass[i], s);
+}
+
+// Atom i of a committed step (held atoms too): x <- x mu of its graph, pos32 = float(x).
+HN_HD inline void npt_scale_one(const NptArgs& a, int i) {
+  const long g = hn_graph_of(a.batch, i, a.m.num_graphs);
+  double mu[9], x[3];
+  for (int k = 0; k < 9; ++k) mu[k] = a.mu[9 * g + k];
+  for (int k = 0; k < 3; ++k) x[k] = a.m.x[3 * (size_t)i + k];
+  npt_scale_atom(x, mu);
+  for (int k = 0; k < 3; ++k) {
+    a.m.x[3 * (size_t)i + k] = x[k];
+    a.m.pos32[3 * (size_t)i + k] = (float)x[k];
+  }
+}
+
+}  // namespace
 
 #endif  // HERMNET_NPT_STEP_H

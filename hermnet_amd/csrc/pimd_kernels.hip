@@ -2,8 +2,9 @@
 // remd_kernels.hip: there the advance stayed and the finish was replaced; here hermnet_pimd_advance takes the place of
 // hermnet_md_advance in front of the search -- the beads of a ring are coupled by harmonic springs, which it integrates
 // exactly in normal modes --, and hermnet_pimd_finish is hermnet_md_finish with a wider log row: md_finish.h's per-atom half
-// and commit around a per-bead kernel that takes E_kin, the spring energy and the centroid-virial sum in the canonical order.
-// A replay has as many launches as DeviceMD's: one in front, three behind.
+// and commit, kernels included (md_finish_atoms_kernel, md_commit_kernel), around a per-bead kernel that takes E_kin, the
+// spring energy and the centroid-virial sum in the canonical order.  A replay has as many launches as DeviceMD's: one in
+// front, three behind.
 //
 // The arithmetic, the phases of a tile and the LDS layout are pimd_step.h's, shared with the host twins at the end of this
 // file.  One workgroup of 256 lanes holds a tile of 256 / P atoms x P lanes; the beads of an atom never leave their tile, so
@@ -35,27 +36,11 @@ __global__ __launch_bounds__(256) void pimd_advance_kernel(PimdAdvanceArgs a) {
   pimd_store(a, first, l, sb, sm);
 }
 
-__global__ __launch_bounds__(256) void pimd_finish_atoms_kernel(PimdFinishArgs a) {
-  const long halted = a.m.state[HN_STATE_CODE], mode = a.m.state[HN_STATE_MODE];
-  if (halted != 0) return;
-  const long code = hn_step_code(a.m.energy, a.m.num_graphs, a.m.total, a.m.capacity);
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < a.m.n) md_finish_one(a.m, i, code, mode);
-}
-
 __global__ __launch_bounds__(256) void pimd_log_kernel(PimdFinishArgs a) {
   __shared__ double part[3][256];
-  const long step = a.m.state[HN_STATE_STEP], halted = a.m.state[HN_STATE_CODE], mode = a.m.state[HN_STATE_MODE];
-  if (halted != 0 || mode != 0) return;
-  if (hn_step_code(a.m.energy, a.m.num_graphs, a.m.total, a.m.capacity) != 0) return;
+  long step;
+  if (!md_committed(a.m, &step)) return;
   pimd_log_bead(a, step, blockIdx.x, part);
-}
-
-__global__ __launch_bounds__(64) void pimd_commit_kernel(PimdFinishArgs a) {
-  const long step = a.m.state[HN_STATE_STEP], halted = a.m.state[HN_STATE_CODE], mode = a.m.state[HN_STATE_MODE];
-  if (halted != 0) return;
-  const long code = hn_step_code(a.m.energy, a.m.num_graphs, a.m.total, a.m.capacity);
-  if (threadIdx.x == 0) md_commit(a.m.state, step, code, mode);
 }
 
 // What the host twins can check and the device entry points cannot: the beads tile the atoms in equal ranges.
@@ -93,9 +78,9 @@ extern "C" int hermnet_pimd_finish(int num_atoms, int num_graphs, const int* gra
   if (!pimd_finish_args_ok(a)) return HN_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (num_atoms > 0)
-    hipLaunchKernelGGL(pimd_finish_atoms_kernel, dim3((unsigned)((num_atoms + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(md_finish_atoms_kernel<>, dim3((unsigned)((num_atoms + 255) / 256)), dim3(256), 0, s, a.m);
   hipLaunchKernelGGL(pimd_log_kernel, dim3((unsigned)num_graphs), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(pimd_commit_kernel, dim3(1), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(md_commit_kernel<>, dim3(1), dim3(64), 0, s, a.m);
   return hipGetLastError() == hipSuccess ? HN_OK : HN_ERR_LAUNCH;
 }
 
@@ -142,14 +127,9 @@ extern "C" int hermnet_host_pimd_finish(int num_atoms, int num_graphs, const int
                              ke_atom_host, log_host, log_steps, state_host},
                             num_graphs > 0 ? num_atoms / num_graphs : 0, spring_c_host, centroid_host};
   if (!pimd_finish_args_ok(a) || !pimd_host_layout_ok(graph_ptr_host, num_graphs, a.n_rep)) return HN_ERR_BAD_ARG;
-  const long step = state_host[HN_STATE_STEP], mode = state_host[HN_STATE_MODE];
-  if (state_host[HN_STATE_CODE] != 0) return HN_OK;
-  const long code = hn_step_code(energy_host, num_graphs, total_host, capacity);
-  for (int i = 0; i < num_atoms; ++i) md_finish_one(a.m, i, code, mode);
-  if (code == 0 && mode == 0) {
+  md_host_finish(a.m, [&](long step) {
     double part[3][256];
     for (int j = 0; j < num_graphs; ++j) pimd_log_bead(a, step, j, part);
-  }
-  md_commit(state_host, step, code, mode);
+  });
   return HN_OK;
 }

@@ -4,10 +4,11 @@
 // committed step, one attempt of the ladder -- the decisions, the velocity rescaling and the new thermostat coefficients
 // never leave the device.
 //
-// The arithmetic and the text of the launches are remd_step.h's (md_finish.h's for the per-atom half), shared with the host
-// twin at the end of this file.  The replicas are COUPLED -- a decision needs two replicas' energies -- so, as in
-// neb_kernels.hip, what one workgroup needs of another's work it reads in the NEXT launch:
-//   1. remd_finish_atoms_kernel   one lane per atom: md_finish_one (second kick, ke_atom; restore on a void step; a prime's copy)
+// The arithmetic and the text of the launches are remd_step.h's, around md_finish.h's skeleton (the per-atom half and its
+// kernel, md_committed, E_kin), shared with the host twin at the end of this file.  The replicas are COUPLED -- a decision
+// needs two replicas' energies -- so, as in neb_kernels.hip, what one workgroup needs of another's work it reads in the NEXT
+// launch:
+//   1. md_finish_atoms_kernel     md_finish.h's, unchanged: second kick, ke_atom; restore on a void step; a prime's copy
 //   2. remd_decide_kernel         one workgroup, a lane per pair: rung_new, vscale, outcome (scratch) from rung / replica_at
 //   3. remd_apply_kernel          one workgroup per replica: E_kin, the log row; where its rung changed, v and sigma
 //   4. remd_commit_kernel         one workgroup: rung, replica_at, attempts, accepts, then state -- the single writer
@@ -19,37 +20,24 @@
 
 namespace {
 
-__host__ __device__ inline long remd_code(const RemdArgs& a) {
-  return hn_step_code(a.m.energy, a.m.num_graphs, a.m.total, a.m.capacity);
-}
-
-__global__ __launch_bounds__(256) void remd_finish_atoms_kernel(RemdArgs a) {
-  const long halted = a.m.state[HN_STATE_CODE], mode = a.m.state[HN_STATE_MODE];
-  if (halted != 0) return;
-  const long code = remd_code(a);
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < a.m.n) md_finish_one(a.m, i, code, mode);
-}
-
 __global__ __launch_bounds__(256) void remd_decide_kernel(RemdArgs a) {
-  const long step = a.m.state[HN_STATE_STEP], halted = a.m.state[HN_STATE_CODE], mode = a.m.state[HN_STATE_MODE];
-  if (halted != 0 || mode != 0) return;
-  if (remd_code(a) != 0) return;
+  long step;
+  if (!md_committed(a.m, &step)) return;
   remd_decide(a, step, threadIdx.x, 256);
 }
 
 __global__ __launch_bounds__(256) void remd_apply_kernel(RemdArgs a) {
   __shared__ double part[1][256];
-  const long step = a.m.state[HN_STATE_STEP], halted = a.m.state[HN_STATE_CODE], mode = a.m.state[HN_STATE_MODE];
-  if (halted != 0 || mode != 0) return;
-  if (remd_code(a) != 0) return;
+  long step;
+  if (!md_committed(a.m, &step)) return;
   remd_apply_replica(a, step, blockIdx.x, part);
 }
 
 __global__ __launch_bounds__(256) void remd_commit_kernel(RemdArgs a) {
   const long step = a.m.state[HN_STATE_STEP], halted = a.m.state[HN_STATE_CODE], mode = a.m.state[HN_STATE_MODE];
   if (halted != 0) return;
-  remd_commit(a, step, remd_code(a), mode, threadIdx.x, 256);
+  const long code = hn_step_code(a.m.energy, a.m.num_graphs, a.m.total, a.m.capacity);
+  remd_commit(a, step, code, mode, threadIdx.x, 256);
 }
 
 // What the host twin can check and the device entry point cannot (its pointers are the device's): the replicas tile the
@@ -79,7 +67,7 @@ extern "C" int hermnet_remd_finish(int num_atoms, int num_graphs, const int* gra
   if (!remd_args_ok(a)) return HN_ERR_BAD_ARG;
   hipStream_t s = (hipStream_t)stream;
   if (num_atoms > 0)
-    hipLaunchKernelGGL(remd_finish_atoms_kernel, dim3((unsigned)((num_atoms + 255) / 256)), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(md_finish_atoms_kernel<>, dim3((unsigned)((num_atoms + 255) / 256)), dim3(256), 0, s, a.m);
   hipLaunchKernelGGL(remd_decide_kernel, dim3(1), dim3(256), 0, s, a);
   hipLaunchKernelGGL(remd_apply_kernel, dim3((unsigned)num_graphs), dim3(256), 0, s, a);
   hipLaunchKernelGGL(remd_commit_kernel, dim3(1), dim3(256), 0, s, a);
@@ -105,15 +93,13 @@ extern "C" int hermnet_host_remd_finish(int num_atoms, int num_graphs, const int
                       down_host, sigma_table_host, sigma_host, rung_host, replica_at_host, rung_new_host, vscale_host,
                       outcome_host, attempts_host, accepts_host};
   if (!remd_args_ok(a) || !remd_host_layout_ok(a)) return HN_ERR_BAD_ARG;
-  const long step = state_host[HN_STATE_STEP], mode = state_host[HN_STATE_MODE];
-  if (state_host[HN_STATE_CODE] != 0) return HN_OK;
-  const long code = remd_code(a);
-  for (int i = 0; i < num_atoms; ++i) md_finish_one(a.m, i, code, mode);
-  if (code == 0 && mode == 0) {
-    double part[1][256];
-    remd_decide(a, step, 0, 1);
-    for (int g = 0; g < num_graphs; ++g) remd_apply_replica(a, step, g, part);
-  }
-  remd_commit(a, step, code, mode, 0, 1);
+  md_host_finish(
+      a.m,
+      [&](long step) {
+        double part[1][256];
+        remd_decide(a, step, 0, 1);
+        for (int g = 0; g < num_graphs; ++g) remd_apply_replica(a, step, g, part);
+      },
+      [&](long step, long code, long mode) { remd_commit(a, step, code, mode, 0, 1); });
   return HN_OK;
 }

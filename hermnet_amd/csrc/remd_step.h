@@ -111,12 +111,12 @@ HN_HD inline void remd_decide(const RemdArgs& a, long step, int first, int strid
 HN_HD inline void remd_apply_replica(const RemdArgs& a, long step, int g, double (*part)[256]) {
 #pragma clang fp contract(off)
   const int lo = hn_graph_lo(a.m.graph_ptr, g), hi = hn_graph_hi(a.m.graph_ptr, g, a.m.n);
-  hn_canonical_sums<1, -1>(lo, hi, part, [&](int i, double* s) { s[0] = s[0] + a.m.ke_atom[i]; });
+  const double e_kin = md_kinetic_sum(a.m, g, part);
   const long was = a.rung[g], now = a.rung_new[g];
   if (hn_lead_lane()) {
     double* row = hn_log_row(a.m.log, step, a.m.log_steps, a.m.num_graphs, g, 5);
     row[0] = (double)a.m.energy[g];
-    row[1] = part[0][0];
+    row[1] = e_kin;
     row[2] = (double)a.m.total[0];
     row[3] = (double)was;
     row[4] = (double)now;

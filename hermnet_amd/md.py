@@ -27,6 +27,7 @@ virial kernels, and `hermnet_md_finish_npt` scales the cell and the coordinates 
 Out of scope: for `DeviceMD` the cell is constant during `run` (barostat: `DeviceNPT`); for both, constraints other than an
 infinite mass (= a fixed atom), atom shards, HTNet, more than one time step per replay."""
 import math
+import types
 
 import numpy as np
 import torch
@@ -39,6 +40,34 @@ KB = 8.617333262e-5                       # eV / K
 ASE_TIME_FS = math.sqrt(AMU_A2_FS2_TO_EV)   # ASE's time unit in fs: v [A/fs] = v_ase / 10.18051
 GPA = 1.0 / 160.2176634                   # 1 GPa in eV / A^3
 HN_MD_BARO = {"isotropic": _lib.HN_MD_BARO_ISOTROPIC, "axes": _lib.HN_MD_BARO_AXES, "full": _lib.HN_MD_BARO_FULL}
+
+
+def stack_atoms(members, who, noun, device, cells_float64=False):
+    """The list `members` of ASE-like structures (anything with `positions`, `numbers`, `cell`, `pbc`, `get_masses()`,
+    `get_velocities()`; ASE units: A and A / (10.18051 fs)) as one batch for the MD drivers: a namespace of `z` [N] and
+    `batch` [N] on `device`, `cell` [B,3,3] (None: every member is open; float64 on the host where `cells_float64`, else the
+    step's float32 on the device), `pos` [N,3], `masses` [N] and `velocities` [N,3] in A/fs (None: no member has any; zeros
+    for a member without) float64 on the host, and `counts`, the members' atom counts.  RuntimeError in the name of `who`
+    unless the `noun` ("replicas", "beads", ...) are all periodic in three directions or all open."""
+    periodic = [bool(np.all(np.asarray(a.pbc))) for a in members]
+    if not all(periodic) and any(np.any(np.asarray(a.pbc)) for a in members):
+        raise RuntimeError("%s: %s periodic in all three directions, or all open" % (who, noun))
+    counts = [len(a.positions) for a in members]
+    cell = None
+    if all(periodic):
+        cell = np.stack([np.asarray(a.cell, dtype=np.float64).reshape(3, 3) for a in members])
+        if not cells_float64:
+            cell = torch.as_tensor(cell).float().to(device)
+    vel = [a.get_velocities() for a in members]
+    v = None
+    if any(u is not None for u in vel):
+        v = np.concatenate([np.zeros((c, 3)) if u is None else np.asarray(u, dtype=np.float64) for u, c in zip(vel, counts)])
+        v = v / ASE_TIME_FS
+    return types.SimpleNamespace(
+        z=torch.as_tensor(np.concatenate([np.asarray(a.numbers) for a in members])).to(device), cell=cell,
+        pos=np.concatenate([np.asarray(a.positions, dtype=np.float64) for a in members]),
+        masses=np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in members]), velocities=v,
+        batch=torch.as_tensor(np.repeat(np.arange(len(members)), counts)).to(device), counts=counts)
 
 
 class DeviceMD(ResidentDriver):
@@ -99,22 +128,39 @@ class DeviceMD(ResidentDriver):
             self.flags |= HN_MD_LANGEVIN
 
     # ---- the two hooks of the capture ---------------------------------------------------------------------------------------
+    # (the blocks of arguments every driver of the family passes, in the order of the C boundary)
+    def _advance_atoms(self):
+        """The advance's eight per-atom pointers, x ... kick."""
+        P = _lib.ptr
+        return (P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick))
+
+    def _advance_cell(self, step):
+        """(flags with the wrap bit as the step's cell says, cell pointer, inverse-cell pointer)."""
+        wrap, cell, inv = self._cell_args(step)
+        return (self.flags | HN_MD_WRAP) if wrap else (self.flags & ~HN_MD_WRAP), cell, inv
+
+    def _finish_atoms(self, step):
+        """The finish's eleven per-atom pointers, x ... ke_atom; pos32 is the step's coordinate input."""
+        P = _lib.ptr
+        return (P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick),
+                P(self.half_mass), P(step.pos), P(self.ke_atom))
+
+    def _finish_tail(self):
+        """What ends every finish: log, log_steps, state, stream."""
+        return _lib.ptr(self.log), self.log_steps, _lib.ptr(self.state), torch.cuda.current_stream(self.device).cuda_stream
+
     def _advance(self, step):
         P = _lib.ptr
-        wrap, cell, inv = self._cell_args(step)
-        flags = (self.flags | HN_MD_WRAP) if wrap else (self.flags & ~HN_MD_WRAP)
-        _lib.call("hermnet_md_advance", self.n, self.num_graphs, flags, self.dt, self.seed, P(self.x), P(self.v), P(self.x0),
-                  P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick), P(self.c1), P(self.sigma),
-                  P(self.batch), cell, inv, P(self._pos_input(step)), P(self.state),
+        flags, cell, inv = self._advance_cell(step)
+        _lib.call("hermnet_md_advance", self.n, self.num_graphs, flags, self.dt, self.seed, *self._advance_atoms(), P(self.c1),
+                  P(self.sigma), P(self.batch), cell, inv, P(self._pos_input(step)), P(self.state),
                   torch.cuda.current_stream(self.device).cuda_stream)
 
     def _finish(self, step, out):
         P = _lib.ptr
         energy, forces, total = self._step_outputs(out)
         _lib.call("hermnet_md_finish", self.n, self.num_graphs, P(self.graph_ptr), P(forces), P(energy), P(total),
-                  int(step.capacity), P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image), P(self.image0),
-                  P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos), P(self.ke_atom), P(self.log), self.log_steps,
-                  P(self.state), torch.cuda.current_stream(self.device).cuda_stream)
+                  int(step.capacity), *self._finish_atoms(step), *self._finish_tail())
 
     def _unpark(self):
         """Clear the halt and evaluate the forces of the current coordinates with the captured graph (mode word 1: no kick,
@@ -148,26 +194,69 @@ class DeviceMD(ResidentDriver):
         self.v.sub_(vcm[b] * (m > 0).double()[:, None])
 
     # ---- ASE hand-off (duck-typed: ASE itself is not needed) --------------------------------------------------------------------
+    CELLS_FLOAT64 = False     # from_atoms: the cell goes on as float64 on the host; else as the step's float32, on the device
+
     @classmethod
     def from_atoms(cls, atoms, model, dt, device="cuda:0", **kw):
-        """`atoms`: anything with `positions`, `numbers`, `cell`, `pbc`, `get_masses()`, `get_velocities()` (ASE units: A and
-        A / (10.18051 fs))."""
-        if not np.all(np.asarray(atoms.pbc)):
-            raise RuntimeError("DeviceMD.from_atoms: a periodic structure (pbc in all three directions)")
+        """`atoms`: one periodic structure -- what `stack_atoms` takes (`DeviceNPT`: its cell is kept in float64)."""
         dev = torch.device(device)
-        v = atoms.get_velocities()
-        return cls(model, torch.as_tensor(np.asarray(atoms.numbers)).to(dev),
-                   torch.as_tensor(np.asarray(atoms.cell, dtype=np.float64).reshape(3, 3)).float().to(dev),
-                   np.asarray(atoms.positions, dtype=np.float64), np.asarray(atoms.get_masses(), dtype=np.float64), dt,
-                   velocities=None if v is None else np.asarray(v, dtype=np.float64) / ASE_TIME_FS, device=dev, **kw)
+        s = stack_atoms([atoms], cls.__name__ + ".from_atoms", "a structure", dev, cls.CELLS_FLOAT64)
+        if s.cell is None:
+            raise RuntimeError("%s.from_atoms: a periodic structure (pbc in all three directions)" % cls.__name__)
+        return cls(model, s.z, s.cell[0], s.pos, s.masses, dt, velocities=s.velocities, device=dev, **kw)
+
+    @staticmethod
+    def _write_atoms(atoms, positions, velocities):
+        """`positions` (A) and `velocities` (A/fs) into `atoms`, in ASE's units."""
+        atoms.positions = positions.copy()
+        atoms.set_velocities(velocities * ASE_TIME_FS)
 
     def to_atoms(self, atoms, snapshot=None):
         """Write positions (wrapped) and velocities (ASE units) of `snapshot` (default: a fetch()) into `atoms`; returns
         the snapshot."""
         s = snapshot if snapshot is not None else self.fetch()
-        atoms.positions = s.positions.copy()
-        atoms.set_velocities(s.velocities * ASE_TIME_FS)
+        self._write_atoms(atoms, s.positions, s.velocities)
         return s
+
+
+def same_copies(name, noun, atomic_number, cell, masses, batch_h, B):
+    """The atom count of one of the B graphs of a batch that must be copies of ONE system (`noun`: "replica", "bead");
+    ValueError in the name of the driver `name` for copies that differ in atom count, atomic numbers, masses or cell."""
+    z, m = np.asarray(torch.as_tensor(atomic_number).cpu()).reshape(-1), host_f64(masses).reshape(-1)
+    if len(batch_h) != len(z) or len(m) != len(z) or np.any(np.diff(batch_h) < 0):
+        raise ValueError("%s: atomic_number, masses and batch are [N], batch non-decreasing" % name)
+    ptr = np.searchsorted(batch_h, np.arange(B + 1))
+    differs = "%s: %s %%d differs from %s 0 in " % (name, noun, noun)
+    for g in range(1, B):
+        mine, first = slice(ptr[g], ptr[g + 1]), slice(ptr[0], ptr[1])
+        if ptr[g + 1] - ptr[g] != ptr[1] - ptr[0]:
+            raise ValueError((differs + "atom count (%d, %d): the %ss are copies of one system")
+                             % (g, ptr[g + 1] - ptr[g], ptr[1] - ptr[0], noun))
+        if np.any(z[mine] != z[first]):
+            raise ValueError((differs + "atomic numbers") % g)
+        if np.any(m[mine] != m[first]):
+            raise ValueError((differs + "masses") % g)
+    if cell is not None:
+        c = host_f64(cell).reshape(-1, 3, 3)
+        if len(c) != B:
+            raise ValueError("%s: cell is [B,3,3], one per %s" % (name, noun))
+        for g in range(1, B):
+            if np.any(c[g] != c[0]):
+                raise ValueError((differs + "cell") % g)
+    return int(ptr[1] - ptr[0])
+
+
+class CopiesMD(DeviceMD):
+    """What the drivers of B copies of ONE system share (`remd.DeviceREMD`: the replicas of a ladder; `pimd.DevicePIMD`: the
+    beads of a ring): copy g's atoms are the rows g n_rep .. (g + 1) n_rep of the batch.  The subclass's constructor sets
+    `n_rep` (from `same_copies`) in front of `DeviceMD`'s."""
+
+    __slots__ = ("n_rep",)
+
+    def _write_member(self, atoms, snapshot, g):
+        """Positions and velocities of copy `g` of `snapshot` into `atoms` (ASE units)."""
+        mine = slice(g * self.n_rep, (g + 1) * self.n_rep)
+        self._write_atoms(atoms, snapshot.positions[mine], snapshot.velocities[mine])
 
 
 def _det3(c):
@@ -267,10 +356,8 @@ class DeviceNPT(DeviceMD):
             raise RuntimeError("DeviceNPT: the step's cell must be a contiguous float32 [B,3,3]")
         _lib.call("hermnet_md_finish_npt", self.n, B, P(self.graph_ptr), P(self.batch), P(forces), P(energy), P(virial),
                   P(total), int(step.capacity), HN_MD_BARO[self.coupling], self.mask, self.max_strain, P(self.p0),
-                  P(self.coupling_c), P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image), P(self.image0),
-                  P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos), P(self.ke_atom), P(self.cell64), P(cell),
-                  P(self.inv_cell), P(self.mu), P(self.clamped), P(self.log), self.log_steps, P(self.state),
-                  torch.cuda.current_stream(self.device).cuda_stream)
+                  P(self.coupling_c), *self._finish_atoms(step), P(self.cell64), P(cell), P(self.inv_cell), P(self.mu),
+                  P(self.clamped), *self._finish_tail())
 
     def resume(self):
         """`DeviceMD.resume`, and the last accepted forces stay: they are those of the configuration BEFORE the last scaling
@@ -292,17 +379,7 @@ class DeviceNPT(DeviceMD):
         s.volume = np.abs(_det3(s.cell))
 
     # ---- ASE hand-off ---------------------------------------------------------------------------------------------------------
-    @classmethod
-    def from_atoms(cls, atoms, model, dt, device="cuda:0", **kw):
-        """As `DeviceMD.from_atoms`; the cell is taken in float64."""
-        if not np.all(np.asarray(atoms.pbc)):
-            raise RuntimeError("DeviceNPT.from_atoms: a periodic structure (pbc in all three directions)")
-        dev = torch.device(device)
-        v = atoms.get_velocities()
-        return cls(model, torch.as_tensor(np.asarray(atoms.numbers)).to(dev),
-                   np.asarray(atoms.cell, dtype=np.float64).reshape(3, 3), np.asarray(atoms.positions, dtype=np.float64),
-                   np.asarray(atoms.get_masses(), dtype=np.float64), dt,
-                   velocities=None if v is None else np.asarray(v, dtype=np.float64) / ASE_TIME_FS, device=dev, **kw)
+    CELLS_FLOAT64 = True                  # `_own_state` makes cell64 of it
 
     def to_atoms(self, atoms, snapshot=None):
         """`DeviceMD.to_atoms`, and the cell (one structure) -- written first and without moving the atoms: the positions

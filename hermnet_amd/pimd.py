@@ -40,9 +40,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._resident import HN_MD_LANGEVIN, HN_MD_WRAP, host_f64
-from .md import ASE_TIME_FS, KB, DeviceMD
-from .remd import DeviceREMD
+from ._resident import HN_MD_LANGEVIN, host_f64
+from .md import KB, CopiesMD, same_copies, stack_atoms
 
 HBAR = 0.6582119569                       # eV fs
 MAX_BEADS = 128                           # csrc/pimd_step.h: HN_PIMD_MAX_BEADS (a tile is 256 / P atoms x P lanes)
@@ -92,7 +91,7 @@ def ring_tables(beads, dt, temperature, mass, tau0=100.0, pile_lambda=1.0, therm
                                  sigma=np.ascontiguousarray(sigma), inv_beads=1.0 / P, spring_c=spring_c, omega_p=omega_p)
 
 
-class DevicePIMD(DeviceMD):
+class DevicePIMD(CopiesMD):
     """See the module docstring.  model, atomic_number [N], cell [B,3,3] (None: open structures; [3,3] with `batch=None`), pos
     [N,3], masses [N], dt, `batch` [N] with `num_graphs` = P, `seed`, `velocities`, `capacity`, `log_steps`, `wrap`,
     `reference_compat`, `device`: `DeviceMD`'s; the P graphs are the beads, a single structure with `batch=None` is P = 1.
@@ -106,7 +105,7 @@ class DevicePIMD(DeviceMD):
     `fetch()`: `DeviceMD`'s snapshot, `log` [rows,P,5] = (E_pot_j, E_kin_j, edges found, spring_j, vir_j) per time step with
     spring_j = sum_a 1/2 m_a omega_P^2 |x_(j,a) - x_(j+1,a)|^2 and vir_j = sum_a (x_(j,a) - centroid_a) . f_(j,a)."""
 
-    __slots__ = ("beads", "n_rep", "tau0", "pile_lambda", "thermostat", "tables", "cmat", "cs", "sw", "ws", "pc1", "psigma",
+    __slots__ = ("beads", "tau0", "pile_lambda", "thermostat", "tables", "cmat", "cs", "sw", "ws", "pc1", "psigma",
                  "spring_c", "centroid")
     LOG_WIDTH = 5
 
@@ -135,11 +134,7 @@ class DevicePIMD(DeviceMD):
             P = int(num_graphs if num_graphs is not None else batch_h[-1] + 1)
             if P > MAX_BEADS:
                 raise ValueError("DevicePIMD: %d beads -- at most %d" % (P, MAX_BEADS))
-            try:
-                self.n_rep = DeviceREMD._same_replicas(atomic_number, cell, masses, batch_h, P)
-            except ValueError as e:
-                raise ValueError("DevicePIMD: the beads of a ring polymer are copies of ONE system -- "
-                                 + str(e).replace("DeviceREMD: ", "").replace("replica", "bead"))
+            self.n_rep = same_copies("DevicePIMD", "bead", atomic_number, cell, masses, batch_h, P)
         self.beads = P                                    # P
         self.tau0 = None if tau0 is None else float(tau0)
         self.pile_lambda, self.thermostat = float(pile_lambda), bool(thermostat)
@@ -164,21 +159,16 @@ class DevicePIMD(DeviceMD):
     # ---- the two hooks of the capture ---------------------------------------------------------------------------------------
     def _advance(self, step):
         P = _lib.ptr
-        wrap, cell, inv = self._cell_args(step)
-        flags = (self.flags | HN_MD_WRAP) if wrap else (self.flags & ~HN_MD_WRAP)
-        _lib.call("hermnet_pimd_advance", self.n, self.num_graphs, flags, self.seed, self.tables.inv_beads, P(self.x), P(self.v),
-                  P(self.x0), P(self.v0), P(self.image), P(self.image0), P(self.f_prev), P(self.kick), P(self.cmat), P(self.cs),
-                  P(self.sw), P(self.ws), P(self.pc1), P(self.psigma), cell, inv, P(self._pos_input(step)), P(self.centroid),
-                  P(self.state), torch.cuda.current_stream(self.device).cuda_stream)
+        flags, cell, inv = self._advance_cell(step)
+        _lib.call("hermnet_pimd_advance", self.n, self.num_graphs, flags, self.seed, self.tables.inv_beads,
+                  *self._advance_atoms(), P(self.cmat), P(self.cs), P(self.sw), P(self.ws), P(self.pc1), P(self.psigma), cell, inv,
+                  P(self._pos_input(step)), P(self.centroid), P(self.state), torch.cuda.current_stream(self.device).cuda_stream)
 
     def _finish(self, step, out):
         P = _lib.ptr
         energy, forces, total = self._step_outputs(out)
         _lib.call("hermnet_pimd_finish", self.n, self.num_graphs, P(self.graph_ptr), P(forces), P(energy), P(total),
-                  int(step.capacity), P(self.x), P(self.v), P(self.x0), P(self.v0), P(self.image), P(self.image0),
-                  P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos), P(self.ke_atom), P(self.spring_c),
-                  P(self.centroid), P(self.log), self.log_steps, P(self.state),
-                  torch.cuda.current_stream(self.device).cuda_stream)
+                  int(step.capacity), *self._finish_atoms(step), P(self.spring_c), P(self.centroid), *self._finish_tail())
 
     # ---- velocities, estimators -------------------------------------------------------------------------------------------------
     def maxwell_boltzmann(self, temperature=None, seed=0):
@@ -213,24 +203,10 @@ class DevicePIMD(DeviceMD):
             if beads is None or int(beads) < 1:
                 raise ValueError("DevicePIMD.from_atoms: beads >= 1")
             images = [atoms] * int(beads)
-        periodic = [bool(np.all(np.asarray(a.pbc))) for a in images]
-        if not all(periodic) and any(np.any(np.asarray(a.pbc)) for a in images):
-            raise RuntimeError("DevicePIMD.from_atoms: beads periodic in all three directions, or all open")
         dev = torch.device(device)
-        counts = [len(a.positions) for a in images]
-        cell = None
-        if all(periodic):
-            cell = torch.as_tensor(np.stack([np.asarray(a.cell, dtype=np.float64).reshape(3, 3) for a in images])).float().to(dev)
-        vel = [a.get_velocities() for a in images]
-        v = None
-        if any(u is not None for u in vel):
-            v = np.concatenate([np.zeros((c, 3)) if u is None else np.asarray(u, dtype=np.float64) for u, c in zip(vel, counts)])
-            v = v / ASE_TIME_FS
-        return cls(model, torch.as_tensor(np.concatenate([np.asarray(a.numbers) for a in images])).to(dev), cell,
-                   np.concatenate([np.asarray(a.positions, dtype=np.float64) for a in images]),
-                   np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in images]), dt, temperature,
-                   batch=torch.as_tensor(np.repeat(np.arange(len(images)), counts)).to(dev), num_graphs=len(images),
-                   velocities=v, device=dev, **kw)
+        s = stack_atoms(images, "DevicePIMD.from_atoms", "beads", dev)
+        return cls(model, s.z, s.cell, s.pos, s.masses, dt, temperature, batch=s.batch, num_graphs=len(images),
+                   velocities=s.velocities, device=dev, **kw)
 
     def to_atoms(self, images, snapshot=None):
         """Write positions (wrapped by the centroid) and velocities (ASE units) of `snapshot` (default: a fetch()) into the
@@ -239,16 +215,13 @@ class DevicePIMD(DeviceMD):
         if not isinstance(images, (list, tuple)) or len(images) != self.beads:
             raise ValueError("DevicePIMD.to_atoms: a list of %d beads" % self.beads)
         for j, atoms in enumerate(images):
-            mine = slice(j * self.n_rep, (j + 1) * self.n_rep)
-            atoms.positions = s.positions[mine].copy()
-            atoms.set_velocities(s.velocities[mine] * ASE_TIME_FS)
+            self._write_member(atoms, s, j)
         return s
 
     def centroid_atoms(self, atoms, snapshot=None):
         """Write the centroid's positions and velocities (the means over the beads; ASE units) of `snapshot` (default: a
         fetch()) into `atoms`.  Returns the snapshot."""
         s = snapshot if snapshot is not None else self.fetch()
-        P = self.beads
-        atoms.positions = s.positions.reshape(P, self.n_rep, 3).sum(axis=0) / P
-        atoms.set_velocities(s.velocities.reshape(P, self.n_rep, 3).sum(axis=0) / P * ASE_TIME_FS)
+        mean = lambda a: a.reshape(self.beads, self.n_rep, 3).sum(axis=0) / self.beads
+        self._write_atoms(atoms, mean(s.positions), mean(s.velocities))
         return s

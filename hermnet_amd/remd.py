@@ -32,10 +32,10 @@ import torch
 
 from . import _lib
 from ._resident import host_f64
-from .md import ASE_TIME_FS, KB, DeviceMD
+from .md import KB, CopiesMD, same_copies, stack_atoms
 
 
-class DeviceREMD(DeviceMD):
+class DeviceREMD(CopiesMD):
     """See the module docstring.  model, atomic_number [N], cell [B,3,3] (None: open structures), pos [N,3], masses [N], dt,
     `batch` [N] with `num_graphs` = B, `seed`, `velocities`, `capacity`, `log_steps`, `wrap`, `reference_compat`, `device`:
     `DeviceMD`'s; the B graphs are the replicas.  `temperatures` [B] (K): the ladder, rung r at temperatures[r], replica g
@@ -49,7 +49,7 @@ class DeviceREMD(DeviceMD):
     held behind the step's exchange) per time step -- E_kin is taken before any rescaling --, `rung` [B], `replica_at` [B],
     `temperature` [B] = temperatures[rung], `attempts` and `accepts` [B-1] per pair (r, r+1)."""
 
-    __slots__ = ("temperatures", "exchange_interval", "n_rep", "sigma_table", "beta", "up", "down", "rung", "replica_at",
+    __slots__ = ("temperatures", "exchange_interval", "sigma_table", "beta", "up", "down", "rung", "replica_at",
                  "rung_new", "vscale", "outcome", "attempts", "accepts")
     LOG_WIDTH = 5
 
@@ -76,34 +76,9 @@ class DeviceREMD(DeviceMD):
             raise ValueError("DeviceREMD: exchange_interval must be an integer >= 1")
         self.temperatures = t                             # the ladder [R] in K, on the host
         self.exchange_interval = int(exchange_interval)   # steps between two attempts
-        self.n_rep = self._same_replicas(atomic_number, cell, masses, batch_h, B)     # atoms of one replica
+        self.n_rep = same_copies("DeviceREMD", "replica", atomic_number, cell, masses, batch_h, B)   # atoms of one replica
         super().__init__(model, atomic_number, cell, pos, masses, dt, temperature=t, friction=friction, seed=seed, batch=batch,
                          num_graphs=B, **kw)
-
-    @staticmethod
-    def _same_replicas(atomic_number, cell, masses, batch_h, B):
-        """The atom count of one replica; refuses replicas that differ (the class docstring's refusals)."""
-        z, m = np.asarray(torch.as_tensor(atomic_number).cpu()).reshape(-1), host_f64(masses).reshape(-1)
-        if len(batch_h) != len(z) or len(m) != len(z) or np.any(np.diff(batch_h) < 0):
-            raise ValueError("DeviceREMD: atomic_number, masses and batch are [N], batch non-decreasing")
-        ptr = np.searchsorted(batch_h, np.arange(B + 1))
-        for g in range(1, B):
-            mine, first = slice(ptr[g], ptr[g + 1]), slice(ptr[0], ptr[1])
-            if ptr[g + 1] - ptr[g] != ptr[1] - ptr[0]:
-                raise ValueError("DeviceREMD: replica %d differs from replica 0 in atom count (%d, %d): a ladder is replicas "
-                                 "of one system" % (g, ptr[g + 1] - ptr[g], ptr[1] - ptr[0]))
-            if np.any(z[mine] != z[first]):
-                raise ValueError("DeviceREMD: replica %d differs from replica 0 in atomic numbers" % g)
-            if np.any(m[mine] != m[first]):
-                raise ValueError("DeviceREMD: replica %d differs from replica 0 in masses" % g)
-        if cell is not None:
-            c = host_f64(cell).reshape(-1, 3, 3)
-            if len(c) != B:
-                raise ValueError("DeviceREMD: cell is [B,3,3], one per replica")
-            for g in range(1, B):
-                if np.any(c[g] != c[0]):
-                    raise ValueError("DeviceREMD: replica %d differs from replica 0 in cell" % g)
-        return int(ptr[1] - ptr[0])
 
     def _own_state(self, masses):
         """`DeviceMD`'s coefficients (sigma of the identity assignment), then the ladder: what needs a division or a square
@@ -131,11 +106,9 @@ class DeviceREMD(DeviceMD):
         P = _lib.ptr
         energy, forces, total = self._step_outputs(out)
         _lib.call("hermnet_remd_finish", self.n, self.num_graphs, P(self.graph_ptr), P(forces), P(energy), P(total),
-                  int(step.capacity), self.exchange_interval, self.seed, P(self.x), P(self.v), P(self.x0), P(self.v0),
-                  P(self.image), P(self.image0), P(self.f_prev), P(self.kick), P(self.half_mass), P(step.pos), P(self.ke_atom),
-                  P(self.beta), P(self.up), P(self.down), P(self.sigma_table), P(self.sigma), P(self.rung), P(self.replica_at),
-                  P(self.rung_new), P(self.vscale), P(self.outcome), P(self.attempts), P(self.accepts), P(self.log),
-                  self.log_steps, P(self.state), torch.cuda.current_stream(self.device).cuda_stream)
+                  int(step.capacity), self.exchange_interval, self.seed, *self._finish_atoms(step), P(self.beta), P(self.up),
+                  P(self.down), P(self.sigma_table), P(self.sigma), P(self.rung), P(self.replica_at), P(self.rung_new),
+                  P(self.vscale), P(self.outcome), P(self.attempts), P(self.accepts), *self._finish_tail())
 
     # ---- the packed fetch's own part ------------------------------------------------------------------------------------------
     def _fetch_extras(self):
@@ -150,28 +123,14 @@ class DeviceREMD(DeviceMD):
     # ---- ASE hand-off (duck-typed) ------------------------------------------------------------------------------------------------
     @classmethod
     def from_atoms(cls, replicas, model, dt, temperatures, friction, exchange_interval, device="cuda:0", **kw):
-        """`replicas`: the list of the ladder's replicas in batch order, anything with `positions`, `numbers`, `cell`, `pbc`,
-        `get_masses()`, `get_velocities()` (ASE units); all periodic in three directions, or all open."""
+        """`replicas`: the list of the ladder's replicas in batch order -- what `md.stack_atoms` takes; all periodic in three
+        directions, or all open."""
         if not isinstance(replicas, (list, tuple)) or len(replicas) < 2:
             raise ValueError("DeviceREMD.from_atoms: a list of 2 replicas or more")
-        periodic = [bool(np.all(np.asarray(a.pbc))) for a in replicas]
-        if not all(periodic) and any(np.any(np.asarray(a.pbc)) for a in replicas):
-            raise RuntimeError("DeviceREMD.from_atoms: replicas periodic in all three directions, or all open")
         dev = torch.device(device)
-        counts = [len(a.positions) for a in replicas]
-        cell = None
-        if all(periodic):
-            cell = torch.as_tensor(np.stack([np.asarray(a.cell, dtype=np.float64).reshape(3, 3) for a in replicas])).float().to(dev)
-        vel = [a.get_velocities() for a in replicas]
-        v = None
-        if any(u is not None for u in vel):
-            v = np.concatenate([np.zeros((c, 3)) if u is None else np.asarray(u, dtype=np.float64) for u, c in zip(vel, counts)])
-            v = v / ASE_TIME_FS
-        return cls(model, torch.as_tensor(np.concatenate([np.asarray(a.numbers) for a in replicas])).to(dev), cell,
-                   np.concatenate([np.asarray(a.positions, dtype=np.float64) for a in replicas]),
-                   np.concatenate([np.asarray(a.get_masses(), dtype=np.float64) for a in replicas]), dt, temperatures, friction,
-                   exchange_interval, batch=torch.as_tensor(np.repeat(np.arange(len(replicas)), counts)).to(dev),
-                   num_graphs=len(replicas), velocities=v, device=dev, **kw)
+        s = stack_atoms(replicas, "DeviceREMD.from_atoms", "replicas", dev)
+        return cls(model, s.z, s.cell, s.pos, s.masses, dt, temperatures, friction, exchange_interval, batch=s.batch,
+                   num_graphs=len(replicas), velocities=s.velocities, device=dev, **kw)
 
     def to_atoms(self, replicas, by_rung=False, snapshot=None):
         """Write positions (wrapped) and velocities (ASE units) of `snapshot` (default: a fetch()) into the list `replicas`:
@@ -181,8 +140,5 @@ class DeviceREMD(DeviceMD):
         if len(replicas) != self.num_graphs:
             raise ValueError("DeviceREMD.to_atoms: a list of %d replicas" % self.num_graphs)
         for k, atoms in enumerate(replicas):
-            g = int(s.replica_at[k]) if by_rung else k
-            mine = slice(g * self.n_rep, (g + 1) * self.n_rep)
-            atoms.positions = s.positions[mine].copy()
-            atoms.set_velocities(s.velocities[mine] * ASE_TIME_FS)
+            self._write_member(atoms, s, int(s.replica_at[k]) if by_rung else k)
         return s

@@ -11,7 +11,7 @@ from hermnet_amd import _lib
 
 AMU = 103.642696562
 KB = 8.617333262e-5
-LANGEVIN, WRAP, NONFINITE = 1, 2, 256
+LANGEVIN, WRAP, CAPACITY_BIT, NONFINITE = 1, 2, 4, 256
 M32 = 0xFFFFFFFF
 
 
@@ -84,13 +84,58 @@ def finish_np(v, f32, kick, half_mass):
     return half_mass * ((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
 
 
-class NumpyMD(object):
+class _State(object):
+    """The state arrays every reference and every wrapper of the MD family starts from (the layout of
+    include/hermnet_hip.h)."""
+
+    def _make_state(self, x, v):
+        n = self.n = len(x)
+        self.x, self.v = np.array(x, dtype=np.float64), np.array(v, dtype=np.float64)
+        self.x0, self.v0 = np.zeros_like(self.x), np.zeros_like(self.v)
+        self.image, self.image0 = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 3), dtype=np.int32)
+        self.f_prev = np.zeros((n, 3), dtype=np.float32)
+        self.pos32 = self.x.astype(np.float32)
+        self.ke_atom = np.zeros(n, dtype=np.float64)
+        self.state = np.zeros(4, dtype=np.int64)
+        return n
+
+    # md_finish.h's skeleton in numpy, for the references whose finish keeps the protocol (NumpyREMD, NumpyPIMD)
+    def _begin_finish(self, f32, energy, total, capacity, B):
+        """hn_step_code, then md_finish_one on every atom: (step, code, mode, forces, energies)."""
+        step, mode = int(self.state[0]), int(self.state[3])
+        f = np.array(f32, dtype=np.float32)
+        e = np.zeros(B, dtype=np.float32) if energy is None else np.array(energy, dtype=np.float32)
+        code = int(total[1]) & 255
+        if int(total[0]) > capacity:
+            code |= CAPACITY_BIT
+        if not np.all(np.isfinite(e)):
+            code |= NONFINITE
+        if mode != 0:
+            if code == 0:
+                self.f_prev = f.copy()
+        elif code != 0:
+            self.x[:], self.image[:], self.v[:] = self.x0, self.image0, self.v0
+            self.pos32 = self.x0.astype(np.float32)
+        else:
+            self.ke_atom = finish_np(self.v, f, self.kick, self.half_mass)
+            self.f_prev = f.copy()
+        return step, code, mode, f, e
+
+    def _commit(self, step, code, mode):
+        """md_commit."""
+        if code != 0:
+            self.state[1], self.state[2] = code, step
+        elif mode == 0:
+            self.state[0] = step + 1
+        if mode != 0:
+            self.state[3] = 0
+
+
+class NumpyMD(_State):
     """The reference trajectory: numpy float64 velocity Verlet / BAOAB with the noise of the library's host form."""
 
     def __init__(self, x, v, masses, dt, cell=None, batch=None, friction=None, temperature=None, seed=0, num_graphs=None):
-        n = len(x)
-        self.x, self.v = np.array(x, dtype=np.float64), np.array(v, dtype=np.float64)
-        self.image = np.zeros((n, 3), dtype=np.int32)
+        n = self._make_state(x, v)
         self.batch = np.zeros(n, dtype=np.int64) if batch is None else np.asarray(batch, dtype=np.int64)
         self.dt, self.seed, self.step = float(dt), seed, 0
         self.kick, self.half_mass, c1, self.sigma = coefficients(masses, dt, self.batch, friction, temperature, num_graphs)
@@ -99,8 +144,7 @@ class NumpyMD(object):
         if cell is not None:
             c = np.asarray(cell, dtype=np.float32).astype(np.float64).reshape(-1, 3, 3)
             self.cell, self.inv = c[self.batch], np.linalg.inv(c)[self.batch]
-        self.f = np.zeros((n, 3), dtype=np.float32)
-        self.ke = None
+        self.f, self.ke = self.f_prev, None
 
     def advance(self):
         xi = host_noise(self.seed, self.step, len(self.x))[1] if self.c1_atom is not None else None
@@ -113,17 +157,14 @@ class NumpyMD(object):
         self.step += 1
 
 
-class HostMD(object):
-    """The library's host twins on numpy arrays (the state layout of include/hermnet_hip.h)."""
+class HostMD(_State):
+    """The library's host twins on numpy arrays (the state layout of include/hermnet_hip.h).  `_evaluation`, `_finish_atoms`
+    and `_finish_tail` are what the finishes of the family's wrappers (HostNPT, HostREMD, HostPIMD) share."""
 
     def __init__(self, x, v, masses, dt, cell=None, batch=None, friction=None, temperature=None, seed=0, log_steps=64,
                  num_graphs=None):
-        n = self.n = len(x)
+        n = self._make_state(x, v)
         self.lib = _lib.load()
-        self.x, self.v = np.array(x, dtype=np.float64), np.array(v, dtype=np.float64)
-        self.x0, self.v0 = np.zeros_like(self.x), np.zeros_like(self.v)
-        self.image, self.image0 = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 3), dtype=np.int32)
-        self.f_prev = np.zeros((n, 3), dtype=np.float32)
         self.batch = np.zeros(n, dtype=np.int64) if batch is None else np.ascontiguousarray(batch, dtype=np.int64)
         self.B = int(num_graphs) if num_graphs is not None else int(self.batch[-1]) + 1
         self.graph_ptr = np.searchsorted(self.batch, np.arange(self.B + 1)).astype(np.int32)
@@ -135,11 +176,8 @@ class HostMD(object):
             self.cell = np.ascontiguousarray(np.asarray(cell, dtype=np.float32).reshape(-1, 9))
             self.inv = np.ascontiguousarray(np.linalg.inv(self.cell.astype(np.float64).reshape(-1, 3, 3)))
             self.flags |= WRAP
-        self.pos32 = self.x.astype(np.float32)
-        self.ke_atom = np.zeros(n, dtype=np.float64)
         self.log_steps = log_steps
         self.log = np.full((log_steps, self.B, 3), -7.0)
-        self.state = np.zeros(4, dtype=np.int64)
 
     def advance(self):
         rc = self.lib.hermnet_host_md_advance(self.n, self.B, self.flags, self.dt, self.seed, _p(self.x), _p(self.v), _p(self.x0),
@@ -149,14 +187,23 @@ class HostMD(object):
         assert rc == 0
         return self.pos32
 
-    def finish(self, f32, energy=None, total=(0, 0), capacity=1 << 20):
-        f = np.ascontiguousarray(f32, dtype=np.float32)
+    def _evaluation(self, f32, energy, total):
+        """(forces, energies -- zeros where none are given --, the list's (found, flags)) as the arrays a finish takes."""
         e = np.zeros(self.B, dtype=np.float32) if energy is None else np.ascontiguousarray(energy, dtype=np.float32)
-        tot = np.array(total, dtype=np.int64)
-        rc = self.lib.hermnet_host_md_finish(self.n, self.B, _p(self.graph_ptr), _p(f), _p(e), _p(tot), capacity, _p(self.x),
-                                             _p(self.v), _p(self.x0), _p(self.v0), _p(self.image), _p(self.image0),
-                                             _p(self.f_prev), _p(self.kick), _p(self.half_mass), _p(self.pos32), _p(self.ke_atom),
-                                             _p(self.log), self.log_steps, _p(self.state))
+        return np.ascontiguousarray(f32, dtype=np.float32), e, np.array(total, dtype=np.int64)
+
+    def _finish_atoms(self):
+        """The eleven per-atom pointers of every finish, x ... ke_atom."""
+        return (_p(self.x), _p(self.v), _p(self.x0), _p(self.v0), _p(self.image), _p(self.image0), _p(self.f_prev),
+                _p(self.kick), _p(self.half_mass), _p(self.pos32), _p(self.ke_atom))
+
+    def _finish_tail(self):
+        return _p(self.log), self.log_steps, _p(self.state)
+
+    def finish(self, f32, energy=None, total=(0, 0), capacity=1 << 20):
+        f, e, tot = self._evaluation(f32, energy, total)
+        rc = self.lib.hermnet_host_md_finish(self.n, self.B, _p(self.graph_ptr), _p(f), _p(e), _p(tot), capacity,
+                                             *self._finish_atoms(), *self._finish_tail())
         assert rc == 0
 
 

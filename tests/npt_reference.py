@@ -174,14 +174,10 @@ class HostNPT(HostMD):
         self.log = np.full((log_steps, B, 5), -7.0)
 
     def finish(self, f32, virial32, energy=None, total=(0, 0), capacity=1 << 20):
-        f = np.ascontiguousarray(f32, dtype=np.float32)
+        f, e, tot = self._evaluation(f32, energy, total)
         w = np.ascontiguousarray(virial32, dtype=np.float32).reshape(self.B, 9)
-        e = np.zeros(self.B, dtype=np.float32) if energy is None else np.ascontiguousarray(energy, dtype=np.float32)
-        tot = np.array(total, dtype=np.int64)
         rc = self.lib.hermnet_host_md_finish_npt(
             self.n, self.B, _p(self.graph_ptr), _p(self.batch), _p(f), _p(e), _p(w), _p(tot), capacity, self.coupling, self.mask,
-            self.max_strain, _p(self.p0), _p(self.c), _p(self.x), _p(self.v), _p(self.x0), _p(self.v0), _p(self.image),
-            _p(self.image0), _p(self.f_prev), _p(self.kick), _p(self.half_mass), _p(self.pos32), _p(self.ke_atom),
-            _p(self.cell64), _p(self.cell), _p(self.inv), _p(self.mu), _p(self.clamped), _p(self.log), self.log_steps,
-            _p(self.state))
+            self.max_strain, _p(self.p0), _p(self.c), *self._finish_atoms(), _p(self.cell64), _p(self.cell), _p(self.inv),
+            _p(self.mu), _p(self.clamped), *self._finish_tail())
         assert rc == 0

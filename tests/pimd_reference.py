@@ -7,8 +7,8 @@ import types
 import numpy as np
 
 from hermnet_amd.pimd import ring_tables
-from md_reference import AMU, KB, LANGEVIN, HostMD, _p, finish_np, host_noise
-from remd_reference import CAPACITY_BIT, NONFINITE, canonical_sum
+from md_reference import AMU, KB, LANGEVIN, HostMD, _p, _State, host_noise
+from remd_reference import canonical_sum
 
 FIELDS = ("x", "v", "image", "f_prev", "pos32", "centroid", "log", "state", "x0", "v0", "image0")
 
@@ -63,37 +63,27 @@ class HostPIMD(_Ring, HostMD):
         return self.pos32
 
     def finish(self, f32, energy=None, total=(0, 0), capacity=1 << 20, expect=0):
-        f = np.ascontiguousarray(f32, dtype=np.float32)
-        e = np.zeros(self.B, dtype=np.float32) if energy is None else np.ascontiguousarray(energy, dtype=np.float32)
-        tot = np.array(total, dtype=np.int64)
+        f, e, tot = self._evaluation(f32, energy, total)
         rc = self.lib.hermnet_host_pimd_finish(
-            self.n, self.B, _p(self.graph_ptr), _p(f), _p(e), _p(tot), capacity, _p(self.x), _p(self.v), _p(self.x0), _p(self.v0),
-            _p(self.image), _p(self.image0), _p(self.f_prev), _p(self.kick), _p(self.half_mass), _p(self.pos32), _p(self.ke_atom),
-            _p(self.spring_c), _p(self.centroid), _p(self.log), self.log_steps, _p(self.state))
+            self.n, self.B, _p(self.graph_ptr), _p(f), _p(e), _p(tot), capacity, *self._finish_atoms(), _p(self.spring_c),
+            _p(self.centroid), *self._finish_tail())
         assert rc == expect, rc
 
 
-class NumpyPIMD(_Ring):
+class NumpyPIMD(_Ring, _State):
     """The reference: pimd_step.h's phases and the finish in numpy float64, operation by operation.  The Gaussians are those
     of the library's host form (`host_noise`), or `gaussians(step)` [P n_rep, 3] where one is given."""
 
     def __init__(self, beads, x, v, masses, dt, temperature, tau0=100.0, pile_lambda=1.0, thermostat=True, seed=0, log_steps=64,
                  cell=None, gaussians=None):
-        n = self.n = len(x)
+        self._make_state(x, v)
         m = np.asarray(masses, dtype=np.float64) * AMU
-        self.x, self.v = np.array(x, dtype=np.float64), np.array(v, dtype=np.float64)
-        self.x0, self.v0 = np.zeros_like(self.x), np.zeros_like(self.v)
-        self.image, self.image0 = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 3), dtype=np.int32)
-        self.f_prev = np.zeros((n, 3), dtype=np.float32)
         self.dt, self.seed, self.gaussians = float(dt), seed, gaussians
         self.kick, self.half_mass = 0.5 * self.dt / m, np.where(np.isfinite(m), 0.5 * m, 0.0)
         self.cell = self.inv = None
         if cell is not None:
             c = np.tile(np.asarray(cell, dtype=np.float32).reshape(1, 3, 3), (beads, 1, 1)).astype(np.float64)
             self.cell, self.inv = c[0], np.linalg.inv(c)[0]
-        self.pos32 = self.x.astype(np.float32)
-        self.ke_atom = np.zeros(n)
-        self.state = np.zeros(4, dtype=np.int64)
         self._make_ring(beads, masses, dt, temperature, tau0, pile_lambda, thermostat, log_steps)
 
     def _flight(self, q, v):
@@ -146,26 +136,11 @@ class NumpyPIMD(_Ring):
         return self.pos32
 
     def finish(self, f32, energy=None, total=(0, 0), capacity=1 << 20):
-        step, halted, mode = (int(w) for w in self.state[[0, 1, 3]])
-        if halted != 0:
+        if self.state[1] != 0:
             return
         P, nr = self.P, self.n_rep
-        f = np.array(f32, dtype=np.float32)
-        e = np.zeros(P, dtype=np.float32) if energy is None else np.array(energy, dtype=np.float32)
-        code = int(total[1]) & 255                                   # hn_step_code
-        if int(total[0]) > capacity:
-            code |= CAPACITY_BIT
-        if not np.all(np.isfinite(e)):
-            code |= NONFINITE
-        if mode != 0:                                                # md_finish_one
-            if code == 0:
-                self.f_prev = f.copy()
-        elif code != 0:
-            self.x[:], self.image[:], self.v[:] = self.x0, self.image0, self.v0
-            self.pos32 = self.x0.astype(np.float32)
-        else:
-            self.ke_atom = finish_np(self.v, f, self.kick, self.half_mass)
-            self.f_prev = f.copy()
+        step, code, mode, f, e = self._begin_finish(f32, energy, total, capacity, P)
+        if code == 0 and mode == 0:
             X, F = self.x.reshape(P, nr, 3), f.astype(np.float64).reshape(P, nr, 3)
             free = self.half_mass[:nr] != 0.0
             for j in range(P):                                       # pimd_log_bead
@@ -176,9 +151,4 @@ class NumpyPIMD(_Ring):
                 self.log[step % self.log_steps, j] = (np.float64(e[j]), canonical_sum(np.where(free, ke, 0.0)), float(total[0]),
                                                       canonical_sum(np.where(free, spring, 0.0)),
                                                       canonical_sum(np.where(free, vir, 0.0)))
-        if code != 0:                                                # md_commit
-            self.state[1], self.state[2] = code, step
-        elif mode == 0:
-            self.state[0] = step + 1
-        if mode != 0:
-            self.state[3] = 0
+        self._commit(step, code, mode)

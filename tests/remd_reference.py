@@ -7,9 +7,7 @@ import types
 
 import numpy as np
 
-from md_reference import AMU, KB, M32, HostMD, _p, advance_np, coefficients, finish_np, host_noise, philox4x32_10
-
-CAPACITY_BIT, NONFINITE = 4, 256
+from md_reference import AMU, KB, M32, HostMD, NumpyMD, _p, advance_np, host_noise, philox4x32_10
 
 
 def ladder(temperatures, masses_rep, dt, friction):
@@ -98,40 +96,22 @@ class HostREMD(_Ladder, HostMD):
         self._make_ladder(masses, dt, temperatures, friction, interval, log_steps)
 
     def finish(self, f32, energy=None, total=(0, 0), capacity=1 << 20, expect=0):
-        f = np.ascontiguousarray(f32, dtype=np.float32)
-        e = np.zeros(self.B, dtype=np.float32) if energy is None else np.ascontiguousarray(energy, dtype=np.float32)
-        tot = np.array(total, dtype=np.int64)
+        f, e, tot = self._evaluation(f32, energy, total)
         rc = self.lib.hermnet_host_remd_finish(
-            self.n, self.B, _p(self.graph_ptr), _p(f), _p(e), _p(tot), capacity, self.interval, self.seed, _p(self.x), _p(self.v),
-            _p(self.x0), _p(self.v0), _p(self.image), _p(self.image0), _p(self.f_prev), _p(self.kick), _p(self.half_mass),
-            _p(self.pos32), _p(self.ke_atom), _p(self.beta), _p(self.up), _p(self.down), _p(self.sigma_table), _p(self.sigma),
-            _p(self.rung), _p(self.replica_at), _p(self.rung_new), _p(self.vscale), _p(self.outcome), _p(self.attempts),
-            _p(self.accepts), _p(self.log), self.log_steps, _p(self.state))
+            self.n, self.B, _p(self.graph_ptr), _p(f), _p(e), _p(tot), capacity, self.interval, self.seed, *self._finish_atoms(),
+            _p(self.beta), _p(self.up), _p(self.down), _p(self.sigma_table), _p(self.sigma), _p(self.rung), _p(self.replica_at),
+            _p(self.rung_new), _p(self.vscale), _p(self.outcome), _p(self.attempts), _p(self.accepts), *self._finish_tail())
         assert rc == expect, rc
 
 
-class NumpyREMD(_Ladder):
+class NumpyREMD(_Ladder, NumpyMD):
     """The reference: md_advance_one (the noise of the library's host form) and the replica-exchange finish in numpy float64,
     operation by operation.  `decisions`: every pair it decided, (step, r, ga, gb, delta, log u, accepted)."""
 
     def __init__(self, x, v, masses, dt, temperatures, friction, interval, seed=0, log_steps=64, cell=None):
-        n = self.n = len(x)
         R = len(temperatures)
-        self.batch = np.repeat(np.arange(R), n // R)
-        self.x, self.v = np.array(x, dtype=np.float64), np.array(v, dtype=np.float64)
-        self.x0, self.v0 = np.zeros_like(self.x), np.zeros_like(self.v)
-        self.image, self.image0 = np.zeros((n, 3), dtype=np.int32), np.zeros((n, 3), dtype=np.int32)
-        self.f_prev = np.zeros((n, 3), dtype=np.float32)
-        self.dt, self.seed = float(dt), seed
-        self.kick, self.half_mass, c1, self.sigma = coefficients(masses, dt, self.batch, friction, temperatures, R)
-        self.c1_atom = c1[self.batch]
-        self.cell = self.inv = None
-        if cell is not None:
-            c = np.asarray(cell, dtype=np.float32).astype(np.float64).reshape(-1, 3, 3)
-            self.cell, self.inv = c[self.batch], np.linalg.inv(c)[self.batch]
-        self.pos32 = self.x.astype(np.float32)
-        self.ke_atom = np.zeros(n)
-        self.state = np.zeros(4, dtype=np.int64)
+        NumpyMD.__init__(self, x, v, masses, dt, cell=cell, batch=np.repeat(np.arange(R), len(x) // R), friction=friction,
+                         temperature=temperatures, seed=seed, num_graphs=R)
         self.decisions = []
         self._make_ladder(masses, dt, temperatures, friction, interval, log_steps)
 
@@ -147,25 +127,9 @@ class NumpyREMD(_Ladder):
         return self.pos32
 
     def finish(self, f32, energy=None, total=(0, 0), capacity=1 << 20):
-        step, halted, mode = (int(w) for w in self.state[[0, 1, 3]])
-        if halted != 0:
+        if self.state[1] != 0:
             return
-        f = np.array(f32, dtype=np.float32)
-        e = np.zeros(self.R, dtype=np.float32) if energy is None else np.array(energy, dtype=np.float32)
-        code = int(total[1]) & 255                                   # hn_step_code
-        if int(total[0]) > capacity:
-            code |= CAPACITY_BIT
-        if not np.all(np.isfinite(e)):
-            code |= NONFINITE
-        if mode != 0:                                                # md_finish_one
-            if code == 0:
-                self.f_prev = f.copy()
-        elif code != 0:
-            self.x[:], self.image[:], self.v[:] = self.x0, self.image0, self.v0
-            self.pos32 = self.x0.astype(np.float32)
-        else:
-            self.ke_atom = finish_np(self.v, f, self.kick, self.half_mass)
-            self.f_prev = f.copy()
+        step, code, mode, f, e = self._begin_finish(f32, energy, total, capacity, self.R)
         if code == 0 and mode == 0:
             # remd_decide
             self.rung_new, self.vscale = self.rung.copy(), np.ones(self.R)
@@ -189,9 +153,4 @@ class NumpyREMD(_Ladder):
             self.replica_at[self.rung_new] = np.arange(self.R)
             self.attempts += self.outcome != 0
             self.accepts += self.outcome == 2
-        if code != 0:                                                # md_commit
-            self.state[1], self.state[2] = code, step
-        elif mode == 0:
-            self.state[0] = step + 1
-        if mode != 0:
-            self.state[3] = 0
+        self._commit(step, code, mode)
