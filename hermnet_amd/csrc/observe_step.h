@@ -205,23 +205,19 @@ HN_HD inline bool obs_rdf_graph_ok(const ObsRdfArgs& a, int g) {
   return true;
 }
 
-// Atom i's coordinate as the pairs read it: fractional in a cell, Cartesian in an open structure.
-HN_HD inline void obs_rdf_coordinate(const ObsRdfArgs& a, int g, int i, double s[3]) {
+// The minimum-image rule, stated once (the RDF's pairs here; metad_step.h's collective variables): the fractional
+// coordinate of a point in the cell whose float64 inverse is `inv` ...
+HN_HD inline void obs_fractional(double x0, double x1, double x2, const double* inv, double s[3]) {
 #pragma clang fp contract(off)
-  const double x0 = a.x[3 * (size_t)i], x1 = a.x[3 * (size_t)i + 1], x2 = a.x[3 * (size_t)i + 2];
-  if (!a.cell32) {
-    s[0] = x0;
-    s[1] = x1;
-    s[2] = x2;
-    return;
-  }
-  const double* inv = a.inv_cell + 9 * (size_t)g;
   for (int k = 0; k < 3; ++k) s[k] = (x0 * inv[k] + x1 * inv[3 + k]) + x2 * inv[6 + k];
 }
 
-HN_HD inline double obs_pair_r2(const double si[3], double sj0, double sj1, double sj2, const double cell[9], bool periodic) {
+// ... and the vector d from point j to point i by rounding their fractional difference to the nearest image and going
+// back through the cell (open structures: the difference itself).  Returns |d|^2.
+HN_HD inline double obs_min_image(const double si[3], double sj0, double sj1, double sj2, const double cell[9], bool periodic,
+                                  double d[3]) {
 #pragma clang fp contract(off)
-  double ds[3] = {si[0] - sj0, si[1] - sj1, si[2] - sj2}, d[3];
+  double ds[3] = {si[0] - sj0, si[1] - sj1, si[2] - sj2};
   if (periodic) {
     for (int k = 0; k < 3; ++k) ds[k] = ds[k] - floor(ds[k] + 0.5);
     for (int j = 0; j < 3; ++j) d[j] = (ds[0] * cell[j] + ds[1] * cell[3 + j]) + ds[2] * cell[6 + j];
@@ -229,6 +225,23 @@ HN_HD inline double obs_pair_r2(const double si[3], double sj0, double sj1, doub
     for (int j = 0; j < 3; ++j) d[j] = ds[j];
   }
   return (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2];
+}
+
+// Atom i's coordinate as the pairs read it: fractional in a cell, Cartesian in an open structure.
+HN_HD inline void obs_rdf_coordinate(const ObsRdfArgs& a, int g, int i, double s[3]) {
+  const double x0 = a.x[3 * (size_t)i], x1 = a.x[3 * (size_t)i + 1], x2 = a.x[3 * (size_t)i + 2];
+  if (!a.cell32) {
+    s[0] = x0;
+    s[1] = x1;
+    s[2] = x2;
+    return;
+  }
+  obs_fractional(x0, x1, x2, a.inv_cell + 9 * (size_t)g, s);
+}
+
+HN_HD inline double obs_pair_r2(const double si[3], double sj0, double sj1, double sj2, const double cell[9], bool periodic) {
+  double d[3];
+  return obs_min_image(si, sj0, sj1, sj2, cell, periodic, d);
 }
 
 // The bin of r2 by comparisons alone (-1: none, r2 >= edge2[bins] or not a number); the float sqrt is only where to start.

@@ -1300,6 +1300,66 @@ int hermnet_host_observe_rdf(int num_atoms, int num_graphs, int num_species, int
                              const int* work_host, int num_work, const long* state_host, long* obs_host, long* counts_host,
                              long* samples_host, long* skipped_host, double* volume_sum_host);
 
+/* Multiple-walker metadynamics inside the replayed MD step (added within ABI v13: new entry points only;
+ * hermnet_amd/metad.py: DeviceMetaD; csrc/metad_kernels.hip, metad_step.h).  A stage of four launches between the force
+ * backward and the UNCHANGED hermnet_md_finish, which is handed forces_b in the place of the step's forces.  The B graphs are B
+ * walkers of ONE system of n_rep = N / B atoms (walker g: rows g n_rep .. (g + 1) n_rep) under one shared bias
+ *   V(s) = sum_k hill_heights[k] prod_d E(-(s_d - hill_centres[k,d])^2 / (2 sigma_d^2)),   k < hill_count[0],
+ * E = the library's own exp (range reduction by ln 2 in two parts, a Horner polynomial of degree 13 on |r| <= ln 2 / 2,
+ * ldexp; 0 below -745), the same bits on the device and on the host.  The cell is fixed and periodic.
+ *
+ * D = num_cvs = 1 or 2 collective variables, every table made on the host:  cv_kind [D,2] int32 = (kind, p);  cv_par [D,8]
+ * float64;  cv_role [D,n_rep] bytes;  cv_weight [D,2,n_rep] float64;  sigma_par [D,2] = (1 / (2 sigma^2), 1 / sigma^2).
+ *   kind 1, distance:  centre a = sum_i cv_weight[d,0,i] u_i, centre b likewise with cv_weight[d,1,:] (normalised weights, 0
+ *     outside a group), u_i = x_i + image_i cell the UNWRAPPED coordinate, the sums in hermnet_md_finish's fixed order;
+ *     s = |minimum image of (a - b)| by hermnet_observe_rdf's rule, ds/dx_i = (wa_i - wb_i) (a - b) / s, 0 at s = 0.
+ *   kind 2, coordination:  s = scale sum_{i in A} sum_{j in B, j != i} st(r_ij), cv_role bit 0 = in A, bit 1 = in B;
+ *     w = r^2 cv_par[0], sw = 1 / (1 + w^p) with w^p by multiplications, st = (sw - cv_par[2]) cv_par[3] for r^2 < cv_par[1]
+ *     and 0 beyond;  cv_par = (1 / r0^2, r_cut^2, sw(w_c), 1 / (1 - sw(w_c)), 2 cv_par[3] / r0^2, scale, 0, 0).  Every atom
+ *     sums its own count and its own gradient over all partners j of its walker in ascending j (minimum image as above):
+ *     no atomics, nothing scattered.
+ * Caller-owned state:  hill_count [1] int64, hill_centres [max_hills,D], hill_heights [max_hills] float64;  scratch cv_atom
+ * [D,N,6] and cv_walker [B,16] float64 (row g = s_0, s_1, V, dV/ds_0, dV/ds_1, height, ...);  forces_b [N,3] float32;
+ * bias_forces [N,3] float64;  cv_log [log_steps,B,D+2] float64.
+ *
+ * hermnet_metad_bias     state[1] != 0: nothing.  Otherwise the step's halt code is formed from energy / total / capacity as
+ *   hermnet_md_finish forms it.  Code != 0: forces_b = forces, nothing else.  Code 0: per walker s, V(s) and dV/ds over the
+ *   hills counted when the step began (hill index in hermnet_md_finish's fixed order);  per atom nb = sum_d dV/ds_d ds_d/dx_i
+ *   from 0.0, bias_forces = -nb, forces_b = (float)((double)forces - nb).  Mode 0 (state[3] == 0) also writes
+ *   cv_log[state[0] % log_steps][g] = (s_1..s_D, V(s), height deposited or 0), and where (state[0] + 1) % pace == 0 walker g
+ *   appends the hill (s, h) at hill_count + g, h = height, or height E(-V(s) inv_kt) where inv_kt = 1 / (kB (gamma - 1) T)
+ *   is not 0;  hill_count += B, never beyond max_hills.  One workgroup alone writes the hill list and its count.
+ * hermnet_metad_cv       the per-atom pass and the CV sums alone:  values [B,D], grads [D,N,3] = ds_d/dx_i.
+ * hermnet_host_metad_exp out[i] = E(a[i]).
+ * The hermnet_host_metad_* twins run the same text on HOST pointers (no stream), bit for bit what the device computes.
+ * HN_ERR_BAD_ARG: a NULL pointer, num_graphs < 1, num_cvs not 1 or 2, num_atoms no multiple of num_graphs, pace / max_hills /
+ *   log_steps < 1;  the host twins also refuse walkers that do not tile the atoms in equal ranges, a kind other than 1 or 2
+ *   and a power outside 1..64. */
+int hermnet_metad_bias(int num_atoms, int num_graphs, int num_cvs, const int* graph_ptr, const double* x, const int* image,
+                       const float* cell, const double* inv_cell, const int* cv_kind, const double* cv_par,
+                       const unsigned char* cv_role, const double* cv_weight, const double* sigma_par, double height,
+                       double inv_kt, long pace, long max_hills, const float* forces, const float* energy, const long* total,
+                       long capacity, const long* state, double* cv_atom, double* cv_walker, long* hill_count,
+                       double* hill_centres, double* hill_heights, float* forces_b, double* bias_forces, double* cv_log,
+                       long log_steps, void* stream);
+int hermnet_metad_cv(int num_atoms, int num_graphs, int num_cvs, const int* graph_ptr, const double* x, const int* image,
+                     const float* cell, const double* inv_cell, const int* cv_kind, const double* cv_par,
+                     const unsigned char* cv_role, const double* cv_weight, double* cv_atom, double* cv_walker, double* values,
+                     double* grads, void* stream);
+int hermnet_host_metad_bias(int num_atoms, int num_graphs, int num_cvs, const int* graph_ptr_host, const double* x_host,
+                            const int* image_host, const float* cell_host, const double* inv_cell_host, const int* cv_kind_host,
+                            const double* cv_par_host, const unsigned char* cv_role_host, const double* cv_weight_host,
+                            const double* sigma_par_host, double height, double inv_kt, long pace, long max_hills,
+                            const float* forces_host, const float* energy_host, const long* total_host, long capacity,
+                            const long* state_host, double* cv_atom_host, double* cv_walker_host, long* hill_count_host,
+                            double* hill_centres_host, double* hill_heights_host, float* forces_b_host,
+                            double* bias_forces_host, double* cv_log_host, long log_steps);
+int hermnet_host_metad_cv(int num_atoms, int num_graphs, int num_cvs, const int* graph_ptr_host, const double* x_host,
+                          const int* image_host, const float* cell_host, const double* inv_cell_host, const int* cv_kind_host,
+                          const double* cv_par_host, const unsigned char* cv_role_host, const double* cv_weight_host,
+                          double* cv_atom_host, double* cv_walker_host, double* values_host, double* grads_host);
+int hermnet_host_metad_exp(long n, const double* a_host, double* out_host);
+
 #ifdef __cplusplus
 }
 #endif
