@@ -1,7 +1,8 @@
 """Writes tests/golden/chain_dispatch.json: what the host side of the node chain kernels (csrc/node_chain*.hip) answers WITHOUT
 launching anything -- per entry point and width the return code of every call it must refuse (or finish as "no rows") in front
 of its launch, the widths each family supports, and the tile height hermnet_node_update_tile_rows picks for four row layouts
-under every setting of the two options it reads.  Recorded from the library as it stood before the host dispatch was
+under every setting of the two options it reads (update_tile16, node_chain_wide; it does not read update_tile64_max, which
+only hermnet_node_update_fwd / _bwd consult at tile_rows = 0, so that option is not varied here).  Recorded from the library as it stood before the host dispatch was
 rearranged; tests/test_cabi_cpu.py holds the library to it entry for entry.  `table(lib)` is shared with that test.
 No call recorded here may reach a launch (its pointers are host memory): every one with rows must come back HN_ERR_BAD_ARG,
 which `table` itself asserts.  Run from the repository root: python tests/golden/gen_chain_dispatch.py"""

@@ -501,7 +501,10 @@ def test_read_out_on_the_matrix_pipe_matches_the_staged_weight_form(rows, monkey
 def _node_chain_case(H, T, counts, uniform, hr):
     """csrc/node_chain.hip (LayerNorm + x_proj chain, PaiNNUpdate chain and their backward kernels on the fp32 matrix
     pipe) vs the fp64 PyTorch restatement of tests/ref_ops.py: ragged relation blocks, an inactive relation, rows of
-    unknown elements, zero-padded channels (hidden_real), both 64- and 32-row tile instances at H = 128."""
+    unknown elements, zero-padded channels (hidden_real).  Through the nodeops wrappers, so the library picks the instances: at
+    H = 128 the 64-row projection kernels and the 32-row update kernels (16-row ones where test_update_chain_on_16_row_tiles
+    forces them) -- NOT the 64-row update instances node_update_fwd / _bwd_kernel<128, 64, 1>, which run only above option
+    update_tile64_max = 0; tests/test_chain_rows.py runs those, and every other compiled instance, by name."""
     from test_host_logic import _layer_weights_and_graph
     from hermnet_amd import nodeops
     dev = _dev()
