@@ -19,7 +19,7 @@
  * ABI version 13 (`HN_ABI_VERSION` below, returned by `hermnet_abi_version`): hermnet_edge_geometry_bwd_virial, then hermnet_graph_virial / _workspace and
  * hermnet_neighbor_count_devcell, then hermnet_node_update_fwd_last / _bwd_last and hermnet_message_scatter_bwd_gedge (the
  * forms without dead work at the two ends of the layer stack), then hermnet_neighbor_batch_workspace / _count / _fill /
- * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table), then hermnet_neb_finish with its hermnet_host_neb_finish twin (the device-resident nudged elastic band), then hermnet_remd_finish with its hermnet_host_remd_finish twin (replica exchange), then hermnet_pimd_advance / _finish with their hermnet_host_pimd_* twins (ring-polymer path-integral MD), then hermnet_observe_frames / _msd / _rdf with their hermnet_host_observe_* twins (MD observers behind a driver's finish) were added within v13 (new entry points only, nothing
+ * _fill_padded (the search of a batch of structures), then the host probe hermnet_host_neighbor_geometry, then hermnet_md_advance / _finish / _noise with their hermnet_host_md_* twins (the device-resident integrator), then hermnet_relax_advance / _finish with their hermnet_host_relax_* twins (the device-resident FIRE relaxation), then hermnet_md_finish_npt with its hermnet_host_md_finish_npt twin (the barostat of the device-resident integrator), then hermnet_species_expand (layer 0's node projection from a per-species table), then hermnet_neb_finish with its hermnet_host_neb_finish twin (the device-resident nudged elastic band), then hermnet_remd_finish with its hermnet_host_remd_finish twin (replica exchange), then hermnet_pimd_advance / _finish with their hermnet_host_pimd_* twins (ring-polymer path-integral MD), then hermnet_observe_frames / _msd / _rdf with their hermnet_host_observe_* twins (MD observers behind a driver's finish), then hermnet_swapmc_advance / _finish with their hermnet_host_swapmc_* twins (species-swap Monte Carlo between MD steps) were added within v13 (new entry points only, nothing
  * existing changed, so the version stays 13); v13 is ADDITIVE over v12 (hermnet_band_product / _grad_a / _grad_b / _grads, hermnet_basis_window,
  * hermnet_edge_unit, hermnet_col_sum: the training path's rbf_proj on the bucketed basis and its neighbours); v12 is ADDITIVE over v11 (hermnet_halo_proj_rows / _accumulate, ranged launches of
  * hermnet_message_scatter_bwd without the finishing launch, hermnet_set_option / _get_option in place of the library's environment
@@ -1359,6 +1359,70 @@ int hermnet_host_metad_cv(int num_atoms, int num_graphs, int num_cvs, const int*
                           const double* cv_par_host, const unsigned char* cv_role_host, const double* cv_weight_host,
                           double* cv_atom_host, double* cv_walker_host, double* values_host, double* grads_host);
 int hermnet_host_metad_exp(long n, const double* a_host, double* out_host);
+
+/* Species-swap Monte Carlo inside the replayed MD step (added within ABI v13: new entry points only; hermnet_amd/swapmc.py:
+ * DeviceSwapMD; csrc/swapmc_kernels.hip, swapmc_step.h).  hermnet_swapmc_advance stands in the place of hermnet_md_advance in
+ * front of the search, hermnet_swapmc_finish in the place of hermnet_md_finish behind the force backward.  In a fixed
+ * composition, exchanging the species of two atoms is exchanging their coordinates: z, masses, velocities and every per-atom
+ * table stay with their rows.
+ *
+ * Caller-owned state beside hermnet_md_advance's / _finish's:  mc [2] int64 = (t, left), the trials committed so far and the
+ * trials still due in this block;  cand [num_cand] int32, per graph its atoms of finite mass sorted by (species, atom), and
+ * cand_ptr [B, S+1] int32, the absolute offsets of each species' range in cand (S = num_species);  beta [B] float64 =
+ * 1 / (kB T);  e_ref [B] float64 the energy of the current configuration;  attempts, accepts [B] int64;  swap_log
+ * [swap_rows,B,4] float64;  scratch: pair [B,2] int32, dval [B] float64, outcome [B] int64.  `seed` is hermnet_md_advance's.
+ *
+ * With the words as the replay begins: halt code != 0: nothing.  state[3] == 1: a PRIME -- hermnet_md_advance's and
+ * hermnet_md_finish's, and e_ref = energy; mc untouched.  Otherwise left > 0: a TRIAL; otherwise an MD STEP --
+ * hermnet_md_advance's and hermnet_md_finish's (the log row's E_kin in the canonical order), and e_ref = energy; where the
+ * new step % swap_interval == 0, left = swaps.
+ * A trial, graph g:  w = Philox4x32-10 of key (seed low, seed high), counter (g, t low, t high, 3);  m = the graph's
+ *   candidates, mulhi(w, m) = ((uint64)w * m) >> 32;  i = cand[ptr[0] + mulhi(w0, m)], s its species with m_s candidates;
+ *   k = mulhi(w1, m - m_s), q = k < ptr[s] - ptr[0] ? k : k + m_s, j = cand[ptr[0] + q];  m - m_s == 0: not tried.
+ *   hermnet_swapmc_advance exchanges x and image of (i, j) and writes their pos32 rows; nothing else.
+ *   hermnet_swapmc_finish:  d = (double)energy[g] - e_ref[g];  delta = -beta[g] d;  accepted iff delta >= 0 or log(u) < delta,
+ *   u = (u(w2,w3) + 1) 2^-53 with hermnet_md_advance's u(,).  Accepted: f_prev of g's atoms = forces, e_ref[g] = energy[g].
+ *   Rejected: (i, j) exchanged back.  swap_log[t % swap_rows][g] = (i, j, d, outcome: 0 not tried, 1 rejected, 2 accepted;
+ *   not tried: -1, -1, 0, 0);  attempts[g] counts tried, accepts[g] accepted trials;  t += 1, left -= 1.  The step's code
+ *   != 0: the trial is void -- every pair exchanged back, state = (step, code, step, 0), mc and every record untouched.
+ *   A trial writes no velocity, no MD log row, and leaves state[0].
+ *   One launch in the advance, four in the finish: one workgroup with a lane per graph that writes the scratch alone; the
+ *   per-atom launch; one workgroup per graph (an MD step's log row); and the one workgroup that alone writes e_ref, the
+ *   counters, swap_log, mc and state.  No atomics; no workgroup reads what another of the same launch writes.
+ * The hermnet_host_swapmc_* twins run the same text on HOST pointers (no stream), bit for bit but for the last digits of
+ * log(u) and of the atoms' Gaussians.
+ * HN_ERR_BAD_ARG: hermnet_md_advance's / _finish's, a NULL pointer (cand may be NULL with num_cand == 0), num_species < 1,
+ *   num_cand < 0, swap_interval < 1, swaps < 0, swap_rows < 1; the host twins also refuse a negative mc word, species ranges
+ *   that do not ascend inside cand and a candidate that is no atom of its graph or does not ascend within its species (the
+ *   device entry points cannot read them: there such a graph is not tried). */
+int hermnet_swapmc_advance(int num_atoms, int num_graphs, int flags, double dt, unsigned long seed, double* x, double* v,
+                           double* x0, double* v0, int* image, int* image0, const float* f_prev, const double* kick,
+                           const double* c1, const double* sigma, const long* batch, const float* cell, const double* inv_cell,
+                           float* pos32, const long* state, const long* mc, const int* graph_ptr, const int* cand,
+                           const int* cand_ptr, int num_species, int num_cand, void* stream);
+int hermnet_swapmc_finish(int num_atoms, int num_graphs, const int* graph_ptr, const long* batch, const float* forces,
+                          const float* energy, const long* total, long capacity, long swap_interval, long swaps,
+                          unsigned long seed, double* x, double* v, const double* x0, const double* v0, int* image,
+                          const int* image0, float* f_prev, const double* kick, const double* half_mass, float* pos32,
+                          double* ke_atom, const double* beta, double* e_ref, long* mc, const int* cand, const int* cand_ptr,
+                          int num_species, int num_cand, int* pair, double* dval, long* outcome, long* attempts, long* accepts,
+                          double* swap_log, long swap_rows, double* log, long log_steps, long* state, void* stream);
+int hermnet_host_swapmc_advance(int num_atoms, int num_graphs, int flags, double dt, unsigned long seed, double* x_host,
+                                double* v_host, double* x0_host, double* v0_host, int* image_host, int* image0_host,
+                                const float* f_prev_host, const double* kick_host, const double* c1_host,
+                                const double* sigma_host, const long* batch_host, const float* cell_host,
+                                const double* inv_cell_host, float* pos32_host, const long* state_host, const long* mc_host,
+                                const int* graph_ptr_host, const int* cand_host, const int* cand_ptr_host, int num_species,
+                                int num_cand);
+int hermnet_host_swapmc_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const long* batch_host,
+                               const float* forces_host, const float* energy_host, const long* total_host, long capacity,
+                               long swap_interval, long swaps, unsigned long seed, double* x_host, double* v_host,
+                               const double* x0_host, const double* v0_host, int* image_host, const int* image0_host,
+                               float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
+                               double* ke_atom_host, const double* beta_host, double* e_ref_host, long* mc_host,
+                               const int* cand_host, const int* cand_ptr_host, int num_species, int num_cand, int* pair_host,
+                               double* dval_host, long* outcome_host, long* attempts_host, long* accepts_host,
+                               double* swap_log_host, long swap_rows, double* log_host, long log_steps, long* state_host);
 
 #ifdef __cplusplus
 }
