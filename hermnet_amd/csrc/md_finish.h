@@ -1,5 +1,6 @@
 // The finish skeleton of the MD drivers (md_kernels.hip: hermnet_md_finish / _npt; remd_kernels.hip: hermnet_remd_finish;
-// pimd_kernels.hip: hermnet_pimd_finish; swapmc_kernels.hip: hermnet_swapmc_finish), stated once as relax_driver.h states
+// pimd_kernels.hip: hermnet_pimd_finish; swapmc_kernels.hip: hermnet_swapmc_finish; nhc_kernels.hip: hermnet_nhc_finish),
+// stated once as relax_driver.h states
 // the relaxations': the arguments of the per-atom half of a finish, that half itself (the second kick, a void step's restore, a prime's copy), the test every
 // kernel behind it makes (md_committed), E_kin in the canonical order, the log row, the commit -- the single writer of
 // `state` --, the two kernels every driver launches unchanged, and the host twins' skeleton (md_host_finish) around the

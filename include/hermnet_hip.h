@@ -1424,6 +1424,66 @@ int hermnet_host_swapmc_finish(int num_atoms, int num_graphs, const int* graph_p
                                double* dval_host, long* outcome_host, long* attempts_host, long* accepts_host,
                                double* swap_log_host, long swap_rows, double* log_host, long log_steps, long* state_host);
 
+/* Nose-Hoover chain NVT inside the replayed MD step (added within ABI v13: new entry points only; hermnet_amd/nhc.py:
+ * DeviceNHC; csrc/nhc_kernels.hip, nhc_step.h).  hermnet_nhc_advance stands in the place of hermnet_md_advance in front of
+ * the search, hermnet_nhc_finish in the place of hermnet_md_finish behind the force backward; a time step is
+ * NHC(dt/2) kick(dt/2) drift(dt) [forces] kick(dt/2) NHC(dt/2) with hermnet_md_advance's NVE kick, drift and wrap and
+ * hermnet_md_finish's kick, void step and commit.  `flags`: hermnet_md_advance's without HN_MD_LANGEVIN.
+ *
+ * Caller-owned state beside hermnet_md_advance's / _finish's, all float64:  xi, v_xi [B,M] the chains (M = chain, 1..8);
+ * xi0, v_xi0 [B,M] their backup;  scale [B,2] the last opening and closing factor;  constants made on the host:  delta
+ * [order] = w_k (dt / 2) / substeps for the Suzuki-Yoshida weights w (order 1, 3 or 5),  kt [B] = kB T,  dof_kt [B] = dof kB T,
+ * q [B,M] = (dof kB T tau^2, kB T tau^2, ...) and inv_q [B,M] = 1 / q -- both 0 for a graph whose thermostat is off.
+ *
+ * NHC(Delta) of graph g (Martyna, Tuckerman, Tobias, Klein 1996): K2 = 2 E_kin, s = 1; substeps times, for every weight, with
+ * d = delta[k]:  v_M += G_M d/2;  j = M-1..1: e = exp(-d/4 v_{j+1}), v_j = (v_j e + G_j d/2) e;  a = exp(-d v_1), s = s a,
+ * K2 = (K2 a) a;  xi_j += d v_j;  j = 1..M-1: the same update with G_j made anew;  v_M += G_M d/2.  G_1 = (K2 - dof_kt)
+ * inv_q_1, G_j = (q_{j-1} v_{j-1}^2 - kt) inv_q_j.  exp is the library's own (hermnet_host_metad_exp): IEEE +, x, floor and
+ * ldexp alone, contraction off, so device, host twin and a numpy transcription agree bit for bit; with inv_q = q = v_xi = 0
+ * every factor is exactly 1.0 and the step is hermnet_md_advance's / _finish's NVE bit for bit.
+ *
+ * hermnet_nhc_advance (no halt code, state[3] == 0; a prime only rewrites pos32 as hermnet_md_advance does): per graph E_kin =
+ *   sum half_mass |v|^2 in the canonical order from v as it stands (not a number the last finish left), (xi0, v_xi0) =
+ *   (xi, v_xi), NHC(dt/2), scale[g][0] = s; per atom v0 = v (unscaled), v = v s, then hermnet_md_advance's NVE step.
+ * hermnet_nhc_finish: hermnet_md_finish's per-atom half; on a step that commits per graph the canonical E_kin = K behind the
+ *   second kick, NHC(dt/2), scale[g][1] = s, log row (width 4) = (energy[g], (K s) s, total[0], E_nhc),
+ *   E_nhc = dof_kt xi_1 + kt sum_{j>=2} xi_j + sum_j q_j v_j^2 / 2;  per atom v = v s;  on a void step (xi, v_xi) = (xi0, v_xi0)
+ *   beside hermnet_md_finish's restore;  then hermnet_md_finish's commit.  Two launches in the advance, four in the finish,
+ *   no atomics; no workgroup reads what another of the same launch writes.
+ * The hermnet_host_nhc_* twins run the same text on HOST pointers (no stream), bit for bit.
+ * HN_ERR_BAD_ARG: hermnet_md_advance's / _finish's, HN_MD_LANGEVIN in flags, chain outside 1..8, order not 1, 3 or 5,
+ *   substeps < 1, a NULL pointer (batch may be NULL: one graph). */
+int hermnet_nhc_advance(int num_atoms, int num_graphs, int flags, double dt, double* x, double* v, double* x0, double* v0,
+                        int* image, int* image0, const float* f_prev, const double* kick, const long* batch, const float* cell,
+                        const double* inv_cell, float* pos32, const long* state, const int* graph_ptr, const double* half_mass,
+                        int chain, int order, int substeps, const double* delta, const double* kt, const double* dof_kt,
+                        const double* q, const double* inv_q, double* xi, double* v_xi, double* xi0, double* v_xi0,
+                        double* scale, void* stream);
+int hermnet_nhc_finish(int num_atoms, int num_graphs, const int* graph_ptr, const long* batch, const float* forces,
+                       const float* energy, const long* total, long capacity, double* x, double* v, const double* x0,
+                       const double* v0, int* image, const int* image0, float* f_prev, const double* kick,
+                       const double* half_mass, float* pos32, double* ke_atom, int chain, int order, int substeps,
+                       const double* delta, const double* kt, const double* dof_kt, const double* q, const double* inv_q,
+                       double* xi, double* v_xi, double* xi0, double* v_xi0, double* scale, double* log, long log_steps,
+                       long* state, void* stream);
+int hermnet_host_nhc_advance(int num_atoms, int num_graphs, int flags, double dt, double* x_host, double* v_host,
+                             double* x0_host, double* v0_host, int* image_host, int* image0_host, const float* f_prev_host,
+                             const double* kick_host, const long* batch_host, const float* cell_host,
+                             const double* inv_cell_host, float* pos32_host, const long* state_host,
+                             const int* graph_ptr_host, const double* half_mass_host, int chain, int order, int substeps,
+                             const double* delta_host, const double* kt_host, const double* dof_kt_host, const double* q_host,
+                             const double* inv_q_host, double* xi_host, double* v_xi_host, double* xi0_host,
+                             double* v_xi0_host, double* scale_host);
+int hermnet_host_nhc_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const long* batch_host,
+                            const float* forces_host, const float* energy_host, const long* total_host, long capacity,
+                            double* x_host, double* v_host, const double* x0_host, const double* v0_host, int* image_host,
+                            const int* image0_host, float* f_prev_host, const double* kick_host,
+                            const double* half_mass_host, float* pos32_host, double* ke_atom_host, int chain, int order,
+                            int substeps, const double* delta_host, const double* kt_host, const double* dof_kt_host,
+                            const double* q_host, const double* inv_q_host, double* xi_host, double* v_xi_host,
+                            double* xi0_host, double* v_xi0_host, double* scale_host, double* log_host, long log_steps,
+                            long* state_host);
+
 #ifdef __cplusplus
 }
 #endif
