@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 import torch
 
-import hermnet_amd as hn
 from hermnet_amd import _lib, synth
 from hermnet_amd.graph import GraphedBatchMDStep, GraphedMDStep
 from hermnet_amd.md import ASE_TIME_FS, HALT_CAPACITY, HALT_NONFINITE, DeviceMD
 from md_reference import AMU, KB, HostMD, NumpyMD, bits, host_noise
+from resident_helpers import _FakeAtoms, _model, _shared_model
 
 pytestmark = pytest.mark.gpu
 
@@ -26,22 +26,6 @@ _CACHE = {}
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _model(seed=8):
-    """The model of test_md_step_with_list_rebuild_replays_as_one_graph."""
-    model = hn.HVNet(["Al", "Ni", "Cu"], rc=5.0, num_layers=3, hidden_channels=128, num_rbf=64).eval()
-    model.load_state_dict(synth.synth_state_dict(model.state_dict(), seed))
-    model = model.to(_dev())
-    for p in model.parameters():
-        p.requires_grad_(False)
-    return model
-
-
-def _shared_model():
-    if "model" not in _CACHE:
-        _CACHE["model"] = _model()
-    return _CACHE["model"]
 
 
 def _velocities(m, temp, seed):
@@ -313,23 +297,6 @@ def test_halt_on_a_non_finite_energy_and_resume():
     assert (end.step, end.halted) == (10, False) and end.log.shape == (5, 1, 3) and np.all(np.isfinite(end.log))
     assert np.all(np.isfinite(end.positions)) and np.all(np.isfinite(end.velocities))
     assert not np.array_equal(end.log[0, :, 0], good.log[4, :, 0])                  # the new weights' energies
-
-
-class _FakeAtoms(object):
-    """What `from_atoms` / `to_atoms` touch of an ase.Atoms."""
-
-    def __init__(self, positions, numbers, cell, masses, velocities):
-        self.positions, self.numbers, self.cell, self.pbc = positions.copy(), numbers, cell, np.array([True, True, True])
-        self._m, self._v = masses, velocities
-
-    def get_masses(self):
-        return self._m
-
-    def get_velocities(self):
-        return self._v
-
-    def set_velocities(self, v):
-        self._v = np.array(v)
 
 
 def test_ase_hand_off_and_momentum():

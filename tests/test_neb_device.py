@@ -10,13 +10,13 @@ import numpy as np
 import pytest
 import torch
 
-import hermnet_amd as hn
 from hermnet_amd import _lib, neb as neb_module, synth
 from hermnet_amd.graph import GraphedBatchMDStep
 from hermnet_amd.md import HALT_CAPACITY
 from hermnet_amd.neb import DeviceNEB
 from hermnet_amd._resident import PARKED
 from neb_reference import HostNEB, NumpyNEB, bits, layout
+from resident_helpers import _shared_model
 
 pytestmark = pytest.mark.gpu
 
@@ -26,18 +26,6 @@ _CACHE = {}
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _shared_model():
-    """The model of tests/test_relax_device.py."""
-    if "model" not in _CACHE:
-        model = hn.HVNet(["Al", "Ni", "Cu"], rc=5.0, num_layers=3, hidden_channels=128, num_rbf=64).eval()
-        model.load_state_dict(synth.synth_state_dict(model.state_dict(), 8))
-        model = model.to(_dev())
-        for p in model.parameters():
-            p.requires_grad_(False)
-        _CACHE["model"] = model
-    return _CACHE["model"]
 
 
 def _band(reps, images, seeds):

@@ -15,6 +15,8 @@ from hermnet_amd.nhc import DeviceNHC, conserved
 from hermnet_amd.observe import MSD, Frames
 from md_reference import AMU, KB, bits
 from nhc_reference import HostNHC
+import resident_helpers as rh
+from resident_helpers import _flat, _put
 import test_md_device as mdt
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +32,6 @@ _CACHE = {}
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _put(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
 
 
 # ---- 1. the kernels against the host twins ----------------------------------------------------------------------------------------
@@ -123,7 +121,7 @@ def _system():
     if "system" not in _CACHE:
         parts = [synth.fcc_alloy_atoms(reps=(2, 2, 2), seed=10 + g) for g in range(4)]
         pos, z = np.concatenate([p[0] for p in parts]), np.concatenate([p[2] for p in parts])
-        m = np.array([mdt.MASS[int(v)] for v in z])
+        m = np.array([rh.MASS[int(v)] for v in z])
         v = np.random.RandomState(3).normal(size=(len(m), 3)) * np.sqrt(KB * T_START / (m * AMU))[:, None]
         _CACHE["system"] = dict(pos=pos, z=z, cell=np.stack([p[1] for p in parts]), m=m, v=v, batch=np.repeat(np.arange(4), 32))
     return _CACHE["system"]
@@ -137,7 +135,7 @@ def _nhc(temperature=T_NHC, tau=TAU, model=None, **kw):
     s = _system()
     args = dict(velocities=s["v"], batch=_put(s["batch"]), num_graphs=4)
     args.update(kw)
-    return DeviceNHC(model or mdt._shared_model(), *_args(s), temperature=temperature, tau=tau, **args)
+    return DeviceNHC(model or rh._shared_model(), *_args(s), temperature=temperature, tau=tau, **args)
 
 
 def _host(s, x, v, temperature=T_NHC, tau=TAU, **kw):
@@ -152,7 +150,7 @@ def _state_bits(snap):
 def _evaluator():
     s, dev = _system(), _dev()
     z, cell, pos, _, _ = _args(s)
-    step = GraphedBatchMDStep(mdt._shared_model(), z, cell, torch.from_numpy(pos.astype(np.float32)).to(dev), _put(s["batch"]), 4)
+    step = GraphedBatchMDStep(rh._shared_model(), z, cell, torch.from_numpy(pos.astype(np.float32)).to(dev), _put(s["batch"]), 4)
 
     def forces(p32):
         e, f = step(torch.from_numpy(np.ascontiguousarray(p32)).to(dev))
@@ -200,17 +198,13 @@ def _observers():
     return [Frames(stride=3, frames=16, velocities=True, images=True), MSD(stride=1, rows=32)]
 
 
-def _flat(entry):
-    return {k: (v.tobytes() if isinstance(v, np.ndarray) else v) for k, v in vars(entry).items()}
-
-
 def test_tau_inf_equals_device_md_nve_bit_for_bit_with_observers():
     """`DeviceNHC(tau=inf)` against `DeviceMD(friction=None)` on the same batch: positions, velocities, images, forces, the
     log's columns 0 to 2 and everything Frames and MSD recorded are bit-equal after 20 steps; xi = v_xi = E_nhc = 0 and both
     factors are exactly 1."""
     s = _system()
     ours = _nhc(tau=np.inf, observers=_observers())
-    plain = DeviceMD(mdt._shared_model(), *_args(s), velocities=s["v"], batch=_put(s["batch"]), num_graphs=4, observers=_observers())
+    plain = DeviceMD(rh._shared_model(), *_args(s), velocities=s["v"], batch=_put(s["batch"]), num_graphs=4, observers=_observers())
     ours.run(20)
     plain.run(20)
     a, b = ours.fetch(), plain.fetch()
@@ -301,7 +295,7 @@ def test_a_replay_has_six_integrator_launches_for_device_mds_four_and_no_copies(
     else is DeviceMD's, and there is no memcpy or memset."""
     from torch.profiler import ProfilerActivity, profile
     s = _system()
-    plain = DeviceMD(mdt._shared_model(), *_args(s), velocities=s["v"], batch=_put(s["batch"]), num_graphs=4)
+    plain = DeviceMD(rh._shared_model(), *_args(s), velocities=s["v"], batch=_put(s["batch"]), num_graphs=4)
     ours = _nhc()
 
     def events(driver):
@@ -332,13 +326,13 @@ def test_ase_hand_off_round_trip():
     velocities of the snapshot arrive in the structure; the default dof is 3 n - 3."""
     s = _system()
     p = slice(0, 32)
-    atoms = mdt._FakeAtoms(s["pos"][p], s["z"][p], s["cell"][0], s["m"][p], s["v"][p] * ASE_TIME_FS)
-    md = DeviceNHC.from_atoms(atoms, mdt._shared_model(), DT, temperature=600.0, tau=30.0, chain=2)
+    atoms = rh._FakeAtoms(s["pos"][p], s["z"][p], s["cell"][0], s["m"][p], s["v"][p] * ASE_TIME_FS)
+    md = DeviceNHC.from_atoms(atoms, rh._shared_model(), DT, temperature=600.0, tau=30.0, chain=2)
     start = md.fetch()
     assert md.num_graphs == 1 and md.dof.tolist() == [93.0] and start.xi.shape == (1, 2)
     assert np.array_equal(start.positions, s["pos"][p]) and np.allclose(start.velocities, s["v"][p], rtol=1e-15, atol=0)
     md.run(2)
-    out = mdt._FakeAtoms(np.zeros((32, 3)), s["z"][p], s["cell"][0], s["m"][p], None)
+    out = rh._FakeAtoms(np.zeros((32, 3)), s["z"][p], s["cell"][0], s["m"][p], None)
     snap = md.to_atoms(out)
     assert snap.step == 2 and not snap.halted and snap.v_xi.all() and snap.log.shape == (2, 1, 4)
     assert np.array_equal(out.positions, snap.positions) and np.array_equal(out.get_velocities(), snap.velocities * ASE_TIME_FS)

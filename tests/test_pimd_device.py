@@ -8,13 +8,13 @@ import numpy as np
 import pytest
 import torch
 
-import hermnet_amd as hn
 from hermnet_amd import _lib, synth
 from hermnet_amd.graph import GraphedBatchMDStep
 from hermnet_amd.md import ASE_TIME_FS, HALT_CAPACITY, HALT_NONFINITE, DeviceMD
 from hermnet_amd.pimd import DevicePIMD
 from md_reference import AMU, KB, bits, host_noise
 from pimd_reference import HostPIMD
+from resident_helpers import _FakeAtoms, _model, _shared_model
 
 pytestmark = pytest.mark.gpu
 
@@ -27,22 +27,6 @@ _CACHE = {}
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _model(seed=8):
-    """The H = 128, L = 3 model of test_md_device.py."""
-    model = hn.HVNet(["Al", "Ni", "Cu"], rc=5.0, num_layers=3, hidden_channels=128, num_rbf=64).eval()
-    model.load_state_dict(synth.synth_state_dict(model.state_dict(), seed))
-    model = model.to(_dev())
-    for p in model.parameters():
-        p.requires_grad_(False)
-    return model
-
-
-def _shared_model():
-    if "model" not in _CACHE:
-        _CACHE["model"] = _model()
-    return _CACHE["model"]
 
 
 # ---- 1. the kernels against the host twins ----------------------------------------------------------------------------------------
@@ -423,23 +407,6 @@ def test_refusals_name_their_reason():
         make(friction=0.01)
     with pytest.raises(ValueError, match="one number"):
         make(temperature=[300.0, 310.0, 320.0, 330.0])
-
-
-class _FakeAtoms(object):
-    """What `from_atoms` / `to_atoms` touch of an ase.Atoms."""
-
-    def __init__(self, positions, numbers, cell, masses, velocities):
-        self.positions, self.numbers, self.cell, self.pbc = positions.copy(), numbers, cell, np.array([True, True, True])
-        self._m, self._v = masses, velocities
-
-    def get_masses(self):
-        return self._m
-
-    def get_velocities(self):
-        return self._v
-
-    def set_velocities(self, v):
-        self._v = np.array(v)
 
 
 def test_ase_hand_off():

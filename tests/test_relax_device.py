@@ -12,12 +12,12 @@ import numpy as np
 import pytest
 import torch
 
-import hermnet_amd as hn
 from hermnet_amd import _lib, synth
 from hermnet_amd.graph import GraphedBatchMDStep, GraphedMDStep
 from hermnet_amd.md import HALT_CAPACITY, HALT_NONFINITE
 from hermnet_amd.relax import DeviceRelax
 from relax_reference import HostRelax, NumpyRelax, bits
+from resident_helpers import _model, _shared_model
 
 pytestmark = pytest.mark.gpu
 
@@ -28,22 +28,6 @@ _CACHE = {}
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _model(seed=8):
-    """The model of tests/test_md_device.py."""
-    model = hn.HVNet(["Al", "Ni", "Cu"], rc=5.0, num_layers=3, hidden_channels=128, num_rbf=64).eval()
-    model.load_state_dict(synth.synth_state_dict(model.state_dict(), seed))
-    model = model.to(_dev())
-    for p in model.parameters():
-        p.requires_grad_(False)
-    return model
-
-
-def _shared_model():
-    if "model" not in _CACHE:
-        _CACHE["model"] = _model()
-    return _CACHE["model"]
 
 
 def _single():

@@ -7,12 +7,12 @@ import numpy as np
 import pytest
 import torch
 
-import hermnet_amd as hn
 from hermnet_amd import _lib, synth
 from hermnet_amd.md import HALT_CAPACITY, DeviceMD
 from hermnet_amd.remd import DeviceREMD
 from md_reference import AMU, KB, bits
 from remd_reference import HostREMD, attempt_of, decide, ladder, pair_uniform
+from resident_helpers import _FakeAtoms, _shared_model
 
 pytestmark = pytest.mark.gpu
 
@@ -27,18 +27,6 @@ _CACHE = {}
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _shared_model():
-    """The H = 128, L = 3 model of test_md_device.py."""
-    if "model" not in _CACHE:
-        model = hn.HVNet(["Al", "Ni", "Cu"], rc=5.0, num_layers=3, hidden_channels=128, num_rbf=64).eval()
-        model.load_state_dict(synth.synth_state_dict(model.state_dict(), 8))
-        model = model.to(_dev())
-        for p in model.parameters():
-            p.requires_grad_(False)
-        _CACHE["model"] = model
-    return _CACHE["model"]
 
 
 # ---- 1. the kernels against the host twin -----------------------------------------------------------------------------------------
@@ -347,23 +335,6 @@ def test_halt_on_list_overflow_and_resume():
     last = remd.fetch()
     assert (last.step, last.halted) == (40, False)
     assert _state_bits(last) == _state_bits(end) and np.array_equal(bits(last.log), bits(log[k:]))
-
-
-class _FakeAtoms(object):
-    """What `from_atoms` / `to_atoms` touch of an ase.Atoms."""
-
-    def __init__(self, positions, numbers, cell, masses, velocities):
-        self.positions, self.numbers, self.cell, self.pbc = positions.copy(), numbers, cell, np.array([True, True, True])
-        self._m, self._v = masses, velocities
-
-    def get_masses(self):
-        return self._m
-
-    def get_velocities(self):
-        return self._v
-
-    def set_velocities(self, v):
-        self._v = np.array(v)
 
 
 def test_ase_hand_off_in_batch_and_in_ladder_order():

@@ -15,7 +15,8 @@ from hermnet_amd.swapmc import DeviceSwapMD
 from md_reference import AMU, KB, advance_np, bits
 from observe_reference import NumpyRDF, state_words
 from swapmc_reference import HostSwapMC, decide, pick_pair, tables, trial_uniform
-import test_md_device as mdt
+import resident_helpers as rh
+from resident_helpers import _flat, _put
 
 pytestmark = pytest.mark.gpu
 
@@ -30,10 +31,6 @@ _CACHE = {}
 
 def _dev():
     return torch.device("cuda:0")
-
-
-def _put(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(_dev())
 
 
 # ---- 1. the kernels against the host twins ----------------------------------------------------------------------------------------
@@ -140,7 +137,7 @@ def _system():
     if "system" not in _CACHE:
         parts = [synth.fcc_alloy_atoms(reps=(2, 2, 2), seed=10 + g) for g in range(4)]
         pos, z = np.concatenate([p[0] for p in parts]), np.concatenate([p[2] for p in parts])
-        m = np.array([mdt.MASS[int(v)] for v in z])
+        m = np.array([rh.MASS[int(v)] for v in z])
         v = np.random.RandomState(3).normal(size=(len(m), 3)) * np.sqrt(KB * T_MD / (m * AMU))[:, None]
         _CACHE["system"] = dict(pos=pos, z=z, cell=np.stack([p[1] for p in parts]), m=m, v=v, batch=np.repeat(np.arange(4), 32))
     return _CACHE["system"]
@@ -157,8 +154,8 @@ def _swapmd(interval=2, swaps=2, friction=None, model=None, cls=DeviceSwapMD, **
         args.update(friction=friction, temperature=T_MD)
     args.update(kw)
     if cls is DeviceMD:
-        return DeviceMD(model or mdt._shared_model(), *_args(s), **args)
-    return DeviceSwapMD(model or mdt._shared_model(), *_args(s), interval, swaps, mc_temperature=T_MC, **args)
+        return DeviceMD(model or rh._shared_model(), *_args(s), **args)
+    return DeviceSwapMD(model or rh._shared_model(), *_args(s), interval, swaps, mc_temperature=T_MC, **args)
 
 
 def _state_bits(snap):
@@ -170,7 +167,7 @@ def _state_bits(snap):
 def _evaluator(model=None):
     s, dev = _system(), _dev()
     z, cell, pos, _, _ = _args(s)
-    step = GraphedBatchMDStep(model or mdt._shared_model(), z, cell, torch.from_numpy(pos.astype(np.float32)).to(dev),
+    step = GraphedBatchMDStep(model or rh._shared_model(), z, cell, torch.from_numpy(pos.astype(np.float32)).to(dev),
                               _put(s["batch"]), 4)
 
     def forces(p32):
@@ -294,10 +291,6 @@ def _observers(rows=32):
     return [Frames(stride=3, frames=16, velocities=True, images=True), RDF(r_max=3.5, bins=35, stride=2), MSD(stride=1, rows=rows)]
 
 
-def _flat(entry):
-    return {k: (v.tobytes() if isinstance(v, np.ndarray) else v) for k, v in vars(entry).items()}
-
-
 def test_no_swaps_equals_device_md_bit_for_bit_with_observers():
     """`DeviceSwapMD(swaps=0)` against `DeviceMD` on the same batch and seed: positions, velocities, images, forces, the log
     and everything Frames, RDF and MSD recorded are bit-equal after 20 Langevin steps; nothing was tried."""
@@ -354,7 +347,7 @@ def test_halt_on_a_void_trial_and_resume_continue_to_the_same_bits():
     positions and forces are the fetched ones bit for bit, nothing is logged.  With the weight restored, resume()
     recaptures, its prime leaves (t, left) alone, the same trial is drawn, and the run ends bit-equal to an uninterrupted
     one -- swap_log rows included.  (The handled non-finite halt of test_md_device.py; nothing faults.)"""
-    model = mdt._model(seed=9)
+    model = rh._model(seed=9)
     whole = _swapmd(model=model)
     whole.run(11)
     mid = whole.fetch()
@@ -400,8 +393,8 @@ def test_ase_hand_off_for_one_structure_and_for_a_list():
     from hermnet_amd.md import ASE_TIME_FS
     s = _system()
     parts = [slice(32 * g, 32 * (g + 1)) for g in range(4)]
-    atoms = [mdt._FakeAtoms(s["pos"][p], s["z"][p], s["cell"][g], s["m"][p], s["v"][p] * ASE_TIME_FS) for g, p in enumerate(parts)]
-    md = DeviceSwapMD.from_atoms(atoms, mdt._shared_model(), DT, 2, 2, mc_temperature=T_MC, seed=SEED)
+    atoms = [rh._FakeAtoms(s["pos"][p], s["z"][p], s["cell"][g], s["m"][p], s["v"][p] * ASE_TIME_FS) for g, p in enumerate(parts)]
+    md = DeviceSwapMD.from_atoms(atoms, rh._shared_model(), DT, 2, 2, mc_temperature=T_MC, seed=SEED)
     start = md.fetch()
     assert np.array_equal(start.positions, s["pos"]) and np.allclose(start.velocities, s["v"], rtol=1e-15, atol=0)
     md.run(6)
@@ -412,9 +405,9 @@ def test_ase_hand_off_for_one_structure_and_for_a_list():
         assert np.array_equal(atoms[g].get_velocities(), end.velocities[p] * ASE_TIME_FS)
     with pytest.raises(ValueError, match="list of 4"):
         md.to_atoms(atoms[:3], snapshot=end)
-    one = DeviceSwapMD.from_atoms(atoms[0], mdt._shared_model(), DT, 1, 1, mc_temperature=300.0, seed=SEED)
+    one = DeviceSwapMD.from_atoms(atoms[0], rh._shared_model(), DT, 1, 1, mc_temperature=300.0, seed=SEED)
     one.run(2)
-    out = mdt._FakeAtoms(np.zeros((32, 3)), s["z"][parts[0]], s["cell"][0], s["m"][parts[0]], None)
+    out = rh._FakeAtoms(np.zeros((32, 3)), s["z"][parts[0]], s["cell"][0], s["m"][parts[0]], None)
     snap = one.to_atoms(out)
     assert (snap.step, snap.swap_trials, one.num_graphs) == (1, 1, 1) and np.array_equal(out.positions, snap.positions)
     assert snap.swap_log.shape == (1, 1, 4) and snap.swap_log[0, 0, 3] in (1.0, 2.0)

@@ -11,33 +11,23 @@ arm's in `fetch()`).  `fmax` is set out of reach, so every evaluation of a windo
 
 Cases: 108 atoms (3x3x3), 1008 atoms (6x6x7), a batch of 64 structures of 32 atoms (2x2x2), every cell strained by 2 %; model
 of BASELINE configs[1]."""
-import argparse
 import json
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
+from resident_bench import FMAX, RELAX_CASES as CASES, fetched, launch_table, main, model_for, ms, on_device, structures, time_arms  # (sets the path)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(1, os.path.join(ROOT, "tests"))
-sys.path.insert(2, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from hermnet_amd.graph import GraphedBatchMDStep, GraphedMDStep  # noqa: E402
-from hermnet_amd.neighbor import neighbor_search, padded_capacity  # noqa: E402
-from hermnet_amd.relax import DeviceCellRelax, DeviceRelax  # noqa: E402
-from cellrelax_reference import NumpyCellRelax  # noqa: E402
-from relax_bench import CASES, FMAX, model_for, setup  # noqa: E402
+from hermnet_amd.graph import GraphedBatchMDStep, GraphedMDStep
+from hermnet_amd.relax import DeviceCellRelax, DeviceRelax
+from cellrelax_reference import NumpyCellRelax
 
 STRAIN = np.array([[0.02, 0.006, 0.0], [0.0, -0.018, 0.004], [0.005, 0.0, 0.021]])
 
 
 def strained(members, sigma):
     """relax_bench's structures, cells and atoms deformed by I + STRAIN; cells [B,3,3] float64."""
-    pos, cell, z, batch = setup(members, sigma)
+    pos, cell, z, batch = structures(members, sigma)
     d = np.eye(3) + STRAIN
     return pos @ d, np.asarray(cell, dtype=np.float64).reshape(-1, 3, 3) @ d, z, batch
 
@@ -78,51 +68,31 @@ def bench(a):
     for name, members in CASES:
         pos, cell, z, batch = strained(members, a.sigma)
         B = len(members)
-        z_t = torch.from_numpy(z).to(dev)
-        p0 = torch.from_numpy(pos.astype(np.float32)).to(dev)
-        kw = {} if batch is None else dict(batch=torch.from_numpy(batch).to(dev), num_graphs=B)
-        cell_t = torch.from_numpy((cell[0] if batch is None else cell).astype(np.float32)).to(dev)
-        first = int(neighbor_search(p0, 5.0, cell_t, **kw)[0].size(1))
-        capacity = padded_capacity(first, margin=a.margin)                # both arms on the same column count
+        own = cell[0] if batch is None else cell
+        z_t, _, _, kw, first, capacity = on_device(dev, pos, own, z, batch, a.margin)    # both arms on the same column count
         host = HostLoop(model, pos, cell, z, batch, dev, capacity)
-        rx = DeviceCellRelax(model, z_t, cell[0] if batch is None else cell, pos, fmax=FMAX, log_steps=max(a.steps, 64),
-                             capacity=capacity, **kw)
+        rx = DeviceCellRelax(model, z_t, own, pos, fmax=FMAX, log_steps=max(a.steps, 64), capacity=capacity, **kw)
         host.run(10)
         rx.run(10)
         rx.fetch()
-        t_host, t_dev, snap = [], [], None
-        for _ in range(a.rounds):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            host.run(a.steps)
-            torch.cuda.synchronize()
-            t_host.append((time.perf_counter() - t0) / a.steps * 1e3)
-            t0 = time.perf_counter()
-            rx.run(a.steps)
-            snap = rx.fetch()
-            t_dev.append((time.perf_counter() - t0) / a.steps * 1e3)
+        t, last = time_arms([("host", a.steps, host.run, dict(sync=True)), ("dev", a.steps, fetched(rx))], a.rounds)
+        snap = last["dev"]
         same = bool(np.array_equal(snap.positions, host.opt.x) and np.array_equal(snap.cell.reshape(B, 9), host.opt.cell64)
                     and np.array_equal(snap.velocities, host.opt.v))
         row = {"case": name, "atoms": int(len(z)), "graphs": B, "edges_at_start": first, "capacity": capacity,
-               "host_loop_ms": [statistics.median(t_host), min(t_host), max(t_host)],
-               "device_cellrelax_ms": [statistics.median(t_dev), min(t_dev), max(t_dev)],
-               "ratio_host_over_device": statistics.median(t_host) / statistics.median(t_dev),
+               "host_loop_ms": ms(t["host"]), "device_cellrelax_ms": ms(t["dev"]),
+               "ratio_host_over_device": statistics.median(t["host"]) / statistics.median(t["dev"]),
                "device_steps_done": snap.step, "device_halted": bool(snap.halted), "host_loop_lists_complete": bool(host.ok),
                "fmax_at_end": float(snap.fmax.max()), "volume_change": float((snap.volume / np.abs(np.linalg.det(cell))).mean() - 1.0),
                "arms_end_bit_equal": same}
         out["cases"].append(row)
         print(json.dumps(row), flush=True)
-    if a.out:
-        with open(a.out, "w") as fh:
-            json.dump(out, fh, indent=1)
-            fh.write("\n")
+    return out
 
 
 def launches(a):
     """Device activity of two DeviceRelax replays and of two DeviceCellRelax replays (a batch of 3 x 32 atoms): the kernels by
     name and count, and every memcpy / memset the profiler saw."""
-    from collections import Counter
-    from torch.profiler import ProfilerActivity, profile
     dev = torch.device("cuda:0")
     model = model_for(dev)
     pos, cell, z, batch = strained([(2, 2, 2)] * 3, a.sigma)
@@ -133,39 +103,11 @@ def launches(a):
     plain_rx.run(4)
     cell_rx.run(4)
     torch.cuda.synchronize()
-
-    def device_events(fn):
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        return Counter(ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA)
-
-    plain = device_events(lambda: plain_rx.run(2))
-    ours = device_events(lambda: cell_rx.run(2))
-    lines = ["device activity of 2 replays, batch of 3 x 32 atoms: DeviceRelax.run(2) | DeviceCellRelax.run(2)    (count name)"]
-    for name in sorted(set(plain) | set(ours)):
-        lines.append("%4d %4d  %s" % (plain.get(name, 0), ours.get(name, 0), name[:150]))
-    extra = {k: c - plain.get(k, 0) for k, c in ours.items() if c != plain.get(k, 0)}
-    copies = {k: c for k, c in ours.items() if "memcpy" in k.lower() or "memset" in k.lower()}
-    lines.append("kernels: DeviceRelax %d, DeviceCellRelax %d; difference: %s" % (sum(plain.values()), sum(ours.values()), extra))
-    lines.append("memcpy / memset activities inside DeviceCellRelax.run(2): %d %s" % (sum(copies.values()), copies))
-    if not ours:
-        lines.append("(the profiler recorded no device activity for graph launches)")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    with open(a.launches, "w") as fh:
-        fh.write(text)
+    launch_table("device activity of 2 replays, batch of 3 x 32 atoms: DeviceRelax.run(2) | DeviceCellRelax.run(2)",
+                 "DeviceRelax", lambda: plain_rx.run(2), "DeviceCellRelax", lambda: cell_rx.run(2), a.launches)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--sigma", type=float, default=0.05, help="rattle of the start coordinates (A)")
-    ap.add_argument("--margin", type=float, default=0.25, help="columns of the padded list beyond the first count")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--launches", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("cellrelax_bench: needs the GPU (nothing is measured without one)")
-    launches(a) if a.launches else bench(a)
+    main("cellrelax_bench", bench, launches,
+         flags=[("--steps", dict(type=int, default=100)),
+                ("--sigma", dict(type=float, default=0.05, help="rattle of the start coordinates (A)"))])

@@ -16,42 +16,22 @@ ONE process, alternating, same walkers, model, seed and start state; a window en
 Cases: 8 walkers of 32 atoms (2x2x2) and 8 of 108 atoms (3x3x3) of the fcc alloy cell at 600 K, friction 0.01 /fs, dt 1 fs,
 one `Distance` and one `Coordination` over all atoms, each at 0 and at max_hills / 2 = 8192 preloaded hills (pace beyond the
 run: the list stays as long as it is); model of BASELINE configs[1]."""
-import argparse
 import json
-import os
 import re
 import statistics
-import sys
-import time
 
 import numpy as np
+from resident_bench import copies, device_events, fetched, launch_table, main, model_for, ms, on_device, time_arms  # (sets the path)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(1, os.path.join(ROOT, "tests"))
-sys.path.insert(2, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from hermnet_amd import synth  # noqa: E402
-from hermnet_amd.graph import GraphedBatchMDStep  # noqa: E402
-from hermnet_amd.md import AMU_A2_FS2_TO_EV, KB, DeviceMD  # noqa: E402
-from hermnet_amd.metad import Coordination, DeviceMetaD, Distance  # noqa: E402
-from hermnet_amd.neighbor import neighbor_search, padded_capacity  # noqa: E402
-from metad_reference import NumpyMetaD  # noqa: E402
-from relax_bench import model_for  # noqa: E402
+from hermnet_amd.graph import GraphedBatchMDStep
+from hermnet_amd.md import DeviceMD
+from hermnet_amd.metad import Coordination, DeviceMetaD, Distance
+from metad_reference import NumpyMetaD
 
 WALKERS, DT, FRICTION, SEED, T, MAX_HILLS = 8, 1.0, 0.01, 2024, 600.0, 16384
 CASES = [("8 x 32 atoms", (2, 2, 2)), ("8 x 108 atoms", (3, 3, 3))]
-MASS = {13: 26.9815, 28: 58.6934, 29: 63.546}
 HEIGHT, SIGMA, PACE = 0.01, [0.05, 1.0], 10 ** 9
-
-
-def walkers(reps):
-    """(pos, cell [B,3,3], z, masses, batch, velocities) of B copies of one rattled cell, Maxwell-Boltzmann velocities."""
-    pos, cell, z = synth.fcc_alloy_atoms(reps=reps)
-    m = np.tile(np.array([MASS[int(v)] for v in z]), WALKERS)
-    v = np.random.RandomState(1).normal(size=(len(m), 3)) * np.sqrt(KB * T / (m * AMU_A2_FS2_TO_EV))[:, None]
-    return np.tile(pos, (WALKERS, 1)), np.tile(cell, (WALKERS, 1, 1)), np.tile(z, WALKERS), m, np.repeat(np.arange(WALKERS), len(z)), v
 
 
 def cvs_for(n_rep):
@@ -87,10 +67,6 @@ class HostLoop(object):
             self._finish(self.ref.advance())
 
 
-def ms(ts):
-    return [statistics.median(ts), min(ts), max(ts)]
-
-
 def bench(a):
     dev = torch.device("cuda:0")
     model = model_for(dev)
@@ -100,35 +76,20 @@ def bench(a):
                    "step (%d steps per window); %d alternating rounds of %d steps, median (min, max)"
                    % (WALKERS, DT, FRICTION, T, a.host_steps, a.rounds, a.steps), "cases": []}
     for name, reps in CASES:
-        pos, cell, z, m, batch, v = walkers(reps)
+        pos, cell, z, m, batch, v = copies(reps, [T] * WALKERS)
         n_rep = len(z) // WALKERS
-        z_t, cell_t = torch.from_numpy(z).to(dev), torch.from_numpy(cell.astype(np.float32)).to(dev)
-        batch_t = torch.from_numpy(batch).to(dev)
-        p0 = torch.from_numpy(pos.astype(np.float32)).to(dev)
-        first = int(neighbor_search(p0, 5.0, cell_t, batch=batch_t, num_graphs=WALKERS)[0].size(1))
-        capacity = padded_capacity(first, margin=a.margin)               # every arm on the same column count
-        kw = dict(batch=batch_t, num_graphs=WALKERS, seed=SEED, velocities=v, log_steps=max(a.steps, 64), capacity=capacity)
+        z_t, cell_t, _, kw, first, capacity = on_device(dev, pos, cell, z, batch, a.margin)    # every arm on the same column count
+        batch_t = kw["batch"]
+        kw.update(seed=SEED, velocities=v, log_steps=max(a.steps, 64), capacity=capacity)
         for count in (0, MAX_HILLS // 2):
             hills = preloaded(count, n_rep)
             plain = DeviceMD(model, z_t, cell_t, pos, m, DT, temperature=T, friction=FRICTION, **kw)
             ours = DeviceMetaD(model, z_t, cell_t, pos, m, DT, cvs_for(n_rep), HEIGHT, SIGMA, PACE, T, friction=FRICTION,
                                max_hills=MAX_HILLS, hills=hills, **kw)
             host = HostLoop(model, z_t, cell_t, pos, cell, m, batch_t, v, hills, capacity, n_rep)
-            t_plain, t_ours, t_host = [], [], []
-            for _ in range(a.rounds):
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                plain.run(a.steps)
-                psnap = plain.fetch()
-                t_plain.append((time.perf_counter() - t0) / a.steps * 1e3)
-                t0 = time.perf_counter()
-                ours.run(a.steps)
-                snap = ours.fetch()
-                t_ours.append((time.perf_counter() - t0) / a.steps * 1e3)
-                t0 = time.perf_counter()
-                host.run(a.host_steps)
-                torch.cuda.synchronize()
-                t_host.append((time.perf_counter() - t0) / a.host_steps * 1e3)
+            t, last = time_arms([("plain", a.steps, fetched(plain)), ("ours", a.steps, fetched(ours)),
+                                 ("host", a.host_steps, host.run, dict(sync=True))], a.rounds)
+            t_plain, t_ours, t_host, psnap, snap = t["plain"], t["ours"], t["host"], last["plain"], last["ours"]
             row = {"case": name, "atoms": int(len(z)), "walkers": WALKERS, "hills": count, "edges_at_start": first,
                    "capacity": capacity, "device_md_ms": ms(t_plain), "device_metad_ms": ms(t_ours), "host_loop_ms": ms(t_host),
                    "bias_cost_ms": statistics.median(t_ours) - statistics.median(t_plain),
@@ -140,78 +101,46 @@ def bench(a):
                    "largest_bias_force": float(np.abs(snap.bias_forces).max())}
             out["cases"].append(row)
             print(json.dumps(row), flush=True)
-    if a.out:
-        with open(a.out, "w") as fh:
-            json.dump(out, fh, indent=1)
-            fh.write("\n")
+    return out
 
 
 def launches(a):
     """Device activity of two DeviceMD replays and of two DeviceMetaD replays on the same batch of 8 x 32 atoms: the kernels
     by name and count, every memcpy / memset the profiler saw, and the mean device time of the stage's four kernels in both
     cases at 0 and at 8192 hills (the pair kernel is metad_cv_kernel)."""
-    from collections import Counter
-    from torch.profiler import ProfilerActivity, profile
     dev = torch.device("cuda:0")
     model = model_for(dev)
-
-    def device_events(fn):
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        return [ev for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA]
-
     lines = []
     for name, reps in CASES:
-        pos, cell, z, m, batch, v = walkers(reps)
+        pos, cell, z, m, batch, v = copies(reps, [T] * WALKERS)
         n_rep = len(z) // WALKERS
         z_t, cell_t = torch.from_numpy(z).to(dev), torch.from_numpy(cell.astype(np.float32)).to(dev)
         kw = dict(batch=torch.from_numpy(batch).to(dev), num_graphs=WALKERS, seed=SEED, velocities=v)
-        plain_md = DeviceMD(model, z_t, cell_t, pos, m, DT, temperature=T, friction=FRICTION, **kw)
-        plain_md.run(4)
-        torch.cuda.synchronize()
-        plain = Counter(ev.name for ev in device_events(lambda: plain_md.run(2)))
         for count in (0, MAX_HILLS // 2):
             biased = DeviceMetaD(model, z_t, cell_t, pos, m, DT, cvs_for(n_rep), HEIGHT, SIGMA, PACE, T, friction=FRICTION,
                                  max_hills=MAX_HILLS, hills=preloaded(count, n_rep), **kw)
             biased.run(4)
             torch.cuda.synchronize()
-            events = device_events(lambda: biased.run(20))
             times = {}
-            for ev in events:
+            for ev in device_events(lambda: biased.run(20)):
                 kernel = re.search(r"metad_\w+", ev.name)
                 if kernel:
                     times.setdefault(kernel.group(0), []).append(ev.device_time)
             lines.append("%s, %d hills: mean device time per launch over 20 replays (us): %s"
                          % (name, count, {k: round(statistics.mean(t), 2) for k, t in sorted(times.items())}))
             if name == CASES[0][0] and count == 0:
-                ours = Counter(ev.name for ev in device_events(lambda: biased.run(2)))
-                head = ["device activity of 2 replays, batch of 8 x 32 atoms: DeviceMD.run(2) | DeviceMetaD.run(2)    (count name)"]
-                for k in sorted(set(plain) | set(ours)):
-                    head.append("%4d %4d  %s" % (plain.get(k, 0), ours.get(k, 0), k[:150]))
-                extra = {k[:100]: c - plain.get(k, 0) for k, c in ours.items() if c != plain.get(k, 0)}
-                extra.update({k[:100]: -c for k, c in plain.items() if k not in ours})
-                copies = {k: c for k, c in ours.items() if "memcpy" in k.lower() or "memset" in k.lower()}
-                head.append("kernels: DeviceMD %d, DeviceMetaD %d; difference: %s" % (sum(plain.values()), sum(ours.values()), extra))
-                head.append("memcpy / memset activities inside DeviceMetaD.run(2): %d %s" % (sum(copies.values()), copies))
-                if not ours:
-                    head.append("(the profiler recorded no device activity for graph launches)")
-                lines = head + lines
+                plain_md = DeviceMD(model, z_t, cell_t, pos, m, DT, temperature=T, friction=FRICTION, **kw)
+                plain_md.run(4)
+                torch.cuda.synchronize()
+                launch_table("device activity of 2 replays, batch of 8 x 32 atoms: DeviceMD.run(2) | DeviceMetaD.run(2)",
+                             "DeviceMD", lambda: plain_md.run(2), "DeviceMetaD", lambda: biased.run(2), a.launches)
     text = "\n".join(lines) + "\n"
     print(text)
-    with open(a.launches, "w") as fh:
+    with open(a.launches, "a") as fh:                   # behind the table
         fh.write(text)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--host-steps", type=int, default=10, help="steps of the host-loop arm per window")
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--margin", type=float, default=0.25, help="columns of the padded list beyond the first count")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--launches", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("metad_bench: needs the GPU (nothing is measured without one)")
-    launches(a) if a.launches else bench(a)
+    main("metad_bench", bench, launches,
+         flags=[("--steps", dict(type=int, default=200)),
+                ("--host-steps", dict(type=int, default=10, help="steps of the host-loop arm per window"))])

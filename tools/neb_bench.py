@@ -10,27 +10,17 @@ device arm's in `fetch()`).  `fmax` is set out of reach, so every evaluation of 
 
 Cases: one band of 8 images of 32 atoms (2x2x2) and one of 8 images of 108 atoms (3x3x3): an fcc alloy cell rattled with two
 seeds as the end points, linear interpolation between them, climbing image on; model of BASELINE configs[1]."""
-import argparse
 import json
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
+from resident_bench import FMAX, fetched, launch_table, main, model_for, ms, on_device, time_arms  # (sets the path)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(1, os.path.join(ROOT, "tests"))
-sys.path.insert(2, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from hermnet_amd import neb, synth  # noqa: E402
-from hermnet_amd.graph import GraphedBatchMDStep  # noqa: E402
-from hermnet_amd.neighbor import neighbor_search, padded_capacity  # noqa: E402
-from hermnet_amd.relax import DeviceRelax  # noqa: E402
-from neb_reference import NumpyNEB, layout  # noqa: E402
-from relax_bench import FMAX, model_for  # noqa: E402
+from hermnet_amd import neb, synth
+from hermnet_amd.graph import GraphedBatchMDStep
+from hermnet_amd.relax import DeviceRelax
+from neb_reference import NumpyNEB, layout
 
 IMAGES = 8
 CASES = [("8 x 32 atoms", (2, 2, 2)), ("8 x 108 atoms", (3, 3, 3))]
@@ -72,48 +62,28 @@ def bench(a):
                    "alternating rounds of %d evaluations, median (min, max)" % (a.sigma, a.rounds, a.steps), "cases": []}
     for name, reps in CASES:
         pos, cell, z, batch, graph_ptr, band_ptr = band(reps, a.sigma)
-        z_t, cell_t = torch.from_numpy(z).to(dev), torch.from_numpy(cell.astype(np.float32)).to(dev)
-        batch_t = torch.from_numpy(batch).to(dev)
-        p0 = torch.from_numpy(pos.astype(np.float32)).to(dev)
-        first = int(neighbor_search(p0, 5.0, cell_t, batch=batch_t, num_graphs=IMAGES)[0].size(1))
-        capacity = padded_capacity(first, margin=a.margin)                # both arms on the same column count
-        host = HostLoop(model, pos, cell_t, z_t, batch_t, graph_ptr, band_ptr, dev, capacity)
-        nb = neb.DeviceNEB(model, z_t, cell_t, pos, batch=batch_t, num_graphs=IMAGES, k=0.1, climb=True, fmax=FMAX,
-                           log_steps=max(a.steps, 64), capacity=capacity)
+        z_t, cell_t, _, kw, first, capacity = on_device(dev, pos, cell, z, batch, a.margin)    # both arms on the same column count
+        host = HostLoop(model, pos, cell_t, z_t, kw["batch"], graph_ptr, band_ptr, dev, capacity)
+        nb = neb.DeviceNEB(model, z_t, cell_t, pos, k=0.1, climb=True, fmax=FMAX, log_steps=max(a.steps, 64), capacity=capacity, **kw)
         host.run(10)
         nb.run(10)
         nb.fetch()
-        t_host, t_dev, snap = [], [], None
-        for _ in range(a.rounds):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            host.run(a.steps)
-            torch.cuda.synchronize()
-            t_host.append((time.perf_counter() - t0) / a.steps * 1e3)
-            t0 = time.perf_counter()
-            nb.run(a.steps)
-            snap = nb.fetch()
-            t_dev.append((time.perf_counter() - t0) / a.steps * 1e3)
+        t, last = time_arms([("host", a.steps, host.run, dict(sync=True)), ("dev", a.steps, fetched(nb))], a.rounds)
+        snap = last["dev"]
         same = bool(np.array_equal(snap.positions, host.opt.x) and np.array_equal(snap.velocities, host.opt.v))
         row = {"case": name, "atoms": int(len(z)), "images": IMAGES, "edges_at_start": first, "capacity": capacity,
-               "host_loop_ms": [statistics.median(t_host), min(t_host), max(t_host)],
-               "device_neb_ms": [statistics.median(t_dev), min(t_dev), max(t_dev)],
-               "ratio_host_over_device": statistics.median(t_host) / statistics.median(t_dev),
+               "host_loop_ms": ms(t["host"]), "device_neb_ms": ms(t["dev"]),
+               "ratio_host_over_device": statistics.median(t["host"]) / statistics.median(t["dev"]),
                "device_steps_done": snap.step, "device_halted": bool(snap.halted), "host_loop_lists_complete": bool(host.ok),
                "fmax_at_end": float(snap.fmax.max()), "climbing_image": int(snap.climbing_image[0]), "arms_end_bit_equal": same}
         out["cases"].append(row)
         print(json.dumps(row), flush=True)
-    if a.out:
-        with open(a.out, "w") as fh:
-            json.dump(out, fh, indent=1)
-            fh.write("\n")
+    return out
 
 
 def launches(a):
     """Device activity of two DeviceRelax replays and of two DeviceNEB replays on the same batch of 5 x 32 atoms: the kernels
     by name and count, and every memcpy / memset the profiler saw."""
-    from collections import Counter
-    from torch.profiler import ProfilerActivity, profile
     dev = torch.device("cuda:0")
     model = model_for(dev)
     pos, cell, z, batch, graph_ptr, band_ptr = band((2, 2, 2), a.sigma, images=5)
@@ -124,39 +94,11 @@ def launches(a):
     plain_rx.run(4)
     band_nb.run(4)
     torch.cuda.synchronize()
-
-    def device_events(fn):
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        return Counter(ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA)
-
-    plain = device_events(lambda: plain_rx.run(2))
-    ours = device_events(lambda: band_nb.run(2))
-    lines = ["device activity of 2 replays, batch of 5 x 32 atoms: DeviceRelax.run(2) | DeviceNEB.run(2)    (count name)"]
-    for name in sorted(set(plain) | set(ours)):
-        lines.append("%4d %4d  %s" % (plain.get(name, 0), ours.get(name, 0), name[:150]))
-    extra = {k[:100]: c - plain.get(k, 0) for k, c in ours.items() if c != plain.get(k, 0)}
-    copies = {k: c for k, c in ours.items() if "memcpy" in k.lower() or "memset" in k.lower()}
-    lines.append("kernels: DeviceRelax %d, DeviceNEB %d; difference: %s" % (sum(plain.values()), sum(ours.values()), extra))
-    lines.append("memcpy / memset activities inside DeviceNEB.run(2): %d %s" % (sum(copies.values()), copies))
-    if not ours:
-        lines.append("(the profiler recorded no device activity for graph launches)")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    with open(a.launches, "w") as fh:
-        fh.write(text)
+    launch_table("device activity of 2 replays, batch of 5 x 32 atoms: DeviceRelax.run(2) | DeviceNEB.run(2)",
+                 "DeviceRelax", lambda: plain_rx.run(2), "DeviceNEB", lambda: band_nb.run(2), a.launches)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--sigma", type=float, default=0.08, help="rattle of the two end points (A)")
-    ap.add_argument("--margin", type=float, default=0.25, help="columns of the padded list beyond the first count")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--launches", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("neb_bench: needs the GPU (nothing is measured without one)")
-    launches(a) if a.launches else bench(a)
+    main("neb_bench", bench, launches,
+         flags=[("--steps", dict(type=int, default=100)),
+                ("--sigma", dict(type=float, default=0.08, help="rattle of the two end points (A)"))])

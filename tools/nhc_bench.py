@@ -14,39 +14,19 @@ alternating, same batch, model and start state; a window ends in a synchronisati
 
 Cases: 1 x 108 atoms (3x3x3), 1 x 1008 atoms (6x6x7) and 64 x 32 atoms (2x2x2; 64 DIFFERENT cells) of the fcc alloy; 600 K,
 tau 100 fs (Langevin: friction 0.01 /fs), dt 1 fs; model of BASELINE configs[1]."""
-import argparse
 import json
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
+from resident_bench import cells, fetched, launch_table, main, model_for, ms, on_device, time_arms  # (sets the path)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(1, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
-
-from hermnet_amd import synth  # noqa: E402
-from hermnet_amd.graph import GraphedBatchMDStep  # noqa: E402
-from hermnet_amd.md import AMU_A2_FS2_TO_EV, KB, DeviceMD  # noqa: E402
-from hermnet_amd.neighbor import neighbor_search, padded_capacity  # noqa: E402
-from hermnet_amd.nhc import DeviceNHC, chain_tables  # noqa: E402
-from relax_bench import model_for  # noqa: E402
+from hermnet_amd.graph import GraphedBatchMDStep
+from hermnet_amd.md import AMU_A2_FS2_TO_EV, DeviceMD
+from hermnet_amd.nhc import DeviceNHC, chain_tables
 
 DT, FRICTION, SEED, T, TAU, CHAIN, ORDER = 1.0, 0.01, 2024, 600.0, 100.0, 3, 3
 CASES = [("1 x 108 atoms", 1, (3, 3, 3)), ("1 x 1008 atoms", 1, (6, 6, 7)), ("64 x 32 atoms", 64, (2, 2, 2))]
-MASS = {13: 26.9815, 28: 58.6934, 29: 63.546}
-
-
-def members(B, reps):
-    """(pos, cell [B,3,3], z, masses, batch, velocities) of B different rattled cells, Maxwell-Boltzmann velocities."""
-    parts = [synth.fcc_alloy_atoms(reps=reps, seed=g) for g in range(B)]
-    pos, z = np.concatenate([p[0] for p in parts]), np.concatenate([p[2] for p in parts])
-    m = np.array([MASS[int(v)] for v in z])
-    v = np.random.RandomState(1).normal(size=(len(m), 3)) * np.sqrt(KB * T / (m * AMU_A2_FS2_TO_EV))[:, None]
-    return pos, np.stack([p[1] for p in parts]), z, m, np.repeat(np.arange(B), [len(p[0]) for p in parts]), v
 
 
 class HostLoop(object):
@@ -108,10 +88,6 @@ class HostLoop(object):
         self.steps += steps
 
 
-def ms(ts):
-    return [statistics.median(ts), min(ts), max(ts)]
-
-
 def bench(a):
     dev = torch.device("cuda:0")
     model = model_for(dev)
@@ -120,30 +96,17 @@ def bench(a):
                    "chains + GraphedBatchMDStep + fetch() every step; %d alternating rounds of %d steps, median (min, max)"
                    % (DT, T, FRICTION, TAU, CHAIN, ORDER, a.rounds, a.steps), "cases": []}
     for name, B, reps in CASES:
-        pos, cell, z, m, batch, v = members(B, reps)
-        z_t, cell_t = torch.from_numpy(z).to(dev), torch.from_numpy(cell.astype(np.float32)).to(dev)
-        batch_t = torch.from_numpy(batch).to(dev)
-        p0 = torch.from_numpy(pos.astype(np.float32)).to(dev)
-        first = int(neighbor_search(p0, 5.0, cell_t, batch=batch_t, num_graphs=B)[0].size(1))
-        capacity = padded_capacity(first, margin=a.margin)                       # every arm on the same column count
-        kw = dict(batch=batch_t, num_graphs=B, velocities=v, log_steps=max(a.steps, 64), capacity=capacity, temperature=T)
+        pos, cell, z, m, batch, v = cells([reps] * B, T)
+        z_t, cell_t, p0, kw, first, capacity = on_device(dev, pos, cell, z, batch, a.margin)    # every arm on the same column count
+        batch_t = kw["batch"]
+        kw.update(velocities=v, log_steps=max(a.steps, 64), capacity=capacity, temperature=T)
         plain = DeviceMD(model, z_t, cell_t, pos, m, DT, friction=FRICTION, seed=SEED, **kw)
         ours = DeviceNHC(model, z_t, cell_t, pos, m, DT, tau=TAU, chain=CHAIN, order=ORDER, **kw)
         host = HostLoop(GraphedBatchMDStep(model, z_t, cell_t, p0, batch_t, B, capacity=capacity), pos, v, m, batch, cell, ours.dof)
-        t_plain, t_ours, t_host = [], [], []
-        for _ in range(a.rounds):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            plain.run(a.steps)
-            psnap = plain.fetch()
-            t_plain.append((time.perf_counter() - t0) / a.steps * 1e3)
-            t0 = time.perf_counter()
-            ours.run(a.steps)
-            snap = ours.fetch()
-            t_ours.append((time.perf_counter() - t0) / a.steps * 1e3)
-            t0 = time.perf_counter()
-            host.run(a.steps)
-            t_host.append((time.perf_counter() - t0) / a.steps * 1e3)
+        # (the host loop's window ends in its last step's fetch())
+        t, last = time_arms([("plain", a.steps, fetched(plain)), ("ours", a.steps, fetched(ours)), ("host", a.steps, host.run)],
+                            a.rounds)
+        t_plain, t_ours, t_host, psnap, snap = t["plain"], t["ours"], t["host"], last["plain"], last["ours"]
         md_ms, ours_ms = statistics.median(t_plain), statistics.median(t_ours)
         row = {"case": name, "atoms": int(len(z)), "graphs": B, "edges_at_start": first, "capacity": capacity,
                "device_md_langevin_ms": ms(t_plain), "device_nhc_ms": ms(t_ours), "host_loop_ms": ms(t_host),
@@ -154,58 +117,25 @@ def bench(a):
                "host_loop_max_abs_dx_vs_device": float(np.abs(host.x - snap.positions).max())}
         out["cases"].append(row)
         print(json.dumps(row), flush=True)
-    if a.out:
-        with open(a.out, "w") as fh:
-            json.dump(out, fh, indent=1)
-            fh.write("\n")
+    return out
 
 
 def launches(a):
     """Device activity of two DeviceMD (NVE) replays and of two DeviceNHC replays on the same batch of 5 x 32 atoms: the kernels
     by name and count, and every memcpy / memset the profiler saw."""
-    from collections import Counter
-    from torch.profiler import ProfilerActivity, profile
     dev = torch.device("cuda:0")
     model = model_for(dev)
-    pos, cell, z, m, batch, v = members(5, (2, 2, 2))
+    pos, cell, z, m, batch, v = cells([(2, 2, 2)] * 5, T)
     z_t, cell_t = torch.from_numpy(z).to(dev), torch.from_numpy(cell.astype(np.float32)).to(dev)
     kw = dict(batch=torch.from_numpy(batch).to(dev), num_graphs=5, velocities=v)
     plain_md = DeviceMD(model, z_t, cell_t, pos, m, DT, **kw)
     nhc_md = DeviceNHC(model, z_t, cell_t, pos, m, DT, temperature=T, tau=TAU, chain=CHAIN, order=ORDER, **kw)
-    def device_events(driver):
-        driver.run(2)
-        torch.cuda.synchronize()
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            driver.run(2)
-            torch.cuda.synchronize()
-        return Counter(ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA)
-
-    ours = device_events(nhc_md)
-    plain = device_events(plain_md)
-    lines = ["device activity of 2 replays, batch of 5 x 32 atoms: DeviceMD.run(2) (NVE) | DeviceNHC.run(2)    (count name)"]
-    for name in sorted(set(plain) | set(ours)):
-        lines.append("%4d %4d  %s" % (plain.get(name, 0), ours.get(name, 0), name[:150]))
-    extra = {k[:100]: c - plain.get(k, 0) for k, c in ours.items() if c != plain.get(k, 0)}
-    extra.update({k[:100]: -c for k, c in plain.items() if k not in ours})
-    copies = {k: c for k, c in ours.items() if "memcpy" in k.lower() or "memset" in k.lower()}
-    lines.append("kernels: DeviceMD %d, DeviceNHC %d; difference: %s" % (sum(plain.values()), sum(ours.values()), extra))
-    lines.append("memcpy / memset activities inside DeviceNHC.run(2): %d %s" % (sum(copies.values()), copies))
-    if not ours:
-        lines.append("(the profiler recorded no device activity for graph launches)")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    with open(a.launches, "w") as fh:
-        fh.write(text)
+    plain_md.run(2)
+    nhc_md.run(2)
+    torch.cuda.synchronize()
+    launch_table("device activity of 2 replays, batch of 5 x 32 atoms: DeviceMD.run(2) (NVE) | DeviceNHC.run(2)",
+                 "DeviceMD", lambda: plain_md.run(2), "DeviceNHC", lambda: nhc_md.run(2), a.launches)
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--margin", type=float, default=0.25, help="columns of the padded list beyond the first count")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--launches", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("nhc_bench: needs the GPU (nothing is measured without one)")
-    launches(a) if a.launches else bench(a)
+    main("nhc_bench", bench, launches, flags=[("--steps", dict(type=int, default=200))])

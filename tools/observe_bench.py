@@ -17,44 +17,18 @@ and the pair-histogram kernel alone on the largest cell (hip events around its t
 
 Cases: 108 atoms (3x3x3), 1008 atoms (6x6x7), a batch of 64 x 32 atoms (2x2x2), BASELINE configs[1] (10x10x25: 10,000 atoms --
 its host loop runs `--big-steps` steps in one round: numpy walks 5e7 pairs per sample); NVE, model of configs[1]."""
-import argparse
 import json
-import os
 import statistics
-import sys
-import time
 
 import numpy as np
+from resident_bench import cells, fetched, launch_table, main, model_for, ms, on_device, time_arms  # (sets the path)
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(1, os.path.join(ROOT, "tests"))
-sys.path.insert(2, os.path.join(ROOT, "tools"))
-import torch  # noqa: E402
+from hermnet_amd.md import DeviceMD
 
-from hermnet_amd import synth  # noqa: E402
-from hermnet_amd.md import AMU_A2_FS2_TO_EV, KB, DeviceMD  # noqa: E402
-from hermnet_amd.neighbor import neighbor_search, padded_capacity  # noqa: E402
-from relax_bench import model_for  # noqa: E402
-
-MASS = {13: 26.9815, 28: 58.6934, 29: 63.546}
 CASES = [("108 atoms", [(3, 3, 3)], 5.0), ("1008 atoms", [(6, 6, 7)], 5.0), ("64 x 32 atoms", [(2, 2, 2)] * 64, 3.5),
          ("configs[1], 10000 atoms", [(10, 10, 25)], 6.0)]
 BINS, STRIDE, FRAME_STRIDE = 120, 5, 10
-
-
-def system(members, temp):
-    """(pos, cells [B,3,3], z, masses, batch, velocities) of a batch of rattled alloy cells."""
-    parts = [synth.fcc_alloy_atoms(reps=r, seed=s) for s, r in enumerate(members)]
-    pos, z = np.concatenate([p[0] for p in parts]), np.concatenate([p[2] for p in parts])
-    batch = np.repeat(np.arange(len(parts)), [len(p[0]) for p in parts])
-    m = np.array([MASS[int(v)] for v in z])
-    v = np.random.RandomState(1).normal(size=pos.shape) * np.sqrt(KB * temp / (m * AMU_A2_FS2_TO_EV))[:, None]
-    return pos, np.stack([p[1] for p in parts]), z, m, batch, v
-
-
-def ms(ts):
-    return [statistics.median(ts), min(ts), max(ts)]
 
 
 class HostLoop(object):
@@ -111,42 +85,29 @@ def bench(a):
     for name, members, r_max in CASES:
         if a.only and a.only not in name:
             continue
-        pos, cells, z, m, batch, v = system(members, a.temp)
+        pos, cell, z, m, batch, v = cells(members, a.temp)
         B, big = len(members), len(z) > 5000
-        z_t, cells_t, batch_t = torch.from_numpy(z).to(dev), torch.from_numpy(cells.astype(np.float32)).to(dev), torch.from_numpy(batch).to(dev)
-        p0 = torch.from_numpy(pos.astype(np.float32)).to(dev)
-        first = int(neighbor_search(p0, 5.0, cells_t, batch=batch_t, num_graphs=B)[0].size(1))
-        kw = dict(velocities=v, batch=batch_t, num_graphs=B, log_steps=max(a.steps, 64), capacity=padded_capacity(first, margin=a.margin))
+        z_t, cells_t, _, kw, first, capacity = on_device(dev, pos, cell, z, batch, a.margin)
+        kw.update(velocities=v, log_steps=max(a.steps, 64), capacity=capacity)
         plain = DeviceMD(model, z_t, cells_t, pos, m, a.dt, **kw)
-        row = {"case": name, "atoms": int(len(z)), "graphs": B, "edges_at_start": first, "capacity": kw["capacity"]}
+        row = {"case": name, "atoms": int(len(z)), "graphs": B, "edges_at_start": first, "capacity": capacity}
+        arms = [("a", a.steps, fetched(plain))]
         if a.plain_only:
-            observed = host = None
+            observed = None
         else:
             from hermnet_amd.observe import MSD, RDF, Frames
             obs = [Frames(stride=FRAME_STRIDE, frames=64), RDF(r_max=r_max, bins=BINS, stride=STRIDE), MSD(stride=STRIDE, rows=64)]
             observed = DeviceMD(model, z_t, cells_t, pos, m, a.dt, observers=obs, **kw)
-            host = HostLoop(DeviceMD(model, z_t, cells_t, pos, m, a.dt, **kw), z, np.searchsorted(batch, np.arange(B + 1)), cells, r_max)
+            host = HostLoop(DeviceMD(model, z_t, cells_t, pos, m, a.dt, **kw), z, np.searchsorted(batch, np.arange(B + 1)), cell, r_max)
             row.update(r_max=r_max, rdf_workgroups=int(obs[1].work.shape[0]))
-        t_a, t_b, t_c, sa, sb, sc = [], [], [], None, None, None
-        for r in range(a.rounds):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            plain.run(a.steps)
-            sa = plain.fetch()
-            t_a.append((time.perf_counter() - t0) / a.steps * 1e3)
-            if observed is None:
-                continue
-            t0 = time.perf_counter()
-            observed.run(a.steps)
-            sb = observed.fetch()
-            t_b.append((time.perf_counter() - t0) / a.steps * 1e3)
             steps_c = a.big_steps if big else a.steps
-            if not big or r == 0:
-                t0 = time.perf_counter()
-                sc = host.run(steps_c)
-                t_c.append((time.perf_counter() - t0) / steps_c * 1e3)
+            # (the host loop's window ends in its last fetch(); on the big cell it takes part in the first round alone)
+            arms += [("b", a.steps, fetched(observed)), ("c", steps_c, host.run, dict(rounds=lambda r: not big or r == 0))]
+        t, last = time_arms(arms, a.rounds)
+        t_a, sa = t["a"], last["a"]
         row.update(plain_ms=ms(t_a), steps_done=int(sa.step), halted=bool(sa.halted))
         if observed is not None:
+            t_b, t_c, sb, sc = t["b"], t["c"], last["b"], last["c"]
             same = bool(np.array_equal(sa.positions.view(np.uint64), sb.positions.view(np.uint64)) and sa.step == sb.step)
             rdf = sb.observers[1]
             counts_equal = None
@@ -169,10 +130,7 @@ def bench(a):
     if a.parent:
         with open(a.parent) as fh:
             add_parent(out, json.load(fh))
-    if a.out:
-        with open(a.out, "w") as fh:
-            json.dump(out, fh, indent=1)
-            fh.write("\n")
+    return out
 
 
 def add_parent(out, parent):
@@ -189,56 +147,25 @@ def add_parent(out, parent):
 def launches(a):
     """Device activity of two replays of DeviceMD without and with the three observers (108 atoms): the kernels by name and
     count, and every memcpy / memset the profiler saw."""
-    from collections import Counter
-    from torch.profiler import ProfilerActivity, profile
     from hermnet_amd.observe import MSD, RDF, Frames
     dev = torch.device("cuda:0")
     model = model_for(dev)
-    pos, cells, z, m, batch, v = system([(3, 3, 3)], a.temp)
-    z_t, cell_t = torch.from_numpy(z).to(dev), torch.from_numpy(cells[0].astype(np.float32)).to(dev)
+    pos, cell, z, m, batch, v = cells([(3, 3, 3)], a.temp)
+    z_t, cell_t = torch.from_numpy(z).to(dev), torch.from_numpy(cell[0].astype(np.float32)).to(dev)
     plain_md = DeviceMD(model, z_t, cell_t, pos, m, a.dt, velocities=v)
     observed = DeviceMD(model, z_t, cell_t, pos, m, a.dt, velocities=v,
                         observers=[Frames(stride=FRAME_STRIDE), RDF(r_max=5.0, bins=BINS, stride=STRIDE), MSD(stride=STRIDE)])
     plain_md.run(4)
     observed.run(4)
     torch.cuda.synchronize()
-
-    def device_events(fn):
-        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        return Counter(ev.name for ev in prof.events() if ev.device_type == torch.autograd.DeviceType.CUDA)
-
-    plain, ours = device_events(lambda: plain_md.run(2)), device_events(lambda: observed.run(2))
-    lines = ["device activity of 2 replays, 108 atoms: DeviceMD.run(2) | DeviceMD(observers=[Frames, RDF, MSD]).run(2)    (count name)"]
-    for name in sorted(set(plain) | set(ours)):
-        lines.append("%4d %4d  %s" % (plain.get(name, 0), ours.get(name, 0), name[:150]))
-    extra = {k[:100]: c - plain.get(k, 0) for k, c in ours.items() if c != plain.get(k, 0)}
-    copies = {k: c for k, c in ours.items() if "memcpy" in k.lower() or "memset" in k.lower()}
-    lines.append("kernels: plain %d, observed %d; difference: %s" % (sum(plain.values()), sum(ours.values()), extra))
-    lines.append("memcpy / memset activities inside the observed run(2): %d %s" % (sum(copies.values()), copies))
-    if not ours:
-        lines.append("(the profiler recorded no device activity for graph launches)")
-    text = "\n".join(lines) + "\n"
-    print(text)
-    with open(a.launches, "w") as fh:
-        fh.write(text)
+    launch_table("device activity of 2 replays, 108 atoms: DeviceMD.run(2) | DeviceMD(observers=[Frames, RDF, MSD]).run(2)",
+                 "plain", lambda: plain_md.run(2), "observed", lambda: observed.run(2), a.launches, inside="the observed run(2)")
 
 
 if __name__ == "__main__":
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--rounds", type=int, default=5)
-    ap.add_argument("--big-steps", type=int, default=10, help="steps of the host loop's one round on the 10,000-atom cell")
-    ap.add_argument("--dt", type=float, default=0.5)
-    ap.add_argument("--temp", type=float, default=300.0)
-    ap.add_argument("--margin", type=float, default=0.25, help="columns of the padded list beyond the first count")
-    ap.add_argument("--only", default=None, help="cases whose name contains this")
-    ap.add_argument("--plain-only", action="store_true")
-    ap.add_argument("--parent", default=None, help="the --out of a --plain-only run on the parent commit: recorded beside every case")
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--launches", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        sys.exit("observe_bench: needs the GPU (nothing is measured without one)")
-    launches(a) if a.launches else bench(a)
+    main("observe_bench", bench, launches,
+         flags=[("--steps", dict(type=int, default=200)),
+                ("--big-steps", dict(type=int, default=10, help="steps of the host loop's one round on the 10,000-atom cell")),
+                ("--dt", dict(type=float, default=0.5)), ("--temp", dict(type=float, default=300.0)),
+                ("--only", dict(default=None, help="cases whose name contains this")), ("--plain-only", dict(action="store_true")),
+                ("--parent", dict(default=None, help="the --out of a --plain-only run on the parent commit: recorded beside every case"))])

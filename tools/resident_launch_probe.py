@@ -13,20 +13,19 @@ ROOT = os.path.abspath(sys.argv[1] if len(sys.argv) > 1 else os.path.join(os.pat
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tools"), os.path.join(ROOT, "tests")]
 import torch  # noqa: E402
 
-import md_device_bench as mb  # noqa: E402
-import relax_bench as rb  # noqa: E402
+import resident_bench as rb  # noqa: E402
 from hermnet_amd.md import DeviceMD  # noqa: E402
 from hermnet_amd.relax import DeviceRelax  # noqa: E402
 
 dev = torch.device("cuda:0")
-model = mb.model_for(dev)
-pos, cell, z, m, v = mb.setup((3, 3, 3), dev, 300.0)
+model = rb.model_for(dev)
+pos, cell, z, m, v = rb.setup((3, 3, 3), 300.0)
 md = DeviceMD(model, torch.from_numpy(z).to(dev), torch.from_numpy(cell.astype(np.float32)).to(dev), pos, m, 0.5, velocities=v,
               friction=0.01, temperature=300.0)
 md.run(5)
 s = md.fetch()
 print("md", ROOT, s.step, s.halted, float(s.log[-1, 0, 0]), float(s.log[-1, 0, 1]))
-pos, cell, z, batch = rb.setup([(2, 2, 2)] * 3, 0.05)
+pos, cell, z, batch = rb.structures([(2, 2, 2)] * 3, 0.05)
 rx = DeviceRelax(model, torch.from_numpy(z).to(dev), torch.from_numpy(cell.astype(np.float32)).to(dev), pos,
                  batch=torch.from_numpy(batch).to(dev), num_graphs=3, fmax=1e-6)
 rx.run(5)
