@@ -14,6 +14,7 @@ from .observe import Frames, MSD, RDF  # noqa: F401
 from .metad import Coordination, DeviceMetaD, Distance, bias_on_grid, free_energy  # noqa: F401
 from .swapmc import DeviceSwapMD  # noqa: F401
 from .nhc import DeviceNHC  # noqa: F401
+from .mtk import DeviceMTK  # noqa: F401
 from .rmnet import PaiNNModule, PaiNNMessage, PaiNNUpdate, ScaledSiLU, RadialBasis  # noqa: F401
 
 __version__ = "0.1.0"

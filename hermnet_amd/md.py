@@ -301,8 +301,9 @@ class DeviceNPT(DeviceMD):
     scaling) and `clamped` [B] (how often a safety condition acted).  A void step, a prime and the parked replays of a capture
     never scale, so halt and `resume()` are `DeviceMD`'s.
 
-    Out of scope: stochastic cell rescaling and MTK (barostats that sample the correct ensemble), velocity scaling, atom
-    shards, HTNet, open structures (they have no volume).  (Relaxing a cell, under pressure too: `relax.DeviceCellRelax`.)"""
+    Out of scope: stochastic cell rescaling (a barostat that samples the correct ensemble: `mtk.DeviceMTK`), velocity
+    scaling, atom shards, HTNet, open structures (they have no volume).  (Relaxing a cell, under pressure too:
+    `relax.DeviceCellRelax`.)"""
 
     __slots__ = ("pressure", "compressibility", "taup", "coupling", "mask", "max_strain", "cell64", "mu", "clamped", "p0",
                  "coupling_c", "_cell_given")

@@ -30,8 +30,8 @@ centre of mass is thermostatted as if it were heat) --, and 3 n_free for a graph
 Halt protocol: `DeviceMD`'s.  A void step returns the chain (xi, v_xi) to the start of the step with the atoms; a prime and
 the parked replays of a capture leave it alone, so a resumed run equals an uninterrupted one, chain state included.
 
-Out of scope: combination with `DeviceNPT` / `DeviceREMD` / `DevicePIMD` / `DeviceMetaD` / `DeviceSwapMD`, an MTK barostat
-(it would stand on this), per-atom ("massive") chains, atom shards, HTNet."""
+Out of scope: combination with `DeviceNPT` / `DeviceREMD` / `DevicePIMD` / `DeviceMetaD` / `DeviceSwapMD` (the MTK barostat
+that stands on this: `mtk.DeviceMTK`), per-atom ("massive") chains, atom shards, HTNet."""
 import numpy as np
 import torch
 

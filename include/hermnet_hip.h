@@ -1484,6 +1484,85 @@ int hermnet_host_nhc_finish(int num_atoms, int num_graphs, const int* graph_ptr_
                             double* xi0_host, double* v_xi0_host, double* scale_host, double* log_host, long log_steps,
                             long* state_host);
 
+/* Nose-Hoover (MTK) barostat NPT inside the replayed MD step (added within ABI v13: new entry points only; hermnet_amd/mtk.py:
+ * DeviceMTK; csrc/mtk_kernels.hip, mtk_step.h -- the definition of the step, operation by operation, is that header's).
+ * hermnet_mtk_advance stands in the place of hermnet_md_advance in front of the search and moves the cell before the search
+ * reads it; hermnet_mtk_finish stands in the place of hermnet_md_finish_npt behind the force backward and the virial.  The
+ * integrator is the measure-preserving, reversible MTK splitting of Tuckerman et al. (J. Phys. A 39, 5629 (2006)):
+ *   NHC_baro NHC_particles baro-kick | scaled kick, scaled drift, cell | [forces, virial] | scaled kick | baro-kick NHC_particles
+ *   NHC_baro,  every half of length dt / 2.  `flags`: hermnet_md_advance's without HN_MD_LANGEVIN.
+ *
+ * Caller-owned state beside hermnet_nhc_advance's / _finish's (the particles' chain: the 13 arguments chain ... scale):
+ *   coupling  HN_MD_BARO_ISOTROPIC (mask must be 7) or HN_MD_BARO_AXES (mask: bit a = Cartesian axis a is coupled, not 0)
+ *   max_strain  in (0, 0.1]: the largest |v_g,a| dt of a step that is not refused
+ *   par [B,5] float64 = (w, 1 / w, 1 + 3 / dof, 1 / dof, P0) with the barostat's mass w = (dof + 3) kB T taup^2 (isotropic) or a
+ *     third of that per axis; taup = inf: w = 1 / w = 0 and the barostat never moves
+ *   dof_kt_b [B], q_b, inv_q_b [B,M]  the barostat chain's tables (dof_b = 1 or the number of coupled axes; Q_1 = dof_b kB T
+ *     taup^2, Q_j = kB T taup^2; both 0 where tau = inf or taup = inf);  xi_b, v_xi_b [B,M] that chain, scale_b [B,2] its last
+ *     opening and closing factor
+ *   v_cell [B,3]  the diagonal of the cell's rate in Cartesian axes (isotropic: three times one number)
+ *   cell64 [B,9] float64 (the truth), cell32 [B,9] float32 (its rounding: what the search reads), inv_cell [B,9] float64 (the
+ *     adjugate inverse of the widened cell32; unwritten while the cell does not move)
+ *   w_prev [B,9] float32  the virial of the last accepted evaluation (P = (sum m v v + sym W) / V)
+ *   factors [B,12]  scratch: a[3], b[3] (the kicks'), rx[3], rv[3] (the drift's) of the step
+ *   backup [B,2M+30]  xi_b, v_xi_b, v_cell, cell64, cell32 (widened), inv_cell at the start of the step
+ *   flag [B] int64  1: this step's factors were refused (|v_g,a| dt > max_strain, or a factor that is not finite) -- identity
+ *     factors are used, the cell stays, and the finish voids the step;  refused [B] int64: how often
+ *   e_code [B] float32  scratch: what the commit kernel reads as the energies (NaN where the barostat voids the step)
+ * hermnet_mtk_finish: `virial` [B,9] float32 is the step's own.  Its code is hermnet_md_finish's | HN_MD_HALT_NONFINITE where a
+ *   graph is flagged or a virial entry is not finite; void: atoms, v_cell, both chains and the three forms of the cell return,
+ *   no row.  Log row (width 7) = (energy[g], E_kin behind the closing factor, total[0], E_nhc of both chains, tr P / 3 at the
+ *   end of the step, volume, P0 V + w sum_coupled v_cell^2 / 2); columns 0 + 1 + 3 + 6 are conserved.  mode 1 (a prime): f_prev =
+ *   forces and w_prev = virial where the code is 0, nothing else.  Two launches in the advance, four in the finish, no atomics.
+ * The hermnet_host_mtk_* twins run the same text on HOST pointers (no stream), bit for bit.
+ * HN_ERR_BAD_ARG: hermnet_nhc_advance's / _finish's, dt <= 0, a coupling other than the two, a mask that is 0, has bits above 7
+ *   or is not 7 under isotropic coupling, max_strain outside (0, 0.1], a NULL pointer (batch may be NULL: one graph). */
+int hermnet_mtk_advance(int num_atoms, int num_graphs, int flags, double dt, double* x, double* v, double* x0, double* v0,
+                        int* image, int* image0, const float* f_prev, const double* kick, const long* batch, float* pos32,
+                        const long* state, const int* graph_ptr, const double* half_mass, int chain, int order, int substeps,
+                        const double* delta, const double* kt, const double* dof_kt, const double* q, const double* inv_q,
+                        double* xi, double* v_xi, double* xi0, double* v_xi0, double* scale, int coupling, int mask,
+                        double max_strain, const double* par, const double* dof_kt_b, const double* q_b, const double* inv_q_b,
+                        double* xi_b, double* v_xi_b, double* scale_b, double* v_cell, double* cell64, float* cell32,
+                        double* inv_cell, float* w_prev, double* factors, double* backup, long* flag, long* refused,
+                        float* e_code, void* stream);
+int hermnet_mtk_finish(int num_atoms, int num_graphs, const int* graph_ptr, const long* batch, const float* forces,
+                       const float* energy, const float* virial, const long* total, long capacity, double dt, double* x,
+                       double* v, const double* x0, const double* v0, int* image, const int* image0, float* f_prev,
+                       const double* kick, const double* half_mass, float* pos32, double* ke_atom, int chain, int order,
+                       int substeps, const double* delta, const double* kt, const double* dof_kt, const double* q,
+                       const double* inv_q, double* xi, double* v_xi, double* xi0, double* v_xi0, double* scale, int coupling,
+                       int mask, double max_strain, const double* par, const double* dof_kt_b, const double* q_b,
+                       const double* inv_q_b, double* xi_b, double* v_xi_b, double* scale_b, double* v_cell, double* cell64,
+                       float* cell32, double* inv_cell, float* w_prev, double* factors, double* backup, long* flag,
+                       long* refused, float* e_code, double* log, long log_steps, long* state, void* stream);
+int hermnet_host_mtk_advance(int num_atoms, int num_graphs, int flags, double dt, double* x_host, double* v_host,
+                             double* x0_host, double* v0_host, int* image_host, int* image0_host, const float* f_prev_host,
+                             const double* kick_host, const long* batch_host, float* pos32_host, const long* state_host,
+                             const int* graph_ptr_host, const double* half_mass_host, int chain, int order, int substeps,
+                             const double* delta_host, const double* kt_host, const double* dof_kt_host, const double* q_host,
+                             const double* inv_q_host, double* xi_host, double* v_xi_host, double* xi0_host,
+                             double* v_xi0_host, double* scale_host, int coupling, int mask, double max_strain,
+                             const double* par_host, const double* dof_kt_b_host, const double* q_b_host,
+                             const double* inv_q_b_host, double* xi_b_host, double* v_xi_b_host, double* scale_b_host,
+                             double* v_cell_host, double* cell64_host, float* cell32_host, double* inv_cell_host,
+                             float* w_prev_host, double* factors_host, double* backup_host, long* flag_host,
+                             long* refused_host, float* e_code_host);
+int hermnet_host_mtk_finish(int num_atoms, int num_graphs, const int* graph_ptr_host, const long* batch_host,
+                            const float* forces_host, const float* energy_host, const float* virial_host,
+                            const long* total_host, long capacity, double dt, double* x_host, double* v_host,
+                            const double* x0_host, const double* v0_host, int* image_host, const int* image0_host,
+                            float* f_prev_host, const double* kick_host, const double* half_mass_host, float* pos32_host,
+                            double* ke_atom_host, int chain, int order, int substeps, const double* delta_host,
+                            const double* kt_host, const double* dof_kt_host, const double* q_host, const double* inv_q_host,
+                            double* xi_host, double* v_xi_host, double* xi0_host, double* v_xi0_host, double* scale_host,
+                            int coupling, int mask, double max_strain, const double* par_host, const double* dof_kt_b_host,
+                            const double* q_b_host, const double* inv_q_b_host, double* xi_b_host, double* v_xi_b_host,
+                            double* scale_b_host, double* v_cell_host, double* cell64_host, float* cell32_host,
+                            double* inv_cell_host, float* w_prev_host, double* factors_host, double* backup_host,
+                            long* flag_host, long* refused_host, float* e_code_host, double* log_host, long log_steps,
+                            long* state_host);
+
 #ifdef __cplusplus
 }
 #endif
