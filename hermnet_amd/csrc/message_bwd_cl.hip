@@ -190,6 +190,9 @@ __device__ __forceinline__ float quad_total(float u, float w) {
   v += dpp_mov<0x4E>(v);    // lane ^ 2
   v += dpp_mov<0x141>(v);   // row_half_mirror
   v += dpp_mov<0x140>(v);   // row_mirror
+  // (the total is complete in every lane, here: the add is only WANTED by the lanes that store, and sunk into their
+  // branch it no longer pairs with the DPP move -- v_mov 0 + v_mov_dpp + v_add where one v_add_f32_dpp does)
+  asm volatile("" : "+v"(v));
   return v;
 }
 
@@ -199,14 +202,18 @@ __device__ __forceinline__ float quad_total(float u, float w) {
 // registers until the one wait at the top of the next edge: that wait names all twelve registers as "+v" operands, so no
 // use can be scheduled in front of it (and the generated code is checked for copies of registers in flight).
 typedef float hn_f4 __attribute__((ext_vector_type(4)));
+// All twelve rows lie within 11 KiB of the first, inside the instruction's 16-bit offset field: ROW0 names the group's
+// first tap, and the three groups of an edge share ONE address register (no v_add_u32 per group).
+template <int ROW0>
 __device__ __forceinline__ void lds_issue4(unsigned addr, hn_f4 (&w)[4]) {
+  static_assert((ROW0 + 3) * 1024 < 65536, "ds_read_b128 offsets are 16 bits");
   asm volatile(
-      "ds_read_b128 %0, %4\n\t"
-      "ds_read_b128 %1, %4 offset:1024\n\t"
-      "ds_read_b128 %2, %4 offset:2048\n\t"
-      "ds_read_b128 %3, %4 offset:3072"
+      "ds_read_b128 %0, %4 offset:%5\n\t"
+      "ds_read_b128 %1, %4 offset:%6\n\t"
+      "ds_read_b128 %2, %4 offset:%7\n\t"
+      "ds_read_b128 %3, %4 offset:%8"
       : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3])
-      : "v"(addr)
+      : "v"(addr), "n"(ROW0 * 1024), "n"((ROW0 + 1) * 1024), "n"((ROW0 + 2) * 1024), "n"((ROW0 + 3) * 1024)
       : "memory");
 }
 // everything this wave has in flight on the LDS / scalar-memory counter has landed (the edge's record and its first two
@@ -329,7 +336,11 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
   const float inv_sqrth = rsqrtf((float)H);
   const float inv_sqrt2 = 0.70710678118654752f;
   float4* gedge = a.gedge + (size_t)cb * a.E;
+  // quad_total leaves edge {0, 2, 1, 3}[k] of a group of four in DPP row k; lane g of a row stores for group g of a
+  // 64-edge batch (group_store), so this lane's edge is index lane `slot_lane` of every batch
   const int row16 = lane >> 4;                       // DPP row of this lane
+  const int slot_lane = 4 * (lane & 15) + ((row16 == 0) ? 0 : (row16 == 1 ? 2 : (row16 == 2 ? 1 : 3)));
+  const unsigned slot_bit = 1u << (slot_lane & 3);   // (WIN) this lane's edge in the group's ownership mask
   // LDS byte address of this lane's record in tap row 0 (the tile starts the dynamic region)
   const unsigned tile_lane = (unsigned)(unsigned long long)((__attribute__((address_space(3))) char*)tile) + (unsigned)lane * 16u;
 
@@ -461,9 +472,9 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
       for (int w = 0; w < 4; ++w) tl[1 + w] = rp[28 + w];
     };
     auto issue_weights = [&](unsigned waddr) {
-      lds_issue4(waddr, wA);
-      lds_issue4(waddr + 4 * (HN_CB * 16), wB);
-      lds_issue4(waddr + 8 * (HN_CB * 16), wC);
+      lds_issue4<0>(waddr, wA);
+      lds_issue4<4>(waddr, wB);
+      lds_issue4<8>(waddr, wC);
     };
     if (e_begin < e_end) {
       load_record(tl0);
@@ -481,10 +492,12 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
       const unsigned my_off = lane < cnt ? (unsigned)a.csc_tgt[base + lane] * (unsigned)(H * 4) : 0u;   // byte offset in gx1
       const int my_pos = lane < cnt ? a.csc_pos[base + lane] : 0;
 
-      auto load_edge = [&](int k) {
+      // An edge's gather offset is read out of its index lane a whole edge BEFORE the loads that take it as their scalar
+      // offset: used at once, the v_readlane's SGPR would cost the wave five idle wait states per edge (s_nop 4).
+      auto edge_offset = [&](int k) { return (unsigned)__builtin_amdgcn_readlane((int)my_off, k); };
+      auto load_edge = [&](unsigned so) {
         EdgeIn in;
         // buffer loads: descriptor + scalar row offset + this lane's channel offset -- no per-lane 64-bit address math
-        const unsigned so = (unsigned)__builtin_amdgcn_readlane((int)my_off, k);
         in.gx1 = buf_load(rs_gx1, c4, so);
         in.g0 = buf_load(rs_gvec1, c4, 3u * so);
         in.g1 = buf_load(rs_gvec1, c4, 3u * so + h4);
@@ -493,7 +506,8 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
       };
 
       // two named buffers, alternating with the parity of the (unrolled) edge slot: no register moves to rotate them
-      EdgeIn in0 = load_edge(0), in1 = in0;
+      EdgeIn in0 = load_edge(edge_offset(0)), in1 = in0;
+      unsigned so_next = edge_offset(1);                      // offset of the edge whose rows the next edge_body requests
       // per-channel Cartesian dE/dD of the current pair of edges / folded pairs (32-lane partial sums)
       float px[2], py[2], pz[2];
       float ux[2], uy[2], uz[2];
@@ -507,9 +521,10 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
           row_request(row);
         }
         // the next edge's rows fly during this edge's math
-        // (index lanes past the batch hold offset 0: a harmless extra read of row 0; only slot 3 can step past lane 63)
-        const int kn = j == 3 ? min(k + 1, 63) : k + 1;
-        if (j & 1) in0 = load_edge(kn); else in1 = load_edge(kn);
+        // (index lanes past the batch hold offset 0: a harmless extra read of row 0; edge k requests the rows of lane
+        // min(k + 1, 63) and reads out the offset of lane min(k + 2, 63): only slots 2 and 3 can step past lane 63)
+        if (j & 1) in0 = load_edge(so_next); else in1 = load_edge(so_next);
+        so_next = edge_offset(j >= 2 ? min(k + 2, 63) : k + 2);
         const EdgeIn& cur = (j & 1) ? in1 : in0;
         float (&tl)[5] = (j & 1) ? tl1 : tl0;
         // ---- (S0, S1) of the three parts: 12 taps, one LDS read each, requested during the previous edge
@@ -594,25 +609,32 @@ __device__ __forceinline__ void message_scatter_bwd_cl_body(const HnBwdClArgs& a
         const float qi = xb * rb_ * invd;
         const float tpar = fmaf(-B, qi, pdv);
         px[j & 1] = fmaf(tpar, rx, g0 * qi); py[j & 1] = fmaf(tpar, ry, g1 * qi); pz[j & 1] = fmaf(tpar, rz, g2 * qi);
+        // the edge's algebra ends HERE: left free, hipcc sinks the dE/dD half behind the next edge's `if (fresh) row_scale()`,
+        // where it still wants this row's xs / xa / xb -- every edge then pays three v_mov to keep both rows' values apart
+        asm volatile("" : "+v"(px[j & 1]), "+v"(py[j & 1]), "+v"(pz[j & 1]));
       };
       auto fold = [&](int h) {
         ux[h] = pair_fold(px[0], px[1]); uy[h] = pair_fold(py[0], py[1]); uz[h] = pair_fold(pz[0], pz[1]);
       };
       // ---- channel sums of (up to) four edges, one 16-byte store per edge (DPP row k holds edge {0,2,1,3}[k])
+      // Who stores: after quad_total all 16 lanes of a DPP row hold the same bits (every step adds a pair of lanes that
+      // already agree, and a + b = b + a), so the row's edge may leave through ANY of them.  Group g of the batch
+      // (edges 4g .. 4g + 3) leaves through lane g of each row: that lane's edge is then fixed for the whole batch --
+      // its CSR slot is fetched with one cross-lane read here, the bounds test of the stream's last, partial group is
+      // folded into its group number, and a group pays one compare for what took four v_readlane and a select tree.
+      const int my_slot = __builtin_amdgcn_ds_bpermute(slot_lane * 4, my_pos);
+      const int my_group = slot_lane < cnt ? (lane & 15) : -1;
+      float4* const my_gedge = gedge + my_slot;
       auto group_store = [&](int k4) {
         const float sx = quad_total(ux[0], ux[1]), sy = quad_total(uy[0], uy[1]), sz = quad_total(uz[0], uz[1]);
-        const int je = (row16 == 0) ? 0 : (row16 == 1 ? 2 : (row16 == 2 ? 1 : 3));
-        const int p0 = __builtin_amdgcn_readlane(my_pos, k4), p1 = __builtin_amdgcn_readlane(my_pos, min(k4 + 1, cnt - 1));
-        const int p2 = __builtin_amdgcn_readlane(my_pos, min(k4 + 2, cnt - 1)), p3 = __builtin_amdgcn_readlane(my_pos, min(k4 + 3, cnt - 1));
-        const int pw = (row16 == 0) ? p0 : (row16 == 1 ? p2 : (row16 == 2 ? p1 : p3));
-        if constexpr (WIN) {
-          if ((lane & 15) == 0 && k4 + je < cnt && ((own_mask >> je) & 1u)) gedge[pw] = make_float4(sx, sy, sz, 0.f);
-        } else {
+        bool mine = my_group == (k4 >> 2);
+        if constexpr (WIN) mine = mine && (own_mask & slot_bit) != 0u;
+        if (mine) {
 #if HN_NT_MSG
-          if ((lane & 15) == 0 && k4 + je < cnt)
-            __builtin_nontemporal_store(hn_f4{sx, sy, sz, 0.f}, reinterpret_cast<hn_f4*>(&gedge[pw]));
+          if constexpr (!WIN) __builtin_nontemporal_store(hn_f4{sx, sy, sz, 0.f}, reinterpret_cast<hn_f4*>(my_gedge));
+          else *my_gedge = make_float4(sx, sy, sz, 0.f);
 #else
-          if ((lane & 15) == 0 && k4 + je < cnt) gedge[pw] = make_float4(sx, sy, sz, 0.f);
+          *my_gedge = make_float4(sx, sy, sz, 0.f);
 #endif
         }
       };
